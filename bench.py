@@ -21,9 +21,13 @@ sharding (total work fixed: "strong" scaling), G = 1 pure frame splitting;
 `--parallelism auto` takes the largest G whose projected rate (committed per-rank
 loads, profiles/per_rank_load.json) reaches 0.75 N times the single GPU's, else the
 best G >= 2 (20 models at N = 8: 2 x 4; 200 models: 8 x 1).  Secondary measurements
-ride in the same line: `pure_model_shard` (when auto took R > 1), `replicated_frames`
+ride in the same line with --full: `pure_model_shard` (when auto took R > 1), `replicated_frames`
 (DB replicated, frames split, no collective) and `sharded_200_models` (BASELINE
 configs[3]: the 200-model DB sharded N ways).  Rank 0 prints ONE JSON line.
+
+A plain run times the headline alone; `--full` adds every other measurement of the
+line (secondary workloads and partitions, C++ hosts, h2d, roofline, CPU baseline).
+`--dump-outputs DIR` writes what the last timed step delivered to the host (N = 1).
 """
 import argparse
 import json
@@ -110,7 +114,18 @@ def parse(argv=None):
                          "exits with an error instead of hanging (default: 900 for N > 1, off for N = 1; 0 = off)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what rides beside the headline: the C++ hosts, the descriptors from pinned host memory, "
+                         "the roofline and POSE figures, the secondary workloads and partitions, the CPU baseline (each can "
+                         "still be left out by its own --no-* option or --h2d-steps 0).  Without it a run times the headline "
+                         "alone")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="N = 1: write what the last timed step delivered to the host, frame by frame, as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if not args.full:
+        args.no_secondary = args.no_cpu_baseline = args.no_roofline = True
+        args.h2d_steps = 0
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -459,6 +474,8 @@ class Job:
         self.pipe.attach_delivery(DELIVER_CAP, max(B, 1))
         self.slot_pending = {}           # slot -> pool indices of the frames of the delivery in flight (None: not counted)
         self.slot_last = {}              # sharded: slot -> pool indices of the batch whose objects ride on the slot's NEXT exchange
+        self.slot_tag = {}               # slot -> tag of the delivery in flight (single GPU)
+        self.capture = None              # --dump-outputs: the records of one timed step (start_capture)
         self.load_frames(args.n_vis)
 
     def load_frames(self, n_vis):
@@ -538,6 +555,12 @@ class Job:
         recs = self.pipe.take_delivery(slot)    # waits for the delivery's event only; raises on capacity / exchange flags
         if recs is None:
             return
+        tag = self.slot_tag.pop(slot, None)
+        cap = self.capture
+        if cap is not None and tag is not None and cap["tags"][0] <= tag < cap["tags"][1]:
+            k = (tag - cap["tags"][0]) * len(recs)
+            cap["records"][k:k + len(recs)] = recs
+            cap["frames"] += len(recs)
         first = self.slot_pending.pop(slot, None)
         if first is None or not count:
             return
@@ -554,6 +577,15 @@ class Job:
             self.slot_last[slot] = first
         else:
             self.slot_pending[slot] = first
+            self.slot_tag[slot] = tag
+
+    def start_capture(self, step):
+        """Keep the delivery records of step `step` (single GPU): record i = the step's i-th frame.  A step's deliveries
+        carry tags step * per_step .. (step + 1) * per_step - 1, one per batch (one per frame without batches)."""
+        from moped_amd import capi
+        per_step = self.groups if self.B > 1 else self.n_frames
+        self.capture = {"tags": (step * per_step, (step + 1) * per_step), "frames": 0,
+                        "records": np.zeros(self.n_frames, capi.frame_block_dtype(DELIVER_CAP))}
 
     def drain(self, count=True):
         """Every delivery in flight reaches the host; with a sharded DB the slots' last batches too (exchange 2 on its own:
@@ -704,6 +736,32 @@ class Job:
         self.pipe.close()
 
 
+DUMP_MAX_FRAMES = 32768   # ~1.6 kB per frame written: at most ~52 MB
+
+
+def dump_outputs(dirname, records):
+    """--dump-outputs: the timed path's results as its caller receives them, one row per frame of the step in the order the
+    frames were enqueued (a step of more than DUMP_MAX_FRAMES frames: a fixed, seeded sample of its frames, `frame_index`
+    says which).  Object slots past a frame's n_objects hold model -1 and zeros (the pinned block keeps stale records there)."""
+    os.makedirs(dirname, exist_ok=True)
+    rows = np.arange(len(records))
+    if len(rows) > DUMP_MAX_FRAMES:
+        rows = np.sort(np.random.default_rng(0).choice(len(rows), DUMP_MAX_FRAMES, replace=False))
+    head, obj = records["head"][rows], records["objects"][rows]
+    valid = np.arange(DELIVER_CAP)[None, :] < np.minimum(head["n_objects"], DELIVER_CAP)[:, None]
+    arrays = {
+        "frame_index": rows.astype(np.float64),
+        "n_objects": head["n_objects"].astype(np.float64),
+        "counts": head["counts"].astype(np.float64),      # accepted matches, clusters, objects after POSE, after FILTER
+        "object_model": np.where(valid, obj["model"], -1).astype(np.float64),
+        "object_pose": np.where(valid[..., None], obj["pose"], 0).astype(np.float32),
+        "object_score": np.where(valid, obj["score"], 0).astype(np.float32),
+        "object_n_points": np.where(valid, obj["n_points"], 0).astype(np.float64),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def measure_pose(job, out_cfg):
     """occupancy and hypotheses/s of the RANSAC kernel, next to every GPU figure.  Live: one isolated
     batch on slot 0 with the library's stage timing (HIP events on the launching stream around every stage)."""
@@ -740,6 +798,8 @@ def measure_pose(job, out_cfg):
 
 def main():
     args = parse()
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.force_exchange or args.steps < 1):
+        raise SystemExit("bench.py: --dump-outputs needs one GPU, no --force-exchange and --steps >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args))     # nothing above or inside touched the GPU
     rank = int(os.environ.get("RANK", "0"))
@@ -807,7 +867,14 @@ def main():
     if B > 1 and not depth_given and args.depth == 16:
         job.calibrate_slots()
     arm_watchdog(wd + 2 * args.steps if wd > 0 else 0)   # (wd = 0 is "off", not "2 s per step": the N = 1 default)
+    if args.dump_outputs:
+        job.start_capture(args.steps - 1)
     dt, t_issue = job.timed(args.steps, args.warmup)
+    if args.dump_outputs:
+        cap, job.capture = job.capture, None
+        if cap["frames"] != job.n_frames:
+            raise SystemExit(f"bench.py: the last timed step delivered {cap['frames']} of its {job.n_frames} frames")
+        dump_outputs(args.dump_outputs, cap["records"])
     fps = job.total_frames(args.steps) / dt    # every one of these frames' objects reached the host inside dt (checked below)
     det_per_frame = job.detections_per_frame()
     delivered = job.detections_detail

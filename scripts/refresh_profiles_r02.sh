@@ -8,16 +8,16 @@ parts=${*:-bench prof traffic ranks sift}
 cd $root
 has() { [[ " $parts " == *" $1 "* ]]; }
 if has bench; then
-  timeout -k 10 500 python bench.py > $out/r02_bench_20models.json 2>$out/bench20.err || { tail -3 $out/bench20.err; exit 1; }
+  timeout -k 10 500 python bench.py --full > $out/r02_bench_20models.json 2>$out/bench20.err || { tail -3 $out/bench20.err; exit 1; }
   echo "bench 20 done"
-  timeout -k 10 500 python bench.py --no-adaptive --no-cpu-baseline > $out/r02_bench_20models_no_adaptive.json 2>>$out/bench20.err || exit 1
-  MH_MATCH_SCREEN=0 timeout -k 10 500 python bench.py --no-cpu-baseline --frames-per-step 256 > $out/r02_bench_20models_exact_f32_match.json 2>>$out/bench20.err || exit 1
+  timeout -k 10 500 python bench.py --full --no-adaptive --no-cpu-baseline > $out/r02_bench_20models_no_adaptive.json 2>>$out/bench20.err || exit 1
+  MH_MATCH_SCREEN=0 timeout -k 10 500 python bench.py --full --no-cpu-baseline --frames-per-step 256 > $out/r02_bench_20models_exact_f32_match.json 2>>$out/bench20.err || exit 1
   echo "bench 20 variants done"
-  timeout -k 10 600 python bench.py --models 200 --frames-per-step 256 --steps 10 --warmup 2 > $out/r02_bench_200models.json 2>$out/bench200.err || { tail -3 $out/bench200.err; exit 1; }
+  timeout -k 10 600 python bench.py --full --models 200 --frames-per-step 256 --steps 10 --warmup 2 > $out/r02_bench_200models.json 2>$out/bench200.err || { tail -3 $out/bench200.err; exit 1; }
   echo "bench 200 done"
-  timeout -k 10 500 python bench.py --models 50 --depth-kind 1 --frames-per-step 512 > $out/r02_bench_50models_depth.json 2>$out/bench50.err || { tail -3 $out/bench50.err; exit 1; }
-  timeout -k 10 500 python bench.py --models 50 --depth-kind 1 --moped3d-frontend --frames-per-step 512 --no-cpu-baseline > $out/r02_bench_50models_moped3d_frontend.json 2>$out/bench50f.err || { tail -3 $out/bench50f.err; exit 1; }
-  timeout -k 10 500 python bench.py --models 50 --depth-kind 1 --moped3d-frontend --depthfill --frames-per-step 512 --no-cpu-baseline > $out/r02_bench_50models_moped3d_frontend_depthfill.json 2>$out/bench50d.err || { tail -3 $out/bench50d.err; exit 1; }
+  timeout -k 10 500 python bench.py --full --models 50 --depth-kind 1 --frames-per-step 512 > $out/r02_bench_50models_depth.json 2>$out/bench50.err || { tail -3 $out/bench50.err; exit 1; }
+  timeout -k 10 500 python bench.py --full --models 50 --depth-kind 1 --moped3d-frontend --frames-per-step 512 --no-cpu-baseline > $out/r02_bench_50models_moped3d_frontend.json 2>$out/bench50f.err || { tail -3 $out/bench50f.err; exit 1; }
+  timeout -k 10 500 python bench.py --full --models 50 --depth-kind 1 --moped3d-frontend --depthfill --frames-per-step 512 --no-cpu-baseline > $out/r02_bench_50models_moped3d_frontend_depthfill.json 2>$out/bench50d.err || { tail -3 $out/bench50d.err; exit 1; }
   echo "bench 50 done"
 fi
 if has prof; then
@@ -26,12 +26,12 @@ if has prof; then
   for d in default 1; do
     a=""; [ $d = 1 ] && a="--depth 1 --frames-per-step 128"
     rm -rf /tmp/rp_$d
-    timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_$d -- python3 $root/bench.py --no-cpu-baseline --h2d-steps 0 $a > $out/r02_bench_20models_depth${d}_under_rocprof.json 2>/tmp/rp_$d.err || { tail -3 /tmp/rp_$d.err; exit 1; }
+    timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_$d -- python3 $root/bench.py --full --no-cpu-baseline --h2d-steps 0 $a > $out/r02_bench_20models_depth${d}_under_rocprof.json 2>/tmp/rp_$d.err || { tail -3 /tmp/rp_$d.err; exit 1; }
     cp $(find /tmp/rp_$d -name "*kernel_stats.csv" | head -1) $out/r02_bench_20models_depth${d}_kernel_stats.csv
     echo "rocprof depth $d done"
   done
   rm -rf /tmp/rp_200
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_200 -- python3 $root/bench.py --models 200 --depth 1 --frames-per-step 32 --steps 4 --warmup 1 --no-cpu-baseline --h2d-steps 0 > $out/r02_bench_200models_depth1_under_rocprof.json 2>/tmp/rp_200.err || { tail -3 /tmp/rp_200.err; exit 1; }
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_200 -- python3 $root/bench.py --full --models 200 --depth 1 --frames-per-step 32 --steps 4 --warmup 1 --no-cpu-baseline --h2d-steps 0 > $out/r02_bench_200models_depth1_under_rocprof.json 2>/tmp/rp_200.err || { tail -3 /tmp/rp_200.err; exit 1; }
   cp $(find /tmp/rp_200 -name "*kernel_stats.csv" | head -1) $out/r02_bench_200models_depth1_kernel_stats.csv
   cd $root
 fi
@@ -73,9 +73,9 @@ fi
 if has ranks; then
   # one GPU carrying what each rank carries at N = 8 / 4 / 2 (a DB of 20/N resp. 200/N models behind the exchange path)
   { for a in "--models 3 --force-exchange" "--models 5 --force-exchange" "--models 10 --force-exchange" "--models 3 --force-exchange --batch 1"; do
-      echo "bench.py $a"; timeout -k 10 400 python bench.py $a --no-cpu-baseline --no-roofline 2>/dev/null | tail -1; done; } > $out/r02_per_rank_load_n8.txt 2>&1
+      echo "bench.py --full $a"; timeout -k 10 400 python bench.py $a --no-cpu-baseline --no-roofline 2>/dev/null | tail -1; done; } > $out/r02_per_rank_load_n8.txt 2>&1
   { for a in "--models 100 --frames-per-step 256 --steps 10" "--models 50 --frames-per-step 512" "--models 25"; do
-      echo "bench.py $a --force-exchange"; timeout -k 10 500 python bench.py $a --force-exchange --no-cpu-baseline --no-roofline 2>/dev/null | tail -1; done; } > $out/r02_per_rank_load_200models.txt 2>&1
+      echo "bench.py --full $a --force-exchange"; timeout -k 10 500 python bench.py $a --force-exchange --no-cpu-baseline --no-roofline 2>/dev/null | tail -1; done; } > $out/r02_per_rank_load_200models.txt 2>&1
 fi
 if has sift; then
   # FEAT and the image -> objects path on the reference's bundled frames

@@ -9,13 +9,13 @@ cd $root
 has() { [[ " $parts " == *" $1 "* ]]; }
 line() { grep "^{" | tail -1; }
 if has bench; then
-  timeout -k 10 600 python bench.py 2>$out/bench20.err | line > $out/r04_bench_20models.json || { tail -3 $out/bench20.err; exit 1; }
+  timeout -k 10 600 python bench.py --full 2>$out/bench20.err | line > $out/r04_bench_20models.json || { tail -3 $out/bench20.err; exit 1; }
   echo "bench 20 done"
-  timeout -k 10 600 python bench.py --models 200 --frames-per-step 256 --steps 10 --warmup 2 --no-secondary 2>$out/bench200.err | line > $out/r04_bench_200models.json || { tail -3 $out/bench200.err; exit 1; }
+  timeout -k 10 600 python bench.py --full --models 200 --frames-per-step 256 --steps 10 --warmup 2 --no-secondary 2>$out/bench200.err | line > $out/r04_bench_200models.json || { tail -3 $out/bench200.err; exit 1; }
   echo "bench 200 done"
-  timeout -k 10 500 python bench.py --models 50 --depth-kind 1 --frames-per-step 512 2>$out/bench50.err | line > $out/r04_bench_50models_depth.json || { tail -3 $out/bench50.err; exit 1; }
-  timeout -k 10 500 python bench.py --models 50 --depth-kind 1 --moped3d-frontend --frames-per-step 512 --no-cpu-baseline 2>$out/bench50f.err | line > $out/r04_bench_50models_moped3d_frontend.json || { tail -3 $out/bench50f.err; exit 1; }
-  timeout -k 10 500 python bench.py --models 50 --depth-kind 1 --moped3d-frontend --depthfill --frames-per-step 512 --no-cpu-baseline 2>$out/bench50d.err | line > $out/r04_bench_50models_moped3d_frontend_depthfill.json || { tail -3 $out/bench50d.err; exit 1; }
+  timeout -k 10 500 python bench.py --full --models 50 --depth-kind 1 --frames-per-step 512 2>$out/bench50.err | line > $out/r04_bench_50models_depth.json || { tail -3 $out/bench50.err; exit 1; }
+  timeout -k 10 500 python bench.py --full --models 50 --depth-kind 1 --moped3d-frontend --frames-per-step 512 --no-cpu-baseline 2>$out/bench50f.err | line > $out/r04_bench_50models_moped3d_frontend.json || { tail -3 $out/bench50f.err; exit 1; }
+  timeout -k 10 500 python bench.py --full --models 50 --depth-kind 1 --moped3d-frontend --depthfill --frames-per-step 512 --no-cpu-baseline 2>$out/bench50d.err | line > $out/r04_bench_50models_moped3d_frontend_depthfill.json || { tail -3 $out/bench50d.err; exit 1; }
   echo "bench 50 done"
 fi
 if has prof; then
@@ -24,12 +24,12 @@ if has prof; then
   for d in default 1; do
     a=""; [ $d = 1 ] && a="--depth 1 --frames-per-step 128"
     rm -rf /tmp/rp_$d
-    timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_$d -- python3 $root/bench.py --no-cpu-baseline --no-secondary --h2d-steps 0 $a 2>/tmp/rp_$d.err | line > $out/r04_bench_20models_depth${d}_under_rocprof.json || { tail -3 /tmp/rp_$d.err; exit 1; }
+    timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_$d -- python3 $root/bench.py --full --no-cpu-baseline --no-secondary --h2d-steps 0 $a 2>/tmp/rp_$d.err | line > $out/r04_bench_20models_depth${d}_under_rocprof.json || { tail -3 /tmp/rp_$d.err; exit 1; }
     cp $(grep -l screen $(find /tmp/rp_$d -name "*kernel_stats.csv") | head -1) $out/r04_bench_20models_depth${d}_kernel_stats.csv   # (the bench's own process: rocprofv3 also writes a file for the mfma_rate child)
     echo "rocprof depth $d done"
   done
   rm -rf /tmp/rp_200
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_200 -- python3 $root/bench.py --models 200 --depth 1 --frames-per-step 32 --steps 4 --warmup 1 --no-cpu-baseline --no-secondary --h2d-steps 0 2>/tmp/rp_200.err | line > $out/r04_bench_200models_depth1_under_rocprof.json || { tail -3 /tmp/rp_200.err; exit 1; }
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_200 -- python3 $root/bench.py --full --models 200 --depth 1 --frames-per-step 32 --steps 4 --warmup 1 --no-cpu-baseline --no-secondary --h2d-steps 0 2>/tmp/rp_200.err | line > $out/r04_bench_200models_depth1_under_rocprof.json || { tail -3 /tmp/rp_200.err; exit 1; }
   cp $(grep -l screen $(find /tmp/rp_200 -name "*kernel_stats.csv") | head -1) $out/r04_bench_200models_depth1_kernel_stats.csv
   cd $root
 fi

@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -85,3 +87,66 @@ def test_default_batch_follows_the_partition():
     assert b.default_batch(a, False) == 16                 # depth attributes travel with a merged batch (round 4)
     a = b.parse(["--depth-kind", "1", "--moped3d-frontend"])
     assert b.default_batch(a, False) == 16                 # a depth map per frame travels with a merged batch too (round 4)
+
+
+def test_a_plain_run_times_the_headline_alone_and_full_keeps_every_leg():
+    b = _bench()
+    a = b.parse(["--steps", "7", "--warmup", "2"])
+    assert not a.full and a.steps == 7 and a.warmup == 2
+    assert a.no_secondary and a.no_cpu_baseline and a.no_roofline and a.h2d_steps == 0
+    a = b.parse(["--full"])
+    assert not (a.no_secondary or a.no_cpu_baseline or a.no_roofline) and a.h2d_steps == 3
+    a = b.parse(["--full", "--no-roofline", "--h2d-steps", "0"])     # each leg can still be left out on its own
+    assert a.no_roofline and a.h2d_steps == 0 and not a.no_secondary and not a.no_cpu_baseline
+
+
+def _records(n):
+    from moped_amd import capi
+    r = np.zeros(n, capi.frame_block_dtype(32))
+    rng = np.random.default_rng(5)
+    r["head"]["n_objects"] = np.arange(n) % 4
+    r["head"]["n_objects"][0] = 40                                # more than a record carries: all 32 slots are valid
+    r["head"]["counts"] = rng.integers(0, 3000, (n, 4))
+    r["objects"]["model"] = rng.integers(0, 20, (n, 32))            # stale values beyond n_objects too
+    r["objects"]["pose"] = rng.standard_normal((n, 32, 7))
+    r["objects"]["score"] = rng.random((n, 32))
+    r["objects"]["n_points"] = rng.integers(7, 300, (n, 32))
+    return r
+
+
+def test_dump_outputs_writes_every_frame_in_order_and_masks_the_slots_past_n_objects(tmp_path):
+    b = _bench()
+    r = _records(48)
+    b.dump_outputs(str(tmp_path / "out"), r)
+    got = {f[:-4]: np.load(str(tmp_path / "out" / f)) for f in os.listdir(str(tmp_path / "out"))}
+    assert set(got) == {"frame_index", "n_objects", "counts", "object_model", "object_pose", "object_score", "object_n_points"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["frame_index"], np.arange(48)) and np.array_equal(got["n_objects"], r["head"]["n_objects"])
+    assert np.array_equal(got["counts"], r["head"]["counts"])
+    n = np.minimum(r["head"]["n_objects"], 32)
+    for f in range(48):
+        k = n[f]
+        assert np.array_equal(got["object_model"][f, :k], r["objects"]["model"][f, :k]) and (got["object_model"][f, k:] == -1).all()
+        assert np.array_equal(got["object_pose"][f, :k], r["objects"]["pose"][f, :k]) and (got["object_pose"][f, k:] == 0).all()
+        assert np.array_equal(got["object_score"][f, :k], r["objects"]["score"][f, :k]) and (got["object_score"][f, k:] == 0).all()
+        assert np.array_equal(got["object_n_points"][f, :k], r["objects"]["n_points"][f, :k])
+
+
+def test_dump_outputs_of_a_large_step_is_a_fixed_sample_within_64_mb(tmp_path):
+    b = _bench()
+    r = _records(b.DUMP_MAX_FRAMES + 1000)
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), r)
+    size = sum(os.path.getsize(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a")))
+    assert size <= 64 * 2 ** 20
+    ia, ib = np.load(str(tmp_path / "a" / "frame_index.npy")), np.load(str(tmp_path / "b" / "frame_index.npy"))
+    assert len(ia) == b.DUMP_MAX_FRAMES and np.array_equal(ia, ib) and (np.diff(ia) > 0).all()
+    assert np.array_equal(np.load(str(tmp_path / "a" / "n_objects.npy")), r["head"]["n_objects"][ia.astype(np.int64)])
+
+
+def test_dump_outputs_is_refused_where_it_would_not_be_the_single_gpu_path():
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MH_BENCH_REHEARSE")}
+    for extra in (["--gpus", "2"], ["--force-exchange"], ["--steps", "0"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs", "unused"] + extra,
+                           capture_output=True, text=True, env=env, timeout=300, cwd=ROOT)
+        assert r.returncode != 0 and "--dump-outputs" in r.stderr and not os.path.exists(os.path.join(ROOT, "unused"))

@@ -18,7 +18,7 @@ def _run(extra, launcher=False, port=0, gpus=2, roofline=False):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["MH_BENCH_REHEARSE"] = "1"
     # --watchdog: a rank that waits for a collective the others never issue ends with its stack, not with the suite's timeout
-    tail = [os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    tail = [os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
             "--h2d-steps", "0", "--watchdog", "300"] + ([] if roofline else ["--no-roofline"]) + extra
     if launcher:   # the way the driver starts N > 1
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(gpus), "--master-addr",
