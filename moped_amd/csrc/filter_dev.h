@@ -25,8 +25,10 @@ struct FilterLds {
   DevCam cams_s[MH_MAX_IMAGES];   // several images: every match is projected through its own image's camera
   int model_s[FL_SLOTS], b_s[FL_SLOTS], n_s[FL_SLOTS], cl_s[FL_SLOTS];   // n_s < 0: the slot holds no object
   float score_s[FL_SLOTS];
-  int vlist_s[FL_SLOTS];        // the slots (below FL_SLOTS) that hold an object, in no particular order: cnt_s of them
+  int vlist_s[FL_SLOTS];        // the slots (below FL_SLOTS) that hold an object, ascending: cnt_s of them
+  int wcnt_s[FT / 64];          // (how many of them each wavefront's 64 slots hold)
 };
+static_assert(FT == FL_SLOTS, "filter_load_slots: one slot per thread");
 
 __device__ __forceinline__ void filter_wave_sync() {   // LDS written by lanes of this wavefront, read by others of it
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -37,18 +39,19 @@ __device__ __forceinline__ void filter_wave_sync() {   // LDS written by lanes o
 // The slots' model, list and (with_scores) score into LDS: one round trip for all of them instead of a chain of four
 // dependent loads per slot inside the loops below (all threads; ends with a barrier).
 // An object holds one of four replicas' slots of a cluster at most times: the loops below walk the LIST of slots with an
-// object (vlist_s), not the slots.
+// object (vlist_s), not the slots.  The list is in slot order, the same in every workgroup: filter_score's grid stride
+// splits ONE list among the workgroups (a list in the order of LDS atomics differs from workgroup to workgroup once
+// more than one wavefront adds to it -- more than 64 slots -- and some objects were scored twice, others never).
 __device__ __forceinline__ void filter_load_slots(FilterLds& S, const FilterBuffers& fb, int n_slots, bool with_scores) {
-  if (threadIdx.x == 0) S.cnt_s = 0;
-  __syncthreads();
-  for (int o = threadIdx.x; o < n_slots && o < FL_SLOTS; o += FT) {
-    const bool v = fb.obj_valid[o] != 0;
+  const int o = threadIdx.x, lane = o & 63, wave = o >> 6;   // slot o < FL_SLOTS == FT
+  const bool in = o < n_slots;
+  const bool v = in && fb.obj_valid[o] != 0;
+  if (in) {
     const int m = v ? fb.obj_model[o] : 0;
     const int b = fb.model_off[m];
     S.model_s[o] = m;
     S.b_s[o] = b;
     S.n_s[o] = v ? fb.model_off[m + 1] - b : -1;
-    if (v) S.vlist_s[atomicAdd(&S.cnt_s, 1)] = o;
     if (with_scores) {
       S.score_s[o] = v ? fb.obj_score[o] : 0.f;
       if (!v) {   // F2's answer for a slot without an object
@@ -57,6 +60,13 @@ __device__ __forceinline__ void filter_load_slots(FilterLds& S, const FilterBuff
       }
     }
   }
+  const unsigned long long bal = __ballot(v);
+  if (lane == 0) S.wcnt_s[wave] = __popcll(bal);
+  __syncthreads();
+  int before = 0;
+  for (int w = 0; w < wave; ++w) before += S.wcnt_s[w];
+  if (v) S.vlist_s[before + __popcll(bal & ((1ull << lane) - 1ull))] = o;
+  if (o == FT - 1) S.cnt_s = before + S.wcnt_s[wave];
   __syncthreads();
 }
 // (slot o's list: from LDS, or -- slots past FL_SLOTS -- from the arrays)

@@ -3,6 +3,7 @@ FILTER2 through mh_frame_enqueue vs the CPU oracle pipeline on the same frames."
 import numpy as np
 import pytest
 
+import filter_cases
 import orclib
 from moped_amd import capi, synth
 
@@ -68,6 +69,9 @@ def test_frame_matches_oracle_pipeline(world, seed, n_vis):
         assert abs(g["score"] - sc) <= 0.05 * sc    # FILTER2 score of the same object, same points
         j = list(fr.visible).index(m)
         assert np.allclose(g["pose"][4:], fr.poses[j][4:], atol=3e-3)
+    out_q, off = orclib.match_accept(idx, d1, d2, 0.8, db.model_of, db.n_models)   # FILTER2 of each object alone: exact
+    filter_cases.assert_delivered_scores(objs, fr.uv[out_q], db.xyz[idx[out_q]], off,
+                                         capi.default_frame_params().f2_feature_distance)
 
 
 def test_frame_no_objects_on_clutter(world):
@@ -203,6 +207,9 @@ def test_frame_with_more_object_slots_than_filter_keeps_in_lds():
     for m, sc in zip(om, osc):
         g = objs[objs["model"] == m][0]
         assert abs(g["score"] - sc) <= 0.05 * sc, (m, g["score"], sc)
+    out_q, off = orclib.match_accept(idx, d1, d2, 0.8, db.model_of, db.n_models)   # FILTER2 of each object alone: exact
+    filter_cases.assert_delivered_scores(objs, fr.uv[out_q], db.xyz[idx[out_q]], off,
+                                         capi.default_frame_params().f2_feature_distance)
 
 
 @pytest.mark.parametrize("seed", [0, 1, 3, 4])

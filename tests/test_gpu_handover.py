@@ -5,6 +5,7 @@ and seeds; the intermediate lists equal the upload-path entry points' and the or
 import numpy as np
 import pytest
 
+import filter_cases
 import orclib
 from moped_amd import capi, synth
 
@@ -22,9 +23,9 @@ def world():
     c.close()
 
 
-def _stepped(c, fr, prm, seed):
+def _stepped(c, fr, prm, seed, uv=None, K=K):
     desc = fr.desc.copy()
-    off, mq, pts = c.step_match(desc, fr.uv, K, CAM0, prm.ratio)
+    off, mq, pts = c.step_match(desc, fr.uv if uv is None else uv, K, CAM0, prm.ratio)
     cm, co, mem = c.step_cluster(prm.ms_radius, prm.ms_merge, prm.ms_min_pts, prm.ms_max_iter)
     o1 = c.step_pose(1, prm.pose1, seed)
     f1 = c.step_filter(1, prm.f1_min_points, prm.f1_feature_distance, prm.f1_min_score, len(o1))
@@ -35,6 +36,27 @@ def _stepped(c, fr, prm, seed):
     return dict(desc=desc, off=off, mq=mq, pts=pts, cm=cm, co=co, mem=mem, o1=o1, f1=f1, o2=o2, lst=lst, f2=f2)
 
 
+def _assert_filters_are_the_oracles(r, prm, K=K):
+    """FILTER on (pts, off, o1) and FILTER2 on (pts, off, lst): what mh_step_filter returned is orclib.filter_projection
+    on exactly those arrays, bit for bit -- every score, keep flag, the out order and every rewritten cluster."""
+    p = r["pts"]
+    uv, xyz = np.stack([p["u"], p["v"]], 1), np.stack([p["x"], p["y"], p["z"]], 1)
+    for which, objs, f, (mp, fd, ms) in ((1, r["o1"], r["f1"], (prm.f1_min_points, prm.f1_feature_distance, prm.f1_min_score)),
+                                         (2, r["lst"], r["f2"], (prm.f2_min_points, prm.f2_feature_distance, prm.f2_min_score))):
+        score, keep, order, co, mem = f
+        w_score, w_keep, w_order, w_clusters = orclib.filter_projection(
+            uv, xyz, r["off"], np.ascontiguousarray(objs["model"]), np.ascontiguousarray(objs["pose"]), K, CAM0, mp, fd, ms)
+        # the survivors in LIST order: the reference erases from frameData.objects in place (FILTER_PROJECTION_CPU.hpp:
+        # 150-160); the oracle reports them model by model (its cluster table).  FILTER2's list (FILTER's survivors, then
+        # POSE2's objects) is not sorted by model.
+        by_obj = dict(zip(w_order.tolist(), w_clusters))
+        want = (w_score, w_keep, np.sort(w_order), [by_obj[o] for o in np.sort(w_order).tolist()])
+        filter_cases.same((score, keep.astype(bool), order, [mem[co[k]:co[k + 1]] for k in range(len(order))]), want,
+                          f"FILTER{which}")
+        if which == 1:   # POSE's objects come sorted by model: the two orders are one
+            assert np.array_equal(order, w_order)
+
+
 @pytest.mark.parametrize("seed,n_vis", [(0, 2), (1, 5), (2, 0), (3, 10)])
 def test_six_step_calls_equal_the_frame_as_one_call(world, seed, n_vis):
     db, c = world
@@ -43,6 +65,7 @@ def test_six_step_calls_equal_the_frame_as_one_call(world, seed, n_vis):
     want_desc = fr.desc.copy()
     want, wc = c.frame_run_host(want_desc, fr.uv, [K], [CAM0], prm, seed=seed + 40)
     r = _stepped(c, fr, prm, seed + 40)
+    _assert_filters_are_the_oracles(r, prm)
     # MATCH: the descriptors normalised in place (MATCH_ANN_CPU.hpp:157), matches[m] in ascending query order
     assert np.array_equal(r["desc"].view(np.uint32), want_desc.view(np.uint32))
     idx, d1, d2 = orclib.match_2nn(orclib.normalize(db.desc), orclib.normalize(fr.desc))
@@ -105,6 +128,7 @@ def test_a_call_out_of_order_or_after_another_use_of_the_frame_arrays_is_refused
     # ... and the next stepped frame is fine again
     r = _stepped(c, fr, prm, 9)
     assert len(r["f2"][2]) >= 2
+    _assert_filters_are_the_oracles(r, prm)
 
 
 def test_match_fetch_into_buffers_that_are_too_small_says_so_and_can_be_repeated(world):
@@ -127,3 +151,32 @@ def test_match_fetch_into_buffers_that_are_too_small_says_so_and_can_be_repeated
     assert rc == 0 and np.array_equal(mq2[:4], mq) and off[-1] == n.value
     cm, co, mem = c.step_cluster()                                                    # the resident frame went on being valid
     assert len(cm) >= 2
+
+
+@pytest.mark.parametrize("name", ["duplicates", "duplicates_big", "slots", "pose2_none"])
+def test_stepped_filters_equal_the_oracle_on_their_own_objects(name):
+    """Held-out frames (tests/filter_cases.py: frame_scene): keypoints of two visible objects at one coordinate, one
+    pair as (0.0, y) / (-0.0, y) -- group_kernel's representatives, by its LDS hash and past 2 048 accepted matches;
+    more than 256 object slots after POSE; a frame where POSE2 finds nothing.  Both FILTERs equal the oracle's on the
+    step's own lists and objects."""
+    db, fr, uv, Kx = filter_cases.frame_scene(name)
+    prm = capi.default_frame_params()
+    c = capi.Context(0)
+    try:
+        c.db_upload(c.normalize(db.desc), db.model_of, db.xyz, db.n_models)
+        c.reserve(len(fr.desc))
+        r = _stepped(c, fr, prm, 17, uv=uv, K=Kx)
+    finally:
+        c.close()
+    p = r["pts"]
+    assert np.array_equal(np.stack([p["u"], p["v"]], 1).view(np.uint32), uv[r["mq"]].view(np.uint32))
+    _assert_filters_are_the_oracles(r, prm, Kx)
+    if name == "duplicates_big":
+        assert r["off"][-1] > 2048
+    if name == "slots":
+        assert len(r["o1"]) > 256
+    if name == "pose2_none":
+        assert len(r["o2"]) == 0 and len(r["f2"][2]) >= 1
+    if name.startswith("duplicates"):   # the (0.0, y) / (-0.0, y) pair is among the matches
+        z = np.nonzero(p["u"] == 0)[0]
+        assert np.signbit(p["u"][z]).any() and (~np.signbit(p["u"][z])).any()

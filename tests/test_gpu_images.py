@@ -6,6 +6,7 @@ frame (mh_frame_set_images)."""
 import numpy as np
 import pytest
 
+import filter_cases
 import orclib
 from moped_amd import capi, synth
 
@@ -117,6 +118,8 @@ def test_frame_with_two_cameras_matches_oracle(scene):
         assert e_g <= e_o + 1.0 and e_g < 1.0
         assert np.linalg.norm(g["pose"][4:] - fr.poses[j][4:]) < 0.005
         assert abs(g["score"] - sc) <= 0.05 * sc               # FILTER2's score over BOTH images' matches
+    filter_cases.assert_delivered_scores(objs, s["uv"], s["xyz"], s["off"], capi.default_frame_params().f2_feature_distance,
+                                         fr.Ks, fr.cams, s["img"])   # FILTER2 of each object alone: exact
     # one image again: the plain frame (image 1's keypoints now read as image 0's: different clusters)
     c.frame_set_images(0)
     pipe.enqueue(0, torch.from_numpy(fr.desc).to(dev), torch.from_numpy(fr.uv).to(dev), seed=9)

@@ -17,8 +17,9 @@ import sys
 import numpy as np
 import pytest
 
+import filter_cases
 import orclib
-from moped_amd import synth
+from moped_amd import capi, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
@@ -61,6 +62,9 @@ def test_device_on_the_fixture_scenes(s):
     pipe.close()
     assert counts[0] == oc[0] and counts[1] == oc[1]          # matches and clusters: index-exact stages
     out_q, off = orclib.match_accept(idx, d1, d2, 0.8, db.model_of, db.n_models)
+    # FILTER2 of each delivered object alone, at the device's pose, over its model's matches: the device's score exactly
+    filter_cases.assert_delivered_scores(objs, fr.uv[out_q], db.xyz[idx[out_q]], off,
+                                         capi.default_frame_params().f2_feature_distance)
 
     def planted_e2(m, pose=None):
         q = out_q[off[m]:off[m + 1]]

@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import filter_cases
 import orclib
 from moped_amd import synth
 from witness import witness
@@ -221,3 +222,23 @@ def test_filter_oracle_equals_the_map_free_witness(block):
         erased_total += len(keep) - int(keep.sum())
         shared += len(uv) > len(np.unique(uv, axis=0))
     assert kept_total > 500 and erased_total > 500 and shared > 300
+
+
+@pytest.mark.parametrize("block", range(2))
+def test_filter_oracle_equals_the_witness_at_the_device_sizes(block):
+    """The oracle the GPU's FILTER is held to (test_gpu_filter.py), checked where the GPU is tested: more than 256
+    objects, models of more than 2 048 matches, equal scores across slot 256 of the sorted list, (0.0, y) against
+    (-0.0, y) -- one key of the reference's map, as std::pair<float, float> compares them."""
+    rng = np.random.default_rng([0xF17E, block])
+    reached = filter_cases.Regimes()
+    for case in range(60):
+        c = filter_cases.make_case(rng, work=60_000)
+        score, keep, order, clusters = res = filter_cases.oracle(c)
+        w_score, w_keep, w_order, w_clusters = witness.filter_projection(c["uv"], c["model_off"], c["obj_model"],
+                                                                         lambda o: filter_cases.err2(c, o), c["min_points"],
+                                                                         c["fd"], c["min_score"])
+        assert np.array_equal(score.view(np.uint32), w_score.view(np.uint32)), (block, case)
+        assert np.array_equal(keep, w_keep) and list(map(int, order)) == w_order, (block, case)
+        assert [list(map(int, cl)) for cl in clusters] == w_clusters, (block, case)
+        reached.add(c, res)
+    assert reached.kept_past_256 and reached.big_cluster and reached.tie_256 and reached.signed_zero_owned, vars(reached)

@@ -141,7 +141,8 @@ def filter_projection(uv, model_off, obj_model, proj_err2, min_points, feature_d
     coordinate gets an integer id once (np.unique over the bit patterns) and the map is two arrays.  One image."""
     uv = np.asarray(uv, f32).reshape(-1, 2)
     n_models, n_obj = len(model_off) - 1, len(obj_model)
-    _, point_id = np.unique(uv.view(np.uint32).astype(np.uint64) @ np.array([1 << 32, 1], np.uint64), return_inverse=True)
+    key = (uv + f32(0)).view(np.uint32).astype(np.uint64)                   # + 0: -0.0 and 0.0 are one key, as std::map sees them
+    _, point_id = np.unique(key @ np.array([1 << 32, 1], np.uint64), return_inverse=True)
     best_score = np.zeros(point_id.max() + 1 if len(uv) else 0, f32)       # pair<Float, Object*> default: (0, NULL)
     best_obj = np.full(len(best_score), -1)
     score = np.zeros(n_obj, f32)
