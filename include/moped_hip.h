@@ -610,6 +610,12 @@ int mh_frame_fetch_match_points(mh_ctx* ctx, mh_corr* corr_host, int cap, int32_
  * other (depth maps per frame, stage timing) only the last one's remain -> MH_ERR_ARG for the others. */
 int mh_frame_fetch_matches_slot(mh_ctx* ctx, int slot, int32_t* query_host, int32_t* model_host, int cap,
                                 int32_t* n_matches);
+/* The representatives of frame `slot`'s list entries, in list order: rep[i] = the first entry j <= i with the same
+ * image coordinate (u, v) as entry i (compared as floats: -0.0 == 0.0), and in frames with several images
+ * (mh_frame_set_images) also the same image -- the key under which FILTER's bestPoints map files entry i
+ * (FILTER_PROJECTION_CPU.hpp:89).  Read only; the same slots and errors as mh_frame_fetch_matches_slot, and slot -1 =
+ * the last frame (the lists mh_frame_fetch_matches gives). */
+int mh_frame_fetch_match_reps_slot(mh_ctx* ctx, int slot, int32_t* rep_host, int cap, int32_t* n_matches);
 /* Device address of the frame's packed result block {int32 n; mh_object[cap]}
  * for exchange 2 (gather of per-rank objects); *bytes = its size. */
 int mh_frame_result_dev(mh_ctx* ctx, void** block_dev, int64_t* bytes);

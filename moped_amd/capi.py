@@ -110,7 +110,7 @@ EXPORTS = [
     "mh_comm_unique_id", "mh_comm_create", "mh_comm_create_all", "mh_comm_create_host", "mh_comm_destroy", "mh_comm_info",
     "mh_frame_enqueue_sharded", "mh_frame_enqueue_sharded_batch", "mh_frame_enqueue_sharded_all",
     "mh_frame_previous_objects", "mh_frame_gather_objects", "mh_frame_enqueue_batch", "mh_frame_set_depth_image_batch",
-    "mh_pose_kernel_info", "mh_db_upload_blocks", "mh_frame_fetch_matches_slot",
+    "mh_pose_kernel_info", "mh_db_upload_blocks", "mh_frame_fetch_matches_slot", "mh_frame_fetch_match_reps_slot",
     "mh_screen_values", "mh_screen_record_value", "mh_screen_record_bounds", "mh_reserve_batch", "mh_frame_run_host",
     "mh_frame_block_stride", "mh_frame_fetch_batch_async", "mh_frame_fetch_previous_async", "mh_frame_fetch_wait",
     "mh_frame_fetch_query", "mh_host_alloc", "mh_host_free", "mh_frame_run_host_begin", "mh_frame_wait_descriptors",
@@ -261,6 +261,8 @@ def load():
     L.mh_frame_gather_objects.argtypes = [vp, vp, i32, vp, i32, C.POINTER(C.c_int32)]
     L.mh_pose_kernel_info.argtypes = [vp, i32, vp]
     L.mh_frame_fetch_matches_slot.argtypes = [vp, i32, vp, vp, i32, C.POINTER(C.c_int32)]
+    L.mh_frame_fetch_match_reps_slot.argtypes = [vp, i32, vp, i32, C.POINTER(C.c_int32)]
+    L.mh_frame_fetch_match_points.argtypes = [vp, vp, i32, C.POINTER(C.c_int32)]
     L.mh_frame_enqueue_rest_frames.argtypes = [vp, vp, i32, vp, i32, i32, i32, i32, C.POINTER(mh_cam),
                                                C.POINTER(mh_frame_params), C.POINTER(C.c_uint64)]
     L.mh_screen_values.argtypes = [vp, vp, i32, i32, vp, C.POINTER(f32), C.POINTER(f32), i32]
@@ -1011,6 +1013,22 @@ class Context:
         self._ck(self.L.mh_frame_fetch_matches_slot(self.h, slot, _ptr(q), _ptr(m), cap, C.byref(n)),
                  "mh_frame_fetch_matches_slot")
         return q[:min(n.value, cap)].copy(), m[:min(n.value, cap)].copy()
+
+    def frame_fetch_match_points(self, cap=1 << 16):
+        """The last frame's accepted matches as correspondences (u, v of the query, x, y, z of its row), list order."""
+        c = np.zeros(cap, CORR_DTYPE)
+        n = C.c_int32(0)
+        self._ck(self.L.mh_frame_fetch_match_points(self.h, _ptr(c), cap, C.byref(n)), "mh_frame_fetch_match_points")
+        return c[:min(n.value, cap)].copy()
+
+    def frame_fetch_match_reps(self, slot=None, cap=1 << 16):
+        """Representatives of the list entries of frame `slot` of the last batch (None: the last frame): the first
+        entry with the same pixel (and image) -- the key of FILTER's bestPoints map."""
+        r = np.zeros(cap, np.int32)
+        n = C.c_int32(0)
+        self._ck(self.L.mh_frame_fetch_match_reps_slot(self.h, -1 if slot is None else slot, _ptr(r), cap, C.byref(n)),
+                 "mh_frame_fetch_match_reps_slot")
+        return r[:min(n.value, cap)].copy()
 
     def frame_enqueue_rest_frames(self, q_uv_ptr, Q, gathered_ptr, n_shards, stride_words, plane_words, B, K, cam,
                                   params: mh_frame_params, seeds, _cam_struct=None):

@@ -1938,6 +1938,30 @@ int mh_frame_fetch_matches_slot(mh_ctx* ctx, int slot, int32_t* query_host, int3
   return MH_OK;
 }
 
+int mh_frame_fetch_match_reps_slot(mh_ctx* ctx, int slot, int32_t* rep_host, int cap, int32_t* n_matches) {
+  if (!ctx || !ctx->fs || !n_matches || cap < 0 || (cap > 0 && !rep_host) || slot < -1 || slot >= MH_MAX_BATCH)
+    return MH_ERR_ARG;
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
+  FrameState* fs = ctx->fs;
+  if (slot < 0) slot = fs->list_first + fs->list_n - 1;   // -1: the last frame (mh_frame_fetch_matches' lists)
+  if (slot < fs->list_first || slot >= fs->list_first + fs->list_n) {
+    ctx->err = "mh_frame_fetch_match_reps_slot: the lists of that frame are gone (frames that went through the steps one "
+               "after the other share one set of working arrays: only the last one's remain)";
+    return MH_ERR_ARG;
+  }
+  const size_t a = (size_t)(slot - fs->list_first) * fs->arena_bytes;   // the frame's copy of the working arrays
+  int32_t snap[4] = {0, 0, 0, 0};
+  MH_HIP(ctx, hipMemcpyAsync(snap, fs->snap + 4 * slot, sizeof snap, hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *n_matches = snap[0];
+  const int take = std::min(snap[0], cap);
+  if (take > 0)
+    MH_HIP(ctx, hipMemcpy(rep_host, reinterpret_cast<const unsigned char*>(fs->m_rep) + a, sizeof(int32_t) * (size_t)take,
+                          hipMemcpyDeviceToHost));
+  return MH_OK;
+}
+
 int mh_frame_fetch_match_points(mh_ctx* ctx, mh_corr* corr_host, int cap, int32_t* n_matches) {
   if (!ctx || !ctx->fs || !n_matches || cap < 0 || (cap > 0 && !corr_host)) return MH_ERR_ARG;
   MH_HIP(ctx, hipSetDevice(ctx->device));
