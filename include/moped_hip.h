@@ -706,6 +706,29 @@ int mh_frame_enqueue_image_batch(mh_ctx* ctx, const uint8_t* const* gray_dev, in
 int mh_frame_features_dev(mh_ctx* ctx, float** desc_dev, float** uv_dev, int32_t** n_dev);
 int mh_frame_keypoints(mh_ctx* ctx, int32_t* n_keypoints);
 
+/* ---- UNDISTORT: lens undistortion (UTIL_UNDISTORT) ------------------------------------ */
+
+/* UTIL_UNDISTORT (src/util/UTIL_UNDISTORT.hpp) on the device.  K = fx, fy, cx, cy (Image::intrinsicLinearCalibration,
+ * :77-81); dist = k1, k2, p1, p2 (intrinsicNonlinearCalibration, :84-87; k3 = 0).  The maps are cvInitUndistortMap's
+ * (:68-98: OpenCV 2.x initUndistortRectifyMap with R = I and the new camera = K, in double); the resampling is
+ * cvRemap(CV_INTER_LINEAR + CV_WARP_FILL_OUTLIERS) (:127: 5-bit fixed-point bilinear, border 0).  A context keeps the
+ * maps of its last MH_MAX_IMAGES cameras (the reference keeps all, keyed by size and calibration, :52-66); a new one is
+ * built on the context's stream.  MH_ERR_ARG: a null pointer, a side <= 0 or > 32767, a non-finite K or dist, fx or
+ * fy = 0. */
+/* The float maps UTIL_UNDISTORT::init builds (:94): mapx, mapy [height][width] each.  Synchronises. */
+int mh_undistort_map(mh_ctx* ctx, int width, int height, const float K[4], const float dist[4],
+                     float* mapx_host, float* mapy_host);
+/* UTIL_UNDISTORT::process for one image (:121-131): height x width bytes; out == in allowed.  Synchronises. */
+int mh_undistort(mh_ctx* ctx, const uint8_t* gray_host, uint8_t* out_host, int width, int height,
+                 const float K[4], const float dist[4]);
+/* The same on device images, stream-ordered, no host synchronisation; out != in (MH_ERR_ARG). */
+int mh_undistort_dev(mh_ctx* ctx, const uint8_t* gray_dev, uint8_t* out_dev, int width, int height,
+                     const float K[4], const float dist[4]);
+/* "UNDISTORTED_IMAGE" ahead of FEAT in the resident image path (config.hpp:59): mh_frame_enqueue_image and
+ * mh_frame_enqueue_image_batch remap their image(s) with (width, height, cam->K, dist) into a staging buffer of the
+ * context, one launch for a batch, and FEAT reads that.  dist = NULL: off (the default). */
+int mh_frame_set_undistort(mh_ctx* ctx, const float dist[4]);
+
 /* ---- model files ------------------------------------------------ */
 
 /* Host-side set of models: parsed from `.moped.xml` files the way Moped::addModel(sXML&)

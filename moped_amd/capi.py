@@ -116,6 +116,7 @@ EXPORTS = [
     "mh_frame_fetch_query", "mh_host_alloc", "mh_host_free", "mh_frame_run_host_begin", "mh_frame_wait_descriptors",
     "mh_step_match", "mh_step_match_fetch", "mh_step_cluster", "mh_step_pose", "mh_step_filter",
     "mh_set_linkage_scratch_limit",
+    "mh_undistort_map", "mh_undistort", "mh_undistort_dev", "mh_frame_set_undistort",
 ]
 COMM_ID_BYTES = 128      # MH_COMM_ID_BYTES
 EX2_OBJECTS = 62         # MH_EX2_OBJECTS
@@ -287,8 +288,20 @@ def load():
         L.mh_step_pose.argtypes = [vp, i32, C.POINTER(mh_pose_params), C.c_uint64, vp, i32, C.POINTER(C.c_int32)]
         L.mh_step_filter.argtypes = [vp, i32, i32, f32, f32, i32, vp, vp, vp, vp, vp, i32, C.POINTER(C.c_int32)]
     L.mh_frame_fetch_query.argtypes = [vp]
+    if hasattr(L, "mh_undistort"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
+        L.mh_undistort_map.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+        L.mh_undistort.argtypes = [vp, vp, vp, i32, i32, vp, vp]
+        L.mh_undistort_dev.argtypes = [vp, vp, vp, i32, i32, vp, vp]
+        L.mh_frame_set_undistort.argtypes = [vp, vp]
     _lib = L
     return L
+
+
+def _calib(v):
+    a = np.ascontiguousarray(v, np.float32).reshape(-1)
+    if a.size != 4:
+        raise ValueError("a calibration has 4 values")
+    return a
 
 
 def make_cam(K, cam) -> mh_cam:
@@ -760,6 +773,36 @@ class Context:
         self._ck(self.L.mh_sift_extract_dev(self.h, C.c_void_p(gray_ptr), w, h, int(double_size), C.c_void_p(desc_ptr),
                                             C.c_void_p(xy_ptr), C.c_void_p(scale_ori_ptr) if scale_ori_ptr else None,
                                             cap, C.c_void_p(n_ptr)), "mh_sift_extract_dev")
+
+    # ---- UNDISTORTED_IMAGE (UTIL_UNDISTORT) ----
+    def undistort(self, gray, K, dist):
+        """-> the 8-bit image undistorted as UTIL_UNDISTORT::process leaves it (K = fx, fy, cx, cy; dist = k1, k2, p1, p2)."""
+        g = np.ascontiguousarray(gray, np.uint8)
+        h, w = g.shape
+        out = np.empty_like(g)
+        k, d = _calib(K), _calib(dist)
+        self._ck(self.L.mh_undistort(self.h, _ptr(g), _ptr(out), w, h, _ptr(k), _ptr(d)), "mh_undistort")
+        return out
+
+    def undistort_dev(self, src_ptr, dst_ptr, w, h, K, dist):
+        """The same on device images (dst != src), stream-ordered."""
+        k, d = _calib(K), _calib(dist)
+        self._ck(self.L.mh_undistort_dev(self.h, C.c_void_p(src_ptr), C.c_void_p(dst_ptr), w, h, _ptr(k), _ptr(d)),
+                 "mh_undistort_dev")
+
+    def undistort_map(self, w, h, K, dist):
+        """-> (mapx, mapy) float32 [h, w]: the maps UTIL_UNDISTORT::init builds."""
+        mx = np.empty((h, w), np.float32)
+        my = np.empty((h, w), np.float32)
+        k, d = _calib(K), _calib(dist)
+        self._ck(self.L.mh_undistort_map(self.h, w, h, _ptr(k), _ptr(d), _ptr(mx), _ptr(my)), "mh_undistort_map")
+        return mx, my
+
+    def frame_set_undistort(self, dist):
+        """Undistort the images of frame_enqueue_image[_batch] with the frame camera's K and these k1, k2, p1, p2
+        before FEAT; None = off."""
+        d = None if dist is None else _calib(dist)
+        self._ck(self.L.mh_frame_set_undistort(self.h, None if d is None else _ptr(d)), "mh_frame_set_undistort")
 
     def project_test(self, pose7, corr, K, cam, thr):
         corr = np.ascontiguousarray(corr, CORR_DTYPE)

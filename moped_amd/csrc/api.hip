@@ -188,6 +188,7 @@ int mh_create(int device, mh_ctx** out) {
 
 void mh_free_frame_state(mh_ctx* ctx);  // api_steps.hip
 void mh_free_sift_state(mh_ctx* ctx);   // api_sift.hip
+void mh_free_undistort_state(mh_ctx* ctx);   // undistort.hip
 
 void mh_destroy(mh_ctx* ctx) {
   if (!ctx) return;
@@ -195,6 +196,7 @@ void mh_destroy(mh_ctx* ctx) {
   if (ctx->stream) hipStreamSynchronize(ctx->stream);
   mh_free_frame_state(ctx);
   mh_free_sift_state(ctx);
+  mh_free_undistort_state(ctx);
   free_screen_bufs(ctx);
   mh::free_exchange(ctx);
   ctx->store.reset();   // the DB goes with its last user

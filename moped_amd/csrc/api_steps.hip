@@ -1558,6 +1558,8 @@ int mh_frame_enqueue_image(mh_ctx* ctx, const uint8_t* gray_dev, int width, int 
   const int Q = max_keypoints;
   int rc = prepare_frame(ctx, Q);
   if (rc) return rc;
+  // UNDISTORTED_IMAGE (mh_frame_set_undistort): FEAT reads the remapped copy in the context's staging buffer
+  if (ctx->und_on && (rc = undistort_frame(ctx, &gray_dev, 1, width, height, cam->K, &gray_dev))) return rc;
   // FEAT: keypoints straight into the frame's query buffers; their number stays on the device
   int32_t* n_dev = nullptr;
   if ((rc = sift_into(ctx, gray_dev, width, height, double_size, Q, ctx->q_desc, ctx->q_uv, &n_dev))) return rc;
@@ -1589,6 +1591,12 @@ int mh_frame_enqueue_image_batch(mh_ctx* ctx, const uint8_t* const* gray_dev, in
   if (!ctx->img_counts) {
     MH_HIP(ctx, hipMalloc(&ctx->img_counts, MH_MAX_BATCH * sizeof(int32_t)));
     MH_HIP(ctx, hipMemsetAsync(ctx->img_counts, 0, MH_MAX_BATCH * sizeof(int32_t), s));
+  }
+  // UNDISTORTED_IMAGE (mh_frame_set_undistort): one remap launch for the B images into the context's staging buffer
+  const uint8_t* staged[MH_MAX_BATCH];
+  if (ctx->und_on) {
+    if ((rc = undistort_frame(ctx, gray_dev, B, width, height, cam->K, staged))) return rc;
+    gray_dev = staged;
   }
   // FEAT image by image into the batch's query rows (image f: rows f Q ..), every image's count in a word of its own
   // (round 4: ONE launch per FEAT stage for all B images -- a frame's 26 dependent launches were what bounded this path)

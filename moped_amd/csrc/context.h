@@ -117,6 +117,9 @@ struct mh_ctx {
   // frame state (group / cluster / pose / filter); defined in frame.h
   struct FrameState* fs = nullptr;
   struct SiftState* sift = nullptr;   // pyramid + keypoint buffers of the SIFT extractor (api_sift.hip)
+  struct UndistortState* und = nullptr;   // undistortion maps + staging (undistort.hip); made on first use
+  bool und_on = false;                // mh_frame_set_undistort: the image paths remap before FEAT
+  float und_dist[4] = {0, 0, 0, 0};   // ... with these k1, k2, p1, p2 and the frame camera's K
   int32_t* feat_count_dev = nullptr;  // frame enqueued from an image: device word with its keypoint count
   int32_t* img_counts = nullptr;      // mh_frame_enqueue_image_batch: [MH_MAX_BATCH] keypoint counts of the batch's images (device)
   int feat_expected = 0;              // keypoints of the last fetched image frame (sizes the next MATCH launch)
@@ -230,6 +233,10 @@ int delivery_begin(mh_ctx* ctx, void* host_block, size_t bytes, unsigned char** 
 int delivery_end(mh_ctx* ctx, void* host_block, size_t bytes, unsigned char* dst_dev, int B, int max_objects, uint32_t tag);
 int sift_into(mh_ctx* ctx, const uint8_t* gray_dev, int width, int height, int double_size, int cap,
               float* desc_dev, float* xy_dev, int32_t** n_dev_out, int32_t* count_word = nullptr);
+// undistort.hip: n device images remapped with the map of (width, height, K, ctx->und_dist) into the context's staging
+// buffer, one launch on the context's stream; staged[f] = image f's undistorted copy
+int undistort_frame(mh_ctx* ctx, const uint8_t* const* gray_dev, int n, int width, int height, const float K[4],
+                    const uint8_t** staged);
 int sift_into_batch(mh_ctx* ctx, const uint8_t* const* gray_dev, int n, int width, int height, int double_size, int cap,
                     float* desc_dev, float* xy_dev, int32_t* count_words);
 
