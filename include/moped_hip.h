@@ -686,6 +686,54 @@ int mh_sift_extract(mh_ctx* ctx, const uint8_t* gray_host, int width, int height
 int mh_sift_extract_dev(mh_ctx* ctx, const uint8_t* gray_dev, int width, int height, int double_size,
                         float* desc_dev, float* xy_dev, float* scale_ori_dev, int cap, int32_t* n_dev);
 
+/* n_images <= MH_MAX_BATCH device images of one size through FEAT alone, ONE launch per stage for all of them (what
+ * mh_frame_enqueue_image_batch runs ahead of MATCH): image i's keypoints at desc_dev + i cap 128 / xy_dev + i cap 2,
+ * its count in counts_dev[i] (device int32).  Asynchronous.  Every image's output is bit for bit that of
+ * mh_sift_extract_dev on it alone. */
+int mh_sift_extract_batch_dev(mh_ctx* ctx, const uint8_t* const* gray_dev, int n_images, int width, int height,
+                              int double_size, float* desc_dev, float* xy_dev, int cap, int32_t* counts_dev);
+
+/* FOR VERIFICATION (tests/test_gpu_sift_stages.py): what the context's LAST extraction left on the device, stage by
+ * stage, for image `slot` of that launch (0 for a single image, 0 .. n_images - 1 after a batch).  Every call
+ * synchronises the context's stream and copies to host memory; none launches a kernel or changes the state.
+ * MH_ERR_ARG: no extraction yet, a slot / octave / level that does not exist. */
+#define MH_SIFT_MAX_OCTAVES 8
+typedef struct {             /* a refined extremum: InterpKeyPoint's result (libsiftfast.cpp:1164-1206) */
+  int32_t octave, index;     /* scale index 1..3 */
+  uint32_t key;              /* generation order within the octave: (index - 1) rows cols + start r * cols + start c */
+  int32_t r, c;              /* final pixel */
+  float x0, x1, x2;          /* offsets in scale, row, column */
+} mh_sift_candidate;
+typedef struct {             /* one (extremum, orientation peak) */
+  int32_t octave, index;
+  uint64_t order;            /* octave << 40 | key << 8 | histogram bin */
+  float fsize, frow, fcol, ori;
+} mh_sift_key;
+/* The octave plan of the last extraction: rows[o], cols[o] for o < *n_octaves (arrays of MH_SIFT_MAX_OCTAVES), and the
+ * number of image slots its launch filled. */
+int mh_sift_debug_plan(mh_ctx* ctx, int32_t* n_images, int32_t* n_octaves, int32_t* rows, int32_t* cols);
+/* kind 0: Gaussian level 0..4 (level 5 is never stored: only its DoG is kept), kind 1: DoG level 0..4 of `octave`;
+ * out_host = rows x cols floats. */
+int mh_sift_debug_level(mh_ctx* ctx, int slot, int octave, int kind, int level, float* out_host);
+/* The candidates in the order the kernel appended them (any), won_host[i] = 1 where candidate i's claim is the owner
+ * word of its final pixel (the first extremum in generation order to end there).  *n = their number; `cap` are written. */
+int mh_sift_debug_candidates(mh_ctx* ctx, int slot, mh_sift_candidate* out_host, uint8_t* won_host, int cap, int32_t* n);
+/* The key buffer, slots in the order the kernel filled them (any).  *n = their number; `cap` are written. */
+int mh_sift_debug_keys(mh_ctx* ctx, int slot, mh_sift_key* out_host, int cap, int32_t* n);
+/* ONE blur level of a host image through a named kernel of the blur chain, with GaussianBlur's kernel for `sigma`:
+ *   0  row kernel + column kernel         any tap count below 64
+ *   1  tile kernel, one level             half-width <= 16
+ *   2  tile kernel, job list              half-width <= 16 (a kernel of its own for 11, 13, 17, 21, 25 taps); half = 1:
+ *                                         the source is read at every second row and column (HalfImageSize fused into
+ *                                         the level) and half_host gets those pixels
+ *   3  HalfImageSize alone                half = 1, sigma unused, dst_host = every second row and column
+ *   4  single-workgroup chain             at most 6 912 pixels, dog_host required
+ * dst_host (and dog_host = source - blurred, optional for 0 .. 2) are rows x cols floats: src_rows x src_cols, or half
+ * of each (rounded down) with half = 1.  A variant that cannot take the arguments returns MH_ERR_ARG and launches
+ * nothing.  Synchronises. */
+int mh_sift_debug_blur(mh_ctx* ctx, int variant, const float* src_host, int src_rows, int src_cols, float sigma, int half,
+                       float* dst_host, float* dog_host, float* half_host);
+
 /* FEAT + the whole frame, image in, objects out, nothing through the host: SIFT of the device image
  * (as mh_sift_extract_dev) straight into the frame's query buffers, then mh_frame_enqueue's launch
  * list.  The keypoint count stays on the device: every launch is sized for `max_keypoints` and the

@@ -65,6 +65,11 @@ STEP_OBJECT_DTYPE = np.dtype([("model", "<i4"), ("pose", "<f4", (7,))])   # mh_s
 DEPTH_DTYPE = np.dtype([("wx", "<f4"), ("wy", "<f4"), ("wz", "<f4"), ("w", "<f4")])
 DEPTH_BACKPROJECTION, DEPTH_REPROJECTION = 1, 2
 POSE_OUT_DTYPE = np.dtype([("pose", "<f4", (7,)), ("cluster", "<i4"), ("n_inliers", "<i4"), ("err", "<f4")])
+SIFT_CANDIDATE_DTYPE = np.dtype([("octave", "<i4"), ("index", "<i4"), ("key", "<u4"), ("r", "<i4"), ("c", "<i4"),
+                                 ("x0", "<f4"), ("x1", "<f4"), ("x2", "<f4")])                      # mh_sift_candidate
+SIFT_KEY_DTYPE = np.dtype([("octave", "<i4"), ("index", "<i4"), ("order", "<u8"), ("fsize", "<f4"), ("frow", "<f4"),
+                           ("fcol", "<f4"), ("ori", "<f4")])                                        # mh_sift_key
+SIFT_MAX_OCTAVES = 8     # MH_SIFT_MAX_OCTAVES
 
 # every symbol include/moped_hip.h declares
 MAX_BATCH = 32   # MH_MAX_BATCH
@@ -117,6 +122,8 @@ EXPORTS = [
     "mh_step_match", "mh_step_match_fetch", "mh_step_cluster", "mh_step_pose", "mh_step_filter",
     "mh_set_linkage_scratch_limit",
     "mh_undistort_map", "mh_undistort", "mh_undistort_dev", "mh_frame_set_undistort",
+    "mh_sift_extract_batch_dev", "mh_sift_debug_plan", "mh_sift_debug_level", "mh_sift_debug_candidates",
+    "mh_sift_debug_keys", "mh_sift_debug_blur",
 ]
 COMM_ID_BYTES = 128      # MH_COMM_ID_BYTES
 EX2_OBJECTS = 62         # MH_EX2_OBJECTS
@@ -181,6 +188,12 @@ def load():
     L.mh_frame_run_host_begin.argtypes = [vp, vp, vp, vp, i32, C.POINTER(mh_cam), i32, C.POINTER(mh_frame_params), C.c_uint64, i32]
     L.mh_sift_extract.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, i32, C.POINTER(C.c_int32)]
     L.mh_sift_extract_dev.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, i32, vp]
+    L.mh_sift_extract_batch_dev.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, vp]
+    L.mh_sift_debug_plan.argtypes = [vp, vp, vp, vp, vp]
+    L.mh_sift_debug_level.argtypes = [vp, i32, i32, i32, i32, vp]
+    L.mh_sift_debug_candidates.argtypes = [vp, i32, vp, vp, i32, C.POINTER(C.c_int32)]
+    L.mh_sift_debug_keys.argtypes = [vp, i32, vp, i32, C.POINTER(C.c_int32)]
+    L.mh_sift_debug_blur.argtypes = [vp, i32, vp, i32, i32, f32, i32, vp, vp, vp]
     L.mh_frame_enqueue_image.argtypes = [vp, vp, i32, i32, i32, i32, C.POINTER(mh_cam), C.POINTER(mh_frame_params),
                                          C.c_uint64]
     L.mh_frame_enqueue_image_batch.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.POINTER(mh_cam), C.POINTER(mh_frame_params), vp]
@@ -773,6 +786,62 @@ class Context:
         self._ck(self.L.mh_sift_extract_dev(self.h, C.c_void_p(gray_ptr), w, h, int(double_size), C.c_void_p(desc_ptr),
                                             C.c_void_p(xy_ptr), C.c_void_p(scale_ori_ptr) if scale_ori_ptr else None,
                                             cap, C.c_void_p(n_ptr)), "mh_sift_extract_dev")
+
+    def sift_batch_dev(self, gray_ptrs, w, h, double_size, desc_ptr, xy_ptr, cap, counts_ptr):
+        """FEAT alone on len(gray_ptrs) device images of one size, one launch per stage; asynchronous."""
+        n = len(gray_ptrs)
+        g = (C.c_void_p * n)(*gray_ptrs)
+        self._ck(self.L.mh_sift_extract_batch_dev(self.h, g, n, w, h, int(double_size), C.c_void_p(desc_ptr),
+                                                  C.c_void_p(xy_ptr), cap, C.c_void_p(counts_ptr)),
+                 "mh_sift_extract_batch_dev")
+
+    # the stages of the last extraction, for verification (mh_sift_debug_*)
+    def sift_debug_plan(self):
+        """-> (image slots of the last launch, [(rows, cols)] per octave)."""
+        ni, no = C.c_int32(0), C.c_int32(0)
+        rows, cols = np.zeros(SIFT_MAX_OCTAVES, np.int32), np.zeros(SIFT_MAX_OCTAVES, np.int32)
+        self._ck(self.L.mh_sift_debug_plan(self.h, C.addressof(ni), C.addressof(no), _ptr(rows), _ptr(cols)),
+                 "mh_sift_debug_plan")
+        return ni.value, [(int(rows[o]), int(cols[o])) for o in range(no.value)]
+
+    def sift_debug_level(self, octave, kind, level, shape, slot=0):
+        """Gaussian (kind 0) / DoG (kind 1) level 0..4 of `octave` -> float32 [rows, cols] (shape from sift_debug_plan)."""
+        out = np.zeros(shape, np.float32)
+        self._ck(self.L.mh_sift_debug_level(self.h, slot, octave, kind, level, _ptr(out)), "mh_sift_debug_level")
+        return out
+
+    def sift_debug_candidates(self, slot=0, cap=65536):
+        """-> (candidates [n] SIFT_CANDIDATE_DTYPE in the kernel's (any) order, won [n] bool)."""
+        out = np.zeros(cap, SIFT_CANDIDATE_DTYPE)
+        won = np.zeros(cap, np.uint8)
+        n = C.c_int32(0)
+        self._ck(self.L.mh_sift_debug_candidates(self.h, slot, _ptr(out), _ptr(won), cap, C.byref(n)),
+                 "mh_sift_debug_candidates")
+        if n.value > cap:
+            raise MhError(f"mh_sift_debug_candidates: {n.value} candidates, room for {cap}")
+        return out[:n.value].copy(), won[:n.value].astype(bool)
+
+    def sift_debug_keys(self, slot=0, cap=16384):
+        """-> keys [n] SIFT_KEY_DTYPE in the kernel's (any) order."""
+        out = np.zeros(cap, SIFT_KEY_DTYPE)
+        n = C.c_int32(0)
+        self._ck(self.L.mh_sift_debug_keys(self.h, slot, _ptr(out), cap, C.byref(n)), "mh_sift_debug_keys")
+        if n.value > cap:
+            raise MhError(f"mh_sift_debug_keys: {n.value} keys, room for {cap}")
+        return out[:n.value].copy()
+
+    def sift_debug_blur(self, variant, src, sigma, half=False, want_dog=True, want_half=False):
+        """One blur level of a float32 image through kernel `variant` (mh_sift_debug_blur) -> (dst, dog or None,
+        half-size copy or None).  A variant that cannot take the arguments raises MhError."""
+        a = np.ascontiguousarray(src, np.float32)
+        shape = (a.shape[0] >> 1, a.shape[1] >> 1) if half else a.shape
+        dst = np.zeros(shape, np.float32)
+        dog = np.zeros(shape, np.float32) if want_dog else None
+        hd = np.zeros(shape, np.float32) if want_half else None
+        self._ck(self.L.mh_sift_debug_blur(self.h, variant, _ptr(a), a.shape[0], a.shape[1], sigma, int(half), _ptr(dst),
+                                           _ptr(dog) if want_dog else None, _ptr(hd) if want_half else None),
+                 "mh_sift_debug_blur")
+        return dst, dog, hd
 
     # ---- UNDISTORTED_IMAGE (UTIL_UNDISTORT) ----
     def undistort(self, gray, K, dist):

@@ -1,5 +1,6 @@
 // C ABI: SIFT extraction (FEAT_SIFT_CPU's job).
 #include <algorithm>
+#include <string>
 #include <vector>
 
 #include "context.h"
@@ -15,6 +16,7 @@ struct SiftState {
   float *desc = nullptr, *xy = nullptr, *scale_ori = nullptr;
   int32_t* n_dev = nullptr;
   unsigned int own_epoch = 0;    // B.own_epoch points here
+  int last_n = 0;                // image slots the last launch filled (mh_sift_debug_*); 0 = none yet
 };
 
 namespace {
@@ -105,6 +107,7 @@ int sift_into(mh_ctx* ctx, const uint8_t* gray_dev, int width, int height, int d
   int32_t* const n_dev = count_word ? count_word : st->n_dev;   // (a batch of images keeps every image's count)
   launch_sift(gray_dev, width, height, double_size ? 1 : 0, st->plan, st->B, cap, desc_dev, xy_dev, nullptr,
               n_dev, ctx->stream);
+  st->last_n = 1;
   MH_HIP(ctx, hipGetLastError());
   if (n_dev_out) *n_dev_out = n_dev;
   return MH_OK;
@@ -119,6 +122,7 @@ int sift_into_batch(mh_ctx* ctx, const uint8_t* const* gray_dev, int n, int widt
   SiftState* st = ctx->sift;
   launch_sift_batch(gray_dev, n, width, height, double_size ? 1 : 0, st->plan, st->B, cap, cap, desc_dev, xy_dev, nullptr,
                     count_words, 1, ctx->stream);
+  st->last_n = n;   // (n = 1 goes image by image into slot 0)
   MH_HIP(ctx, hipGetLastError());
   return MH_OK;
 }
@@ -145,6 +149,7 @@ int mh_sift_extract_dev(mh_ctx* ctx, const uint8_t* gray_dev, int width, int hei
   SiftState* st = ctx->sift;
   launch_sift(gray_dev, width, height, double_size ? 1 : 0, st->plan, st->B, cap, desc_dev, xy_dev, scale_ori_dev,
               n_dev, ctx->stream);
+  st->last_n = 1;
   MH_HIP(ctx, hipGetLastError());
   return MH_OK;
 }
@@ -165,6 +170,7 @@ int mh_sift_extract(mh_ctx* ctx, const uint8_t* gray_host, int width, int height
   MH_HIP(ctx, hipMemcpyAsync(st->gray, gray_host, (size_t)width * height, hipMemcpyHostToDevice, s));
   launch_sift(st->gray, width, height, double_size ? 1 : 0, st->plan, st->B, st->cap, st->desc, st->xy, st->scale_ori,
               st->n_dev, s);
+  st->last_n = 1;
   MH_HIP(ctx, hipGetLastError());
   int32_t head[4] = {0, 0, 0, 0};
   int32_t n = 0;
@@ -185,6 +191,156 @@ int mh_sift_extract(mh_ctx* ctx, const uint8_t* gray_host, int width, int height
     return MH_ERR_CAPACITY;
   }
   return MH_OK;
+}
+
+int mh_sift_extract_batch_dev(mh_ctx* ctx, const uint8_t* const* gray_dev, int n_images, int width, int height,
+                              int double_size, float* desc_dev, float* xy_dev, int cap, int32_t* counts_dev) {
+  if (!ctx || !gray_dev || n_images <= 0 || n_images > MH_MAX_BATCH || width <= 0 || height <= 0 || !desc_dev || !xy_dev ||
+      cap <= 0 || !counts_dev) {
+    if (ctx) ctx->err = "mh_sift_extract_batch_dev: bad argument";
+    return MH_ERR_ARG;
+  }
+  for (int i = 0; i < n_images; ++i)
+    if (!gray_dev[i]) {
+      ctx->err = "mh_sift_extract_batch_dev: bad argument";
+      return MH_ERR_ARG;
+    }
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
+  return mh::sift_into_batch(ctx, gray_dev, n_images, width, height, double_size, cap, desc_dev, xy_dev, counts_dev);
+}
+
+// ---- for verification: the stages of the last extraction (include/moped_hip.h) ------------------------------------
+static_assert(sizeof(mh_sift_candidate) == sizeof(SiftCandidate) && sizeof(mh_sift_key) == sizeof(SiftKey) &&
+                  MH_SIFT_MAX_OCTAVES == SIFT_MAX_OCTAVES,
+              "the header's records are the kernels' records");
+
+namespace {
+
+// the state of the last extraction, stream idle; null (and ctx->err) when there is none or `slot` was not filled
+SiftState* last_sift(mh_ctx* ctx, int slot, const char* who) {
+  if (!ctx) return nullptr;
+  SiftState* st = ctx->sift;
+  if (!st || st->last_n <= 0 || slot < 0 || slot >= st->last_n) {
+    ctx->err = std::string(who) + ": no extraction yet, or no such image slot";
+    return nullptr;
+  }
+  return st;
+}
+
+}  // namespace
+
+int mh_sift_debug_plan(mh_ctx* ctx, int32_t* n_images, int32_t* n_octaves, int32_t* rows, int32_t* cols) {
+  SiftState* st = last_sift(ctx, 0, "mh_sift_debug_plan");
+  if (!st || !n_octaves || !rows || !cols) return MH_ERR_ARG;
+  if (n_images) *n_images = st->last_n;
+  *n_octaves = st->plan.n_octaves;
+  for (int o = 0; o < st->plan.n_octaves; ++o) {
+    rows[o] = st->plan.rows[o];
+    cols[o] = st->plan.cols[o];
+  }
+  return MH_OK;
+}
+
+int mh_sift_debug_level(mh_ctx* ctx, int slot, int octave, int kind, int level, float* out_host) {
+  SiftState* st = last_sift(ctx, slot, "mh_sift_debug_level");
+  if (!st) return MH_ERR_ARG;
+  if (octave < 0 || octave >= st->plan.n_octaves || kind < 0 || kind > 1 || level < 0 || level > 4 || !out_host) {
+    ctx->err = "mh_sift_debug_level: no such image (Gaussian levels 0..4 and DoG levels 0..4 are kept)";
+    return MH_ERR_ARG;
+  }
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  // the layout launch_sift_images gives the pyramid: per octave 6 Gaussian + 5 DoG images
+  size_t at = 0;
+  for (int o = 0; o < octave; ++o) at += (size_t)st->plan.rows[o] * st->plan.cols[o] * SIFT_IMAGES_PER_OCTAVE;
+  const size_t px = (size_t)st->plan.rows[octave] * st->plan.cols[octave];
+  at += px * (kind == 0 ? level : 6 + level);
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  MH_HIP(ctx, hipMemcpy(out_host, st->B.pyramid + (size_t)slot * st->plan.floats + at, px * sizeof(float),
+                        hipMemcpyDeviceToHost));
+  return MH_OK;
+}
+
+int mh_sift_debug_candidates(mh_ctx* ctx, int slot, mh_sift_candidate* out_host, uint8_t* won_host, int cap, int32_t* n) {
+  SiftState* st = last_sift(ctx, slot, "mh_sift_debug_candidates");
+  if (!st || !out_host || !won_host || cap < 0 || !n) return MH_ERR_ARG;
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  int32_t head[4];
+  MH_HIP(ctx, hipMemcpy(head, st->B.counters + 4 * slot, sizeof head, hipMemcpyDeviceToHost));
+  *n = std::min(head[0], st->B.cand_cap);
+  const int take = std::min(*n, cap);
+  if (take <= 0) return MH_OK;
+  MH_HIP(ctx, hipMemcpy(out_host, st->B.cand + (size_t)slot * st->B.cand_cap, (size_t)take * sizeof(SiftCandidate),
+                        hipMemcpyDeviceToHost));
+  std::vector<unsigned int> own(st->B.owner_elems);
+  MH_HIP(ctx, hipMemcpy(own.data(), st->B.owner + (size_t)slot * st->B.owner_elems, own.size() * sizeof(unsigned int),
+                        hipMemcpyDeviceToHost));
+  const unsigned prefix = sift_own_prefix(st->plan, st->own_epoch);
+  std::vector<size_t> first(st->plan.n_octaves, 0);
+  for (int o = 1; o < st->plan.n_octaves; ++o) first[o] = first[o - 1] + (size_t)st->plan.rows[o - 1] * st->plan.cols[o - 1];
+  for (int i = 0; i < take; ++i) {
+    const mh_sift_candidate& q = out_host[i];
+    won_host[i] = 0;
+    if (q.octave < 0 || q.octave >= st->plan.n_octaves || q.r < 0 || q.r >= st->plan.rows[q.octave] || q.c < 0 ||
+        q.c >= st->plan.cols[q.octave])
+      continue;
+    won_host[i] = own[first[q.octave] + (size_t)q.r * st->plan.cols[q.octave] + q.c] == (prefix | q.key) ? 1 : 0;
+  }
+  return MH_OK;
+}
+
+int mh_sift_debug_keys(mh_ctx* ctx, int slot, mh_sift_key* out_host, int cap, int32_t* n) {
+  SiftState* st = last_sift(ctx, slot, "mh_sift_debug_keys");
+  if (!st || !out_host || cap < 0 || !n) return MH_ERR_ARG;
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  int32_t head[4];
+  MH_HIP(ctx, hipMemcpy(head, st->B.counters + 4 * slot, sizeof head, hipMemcpyDeviceToHost));
+  *n = std::min(head[1], st->B.key_cap);
+  const int take = std::min(*n, cap);
+  if (take > 0)
+    MH_HIP(ctx, hipMemcpy(out_host, st->B.keys + (size_t)slot * st->B.key_cap, (size_t)take * sizeof(SiftKey),
+                          hipMemcpyDeviceToHost));
+  return MH_OK;
+}
+
+int mh_sift_debug_blur(mh_ctx* ctx, int variant, const float* src_host, int src_rows, int src_cols, float sigma, int half,
+                       float* dst_host, float* dog_host, float* half_host) {
+  if (!ctx || !src_host || !dst_host || src_rows <= 0 || src_cols <= 0 || src_rows > 32767 || src_cols > 32767) {
+    if (ctx) ctx->err = "mh_sift_debug_blur: bad argument";
+    return MH_ERR_ARG;
+  }
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
+  const int rows = half ? src_rows >> 1 : src_rows, cols = half ? src_cols >> 1 : src_cols;
+  const size_t spx = (size_t)src_rows * src_cols, px = (size_t)std::max(rows, 0) * std::max(cols, 0);
+  // one allocation: source | dst | dog | half | scratch (8 images)
+  float* buf = nullptr;
+  MH_HIP(ctx, hipMalloc(&buf, (spx + 11 * std::max<size_t>(px, 1)) * sizeof(float)));
+  float *src = buf, *dst = buf + spx, *dog = dst + px, *hdst = dog + px, *scratch = hdst + px;
+  int rc = MH_OK;
+  hipError_t e = hipMemcpyAsync(src, src_host, spx * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) {
+    if (launch_sift_blur_variant(variant, src, src_rows, src_cols, sigma, half ? 1 : 0, dst, dog_host ? dog : nullptr,
+                                 half_host ? hdst : nullptr, scratch, ctx->stream)) {
+      ctx->err = "mh_sift_debug_blur: this variant does not take these arguments";
+      rc = MH_ERR_ARG;
+    } else {
+      e = hipGetLastError();
+      if (e == hipSuccess) e = hipMemcpyAsync(dst_host, dst, px * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
+      if (e == hipSuccess && dog_host) e = hipMemcpyAsync(dog_host, dog, px * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
+      if (e == hipSuccess && half_host) e = hipMemcpyAsync(half_host, hdst, px * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
+    }
+  }
+  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
+  hipFree(buf);
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess) {
+    ctx->err = std::string("mh_sift_debug_blur: ") + hipGetErrorString(e);
+    return MH_ERR_HIP;
+  }
+  return rc;
 }
 
 }  // extern "C"

@@ -88,4 +88,20 @@ void launch_sift_batch(const uint8_t* const* gray, int n, int width, int height,
                        const SiftBuffers& B, int out_cap, int out_step, float* desc_out, float* xy_out,
                        float* scale_ori_out, int32_t* n_out, int n_out_step, hipStream_t s);
 
+
+// The owner map's claim prefix (SiftBatch::own_prefix) of the launch that left `epoch` in *SiftBuffers::own_epoch.
+unsigned sift_own_prefix(const SiftPlan& plan, unsigned epoch);
+
+// For verification (mh_sift_debug_blur): ONE blur level of one image through a named kernel, with the kernel of `sigma`
+// (GaussianBlur's, make_taps).  dst / dog (optional: source - blurred) are rows x cols images on the device.
+//   0  blur_rows_kernel + blur_cols_kernel (scratch: rows x cols floats)
+//   1  blur_level_kernel                    half-width <= 16
+//   2  blur_jobs_kernel                     half-width <= 16; half = 1: the source is the previous octave (src_rows x
+//                                           src_cols, read at every second row / column), half_dst gets those pixels
+//   3  half_kernel                          half = 1, no blur: dst = every second row / column of the source
+//   4  small_octaves_kernel                 rows x cols <= 6 912, dog required (scratch: 8 rows x cols floats)
+// Returns 0 after launching, 1 -- and launches nothing -- when the variant cannot take the arguments.
+int launch_sift_blur_variant(int variant, const float* src, int src_rows, int src_cols, float sigma, int half, float* dst,
+                             float* dog, float* half_dst, float* scratch, hipStream_t s);
+
 }  // namespace mh

@@ -8,6 +8,8 @@
 // Gauss-Jordan with row pivoting for the 3x3 fit, per-bin accumulation in raster order of the
 // samples -- so the only differences to the oracle come from the device's expf / atan2f /
 // sinf / cosf / powf (a few ulp).  The Gaussian kernels are computed on the host with libm.
+// tests/test_gpu_sift_stages.py holds that stage by stage (read back through mh_sift_debug_*): pyramid, extrema and key
+// positions equal the oracle's as uint32 on every blur kernel below, fSize within 4 ulp (powf: 2 measured), angles 1e-3 rad.
 //
 // Layout: the WHOLE pyramid stays resident (14 images per octave, all octaves: ~90 MB for a
 // doubled 640x480 frame), so everything after the blur chain runs ONCE over all octaves:
@@ -1408,6 +1410,19 @@ int sift_plan(int width, int height, int double_size, SiftPlan* plan) {
 }
 
 namespace {
+unsigned sift_key_bits(const SiftPlan& plan) {   // (a key is below kScales rows cols of octave 0)
+  unsigned key_bits = 1;
+  while (key_bits < 32 && (1ull << key_bits) < (unsigned long long)kScales * plan.rows[0] * plan.cols[0]) ++key_bits;
+  return key_bits;
+}
+}  // namespace
+
+unsigned sift_own_prefix(const SiftPlan& plan, unsigned epoch) {
+  const unsigned key_bits = sift_key_bits(plan);
+  return key_bits >= 32 ? 0u : epoch << key_bits;
+}
+
+namespace {
 
 // launch_sift / launch_sift_batch: n images (n = 1: `grays` holds the one) in one launch per stage
 void launch_sift_images(const uint8_t* const* grays, int n, int width, int height, int double_size, const SiftPlan& plan,
@@ -1444,15 +1459,14 @@ void launch_sift_images(const uint8_t* const* grays, int n, int width, int heigh
   }
   // (the counters are cleared by prepare_kernel; the owner map is not cleared at all: SiftBatch::own_prefix)
   {
-    unsigned key_bits = 1;
-    while (key_bits < 32 && (1ull << key_bits) < (unsigned long long)kScales * plan.rows[0] * plan.cols[0]) ++key_bits;
-    const unsigned n_prefix = key_bits >= 31 ? 1u : 1u << (32 - key_bits);   // (a key is below kScales rows cols of octave 0)
+    const unsigned key_bits = sift_key_bits(plan);
+    const unsigned n_prefix = key_bits >= 31 ? 1u : 1u << (32 - key_bits);
     if (*B.own_epoch == 0 || n_prefix == 1) {
       hipMemsetAsync(B.owner, 0xFF, B.owner_elems * sizeof(unsigned int) * B.images, s);
       *B.own_epoch = n_prefix;
     }
     --*B.own_epoch;
-    Bt.own_prefix = key_bits >= 32 ? 0u : *B.own_epoch << key_bits;
+    Bt.own_prefix = sift_own_prefix(plan, *B.own_epoch);
   }
 
   const SiftOctave& O0 = P.oct[0];
@@ -1664,6 +1678,77 @@ void launch_sift_batch(const uint8_t* const* gray, int n, int width, int height,
   }
   launch_sift_images(gray, n, width, height, double_size, plan, B, out_cap, out_step, desc_out, xy_out, scale_ori_out,
                      n_out, n_out_step, s);
+}
+
+// One blur level through a named kernel (sift.h): the launches launch_sift_images makes for a level, on one image.
+int launch_sift_blur_variant(int variant, const float* src, int src_rows, int src_cols, float sigma, int half, float* dst,
+                             float* dog, float* half_dst, float* scratch, hipStream_t s) {
+  if (variant < 0 || variant > 4 || !src || !dst || src_rows <= 0 || src_cols <= 0) return 1;
+  const int rows = half ? src_rows >> 1 : src_rows, cols = half ? src_cols >> 1 : src_cols;
+  if (rows <= 0 || cols <= 0) return 1;
+  const dim3 tb(256), grid((cols + 255) / 256, rows, 1);
+  if (variant == 3) {   // HalfImageSize alone
+    if (!half || dog || half_dst) return 1;
+    hipLaunchKernelGGL(half_kernel, grid, tb, 0, s, src, src_cols, dst, rows, cols, (size_t)0);
+    return 0;
+  }
+  if (!(sigma > 0.f) || !(2.0f * 4.0f * sigma + 1.0f < (float)(MAX_TAPS - 1))) return 1;   // (make_taps would cut the kernel short)
+  const Taps t = make_taps(sigma);
+  const int w = t.n >> 1;
+  if (half && (variant != 2 || !half_dst)) return 1;   // only the tile kernel's jobs read the previous octave
+  if (!half && half_dst) return 1;
+  switch (variant) {
+    case 0:
+      if (!scratch) return 1;
+      hipLaunchKernelGGL(blur_rows_kernel, grid, tb, 0, s, src, scratch, rows, cols, t);
+      hipLaunchKernelGGL(blur_cols_kernel, grid, tb, 0, s, (const float*)scratch, dst, rows, cols, t, src, dog);
+      return 0;
+    case 1:
+      if (w > BT_MAXW) return 1;
+      hipLaunchKernelGGL(blur_level_kernel, dim3((cols + BT_X - 1) / BT_X, (rows + BT_Y - 1) / BT_Y), dim3(BT_THREADS), 0, s,
+                         src, dst, rows, cols, t, src, dog);
+      return 0;
+    case 2: {
+      if (w > BT_MAXW) return 1;
+      BlurJobs J;
+      J.n = 1;
+      BlurJob& b = J.j[0];
+      b.src = src;
+      b.dst = dst;
+      b.dog = dog;
+      b.half_dst = half ? half_dst : nullptr;
+      b.rows = rows;
+      b.cols = cols;
+      b.src_cols = src_cols;
+      b.half = half ? 1 : 0;
+      b.taps = 0;
+      b.tiles_x = (cols + BT_X - 1) / BT_X;
+      b.tile_begin = 0;
+      b.src_step = b.pyr_step = 0;
+      J.j[1] = b;
+      J.t[0] = J.t[1] = t;
+      hipLaunchKernelGGL(blur_jobs_kernel, dim3(b.tiles_x * ((rows + BT_Y - 1) / BT_Y), 1), dim3(BT_THREADS), 0, s, J);
+      return 0;
+    }
+    default: {   // 4: the single-workgroup chain on a pyramid of one octave whose five levels all use this kernel
+      const size_t px = (size_t)rows * cols;
+      if (px > (size_t)SO_CAP || !dog || !scratch) return 1;
+      SiftPyramid P;
+      memset(&P, 0, sizeof P);
+      P.n_octaves = 1;
+      P.oct[0].rows = rows;
+      P.oct[0].cols = cols;
+      P.oct[0].gaus[0] = const_cast<float*>(src);   // (octave 0's first level is only read)
+      for (int i = 1; i < kScales + 3; ++i) {
+        P.oct[0].gaus[i] = i == 1 ? dst : scratch + (size_t)(2 * (i - 2)) * px;
+        P.oct[0].dog[i - 1] = i == 1 ? dog : scratch + (size_t)(2 * (i - 2) + 1) * px;
+      }
+      Taps5 T5;
+      for (int i = 0; i < kScales + 2; ++i) T5.t[i] = t;
+      hipLaunchKernelGGL(small_octaves_kernel, dim3(1), dim3(1024), 0, s, P, 0, T5, (size_t)0);
+      return 0;
+    }
+  }
 }
 
 }  // namespace mh

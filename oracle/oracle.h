@@ -206,6 +206,25 @@ int orc_sift(const uint8_t* gray, int w, int h, int double_size, float* xy, floa
 /* One pyramid image of that run: kind 0 = Gaussian i, 1 = DoG i of `octave`. */
 int orc_sift_image(const uint8_t* gray, int w, int h, int double_size, int octave, int kind, int i,
                    float* out, int* rows, int* cols);
+/* Every stage of ONE run (the same run_sift): the handle keeps the whole pyramid, every scan hit that reached
+ * InterpKeyPoint in generation order and the orientation peaks of the hits that took their pixel.
+ *   octaves: rows / cols per octave, returns their number;  level: kind 0 = Gaussian i (0..5), 1 = DoG i (0..4);
+ *   hits:  ints [n][10] = octave, scale index, start r, start c, final r, final c, passed the final test, took the
+ *          pixel, first peak, number of peaks;  floats [n][7] = X0, X1, X2, val, fSize, frow, fcol (the last three
+ *          only where the pixel was taken);
+ *   peaks: hit_bin [m][2] = hit, histogram bin;  ang [m] = interpolated angle; in the order AssignOriHist emits them.
+ * hits / peaks return the total number and write at most `cap`. */
+void* orc_sift_run(const uint8_t* gray, int w, int h, int double_size);
+void orc_sift_run_free(void* run);
+int orc_sift_run_octaves(const void* run, int* rows, int* cols, int cap);
+int orc_sift_run_level(const void* run, int octave, int kind, int i, float* out);
+int orc_sift_run_hits(const void* run, int32_t* ints, float* floats, int cap);
+int orc_sift_run_peaks(const void* run, int32_t* hit_bin, float* ang, int cap);
+/* The pieces of the blur chain on their own: GaussianBlur's tap count for a sigma, GaussianBlur (rows x cols -> the
+ * same size), HalfImageSize (rows x cols -> rows / 2 x cols / 2). */
+int orc_sift_taps(float sigma);
+void orc_sift_blur(const float* src, int rows, int cols, float sigma, float* dst);
+void orc_sift_half(const float* src, int rows, int cols, float* dst);
 
 /* moped3d's DEPTHFILL step, DEPTH_FILL_EXACT_CPU::fillInScaled
  * (moped3d/libmoped/src/depthfill/DEPTH_FILL_EXACT_CPU.hpp:268-349; see depthfill_oracle.cpp): depth [h][w][4]

@@ -662,6 +662,100 @@ def sift_image(gray, octave, kind, i, double_size=True):
     return out
 
 
+class SiftRun:
+    """Every stage of one oracle run (orc_sift_run): .octaves = [(rows, cols)], .level(o, kind, i), .hits (structured
+    array in generation order), .peaks (hit, bin, ang)."""
+    HIT = np.dtype([("octave", "<i4"), ("index", "<i4"), ("r0", "<i4"), ("c0", "<i4"), ("r", "<i4"), ("c", "<i4"),
+                    ("passed", "<i4"), ("took", "<i4"), ("first_peak", "<i4"), ("n_peaks", "<i4"),
+                    ("x0", "<f4"), ("x1", "<f4"), ("x2", "<f4"), ("val", "<f4"), ("fsize", "<f4"), ("frow", "<f4"),
+                    ("fcol", "<f4")])
+    PEAK = np.dtype([("hit", "<i4"), ("bin", "<i4"), ("ang", "<f4")])
+    _run = None
+
+    def __init__(self, gray, double_size=True):
+        g = _c(gray, np.uint8)
+        h, w = g.shape
+        L = lib()
+        L.orc_sift_run.restype = C.c_void_p
+        L.orc_sift_run.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.orc_sift_run_free.restype = None
+        L.orc_sift_run_free.argtypes = [C.c_void_p]
+        L.orc_sift_run_octaves.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.orc_sift_run_level.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.orc_sift_run_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.orc_sift_run_peaks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        self.double_size = bool(double_size)
+        self._L = L
+        self._run = run = L.orc_sift_run(g.ctypes.data, w, h, int(double_size))
+        rows, cols = np.zeros(32, np.int32), np.zeros(32, np.int32)
+        n = L.orc_sift_run_octaves(run, rows.ctypes.data, cols.ctypes.data, 32)
+        self.octaves = [(int(rows[o]), int(cols[o])) for o in range(n)]
+        nh = L.orc_sift_run_hits(run, None, None, 0)
+        ints, flts = np.zeros((max(nh, 1), 10), np.int32), np.zeros((max(nh, 1), 7), np.float32)
+        L.orc_sift_run_hits(run, ints.ctypes.data, flts.ctypes.data, nh)
+        self.hits = np.zeros(nh, self.HIT)
+        for k, name in enumerate(self.HIT.names[:10]):
+            self.hits[name] = ints[:nh, k]
+        for k, name in enumerate(self.HIT.names[10:]):
+            self.hits[name] = flts[:nh, k]
+        npk = L.orc_sift_run_peaks(run, None, None, 0)
+        hb, ang = np.zeros((max(npk, 1), 2), np.int32), np.zeros(max(npk, 1), np.float32)
+        L.orc_sift_run_peaks(run, hb.ctypes.data, ang.ctypes.data, npk)
+        self.peaks = np.zeros(npk, self.PEAK)
+        self.peaks["hit"], self.peaks["bin"], self.peaks["ang"] = hb[:npk, 0], hb[:npk, 1], ang[:npk]
+
+    def close(self):
+        if self._run:
+            self._L.orc_sift_run_free(self._run)
+            self._run = None
+
+    __del__ = close
+
+    def level(self, octave, kind, i):
+        """Gaussian (kind 0, i = 0..5) / DoG (kind 1, i = 0..4) image of `octave`: a copy, float32 [rows, cols]."""
+        out = np.zeros(self.octaves[octave], np.float32)
+        if self._L.orc_sift_run_level(self._run, octave, kind, i, out.ctypes.data) != out.size:
+            raise IndexError((octave, kind, i))
+        return out
+
+    def keys(self):
+        """The keypoints the hits and peaks stand for, in the reference's list order (generation order reversed):
+        (xy [n,2] = (col,row), scale_ori [n,2]) as make_key scales them."""
+        h = self.hits[self.peaks["hit"]]
+        fscale = (np.float32(0.5 if self.double_size else 1.0) * np.exp2(h["octave"]).astype(np.float32)).astype(np.float32)
+        xy = np.stack([fscale * h["fcol"], fscale * h["frow"]], 1).astype(np.float32)
+        so = np.stack([fscale * h["fsize"], self.peaks["ang"]], 1).astype(np.float32)
+        return xy[::-1].copy(), so[::-1].copy()
+
+
+def sift_taps(sigma):
+    L = lib()
+    L.orc_sift_taps.argtypes = [C.c_float]
+    return int(L.orc_sift_taps(sigma))
+
+
+def sift_blur(img, sigma):
+    """GaussianBlur (blur()) of a float32 image."""
+    a = _c(img, np.float32)
+    out = np.zeros_like(a)
+    L = lib()
+    L.orc_sift_blur.restype = None
+    L.orc_sift_blur.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]
+    L.orc_sift_blur(a.ctypes.data, a.shape[0], a.shape[1], sigma, out.ctypes.data)
+    return out
+
+
+def sift_half(img):
+    """HalfImageSize: every second row and column."""
+    a = _c(img, np.float32)
+    out = np.zeros((a.shape[0] >> 1, a.shape[1] >> 1), np.float32)
+    L = lib()
+    L.orc_sift_half.restype = None
+    L.orc_sift_half.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.orc_sift_half(a.ctypes.data, a.shape[0], a.shape[1], out.ctypes.data)
+    return out
+
+
 def ref_sift(gray, cap=16384):
     """The reference's own libsiftfast build (oracle/_ref), called like FEAT_SIFT_CPU does."""
     g = _c(gray, np.uint8)

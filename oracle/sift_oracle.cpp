@@ -270,9 +270,24 @@ void smooth_hist(float* h, int n) {
   h[n - 1] = (prev + h[n - 1] + first) * 0.3333333f;
 }
 
+// What a run shows of its stages (orc_sift_run): every scan hit that reached interp_key, in generation order, and the
+// orientation peaks of the ones that took their pixel, in the order assign_ori emits them.
+struct Hit {
+  int octave, index, r0, c0, r, c, passed, took, first_peak, n_peaks;
+  float X[3], val, fsize, frow, fcol;
+};
+struct Peak {
+  int hit, bin;
+  float ang;
+};
+struct Trace {
+  std::vector<Hit> hits;
+  std::vector<Peak> peaks;
+};
+
 // AssignOriHist (:1274-1382)
 void assign_ori(std::vector<Key>& out, const Img& grad, const Img& orim, float fscale, float fSize, float frow,
-                float fcol) {
+                float fcol, Trace* trace) {
   const int rowstart = (int)(frow + 0.5f), colstart = (int)(fcol + 0.5f);
   const int rows = grad.rows, cols = grad.cols;
   float hist[36];
@@ -313,14 +328,20 @@ void assign_ori(std::vector<Key>& out, const Img& grad, const Img& orim, float f
       f2 = -f2;
     }
     const float peak = 0.5f * (f0 - f2) / (f0 - 2.0f * f1 + f2);
-    make_key(out, grad, orim, fscale, fSize, frow, fcol, (i + peak) * forimult + foriadd);
+    const float forient = (i + peak) * forimult + foriadd;
+    if (trace) {
+      trace->peaks.push_back(Peak{(int)trace->hits.size() - 1, i, forient});
+      ++trace->hits.back().n_peaks;
+    }
+    make_key(out, grad, orim, fscale, fSize, frow, fcol, forient);
   }
 }
 
 // InterpKeyPoint (:1164-1206): the recursion as a loop
 void interp_key(std::vector<Key>& out, const Img* dog, int index, int r, int c, const Img& grad, const Img& orim,
-                std::vector<char>& taken, float fscale, float peak_thresh) {
+                std::vector<char>& taken, float fscale, float peak_thresh, int octave, Trace* trace) {
   const int rows = dog[0].rows, cols = dog[0].cols;
+  const int r_start = r, c_start = c;
   float X[3], val = 0;
   for (int steps = 5;; --steps) {
     val = fit_quadratic(X, dog, index, r, c);
@@ -336,12 +357,36 @@ void interp_key(std::vector<Key>& out, const Img* dog, int index, int r, int c, 
     }
     break;
   }
+  if (trace) {
+    Hit h;
+    memset(&h, 0, sizeof h);
+    h.octave = octave;
+    h.index = index;
+    h.r0 = r_start;
+    h.c0 = c_start;
+    h.r = r;
+    h.c = c;
+    h.X[0] = X[0];
+    h.X[1] = X[1];
+    h.X[2] = X[2];
+    h.val = val;
+    h.first_peak = (int)trace->peaks.size();
+    trace->hits.push_back(h);
+  }
   if (fabsf(X[0]) <= 1.5f && fabsf(X[1]) <= 1.5f && fabsf(X[2]) <= 1.5f && fabsf(val) >= peak_thresh) {
+    if (trace) trace->hits.back().passed = 1;
     char& t = taken[(size_t)r * cols + c];
     if (!t) {
       t = 1;
       const float fSize = kInitSigma * powf(2.0f, ((float)index + X[0]) / (float)kScales);
-      assign_ori(out, grad, orim, fscale, fSize, (float)r + X[1], (float)c + X[2]);
+      if (trace) {
+        Hit& h = trace->hits.back();
+        h.took = 1;
+        h.fsize = fSize;
+        h.frow = (float)r + X[1];
+        h.fcol = (float)c + X[2];
+      }
+      assign_ori(out, grad, orim, fscale, fSize, (float)r + X[1], (float)c + X[2], trace);
     }
   }
 }
@@ -350,10 +395,19 @@ struct Pyramid {
   std::vector<std::vector<Img>> gaus, dog;  // [octave][i]
 };
 
+// HalfImageSize (:390-408)
+Img half_size(const Img& src) {
+  Img half(src.rows >> 1, src.cols >> 1);
+  for (int r = 0; r < half.rows; ++r)
+    for (int c = 0; c < half.cols; ++c) half.at(r, c) = src.at(2 * r, 2 * c);
+  return half;
+}
+
 // GetKeypoints / OctaveKeypoints / FindMaxMin (:301-361, :410-438, :891-957).  Keypoints come
 // out in GENERATION order (octave, scale index, row, column, histogram peak ascending); the
 // reference's linked list is that order reversed (every new key is pushed on the front).
-void run_sift(const uint8_t* gray, int w, int h, int double_size, std::vector<Key>& keys, Pyramid* pyr) {
+void run_sift(const uint8_t* gray, int w, int h, int double_size, std::vector<Key>& keys, Pyramid* pyr,
+              Trace* trace = nullptr) {
   const float peak_thresh = 0.04f / (float)kScales;
   Img org(h, w);
   for (int y = 0; y < h; ++y)
@@ -381,6 +435,7 @@ void run_sift(const uint8_t* gray, int w, int h, int double_size, std::vector<Ke
   }
   const float fwidth = powf(2.0f, 1.0f / (float)kScales);
   const float fincsigma = sqrtf(fwidth * fwidth - 1.0f);
+  int octave = 0;
   while (cur.rows > 12 && cur.cols > 12) {
     std::vector<Img> gaus(kScales + 3), dog(kScales + 2);
     gaus[0] = cur;
@@ -402,19 +457,17 @@ void run_sift(const uint8_t* gray, int w, int h, int double_size, std::vector<Ke
           if (fabsf(v) > peak_thresh * 0.8f && local_extremum(v, dog[index], r, c) &&
               local_extremum(v, dog[index - 1], r, c) && local_extremum(v, dog[index + 1], r, c) &&
               not_on_edge(dog[index], r, c))
-            interp_key(keys, dog.data(), index, r, c, grad, orim, taken, fscale, peak_thresh);
+            interp_key(keys, dog.data(), index, r, c, grad, orim, taken, fscale, peak_thresh, octave, trace);
         }
     }
-    // HalfImageSize of gaus[Scales] (:390-408)
-    Img half(rows >> 1, cols >> 1);
-    for (int r = 0; r < half.rows; ++r)
-      for (int c = 0; c < half.cols; ++c) half.at(r, c) = gaus[kScales].at(2 * r, 2 * c);
+    Img half = half_size(gaus[kScales]);
     if (pyr) {
       pyr->gaus.push_back(gaus);
       pyr->dog.push_back(dog);
     }
     cur = half;
     fscale += fscale;
+    ++octave;
   }
 }
 
@@ -454,6 +507,80 @@ int orc_sift_image(const uint8_t* gray, int w, int h, int double_size, int octav
   *cols = v[i].cols;
   if (out) memcpy(out, v[i].px.data(), v[i].px.size() * sizeof(float));
   return (int)v[i].px.size();
+}
+
+// ---- one run, every stage (tests/test_sift_stages_cpu.py, tests/test_gpu_sift_stages.py) ----
+struct SiftRun {
+  Pyramid pyr;
+  Trace trace;
+  std::vector<Key> keys;
+};
+
+void* orc_sift_run(const uint8_t* gray, int w, int h, int double_size) {
+  SiftRun* R = new SiftRun;
+  run_sift(gray, w, h, double_size, R->keys, &R->pyr, &R->trace);
+  return R;
+}
+
+void orc_sift_run_free(void* run) { delete static_cast<SiftRun*>(run); }
+
+int orc_sift_run_octaves(const void* run, int* rows, int* cols, int cap) {
+  const SiftRun* R = static_cast<const SiftRun*>(run);
+  const int n = (int)R->pyr.gaus.size();
+  for (int o = 0; o < n && o < cap; ++o) {
+    rows[o] = R->pyr.gaus[o][0].rows;
+    cols[o] = R->pyr.gaus[o][0].cols;
+  }
+  return n;
+}
+
+int orc_sift_run_level(const void* run, int octave, int kind, int i, float* out) {
+  const SiftRun* R = static_cast<const SiftRun*>(run);
+  if (octave < 0 || octave >= (int)R->pyr.gaus.size()) return 0;
+  const std::vector<Img>& v = kind == 0 ? R->pyr.gaus[octave] : R->pyr.dog[octave];
+  if (i < 0 || i >= (int)v.size()) return 0;
+  memcpy(out, v[i].px.data(), v[i].px.size() * sizeof(float));
+  return (int)v[i].px.size();
+}
+
+int orc_sift_run_hits(const void* run, int32_t* ints, float* floats, int cap) {
+  const SiftRun* R = static_cast<const SiftRun*>(run);
+  const int n = (int)R->trace.hits.size();
+  for (int i = 0; i < n && i < cap; ++i) {
+    const Hit& h = R->trace.hits[i];
+    const int32_t iv[10] = {h.octave, h.index, h.r0, h.c0, h.r, h.c, h.passed, h.took, h.first_peak, h.n_peaks};
+    const float fv[7] = {h.X[0], h.X[1], h.X[2], h.val, h.fsize, h.frow, h.fcol};
+    memcpy(ints + (size_t)10 * i, iv, sizeof iv);
+    memcpy(floats + (size_t)7 * i, fv, sizeof fv);
+  }
+  return n;
+}
+
+int orc_sift_run_peaks(const void* run, int32_t* hit_bin, float* ang, int cap) {
+  const SiftRun* R = static_cast<const SiftRun*>(run);
+  const int n = (int)R->trace.peaks.size();
+  for (int i = 0; i < n && i < cap; ++i) {
+    hit_bin[2 * i] = R->trace.peaks[i].hit;
+    hit_bin[2 * i + 1] = R->trace.peaks[i].bin;
+    ang[i] = R->trace.peaks[i].ang;
+  }
+  return n;
+}
+
+int orc_sift_taps(float sigma) { return (int)gauss_kernel(sigma).size(); }
+
+void orc_sift_blur(const float* src, int rows, int cols, float sigma, float* dst) {
+  Img s(rows, cols), d;
+  memcpy(s.px.data(), src, s.px.size() * sizeof(float));
+  blur(d, s, sigma);
+  memcpy(dst, d.px.data(), d.px.size() * sizeof(float));
+}
+
+void orc_sift_half(const float* src, int rows, int cols, float* dst) {
+  Img s(rows, cols);
+  memcpy(s.px.data(), src, s.px.size() * sizeof(float));
+  const Img d = half_size(s);
+  memcpy(dst, d.px.data(), d.px.size() * sizeof(float));
 }
 
 }  // extern "C"
