@@ -167,6 +167,24 @@ int mh_screen_values(mh_ctx* ctx, const float* q_host, int Q, int n_rows, float*
 uint16_t mh_screen_record_value(float top, float thr);
 void mh_screen_record_bounds(uint16_t value_bits, uint32_t row0, float tau, float spread, int N, float dmax, float* lo,
                              float* hi);
+/* The one-sweep launches (pass A of the large launches keeps the identity of its best 8-row blocks, pass B leaves the
+ * sampled tiles out); host arithmetic for tests, the same inline functions the kernels run:
+ *   mh_screen_pack_value    a block's largest screen value with the block's number `id` in its low `bits` mantissa bits
+ *   mh_screen_pack_pert     a bound of |packed - value| for every screen value of a query with dot(q,q) = qq
+ *   mh_screen_sample_bounds what pass C concludes from the record of a sampled tile's block (value_bits = f16 of packed
+ *                           value - tau): *lo <= the block's largest screen value <= *hi
+ *   mh_screen_launch_plan   how a two-stage MATCH of Q queries (q_expected of them expected, 0 = Q) against N rows is
+ *                           launched: out = {1 if one sweep, first sampled tile, sampling stride, sampled tiles, pass A
+ *                           splits, identity bits, pass B splits, pass B tiles}; all zero when the launch does not run
+ *                           on the 16x16x32 passes
+ *   mh_match_incomplete     queries since the last reset for which a lane slot of pass A held more blocks above the
+ *                           threshold than it keeps, so that pass C swept that slot's rows (bounded; never the brute-force
+ *                           search mh_match_stats counts).  Synchronises the context's stream. */
+float mh_screen_pack_value(float v, uint32_t id, int bits);
+float mh_screen_pack_pert(float qq, float dmax, int bits);
+void mh_screen_sample_bounds(uint16_t value_bits, float tau, float pert, float dmax, float* lo, float* hi);
+void mh_screen_launch_plan(int Q, int q_expected, int N, int32_t out[8]);
+int mh_match_incomplete(mh_ctx* ctx, uint32_t* count, int reset);
 
 /* Device-pointer forms for a model-sharded DB: local top-2 of this shard
  * (idx carries index_base; -1 when the shard is empty), then the merge of S

@@ -124,6 +124,7 @@ EXPORTS = [
     "mh_undistort_map", "mh_undistort", "mh_undistort_dev", "mh_frame_set_undistort",
     "mh_sift_extract_batch_dev", "mh_sift_debug_plan", "mh_sift_debug_level", "mh_sift_debug_candidates",
     "mh_sift_debug_keys", "mh_sift_debug_blur",
+    "mh_screen_pack_value", "mh_screen_pack_pert", "mh_screen_sample_bounds", "mh_screen_launch_plan", "mh_match_incomplete",
 ]
 COMM_ID_BYTES = 128      # MH_COMM_ID_BYTES
 EX2_OBJECTS = 62         # MH_EX2_OBJECTS
@@ -284,6 +285,16 @@ def load():
     L.mh_screen_record_value.restype = C.c_uint16
     L.mh_screen_record_bounds.argtypes = [C.c_uint16, C.c_uint32, f32, f32, i32, f32, C.POINTER(f32), C.POINTER(f32)]
     L.mh_screen_record_bounds.restype = None
+    if hasattr(L, "mh_screen_pack_value"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
+        L.mh_screen_pack_value.argtypes = [f32, C.c_uint32, i32]
+        L.mh_screen_pack_value.restype = f32
+        L.mh_screen_pack_pert.argtypes = [f32, f32, i32]
+        L.mh_screen_pack_pert.restype = f32
+        L.mh_screen_sample_bounds.argtypes = [C.c_uint16, f32, f32, f32, C.POINTER(f32), C.POINTER(f32)]
+        L.mh_screen_sample_bounds.restype = None
+        L.mh_screen_launch_plan.argtypes = [i32, i32, i32, vp]
+        L.mh_screen_launch_plan.restype = None
+        L.mh_match_incomplete.argtypes = [vp, C.POINTER(C.c_uint32), i32]
     L.mh_db_upload_blocks.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, i32, i32]
     L.mh_frame_block_stride.argtypes = [i32]
     L.mh_frame_block_stride.restype = C.c_size_t
@@ -375,6 +386,22 @@ def screen_record_bounds(value_bits, row0, tau, spread, N, dmax):
     load().mh_screen_record_bounds(int(value_bits), int(row0), float(tau), float(spread), int(N), float(dmax),
                                    C.byref(lo), C.byref(hi))
     return lo.value, hi.value
+
+
+def screen_sample_bounds(value_bits, tau, pert, dmax):
+    """mh_screen_sample_bounds (host arithmetic): (lo, hi) of the largest screen value of a sampled tile's block."""
+    lo, hi = C.c_float(0), C.c_float(0)
+    load().mh_screen_sample_bounds(int(value_bits), float(tau), float(pert), float(dmax), C.byref(lo), C.byref(hi))
+    return lo.value, hi.value
+
+
+def screen_launch_plan(Q, N, q_expected=0) -> dict:
+    """mh_screen_launch_plan (host arithmetic): how a two-stage MATCH of Q queries against N rows is launched; all zero
+    when it does not run on the 16x16x32 passes."""
+    o = np.zeros(8, np.int32)
+    load().mh_screen_launch_plan(int(Q), int(q_expected), int(N), _ptr(o))
+    keys = ("onesweep", "tile_first", "tile_stride", "sampled_tiles", "splits_a", "pack_bits", "splits_b", "tiles_b")
+    return {k: int(v) for k, v in zip(keys, o)}
 
 
 FRAME_HEAD_DTYPE = np.dtype([("n_objects", "<i4"), ("flags", "<i4"), ("counts", "<i4", (4,)), ("tag", "<u4"), ("frame", "<i4")])
@@ -603,6 +630,13 @@ class Context:
         self._ck(self.L.mh_match_stats(self.h, int(Q), _ptr(st), int(reset)), "mh_match_stats")
         return {"candidates": int(st[0]), "brute_force_queries": int(st[1]), "queries": int(st[2]),
                 "two_stage": bool(st[3])}
+
+    def match_incomplete(self, reset=False) -> int:
+        """Queries since the last reset whose sampled-tile records were incomplete and that took pass C's bounded
+        sweep of a lane slot's rows instead (mh_match_incomplete)."""
+        n = C.c_uint32(0)
+        self._ck(self.L.mh_match_incomplete(self.h, C.byref(n), int(reset)), "mh_match_incomplete")
+        return int(n.value)
 
     def normalize(self, desc):
         d = np.ascontiguousarray(desc, np.float32).copy()

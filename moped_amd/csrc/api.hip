@@ -44,7 +44,7 @@ int ensure_pinned(mh_ctx* ctx, size_t bytes) {
 
 static void free_screen_bufs(mh_ctx* ctx) {
   ScreenBufs& b = ctx->sbuf;
-  for (void* p : {(void*)b.qh, (void*)b.qbad, (void*)b.part, (void*)b.tau, (void*)b.ovf_cnt, (void*)b.recs, (void*)b.ovf, (void*)b.stats})
+  for (void* p : {(void*)b.qh, (void*)b.qbad, (void*)b.part, (void*)b.tau, (void*)b.ovf_cnt, (void*)b.recs, (void*)b.ovf, (void*)b.stats, (void*)b.inc})
     if (p) hipFree(p);
   b = ScreenBufs();
 }
@@ -95,12 +95,14 @@ int ensure_match_scratch(mh_ctx* ctx, int Q) {
     const size_t slots = (size_t)q_pad * screen_rec_slots();
     MH_HIP(ctx, hipMalloc(&b.qh, (size_t)q_pad * DIM * sizeof(_Float16)));
     MH_HIP(ctx, hipMalloc(&b.qbad, (size_t)q_pad));
-    MH_HIP(ctx, hipMalloc(&b.part, (size_t)screen_max_splits_a() * q_pad * sizeof(float2)));
+    MH_HIP(ctx, hipMalloc(&b.part, screen_part_bytes(q_pad)));
     MH_HIP(ctx, hipMalloc(&b.tau, (size_t)q_pad * sizeof(float)));
     MH_HIP(ctx, hipMalloc(&b.recs, slots * sizeof(uint2)));
     MH_HIP(ctx, hipMalloc(&b.ovf_cnt, (size_t)q_pad * sizeof(int32_t)));
     MH_HIP(ctx, hipMalloc(&b.ovf, (size_t)q_pad * SCREEN_OVF_CAP * sizeof(uint2)));
     MH_HIP(ctx, hipMalloc(&b.stats, (size_t)q_pad * 3 * sizeof(unsigned int)));
+    MH_HIP(ctx, hipMalloc(&b.inc, ((size_t)q_pad + 1) * sizeof(unsigned int)));
+    MH_HIP(ctx, hipMemsetAsync(b.inc, 0, ((size_t)q_pad + 1) * sizeof(unsigned int), ctx->stream));
     MH_HIP(ctx, hipMemsetAsync(b.recs, 0, slots * sizeof(uint2), ctx->stream));
     MH_HIP(ctx, hipMemsetAsync(b.ovf_cnt, 0, (size_t)q_pad * sizeof(int32_t), ctx->stream));
     MH_HIP(ctx, hipMemsetAsync(b.stats, 0, (size_t)q_pad * 3 * sizeof(unsigned int), ctx->stream));
@@ -616,6 +618,37 @@ void mh_screen_record_bounds(uint16_t value_bits, uint32_t row0, float tau, floa
   screen_record_bounds(value_bits, row0, tau, spread, N, dmax, l, h);
   if (lo) *lo = l;
   if (hi) *hi = h;
+}
+
+float mh_screen_pack_value(float v, uint32_t id, int bits) { return screen_pack_value(v, id, bits); }
+
+float mh_screen_pack_pert(float qq, float dmax, int bits) { return screen_pack_pert(qq, dmax, bits); }
+
+void mh_screen_sample_bounds(uint16_t value_bits, float tau, float pert, float dmax, float* lo, float* hi) {
+  float l, h;
+  screen_sample_bounds(value_bits, tau, pert, dmax, l, h);
+  if (lo) *lo = l;
+  if (hi) *hi = h;
+}
+
+void mh_screen_launch_plan(int Q, int q_expected, int N, int32_t out[8]) {
+  int v[8];
+  screen_launch_plan(Q, q_expected, N, v);
+  for (int k = 0; k < 8; ++k) out[k] = v[k];
+}
+
+int mh_match_incomplete(mh_ctx* ctx, uint32_t* count, int reset) {
+  if (!ctx || !count) return MH_ERR_ARG;
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *count = 0;
+  if (ctx->sbuf.inc) {
+    unsigned int* c = ctx->sbuf.inc + ctx->sbuf.q_pad;
+    MH_HIP(ctx, hipMemcpy(count, c, sizeof(unsigned int), hipMemcpyDeviceToHost));
+    if (reset) MH_HIP(ctx, hipMemset(c, 0, sizeof(unsigned int)));
+  }
+  return MH_OK;
 }
 
 int mh_screen_values(mh_ctx* ctx, const float* q_host, int Q, int n_rows, float* out_host, float* dmax, float* spread,

@@ -239,7 +239,10 @@ __global__ void screen_prepare_kernel(const float* __restrict__ qn, const float*
 //                  row0 + (r & 3) + 8 (r >> 2) for the set bits r.  A lane owns the sub-list (query, split, half)
 //                  -- `sub_cap` slots nobody else writes, no atomics; a sub-list that is full spills into the
 //                  query's overflow list (atomic append, rare).  bits = 0 marks an empty slot.
-constexpr int SC_SLOTS_MAX = 256;   // record slots per query: 2 halves x splits x sub_cap <= this
+constexpr int SC_SLOTS_MAX = 256;   // pass B's record slots per query: 2 halves x splits x sub_cap <= this
+// ... and behind them the slots of the records pass A's sampled tiles leave (screen_handover_kernel; the one-sweep launches)
+constexpr int SC_SA_SLOTS = 32;
+constexpr int SC_SLOT_PITCH = SC_SLOTS_MAX + SC_SA_SLOTS;
 
 #ifdef SC_PROF   // experiment build (make EXTRA=-DSC_PROF ...): switch parts of passes A/B off (results are wrong then)
 // and stamp a workgroup's time; scripts/screen_prof.py
@@ -260,7 +263,8 @@ struct ScreenArgs {
   const float* qnorm;
   const uint8_t* qbad;
   const int32_t* q_count;
-  float2* part;          // pass A's output, [n_splits_a][q_pad]
+  float2* part;          // pass A's output, [n_splits_a][q_pad] (screen_kernel)
+  float* part5;          // ... of screen16_kernel: [n_splits_a x 4 quarters][SC_TOPK + 1][q_pad], the same memory
   const float* tau;      // pass B's input, [q_pad] (screen_tau_kernel)
   uint2* recs;           // [q_pad][SC_SLOTS_MAX], empty (bits 0) on entry of pass B (pass C re-empties)
   int32_t* ovf_cnt;      // [q_pad], zero on entry
@@ -269,6 +273,8 @@ struct ScreenArgs {
   int n_sel, tile_first, tile_stride;   // the pass covers tiles tile_first + j * tile_stride, j < n_sel
   int tiles_base, tiles_rem, n_splits;  // split s takes tiles_base selected tiles, the first tiles_rem one more
   int n_splits_a;
+  unsigned pack_keep;    // pass A (screen16_kernel): the bits of a block maximum that survive the packing of the block's number
+  int skip_first, skip_stride;   // pass B (screen16_kernel): selected tile j = the j-th tile that is NOT skip_first + i * skip_stride; 0 = no tile is skipped
   float dmax;
   int ablate;            // SC_PROF builds only: 1 = no finish(), 2 = stage only the first tile, 4 = no MFMAs, 8 = no end-of-tile barrier
 };
@@ -300,6 +306,106 @@ __global__ void screen_tau_kernel(const float2* __restrict__ part, int n_splits_
     t = S - screen_margin(qnorm[q], dmax);
   }
   tau[q] = t;
+}
+
+// ---- pass A of the one-sweep launches: the sampled tiles' blocks that can matter, kept by identity -----------------
+// screen16_kernel's pass A keeps, per LANE SLOT (split x quarter: the rows one lane sees of one query), the SC_TOPK
+// largest block maxima with the block each belongs to, and the next largest value: the block's number inside the lane
+// slot (local tile x 4 + row block) replaces the low `bits` mantissa bits of the maximum (screen_pack_value), so the
+// insertion into the sorted list is branch-free (one v_max, SC_TOPK v_med3) and the packed values of a lane slot are
+// all different.  screen_handover_kernel turns the lists into the query's threshold AND into the records of the sampled
+// tiles, so that pass B need not multiply those tiles a second time.  Why that is exact (P = screen_pack_pert: a
+// packed value lies within P of the block maximum it was made from; all lane slots hold different rows):
+//   - T = (second largest packed value over all lists) - P <= the second largest block maximum of the sample <= the
+//     second largest screen value over distinct rows: tau = T - screen_margin is a valid threshold (header);
+//   - a block of a sampled tile whose maximum exceeds tau has a packed value v' > tau - P.  Either v' is among its lane
+//     slot's SC_TOPK largest -- then it becomes a record (all 8 rows of the block, value v' - tau) -- or it is not, and
+//     then the slot's (SC_TOPK + 1)-th value is >= v' > tau - P and the query is marked INCOMPLETE for that lane slot:
+//     pass C runs the canonical chain over the slot's rows instead of its records (none is written for such a slot);
+//   - a padding row's screen value is -inf and a block of padding rows would pack into a NaN: block maxima are floored
+//     at SC_PACK_FLOOR, far below any real row's value, and anything that low counts as "no block" here.
+// tests/test_screen_handover_cpu.py restates the lists and this kernel's decisions against the direct definition.
+constexpr int SC_TOPK = 4;
+constexpr int SC_PART5 = SC_TOPK + 1;           // floats per (lane slot, query) in `part5`
+constexpr int SC_SA_SPLITS_MAX = 28;            // pass A splits of a one-sweep launch: bits 0..27 of a query's incomplete word (28..31: the quarters)
+constexpr int SC_PACK_BITS_MAX = 10;            // block numbers up to 1024 per lane slot: P <= 2^-13 of the largest screen value, a tenth of the margin
+constexpr float SC_PACK_FLOOR = -1e38f;
+constexpr unsigned SC_REC_LAYOUT16 = 0x80000000u;   // in a record's row word: the rows of the 16x16x32 passes
+constexpr unsigned SC_REC_SAMPLE = 0x40000000u; // in a record's row word: made by screen_handover_kernel (value = packed maximum - tau, all 8 rows)
+
+// what pass C has to know about pass A's sweep to find a lane slot's rows again
+struct SampleGeom {
+  int sa_slots;          // 0: no hand-over (pass B swept every tile)
+  int pack_bits;
+  int tile_first, tile_stride, tiles_base, tiles_rem, n_sel;
+};
+
+// One thread per query; the lane slots' values of neighbouring queries are neighbours in memory.
+// tau = +inf for queries that do not exist in this frame or that the screen cannot vouch for (pass B then leaves them
+// no records; pass C searches the latter by brute force).
+__global__ void screen_handover_kernel(const float* __restrict__ part5, int n_lane_slots, int q_pad, int Q,
+                                       const int32_t* __restrict__ q_count, const float* __restrict__ qnorm,
+                                       const uint8_t* __restrict__ qbad, float dmax, SampleGeom g, float* __restrict__ tau,
+                                       uint2* __restrict__ recs, unsigned int* __restrict__ inc) {
+  MH_TRACE_SCOPE(mh::TK_TAU);
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= q_pad) return;
+  const int Qe = q_count ? min(Q, *q_count) : Q;
+  float t = __builtin_inff();
+  unsigned incw = 0;
+  if (q < Qe && !qbad[q]) {
+    auto val = [&](int ls, int k) {
+      const float v = part5[((size_t)ls * SC_PART5 + k) * q_pad + q];
+      return v < 0.5f * SC_PACK_FLOOR ? -__builtin_inff() : v;
+    };
+    float B = -__builtin_inff(), S = -__builtin_inff();
+#pragma unroll 4   // (the kernel is a chain of L2 round trips: four lane slots' loads in flight at a time)
+    for (int ls = 0; ls < n_lane_slots; ++ls) {
+      const float p1 = val(ls, 0), p2 = val(ls, 1);
+      S = fmaxf(fminf(B, p1), fmaxf(S, p2));
+      B = fmaxf(B, p1);
+    }
+    const float P = screen_pack_pert(qnorm[q], dmax, g.pack_bits);
+    t = S - P - screen_margin(qnorm[q], dmax);
+    if (g.sa_slots > 0 && t > -__builtin_inff()) {   // (t = -inf: pass B's lists overflow and pass C searches by brute force)
+      const float thr = t - P;
+      unsigned sm = 0, qm = 0;   // the incomplete lane slots, as (splits) x (quarters): a superset
+#pragma unroll 4
+      for (int ls = 0; ls < n_lane_slots; ++ls)
+        if (val(ls, SC_TOPK) > thr) {
+          sm |= 1u << (ls >> 2);
+          qm |= 1u << (ls & 3);
+        }
+      uint2* mine = recs + (size_t)q * SC_SLOT_PITCH + SC_SLOTS_MAX;
+      const unsigned id_mask = (1u << g.pack_bits) - 1u;
+      int n = 0;
+      bool full = false;
+      for (int ls = 0; ls < n_lane_slots && !full; ++ls) {
+        const int split = ls >> 2, quarter = ls & 3;
+        if (((sm >> split) & 1u) && ((qm >> quarter) & 1u)) continue;   // pass C sweeps this slot's rows
+        for (int k = 0; k < SC_TOPK; ++k) {
+          const float v = val(ls, k);
+          if (!(v > thr)) break;   // the list is sorted
+          if (n == g.sa_slots) {
+            full = true;
+            break;
+          }
+          const unsigned id = __float_as_uint(v) & id_mask;
+          const int sel = split * g.tiles_base + min(split, g.tiles_rem) + (int)(id >> 2);
+          const unsigned row0 = (unsigned)((g.tile_first + sel * g.tile_stride) * SC_TILE + (int)(id & 3u) * 32 + 4 * quarter);
+          mine[n++] = make_uint2(row0 | SC_REC_LAYOUT16 | SC_REC_SAMPLE, 0xFFu | ((unsigned)screen_record_value(v, t) << 16));
+        }
+      }
+      if (full) {   // more records than slots (never seen): every lane slot's rows go to pass C's sweep instead
+        for (int j = 0; j < n; ++j) mine[j] = make_uint2(0u, 0u);
+        sm = (1u << (n_lane_slots >> 2)) - 1u;
+        qm = 0xFu;
+      }
+      if (sm) incw = sm | (qm << 28);
+    }
+  }
+  tau[q] = t;
+  if (inc) inc[q] = incw;
 }
 
 // Four LDS-DMA pieces (1 KB each: 16 bytes per lane to lds_i + lane * 16) in one statement: the source of piece i
@@ -451,7 +557,7 @@ __global__ __launch_bounds__(64 * NW, 2) void screen_kernel(const ScreenArgs A) 
   auto emit = [&](const v16f& acc, int nb, int row0, float top, float thr, int pos) {
     const int q = q0 + nb * 32 + l32;
     if (n_rec[nb] < A.sub_cap) {
-      const unsigned dst = (unsigned)q * SC_SLOTS_MAX + (2 * split + half) * A.sub_cap + n_rec[nb];
+      const unsigned dst = (unsigned)q * SC_SLOT_PITCH + (2 * split + half) * A.sub_cap + n_rec[nb];
       ++n_rec[nb];
       if (pos < SC_RECBUF) {
         uint4* e = recbuf + 5 * pos;
@@ -690,7 +796,6 @@ __global__ __launch_bounds__(64 * NW, 2) void screen_kernel(const ScreenArgs A) 
 // Staging, swizzle (chunk ^ (row & 15): a 16-lane group reads 16 rows at one chunk index -- all 64 banks once), the
 // XCD-aware unit map, the parked records and the exactness argument are those of screen_kernel.
 typedef float v4f __attribute__((ext_vector_type(4)));
-constexpr unsigned SC_REC_LAYOUT16 = 0x80000000u;   // in a record's row word: the rows of the 16x16x32 passes
 constexpr int SC_REC16_BYTES = 48;                  // {slot, row0, thr, top, 8 dots}
 constexpr int SC_RECBUF16 = 8 * 1024 / SC_REC16_BYTES;   // 170 parked hits per wavefront in 8 KB
 constexpr int SC_LDS16_TAU = SC_LDS_TILES + 8 * SC_RECBUF16 * SC_REC16_BYTES;   // the wavefronts' thresholds: 8 x 128 floats
@@ -726,15 +831,29 @@ __global__ __launch_bounds__(512, 2) void screen16_kernel(const ScreenArgs A) {
 
   const unsigned voff = (unsigned)(wave * 1024 + (lane >> 4) * 256 + (((lane & 15) ^ ((wave * 4 + (lane >> 4)) & 15)) << 4));
   const unsigned voff_dd = (unsigned)((wave * 64 + lane) * 4);
-  auto stage = [&](int sel, int buf) {
-    const int tile = A.tile_first + sel * A.tile_stride;
+  // The sweep's tiles.  Pass A: tile_first + sel * tile_stride.  Pass B of a one-sweep launch: the sel-th tile pass A did
+  // NOT see (those are skip_first + i * skip_stride) -- the tile number runs along with `sel`, and `gap` counts the
+  // tiles left before the next one to jump over; the one division is here, in front of the loop.
+  int tile_cur = A.tile_first + sel_begin * A.tile_stride, gap_cur = 0x7FFFFFFF;
+  if (MODE == 1 && A.skip_stride > 1) {
+    const int d = A.skip_stride - 1;
+    if (sel_begin < A.skip_first) {
+      tile_cur = sel_begin;
+      gap_cur = A.skip_first - sel_begin;
+    } else {
+      const int jj = sel_begin - A.skip_first;
+      tile_cur = sel_begin + 1 + jj / d;
+      gap_cur = d - jj % d;
+    }
+  }
+  auto stage = [&](int tile, int buf) {
     const unsigned char* tb = reinterpret_cast<const unsigned char*>(A.dbh) + (size_t)tile * SC_TILE_BYTES;
     const unsigned l = lds_base + buf * SC_TILE_BYTES + wave * 1024;
     dma16x4(voff, tb, tb + 8192, tb + 16384, tb + 24576, l, l + 8192, l + 16384, l + 24576);
     if (wave < 3)
       dma4(voff_dd, A.dneg + (size_t)tile * SC_DD, lds_base + SC_NBUF * SC_TILE_BYTES + buf * (SC_DD * 4) + wave * 256);
   };
-  if (sel_begin < sel_end) stage(sel_begin, 0);
+  if (sel_begin < sel_end) stage(tile_cur, 0);
   // ---- B operands: the lane's query of either 16-query tile of each block, k = 32 s + 8 quarter .. + 7 ----
   half8 bq[NQB][2][4];
 #pragma unroll
@@ -748,16 +867,16 @@ __global__ __launch_bounds__(512, 2) void screen16_kernel(const ScreenArgs A) {
   // per-query state of the lane's 2 NQB queries.  Pass B is at the register limit (128 for the queries' operands, 32 + 16
   // + 16 for a row block's fragments, the accumulators and the pending block): the thresholds wait in LDS (two ds_read_b32
   // per block, in the MFMAs' shadow) and the sub-lists' record counts are bytes of NQB / 2 registers.
-  float b1[NQB][2], b2[NQB][2];
+  // pass A: the lane's SC_TOPK largest packed block maxima per query, sorted, and the next largest value
+  float pk[NQB][2][SC_PART5];
   unsigned n_rec[(NQB + 1) / 2] = {};   // [nb >> 1]: byte 2 (nb & 1) + tj
   float* const tau_lds = reinterpret_cast<float*>(lds + SC_LDS16_TAU) + wave * 128;
 #pragma unroll
   for (int nb = 0; nb < NQB; ++nb)
 #pragma unroll
-    for (int tj = 0; tj < 2; ++tj) {
-      b1[nb][tj] = -__builtin_inff();
-      b2[nb][tj] = -__builtin_inff();
-    }
+    for (int tj = 0; tj < 2; ++tj)
+#pragma unroll
+      for (int k = 0; k < SC_PART5; ++k) pk[nb][tj][k] = -__builtin_inff();
   if (MODE == 1)
     for (int i = lane; i < QW; i += 64) tau_lds[i] = A.tau[q0 + i];
   __builtin_amdgcn_s_waitcnt(0x0F70);
@@ -777,7 +896,7 @@ __global__ __launch_bounds__(512, 2) void screen16_kernel(const ScreenArgs A) {
   auto emit = [&](const v4f& d0, const v4f& d1, unsigned& nrec_word, int shift, int q, int row0, float top, float thr, int pos) {
     const int nrec = (int)((nrec_word >> shift) & 0xFFu);
     if (nrec < A.sub_cap) {   // (sub_cap <= SC_SLOTS_MAX / 4 = 64 < 256, static_assert at SB16_MAX: the byte cannot wrap)
-      const unsigned dst = (unsigned)q * SC_SLOTS_MAX + (4 * split + quarter) * A.sub_cap + nrec;
+      const unsigned dst = (unsigned)q * SC_SLOT_PITCH + (4 * split + quarter) * A.sub_cap + nrec;
       nrec_word += 1u << shift;
       if (pos < SC_RECBUF16) {
         uint4* e = recbuf + 3 * pos;
@@ -843,6 +962,32 @@ __global__ __launch_bounds__(512, 2) void screen16_kernel(const ScreenArgs A) {
   auto max8 = [&](const v4f& x, const v4f& y) {
     return max3(max3(max3(x[0], x[1], x[2]), x[3], y[0]), max3(y[1], y[2], y[3]), -__builtin_inff());
   };
+  // Pass A takes the maxima of a block whose MFMAs have JUST been issued (pass B looks at the block before): hipcc pads
+  // no wait states between a matrix instruction and an asm statement that reads its result, and the last two
+  // accumulators then read as what the registers held before (a block maximum that misses rows 17..19 of its lane's
+  // eight: harmless for a threshold that only has to be low enough, fatal for a hand-over).  So both queries' maxima
+  // are ONE statement that opens with the wait states of an 8-pass MFMA's result (11; 16 here), floored for the packing.
+  auto max8x2_after_mfma = [](const v4f (&acc)[2][2], float floor, float& m0, float& m1) {
+    float t0, t1;
+    asm("s_nop 7\n\ts_nop 7\n\t"
+        "v_max3_f32 %0, %4, %5, %6\n\t"
+        "v_max3_f32 %1, %12, %13, %14\n\t"
+        "v_max3_f32 %2, %9, %10, %11\n\t"
+        "v_max3_f32 %3, %17, %18, %19\n\t"
+        "v_max3_f32 %0, %0, %7, %8\n\t"
+        "v_max3_f32 %1, %1, %15, %16\n\t"
+        "v_max3_f32 %0, %0, %2, %20\n\t"
+        "v_max3_f32 %1, %1, %3, %20"
+        : "=&v"(m0), "=&v"(m1), "=&v"(t0), "=&v"(t1)
+        : "v"(acc[0][0][0]), "v"(acc[0][0][1]), "v"(acc[0][0][2]), "v"(acc[0][0][3]), "v"(acc[1][0][0]), "v"(acc[1][0][1]),
+          "v"(acc[1][0][2]), "v"(acc[1][0][3]), "v"(acc[0][1][0]), "v"(acc[0][1][1]), "v"(acc[0][1][2]), "v"(acc[0][1][3]),
+          "v"(acc[1][1][0]), "v"(acc[1][1][1]), "v"(acc[1][1][2]), "v"(acc[1][1][3]), "v"(floor));
+  };
+  auto max2 = [](float a, float b) {   // (as an instruction, like max3: the packed values are never NaN)
+    float r;
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+  };
 
   int side = 0;
   // the pending block starts as one no threshold lets through (its dots -inf): the loop needs no "is there one yet"
@@ -855,10 +1000,17 @@ __global__ __launch_bounds__(512, 2) void screen16_kernel(const ScreenArgs A) {
   MH_TRACE_PHASE(trace_loop_, MODE == 1 ? mh::TK_PASS_B_LOOP : mh::TK_PASS_A_LOOP);
   for (int sel = sel_begin; sel < sel_end; ++sel) {
     const bool more = sel + 1 < sel_end;
-    if (more) stage(sel + 1, side ^ 1);
+    int tile_nxt = tile_cur + (MODE == 0 ? A.tile_stride : 1), gap_nxt = gap_cur - 1;
+    if (gap_nxt == 0) {   // the next tile is one of pass A's: over it
+      tile_nxt += 1;
+      gap_nxt = A.skip_stride - 1;
+    }
+    if (more) stage(tile_nxt, side ^ 1);
     const unsigned char* T = lds + side * SC_TILE_BYTES;
     const float* ddp = reinterpret_cast<const float*>(lds + SC_NBUF * SC_TILE_BYTES + side * (SC_DD * 4));
-    const int row_tile = (A.tile_first + sel * A.tile_stride) * SC_TILE;
+    const int row_tile = tile_cur * SC_TILE;
+    tile_cur = tile_nxt;
+    gap_cur = gap_nxt;
     // (a wavefront none of whose 128 queries exists -- the tail of the last query block -- only helps with the staging
     // and the barriers: the SIMD's matrix pipe is then its neighbour's alone)
     if (!live) {
@@ -867,6 +1019,7 @@ __global__ __launch_bounds__(512, 2) void screen16_kernel(const ScreenArgs A) {
       for (int rb = 0; rb < SC_TILE / 32; ++rb) {
         half8 a[2][4];
         load_rb(T, rb, a);
+        const unsigned blk = (unsigned)((sel - sel_begin) * 4 + rb) & ~A.pack_keep;   // the block's number inside the lane slot
         v4f init[2];
 #pragma unroll
         for (int ti = 0; ti < 2; ++ti) {
@@ -884,11 +1037,17 @@ __global__ __launch_bounds__(512, 2) void screen16_kernel(const ScreenArgs A) {
               for (int tj = 0; tj < 2; ++tj)
                 acc[ti][tj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[ti][s], bq[nb][tj][s], acc[ti][tj], 0, 0, 0);
           __builtin_amdgcn_sched_barrier(0);
+          float mx[2];
+          max8x2_after_mfma(acc, SC_PACK_FLOOR, mx[0], mx[1]);
 #pragma unroll
           for (int tj = 0; tj < 2; ++tj) {
-            const float m = max8(acc[0][tj], acc[1][tj]);
-            b2[nb][tj] = __builtin_amdgcn_fmed3f(b1[nb][tj], b2[nb][tj], m);
-            b1[nb][tj] = fmaxf(b1[nb][tj], m);
+            // the block's maximum with its number in the low mantissa bits, into the sorted list: level k becomes the
+            // median of (level k - 1, level k, new) -- from the bottom up, every level from the OLD level above it
+            const float m = __uint_as_float((__float_as_uint(mx[tj]) & A.pack_keep) | blk);
+            float(&p)[SC_PART5] = pk[nb][tj];
+#pragma unroll
+            for (int k = SC_PART5 - 1; k > 0; --k) p[k] = __builtin_amdgcn_fmed3f(p[k - 1], p[k], m);
+            p[0] = max2(p[0], m);
           }
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -953,20 +1112,17 @@ __global__ __launch_bounds__(512, 2) void screen16_kernel(const ScreenArgs A) {
     flush_parked();
   }
   if (MODE == 0) {
-    // the four quarters of the wavefront hold different rows of the same queries
+    // every lane its own lists (the four quarters of the wavefront hold different rows of the same queries: four lane
+    // slots); 16 lanes = 16 neighbouring queries = one 64-byte line per store
 #pragma unroll
     for (int nb = 0; nb < NQB; ++nb)
 #pragma unroll
       for (int tj = 0; tj < 2; ++tj) {
-        float B = b1[nb][tj], S = b2[nb][tj];
-#pragma unroll
-        for (int d = 16; d <= 32; d <<= 1) {
-          const float ob = __shfl_xor(B, d), os = __shfl_xor(S, d);
-          S = fmaxf(fminf(B, ob), fmaxf(S, os));
-          B = fmaxf(B, ob);
-        }
         const int q = q0 + nb * 32 + 16 * tj + l16;
-        if (quarter == 0 && q < A.q_pad) A.part[(size_t)split * A.q_pad + q] = make_float2(B, S);
+        if (q < A.q_pad) {
+#pragma unroll
+          for (int k = 0; k < SC_PART5; ++k) A.part5[((size_t)(split * 4 + quarter) * SC_PART5 + k) * A.q_pad + q] = pk[nb][tj][k];
+        }
       }
   }
 }
@@ -1032,7 +1188,8 @@ __global__ __launch_bounds__(64 * RS_WAVES) void rescore_kernel(
     const int32_t* __restrict__ q_count, const float* __restrict__ db, const float* __restrict__ dnorm, int N,
     RowMap rmap, uint2* __restrict__ recs, int n_slots, int32_t* __restrict__ ovf_cnt, uint2* __restrict__ ovf,
     int ovf_cap, float dmax, const float* __restrict__ tau, float spread, int32_t* __restrict__ idx1, float* __restrict__ d1, float* __restrict__ d2,
-    unsigned int* __restrict__ stats, int32_t zero_idx, float zero_d1, float zero_d2) {
+    unsigned int* __restrict__ stats, int32_t zero_idx, float zero_d1, float zero_d2, SampleGeom g,
+    const unsigned int* __restrict__ inc, unsigned int* __restrict__ inc_count) {
   MH_TRACE_SCOPE(mh::TK_PASS_C);
   __shared__ __attribute__((aligned(16))) float q_s[RS_WAVES][DIM];
   __shared__ __attribute__((aligned(16))) int cand_s[RS_WAVES][RS_MAXC];   // the candidate list, then RS_STAGE rows of them
@@ -1043,22 +1200,27 @@ __global__ __launch_bounds__(64 * RS_WAVES) void rescore_kernel(
   if (q >= Q) return;
   // Everything the query's wavefront reads before it knows its candidates is asked for HERE, in one go: the kernel lives
   // on round trips (a query is ~a dozen loads and ~400 fmaf), and loads issued behind the branches below each cost one.
-  constexpr int RS_ITERS = (SC_SLOTS_MAX + SCREEN_OVF_CAP + 63) / 64;
-  uint2* mine = recs + (size_t)q * SC_SLOTS_MAX;
+  // the query's slots in scan order: pass B's n_slots, then (one-sweep launches) the g.sa_slots of the sampled tiles'
+  // records, which lie behind pass B's SC_SLOTS_MAX; then the overflow list
+  constexpr int RS_ITERS = (SC_SLOT_PITCH + SCREEN_OVF_CAP + 63) / 64;
+  uint2* mine = recs + (size_t)q * SC_SLOT_PITCH;
+  const int n_own = n_slots + g.sa_slots;
+  auto slot_at = [&](int j) -> uint2& { return mine[j < n_slots ? j : SC_SLOTS_MAX + (j - n_slots)]; };
   uint2 recv[RS_ITERS];
 #pragma unroll
   for (int it = 0; it < RS_ITERS; ++it) {
     const int j = it * 64 + lane;
-    recv[it] = j < n_slots ? mine[j] : make_uint2(0u, 0u);
+    recv[it] = j < n_own ? slot_at(j) : make_uint2(0u, 0u);
   }
   const int Qe = q_count ? min(Q, *q_count) : Q;
   const int bad = qbad[q];
   const float nq = qnorm[q];
   const float tau_q = tau[q];
   const int n_ovf = ovf_cnt[q];
+  const unsigned incw = inc ? inc[q] : 0u;
   const float2 qv = reinterpret_cast<const float2*>(qn + (size_t)q * DIM)[lane];
   // (the values are wanted HERE: without this the compiler moves the loads behind the tests below, one round trip each)
-  asm volatile("" ::"v"(bad), "v"(nq), "v"(tau_q), "v"(n_ovf), "v"(qv.x), "v"(qv.y), "s"(Qe));
+  asm volatile("" ::"v"(bad), "v"(nq), "v"(tau_q), "v"(n_ovf), "v"(incw), "v"(qv.x), "v"(qv.y), "s"(Qe));
   if (q >= Qe) {   // no such query in this frame: "no neighbour", like combine_splits_kernel (pass B left it no records)
     if (lane == 0) {
       idx1[q] = -1;
@@ -1098,21 +1260,24 @@ __global__ __launch_bounds__(64 * RS_WAVES) void rescore_kernel(
     // more than screen_margin below that bound cannot hold one.  Pass A's threshold comes from an eighth of the rows
     // and lets ~25 rows per query through; ~3 survive this one and get their 512-byte row fetched.
     float l1 = -__builtin_inff(), l2 = -__builtin_inff();   // the lane's two largest lower bounds
-    auto bounds = [tau_q, spread, N, dmax](uint2 rec, float& lo, float& hi) {
+    const float pert = screen_pack_pert(nq, dmax, g.pack_bits);
+    auto bounds = [tau_q, spread, N, dmax, pert](uint2 rec, float& lo, float& hi) {
       // the record's value: (largest dot of the block + the block's largest -dd/2) - tau, rounded to f16.  The block's
       // largest screen value is at most that, and at least that less the spread of -dd/2 inside a block (`spread`: the
       // largest over the DB's blocks of real rows, ~1e-7 for L2-normalised rows); a block with padding rows (their
       // dot is 0, their -dd/2 is -inf) gives no lower bound.  (screen.h; checked in host arithmetic by the CPU tests)
-      screen_record_bounds((unsigned short)(rec.y >> 16), rec.x & 0x7FFFFFFFu, tau_q, spread, N, dmax, lo, hi);
+      // (a record of a sampled tile carries that block's own largest screen value, seen through pass A's packing)
+      if (rec.x & SC_REC_SAMPLE) screen_sample_bounds((unsigned short)(rec.y >> 16), tau_q, pert, dmax, lo, hi);
+      else screen_record_bounds((unsigned short)(rec.y >> 16), rec.x & 0x3FFFFFFFu, tau_q, spread, N, dmax, lo, hi);
     };
 #pragma unroll
     for (int it = 0; it < RS_ITERS; ++it) {
       const int j = it * 64 + lane;
       uint2 rec = recv[it];
-      if (j < n_slots) {
-        if (rec.y) mine[j] = make_uint2(0u, 0u);
-      } else if (j < n_slots + n_ovf) {
-        rec = ovf[(size_t)q * ovf_cap + (j - n_slots)];
+      if (j < n_own) {
+        if (rec.y) slot_at(j) = make_uint2(0u, 0u);
+      } else if (j < n_own + n_ovf) {
+        rec = ovf[(size_t)q * ovf_cap + (j - n_own)];
       }
       recv[it] = rec;
       if (rec.y & 0xFFFFu) {
@@ -1141,7 +1306,7 @@ __global__ __launch_bounds__(64 * RS_WAVES) void rescore_kernel(
       // which rows a bit stands for: records of the 32x32x16 passes hold 16 rows, row0 + (r & 3) + 8 (r >> 2); those of
       // the 16x16x32 passes (bit 31 of the row word) 8 rows, row0 + (r & 3) + 16 (r >> 2)
       const int hi_stride = (rec.x & 0x80000000u) ? 16 : 8;
-      const int row0 = (int)(rec.x & 0x7FFFFFFFu);
+      const int row0 = (int)(rec.x & 0x3FFFFFFFu);
       // candidates in any order (the exact top-2 below breaks ties by row number): an LDS counter hands out places
       while (bits) {
         const int r = __builtin_ctz(bits);
@@ -1154,7 +1319,7 @@ __global__ __launch_bounds__(64 * RS_WAVES) void rescore_kernel(
     n_cand = ncand_s[wave];
     if (n_cand > RS_MAXC) brute = true;
   } else if (n_ovf > ovf_cap) {
-    for (int j = lane; j < n_slots; j += 64) mine[j] = make_uint2(0u, 0u);   // the lists overflowed: empty every slot
+    for (int j = lane; j < n_own; j += 64) slot_at(j) = make_uint2(0u, 0u);   // the lists overflowed: empty every slot
   }
   if (n_ovf && lane == 0) ovf_cnt[q] = 0;
   wave_lds_sync();
@@ -1206,6 +1371,23 @@ __global__ __launch_bounds__(64 * RS_WAVES) void rescore_kernel(
       const int row = brute ? k : cand_s[wave][k];
       if (row >= 0 && row < N) take(best, exact_dist(q_s[wave], db + (size_t)row * DIM, nq, dnorm[row]), row);
     }
+  }
+  if (incw && !brute) {
+    // An incomplete query (screen_handover_kernel): some lane slots of pass A held more blocks above the threshold than
+    // their lists keep, and left no records.  The canonical chain over those slots' rows -- the sampled tiles of the
+    // marked splits, the rows 16 i + 4 quarter .. + 3 of the marked quarters -- takes their place: bounded (a lane
+    // slot is 1 / (4 x pass A's splits) of an eighth of the DB), and none of these rows is in a record.
+    for (unsigned sm = incw & 0x0FFFFFFFu; sm; sm &= sm - 1) {
+      const int split = __builtin_ctz(sm);
+      const int sel0 = split * g.tiles_base + min(split, g.tiles_rem);
+      const int sel1 = min(sel0 + g.tiles_base + (split < g.tiles_rem ? 1 : 0), g.n_sel);
+      for (int k = sel0 * SC_TILE + lane; k < sel1 * SC_TILE; k += 64) {
+        const int row = (g.tile_first + (k >> 7) * g.tile_stride) * SC_TILE + (k & 127);
+        if (((incw >> (28 + ((k & 15) >> 2))) & 1u) && row < N)
+          take(best, exact_dist(q_s[wave], db + (size_t)row * DIM, nq, dnorm[row]), row);
+      }
+    }
+    if (lane == 0 && inc_count) atomicAdd(inc_count, 1u);
   }
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
@@ -1321,10 +1503,14 @@ void launch_screen_prepare(const float* qn, const float* qnorm, int Q, int q_pad
                      q_pad, qh, qbad);
 }
 
-size_t screen_rec_slots() { return SC_SLOTS_MAX; }
+size_t screen_rec_slots() { return SC_SLOT_PITCH; }
 
 int screen_q_pad(int Q) { return (Q + SC_QPAD - 1) / SC_QPAD * SC_QPAD; }
 int screen_max_splits_a() { return 64; }
+// per query: a float2 per pass A split (screen_kernel), or SC_PART5 floats per lane slot of a one-sweep launch
+size_t screen_part_bytes(int q_pad) {
+  return (size_t)q_pad * std::max<size_t>(screen_max_splits_a() * sizeof(float2), (size_t)SC_SA_SPLITS_MAX * 4 * SC_PART5 * sizeof(float));
+}
 
 // When the screen pays: enough (query, row) pairs to be bound by arithmetic rather than by its launches, and
 // enough rows for pass A's sample to mean something.  MH_MATCH_SCREEN = 0 / 1 pins the choice for the process
@@ -1405,15 +1591,16 @@ void launch_passes(ScreenArgs a, int Q, int qe, int n_tiles, int sample, int blo
   *n_slots_out = 2 * Sb * a.sub_cap;
 }
 
-// the same launch policy for the 16x16x32 kernels (eight wavefronts; a query's slots shared out over 4 x splits sub-lists)
+// The launch policy of the 16x16x32 kernels (eight wavefronts; a query's slots shared out over 4 x splits sub-lists), as
+// host arithmetic: launch_passes16 launches what this says, screen_launch_plan shows it to the tests.
+struct Plan16 {
+  bool onesweep;                                  // pass A hands its tiles' records over, pass B skips them
+  int stride, tile_first, n_sel_a, Sa, pack_bits; // pass A
+  int n_sel_b, Sb, sub_cap;                       // pass B
+};
 template <int NQB>
-void launch_passes16(ScreenArgs a, int Q, int qe, int n_tiles, int sample, int blocks_a, int blocks_b, int* n_slots_out,
-                     hipEvent_t* ev, hipStream_t s) {
+Plan16 plan_passes16(int qe, int n_tiles, int sample, int blocks_a, int blocks_b) {
   constexpr int QB = 32 * NQB * 8;
-  static DynLds attr0, attr1;
-  attr0.ensure(screen16_kernel<0, NQB>, SC_LDS16_BYTES);
-  attr1.ensure(screen16_kernel<1, NQB>, SC_LDS16_BYTES);
-  const int nqb = (Q + QB - 1) / QB;
   const int nqb_e = (qe + QB - 1) / QB;
   auto splits_for = [&](int n_sel, int target, int s_max) {
     int S = std::max(1, target / nqb_e);
@@ -1421,79 +1608,154 @@ void launch_passes16(ScreenArgs a, int Q, int qe, int n_tiles, int sample, int b
     if (S >= 8 && (S / 8 * 8) * 33 >= S * 32) S = S / 8 * 8;
     return std::max(S, 1);
   };
+  Plan16 p;
   // (a shard of a few models: the records a query leaves do not shrink with the shard, the MFMA work beside them does --
   // every 4th tile there: half the records for 1/8 more of pass A's rows.  15 000 rows x 96 000 queries: pass B 0.38 ->
   // 0.34 ms, pass A 0.055 -> 0.09, the rank's frames/s +2.5%)
   const int every = sample == 8 && n_tiles < 256 ? 4 : sample;
-  const int stride = n_tiles >= 4 * every ? every : 1;
-  const int n_sel_a = (n_tiles + stride - 1) / stride;
-  const int Sa = splits_for(n_sel_a, blocks_a, screen_max_splits_a());
-  a.n_sel = n_sel_a;
-  a.tile_first = std::min(stride / 2, n_tiles - 1 - (n_sel_a - 1) * stride);
-  if (a.tile_first < 0) a.tile_first = 0;
-  a.tile_stride = stride;
-  a.n_splits = Sa;
-  a.tiles_base = n_sel_a / Sa;
-  a.tiles_rem = n_sel_a % Sa;
-  a.n_splits_a = Sa;
-  hipLaunchKernelGGL((screen16_kernel<0, NQB>), dim3(nqb * Sa), dim3(512), SC_LDS16_BYTES, s, a);
-  if (ev) hipEventRecord(ev[2], s);
-  hipLaunchKernelGGL(screen_tau_kernel, dim3((a.q_pad + 255) / 256), dim3(256), 0, s, a.part, Sa, a.q_pad, a.Q, a.q_count,
-                     a.qnorm, a.qbad, a.dmax, const_cast<float*>(a.tau));
-#ifdef MH_EXPERIMENTS
-  // what the records cost pass B: thresholds no value reaches (WRONG results: timing only)
-  if (exp_int("MH_SCREEN_NO_HITS", 0)) hipMemsetAsync(const_cast<float*>(a.tau), 0x7f, (size_t)a.q_pad * sizeof(float), s);
-#endif
-  if (ev) hipEventRecord(ev[3], s);
+  p.stride = n_tiles >= 4 * every ? every : 1;
+  p.n_sel_a = (n_tiles + p.stride - 1) / p.stride;
+  p.Sa = splits_for(p.n_sel_a, blocks_a, SC_SA_SPLITS_MAX);   // (the lists of 4 x Sa lane slots per query: screen_part_bytes)
+  p.tile_first = std::max(0, std::min(p.stride / 2, n_tiles - 1 - (p.n_sel_a - 1) * p.stride));
+  // One sweep: pass A keeps the identity of its best blocks (the block's number inside a lane slot in the low mantissa
+  // bits of the block's maximum) and pass B leaves the sampled tiles out.  Not when pass A sees every tile anyway, nor
+  // when a lane slot would have more blocks than SC_PACK_BITS_MAX bits count even with all the splits pass A may have
+  // (7 M rows): pass B then sweeps all tiles as before, and the block maxima stay as they are (0 bits).
+  static const int onesweep_on = exp_int("MH_SCREEN_ONESWEEP", 1);   // experiment builds: 0 = pass B sweeps every tile (scripts/ab_env.sh)
+  if (onesweep_on && p.stride > 1)   // (a long sweep: more, shorter splits rather than wider block numbers)
+    while (4 * ((p.n_sel_a + p.Sa - 1) / p.Sa) > (1 << SC_PACK_BITS_MAX) && p.Sa < SC_SA_SPLITS_MAX) ++p.Sa;
+  const int blocks_slot = 4 * ((p.n_sel_a + p.Sa - 1) / p.Sa);
+  int bits = 2;
+  while ((1 << bits) < blocks_slot) ++bits;
+  p.onesweep = onesweep_on && p.stride > 1 && bits <= SC_PACK_BITS_MAX;
+  p.pack_bits = p.onesweep ? bits : 0;
   // Pass B's splits.  A query's 256 record slots are shared out over 4 x Sb lane-private sub-lists here (the 32x32x16
   // passes: 2 x Sb), and a sub-list needs room for three records or queries spill into the overflow list and from there
   // into pass C's brute-force search (12 000 queries x 250 000 rows ran 42 splits with ONE slot per sub-list for a while:
   // 42 brute-force queries per launch, pass C 10 ms instead of 0.03): Sb <= 21.  One workgroup per compute unit, so the
-  // launch takes ceil(workgroups / 256) rounds of n_tiles / Sb tiles each: the Sb with the least rounds x tiles, the
+  // launch takes ceil(workgroups / 256) rounds of tiles / Sb tiles each: the Sb with the least rounds x tiles, the
   // larger of equals.  (blocks_b > 0: an experiment's request, capped the same way.)
   constexpr int SB16_MAX = SC_SLOTS_MAX / 12;
   // screen16_kernel counts a query's records per sub-list in one byte of n_rec[]; sub_cap <= SC_SLOTS_MAX / (4 * Sb)
   static_assert(SC_SLOTS_MAX / 4 < 256, "a sub-list's record count must fit the byte screen16_kernel keeps it in");
-  int Sb = 1;
+  p.n_sel_b = p.onesweep ? n_tiles - p.n_sel_a : n_tiles;
+  p.Sb = 1;
   if (blocks_b > 0) {
-    Sb = std::min(splits_for(n_tiles, blocks_b, SC_SLOTS_MAX / 4), SB16_MAX);
+    p.Sb = std::min(splits_for(p.n_sel_b, blocks_b, SC_SLOTS_MAX / 4), SB16_MAX);
   } else {
     double best = 1e30;
-    for (int c = 1; c <= std::min(SB16_MAX, std::max(1, n_tiles / 8)); ++c) {
-      const double cost = (double)((nqb_e * c + 255) / 256) * (double)((n_tiles + c - 1) / c);
+    for (int c = 1; c <= std::min(SB16_MAX, std::max(1, p.n_sel_b / 8)); ++c) {
+      const double cost = (double)((nqb_e * c + 255) / 256) * (double)((p.n_sel_b + c - 1) / c);
       if (cost <= best) {
         best = cost;
-        Sb = c;
+        p.Sb = c;
       }
     }
   }
-  a.n_sel = n_tiles;
-  a.tile_first = 0;
-  a.tile_stride = 1;
-  a.n_splits = Sb;
-  a.tiles_base = n_tiles / Sb;
-  a.tiles_rem = n_tiles % Sb;
   // slots per sub-list: room for three records, and on a small DB ~96 slots per query in all (a query gets ~20 records)
   // rather than everything the 256 slots allow -- pass C reads (and re-empties) every slot of every query, and on a
   // shard of a few models, where few splits fill the chip, 8 slots per sub-list made that scan 2 KB per query where 768
   // bytes do.  Large DBs keep all 256: their queries' record counts have a long tail (1 M rows, 32 000 queries, 8
   // splits: 96 slots sent 117 queries per launch into pass C's brute-force search, 69 ms instead of 3).
   const int slots_target = n_tiles >= 2048 ? SC_SLOTS_MAX : (n_tiles >= 512 ? 160 : 96);
-  a.sub_cap = std::max(1, std::min(std::max(3, (slots_target + 4 * Sb - 1) / (4 * Sb)), SC_SLOTS_MAX / (4 * Sb)));
-  hipLaunchKernelGGL((screen16_kernel<1, NQB>), dim3(nqb * Sb), dim3(512), SC_LDS16_BYTES, s, a);
+  p.sub_cap = std::max(1, std::min(std::max(3, (slots_target + 4 * p.Sb - 1) / (4 * p.Sb)), SC_SLOTS_MAX / (4 * p.Sb)));
+  return p;
+}
+
+template <int NQB>
+void launch_passes16(ScreenArgs a, int Q, int qe, int n_tiles, int sample, int blocks_a, int blocks_b, int* n_slots_out,
+                     SampleGeom* geom_out, unsigned int* inc, hipEvent_t* ev, hipStream_t s) {
+  constexpr int QB = 32 * NQB * 8;
+  static DynLds attr0, attr1;
+  attr0.ensure(screen16_kernel<0, NQB>, SC_LDS16_BYTES);
+  attr1.ensure(screen16_kernel<1, NQB>, SC_LDS16_BYTES);
+  const int nqb = (Q + QB - 1) / QB;
+  const Plan16 p = plan_passes16<NQB>(qe, n_tiles, sample, blocks_a, blocks_b);
+  // pass A: every `stride`-th tile, starting in the middle of the first stride
+  a.n_sel = p.n_sel_a;
+  a.tile_first = p.tile_first;
+  a.tile_stride = p.stride;
+  a.n_splits = p.Sa;
+  a.tiles_base = p.n_sel_a / p.Sa;
+  a.tiles_rem = p.n_sel_a % p.Sa;
+  a.n_splits_a = p.Sa;
+  a.pack_keep = ~((1u << p.pack_bits) - 1u);
+  a.skip_first = a.skip_stride = 0;
+  hipLaunchKernelGGL((screen16_kernel<0, NQB>), dim3(nqb * p.Sa), dim3(512), SC_LDS16_BYTES, s, a);
+  if (ev) hipEventRecord(ev[2], s);
+  SampleGeom g = {p.onesweep ? SC_SA_SLOTS : 0, p.pack_bits, a.tile_first, a.tile_stride, a.tiles_base, a.tiles_rem, a.n_sel};
+  // (one wavefront per workgroup: 768 workgroups for config 1's 49 152 queries, where 192 of 256 threads left a quarter of the compute units idle)
+  hipLaunchKernelGGL(screen_handover_kernel, dim3((a.q_pad + 63) / 64), dim3(64), 0, s, (const float*)a.part5, 4 * p.Sa, a.q_pad,
+                     a.Q, a.q_count, a.qnorm, a.qbad, a.dmax, g, const_cast<float*>(a.tau), a.recs, inc);
+#ifdef MH_EXPERIMENTS
+  // what the records cost pass B: thresholds no value reaches (WRONG results: timing only)
+  if (exp_int("MH_SCREEN_NO_HITS", 0)) hipMemsetAsync(const_cast<float*>(a.tau), 0x7f, (size_t)a.q_pad * sizeof(float), s);
+#endif
+  if (ev) hipEventRecord(ev[3], s);
+  // pass B: the tiles pass A did not see (all tiles when there is no hand-over)
+  a.n_sel = p.n_sel_b;
+  a.tile_first = 0;
+  a.tile_stride = 1;
+  a.skip_first = p.onesweep ? p.tile_first : 0;
+  a.skip_stride = p.onesweep ? p.stride : 0;
+  a.n_splits = p.Sb;
+  a.tiles_base = p.n_sel_b / p.Sb;
+  a.tiles_rem = p.n_sel_b % p.Sb;
+  a.sub_cap = p.sub_cap;
+  hipLaunchKernelGGL((screen16_kernel<1, NQB>), dim3(nqb * p.Sb), dim3(512), SC_LDS16_BYTES, s, a);
   if (ev) hipEventRecord(ev[4], s);
-  *n_slots_out = 4 * Sb * a.sub_cap;
+  *n_slots_out = 4 * p.Sb * a.sub_cap;
+  *geom_out = g;
+}
+
+// which kernels a MATCH launch runs on (launch_match_screen): queries per workgroup / 256, and whether the 16x16x32 passes
+struct ShapeChoice {
+  int nqb_sel;
+  bool passes16;
+};
+ShapeChoice choose_shape(int qe, int n_tiles) {
+  static const int nqb_pin = exp_int("MH_SCREEN_NQB", 0);
+  // queries per workgroup: 1024 (four 32-query blocks per wavefront: every row fragment read from LDS feeds four
+  // MFMAs; 256 VGPRs, no prefetched copy of the next row block) when the launch is large enough for workgroups of
+  // >= 16 tiles -- pass B alone 8-10% faster, config 2 +9.7% frames/s --, else 512 (two blocks, row fragments
+  // prefetched), or 256 for small frames.  768 is selectable for experiments.
+  int nqb_sel = qe > 640 ? 2 : 1;
+  if (qe >= 2048 && (long)n_tiles * ((qe + 1023) / 1024) >= 16L * 256) nqb_sel = 4;
+  if (nqb_pin >= 1 && nqb_pin <= 4) nqb_sel = nqb_pin;
+  // the MFMA shape of the large launches: 16x16x32 (SC_SHAPE16_LARGE; MH_SCREEN_SHAPE = 1 / 2 pins 32x32x16 / 16x16x32 in experiment builds)
+  static const int shape_pin = exp_int("MH_SCREEN_SHAPE", 0);
+  const bool shape16 = shape_pin == 2 || (shape_pin == 0 && SC_SHAPE16_LARGE);
+  // (16x16x32 from 12 query blocks of 1024: with fewer, 21 splits leave compute units without a workgroup)
+  const bool p16 = shape16 && ((nqb_sel == 4 && (shape_pin == 2 || (qe + 1023) / 1024 >= 12)) || (nqb_sel == 2 && shape_pin == 2));
+  return {nqb_sel, p16};
+}
+
+int screen_sample_every() {
+  static const int sample = std::max(1, exp_int("MH_SCREEN_SAMPLE", 8));   // pass A looks at every `sample`-th tile
+  return sample;
 }
 
 }  // namespace
 
+void screen_launch_plan(int Q, int q_expected, int N, int out[8]) {
+  const int qe = (q_expected > 0 && q_expected < Q) ? std::max(q_expected, std::min(Q, 256)) : Q;
+  const int n_tiles = (N + SC_TILE - 1) / SC_TILE;
+  for (int k = 0; k < 8; ++k) out[k] = 0;
+  const ShapeChoice shape = choose_shape(qe, n_tiles);
+  if (!shape.passes16) return;
+  const int blocks_b = std::max(0, exp_int("MH_SCREEN_BLOCKS", 0)), blocks_a = std::max(1, exp_int("MH_SCREEN_BLOCKS_A", 256));
+  const Plan16 p = shape.nqb_sel == 4 ? plan_passes16<4>(qe, n_tiles, screen_sample_every(), blocks_a, blocks_b)
+                                      : plan_passes16<2>(qe, n_tiles, screen_sample_every(), blocks_a, blocks_b);
+  const int v[8] = {p.onesweep ? 1 : 0, p.tile_first, p.stride, p.n_sel_a, p.Sa, p.pack_bits, p.Sb, p.n_sel_b};
+  for (int k = 0; k < 8; ++k) out[k] = v[k];
+}
+
 void launch_match_screen(const float* qn, const float* qnorm, int Q, const float* db, const float* dnorm, int N,
                          const RowMap& rmap, const ScreenDb& sdb, const ScreenBufs& sb, int32_t* idx1, float* d1,
                          float* d2, hipStream_t s, const int32_t* q_count, int q_expected) {
-  static const int sample = std::max(1, exp_int("MH_SCREEN_SAMPLE", 8));      // pass A looks at every `sample`-th tile
+  const int sample = screen_sample_every();
   static const int blocks_b = std::max(0, exp_int("MH_SCREEN_BLOCKS", 0));    // workgroups of pass B; 0 = by size (launch_passes)
   static const int blocks_a = std::max(1, exp_int("MH_SCREEN_BLOCKS_A", 256));
-  static const int nqb_pin = exp_int("MH_SCREEN_NQB", 0);
   const int q_pad = screen_q_pad(Q);
   const int qe = (q_expected > 0 && q_expected < Q) ? std::max(q_expected, std::min(Q, 256)) : Q;
   const int n_tiles = (N + SC_TILE - 1) / SC_TILE;
@@ -1517,6 +1779,9 @@ void launch_match_screen(const float* qn, const float* qnorm, int Q, const float
   a.qbad = sb.qbad;
   a.q_count = q_count;
   a.part = sb.part;
+  a.part5 = reinterpret_cast<float*>(sb.part);
+  a.pack_keep = ~0u;
+  a.skip_first = a.skip_stride = 0;
   a.tau = sb.tau;
   a.recs = sb.recs;
   a.ovf_cnt = sb.ovf_cnt;
@@ -1531,23 +1796,15 @@ void launch_match_screen(const float* qn, const float* qnorm, int Q, const float
 #else
   a.ablate = 0;
 #endif
-  // queries per workgroup: 1024 (four 32-query blocks per wavefront: every row fragment read from LDS feeds four
-  // MFMAs; 256 VGPRs, no prefetched copy of the next row block) when the launch is large enough for workgroups of
-  // >= 16 tiles -- pass B alone 8-10% faster, config 2 +9.7% frames/s --, else 512 (two blocks, row fragments
-  // prefetched), or 256 for small frames.  768 is selectable for experiments.
-  int nqb_sel = qe > 640 ? 2 : 1;
-  if (qe >= 2048 && (long)n_tiles * ((qe + 1023) / 1024) >= 16L * 256) nqb_sel = 4;
-  if (nqb_pin >= 1 && nqb_pin <= 4) nqb_sel = nqb_pin;
+  const ShapeChoice shape = choose_shape(qe, n_tiles);
+  const int nqb_sel = shape.nqb_sel;
   int n_slots = 0;
+  SampleGeom geom = {0, 0, 0, 1, 0, 0, 0};
   // wavefronts per workgroup: four (two workgroups share a CU) for the large launches, see the top of the file
   static const int nw_pin = exp_int("MH_SCREEN_NW", 0);
   const int nw_sel = nw_pin == 4 || nw_pin == 8 ? nw_pin : (nqb_sel == 4 ? SC_NW_LARGE : 8);
-  // the MFMA shape of the large launches: 16x16x32 (SC_SHAPE16_LARGE; MH_SCREEN_SHAPE = 1 / 2 pins 32x32x16 / 16x16x32 in experiment builds)
-  static const int shape_pin = exp_int("MH_SCREEN_SHAPE", 0);
-  const bool shape16 = shape_pin == 2 || (shape_pin == 0 && SC_SHAPE16_LARGE);
-  // (16x16x32 from 12 query blocks of 1024: with fewer, 21 splits leave compute units without a workgroup)
-  if (nqb_sel == 4 && shape16 && (shape_pin == 2 || (qe + 1023) / 1024 >= 12)) launch_passes16<4>(a, Q, qe, n_tiles, sample, blocks_a, blocks_b, &n_slots, sb.ev, sbig);
-  else if (nqb_sel == 2 && shape16 && shape_pin == 2) launch_passes16<2>(a, Q, qe, n_tiles, sample, blocks_a, blocks_b, &n_slots, sb.ev, sbig);
+  if (shape.passes16 && nqb_sel == 4) launch_passes16<4>(a, Q, qe, n_tiles, sample, blocks_a, blocks_b, &n_slots, &geom, sb.inc, sb.ev, sbig);
+  else if (shape.passes16) launch_passes16<2>(a, Q, qe, n_tiles, sample, blocks_a, blocks_b, &n_slots, &geom, sb.inc, sb.ev, sbig);
   else if (nqb_sel == 4 && nw_sel == 4) launch_passes<4, 4>(a, Q, qe, n_tiles, sample, blocks_a, blocks_b, &n_slots, sb.ev, sbig, 256);
   else if (nqb_sel == 4) launch_passes<4, 8>(a, Q, qe, n_tiles, sample, blocks_a, blocks_b, &n_slots, sb.ev, sbig, 256);
   else if (nqb_sel == 3) launch_passes<3, 8>(a, Q, qe, n_tiles, sample, blocks_a, blocks_b, &n_slots, sb.ev, sbig, 256);
@@ -1561,7 +1818,8 @@ void launch_match_screen(const float* qn, const float* qnorm, int Q, const float
   // pass C
   hipLaunchKernelGGL(rescore_kernel, dim3((Q + RS_WAVES - 1) / RS_WAVES), dim3(64 * RS_WAVES), 0, s, qn, qnorm, sb.qbad, Q,
                      q_count, db, dnorm, N, rmap, sb.recs, n_slots, sb.ovf_cnt, sb.ovf, sb.ovf_cap, sdb.dmax, (const float*)sb.tau, sdb.spread, idx1, d1, d2,
-                     sb.stats, sdb.zero_idx, sdb.zero_d1, sdb.zero_d2);
+                     sb.stats, sdb.zero_idx, sdb.zero_d1, sdb.zero_d2, geom, geom.sa_slots > 0 ? (const unsigned int*)sb.inc : nullptr,
+                     sb.inc ? sb.inc + sb.q_pad : nullptr);
   if (sb.ev) hipEventRecord(sb.ev[5], s);
 }
 

@@ -23,7 +23,7 @@ struct ScreenDb {
 struct ScreenBufs {
   _Float16* qh = nullptr;          // [q_pad][128]
   uint8_t* qbad = nullptr;         // [q_pad] queries the screen does not vouch for (brute force in pass C)
-  float2* part = nullptr;          // [screen_max_splits_a()][q_pad] pass A's per-split top-2 values
+  float2* part = nullptr;          // [screen_part_bytes(q_pad)] pass A's output: per-split top-2 values, or the lane slots' lists of the one-sweep launches
   float* tau = nullptr;            // [q_pad] the queries' thresholds for pass B
   uint2* recs = nullptr;           // [q_pad][screen_rec_slots()] candidate records, all empty between frames
   int32_t* ovf_cnt = nullptr;      // [q_pad] records in the query's overflow list; zero between frames
@@ -36,6 +36,9 @@ struct ScreenBufs {
   hipStream_t big = nullptr;
   hipEvent_t ev_in = nullptr, ev_out = nullptr;
   unsigned int* stats = nullptr;   // optional [q_pad][3] per-query tallies: candidate rows, brute-force searches, searches
+  // [q_pad] the queries' incomplete words of the one-sweep launches (which lane slots of pass A pass C has to sweep; 0 = none),
+  // then one counter: queries that took that sweep since the last mh_match_incomplete(reset)
+  unsigned int* inc = nullptr;
 };
 
 // ---- what a candidate record says about its block (pass B writes it, pass C prunes by it) -------------------------
@@ -67,6 +70,42 @@ __host__ __device__ inline void screen_record_bounds(unsigned short value_bits, 
   lo = fin && whole && spread < 1e30f ? tau_q + dv - spread - eps : -__builtin_inff();
 }
 
+// ---- the one-sweep launches: pass A's block maxima carry their block's number ---------------------------------------
+// screen16_kernel's pass A replaces the low `bits` mantissa bits of a block's largest screen value by the block's number
+// inside its lane slot (match_screen.hip, "pass A of the one-sweep launches").
+__host__ __device__ inline float screen_pack_value(float v, unsigned id, int bits) {
+  const unsigned keep = ~((1u << bits) - 1u);
+  unsigned u;
+  __builtin_memcpy(&u, &v, 4);
+  u = (u & keep) | (id & ~keep);
+  __builtin_memcpy(&v, &u, 4);
+  return v;
+}
+// How far a packed value can lie from the value it was made from, either way: the low `bits` bits of a normal float are
+// worth less than 2^(bits - 23) |v|, those of a subnormal less than 2^(bits - 149); and every screen value of a query
+// satisfies |v| <= W = |q_h| |d_h| + dd / 2 + the f32 accumulation <= 1.01 (|q| Dmax + Dmax^2 / 2) + 4e-7 (|q| + Dmax)
+// (f16 rounding of the operands: a factor (1 + 2^-11)^2, and 2^-25 per element in the subnormal range, as in
+// screen_margin).  tests/test_screen_pack_cpu.py checks it in float64.
+__host__ __device__ inline float screen_pack_pert(float qq, float dmax, int bits) {
+  const float nq = sqrtf(fmaxf(qq, 0.f));
+  const float W = 1.01f * (nq * dmax + 0.5f * dmax * dmax) + 4e-7f * (nq + dmax) + 1e-30f;
+  return W * ldexpf(1.f, bits - 23);
+}
+// Bounds of the largest screen value of a block of a SAMPLED tile from its record (screen_handover_kernel): the record
+// carries f16(v' - tau) with v' the block's packed maximum -- pass A's accumulators start at the rows' own -dd/2, so the
+// block's maximum is its largest screen value itself (no `spread`, and padding rows, at -inf, do not matter: a record's
+// maximum is a real row's).  `pert` = screen_pack_pert of the query.
+__host__ __device__ inline void screen_sample_bounds(unsigned short value_bits, float tau_q, float pert, float dmax, float& lo,
+                                                     float& hi) {
+  _Float16 h;
+  __builtin_memcpy(&h, &value_bits, 2);
+  const float dv = (float)h;
+  const float eps = fabsf(dv) * 0.001f + 1e-6f + 4e-7f * (fabsf(tau_q) + 0.5f * dmax * dmax);   // as in screen_record_bounds
+  const bool fin = fabsf(dv) < 6.0e4f && fabsf(tau_q) < 1e30f;
+  hi = fin ? tau_q + dv + eps + pert : __builtin_inff();
+  lo = fin ? tau_q + dv - eps - pert : -__builtin_inff();
+}
+
 constexpr int SCREEN_OVF_CAP = 64;   // records in a query's overflow list before the query falls back to brute force
 size_t screen_rec_slots();           // record slots per query
 
@@ -86,6 +125,11 @@ void launch_db_to_half(const float* db, const float* dnorm, int N, _Float16* dbh
                        hipStream_t s);
 int screen_q_pad(int Q);
 int screen_max_splits_a();
+size_t screen_part_bytes(int q_pad);   // pass A's output buffer
+// The launch plan of a MATCH call, as launch_match_screen makes it (host arithmetic, for tests that have to know which
+// tiles pass A samples): out = {one-sweep launch (0 / 1), tile_first, tile_stride, sampled tiles, pass A splits, pack bits,
+// pass B splits, pass B tiles}
+void screen_launch_plan(int Q, int q_expected, int N, int out[8]);
 // mode: -1 = decide by size, 0 = never, 1 = whenever the DB has an f16 image (mh_match_set_mode)
 bool screen_wanted(int q_expected, int N, int mode = -1);
 // Same contract as launch_match (match.hip): exact (idx1, d1, d2) per query.
