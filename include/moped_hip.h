@@ -179,12 +179,20 @@ void mh_screen_record_bounds(uint16_t value_bits, uint32_t row0, float tau, floa
  *                           on the 16x16x32 passes
  *   mh_match_incomplete     queries since the last reset for which a lane slot of pass A held more blocks above the
  *                           threshold than it keeps, so that pass C swept that slot's rows (bounded; never the brute-force
- *                           search mh_match_stats counts).  Synchronises the context's stream. */
+ *                           search mh_match_stats counts).  Synchronises the context's stream.
+ *   mh_screen_sample_values the values pass C names the rows of a sampled tile's record by, from the code it runs: for
+ *                           query q (host, [Q][128], normalised) and the two 8-row lane blocks row0[2 q], row0[2 q + 1]
+ *                           (row0 = 128 tile + 32 row block + 4 quarter; bit b = row row0 + (b & 3) + 16 (b >> 2)),
+ *                           out[q][8 block + b].  They are mh_screen_values(shape 2)'s, bit for bit. */
 float mh_screen_pack_value(float v, uint32_t id, int bits);
 float mh_screen_pack_pert(float qq, float dmax, int bits);
 void mh_screen_sample_bounds(uint16_t value_bits, float tau, float pert, float dmax, float* lo, float* hi);
 void mh_screen_launch_plan(int Q, int q_expected, int N, int32_t out[8]);
 int mh_match_incomplete(mh_ctx* ctx, uint32_t* count, int reset);
+int mh_screen_sample_values(mh_ctx* ctx, const float* q_host, int Q, const int32_t* row0_host, float* out_host);
+/* mh_match_stats' candidate rows -- rows that ran the canonical chain in pass C -- per query since the last reset:
+ * out[q] for the first Q queries of the context's two-stage launches.  Synchronises the context's stream. */
+int mh_match_query_candidates(mh_ctx* ctx, int Q, uint32_t* out);
 
 /* Device-pointer forms for a model-sharded DB: local top-2 of this shard
  * (idx carries index_base; -1 when the shard is empty), then the merge of S

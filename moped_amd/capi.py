@@ -125,6 +125,7 @@ EXPORTS = [
     "mh_sift_extract_batch_dev", "mh_sift_debug_plan", "mh_sift_debug_level", "mh_sift_debug_candidates",
     "mh_sift_debug_keys", "mh_sift_debug_blur",
     "mh_screen_pack_value", "mh_screen_pack_pert", "mh_screen_sample_bounds", "mh_screen_launch_plan", "mh_match_incomplete",
+    "mh_screen_sample_values", "mh_match_query_candidates",
 ]
 COMM_ID_BYTES = 128      # MH_COMM_ID_BYTES
 EX2_OBJECTS = 62         # MH_EX2_OBJECTS
@@ -295,6 +296,9 @@ def load():
         L.mh_screen_launch_plan.argtypes = [i32, i32, i32, vp]
         L.mh_screen_launch_plan.restype = None
         L.mh_match_incomplete.argtypes = [vp, C.POINTER(C.c_uint32), i32]
+    if hasattr(L, "mh_screen_sample_values"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
+        L.mh_screen_sample_values.argtypes = [vp, vp, i32, vp, vp]
+        L.mh_match_query_candidates.argtypes = [vp, i32, vp]
     L.mh_db_upload_blocks.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, i32, i32]
     L.mh_frame_block_stride.argtypes = [i32]
     L.mh_frame_block_stride.restype = C.c_size_t
@@ -609,6 +613,16 @@ class Context:
                                          int(shape)), "mh_screen_values")
         return out, dmax.value, spread.value
 
+    def screen_sample_values(self, qn, row0):
+        """mh_screen_sample_values: [Q][2][8] -- for query q the screen values of the 8 rows of the lane blocks row0[q][0]
+        and row0[q][1] (bit b = row row0 + (b & 3) + 16 (b >> 2)), from the code pass C names a sampled record's rows with."""
+        qn = np.ascontiguousarray(qn, np.float32)
+        row0 = np.ascontiguousarray(row0, np.int32)
+        assert row0.shape == (qn.shape[0], 2)
+        out = np.zeros((qn.shape[0], 2, 8), np.float32)
+        self._ck(self.L.mh_screen_sample_values(self.h, _ptr(qn), qn.shape[0], _ptr(row0), _ptr(out)), "mh_screen_sample_values")
+        return out
+
     def match_set_mode(self, mode: int):
         """-1 auto, 0 exact f32 kernels only, 1 two-stage (f16 screen + exact rescoring) whenever possible,
         2 / 3 the exact VALU / f32 matrix-pipe kernel whatever the query count."""
@@ -630,6 +644,12 @@ class Context:
         self._ck(self.L.mh_match_stats(self.h, int(Q), _ptr(st), int(reset)), "mh_match_stats")
         return {"candidates": int(st[0]), "brute_force_queries": int(st[1]), "queries": int(st[2]),
                 "two_stage": bool(st[3])}
+
+    def match_query_candidates(self, Q):
+        """mh_match_query_candidates: per query, the rows that ran pass C's canonical chain since the last match_stats reset."""
+        out = np.zeros(int(Q), np.uint32)
+        self._ck(self.L.mh_match_query_candidates(self.h, int(Q), _ptr(out)), "mh_match_query_candidates")
+        return out
 
     def match_incomplete(self, reset=False) -> int:
         """Queries since the last reset whose sampled-tile records were incomplete and that took pass C's bounded

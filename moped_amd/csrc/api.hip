@@ -694,6 +694,47 @@ int mh_screen_values(mh_ctx* ctx, const float* q_host, int Q, int n_rows, float*
   return rc;
 }
 
+int mh_screen_sample_values(mh_ctx* ctx, const float* q_host, int Q, const int32_t* row0_host, float* out_host) {
+  if (!ctx || !q_host || !row0_host || !out_host || Q <= 0) return MH_ERR_ARG;
+  if (!ctx->sdb.dbh) {
+    ctx->err = "mh_screen_sample_values: the database has no f16 image (fewer than 4096 rows?)";
+    return MH_ERR_ARG;
+  }
+  const int n_pad = (ctx->N + 127) / 128 * 128;
+  for (int i = 0; i < 2 * Q; ++i) {
+    const int r = row0_host[i];
+    if (r < 0 || (r & 3) || (r & 31) >= 16 || r + 19 >= n_pad) {
+      ctx->err = "mh_screen_sample_values: row0 is not the first row of a lane's block (32 b + 4 quarter) inside the padded DB";
+      return MH_ERR_ARG;
+    }
+  }
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
+  float *qd = nullptr, *out = nullptr;
+  int32_t* rd = nullptr;
+  int rc = MH_OK;
+  auto done = [&]() {
+    for (void* p : {(void*)qd, (void*)out, (void*)rd})
+      if (p) hipFree(p);
+  };
+  if (hipMalloc(&qd, (size_t)Q * DIM * 4) != hipSuccess || hipMalloc(&out, (size_t)Q * 16 * 4) != hipSuccess ||
+      hipMalloc(&rd, (size_t)Q * 2 * 4) != hipSuccess) {
+    done();
+    ctx->err = "mh_screen_sample_values: out of device memory";
+    return MH_ERR_HIP;
+  }
+  hipMemcpyAsync(qd, q_host, (size_t)Q * DIM * 4, hipMemcpyHostToDevice, ctx->stream);
+  hipMemcpyAsync(rd, row0_host, (size_t)Q * 2 * 4, hipMemcpyHostToDevice, ctx->stream);
+  launch_screen_sample_values(qd, Q, ctx->sdb, rd, out, ctx->stream);
+  if (hipMemcpyAsync(out_host, out, (size_t)Q * 16 * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+      hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
+    ctx->err = "mh_screen_sample_values: device error";
+    rc = MH_ERR_HIP;
+  }
+  done();
+  return rc;
+}
+
 int mh_match_set_mode(mh_ctx* ctx, int mode) {
   if (!ctx || mode < -1 || mode > 3) return MH_ERR_ARG;
   ctx->match_mode = mode;
@@ -731,6 +772,21 @@ int mh_match_stats(mh_ctx* ctx, int Q, uint32_t stats[4], int reset) {
     for (int k = 0; k < 3; ++k) stats[k] = (uint32_t)std::min<unsigned long long>(sum[k], 0xFFFFFFFFull);
     if (reset) MH_HIP(ctx, hipMemset(ctx->sbuf.stats, 0, h.size() * sizeof(unsigned int)));
   }
+  return MH_OK;
+}
+
+int mh_match_query_candidates(mh_ctx* ctx, int Q, uint32_t* out) {
+  if (!ctx || !out || Q <= 0) return MH_ERR_ARG;
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (!ctx->sbuf.stats || Q > ctx->sbuf.q_pad) {
+    ctx->err = "mh_match_query_candidates: no two-stage scratch for that many queries";
+    return MH_ERR_ARG;
+  }
+  std::vector<unsigned int> h((size_t)Q * 3);
+  MH_HIP(ctx, hipMemcpy(h.data(), ctx->sbuf.stats, h.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+  for (int q = 0; q < Q; ++q) out[q] = h[3 * (size_t)q];
   return MH_OK;
 }
 

@@ -319,11 +319,22 @@ __global__ void screen_tau_kernel(const float2* __restrict__ part, int n_splits_
 //   - T = (second largest packed value over all lists) - P <= the second largest block maximum of the sample <= the
 //     second largest screen value over distinct rows: tau = T - screen_margin is a valid threshold (header);
 //   - a block of a sampled tile whose maximum exceeds tau has a packed value v' > tau - P.  Either v' is among its lane
-//     slot's SC_TOPK largest -- then it becomes a record (all 8 rows of the block, value v' - tau) -- or it is not, and
+//     slot's SC_TOPK largest -- then it becomes a record (the block's 8 rows, not yet told apart; value v' - tau) -- or it is not, and
 //     then the slot's (SC_TOPK + 1)-th value is >= v' > tau - P and the query is marked INCOMPLETE for that lane slot:
 //     pass C runs the canonical chain over the slot's rows instead of its records (none is written for such a slot);
 //   - a padding row's screen value is -inf and a block of padding rows would pack into a NaN: block maxima are floored
 //     at SC_PACK_FLOOR, far below any real row's value, and anything that low counts as "no block" here.
+//   - which rows of a handed-over block get the exact treatment (pass C): screen_handover_kernel knows the block's packed
+//     maximum only, so its record's mask says "all 8 rows" (0xFF) and means "not evaluated".  For the records that
+//     survive its thinning, pass C RECOMPUTES the block's 8 screen values with pass A's arithmetic (sample_pair_values:
+//     the same v_mfma_f32_16x16x32_f16, accumulator seeded with the rows' -dd/2, four k-steps in ascending k, the same
+//     f16 operands; an element of the product does not depend on which row or column of the operand tiles it sits in) and
+//     keeps the rows with w~_r > tau.  These ARE the values pass A saw before it packed their maximum, i.e. values in an
+//     arithmetic the header's E covers (pass A's accumulators): a row of the exact top-2 has w~_r >= T - 2E - slack, so it
+//     is above tau -- the header's rule "every row above tau is emitted", applied to the sampled tiles as pass B applies it
+//     to the others; no new bound.  The mask can be EMPTY (the record test used tau - P: a packed maximum in
+//     (tau - P, tau] whose block has no row above tau): the record then leaves no candidate.
+//     tests/test_gpu_sample_mask.py holds the recomputed values against mh_screen_values(shape 2) bit for bit.
 // tests/test_screen_handover_cpu.py restates the lists and this kernel's decisions against the direct definition.
 constexpr int SC_TOPK = 4;
 constexpr int SC_PART5 = SC_TOPK + 1;           // floats per (lane slot, query) in `part5`
@@ -331,7 +342,7 @@ constexpr int SC_SA_SPLITS_MAX = 28;            // pass A splits of a one-sweep 
 constexpr int SC_PACK_BITS_MAX = 10;            // block numbers up to 1024 per lane slot: P <= 2^-13 of the largest screen value, a tenth of the margin
 constexpr float SC_PACK_FLOOR = -1e38f;
 constexpr unsigned SC_REC_LAYOUT16 = 0x80000000u;   // in a record's row word: the rows of the 16x16x32 passes
-constexpr unsigned SC_REC_SAMPLE = 0x40000000u; // in a record's row word: made by screen_handover_kernel (value = packed maximum - tau, all 8 rows)
+constexpr unsigned SC_REC_SAMPLE = 0x40000000u; // in a record's row word: made by screen_handover_kernel (value = packed maximum - tau; mask 0xFF = pass C names the rows above tau)
 
 // what pass C has to know about pass A's sweep to find a lane slot's rows again
 struct SampleGeom {
@@ -340,72 +351,129 @@ struct SampleGeom {
   int tile_first, tile_stride, tiles_base, tiles_rem, n_sel;
 };
 
-// One thread per query; the lane slots' values of neighbouring queries are neighbours in memory.
+// A workgroup = 64 queries along the lanes (the lane slots' values of neighbouring queries are neighbours in memory) x
+// blockDim.y parts; a thread loads the lists of ITS HS lane slots -- HS x SC_PART5 values, all in flight at once, kept
+// in registers -- and the parts of a query meet in LDS three times: the two largest packed values (-> tau), the
+// incomplete lane slots (the fifth values against tau - P), and the parts' record counts (-> where a part's records go:
+// in lane slot order, as one thread walking all lists would write them).
 // tau = +inf for queries that do not exist in this frame or that the screen cannot vouch for (pass B then leaves them
 // no records; pass C searches the latter by brute force).
-__global__ void screen_handover_kernel(const float* __restrict__ part5, int n_lane_slots, int q_pad, int Q,
-                                       const int32_t* __restrict__ q_count, const float* __restrict__ qnorm,
-                                       const uint8_t* __restrict__ qbad, float dmax, SampleGeom g, float* __restrict__ tau,
-                                       uint2* __restrict__ recs, unsigned int* __restrict__ inc) {
+constexpr int HO_PARTS_MAX = 16;
+template <int HS>
+__global__ __launch_bounds__(64 * HO_PARTS_MAX) void screen_handover_kernel(
+    const float* __restrict__ part5, int n_lane_slots, int q_pad, int Q, const int32_t* __restrict__ q_count,
+    const float* __restrict__ qnorm, const uint8_t* __restrict__ qbad, float dmax, SampleGeom g, float* __restrict__ tau,
+    uint2* __restrict__ recs, unsigned int* __restrict__ inc) {
   MH_TRACE_SCOPE(mh::TK_TAU);
-  const int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= q_pad) return;
+  __shared__ float s_b[HO_PARTS_MAX][64], s_s[HO_PARTS_MAX][64];
+  __shared__ int s_cnt[HO_PARTS_MAX][64];
+  __shared__ unsigned s_sm[64], s_qm[64];
+  const int ql = threadIdx.x, part = threadIdx.y, n_parts = blockDim.y;
+  const int q = blockIdx.x * 64 + ql;
   const int Qe = q_count ? min(Q, *q_count) : Q;
-  float t = __builtin_inff();
-  unsigned incw = 0;
-  if (q < Qe && !qbad[q]) {
-    auto val = [&](int ls, int k) {
-      const float v = part5[((size_t)ls * SC_PART5 + k) * q_pad + q];
-      return v < 0.5f * SC_PACK_FLOOR ? -__builtin_inff() : v;
-    };
-    float B = -__builtin_inff(), S = -__builtin_inff();
-#pragma unroll 4   // (the kernel is a chain of L2 round trips: four lane slots' loads in flight at a time)
-    for (int ls = 0; ls < n_lane_slots; ++ls) {
-      const float p1 = val(ls, 0), p2 = val(ls, 1);
-      S = fmaxf(fminf(B, p1), fmaxf(S, p2));
-      B = fmaxf(B, p1);
-    }
-    const float P = screen_pack_pert(qnorm[q], dmax, g.pack_bits);
-    t = S - P - screen_margin(qnorm[q], dmax);
-    if (g.sa_slots > 0 && t > -__builtin_inff()) {   // (t = -inf: pass B's lists overflow and pass C searches by brute force)
-      const float thr = t - P;
-      unsigned sm = 0, qm = 0;   // the incomplete lane slots, as (splits) x (quarters): a superset
-#pragma unroll 4
-      for (int ls = 0; ls < n_lane_slots; ++ls)
-        if (val(ls, SC_TOPK) > thr) {
-          sm |= 1u << (ls >> 2);
-          qm |= 1u << (ls & 3);
-        }
-      uint2* mine = recs + (size_t)q * SC_SLOT_PITCH + SC_SLOTS_MAX;
-      const unsigned id_mask = (1u << g.pack_bits) - 1u;
-      int n = 0;
-      bool full = false;
-      for (int ls = 0; ls < n_lane_slots && !full; ++ls) {
-        const int split = ls >> 2, quarter = ls & 3;
-        if (((sm >> split) & 1u) && ((qm >> quarter) & 1u)) continue;   // pass C sweeps this slot's rows
-        for (int k = 0; k < SC_TOPK; ++k) {
-          const float v = val(ls, k);
-          if (!(v > thr)) break;   // the list is sorted
-          if (n == g.sa_slots) {
-            full = true;
-            break;
-          }
-          const unsigned id = __float_as_uint(v) & id_mask;
-          const int sel = split * g.tiles_base + min(split, g.tiles_rem) + (int)(id >> 2);
-          const unsigned row0 = (unsigned)((g.tile_first + sel * g.tile_stride) * SC_TILE + (int)(id & 3u) * 32 + 4 * quarter);
-          mine[n++] = make_uint2(row0 | SC_REC_LAYOUT16 | SC_REC_SAMPLE, 0xFFu | ((unsigned)screen_record_value(v, t) << 16));
-        }
+  const bool live = q < q_pad && q < Qe && !qbad[q];
+  const int ls0 = part * HS;
+  float v[HS][SC_PART5];
+#pragma unroll
+  for (int j = 0; j < HS; ++j)
+#pragma unroll
+    for (int k = 0; k < SC_PART5; ++k)
+      v[j][k] = live && ls0 + j < n_lane_slots ? part5[((size_t)(ls0 + j) * SC_PART5 + k) * q_pad + q] : -__builtin_inff();
+  const float qq = live ? qnorm[q] : 0.f;
+  if (part == 0) {
+    s_sm[ql] = 0u;
+    s_qm[ql] = 0u;
+  }
+  float B = -__builtin_inff(), S = -__builtin_inff();
+#pragma unroll
+  for (int j = 0; j < HS; ++j) {
+#pragma unroll
+    for (int k = 0; k < SC_PART5; ++k) v[j][k] = v[j][k] < 0.5f * SC_PACK_FLOOR ? -__builtin_inff() : v[j][k];
+    S = fmaxf(fminf(B, v[j][0]), fmaxf(S, v[j][1]));
+    B = fmaxf(B, v[j][0]);
+  }
+  s_b[part][ql] = B;
+  s_s[part][ql] = S;
+  __syncthreads();
+  // (the second largest of all the parts' values: max and min only, the same number in any order)
+  B = S = -__builtin_inff();
+  for (int p = 0; p < n_parts; ++p) {
+    const float ob = s_b[p][ql], os = s_s[p][ql];
+    S = fmaxf(fminf(B, ob), fmaxf(S, os));
+    B = fmaxf(B, ob);
+  }
+  const float P = screen_pack_pert(qq, dmax, g.pack_bits);
+  const float t = live ? S - P - screen_margin(qq, dmax) : __builtin_inff();
+  const float thr = t - P;
+  // (t = -inf: pass B's lists overflow and pass C searches by brute force)
+  const bool hand = live && g.sa_slots > 0 && t > -__builtin_inff();
+  unsigned sm = 0, qm = 0;   // the incomplete lane slots, as (splits) x (quarters): a superset
+  if (hand) {
+#pragma unroll
+    for (int j = 0; j < HS; ++j)
+      if (v[j][SC_TOPK] > thr) {   // (no list behind the last lane slot: -inf)
+        sm |= 1u << ((ls0 + j) >> 2);
+        qm |= 1u << ((ls0 + j) & 3);
       }
-      if (full) {   // more records than slots (never seen): every lane slot's rows go to pass C's sweep instead
-        for (int j = 0; j < n; ++j) mine[j] = make_uint2(0u, 0u);
-        sm = (1u << (n_lane_slots >> 2)) - 1u;
-        qm = 0xFu;
-      }
-      if (sm) incw = sm | (qm << 28);
+    if (sm) {
+      atomicOr(&s_sm[ql], sm);
+      atomicOr(&s_qm[ql], qm);
     }
   }
-  tau[q] = t;
-  if (inc) inc[q] = incw;
+  __syncthreads();
+  sm = s_sm[ql];
+  qm = s_qm[ql];
+  // this part's records: of every lane slot pass C does not sweep, the listed blocks above tau - P (the lists are sorted)
+  int n_j[HS], cnt = 0;
+#pragma unroll
+  for (int j = 0; j < HS; ++j) {
+    const int ls = ls0 + j;
+    const bool swept = ((sm >> (ls >> 2)) & 1u) && ((qm >> (ls & 3)) & 1u);
+    n_j[j] = 0;
+    bool run = hand && !swept;
+#pragma unroll
+    for (int k = 0; k < SC_TOPK; ++k) {
+      run = run && v[j][k] > thr;
+      n_j[j] += run ? 1 : 0;
+    }
+    cnt += n_j[j];
+  }
+  s_cnt[part][ql] = cnt;
+  __syncthreads();
+  int before = 0, total = 0;
+  for (int p = 0; p < n_parts; ++p) {
+    const int c = s_cnt[p][ql];
+    before += p < part ? c : 0;
+    total += c;
+  }
+  // more records than slots (never seen): none is written, every lane slot's rows go to pass C's sweep instead
+  const bool full = total > g.sa_slots;
+  if (cnt && !full) {
+    uint2* mine = recs + (size_t)q * SC_SLOT_PITCH + SC_SLOTS_MAX + before;
+    const unsigned id_mask = (1u << g.pack_bits) - 1u;
+    int n = 0;
+#pragma unroll
+    for (int j = 0; j < HS; ++j) {
+      const int split = (ls0 + j) >> 2, quarter = (ls0 + j) & 3;
+#pragma unroll
+      for (int k = 0; k < SC_TOPK; ++k)
+        if (k < n_j[j]) {
+          const unsigned id = __float_as_uint(v[j][k]) & id_mask;
+          const int sel = split * g.tiles_base + min(split, g.tiles_rem) + (int)(id >> 2);
+          const unsigned row0 = (unsigned)((g.tile_first + sel * g.tile_stride) * SC_TILE + (int)(id & 3u) * 32 + 4 * quarter);
+          // (the mask says "all 8 rows": pass C names the rows above tau itself, for the records its thinning leaves)
+          mine[n++] = make_uint2(row0 | SC_REC_LAYOUT16 | SC_REC_SAMPLE, 0xFFu | ((unsigned)screen_record_value(v[j][k], t) << 16));
+        }
+    }
+  }
+  if (part == 0 && q < q_pad) {
+    if (full) {
+      sm = (1u << (n_lane_slots >> 2)) - 1u;
+      qm = 0xFu;
+    }
+    tau[q] = t;
+    if (inc) inc[q] = sm ? sm | (qm << 28) : 0u;
+  }
 }
 
 // Four LDS-DMA pieces (1 KB each: 16 bytes per lane to lds_i + lane * 16) in one statement: the source of piece i
@@ -1159,7 +1227,7 @@ constexpr int RS_STAGE = 8;          // candidate rows staged through LDS (8 x 5
 static_assert(RS_STAGE * DIM * 4 <= RS_MAXC * 4 && RS_STAGE % 2 == 0 && RS_STAGE <= 32, "staged rows live in the candidate list's LDS");
 
 __device__ __forceinline__ float exact_dist(const float* __restrict__ q_lds, const float* __restrict__ row, float nq, float dn) {
-  // 64 bytes x 2 in flight per step: 48 VGPRs, ten wavefronts per SIMD.  (Round 3: the whole 512-byte row in flight before
+  // 64 bytes x 2 in flight per step: 48 VGPRs here (the kernel around it: 64, eight wavefronts per SIMD).  (Round 3: the whole 512-byte row in flight before
   // the chain -- one round trip per row instead of four -- takes 160 VGPRs, three wavefronts per SIMD, and pass C went
   // from 0.047 to 0.071 ms per 24 000 queries: it lives on the number of queries in flight, not on one query's latency.)
   float s = 0.f;
@@ -1183,17 +1251,51 @@ __device__ __forceinline__ void wave_lds_sync() {   // LDS written by some lanes
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-__global__ __launch_bounds__(64 * RS_WAVES) void rescore_kernel(
+// The screen values of the 8 + 8 rows of two sampled blocks (records of screen_handover_kernel: rows row0 + r + 16 ti) for ONE
+// query, by pass A's arithmetic: one v_mfma_f32_16x16x32_f16 set, accumulator seeded with the rows' -dd/2, the four k-steps
+// in ascending k (screen16_kernel MODE 0, screen_values_kernel shape 2).  Operand row i = l & 15: block X's row bit i for
+// i < 8, block Y's row bit i - 8 above; lane l holds k = 32 s + 8 (l >> 4) + j as in the passes; the query -- the f16 of its
+// f32 coordinates, the conversion of screen_prepare_kernel -- sits in every column.  An element of the product depends on its
+// own row and column only, so these are the values pass A folded into the block's maximum.  Result: lane group g = l >> 4
+// holds operand rows 4 g .. 4 g + 3 = block g >> 1, mask bits 4 (g & 1) + r.
+__device__ __forceinline__ v4f sample_pair_values(const float* __restrict__ q_lds, const _Float16* __restrict__ dbh,
+                                                  const float* __restrict__ dneg, int row0x, int row0y, int lane) {
+  const int g = lane >> 4, i = lane & 15;
+  const int arow = (i < 8 ? row0x : row0y) + (i & 3) + 16 * ((i >> 2) & 1);
+  const half8* ap = reinterpret_cast<const half8*>(dbh + (size_t)arow * DIM + 8 * g);
+  half8 a[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) a[s] = ap[4 * s];
+  const int crow = (g < 2 ? row0x : row0y) + 16 * (g & 1);
+  const float4 c = *reinterpret_cast<const float4*>(dneg + (size_t)(crow >> 7) * SC_DD + (crow & 127));
+  v4f acc = {c.x, c.y, c.z, c.w};
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const float4 y0 = *reinterpret_cast<const float4*>(q_lds + 32 * s + 8 * g), y1 = *reinterpret_cast<const float4*>(q_lds + 32 * s + 8 * g + 4);
+    half8 b;
+    b[0] = (_Float16)y0.x; b[1] = (_Float16)y0.y; b[2] = (_Float16)y0.z; b[3] = (_Float16)y0.w;
+    b[4] = (_Float16)y1.x; b[5] = (_Float16)y1.y; b[6] = (_Float16)y1.z; b[7] = (_Float16)y1.w;
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[s], b, acc, 0, 0, 0);
+  }
+  return acc;
+}
+
+// (eight wavefronts per SIMD -- what the kernel's LDS allows -- instead of the five its 82 VGPRs would: 64 VGPRs and four
+// spilled registers; the kernel lives on queries in flight.  Config 1: 0.096 -> 0.085 ms)
+__global__ __launch_bounds__(64 * RS_WAVES) __attribute__((amdgpu_waves_per_eu(8, 8))) void rescore_kernel(
     const float* __restrict__ qn, const float* __restrict__ qnorm, const uint8_t* __restrict__ qbad, int Q,
     const int32_t* __restrict__ q_count, const float* __restrict__ db, const float* __restrict__ dnorm, int N,
     RowMap rmap, uint2* __restrict__ recs, int n_slots, int32_t* __restrict__ ovf_cnt, uint2* __restrict__ ovf,
     int ovf_cap, float dmax, const float* __restrict__ tau, float spread, int32_t* __restrict__ idx1, float* __restrict__ d1, float* __restrict__ d2,
     unsigned int* __restrict__ stats, int32_t zero_idx, float zero_d1, float zero_d2, SampleGeom g,
-    const unsigned int* __restrict__ inc, unsigned int* __restrict__ inc_count) {
+    const unsigned int* __restrict__ inc, unsigned int* __restrict__ inc_count, const _Float16* __restrict__ dbh,
+    const float* __restrict__ dneg) {
   MH_TRACE_SCOPE(mh::TK_PASS_C);
   __shared__ __attribute__((aligned(16))) float q_s[RS_WAVES][DIM];
   __shared__ __attribute__((aligned(16))) int cand_s[RS_WAVES][RS_MAXC];   // the candidate list, then RS_STAGE rows of them
   __shared__ int ncand_s[RS_WAVES];
+  __shared__ int samp_s[RS_WAVES][SC_SA_SLOTS];   // row0 of the sampled tiles' records that survive the thinning
+  __shared__ int nsamp_s[RS_WAVES];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int q = blockIdx.x * RS_WAVES + wave;
@@ -1246,7 +1348,10 @@ __global__ __launch_bounds__(64 * RS_WAVES) void rescore_kernel(
     }
     return;
   }
-  if (lane == 0) ncand_s[wave] = 0;
+  if (lane == 0) {
+    ncand_s[wave] = 0;
+    nsamp_s[wave] = 0;
+  }
   q_s[wave][2 * lane] = qv.x;
   q_s[wave][2 * lane + 1] = qv.y;
   // ---- records -> candidate row list in LDS; the slots read are emptied for the next frame ----
@@ -1307,6 +1412,13 @@ __global__ __launch_bounds__(64 * RS_WAVES) void rescore_kernel(
       // the 16x16x32 passes (bit 31 of the row word) 8 rows, row0 + (r & 3) + 16 (r >> 2)
       const int hi_stride = (rec.x & 0x80000000u) ? 16 : 8;
       const int row0 = (int)(rec.x & 0x3FFFFFFFu);
+      // a sampled tile's record names no rows (its mask is all 8): which of them lie above tau is found below, for the
+      // records that are still here
+      if (bits && (rec.x & SC_REC_SAMPLE)) {
+        const int w = atomicAdd(&nsamp_s[wave], 1);
+        if (w < SC_SA_SLOTS) samp_s[wave][w] = row0;
+        bits = 0;
+      }
       // candidates in any order (the exact top-2 below breaks ties by row number): an LDS counter hands out places
       while (bits) {
         const int r = __builtin_ctz(bits);
@@ -1316,6 +1428,27 @@ __global__ __launch_bounds__(64 * RS_WAVES) void rescore_kernel(
       }
     }
     wave_lds_sync();
+    // The surviving sampled records, two per MFMA set: the rows whose screen value -- pass A's own, see sample_pair_values --
+    // exceeds tau become candidates, as pass B's rule has it for every other tile; a record none of whose rows does (its
+    // packed maximum lay between tau - P and tau) leaves none.
+    const int n_samp = min(nsamp_s[wave], SC_SA_SLOTS), n_pad_rows = (N + SC_TILE - 1) / SC_TILE * SC_TILE;
+    for (int p = 0; p < n_samp; p += 2) {
+      const bool pair = p + 1 < n_samp;
+      const int rx = samp_s[wave][p], ry = samp_s[wave][pair ? p + 1 : p];
+      if (rx + 19 >= n_pad_rows || ry + 19 >= n_pad_rows) continue;   // (not a block of the DB: never written)
+      const v4f w = sample_pair_values(q_s[wave], dbh, dneg, rx, ry, lane);
+      const int grp = lane >> 4;
+      if ((lane & 15) == 0 && (grp < 2 || pair)) {
+        const int base = (grp < 2 ? rx : ry) + 16 * (grp & 1);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (w[r] > tau_q) {
+            const int at = atomicAdd(&ncand_s[wave], 1);
+            if (at < RS_MAXC) cand_s[wave][at] = base + r;
+          }
+      }
+    }
+    if (n_samp) wave_lds_sync();
     n_cand = ncand_s[wave];
     if (n_cand > RS_MAXC) brute = true;
   } else if (n_ovf > ovf_cap) {
@@ -1458,6 +1591,22 @@ __global__ __launch_bounds__(64) void screen_values_kernel(const _Float16* __res
   for (int r = 0; r < 16; ++r) out[(size_t)(q0 + l32) * n_rows + r0 + (r & 3) + 8 * (r >> 2) + 4 * half] = acc[r];
 }
 
+// The values pass C names a sampled record's rows by (sample_pair_values, the function rescore_kernel calls): one wavefront
+// per query and pair of blocks, out[q][8 block + bit].
+__global__ __launch_bounds__(64) void screen_sample_values_kernel(const float* __restrict__ qn, const _Float16* __restrict__ dbh,
+                                                                  const float* __restrict__ dneg, const int32_t* __restrict__ row0,
+                                                                  float* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) float q_s[DIM];
+  const int lane = threadIdx.x, q = blockIdx.x;
+  const float2 qv = reinterpret_cast<const float2*>(qn + (size_t)q * DIM)[lane];
+  q_s[2 * lane] = qv.x;
+  q_s[2 * lane + 1] = qv.y;
+  __syncthreads();
+  const v4f w = sample_pair_values(q_s, dbh, dneg, row0[2 * q], row0[2 * q + 1], lane);
+  if ((lane & 15) == 0)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) out[(size_t)q * 16 + 4 * (lane >> 4) + r] = w[r];
+}
 
 }  // namespace
 
@@ -1497,6 +1646,10 @@ void launch_screen_values(const _Float16* qh, int Q, const ScreenDb& sdb, int n_
   if (Q <= 0 || n_rows <= 0) return;
   const int shape16 = shape == 2 || (shape == 0 && SC_SHAPE16_LARGE);
   hipLaunchKernelGGL(screen_values_kernel, dim3(Q / 32, n_rows / 32), dim3(64), 0, s, qh, sdb.dbh, sdb.dneg, n_rows, out, shape16);
+}
+void launch_screen_sample_values(const float* qn, int Q, const ScreenDb& sdb, const int32_t* row0, float* out, hipStream_t s) {
+  if (Q <= 0) return;
+  hipLaunchKernelGGL(screen_sample_values_kernel, dim3(Q), dim3(64), 0, s, qn, sdb.dbh, sdb.dneg, row0, out);
 }
 void launch_screen_prepare(const float* qn, const float* qnorm, int Q, int q_pad, _Float16* qh, uint8_t* qbad, hipStream_t s) {
   hipLaunchKernelGGL(screen_prepare_kernel, dim3((q_pad * 16 + 255) / 256), dim3(256), 0, s, qn, qnorm, Q, (const int32_t*)nullptr,
@@ -1684,9 +1837,15 @@ void launch_passes16(ScreenArgs a, int Q, int qe, int n_tiles, int sample, int b
   hipLaunchKernelGGL((screen16_kernel<0, NQB>), dim3(nqb * p.Sa), dim3(512), SC_LDS16_BYTES, s, a);
   if (ev) hipEventRecord(ev[2], s);
   SampleGeom g = {p.onesweep ? SC_SA_SLOTS : 0, p.pack_bits, a.tile_first, a.tile_stride, a.tiles_base, a.tiles_rem, a.n_sel};
-  // (one wavefront per workgroup: 768 workgroups for config 1's 49 152 queries, where 192 of 256 threads left a quarter of the compute units idle)
-  hipLaunchKernelGGL(screen_handover_kernel, dim3((a.q_pad + 63) / 64), dim3(64), 0, s, (const float*)a.part5, 4 * p.Sa, a.q_pad,
-                     a.Q, a.q_count, a.qnorm, a.qbad, a.dmax, g, const_cast<float*>(a.tau), a.recs, inc);
+  // 64 queries per workgroup, one wavefront per split of pass A (its four lane slots) -- or per two splits when pass A has
+  // more than HO_PARTS_MAX
+  static_assert(SC_SA_SPLITS_MAX <= 2 * HO_PARTS_MAX, "a thread of screen_handover_kernel holds at most 8 lane slots");
+  if (p.Sa <= HO_PARTS_MAX)
+    hipLaunchKernelGGL(screen_handover_kernel<4>, dim3((a.q_pad + 63) / 64), dim3(64, p.Sa), 0, s, (const float*)a.part5, 4 * p.Sa,
+                       a.q_pad, a.Q, a.q_count, a.qnorm, a.qbad, a.dmax, g, const_cast<float*>(a.tau), a.recs, inc);
+  else
+    hipLaunchKernelGGL(screen_handover_kernel<8>, dim3((a.q_pad + 63) / 64), dim3(64, (p.Sa + 1) / 2), 0, s, (const float*)a.part5,
+                       4 * p.Sa, a.q_pad, a.Q, a.q_count, a.qnorm, a.qbad, a.dmax, g, const_cast<float*>(a.tau), a.recs, inc);
 #ifdef MH_EXPERIMENTS
   // what the records cost pass B: thresholds no value reaches (WRONG results: timing only)
   if (exp_int("MH_SCREEN_NO_HITS", 0)) hipMemsetAsync(const_cast<float*>(a.tau), 0x7f, (size_t)a.q_pad * sizeof(float), s);
@@ -1819,7 +1978,7 @@ void launch_match_screen(const float* qn, const float* qnorm, int Q, const float
   hipLaunchKernelGGL(rescore_kernel, dim3((Q + RS_WAVES - 1) / RS_WAVES), dim3(64 * RS_WAVES), 0, s, qn, qnorm, sb.qbad, Q,
                      q_count, db, dnorm, N, rmap, sb.recs, n_slots, sb.ovf_cnt, sb.ovf, sb.ovf_cap, sdb.dmax, (const float*)sb.tau, sdb.spread, idx1, d1, d2,
                      sb.stats, sdb.zero_idx, sdb.zero_d1, sdb.zero_d2, geom, geom.sa_slots > 0 ? (const unsigned int*)sb.inc : nullptr,
-                     sb.inc ? sb.inc + sb.q_pad : nullptr);
+                     sb.inc ? sb.inc + sb.q_pad : nullptr, sdb.dbh, sdb.dneg);
   if (sb.ev) hipEventRecord(sb.ev[5], s);
 }
 

@@ -116,6 +116,10 @@ float screen_margin_host(float qq, float dmax);   // tau = T - margin (the error
 // the queries' f16 image).  For tests of the error model against the HARDWARE's accumulation (mh_screen_values).
 // shape: 0 = the instruction the large launches use, 1 = v_mfma_f32_32x32x16_f16, 2 = v_mfma_f32_16x16x32_f16
 void launch_screen_values(const _Float16* qh, int Q, const ScreenDb& sdb, int n_rows, float* out, hipStream_t s, int shape);
+// What pass C names the rows of a sampled tile's record by: for query q (device, [Q][128] f32, normalised) the screen values of
+// the 8 + 8 rows of the blocks row0[2 q] and row0[2 q + 1] (a record's row0: tile x 128 + 32 row block + 4 quarter; bit b =
+// row row0 + (b & 3) + 16 (b >> 2)), out[q][8 block + bit], by the code rescore_kernel runs (mh_screen_sample_values).
+void launch_screen_sample_values(const float* qn, int Q, const ScreenDb& sdb, const int32_t* row0, float* out, hipStream_t s);
 void launch_screen_prepare(const float* qn, const float* qnorm, int Q, int q_pad, _Float16* qh, uint8_t* qbad, hipStream_t s);
 size_t screen_db_half_elems(int N);
 size_t screen_dneg_elems(int N);   // floats of the -dd/2 array: 192 per 128-row tile (rows, row blocks' extrema)
