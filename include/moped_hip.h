@@ -10,6 +10,7 @@
  *
  * What each entry point replaces (paths relative to moped2/libmoped/):
  *   mh_db_upload        MATCH_ANN_CPU::Update            src/match/MATCH_ANN_CPU.hpp:72-109
+ *   mh_db_splice        Moped::addModel / removeModel    src/moped.cpp:139-159 (+ the Update() they trigger)
  *   mh_normalize        MATCH_ANN_CPU::norm              src/match/MATCH_ANN_CPU.hpp:54-57
  *   mh_match            MATCH_ANN_CPU::process search    src/match/MATCH_ANN_CPU.hpp:155-165
  *                       (= MATCH_FLANN_CPU::process      src/match/MATCH_FLANN_CPU.hpp:133-191)
@@ -103,6 +104,59 @@ int mh_db_size(const mh_ctx* ctx, int* N, int* n_models);
  * user; a later mh_db_upload into either context gives that context a new store of its own and leaves
  * the other one's untouched.  Frames already enqueued on `dst` finish on its old database first. */
 int mh_db_share(mh_ctx* dst, mh_ctx* src);
+
+/* ---- edits of the resident database: addModel / removeModel (src/moped.cpp:139-159) ------------------------------
+ * The reference serves a change of the model set by rebuilding its kd-tree over all models (modelsUpdated() ->
+ * MATCH_ANN_CPU::Update, src/match/MATCH_ANN_CPU.hpp:72-109).  Here one model is added, replaced or removed ON THE
+ * DEVICE, while the other contexts' frames keep flowing.  All three are one splice of the row array,
+ *   new = old[0, b) ++ rows ++ old[e, N),
+ * and what an edit leaves equals, byte for byte, what mh_db_upload_raw makes of the same rows.
+ *
+ * Editable: a store whose rows are grouped by model in ascending order (empty models allowed), uploaded in one block
+ * with index_base 0 -- or no store at all (an empty one).  Every entry point below returns MH_ERR_ARG on anything
+ * else, and on a model index out of range, before anything is launched; the store is then as it was.  Sharded stores
+ * (index_base != 0, mh_db_upload_blocks) are not editable: every rank's global rows would have to move together. */
+enum { MH_DB_INSERT = 0, MH_DB_REPLACE = 1, MH_DB_REMOVE = 2 };
+/* Rows of model `model` of the context's store: [*row_begin, *row_begin + *n_rows). */
+int mh_db_model_rows(const mh_ctx* ctx, int model, int32_t* row_begin, int32_t* n_rows);
+/* INSERT: the n_rows rows become model `model` (0 .. n_models; n_models = append, what addModel does for a new name,
+ *   moped.cpp:146); later models move up by one.
+ * REPLACE: model `model` gets these rows and keeps its index (addModel with a known name, moped.cpp:141-144).
+ * REMOVE: model `model` leaves, later models move down by one (removeModel, moped.cpp:152-159); desc / xyz unused.
+ * desc [n_rows][128], xyz [n_rows][3]: host pointers, or device pointers with on_device != 0 (e.g. the rows
+ * mh_frame_features_dev hands out).  normalize != 0: the rows are raw and are L2-normalised on the device
+ * (MATCH_ANN_CPU.hpp:94), else they are normalised already, as for mh_db_upload.
+ *
+ * Ordered on the context's stream: frames this context enqueued before the edit finish on the old arrays, frames
+ * enqueued after it search the new ones.  The one host wait is the read-back of the statistics words, as in
+ * mh_db_upload.  The edit fills a second buffer set and the context flips to it; contexts that share the old store
+ * keep it, untouched, until they adopt the new one (mh_db_adopt).  The per-frame capacities of the context follow
+ * the new model count at its next frame unless mh_db_reserve sized them. */
+int mh_db_splice(mh_ctx* ctx, int op, int model, const float* desc, const float* xyz, int n_rows, int normalize,
+                 int on_device);
+/* Capacity for edits: the live buffer set and one spare for max_rows rows each, staging for the new rows of an edit
+ * (up to 65536; larger models grow it), and -- through mh_reserve / mh_reserve_batch called AFTER this -- per-model
+ * tables for max_models models.  Inside that capacity an edit allocates and frees nothing: it fills the spare, and
+ * the set it retires becomes the spare once its last holder has let go.  If the spare is still held (contexts that
+ * have not adopted the previous edit), the edit allocates a fresh set; a retired set beyond the one spare is freed,
+ * and THAT FREE STALLS THE DEVICE (hipFree waits for all of it).  Callable with or without a store. */
+int mh_db_reserve(mh_ctx* ctx, int64_t max_rows, int max_models);
+/* Stream-ordered mh_db_share: `dst` takes the store `src` holds now without blocking the host.  dst's stream waits
+ * for the event the edit recorded; dst's frames in flight finish on the store it had, which dst holds until an event
+ * recorded on its own stream here has completed (polled at dst's later calls, waited for in mh_destroy). */
+int mh_db_adopt(mh_ctx* dst, mh_ctx* src);
+/* Edits since the upload of the store the context holds: a host sees which contexts have yet to adopt. */
+int mh_db_generation(const mh_ctx* ctx, uint64_t* generation);
+/* For tests and measurements, in the style of mh_sift_debug_*.  which: 0 desc [rows padded to 128][128] f32, 1 norm
+ * [padded], 2 xyz [N][3], 3 model [N], 4 desc_h [padded][128] f16, 5 neg_h [padded / 128][192] f32 (4, 5: nothing when
+ * the store has no f16 image).  bytes beyond what the store defines -> MH_ERR_ARG.  Synchronises the context. */
+int mh_db_debug_fetch(mh_ctx* ctx, int which, void* out_host, size_t bytes);
+/* {bits of dmax, bits of spread, zero_idx, bits of zero_d1, bits of zero_d2, usable, has an f16 image, N} */
+int mh_db_debug_screen(mh_ctx* ctx, uint32_t out[8]);
+/* 0: edits run the fused pass (default); 1: device copies + the upload's preparation (the route it is measured against) */
+int mh_db_debug_route(mh_ctx* ctx, int route);
+/* Device time of the last edit's pass over the rows (after mh_enable_timing), without staging and aggregates. */
+int mh_db_edit_ms(mh_ctx* ctx, float* ms);
 
 /* ---- MATCH ---------------------------------------------------------------- */
 
@@ -831,6 +885,8 @@ int mh_models_load(mh_model_set** out, const char* path);
  * uploads their rows, L2-normalises them on the device (A1) and sets index_base to the
  * first row, so row and model ids stay global. */
 int mh_db_upload_models(mh_ctx* ctx, const mh_model_set* s, int first_model, int n_models);
+/* mh_db_splice with the rows of model `set_index` of a parsed set, normalised on the device (s unused for REMOVE). */
+int mh_db_splice_models(mh_ctx* ctx, int op, int model, const mh_model_set* s, int set_index);
 /* mh_db_upload with the normalisation done on the device (normalize != 0). */
 int mh_db_upload_raw(mh_ctx* ctx, const float* desc_host, const int32_t* model_of_host,
                      const float* xyz_host, int N, int n_models, int32_t index_base, int normalize);

@@ -110,6 +110,8 @@ EXPORTS = [
     "mh_models_create", "mh_models_destroy", "mh_models_last_error", "mh_models_add_xml",
     "mh_models_add_xml_buffer", "mh_models_count", "mh_models_rows", "mh_models_name", "mh_models_range",
     "mh_models_desc", "mh_models_xyz", "mh_models_save", "mh_models_load", "mh_db_upload_models",
+    "mh_db_splice", "mh_db_reserve", "mh_db_adopt", "mh_db_generation", "mh_db_model_rows", "mh_db_splice_models",
+    "mh_db_debug_fetch", "mh_db_debug_screen", "mh_db_debug_route", "mh_db_edit_ms",
     "mh_db_upload_raw", "mh_db_share", "mh_match_stats", "mh_match_set_mode", "mh_match_launches", "mh_pose_set_split", "mh_frame_fetch_match_points", "mh_screen_margin", "mh_frame_counters", "mh_match_timing", "mh_frame_set_images", "mh_filter_images",
     "mh_pose_ransac_images",
     "mh_comm_unique_id", "mh_comm_create", "mh_comm_create_all", "mh_comm_create_host", "mh_comm_destroy", "mh_comm_info",
@@ -131,6 +133,8 @@ COMM_ID_BYTES = 128      # MH_COMM_ID_BYTES
 EX2_OBJECTS = 62         # MH_EX2_OBJECTS
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)   # mh_allgather_fn
 
+DIM = 128   # MH_DESC_DIM
+DB_INSERT, DB_REPLACE, DB_REMOVE = 0, 1, 2   # MH_DB_*
 _lib = None
 
 
@@ -244,6 +248,16 @@ def load():
     L.mh_frame_fetch.argtypes = [vp, vp, i32, C.POINTER(C.c_int32), vp]
     L.mh_frame_result_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
     L.mh_db_share.argtypes = [vp, vp]
+    L.mh_db_splice.argtypes = [vp, i32, i32, vp, vp, i32, i32, i32]
+    L.mh_db_reserve.argtypes = [vp, C.c_int64, i32]
+    L.mh_db_adopt.argtypes = [vp, vp]
+    L.mh_db_generation.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.mh_db_model_rows.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.mh_db_splice_models.argtypes = [vp, i32, i32, vp, i32]
+    L.mh_db_debug_fetch.argtypes = [vp, i32, vp, C.c_size_t]
+    L.mh_db_debug_screen.argtypes = [vp, vp]
+    L.mh_db_debug_route.argtypes = [vp, i32]
+    L.mh_db_edit_ms.argtypes = [vp, C.POINTER(f32)]
     L.mh_match_stats.argtypes = [vp, i32, vp, i32]
     L.mh_match_set_mode.argtypes = [vp, i32]
     L.mh_match_launches.argtypes = [vp, vp]
@@ -580,6 +594,79 @@ class Context:
     def db_share(self, src: "Context"):
         """Use the database `src` holds (no copy; one store per GPU for all frames in flight)."""
         self._ck(self.L.mh_db_share(self.h, src.h), "mh_db_share")
+
+    # ---- edits of the resident DB (mh_db_splice and friends) ----
+    def db_splice(self, op, model, desc=None, xyz=None, normalize=False, on_device=False, n_rows=None):
+        """mh_db_splice: op = DB_INSERT / DB_REPLACE / DB_REMOVE of model `model`.  desc [n][128], xyz [n][3]: host
+        arrays, or device pointers (ints) with on_device and n_rows."""
+        if op == DB_REMOVE:
+            self._ck(self.L.mh_db_splice(self.h, op, int(model), None, None, 0, 0, 0), "mh_db_splice")
+            return
+        if on_device:
+            self._ck(self.L.mh_db_splice(self.h, op, int(model), C.c_void_p(desc), C.c_void_p(xyz), int(n_rows),
+                                         int(normalize), 1), "mh_db_splice")
+            return
+        desc = np.ascontiguousarray(desc, np.float32).reshape(-1, DIM)
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        assert desc.shape[0] == xyz.shape[0]
+        self._ck(self.L.mh_db_splice(self.h, op, int(model), _ptr(desc), _ptr(xyz), desc.shape[0], int(normalize), 0),
+                 "mh_db_splice")
+
+    def db_splice_models(self, op, model, models: "ModelSet | None" = None, set_index=0):
+        """mh_db_splice_models: the rows of model `set_index` of a parsed set, normalised on the device."""
+        self._ck(self.L.mh_db_splice_models(self.h, op, int(model), models.h if models is not None else None, int(set_index)),
+                 "mh_db_splice_models")
+
+    def db_reserve(self, max_rows, max_models):
+        self._ck(self.L.mh_db_reserve(self.h, int(max_rows), int(max_models)), "mh_db_reserve")
+
+    def db_adopt(self, src: "Context"):
+        """Stream-ordered db_share: take the store `src` holds now; no host wait."""
+        self._ck(self.L.mh_db_adopt(self.h, src.h), "mh_db_adopt")
+
+    def db_generation(self) -> int:
+        g = C.c_uint64(0)
+        self._ck(self.L.mh_db_generation(self.h, C.byref(g)), "mh_db_generation")
+        return int(g.value)
+
+    def db_size(self):
+        n, m = C.c_int(0), C.c_int(0)
+        self._ck(self.L.mh_db_size(self.h, C.byref(n), C.byref(m)), "mh_db_size")
+        return n.value, m.value
+
+    def db_model_rows(self, model):
+        """(row_begin, n_rows) of a model of the resident store."""
+        b, n = C.c_int32(0), C.c_int32(0)
+        self._ck(self.L.mh_db_model_rows(self.h, int(model), C.byref(b), C.byref(n)), "mh_db_model_rows")
+        return b.value, n.value
+
+    def db_debug_screen(self) -> dict:
+        """ScreenDb's scalars as bit patterns (mh_db_debug_screen)."""
+        o = np.zeros(8, np.uint32)
+        self._ck(self.L.mh_db_debug_screen(self.h, _ptr(o)), "mh_db_debug_screen")
+        names = ("dmax_bits", "spread_bits", "zero_idx", "zero_d1_bits", "zero_d2_bits", "usable", "has_image", "N")
+        return dict(zip(names, (int(v) for v in o)))
+
+    def db_debug_fetch(self, which: str) -> np.ndarray:
+        """Everything the store defines of one array, as raw bytes viewed in the array's type: 'desc', 'norm', 'xyz',
+        'model', 'desc_h' (uint16 bit patterns), 'neg_h' (the last two empty when the store has no f16 image)."""
+        sc = self.db_debug_screen()
+        N, img = sc["N"], sc["has_image"]
+        n_pad = (N + 127) // 128 * 128
+        k, dt, n = {"desc": (0, np.float32, n_pad * DIM), "norm": (1, np.float32, n_pad), "xyz": (2, np.float32, N * 3),
+                    "model": (3, np.int32, N), "desc_h": (4, np.uint16, n_pad * DIM if img else 0),
+                    "neg_h": (5, np.float32, n_pad // 128 * 192 if img else 0)}[which]
+        out = np.zeros(n, dt)
+        self._ck(self.L.mh_db_debug_fetch(self.h, k, _ptr(out), out.nbytes), "mh_db_debug_fetch")
+        return out
+
+    def db_debug_route(self, route: int):
+        self._ck(self.L.mh_db_debug_route(self.h, int(route)), "mh_db_debug_route")
+
+    def db_edit_ms(self) -> float:
+        ms = C.c_float(0)
+        self._ck(self.L.mh_db_edit_ms(self.h, C.byref(ms)), "mh_db_edit_ms")
+        return float(ms.value)
 
     def frame_counters(self) -> dict:
         """Device-side counters of the last frame on this context (see mh_frame_counters)."""
@@ -1419,6 +1506,10 @@ class ModelSet:
         """Update() for a block of models: rows normalised on the device, ids stay global."""
         n_models = self.n_models - first_model if n_models is None else n_models
         ctx._ck(self.L.mh_db_upload_models(ctx.h, self.h, first_model, n_models), "mh_db_upload_models")
+
+    def splice(self, ctx: "Context", op: int, model: int, set_index: int = 0):
+        """addModel / removeModel on the resident DB: model `set_index` of this set -> Context.db_splice_models."""
+        ctx.db_splice_models(op, model, self, set_index)
 
     def close(self):
         if self.h:

@@ -14,6 +14,7 @@ using namespace mh;
 namespace mh {
 
 int use_stream(mh_ctx* ctx) {
+  if (!ctx->held.empty()) db_poll_held(ctx, false);
   if (ctx->stream) return MH_OK;
   if (!ctx->own_stream) MH_HIP(ctx, hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
   ctx->stream = ctx->own_stream;
@@ -50,7 +51,7 @@ static void free_screen_bufs(mh_ctx* ctx) {
 }
 
 // the context's view of its store
-static void bind_store(mh_ctx* ctx) {
+void bind_store(mh_ctx* ctx) {
   const DbStore* st = ctx->store.get();
   ctx->N = st ? st->N : 0;
   ctx->n_models = st ? st->n_models : 0;
@@ -201,7 +202,13 @@ void mh_destroy(mh_ctx* ctx) {
   mh_free_undistort_state(ctx);
   free_screen_bufs(ctx);
   mh::free_exchange(ctx);
+  db_poll_held(ctx, true);
+  for (hipEvent_t e : ctx->held_events) hipEventDestroy(e);
+  for (hipEvent_t e : ctx->db_ev)
+    if (e) hipEventDestroy(e);
+  if (ctx->db_stage) hipFree(ctx->db_stage);
   ctx->store.reset();   // the DB goes with its last user
+  ctx->pool.reset();
   void* ptrs[] = {ctx->q_desc, ctx->q_norm,
                   ctx->q_uv,    ctx->nn_idx,  ctx->nn_d1,  ctx->nn_d2,    ctx->match_scratch,
                   ctx->scratch, ctx->match_pack, ctx->rules.ratio_table, ctx->rules.inv_size, ctx->rules.cnt,
@@ -328,12 +335,19 @@ int mh_db_upload_raw(mh_ctx* ctx, const float* desc_host, const int32_t* model_o
     if (ctx) ctx->err = "mh_db_upload: bad argument";
     return MH_ERR_ARG;
   }
-  // every later kernel indexes per-model tables with these values
-  for (int i = 0; i < N; ++i)
+  // every later kernel indexes per-model tables with these values; an edit (db_edit.hip) needs the rows grouped by
+  // model in ascending order, and then each model's row range
+  bool grouped = true;
+  std::vector<int32_t> model_begin((size_t)n_models + 1, 0);
+  for (int i = 0; i < N; ++i) {
     if (model_of_host[i] < 0 || model_of_host[i] >= n_models) {
       ctx->err = "mh_db_upload: model_of value outside [0, n_models)";
       return MH_ERR_ARG;
     }
+    if (i > 0 && model_of_host[i] < model_of_host[i - 1]) grouped = false;
+    ++model_begin[model_of_host[i] + 1];
+  }
+  for (int m = 0; m < n_models; ++m) model_begin[m + 1] += model_begin[m];
   MH_HIP(ctx, hipSetDevice(ctx->device));
   if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -341,12 +355,14 @@ int mh_db_upload_raw(mh_ctx* ctx, const float* desc_host, const int32_t* model_o
   // +inf norm terms (a padding row can never enter a top-2)
   const size_t Npad = ((size_t)N + 127) / 128 * 128;
   if (!ctx->store || ctx->store.use_count() > 1) {   // other contexts read the old store: leave it alone
-    ctx->store = std::make_shared<DbStore>();
-    ctx->store->device = ctx->device;
+    ctx->store = make_store(ctx->device);
   }
   DbStore* st = ctx->store.get();
   st->N = 0;
   st->screen = ScreenDb();
+  st->grouped = grouped;
+  st->model_begin = grouped ? std::move(model_begin) : std::vector<int32_t>();
+  st->generation = 0;
   bind_store(ctx);
   if (Npad > st->cap) {
     st->cap = 0;   // until every array has its new size
@@ -393,17 +409,7 @@ int mh_db_upload_raw(mh_ctx* ctx, const float* desc_host, const int32_t* model_o
       unsigned int h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
       MH_HIP(ctx, hipMemcpyAsync(h, st->stats, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
       MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      float dd_max, x_max;
-      std::memcpy(&dd_max, &h[0], 4);
-      std::memcpy(&x_max, &h[1], 4);
-      st->screen.dbh = st->desc_h;
-      st->screen.dneg = st->neg_h;
-      st->screen.dmax = std::sqrt(dd_max);
-      std::memcpy(&st->screen.spread, &h[3], 4);   // (0 for a DB of fewer than 32 rows: no whole block, never used)
-      st->screen.zero_idx = (int32_t)h[4];
-      std::memcpy(&st->screen.zero_d1, &h[5], 4);
-      std::memcpy(&st->screen.zero_d2, &h[6], 4);
-      st->screen.usable = h[2] == 0 && x_max < 60000.f;   // (a NaN coordinate reads as a huge bit pattern: not < 60000)
+      screen_from_stats(st, h);
     }
   }
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -465,6 +471,8 @@ int mh_db_share(mh_ctx* dst, mh_ctx* src) {
   if (dst->stream) MH_HIP(dst, hipStreamSynchronize(dst->stream));   // frames of dst still reading its old DB
   if (src->stream) MH_HIP(src, hipStreamSynchronize(src->stream));   // the upload into src has completed (it is synchronous) -- cheap
   dst->store = src->store;
+  dst->pool = src->pool;   // (the buffer sets of later edits, and what mh_db_reserve asked the per-model tables for)
+  dst->db_models_reserved = src->db_models_reserved;
   bind_store(dst);
   return MH_OK;
 }

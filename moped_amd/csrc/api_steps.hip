@@ -789,7 +789,8 @@ int mh_reserve(mh_ctx* ctx, int max_queries, int max_clusters, int max_objects) 
   if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
   int rc = ensure_frame_buffers(ctx, max_queries);
   if (rc) return rc;
-  return ensure_fs(ctx, ctx->max_q, max_clusters, max_objects, ctx->n_models);
+  // (after mh_db_reserve: per-model tables for as many models as the edits may bring, so that no frame reallocates them)
+  return ensure_fs(ctx, ctx->max_q, max_clusters, max_objects, std::max(ctx->n_models, ctx->db_models_reserved));
 }
 
 int mh_reserve_batch(mh_ctx* ctx, int queries_per_frame, int frames, int max_clusters, int max_objects) {
@@ -800,7 +801,7 @@ int mh_reserve_batch(mh_ctx* ctx, int queries_per_frame, int frames, int max_clu
   int rc = ensure_frame_buffers(ctx, queries_per_frame * frames);
   if (rc) return rc;
   if ((rc = ensure_match_scratch(ctx, queries_per_frame * frames))) return rc;
-  return ensure_fs(ctx, queries_per_frame, max_clusters, max_objects, ctx->n_models, frames);
+  return ensure_fs(ctx, queries_per_frame, max_clusters, max_objects, std::max(ctx->n_models, ctx->db_models_reserved), frames);
 }
 
 void mh_frame_default_params(mh_frame_params* p) {

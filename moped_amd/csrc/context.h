@@ -2,7 +2,10 @@
 // MATCH_ANN_CPU keeps between frames, MATCH_ANN_CPU.hpp:70) plus the per-frame
 // device buffers.  Everything lives in HBM; host pointers only at the C ABI.
 #pragma once
+#include <cmath>
+#include <cstring>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -13,7 +16,20 @@
 // The model database in HBM.  Contexts (= frames in flight) of one device may share one store
 // (mh_db_share): one upload and one copy per GPU instead of one per frame slot, and one set of lines in
 // the Infinity Cache for all frames in flight.  A store that is shared is never resized or rewritten:
-// an upload into a context whose store has other users gives that context a fresh store.
+// an upload into a context whose store has other users gives that context a fresh store.  An edit (db_edit.hip) never
+// writes the live store either: it fills a second buffer set and the editing context flips to it.
+struct DbStore;
+
+// The buffer sets of one edited database: the reserved capacity and one idle set (the spare) that the next edit writes.
+// Shared by the contexts that share the store; a set parks here when its last holder lets go of it (retire_store).
+struct DbPool {
+  std::mutex mu;
+  size_t cap_rows = 0;       // mh_db_reserve: rows every new set is allocated for (0: as many as the edit needs)
+  int max_models = 0;        // mh_db_reserve: models the contexts' per-model tables are sized for
+  DbStore* spare = nullptr;  // idle set, owned
+  ~DbPool();
+};
+
 struct DbStore {
   int device = 0;
   int N = 0, n_models = 0;
@@ -31,15 +47,62 @@ struct DbStore {
   size_t cap_h = 0;            // elements allocated
   unsigned int* stats = nullptr;
   mh::ScreenDb screen;
+  // what an edit needs to know (host side): the rows are grouped by model in ascending order, and then model m's rows
+  // are [model_begin[m], model_begin[m + 1]) (empty models allowed)
+  bool grouped = false;
+  std::vector<int32_t> model_begin;   // [n_models + 1] when grouped
+  uint64_t generation = 0;            // edits since the upload (mh_db_generation)
+  hipEvent_t ready = nullptr;         // recorded behind the edit that filled this set (mh_db_adopt waits on it)
+  std::shared_ptr<DbPool> pool;       // where the set parks when its last holder lets go (none: it is freed)
   ~DbStore() {
     int cur = 0;
     const bool have = hipGetDevice(&cur) == hipSuccess;
     hipSetDevice(device);
     for (void* p : {(void*)desc, (void*)norm, (void*)xyz, (void*)model, (void*)desc_h, (void*)neg_h, (void*)stats, (void*)blk_glo, (void*)blk_llo})
       if (p) hipFree(p);
+    if (ready) hipEventDestroy(ready);
     if (have) hipSetDevice(cur);
   }
 };
+
+inline DbPool::~DbPool() { delete spare; }
+
+// Deleter of every store: a set whose pool has no spare becomes the spare (its holders are done with it: the editing
+// context waited for its stream, an adopting one for the event behind its last frame on the old set); any other set is
+// freed -- and hipFree stalls the device.
+inline void retire_store(DbStore* st) {
+  if (!st) return;
+  std::shared_ptr<DbPool> pool = std::move(st->pool);
+  st->pool.reset();
+  if (pool) {
+    std::lock_guard<std::mutex> lock(pool->mu);
+    if (!pool->spare && st->n_blocks <= 1 && st->cap >= pool->cap_rows) {
+      pool->spare = st;
+      return;
+    }
+  }
+  delete st;
+}
+inline std::shared_ptr<DbStore> make_store(int device) {
+  std::shared_ptr<DbStore> st(new DbStore, retire_store);
+  st->device = device;
+  return st;
+}
+
+// ScreenDb's scalars from the eight statistics words (launch_db_to_half / db_splice_kernel + the aggregate kernels)
+inline void screen_from_stats(DbStore* st, const unsigned int h[8]) {
+  float dd_max, x_max;
+  std::memcpy(&dd_max, &h[0], 4);
+  std::memcpy(&x_max, &h[1], 4);
+  st->screen.dbh = st->desc_h;
+  st->screen.dneg = st->neg_h;
+  st->screen.dmax = std::sqrt(dd_max);
+  std::memcpy(&st->screen.spread, &h[3], 4);   // (0 for a DB of fewer than 32 rows: no whole block, never used)
+  st->screen.zero_idx = (int32_t)h[4];
+  std::memcpy(&st->screen.zero_d1, &h[5], 4);
+  std::memcpy(&st->screen.zero_d2, &h[6], 4);
+  st->screen.usable = h[2] == 0 && x_max < 60000.f;   // (a NaN coordinate reads as a huge bit pattern: not < 60000)
+}
 
 // A lane: a few streams for the kernels whose workgroups take whole compute units (passes A and B of the two-stage
 // MATCH), either confined to a CU mask that leaves `reserve` units of every XCD to everything else, or of lower priority
@@ -70,6 +133,20 @@ struct mh_ctx {
   mh::ScreenBufs sbuf;           // the screen's per-frame scratch
   int match_mode = -1;           // mh_match_set_mode
   int pose_split = 1;            // mh_pose_set_split: POSE as two launches (hypotheses, one-wavefront refines) in the frame paths
+  // ---- edits of the resident DB (db_edit.hip) ----
+  std::shared_ptr<DbPool> pool;      // buffer sets of the store this context edits or adopted
+  int db_models_reserved = 0;        // mh_db_reserve's max_models: mh_reserve / mh_reserve_batch size the per-model tables for it
+  struct HeldStore {                 // mh_db_adopt: the previous store, kept until `done` (recorded on this context's stream at adoption) has completed
+    std::shared_ptr<DbStore> store;
+    hipEvent_t done = nullptr;
+  };
+  std::vector<HeldStore> held;
+  std::vector<hipEvent_t> held_events;   // idle events of released entries
+  float* db_stage = nullptr;         // an edit's new rows: [cap][128] descriptors, [cap] norm terms, [cap][3] coordinates
+  size_t db_stage_cap = 0;           // rows
+  int db_edit_route = 0;             // 0: the fused pass (db_splice_kernel); 1: device copies + the upload's preparation (mh_db_debug_route)
+  hipEvent_t db_ev[2] = {nullptr, nullptr};   // around an edit's pass over the rows when timing is on (mh_db_edit_ms)
+  bool db_ev_valid = false;
   uint32_t match_launches[3] = {0, 0, 0};   // MATCH launch sequences by kernel: VALU, f32 matrix pipe, two-stage (mh_match_launches)
   struct mh_lane* lane = nullptr;   // mh_set_lane: where the chip-filling MATCH passes run (not owned)
   hipStream_t lane_stream = nullptr;
@@ -218,6 +295,8 @@ void free_exchange(mh_ctx* ctx);   // comm.hip
   } while (0)
 
 int use_stream(mh_ctx* ctx);  // make sure ctx->stream is valid (creates the own stream lazily)
+void bind_store(mh_ctx* ctx);   // the context's view of its store (api.hip)
+void db_poll_held(mh_ctx* ctx, bool wait);   // db_edit.hip: let go of adopted-away stores whose event has completed (wait: all of them)
 int ensure_frame_buffers(mh_ctx* ctx, int Q);
 int ensure_scratch(mh_ctx* ctx, size_t bytes);
 int ensure_pinned(mh_ctx* ctx, size_t bytes);

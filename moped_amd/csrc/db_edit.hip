@@ -1,0 +1,538 @@
+// Edits of the resident model database: add, replace, remove one model (moped.cpp:139-159) without starting over.
+//
+// All three are one splice of the row array, new = old[0, b) ++ rows ++ old[e, N), with the model ids behind the splice
+// point shifted by +1, 0 or -1.  An edit never works in place -- other contexts (frames in flight) read the live arrays --
+// it fills a second buffer set and the editing context flips to it; the contexts that share the old set keep it until
+// they adopt the new one (mh_db_adopt), stream ordered, with no host wait.  What an edit leaves is, byte for byte, what
+// mh_db_upload_raw makes of the same rows: the new rows' norm terms come from the upload's own launches, moved rows keep
+// theirs, the f16 image is the same conversion of the same floats, and the aggregates (dmax, spread, the zero query's
+// answer, usable) are recomputed over all rows by the upload's kernels, never patched -- removing a model can lower any
+// of them.
+#include <algorithm>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "context.h"
+#include "steps.h"
+
+using namespace mh;
+
+namespace {
+
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+constexpr int DB_DD = 192;   // floats per 128-row tile of the -dd/2 array (SC_DD of match_screen.hip; checked in alloc_set)
+
+struct SpliceArgs {
+  const float* old_desc;   // the live set
+  const float* old_norm;
+  const float* old_xyz;
+  const int32_t* old_model;
+  const float* new_desc;   // the staged rows
+  const float* new_norm;
+  const float* new_xyz;
+  float* desc;             // the set being filled
+  float* norm;
+  float* xyz;
+  int32_t* model;
+  _Float16* dbh;           // nullptr: the result has no f16 image
+  float* dneg;
+  unsigned int* stats;
+  int N;                   // rows of the result
+  int b, n_rows;           // the staged rows become rows [b, b + n_rows)
+  int shift;               // rows behind them come from old row r - shift
+  int model_id, model_delta;   // model of the staged rows; what the models behind them move by
+  size_t n_chunks;         // 8-float chunks of the result's padded extent
+};
+
+// One pass over the destination, shaped like db_to_half_kernel (match_screen.hip): one 8-float chunk per thread step,
+// grid-strided; the f32 chunk is read once and written twice (f32, f16), chunk 0 of a row carries the row's scalars.
+__global__ __launch_bounds__(256) void db_splice_kernel(const SpliceArgs a) {
+  __shared__ unsigned int red[3];
+  if (threadIdx.x < 3) red[threadIdx.x] = 0;
+  __syncthreads();
+  float x_max = 0.f, dd_max = 0.f;
+  unsigned int bad = 0;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n_chunks; i += (size_t)gridDim.x * blockDim.x) {
+    const int row = (int)(i >> 4);
+    const int c = (int)(i & 15);
+    float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
+    const bool real = row < a.N;
+    const bool staged = real && row >= a.b && row < a.b + a.n_rows;
+    const int src = staged ? row - a.b : (row < a.b ? row : row - a.shift);
+    if (real) {
+      const float4* p = reinterpret_cast<const float4*>((staged ? a.new_desc : a.old_desc) + (size_t)src * DIM) + 2 * c;
+      lo = p[0];
+      hi = p[1];
+    }
+    reinterpret_cast<float4*>(a.desc)[2 * i] = lo;
+    reinterpret_cast<float4*>(a.desc)[2 * i + 1] = hi;
+    if (a.dbh) {
+      half8 h;
+      h[0] = (_Float16)lo.x; h[1] = (_Float16)lo.y; h[2] = (_Float16)lo.z; h[3] = (_Float16)lo.w;
+      h[4] = (_Float16)hi.x; h[5] = (_Float16)hi.y; h[6] = (_Float16)hi.z; h[7] = (_Float16)hi.w;
+      reinterpret_cast<half8*>(a.dbh)[i] = h;
+    }
+    if (c == 0) {
+      // padding rows: +inf norm term, -inf -dd/2 (a reused set holds an older generation's rows there)
+      const float dd = real ? (staged ? a.new_norm : a.old_norm)[src] : __builtin_inff();
+      a.norm[row] = dd;
+      if (a.dbh) a.dneg[(size_t)(row >> 7) * DB_DD + (row & 127)] = -0.5f * dd;
+      if (real) {
+        const float* x = (staged ? a.new_xyz : a.old_xyz) + (size_t)src * 3;
+        a.xyz[(size_t)row * 3] = x[0];
+        a.xyz[(size_t)row * 3 + 1] = x[1];
+        a.xyz[(size_t)row * 3 + 2] = x[2];
+        a.model[row] = staged ? a.model_id : a.old_model[src] + (row < a.b ? 0 : a.model_delta);
+        if (!(dd >= 0.f) || dd == __builtin_inff()) bad = 1;
+        else dd_max = fmaxf(dd_max, dd);
+      }
+    }
+    if (real)   // (fmaxf drops NaNs: a NaN coordinate shows in the row's norm term)
+      x_max = fmaxf(x_max, fmaxf(fmaxf(fmaxf(fabsf(lo.x), fabsf(lo.y)), fmaxf(fabsf(lo.z), fabsf(lo.w))),
+                                 fmaxf(fmaxf(fabsf(hi.x), fabsf(hi.y)), fmaxf(fabsf(hi.z), fabsf(hi.w)))));
+  }
+  if (!a.dbh) return;   // (uniform: no image, no statistics)
+  // non-negative floats order like their bit patterns
+  atomicMax(&red[0], __float_as_uint(dd_max));
+  atomicMax(&red[1], __float_as_uint(x_max));
+  if (bad) atomicOr(&red[2], 1u);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    atomicMax(&a.stats[0], red[0]);
+    atomicMax(&a.stats[1], red[1]);
+    if (red[2]) atomicOr(&a.stats[2], 1u);
+  }
+}
+
+// the copy route's model ids: rows [first, N) move by delta
+__global__ void db_model_shift_kernel(int32_t* __restrict__ model, int first, int N, int delta, int fill_first, int fill_n,
+                                      int model_id) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= N) return;
+  if (r >= fill_first && r < fill_first + fill_n) model[r] = model_id;
+  else if (r >= first) model[r] += delta;
+}
+
+const char* why_not_editable(const DbStore* st) {
+  if (!st) return nullptr;   // no store = an empty one
+  if (!st->grouped) return "the rows of the store are not grouped by model in ascending order";
+  if (st->n_blocks > 1) return "the store was uploaded in blocks (a sharded store is not editable)";
+  if (st->index_base != 0) return "the store's index_base is not 0 (a sharded store is not editable)";
+  return nullptr;
+}
+
+int refuse(mh_ctx* ctx, const char* who, const char* why) {
+  ctx->err = std::string(who) + ": " + why;
+  return MH_ERR_ARG;
+}
+
+template <typename T>
+hipError_t dev_alloc(T*& p, size_t n) {
+  return hipMalloc(&p, (n > 0 ? n : 1) * sizeof(T));
+}
+
+// a buffer set for cap_rows rows (a multiple of 128), with the f16 image's arrays when a store of that many rows can have one
+int alloc_set(mh_ctx* ctx, size_t cap_rows, std::shared_ptr<DbStore>& out) {
+  if (screen_dneg_elems(128) != (size_t)DB_DD) {
+    ctx->err = "db_edit: the -dd/2 array's tile pitch has changed";
+    return MH_ERR_HIP;
+  }
+  std::shared_ptr<DbStore> st = make_store(ctx->device);
+  cap_rows = std::max<size_t>(cap_rows, 128);
+  MH_HIP(ctx, dev_alloc(st->desc, cap_rows * DIM));
+  MH_HIP(ctx, dev_alloc(st->norm, cap_rows));
+  MH_HIP(ctx, dev_alloc(st->xyz, cap_rows * 3));
+  MH_HIP(ctx, dev_alloc(st->model, cap_rows));
+  st->cap = cap_rows;
+  if (screen_wanted(1 << 30, (int)cap_rows)) {
+    MH_HIP(ctx, dev_alloc(st->desc_h, screen_db_half_elems((int)cap_rows)));
+    MH_HIP(ctx, dev_alloc(st->neg_h, screen_dneg_elems((int)cap_rows)));
+    st->cap_h = screen_db_half_elems((int)cap_rows);
+    MH_HIP(ctx, dev_alloc(st->stats, 8));
+  }
+  MH_HIP(ctx, hipEventCreateWithFlags(&st->ready, hipEventDisableTiming));
+  st->pool = ctx->pool;
+  out = std::move(st);
+  return MH_OK;
+}
+
+bool set_fits(const DbStore* st, size_t n_pad, bool image) {
+  return st->cap >= n_pad && (!image || (st->cap_h >= n_pad * DIM && st->stats)) && st->ready;
+}
+
+// the set the next edit fills: the pool's spare when it is large enough, else a fresh one (a spare that is too small is
+// freed first -- that free stalls the device)
+int take_set(mh_ctx* ctx, size_t n_pad, bool image, std::shared_ptr<DbStore>& out) {
+  DbStore* spare = nullptr;
+  size_t cap_rows = 0;
+  {
+    std::lock_guard<std::mutex> lock(ctx->pool->mu);
+    spare = ctx->pool->spare;
+    ctx->pool->spare = nullptr;
+    cap_rows = ctx->pool->cap_rows;
+  }
+  if (spare && !spare->ready && hipEventCreateWithFlags(&spare->ready, hipEventDisableTiming) != hipSuccess) spare->ready = nullptr;
+  if (spare && set_fits(spare, n_pad, image)) {
+    spare->pool = ctx->pool;
+    out = std::shared_ptr<DbStore>(spare, retire_store);
+    return MH_OK;
+  }
+  delete spare;
+  return alloc_set(ctx, std::max(n_pad, cap_rows), out);
+}
+
+int ensure_stage(mh_ctx* ctx, size_t rows) {
+  if (rows <= ctx->db_stage_cap) return MH_OK;
+  if (ctx->db_stage) MH_HIP(ctx, hipFree(ctx->db_stage));
+  ctx->db_stage = nullptr;
+  ctx->db_stage_cap = 0;
+  const size_t cap = std::max<size_t>(rows + rows / 4, 4096);
+  MH_HIP(ctx, hipMalloc(&ctx->db_stage, cap * (DIM + 1 + 3) * sizeof(float)));
+  ctx->db_stage_cap = cap;
+  return MH_OK;
+}
+
+// The pass over the rows of an edit + the aggregates + the flip.  b, e: the old rows [b, e) leave; the n_rows staged rows
+// take their place as model `model_id`; the models of the rows behind them move by model_delta; `table` = the new
+// per-model row ranges.
+int run_splice(mh_ctx* ctx, int b, int e, int n_rows, int model_id, int model_delta, std::vector<int32_t> table) {
+  const DbStore* old = ctx->store.get();
+  const int N_old = old ? old->N : 0;
+  const long long N_ll = (long long)N_old - (e - b) + n_rows;
+  if (N_ll > 0x7FFFFF00ll) {
+    ctx->err = "mh_db_splice: more than 2^31 - 256 rows";
+    return MH_ERR_CAPACITY;
+  }
+  const int N = (int)N_ll;
+  const size_t n_pad = ((size_t)N + 127) / 128 * 128;
+  const bool image = N > 0 && screen_wanted(1 << 30, N);
+  if (!ctx->pool) ctx->pool = std::make_shared<DbPool>();
+  std::shared_ptr<DbStore> st;
+  int rc = take_set(ctx, n_pad, image, st);
+  if (rc) return rc;
+  st->N = 0;
+  st->screen = ScreenDb();
+  st->n_blocks = 0;
+  st->index_base = 0;
+  const float* stage = ctx->db_stage;
+  const float* stage_norm = stage ? stage + ctx->db_stage_cap * DIM : nullptr;
+  const float* stage_xyz = stage ? stage_norm + ctx->db_stage_cap : nullptr;
+  const bool timed = ctx->timing;
+  if (timed)
+    for (hipEvent_t& ev : ctx->db_ev)
+      if (!ev) MH_HIP(ctx, hipEventCreate(&ev));
+  ctx->db_ev_valid = false;
+  if (N > 0) {
+    if (image) MH_HIP(ctx, hipMemsetAsync(st->stats, 0, 8 * sizeof(unsigned int), ctx->stream));
+    if (timed) MH_HIP(ctx, hipEventRecord(ctx->db_ev[0], ctx->stream));
+    if (ctx->db_edit_route == 0) {
+      SpliceArgs a;
+      a.old_desc = old ? old->desc : nullptr;
+      a.old_norm = old ? old->norm : nullptr;
+      a.old_xyz = old ? old->xyz : nullptr;
+      a.old_model = old ? old->model : nullptr;
+      a.new_desc = stage;
+      a.new_norm = stage_norm;
+      a.new_xyz = stage_xyz;
+      a.desc = st->desc;
+      a.norm = st->norm;
+      a.xyz = st->xyz;
+      a.model = st->model;
+      a.dbh = image ? st->desc_h : nullptr;
+      a.dneg = image ? st->neg_h : nullptr;
+      a.stats = st->stats;
+      a.N = N;
+      a.b = b;
+      a.n_rows = n_rows;
+      a.shift = n_rows - (e - b);
+      a.model_id = model_id;
+      a.model_delta = model_delta;
+      a.n_chunks = n_pad * (DIM / 8);
+      const unsigned blocks = (unsigned)std::min<size_t>((a.n_chunks + 255) / 256, 2048);
+      hipLaunchKernelGGL(db_splice_kernel, dim3(blocks), dim3(256), 0, ctx->stream, a);
+    } else {
+      // the route the fused pass is measured against: device copies of the three runs of every array, then the upload's
+      // own preparation of the f16 image
+      const size_t tail = (size_t)N_old - e;   // old rows [e, N_old) -> new rows [b + n_rows, N)
+      auto runs = [&](void* dst, const void* src_old, const void* src_new, size_t row_bytes) -> hipError_t {
+        hipError_t err = hipSuccess;
+        if (b > 0) err = hipMemcpyAsync(dst, src_old, (size_t)b * row_bytes, hipMemcpyDeviceToDevice, ctx->stream);
+        if (err == hipSuccess && n_rows > 0)
+          err = hipMemcpyAsync((char*)dst + (size_t)b * row_bytes, src_new, (size_t)n_rows * row_bytes, hipMemcpyDeviceToDevice, ctx->stream);
+        if (err == hipSuccess && tail > 0)
+          err = hipMemcpyAsync((char*)dst + ((size_t)b + n_rows) * row_bytes, (const char*)src_old + (size_t)e * row_bytes,
+                               tail * row_bytes, hipMemcpyDeviceToDevice, ctx->stream);
+        return err;
+      };
+      MH_HIP(ctx, runs(st->desc, old ? old->desc : nullptr, stage, DIM * sizeof(float)));
+      MH_HIP(ctx, runs(st->norm, old ? old->norm : nullptr, stage_norm, sizeof(float)));
+      MH_HIP(ctx, runs(st->xyz, old ? old->xyz : nullptr, stage_xyz, 3 * sizeof(float)));
+      if (b > 0) MH_HIP(ctx, hipMemcpyAsync(st->model, old->model, (size_t)b * 4, hipMemcpyDeviceToDevice, ctx->stream));
+      if (tail > 0)
+        MH_HIP(ctx, hipMemcpyAsync(st->model + b + n_rows, old->model + e, tail * 4, hipMemcpyDeviceToDevice, ctx->stream));
+      hipLaunchKernelGGL(db_model_shift_kernel, dim3((N + 255) / 256), dim3(256), 0, ctx->stream, st->model, b + n_rows, N,
+                         model_delta, b, n_rows, model_id);
+      if (n_pad > (size_t)N) {
+        MH_HIP(ctx, hipMemsetAsync(st->desc + (size_t)N * DIM, 0, (n_pad - N) * DIM * sizeof(float), ctx->stream));
+        MH_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)(st->norm + N), 0x7F800000, n_pad - N, ctx->stream));
+      }
+      if (image) launch_db_to_half(st->desc, st->norm, N, st->desc_h, st->neg_h, st->stats, ctx->stream);
+    }
+    if (timed) MH_HIP(ctx, hipEventRecord(ctx->db_ev[1], ctx->stream));
+    if (image && ctx->db_edit_route == 0) launch_db_aggregates(st->norm, N, st->neg_h, st->stats, ctx->stream);
+    MH_HIP(ctx, hipGetLastError());
+  }
+  MH_HIP(ctx, hipEventRecord(st->ready, ctx->stream));
+  // the only host wait: the statistics words (the upload path waits for the same read-back).  It also means that this
+  // context's frames on the old set have finished, so the old set may become the spare when its other holders let go.
+  unsigned int h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (image) MH_HIP(ctx, hipMemcpyAsync(h, st->stats, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (image) screen_from_stats(st.get(), h);
+  ctx->db_ev_valid = timed && N > 0;
+  st->N = N;
+  st->n_models = (int)table.size() - 1;
+  st->grouped = true;
+  st->model_begin = std::move(table);
+  st->generation = (old ? old->generation : 0) + 1;
+  // flip: contexts that share the old set keep it; it parks in the pool when the last of them lets go
+  std::shared_ptr<DbStore> prev = std::move(ctx->store);
+  if (prev && !prev->pool) prev->pool = ctx->pool;
+  ctx->store = std::move(st);
+  bind_store(ctx);
+  return MH_OK;
+}
+
+}  // namespace
+
+namespace mh {
+
+void db_poll_held(mh_ctx* ctx, bool wait) {
+  size_t keep = 0;
+  for (size_t i = 0; i < ctx->held.size(); ++i) {
+    mh_ctx::HeldStore& h = ctx->held[i];
+    bool done = true;
+    if (h.done) {
+      if (wait) hipEventSynchronize(h.done);
+      else if (hipEventQuery(h.done) == hipErrorNotReady) {
+        (void)hipGetLastError();   // (not an error: the runtime remembers it as one)
+        done = false;
+      }
+    }
+    if (done) {
+      if (h.done) ctx->held_events.push_back(h.done);
+      h.store.reset();
+    } else {
+      if (keep != i) ctx->held[keep] = std::move(h);
+      ++keep;
+    }
+  }
+  ctx->held.resize(keep);
+}
+
+}  // namespace mh
+
+extern "C" {
+
+int mh_db_model_rows(const mh_ctx* ctx, int model, int32_t* row_begin, int32_t* n_rows) {
+  if (!ctx) return MH_ERR_ARG;
+  mh_ctx* c = const_cast<mh_ctx*>(ctx);
+  const DbStore* st = ctx->store.get();
+  if (!st || !st->grouped) return refuse(c, "mh_db_model_rows", "the rows of the store are not grouped by model in ascending order");
+  if (model < 0 || model >= st->n_models) return refuse(c, "mh_db_model_rows", "model index out of range");
+  if (row_begin) *row_begin = st->model_begin[model];
+  if (n_rows) *n_rows = st->model_begin[model + 1] - st->model_begin[model];
+  return MH_OK;
+}
+
+int mh_db_generation(const mh_ctx* ctx, uint64_t* generation) {
+  if (!ctx || !generation) return MH_ERR_ARG;
+  *generation = ctx->store ? ctx->store->generation : 0;
+  return MH_OK;
+}
+
+int mh_db_splice(mh_ctx* ctx, int op, int model, const float* desc, const float* xyz, int n_rows, int normalize,
+                 int on_device) {
+  if (!ctx) return MH_ERR_ARG;
+  if (op < MH_DB_INSERT || op > MH_DB_REMOVE) return refuse(ctx, "mh_db_splice", "unknown operation");
+  if (op == MH_DB_REMOVE) n_rows = 0;
+  if (n_rows < 0 || (n_rows > 0 && (!desc || !xyz))) return refuse(ctx, "mh_db_splice", "bad argument");
+  const DbStore* old = ctx->store.get();
+  if (const char* why = why_not_editable(old)) return refuse(ctx, "mh_db_splice", why);
+  const int nm = old ? old->n_models : 0;
+  if (op == MH_DB_INSERT ? (model < 0 || model > nm) : (model < 0 || model >= nm))
+    return refuse(ctx, "mh_db_splice", nm == 0 && op != MH_DB_INSERT ? "model index out of range (the store is empty)"
+                                                                       : "model index out of range");
+  if (op == MH_DB_INSERT && nm + 1 > MH_MAX_MODELS) {
+    ctx->err = "mh_db_splice: more than MH_MAX_MODELS models";
+    return MH_ERR_CAPACITY;
+  }
+  // the rows that leave, [b, e), and the new per-model table
+  static const std::vector<int32_t> none(1, 0);
+  const std::vector<int32_t>& begin = old ? old->model_begin : none;   // [nm + 1]
+  const int b = begin[op == MH_DB_INSERT ? model : model];
+  const int e = op == MH_DB_INSERT ? b : begin[model + 1];
+  const int shift = n_rows - (e - b);
+  const int delta = op == MH_DB_INSERT ? 1 : op == MH_DB_REMOVE ? -1 : 0;
+  std::vector<int32_t> table(begin.begin(), begin.begin() + model + 1);   // models up to `model` begin where they began
+  if (op == MH_DB_INSERT) table.push_back(b + n_rows);                     // the model that was `model`, behind the new rows
+  for (int m = model + (op == MH_DB_REMOVE ? 2 : 1); m <= nm; ++m) table.push_back(begin[m] + shift);
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
+  // stage the new rows: their norm terms by the upload's own launches, so that their bits are the upload's by construction
+  if (n_rows > 0) {
+    int rc = ensure_stage(ctx, (size_t)n_rows);
+    if (rc) return rc;
+    float* sd = ctx->db_stage;
+    float* sn = sd + ctx->db_stage_cap * DIM;
+    float* sx = sn + ctx->db_stage_cap;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    MH_HIP(ctx, hipMemcpyAsync(sd, desc, (size_t)n_rows * DIM * sizeof(float), kind, ctx->stream));
+    MH_HIP(ctx, hipMemcpyAsync(sx, xyz, (size_t)n_rows * 3 * sizeof(float), kind, ctx->stream));
+    if (normalize) launch_normalize(sd, sn, n_rows, ctx->stream);
+    else launch_row_norms(sd, sn, n_rows, ctx->stream);
+    MH_HIP(ctx, hipGetLastError());
+  }
+  return run_splice(ctx, b, e, n_rows, model, delta, std::move(table));
+}
+
+int mh_db_reserve(mh_ctx* ctx, int64_t max_rows, int max_models) {
+  if (!ctx || max_rows < 0 || max_rows > 0x7FFFFF00ll || max_models < 0 || max_models > MH_MAX_MODELS)
+    return ctx ? refuse(ctx, "mh_db_reserve", "bad argument") : MH_ERR_ARG;
+  if (const char* why = why_not_editable(ctx->store.get())) return refuse(ctx, "mh_db_reserve", why);
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
+  if (!ctx->pool) ctx->pool = std::make_shared<DbPool>();
+  const size_t cap_rows = std::max<size_t>(((size_t)max_rows + 127) / 128 * 128, 128);
+  DbStore* stale = nullptr;
+  {
+    std::lock_guard<std::mutex> lock(ctx->pool->mu);
+    ctx->pool->cap_rows = std::max(ctx->pool->cap_rows, cap_rows);
+    ctx->pool->max_models = std::max(ctx->pool->max_models, max_models);
+    if (ctx->pool->spare && ctx->pool->spare->cap < ctx->pool->cap_rows) std::swap(stale, ctx->pool->spare);
+  }
+  delete stale;
+  ctx->db_models_reserved = ctx->pool->max_models;
+  int rc = ensure_stage(ctx, (size_t)std::min<int64_t>(std::max<int64_t>(max_rows, 1), 65536));
+  if (rc) return rc;
+  // the live set at capacity: the identity splice into a fresh set (an empty store if the context has none) ...
+  const DbStore* old = ctx->store.get();
+  if (!old || !set_fits(old, ctx->pool->cap_rows, screen_wanted(1 << 30, (int)ctx->pool->cap_rows))) {
+    std::vector<int32_t> table = old ? old->model_begin : std::vector<int32_t>(1, 0);
+    const uint64_t gen = old ? old->generation : 0;
+    rc = run_splice(ctx, 0, 0, 0, 0, 0, std::move(table));
+    if (rc) return rc;
+    ctx->store->generation = gen;   // (the same rows: not an edit)
+  } else if (!ctx->store->pool) {
+    ctx->store->pool = ctx->pool;
+  }
+  // ... and the spare
+  bool have_spare;
+  {
+    std::lock_guard<std::mutex> lock(ctx->pool->mu);
+    have_spare = ctx->pool->spare != nullptr;
+  }
+  if (!have_spare) {
+    std::shared_ptr<DbStore> spare;
+    if ((rc = alloc_set(ctx, ctx->pool->cap_rows, spare))) return rc;
+    spare.reset();   // parks in the pool
+  }
+  return MH_OK;
+}
+
+int mh_db_adopt(mh_ctx* dst, mh_ctx* src) {
+  if (!dst || !src || !src->store) {
+    if (dst) dst->err = "mh_db_adopt: the source context holds no database";
+    return MH_ERR_ARG;
+  }
+  if (dst == src || dst->store == src->store) return MH_OK;
+  if (dst->device != src->device) return refuse(dst, "mh_db_adopt", "contexts on different devices");
+  MH_HIP(dst, hipSetDevice(dst->device));
+  if (int rc_stream = mh::use_stream(dst)) return rc_stream;
+  db_poll_held(dst, false);
+  // frames enqueued on dst from here on run behind the edit that filled the store ...
+  if (src->store->ready) MH_HIP(dst, hipStreamWaitEvent(dst->stream, src->store->ready, 0));
+  else if (src->stream) MH_HIP(dst, hipStreamSynchronize(src->stream));   // (an uploaded store: the upload was synchronous)
+  // ... and dst's frames in flight finish on the store it had: it is held until an event behind them has completed
+  if (dst->store) {
+    mh_ctx::HeldStore h;
+    if (!dst->held_events.empty()) {
+      h.done = dst->held_events.back();
+      dst->held_events.pop_back();
+    } else {
+      MH_HIP(dst, hipEventCreateWithFlags(&h.done, hipEventDisableTiming));
+    }
+    MH_HIP(dst, hipEventRecord(h.done, dst->stream));
+    h.store = std::move(dst->store);
+    if (!h.store->pool) h.store->pool = src->pool;
+    dst->held.push_back(std::move(h));
+  }
+  dst->store = src->store;
+  dst->pool = src->pool;
+  dst->db_models_reserved = src->db_models_reserved;
+  bind_store(dst);
+  return MH_OK;
+}
+
+int mh_db_splice_models(mh_ctx* ctx, int op, int model, const mh_model_set* s, int set_index) {
+  if (!ctx) return MH_ERR_ARG;
+  if (op == MH_DB_REMOVE) return mh_db_splice(ctx, op, model, nullptr, nullptr, 0, 0, 0);
+  int64_t row_begin = 0, n_rows = 0;
+  if (!s || mh_models_range(s, set_index, &row_begin, &n_rows, nullptr) != MH_OK || n_rows > 0x7FFFFF00ll)
+    return refuse(ctx, "mh_db_splice_models", "no such model in the set");
+  return mh_db_splice(ctx, op, model, mh_models_desc(s) + row_begin * DIM, mh_models_xyz(s) + row_begin * 3, (int)n_rows, 1, 0);
+}
+
+int mh_db_debug_route(mh_ctx* ctx, int route) {
+  if (!ctx || route < 0 || route > 1) return MH_ERR_ARG;
+  ctx->db_edit_route = route;
+  return MH_OK;
+}
+
+int mh_db_edit_ms(mh_ctx* ctx, float* ms) {
+  if (!ctx || !ms) return MH_ERR_ARG;
+  if (!ctx->db_ev_valid) return refuse(ctx, "mh_db_edit_ms", "no timed edit (mh_enable_timing before the edit)");
+  MH_HIP(ctx, hipEventElapsedTime(ms, ctx->db_ev[0], ctx->db_ev[1]));
+  return MH_OK;
+}
+
+int mh_db_debug_fetch(mh_ctx* ctx, int which, void* out_host, size_t bytes) {
+  if (!ctx || which < 0 || which > 5 || (bytes > 0 && !out_host)) return MH_ERR_ARG;
+  const DbStore* st = ctx->store.get();
+  const size_t N = st ? (size_t)st->N : 0, n_pad = (N + 127) / 128 * 128;
+  const bool image = st && st->screen.dbh;
+  const void* src = nullptr;
+  size_t extent = 0;
+  switch (which) {
+    case 0: src = st ? st->desc : nullptr; extent = n_pad * DIM * sizeof(float); break;
+    case 1: src = st ? st->norm : nullptr; extent = n_pad * sizeof(float); break;
+    case 2: src = st ? st->xyz : nullptr; extent = N * 3 * sizeof(float); break;
+    case 3: src = st ? st->model : nullptr; extent = N * sizeof(int32_t); break;
+    case 4: src = image ? st->desc_h : nullptr; extent = image ? n_pad * DIM * sizeof(_Float16) : 0; break;
+    default: src = image ? st->neg_h : nullptr; extent = image ? n_pad / 128 * DB_DD * sizeof(float) : 0; break;
+  }
+  if (bytes > extent) return refuse(ctx, "mh_db_debug_fetch", "more bytes than the store defines for that array");
+  if (bytes == 0) return MH_OK;
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  MH_HIP(ctx, hipMemcpy(out_host, src, bytes, hipMemcpyDeviceToHost));
+  return MH_OK;
+}
+
+int mh_db_debug_screen(mh_ctx* ctx, uint32_t out[8]) {
+  if (!ctx || !out) return MH_ERR_ARG;
+  const ScreenDb& s = ctx->sdb;
+  std::memcpy(&out[0], &s.dmax, 4);
+  std::memcpy(&out[1], &s.spread, 4);
+  out[2] = (uint32_t)s.zero_idx;
+  std::memcpy(&out[3], &s.zero_d1, 4);
+  std::memcpy(&out[4], &s.zero_d2, 4);
+  out[5] = s.usable ? 1u : 0u;
+  out[6] = s.dbh ? 1u : 0u;
+  out[7] = (uint32_t)ctx->N;
+  return MH_OK;
+}
+
+}  // extern "C"

@@ -1637,7 +1637,12 @@ void launch_db_to_half(const float* db, const float* dnorm, int N, _Float16* dbh
   if (n_chunks == 0) return;
   const unsigned blocks = (unsigned)std::min<size_t>((n_chunks + 255) / 256, 2048);
   hipLaunchKernelGGL(db_to_half_kernel, dim3(blocks), dim3(256), 0, s, db, dnorm, N, n_chunks, dbh, dneg, stats);
-  const int n_tiles = (int)(n_chunks * 8 / ((size_t)SC_TILE * DIM));
+  launch_db_aggregates(dnorm, N, dneg, stats, s);
+}
+
+void launch_db_aggregates(const float* dnorm, int N, float* dneg, unsigned int* stats, hipStream_t s) {
+  const int n_tiles = (N + SC_TILE - 1) / SC_TILE;
+  if (n_tiles == 0) return;
   hipLaunchKernelGGL(db_block_bounds_kernel, dim3((n_tiles * 4 + 255) / 256), dim3(256), 0, s, dnorm, N, n_tiles, dneg, stats);
   hipLaunchKernelGGL(db_zero_query_kernel, dim3(1), dim3(1024), 0, s, dnorm, N, stats);
 }

@@ -127,6 +127,10 @@ size_t screen_dneg_elems(int N);   // floats of the -dd/2 array: 192 per 128-row
 // row / norm term / second norm term of an all-zero query's answer} (8 words, zeroed by the caller)
 void launch_db_to_half(const float* db, const float* dnorm, int N, _Float16* dbh, float* dneg, unsigned int* stats,
                        hipStream_t s);
+// the part of it that reads only the norm terms: the row blocks' extrema (entries 128..191 of every tile of dneg, stats[3])
+// and the zero query's answer (stats[4..6]); launch_db_to_half ends with it, an edit of the DB (db_edit.hip) runs it
+// behind its own pass over the rows
+void launch_db_aggregates(const float* dnorm, int N, float* dneg, unsigned int* stats, hipStream_t s);
 int screen_q_pad(int Q);
 int screen_max_splits_a();
 size_t screen_part_bytes(int q_pad);   // pass A's output buffer

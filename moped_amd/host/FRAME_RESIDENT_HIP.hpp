@@ -28,6 +28,7 @@ class FRAME_RESIDENT_HIP : public MopedAlg {
   string DescriptorType;
   mh_frame_params prm;
   bool skipCalculation;
+  int IncrementalModels;   // config key, default 0: Update() edits the resident database instead of uploading every model again
   unsigned long frameCounter;
   int FillMatches;
   // the frame's descriptors / keypoints / image indices as the C ABI takes them: ONE page-locked block (mh_host_alloc),
@@ -60,6 +61,12 @@ class FRAME_RESIDENT_HIP : public MopedAlg {
     mh_ctx* ctx = HipSession::get();
     size_t n = 0;
     for (size_t m = 0; m < models->size(); ++m) n += (*models)[m]->IPs[DescriptorType].size();
+    // IncrementalModels: the resident database is edited instead (HipResidentModels, hip_session.hpp)
+    if (IncrementalModels && HipResidentModels::get().update(ctx, *models, DescriptorType)) {
+      skipCalculation = n <= 1;
+      configUpdated = false;
+      return;
+    }
     vector<float> desc(n * MH_DESC_DIM), xyz(n * 3);
     vector<int32_t> owner(n);
     size_t x = 0;
@@ -85,6 +92,7 @@ class FRAME_RESIDENT_HIP : public MopedAlg {
         return;
       }
       skipCalculation = false;
+      if (IncrementalModels) HipResidentModels::get().record(*models, DescriptorType);
     }
     configUpdated = false;
   }
@@ -96,7 +104,7 @@ class FRAME_RESIDENT_HIP : public MopedAlg {
                      int MinPoints1, Float FeatureDistance1, Float MinScore1,                                // FILTER
                      int NHyp2, int MaxObj2, int NPtsAlign2, int MinNPts2, Float ErrorThreshold2,            // POSE2
                      int MinPoints2, Float FeatureDistance2, Float MinScore2)                                // FILTER2
-      : DescriptorSize(DescriptorSize), DescriptorType(DescriptorType), skipCalculation(true), frameCounter(0), FillMatches(0),
+      : DescriptorSize(DescriptorSize), DescriptorType(DescriptorType), skipCalculation(true), IncrementalModels(0), frameCounter(0), FillMatches(0),
         pinBlock(NULL), pinBytes(0), packed(NULL), uv(NULL), imageOf(NULL) {
     mh_frame_default_params(&prm);
     prm.ratio = (float)Ratio;
@@ -152,6 +160,8 @@ class FRAME_RESIDENT_HIP : public MopedAlg {
 #define MH_FR_SET(NAME, VAR) hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_HIP", NAME, VAR);
     MH_FR_CONFIG(MH_FR_SET)
 #undef MH_FR_SET
+    // (accepted here and not published by getConfig, which carries the reference's constants)
+    hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_HIP", "IncrementalModels", IncrementalModels);
   }
 #undef MH_FR_CONFIG
 

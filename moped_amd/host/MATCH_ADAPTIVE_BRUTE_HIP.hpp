@@ -26,6 +26,7 @@ class MATCH_ADAPTIVE_BRUTE_HIP : public MopedAlg {
   Float DimensionPeak, DimensionFade;
   Float MaximumDepth, DefaultDepth, CauchyScale;
   bool skipCalculation;
+  int IncrementalModels;   // config key, default 0: Update() edits the resident database instead of uploading every model again
   vector<int> correspModel;
   vector<Pt<3>*> correspFeat;
   vector<float> packed;
@@ -88,21 +89,26 @@ class MATCH_ADAPTIVE_BRUTE_HIP : public MopedAlg {
     for (size_t m = 0; m < models->size(); ++m) n += (*models)[m]->IPs[DescriptorType].size();
     correspModel.resize(n);
     correspFeat.resize(n);
-    packed.resize(n * MH_DESC_DIM);
-    vector<float> xyz(n * 3);
-    vector<int32_t> owner(n);
+    // IncrementalModels: the resident database is edited (HipResidentModels, hip_session.hpp), only the tables are rebuilt
+    const bool edited = IncrementalModels && HipResidentModels::get().update(ctx, *models, DescriptorType);
+    if (!edited) packed.resize(n * MH_DESC_DIM);
+    vector<float> xyz(edited ? 0 : n * 3);
+    vector<int32_t> owner(edited ? 0 : n);
     size_t x = 0;
     for (size_t m = 0; m < models->size(); ++m) {
       vector<Model::IP>& ips = (*models)[m]->IPs[DescriptorType];
       for (size_t f = 0; f < ips.size(); ++f, ++x) {
         correspModel[x] = (int)m;
         correspFeat[x] = &ips[f].coord3D;
+        if (edited) continue;
         owner[x] = (int32_t)m;
         for (int i = 0; i < MH_DESC_DIM; ++i) packed[x * MH_DESC_DIM + i] = ips[f].descriptor[i];
         for (int i = 0; i < 3; ++i) xyz[x * 3 + i] = ips[f].coord3D[i];
       }
     }
-    if (n > 1) {
+    if (edited) {
+      skipCalculation = n <= 1;
+    } else if (n > 1) {
       if (mh_normalize(ctx, &packed[0], (int)n) != MH_OK) { HipSession::warn("mh_normalize"); return; }
       x = 0;
       for (size_t m = 0; m < models->size(); ++m) {       // Update() normalises the model descriptors in place (:122)
@@ -115,6 +121,7 @@ class MATCH_ADAPTIVE_BRUTE_HIP : public MopedAlg {
         return;
       }
       skipCalculation = false;
+      if (IncrementalModels) HipResidentModels::get().record(*models, DescriptorType);
     }
     // intrinsics of the gray image (:146-153)
     Pt<4> k;
@@ -140,7 +147,7 @@ class MATCH_ADAPTIVE_BRUTE_HIP : public MopedAlg {
                            Float MaxRatioMin, Float MaxRatioMax, Float DimensionPeak, Float DimensionFade)
       : DescriptorSize(DescriptorSize), DescriptorType(DescriptorType), MinRatioMin(MinRatioMin),
         MinRatioMax(MinRatioMax), MaxRatioMin(MaxRatioMin), MaxRatioMax(MaxRatioMax), DimensionPeak(DimensionPeak),
-        DimensionFade(DimensionFade), MaximumDepth(4.0), DefaultDepth(1.0), CauchyScale(0.1), skipCalculation(true) {
+        DimensionFade(DimensionFade), MaximumDepth(4.0), DefaultDepth(1.0), CauchyScale(0.1), skipCalculation(true), IncrementalModels(0) {
     capable = (DescriptorSize == MH_DESC_DIM) && HipSession::get() != 0;
   }
 
@@ -157,7 +164,9 @@ class MATCH_ADAPTIVE_BRUTE_HIP : public MopedAlg {
     hipGetConfig(config, _stepName, _alg, "MATCH_ADAPTIVE_BRUTE_HIP", "DescriptorType", DescriptorType);
     hipGetConfig(config, _stepName, _alg, "MATCH_ADAPTIVE_BRUTE_HIP", "DescriptorSize", DescriptorSize);
   }
-  void setConfig(map<string, string>&) {}
+  void setConfig(map<string, string>& config) {   // (IncrementalModels is accepted here and not published by getConfig)
+    hipSetConfig(config, _stepName, _alg, "MATCH_ADAPTIVE_BRUTE_HIP", "IncrementalModels", IncrementalModels);
+  }
 
   void process(FrameData& frameData) {
     if (configUpdated) Update(frameData);

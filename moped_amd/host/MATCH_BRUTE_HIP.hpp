@@ -27,6 +27,7 @@ class MATCH_BRUTE_HIP : public MopedAlg {
   string DescriptorType;
   Float Ratio;
   bool skipCalculation;
+  int IncrementalModels;   // config key, default 0: Update() edits the resident database instead of uploading every model again
   vector<int> correspModel;
   vector<Pt<3>*> correspFeat;
   vector<float> packed;
@@ -108,9 +109,31 @@ class MATCH_BRUTE_HIP : public MopedAlg {
     return true;
   }
 
+  // IncrementalModels: the resident database is edited (HipResidentModels, hip_session.hpp); only the row -> model and
+  // row -> coord3D tables of the upload path are rebuilt here
+  bool UpdateIncremental(mh_ctx* ctx) {
+    if (!HipResidentModels::get().update(ctx, *models, DescriptorType)) return false;
+    size_t n = 0;
+    for (size_t m = 0; m < models->size(); ++m) n += (*models)[m]->IPs[DescriptorType].size();
+    correspModel.resize(n);
+    correspFeat.resize(n);
+    size_t x = 0;
+    for (size_t m = 0; m < models->size(); ++m) {
+      vector<Model::IP>& ips = (*models)[m]->IPs[DescriptorType];
+      for (size_t f = 0; f < ips.size(); ++f, ++x) {
+        correspModel[x] = (int)m;
+        correspFeat[x] = &ips[f].coord3D;
+      }
+    }
+    skipCalculation = n <= 1;   // (the reference's rule, :102)
+    configUpdated = false;
+    return true;
+  }
+
   void Update() {
     skipCalculation = true;
     mh_ctx* ctx = HipSession::get();
+    if (IncrementalModels && UpdateIncremental(ctx)) return;
     size_t n = 0;
     for (size_t m = 0; m < models->size(); ++m) n += (*models)[m]->IPs[DescriptorType].size();
     correspModel.resize(n);
@@ -144,6 +167,7 @@ class MATCH_BRUTE_HIP : public MopedAlg {
         return;
       }
       skipCalculation = false;
+      if (IncrementalModels) HipResidentModels::get().record(*models, DescriptorType);
     }
     configUpdated = false;
   }
@@ -151,7 +175,7 @@ class MATCH_BRUTE_HIP : public MopedAlg {
  public:
   MATCH_BRUTE_HIP(int DescriptorSize, string DescriptorType, Float Ratio)
       : DescriptorSize(DescriptorSize), DescriptorType(DescriptorType), Ratio(Ratio), skipCalculation(true),
-        pinBlock(NULL), pinBytes(0), pinDesc(NULL), pinUv(NULL) {
+        IncrementalModels(0), pinBlock(NULL), pinBytes(0), pinDesc(NULL), pinUv(NULL) {
     capable = (DescriptorSize == MH_DESC_DIM) && HipSession::get() != 0;
   }
 
@@ -160,7 +184,10 @@ class MATCH_BRUTE_HIP : public MopedAlg {
     hipGetConfig(config, _stepName, _alg, "MATCH_BRUTE_HIP", "DescriptorSize", DescriptorSize);
     hipGetConfig(config, _stepName, _alg, "MATCH_BRUTE_HIP", "Ratio", Ratio);
   }
-  void setConfig(map<string, string>&) {}  // a no-op in the reference as well
+  // (a no-op in the reference; IncrementalModels is accepted here and not published by getConfig)
+  void setConfig(map<string, string>& config) {
+    hipSetConfig(config, _stepName, _alg, "MATCH_BRUTE_HIP", "IncrementalModels", IncrementalModels);
+  }
 
   void process(FrameData& frameData) {
     HipHandover::get().drop();   // MATCH begins a frame: whatever is resident belongs to an earlier one

@@ -112,6 +112,96 @@ struct HipHandover {
   HipHandover() : stage(-1), frame(0), matchesTag(0), clustersTag(0), objectsTag(0), taken(0) {}
 };
 
+// Opt-in (config key IncrementalModels = 1 of MATCH_BRUTE_HIP, MATCH_ADAPTIVE_BRUTE_HIP, FRAME_RESIDENT_HIP): Update()
+// compares `models` with what is resident on the device -- SP_Model pointer and descriptor count per index -- and, if the
+// difference is a run of appends, one removal, or replaces, edits the resident database (mh_db_splice) instead of
+// packing, normalising and uploading every model again.  Only the changed models' descriptors are normalised and
+// written back (the reference normalises every model on every Update, MATCH_ANN_CPU.hpp:94).  One instance per process,
+// like the context whose store it describes.
+struct HipResidentModels {
+  std::vector<const void*> ptr;   // the SP_Model each resident model came from
+  std::vector<size_t> count;      // ... and its descriptor count
+  std::string type;               // DescriptorType the rows were taken from
+  bool valid;                     // the store holds exactly these models, normalised
+  unsigned long fullUploads, splices;   // (tests, db_edit_step_test)
+
+  static HipResidentModels& get() {
+    static HipResidentModels r;
+    return r;
+  }
+  static bool same(const SP_Model& m, const std::string& type, const void* p, size_t n) {
+    std::map<std::string, std::vector<Model::IP> >::const_iterator it = m->IPs.find(type);
+    return m.get() == p && (it == m->IPs.end() ? 0 : it->second.size()) == n;
+  }
+  // what the full path leaves resident
+  void record(const std::vector<SP_Model>& models, const std::string& t) {
+    ptr.resize(models.size());
+    count.resize(models.size());
+    for (size_t m = 0; m < models.size(); ++m) {
+      ptr[m] = models[m].get();
+      count[m] = models[m]->IPs[t].size();
+    }
+    type = t;
+    valid = true;
+    ++fullUploads;
+  }
+  // one model's rows: normalised on the device, written back, spliced in
+  bool splice(mh_ctx* ctx, int op, int index, Model* model, const std::string& t) {
+    if (op == MH_DB_REMOVE) return mh_db_splice(ctx, op, index, 0, 0, 0, 0, 0) == MH_OK;
+    std::vector<Model::IP>& ips = model->IPs[t];
+    const size_t n = ips.size();
+    std::vector<float> desc(n * MH_DESC_DIM + 1), xyz(n * 3 + 1);
+    for (size_t f = 0; f < n; ++f) {
+      for (int i = 0; i < MH_DESC_DIM; ++i) desc[f * MH_DESC_DIM + i] = ips[f].descriptor[i];
+      for (int i = 0; i < 3; ++i) xyz[f * 3 + i] = ips[f].coord3D[i];
+    }
+    if (n > 0 && mh_normalize(ctx, &desc[0], (int)n) != MH_OK) return false;
+    for (size_t f = 0; f < n; ++f)
+      for (int i = 0; i < MH_DESC_DIM; ++i) ips[f].descriptor[i] = desc[f * MH_DESC_DIM + i];
+    return mh_db_splice(ctx, op, index, &desc[0], &xyz[0], (int)n, 0, 0) == MH_OK;
+  }
+  // true: the store now holds `models` (nothing to do counts); false: not a difference this serves, or a call failed --
+  // the caller takes the full path, which is always valid
+  bool update(mh_ctx* ctx, std::vector<SP_Model>& models, const std::string& t) {
+    if (!valid || t != type) return false;
+    const size_t had = ptr.size(), now = models.size();
+    valid = false;   // until every edit below has succeeded
+    if (now + 1 == had) {   // one removal
+      size_t k = 0;
+      while (k < now && same(models[k], t, ptr[k], count[k])) ++k;
+      for (size_t i = k; i < now; ++i)
+        if (!same(models[i], t, ptr[i + 1], count[i + 1])) return false;
+      if (!splice(ctx, MH_DB_REMOVE, (int)k, 0, t)) return false;
+      ptr.erase(ptr.begin() + k);
+      count.erase(count.begin() + k);
+      ++splices;
+    } else if (now >= had) {   // replaces, or a run of appends behind unchanged models
+      if (now > had)
+        for (size_t i = 0; i < had; ++i)
+          if (!same(models[i], t, ptr[i], count[i])) return false;
+      for (size_t i = 0; i < now; ++i) {
+        if (i < had && same(models[i], t, ptr[i], count[i])) continue;
+        if (!splice(ctx, i < had ? MH_DB_REPLACE : MH_DB_INSERT, (int)i, models[i].get(), t)) return false;
+        if (i < had) {
+          ptr[i] = models[i].get();
+          count[i] = models[i]->IPs[t].size();
+        } else {
+          ptr.push_back(models[i].get());
+          count.push_back(models[i]->IPs[t].size());
+        }
+        ++splices;
+      }
+    } else {
+      return false;
+    }
+    valid = true;
+    return true;
+  }
+
+ private:
+  HipResidentModels() : valid(false), fullUploads(0), splices(0) {}
+};
+
 // The cameras of a frame for the *_images entry points.  The reference projects every match through
 // *frameData.images[match.imageIdx] whatever else the image list holds (FILTER_PROJECTION_CPU.hpp:100-104,
 // POSE_RANSAC_LM_DIFF_REPROJECTION_CPU.hpp:228-237) -- a moped3d frame carries its depth and distance maps as

@@ -57,6 +57,31 @@ class ShardedDB:
         self.n_models = n_models          # model ids stay global
         self.rank, self.world, self.assign = rank, world, assign
 
+    def splice(self, op: int, model: int, desc=None, xyz=None):
+        """Keeps the host arrays in step with an edit of the resident store (Context.db_splice): model `model` inserted,
+        replaced or removed, later models renumbered.  One rank only: a sharded store is not editable."""
+        if self.world > 1 or len(self.block_rows) > 1 or self.row_lo != 0:
+            raise ValueError("a sharded model database cannot be edited in place")
+        if op == capi.DB_INSERT:
+            b = e = int(np.searchsorted(self.model_of, model, "left"))
+        else:
+            b, e = (int(np.searchsorted(self.model_of, model, side)) for side in ("left", "right"))
+        if op == capi.DB_REMOVE:
+            desc, xyz = np.zeros((0, 128), np.float32), np.zeros((0, 3), np.float32)
+        desc = np.ascontiguousarray(desc, np.float32).reshape(-1, 128)
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        delta = {capi.DB_INSERT: 1, capi.DB_REPLACE: 0, capi.DB_REMOVE: -1}[op]
+        self.desc = np.ascontiguousarray(np.concatenate([self.desc[:b], desc, self.desc[e:]]))
+        self.xyz = np.ascontiguousarray(np.concatenate([self.xyz[:b], xyz, self.xyz[e:]]))
+        self.model_of = np.concatenate([self.model_of[:b], np.full(len(desc), model, np.int32),
+                                        self.model_of[e:] + np.int32(delta)]).astype(np.int32)
+        self.n_models += delta
+        n = len(self.model_of)
+        self.rows = np.arange(n, dtype=np.int32)
+        self.row_lo, self.row_hi = 0, n
+        self.block_global_row = np.zeros(1 if n else 0, np.int32)
+        self.block_rows = np.full(1 if n else 0, n, np.int32)
+
     def upload(self, ctx: "capi.Context", normalized):
         if len(self.block_rows) > 1:
             ctx.db_upload_blocks(normalized, self.model_of, self.xyz, self.n_models, self.block_global_row, self.block_rows)
@@ -80,7 +105,7 @@ class FramePipeline:
     def __init__(self, device: int, db: ShardedDB, depth: int = 1, max_queries: int = 4096,
                  params: capi.mh_frame_params | None = None, K=None, cam=None, group=None,
                  force_exchange: bool = False, n_comms: int = 4, batch: int = 1, lane: "tuple | None" = None,
-                 id_leader: "int | None" = None):
+                 id_leader: "int | None" = None, db_capacity: "tuple | None" = None):
         from . import synth
         self.dev = torch.device(f"cuda:{device}")
         torch.cuda.set_device(self.dev)
@@ -106,6 +131,8 @@ class FramePipeline:
                 # model descriptors are L2-normalised once, like Update() (MATCH_ANN_CPU.hpp:94)
                 normalized = c.normalize(db.desc) if db.desc.shape[0] else db.desc
                 db.upload(c, normalized)
+                if db_capacity:   # (max_rows, max_models): edits inside it allocate nothing (mh_db_reserve)
+                    c.db_reserve(*db_capacity)
             else:
                 c.db_share(self.ctxs[0])   # one store per GPU: every frame in flight searches the same copy
             if batch > 1:   # frames travel in batches: per-frame working arrays, `batch` copies (mh_reserve_batch)
@@ -115,6 +142,7 @@ class FramePipeline:
             self.ctxs.append(c)
             self.streams.append(s)
         self.depth = depth
+        self.model_names = [None] * db.n_models   # add_model(name=...): a known name replaces, like Moped::addModel
         # lane = (n_streams, reserve_cus_per_xcd, low_priority): the contexts' chip-filling MATCH passes on shared streams
         self.lane = None
         if lane:
@@ -162,6 +190,37 @@ class FramePipeline:
         r, w, rccl = self.comms[0].info()
         return {"rank": r, "world": w, "transport": "RCCL ncclAllGather" if rccl else "host callback (gloo)",
                 "communicators": len(self.comms)}
+
+    # ---- the model set while frames flow: Moped::addModel / removeModel (moped.cpp:139-159) ---------------
+    def _edit(self, op, model, desc=None, xyz=None):
+        """One splice on slot 0's context, stream ordered; the other slots adopt the new store behind their frames in
+        flight.  No stream is synchronised: frames already enqueued finish on the store they were enqueued against."""
+        if self.world > 1 or self.exchange:
+            raise ValueError("a sharded model database cannot be edited in place: rebuild the pipeline")
+        self.ctxs[0].db_splice(op, model, desc, xyz, normalize=True)   # raw rows, normalised on the device like Update()
+        for c in self.ctxs[1:]:
+            c.db_adopt(self.ctxs[0])
+        self.db.splice(op, model, desc, xyz)
+
+    def add_model(self, desc, xyz, name=None) -> int:
+        """desc [n,128] raw descriptors, xyz [n,3].  A new model is appended; a name already known replaces that model
+        and keeps its index (moped.cpp:141-144).  Returns the model's index."""
+        if name is not None and name in self.model_names:
+            i = self.model_names.index(name)
+            self._edit(capi.DB_REPLACE, i, desc, xyz)
+            return i
+        i = self.db.n_models
+        self._edit(capi.DB_INSERT, i, desc, xyz)
+        self.model_names.append(name)
+        return i
+
+    def replace_model(self, i: int, desc, xyz):
+        self._edit(capi.DB_REPLACE, i, desc, xyz)
+
+    def remove_model(self, i: int):
+        """Later models move down by one (removeModel erases from the vector, moped.cpp:152-159)."""
+        self._edit(capi.DB_REMOVE, i)
+        del self.model_names[i]
 
     # ---- single frame in slot i ------------------------------------------------------
     def enqueue(self, slot: int, q_desc: torch.Tensor, q_uv: torch.Tensor, seed: int = 1,
