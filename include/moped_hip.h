@@ -834,6 +834,42 @@ int mh_frame_enqueue_image_batch(mh_ctx* ctx, const uint8_t* const* gray_dev, in
 int mh_frame_features_dev(mh_ctx* ctx, float** desc_dev, float** uv_dev, int32_t** n_dev);
 int mh_frame_keypoints(mh_ctx* ctx, int32_t* n_keypoints);
 
+/* ONE frame seen by n_images cameras, images resident on the device: FEAT of every image
+ * (FEAT_SIFT_CPU.hpp:80-107: image 0's keypoints in libsiftfast's list order, then image 1's, ...,
+ * imageIdx = i), then MATCH..FILTER2 of the frame with every keypoint in its own image
+ * (what mh_frame_set_images + mh_frame_enqueue do for a host that knows the counts): CLUSTER per (model, image)
+ * (CLUSTER_MEAN_SHIFT_CPU.hpp:189-195), POSE through cams[image], FILTER keyed by (coord2D, image).
+ * gray_dev: HOST array of n_images device images, all width x height; cams[n_images].  The frame's list is packed:
+ * image 0's first min(count, max_keypoints_per_image) keypoints, then image 1's, ...; one frame takes
+ * n_images * max_keypoints_per_image rows (mh_reserve).  The counts never leave the device: one launch packs the
+ * list, MATCH is launched for the capacity and reads the total.  mh_frame_fetch as for any frame; mh_frame_keypoints
+ * = the total; mh_frame_features_dev = the packed, normalised list; mh_frame_image_counts = what each image gave.
+ * n_images = 1 gives bit for bit what mh_frame_enqueue_image gives.  The call owns the context's image indices and
+ * cameras (mh_frame_set_images) for its own duration only.  UNDISTORTED_IMAGE: mh_frame_set_undistort_images, or
+ * mh_frame_set_undistort's one set of coefficients with every camera's K.
+ * MH_ERR_CAPACITY: n_images > MH_MAX_IMAGES.  MH_ERR_ARG: a depth map, depth rules or per-query depth attributes are
+ * set (several cameras: the linkage clusterer too).  Nothing of the context changes on a refusal. */
+int mh_frame_enqueue_images(mh_ctx* ctx, const uint8_t* const* gray_dev, int n_images, int width, int height,
+                            int double_size, int max_keypoints_per_image, const mh_cam* cams,
+                            const mh_frame_params* prm, uint64_t seed);
+/* B = n_frames such frames of one rig (cams[n_images]): frame f's images are gray_dev[f * n_images .. f * n_images +
+ * n_images - 1], its packed list starts at row f * n_images * max_keypoints_per_image, its total lies in a device word
+ * of its own.  FEAT: one launch per stage for all n_frames * n_images <= MH_MAX_BATCH images (more: MH_ERR_CAPACITY);
+ * one launch packs every frame's list; ONE MATCH launch sequence; CLUSTER..FILTER2 into result slots 0 .. B-1
+ * (mh_frame_fetch_slot), merged where one camera allows it.  Every frame's objects and counts are bit for bit those of
+ * mh_frame_enqueue_images(..., seeds[f]) on it alone.  Reserve with mh_reserve_batch(n_images *
+ * max_keypoints_per_image, n_frames, ...). */
+int mh_frame_enqueue_images_batch(mh_ctx* ctx, const uint8_t* const* gray_dev, int n_frames, int n_images, int width,
+                                  int height, int double_size, int max_keypoints_per_image, const mh_cam* cams,
+                                  const mh_frame_params* prm, const uint64_t* seeds);
+/* Keypoints each image contributed to the frame last fetched with mh_frame_fetch (after clamping to the per-image
+ * capacity): min(cap, *n_images) counts are written.  A frame of mh_frame_enqueue_image counts as one image.
+ * MH_ERR_ARG: no such frame fetched yet. */
+int mh_frame_image_counts(mh_ctx* ctx, int32_t* counts, int cap, int32_t* n_images);
+/* The image index (device int32, one per row) beside the list mh_frame_features_dev hands out, for the frame
+ * mh_frame_enqueue_images enqueued last (FEAT_SIFT_CPU.hpp:100: imageIdx).  MH_ERR_ARG: the last frame is no such frame. */
+int mh_frame_features_image_dev(mh_ctx* ctx, int32_t** q_image_dev);
+
 /* ---- UNDISTORT: lens undistortion (UTIL_UNDISTORT) ------------------------------------ */
 
 /* UTIL_UNDISTORT (src/util/UTIL_UNDISTORT.hpp) on the device.  K = fx, fy, cx, cy (Image::intrinsicLinearCalibration,
@@ -856,6 +892,11 @@ int mh_undistort_dev(mh_ctx* ctx, const uint8_t* gray_dev, uint8_t* out_dev, int
  * mh_frame_enqueue_image_batch remap their image(s) with (width, height, cam->K, dist) into a staging buffer of the
  * context, one launch for a batch, and FEAT reads that.  dist = NULL: off (the default). */
 int mh_frame_set_undistort(mh_ctx* ctx, const float dist[4]);
+/* UNDISTORTED_IMAGE per camera for mh_frame_enqueue_images[_batch] (UTIL_UNDISTORT.hpp:52-66 keys its maps by
+ * calibration): dist[i] goes with cams[i].K, every image is remapped with its camera's map -- the entries of the same
+ * cache of MH_MAX_IMAGES maps, still one remap launch per call.  n_images must be the rig's (else the enqueue returns
+ * MH_ERR_ARG).  NULL / 0 = off. */
+int mh_frame_set_undistort_images(mh_ctx* ctx, const float (*dist)[4], int n_images);
 
 /* ---- model files ------------------------------------------------ */
 

@@ -128,6 +128,8 @@ EXPORTS = [
     "mh_sift_debug_keys", "mh_sift_debug_blur",
     "mh_screen_pack_value", "mh_screen_pack_pert", "mh_screen_sample_bounds", "mh_screen_launch_plan", "mh_match_incomplete",
     "mh_screen_sample_values", "mh_match_query_candidates",
+    "mh_frame_enqueue_images", "mh_frame_enqueue_images_batch", "mh_frame_set_undistort_images", "mh_frame_image_counts",
+    "mh_frame_features_image_dev",
 ]
 COMM_ID_BYTES = 128      # MH_COMM_ID_BYTES
 EX2_OBJECTS = 62         # MH_EX2_OBJECTS
@@ -335,6 +337,12 @@ def load():
         L.mh_undistort.argtypes = [vp, vp, vp, i32, i32, vp, vp]
         L.mh_undistort_dev.argtypes = [vp, vp, vp, i32, i32, vp, vp]
         L.mh_frame_set_undistort.argtypes = [vp, vp]
+    if hasattr(L, "mh_frame_enqueue_images"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
+        L.mh_frame_enqueue_images.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, C.POINTER(mh_frame_params), C.c_uint64]
+        L.mh_frame_enqueue_images_batch.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, C.POINTER(mh_frame_params), vp]
+        L.mh_frame_set_undistort_images.argtypes = [vp, vp, i32]
+        L.mh_frame_image_counts.argtypes = [vp, vp, i32, C.POINTER(C.c_int32)]
+        L.mh_frame_features_image_dev.argtypes = [vp, C.POINTER(vp)]
     _lib = L
     return L
 
@@ -1195,6 +1203,54 @@ class Context:
         sd = (C.c_uint64 * B)(*[int(x) for x in seeds])
         self._ck(self.L.mh_frame_enqueue_image_batch(self.h, g, B, w, h, int(double_size), max_keypoints, C.byref(c),
                                                      C.byref(params), sd), "mh_frame_enqueue_image_batch")
+
+    def frame_enqueue_images(self, gray_ptrs, w, h, double_size, max_keypoints_per_image, Ks, cams,
+                             params: mh_frame_params, seed=1, _cam_structs=None):
+        """ONE frame seen by len(gray_ptrs) cameras, images resident on the device (Ks [n,4], cams [n,7]): FEAT of every
+        image, the lists packed on the device, MATCH..FILTER2 with every keypoint in its own image."""
+        n = len(gray_ptrs)
+        arr = _cam_structs or make_cams(Ks, cams)
+        if len(arr) != n:
+            raise ValueError("one camera per image")
+        g = (C.c_void_p * max(n, 1))(*gray_ptrs)
+        self._ck(self.L.mh_frame_enqueue_images(self.h, g, n, w, h, int(double_size), max_keypoints_per_image, arr,
+                                                C.byref(params), seed), "mh_frame_enqueue_images")
+
+    def frame_enqueue_images_batch(self, gray_ptrs, n_images, w, h, double_size, max_keypoints_per_image, Ks, cams,
+                                   params: mh_frame_params, seeds, _cam_structs=None):
+        """len(gray_ptrs) / n_images frames of one rig (frame f's images: gray_ptrs[f n_images : (f + 1) n_images]) into
+        result slots 0.. (frame_fetch_slot)."""
+        n_frames, rest = divmod(len(gray_ptrs), max(n_images, 1))
+        arr = _cam_structs or make_cams(Ks, cams)
+        if rest or len(arr) != n_images or len(seeds) != n_frames:
+            raise ValueError("n_images images and one seed per frame, one camera per image of the rig")
+        g = (C.c_void_p * max(len(gray_ptrs), 1))(*gray_ptrs)
+        sd = (C.c_uint64 * max(n_frames, 1))(*[int(x) for x in seeds])
+        self._ck(self.L.mh_frame_enqueue_images_batch(self.h, g, n_frames, n_images, w, h, int(double_size),
+                                                      max_keypoints_per_image, arr, C.byref(params), sd),
+                 "mh_frame_enqueue_images_batch")
+
+    def frame_set_undistort_images(self, dists):
+        """Undistort the images of frame_enqueue_images[_batch], camera i with its K and dists[i] = k1, k2, p1, p2;
+        None = off."""
+        if dists is None or len(dists) == 0:
+            self._ck(self.L.mh_frame_set_undistort_images(self.h, None, 0), "mh_frame_set_undistort_images")
+            return
+        d = np.ascontiguousarray(dists, np.float32).reshape(-1, 4)
+        self._ck(self.L.mh_frame_set_undistort_images(self.h, _ptr(d), len(d)), "mh_frame_set_undistort_images")
+
+    def frame_image_counts(self):
+        """Keypoints every image contributed to the frame last fetched (after clamping to the per-image capacity)."""
+        out = np.zeros(8, np.int32)   # MH_MAX_IMAGES
+        n = C.c_int32(0)
+        self._ck(self.L.mh_frame_image_counts(self.h, _ptr(out), len(out), C.byref(n)), "mh_frame_image_counts")
+        return out[:n.value].copy()
+
+    def frame_features_image_dev(self):
+        """Device int32 pointer: the image index of every row of the list frame_features_dev hands out."""
+        q = C.c_void_p()
+        self._ck(self.L.mh_frame_features_image_dev(self.h, C.byref(q)), "mh_frame_features_image_dev")
+        return q.value
 
     def set_linkage_scratch_limit(self, nbytes):
         """Bound of the linkage clusterer's similarity-matrix scratch for this context (0: the default, 4 GiB)."""

@@ -1,4 +1,5 @@
 // C ABI: CLUSTER / POSE / FILTER entry points and the device-resident frame.
+#include <climits>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -71,6 +72,7 @@ struct FrameState {
     int32_t snap[4];
     FrameCounts fc;
     int32_t n_feat;
+    int32_t img_n[MH_MAX_IMAGES];   // mh_frame_enqueue_images: the images' clamped counts lie right behind the frame's total (one copy)
   }* fetch_pin = nullptr;
   // one frame alone: the closing workgroup of FILTER2 writes the frame's head, counters and objects HERE itself
   // (page-locked, device-writable): mh_frame_fetch then synchronises and reads -- no copy at all
@@ -252,6 +254,12 @@ FilterBuffers make_fb(const mh_ctx* ctx, const FrameState* fs, int n_models) {
 }
 
 __global__ void set_scalar_kernel(int32_t* p, int32_t v) { *p = v; }
+
+// mh_ctx::ImagesFrame::words, [3][MH_MAX_BATCH]: FEAT's count per image first.  A batch keeps its frames' totals in the
+// second row and its images' clamped counts in the third; a frame alone keeps its total at the head of the third row and
+// its images' clamped counts right behind it, so that mh_frame_fetch reads them with one copy.
+static_assert(1 + MH_MAX_IMAGES <= MH_MAX_BATCH, "a frame's total and counts fit one row of the words");
+inline int32_t* images_single_total(const mh_ctx* ctx) { return ctx->imf.words ? ctx->imf.words + 2 * MH_MAX_BATCH : nullptr; }
 
 // mh_frame_enqueue_image_batch: the B images' keypoints lie at a fixed stride of Q rows; rows past an image's count
 // become zero rows with a norm term of -1 before MATCH -- "no such query" to the two-stage search (a plain zero query is
@@ -1630,6 +1638,181 @@ int mh_frame_enqueue_image_batch(mh_ctx* ctx, const uint8_t* const* gray_dev, in
   return rc;
 }
 
+// Storage of the image hand-over: FEAT's staging for `images` images of `cap` rows, the count words, the rig's table,
+// the image index of `list_rows` packed rows.
+static int ensure_images_frame(mh_ctx* ctx, int images, int cap, size_t list_rows) {
+  mh_ctx::ImagesFrame& m = ctx->imf;
+  const size_t rows = (size_t)images * cap;
+  if (rows > m.rows) {
+    if (m.rows) MH_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (a frame in flight may still read the old staging)
+    if (m.desc) hipFree(m.desc);
+    if (m.xy) hipFree(m.xy);
+    m.desc = m.xy = nullptr;
+    m.rows = 0;
+    MH_HIP(ctx, hipMalloc(&m.desc, rows * DIM * sizeof(float)));
+    MH_HIP(ctx, hipMalloc(&m.xy, rows * 2 * sizeof(float)));
+    m.rows = rows;
+  }
+  if (!m.words) {
+    MH_HIP(ctx, hipMalloc(&m.words, 3 * MH_MAX_BATCH * sizeof(int32_t)));
+    MH_HIP(ctx, hipMemsetAsync(m.words, 0, 3 * MH_MAX_BATCH * sizeof(int32_t), ctx->stream));
+  }
+  if (!m.cams) MH_HIP(ctx, hipMalloc(&m.cams, sizeof(DevCam) * MH_MAX_IMAGES));
+  if (list_rows > m.q_img_cap) {
+    if (m.q_img_cap) MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (m.q_img) hipFree(m.q_img);
+    m.q_img = nullptr;
+    m.q_img_cap = 0;
+    MH_HIP(ctx, hipMalloc(&m.q_img, list_rows * sizeof(int32_t)));
+    MH_HIP(ctx, hipMemsetAsync(m.q_img, 0, list_rows * sizeof(int32_t), ctx->stream));   // (rows past a frame's total are never written)
+    m.q_img_cap = list_rows;
+  }
+  return MH_OK;
+}
+
+// F frames of n cameras each from F n device images: FEAT of all of them with one launch per stage into the staging
+// area, ONE launch that packs every frame's list (images_pack.hip), then the frame(s) as mh_frame_enqueue_image
+// (batched = false: F = 1) or mh_frame_enqueue_image_batch run theirs, every keypoint in its own image.
+static int enqueue_images(mh_ctx* ctx, const char* who, const uint8_t* const* gray_dev, int F, int n, int width, int height,
+                          int double_size, int cap, const mh_cam* cams, const mh_frame_params* prm, const uint64_t* seeds,
+                          bool batched) {
+  if (!ctx) return MH_ERR_ARG;
+  auto refuse = [&](int rc, const char* why) {
+    ctx->err = std::string(who) + ": " + why;
+    return rc;
+  };
+  if (!gray_dev || F < 1 || n < 1 || width <= 0 || height <= 0 || cap <= 0 || !cams || !prm || !seeds)
+    return refuse(MH_ERR_ARG, "bad argument");
+  if (n > MH_MAX_IMAGES) return refuse(MH_ERR_CAPACITY, "more than MH_MAX_IMAGES cameras");
+  if (F > MH_MAX_BATCH || F * n > MH_MAX_BATCH) return refuse(MH_ERR_CAPACITY, "more than MH_MAX_BATCH images in one call");
+  if ((long long)F * n * cap > INT_MAX) return refuse(MH_ERR_CAPACITY, "too many rows");
+  for (int j = 0; j < F * n; ++j)
+    if (!gray_dev[j]) return refuse(MH_ERR_ARG, "null image");
+  if (ctx->depth_img.img || ctx->rules.on || ctx->q_depth || (n > 1 && ctx->linkage_on))
+    return refuse(MH_ERR_ARG, "depth maps / rules / attributes and the linkage clusterer are single-camera");
+  if (ctx->imf.und_n && ctx->imf.und_n != n)
+    return refuse(MH_ERR_ARG, "mh_frame_set_undistort_images gave coefficients for another number of cameras");
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
+  // the call owns the context's image indices and cameras for its own duration: whatever mh_frame_set_images left is the
+  // caller's again afterwards, and a later one-camera frame finds no image index of this one
+  struct Restore {
+    mh_ctx* ctx;
+    const int32_t* q_img;
+    DevCam* cams_dev;
+    int n_images;
+    ~Restore() {
+      ctx->q_img = q_img;
+      ctx->cams_dev = cams_dev;
+      ctx->n_images = n_images;
+      ctx->batch_q0 = ctx->batch_f = 0;
+      if (ctx->fs) ctx->fs->slot = 0;
+    }
+  } restore{ctx, ctx->q_img, ctx->cams_dev, ctx->n_images};
+  ctx->q_img = nullptr;
+  ctx->n_images = n;   // (sizes CLUSTER's per-(model, image) tables in prepare_frame)
+  const int Q = n * cap;   // rows of one frame
+  const bool merge = batched && F > 1 && n == 1 && merged_batch_ok(ctx, prm);
+  int rc = prepare_frame(ctx, F * Q, Q, merge ? F : 1);
+  if (rc) return rc;
+  if ((rc = ensure_images_frame(ctx, F * n, cap, (size_t)F * Q))) return rc;
+  mh_ctx::ImagesFrame& m = ctx->imf;
+  if (n > 1) {
+    ctx->q_img = m.q_img;
+    ctx->cams_dev = m.cams;
+  }
+  hipStream_t s = ctx->stream;
+  // UNDISTORTED_IMAGE per camera: one remap launch, every image with the map of its camera (one set of coefficients
+  // from mh_frame_set_undistort goes with every camera's K)
+  const uint8_t* staged[MH_MAX_BATCH];
+  if (m.und_n || ctx->und_on) {
+    float one[MH_MAX_IMAGES][4];
+    for (int i = 0; i < n; ++i) std::memcpy(one[i], ctx->und_dist, sizeof one[i]);
+    if ((rc = undistort_frame_images(ctx, gray_dev, F * n, n, width, height, cams, m.und_n ? m.und_dist : one, staged))) return rc;
+    gray_dev = staged;
+  }
+  // FEAT: one launch per stage for the F n images, image j's list at rows j cap .. of the staging area
+  if ((rc = sift_into_batch(ctx, gray_dev, F * n, width, height, double_size, cap, m.desc, m.xy, m.words))) return rc;
+  ImagesPackArgs pa;
+  pa.sdesc = m.desc;
+  pa.sxy = m.xy;
+  pa.scount = m.words;
+  pa.desc = ctx->q_desc;
+  pa.uv = ctx->q_uv;
+  pa.q_img = m.q_img;
+  pa.totals = batched ? m.words + MH_MAX_BATCH : images_single_total(ctx);
+  pa.counts = batched ? m.words + 2 * MH_MAX_BATCH : images_single_total(ctx) + 1;
+  pa.cams_dev = m.cams;
+  pa.cap = cap;
+  pa.n_images = n;
+  for (int i = 0; i < MH_MAX_IMAGES; ++i) pa.cams[i] = make_devcam(cams[i < n ? i : 0]);
+  launch_images_pack(pa, F, s);
+  MH_HIP(ctx, hipGetLastError());
+  if (!batched) {   // the frame alone, as mh_frame_enqueue_image: launches for the capacity, the kernels read the total
+    int32_t* n_dev = pa.totals;
+    ctx->feat_count_dev = n_dev;
+    m.n_live = n;
+    stamp(ctx, 0);
+    launch_normalize(ctx->q_desc, ctx->q_norm, Q, s, n_dev);
+    if ((rc = ctx_match(ctx, ctx->q_desc, ctx->q_norm, Q, ctx->nn_idx, ctx->nn_d1, ctx->nn_d2, n_dev, ctx->feat_expected)))
+      return rc;
+    stamp(ctx, 1);
+    return frame_rest(ctx, ctx->q_uv, Q, nullptr, 0, &cams[0], prm, seeds[0]);
+  }
+  // the batch, as mh_frame_enqueue_image_batch with a frame's packed list in an image's place
+  launch_normalize_batch(ctx->q_desc, ctx->q_norm, Q, F, s, pa.totals);
+  MH_HIP(ctx, hipGetLastError());
+  ctx->feat_count_dev = nullptr;
+  m.n_live = 0;
+  stamp(ctx, 0);
+  hipLaunchKernelGGL(image_batch_tail_kernel, dim3((F * Q * (DIM / 4) + 255) / 256), dim3(256), 0, s, ctx->q_desc, ctx->q_norm,
+                     pa.totals, Q, F);
+  if ((rc = ctx_match(ctx, ctx->q_desc, ctx->q_norm, F * Q, ctx->nn_idx, ctx->nn_d1, ctx->nn_d2))) return rc;
+  hipLaunchKernelGGL(image_batch_mask_kernel, dim3((F * Q + 255) / 256), dim3(256), 0, s, ctx->nn_idx, ctx->nn_d1, ctx->nn_d2,
+                     pa.totals, Q, F);
+  stamp(ctx, 1);
+  if (merge) {
+    if ((rc = ensure_batch_arenas(ctx, F))) return rc;
+    ctx->batch_q0 = 0;
+    ctx->fs->slot = 0;
+    return frame_rest(ctx, ctx->q_uv, Q, nullptr, 0, &cams[0], prm, seeds[0], seeds, F);
+  }
+  for (int f = 0; f < F && rc == MH_OK; ++f) {
+    ctx->batch_q0 = f * Q;
+    ctx->batch_f = f;   // (the frame's slice of the image indices)
+    ctx->fs->slot = f;
+    rc = frame_rest(ctx, ctx->q_uv + 2 * (size_t)f * Q, Q, nullptr, 0, &cams[0], prm, seeds[f]);
+  }
+  return rc;
+}
+
+int mh_frame_enqueue_images(mh_ctx* ctx, const uint8_t* const* gray_dev, int n_images, int width, int height, int double_size,
+                            int max_keypoints_per_image, const mh_cam* cams, const mh_frame_params* prm, uint64_t seed) {
+  return enqueue_images(ctx, "mh_frame_enqueue_images", gray_dev, 1, n_images, width, height, double_size,
+                        max_keypoints_per_image, cams, prm, &seed, false);
+}
+
+int mh_frame_enqueue_images_batch(mh_ctx* ctx, const uint8_t* const* gray_dev, int n_frames, int n_images, int width,
+                                  int height, int double_size, int max_keypoints_per_image, const mh_cam* cams,
+                                  const mh_frame_params* prm, const uint64_t* seeds) {
+  return enqueue_images(ctx, "mh_frame_enqueue_images_batch", gray_dev, n_frames, n_images, width, height, double_size,
+                        max_keypoints_per_image, cams, prm, seeds, true);
+}
+
+int mh_frame_image_counts(mh_ctx* ctx, int32_t* counts, int cap, int32_t* n_images) {
+  if (!ctx || !n_images || cap < 0 || (cap > 0 && !counts) || ctx->imf.last_n <= 0) return MH_ERR_ARG;
+  *n_images = ctx->imf.last_n;
+  for (int i = 0; i < ctx->imf.last_n && i < cap; ++i) counts[i] = ctx->imf.last[i];
+  return MH_OK;
+}
+
+int mh_frame_features_image_dev(mh_ctx* ctx, int32_t** q_image_dev) {
+  if (!ctx || !q_image_dev || !ctx->feat_count_dev || ctx->feat_count_dev != images_single_total(ctx) || !ctx->imf.n_live)
+    return MH_ERR_ARG;
+  *q_image_dev = ctx->imf.q_img;
+  return MH_OK;
+}
+
 int mh_frame_features_dev(mh_ctx* ctx, float** desc_dev, float** uv_dev, int32_t** n_dev) {
   if (!ctx || !ctx->feat_count_dev) return MH_ERR_ARG;
   if (desc_dev) *desc_dev = ctx->q_desc;
@@ -1764,14 +1947,21 @@ int mh_frame_fetch(mh_ctx* ctx, mh_object* objects_host, int max_objects, int32_
   MH_HIP(ctx, hipMemcpyAsync(pin.snap, fs->snap, sizeof pin.snap, hipMemcpyDeviceToHost, ctx->stream));
   MH_HIP(ctx, hipMemcpyAsync(&pin.fc, fs->counts, sizeof pin.fc, hipMemcpyDeviceToHost, ctx->stream));
   pin.n_feat = -1;
+  // (a frame of several cameras: its images' counts come with its total)
+  const int rig = ctx->feat_count_dev && ctx->feat_count_dev == images_single_total(ctx) ? ctx->imf.n_live : 0;
   if (ctx->feat_count_dev)
-    MH_HIP(ctx, hipMemcpyAsync(&pin.n_feat, ctx->feat_count_dev, sizeof pin.n_feat, hipMemcpyDeviceToHost, ctx->stream));
+    MH_HIP(ctx, hipMemcpyAsync(&pin.n_feat, ctx->feat_count_dev, sizeof(int32_t) * (1 + rig), hipMemcpyDeviceToHost, ctx->stream));
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const int32_t* head = pin.head;
   const int32_t* snap = pin.snap;
   const FrameCounts fc = pin.fc;
   const int32_t n_feat = pin.n_feat;
-  if (n_feat >= 0) ctx->feat_expected = ctx->feat_last = n_feat;
+  if (n_feat >= 0) {
+    ctx->feat_expected = ctx->feat_last = n_feat;
+    ctx->imf.last_n = rig ? rig : 1;
+    ctx->imf.last[0] = n_feat;
+    for (int i = 0; i < rig; ++i) ctx->imf.last[i] = pin.img_n[i];
+  }
   const int n = head[0];
   *n_objects = n;
   if (counts) std::memcpy(counts, snap, 4 * sizeof(int32_t));

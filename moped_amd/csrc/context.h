@@ -228,6 +228,23 @@ struct mh_ctx {
   mh::DevCam* cams_dev = nullptr;     // device, [MH_MAX_IMAGES]
   int n_images = 1;
 
+  // frames with several cameras from device images (mh_frame_enqueue_images[_batch]): FEAT writes every image's list at a
+  // stride of `cap` rows here, images_pack_kernel hands them over to the frames' packed lists (images_pack.hip)
+  struct ImagesFrame {
+    float* desc = nullptr;         // device [rows][128]
+    float* xy = nullptr;           // device [rows][2]
+    size_t rows = 0;
+    int32_t* words = nullptr;      // device [3][MH_MAX_BATCH]: FEAT's count per image | the clamped count per image | the total per frame
+    int32_t* q_img = nullptr;      // device: image index of every row of the packed lists
+    size_t q_img_cap = 0;
+    mh::DevCam* cams = nullptr;    // device [MH_MAX_IMAGES]: the rig of the call in flight (the table of mh_frame_set_images stays the caller's)
+    int n_live = 0;                // images of the frame whose total feat_count_dev names (0: not such a frame)
+    int last_n = 0;                // mh_frame_image_counts: images of the frame last fetched, their clamped counts
+    int32_t last[MH_MAX_IMAGES] = {};
+    int und_n = 0;                 // mh_frame_set_undistort_images: cameras with coefficients of their own (0 = off)
+    float und_dist[MH_MAX_IMAGES][4] = {};
+  } imf;
+
   // optional depth attributes of the current queries (moped3d residuals)
   const mh_depth* q_depth = nullptr;
   int depth_kind = 0;
@@ -318,5 +335,27 @@ int undistort_frame(mh_ctx* ctx, const uint8_t* const* gray_dev, int n, int widt
                     const uint8_t** staged);
 int sift_into_batch(mh_ctx* ctx, const uint8_t* const* gray_dev, int n, int width, int height, int double_size, int cap,
                     float* desc_dev, float* xy_dev, int32_t* count_words);
+// undistort.hip: the same for a rig -- image f is camera f % n_cams' and gets the map of (cams[..].K, dist[..])
+int undistort_frame_images(mh_ctx* ctx, const uint8_t* const* gray_dev, int n, int n_cams, int width, int height,
+                           const mh_cam* cams, const float (*dist)[4], const uint8_t** staged);
+
+// images_pack.hip: the hand-over from FEAT's strided per-image lists to the packed lists of n_frames frames of n_images
+// cameras each, one launch.  Image j = f n_images + i has sdesc + j cap 128, sxy + j cap 2 and its count in scount[j]
+// (clamped to cap here); frame f's list starts at row f n_images cap of desc / uv / q_img, image after image, its length
+// goes to totals[f], the clamped counts to counts[j], the rig to cams_dev.
+struct ImagesPackArgs {
+  const float* sdesc;
+  const float* sxy;
+  const int32_t* scount;
+  float* desc;
+  float* uv;
+  int32_t* q_img;
+  int32_t* totals;
+  int32_t* counts;
+  DevCam* cams_dev;
+  int cap, n_images;
+  DevCam cams[MH_MAX_IMAGES];
+};
+void launch_images_pack(const ImagesPackArgs& a, int n_frames, hipStream_t s);
 
 }  // namespace mh

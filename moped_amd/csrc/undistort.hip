@@ -37,6 +37,7 @@ struct UndMap {
 struct RemapImages {
   const uint8_t* src[MH_MAX_BATCH];
   uint8_t* dst[MH_MAX_BATCH];
+  const FixPos* fix[MH_MAX_BATCH];   // every image its camera's map (one camera: the same pointer throughout)
 };
 
 // cvRound of mapx * INTER_TAB_SIZE (round half to even); NaN and values beyond int32 give INT_MIN, as the
@@ -85,12 +86,13 @@ __global__ void map_build_kernel(int w, int h, double fx, double fy, double cx, 
 }
 
 // remapBilinear (OpenCV 2.x, imgwarp.cpp) on 8-bit pixels, BORDER_CONSTANT 0: one thread per output pixel,
-// blockIdx.z = image of a batch (all of one size and one map)
-__global__ void remap_kernel(RemapImages imgs, const FixPos* __restrict__ fix, int w, int h) {
+// blockIdx.z = image of a batch (all of one size, every one with the map of its camera)
+__global__ void remap_kernel(RemapImages imgs, int w, int h) {
   const size_t n = (size_t)w * h;
   const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n) return;
   const uint8_t* __restrict__ src = imgs.src[blockIdx.z];
+  const FixPos* __restrict__ fix = imgs.fix[blockIdx.z];
   const FixPos f = fix[p];
   const int sx = f.sx, sy = f.sy, ax = f.a & 31, ay = f.a >> 5;
   const bool x0 = sx >= 0 && sx < w, x1 = sx + 1 >= 0 && sx + 1 < w;
@@ -204,17 +206,23 @@ int get_map(mh_ctx* ctx, int width, int height, const float* K, const float* dis
   return MH_OK;
 }
 
-int launch_remap(mh_ctx* ctx, const UndMap* m, const uint8_t* const* src, uint8_t* const* dst, int n_images) {
+// maps[f % n_maps] = the map of image f (a rig's images lie camera after camera, frame after frame)
+int launch_remap(mh_ctx* ctx, UndMap* const* maps, int n_maps, const uint8_t* const* src, uint8_t* const* dst, int n_images) {
   RemapImages imgs = {};
   for (int f = 0; f < n_images; ++f) {
     imgs.src[f] = src[f];
     imgs.dst[f] = dst[f];
+    imgs.fix[f] = maps[f % n_maps]->fix;
   }
+  const UndMap* m = maps[0];
   const size_t n = (size_t)m->width * m->height;
   hipLaunchKernelGGL(remap_kernel, dim3((unsigned)((n + 255) / 256), 1, n_images), dim3(256), 0, ctx->stream, imgs,
-                     m->fix, m->width, m->height);
+                     m->width, m->height);
   MH_HIP(ctx, hipGetLastError());
   return MH_OK;
+}
+int launch_remap(mh_ctx* ctx, UndMap* m, const uint8_t* const* src, uint8_t* const* dst, int n_images) {
+  return launch_remap(ctx, &m, 1, src, dst, n_images);
 }
 
 int enter(mh_ctx* ctx) {
@@ -240,6 +248,27 @@ int undistort_frame(mh_ctx* ctx, const uint8_t* const* gray_dev, int n, int widt
   for (int f = 0; f < n; ++f) dst[f] = st->out + f * px;
   if (int rc = launch_remap(ctx, m, gray_dev, dst, n)) return rc;
   for (int f = 0; f < n; ++f) staged[f] = dst[f];   // (after the launch: staged may be gray_dev itself)
+  return MH_OK;
+}
+
+// Frames with several cameras (mh_frame_enqueue_images*): image f belongs to camera f % n_cams and is remapped with the
+// map of (width, height, cams[f % n_cams].K, dist[f % n_cams]) -- the entries of the same cache, still one launch.
+int undistort_frame_images(mh_ctx* ctx, const uint8_t* const* gray_dev, int n, int n_cams, int width, int height,
+                           const mh_cam* cams, const float (*dist)[4], const uint8_t** staged) {
+  static_assert(UND_ENTRIES >= MH_MAX_IMAGES, "a rig's maps must fit the cache together");
+  if (n_cams < 1 || n_cams > MH_MAX_IMAGES) return bad(ctx, "mh_frame_enqueue_images (undistortion)", "camera count");
+  for (int i = 0; i < n_cams; ++i)
+    if (int rc = check_camera(ctx, "mh_frame_enqueue_images (undistortion)", width, height, cams[i].K, dist[i])) return rc;
+  UndMap* maps[MH_MAX_IMAGES];
+  for (int i = 0; i < n_cams; ++i)   // (a miss evicts the least recently used entry: never one this loop has just touched)
+    if (int rc = get_map(ctx, width, height, cams[i].K, dist[i], &maps[i])) return rc;
+  const size_t px = (size_t)width * height;
+  UndistortState* st = ctx->und;
+  if (int rc = grow(ctx, st->out, st->out_cap, px * n)) return rc;
+  uint8_t* dst[MH_MAX_BATCH];
+  for (int f = 0; f < n; ++f) dst[f] = st->out + f * px;
+  if (int rc = launch_remap(ctx, maps, n_cams, gray_dev, dst, n)) return rc;
+  for (int f = 0; f < n; ++f) staged[f] = dst[f];
   return MH_OK;
 }
 
@@ -309,6 +338,23 @@ int mh_frame_set_undistort(mh_ctx* ctx, const float dist[4]) {
   if (!finite4(dist)) return bad(ctx, "mh_frame_set_undistort", "non-finite coefficients");
   std::memcpy(ctx->und_dist, dist, sizeof ctx->und_dist);
   ctx->und_on = true;
+  return MH_OK;
+}
+
+int mh_frame_set_undistort_images(mh_ctx* ctx, const float (*dist)[4], int n_images) {
+  if (!ctx) return MH_ERR_ARG;
+  if (!dist || n_images <= 0) {
+    ctx->imf.und_n = 0;
+    return MH_OK;
+  }
+  if (n_images > MH_MAX_IMAGES) {
+    ctx->err = "mh_frame_set_undistort_images: more than MH_MAX_IMAGES cameras";
+    return MH_ERR_CAPACITY;
+  }
+  for (int i = 0; i < n_images; ++i)
+    if (!finite4(dist[i])) return bad(ctx, "mh_frame_set_undistort_images", "non-finite coefficients");
+  std::memcpy(ctx->imf.und_dist, dist, sizeof(float) * 4 * n_images);
+  ctx->imf.und_n = n_images;
   return MH_OK;
 }
 

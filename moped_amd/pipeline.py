@@ -260,6 +260,31 @@ class FramePipeline:
         c.frame_enqueue_sharded_batch(self._comm(slot), q_desc.data_ptr(), q_uv.data_ptr(), Q, B, self.K, self.cam,
                                       self.params, seeds, _cam_struct=self._cam)
 
+    # ---- frames with several cameras from device images ------------------------------------------
+    def enqueue_images(self, slot: int, gray_ptrs, w: int, h: int, Ks, cams, seed: int = 1, max_keypoints: int = 2048,
+                       double_size: bool = True, keep=None):
+        """ONE frame seen by len(gray_ptrs) cameras (Ks [n,4], cams [n,7]): 8-bit device images of one size in, objects
+        out (fetch), the keypoint counts never leave the device.  The slot's context must have room for
+        n * max_keypoints queries.  `keep`: the images' tensors, held until the slot's next enqueue."""
+        if self.exchange:
+            raise ValueError("frames from device images run on one GPU's whole database")
+        self._inputs[slot] = keep
+        self._batch[slot] = 1
+        self.ctxs[slot].frame_enqueue_images(list(gray_ptrs), w, h, double_size, max_keypoints, Ks, cams, self.params, seed)
+
+    def enqueue_images_batch(self, slot: int, gray_ptrs, n_images: int, w: int, h: int, Ks, cams, seeds,
+                             max_keypoints: int = 2048, double_size: bool = True, keep=None):
+        """len(seeds) frames of one rig of n_images cameras (frame f's images: gray_ptrs[f n_images : (f + 1) n_images])
+        through one FEAT launch per stage and ONE MATCH launch sequence; their objects in result slots 0.. (fetch_batch)."""
+        if self.exchange:
+            raise ValueError("frames from device images run on one GPU's whole database")
+        B = len(seeds)
+        assert 1 <= B * n_images <= capi.MAX_BATCH
+        self._inputs[slot] = keep
+        self._batch[slot] = B
+        self.ctxs[slot].frame_enqueue_images_batch(list(gray_ptrs), n_images, w, h, double_size, max_keypoints, Ks, cams,
+                                                   self.params, seeds)
+
     def fetch_batch(self, slot: int, B: int):
         return [self.ctxs[slot].frame_fetch_slot(f) for f in range(B)]
 
