@@ -1,5 +1,5 @@
 // C ABI of libmoped_hip.so: context, model database, MATCH entry points.
-// (CLUSTER / POSE / FILTER / frame entry points live in api_steps.hip.)
+// (CLUSTER / POSE / FILTER / frame entry points live in api_frame.hip, api_stage.hip and api_step.hip.)
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -189,7 +189,7 @@ int mh_create(int device, mh_ctx** out) {
   return MH_OK;
 }
 
-void mh_free_frame_state(mh_ctx* ctx);  // api_steps.hip
+void mh_free_frame_state(mh_ctx* ctx);  // frame_rest.hip
 void mh_free_sift_state(mh_ctx* ctx);   // api_sift.hip
 void mh_free_undistort_state(mh_ctx* ctx);   // undistort.hip
 

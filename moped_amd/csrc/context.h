@@ -174,12 +174,10 @@ struct mh_ctx {
   // after normalize_kernel, so that the 1.5 MB copy runs beside MATCH .. FILTER2 instead of after them
   hipStream_t wb_stream = nullptr;
   hipEvent_t wb_ev = nullptr;
-  bool wb_want = false;   // the frame being enqueued records wb_ev after its normalisation
   bool wb_pending = false;   // a write-back is in flight on wb_stream (mh_frame_wait_descriptors)
 
-  // mh_step_*: the frame's six slots one call each.  stage_lo / stage_hi: what the next frame_rest launches (0 .. 5 =
-  // everything); step: where the resident frame stands and what the host needs to know to read its results back.
-  int stage_lo = 0, stage_hi = 5;
+  // mh_step_*: the frame's six slots one call each (api_step.hip).  step: where the resident frame stands and what the
+  // host needs to know to read its results back.
   struct StepState {
     int done = -1;          // last stage run on the resident frame (-1: none / invalidated)
     int Q = 0, M = 0;       // queries, accepted matches
@@ -191,7 +189,7 @@ struct mh_ctx {
     std::vector<int32_t> valid_model; // ... and the model of each
   } step;
 
-  // frame state (group / cluster / pose / filter); defined in frame.h
+  // frame state (group / cluster / pose / filter): frame.h, allocated by frame_rest.hip
   struct FrameState* fs = nullptr;
   struct SiftState* sift = nullptr;   // pyramid + keypoint buffers of the SIFT extractor (api_sift.hip)
   struct UndistortState* und = nullptr;   // undistortion maps + staging (undistort.hip); made on first use
@@ -201,13 +199,9 @@ struct mh_ctx {
   int32_t* img_counts = nullptr;      // mh_frame_enqueue_image_batch: [MH_MAX_BATCH] keypoint counts of the batch's images (device)
   int feat_expected = 0;              // keypoints of the last fetched image frame (sizes the next MATCH launch)
   int feat_last = -1;
-  int batch_q0 = 0;                   // first query of the frame frame_rest works on (mh_frame_enqueue_batch)
-  int batch_f = 0;                    // ... and its number in the batch: the frame's slice of per-query attributes that lie frame after frame (q_img)
   const float4* batch_img[MH_MAX_BATCH] = {};   // depth maps of the frames of a batch (mh_frame_set_depth_image_batch)
   const float* batch_fill[MH_MAX_BATCH] = {};
   int batch_imgs = 0;                 // how many of them are set (0: one depth map, one frame)
-  int exchange_plane = 0;             // words between the idx / d1 / d2 planes of one shard's block (0 = Q)
-  int exchange_stride = 0;            // words between the shards' blocks of the gathered exchange buffer (0 = 3 Q)
   const int32_t* exchange_tags = nullptr;   // comm.hip: shard 0's tag words in the gathered buffer (checked by the frame's first launch)
 
   // N > 1 (comm.hip): the send / receive blocks of the frame exchange, the flush buffer of the last frames
@@ -322,7 +316,7 @@ int ensure_match_scratch(mh_ctx* ctx, int Q);
 // two-stage screen when it pays and the DB allows it, else by the exact kernels (bit-identical results either way).
 int ctx_match(mh_ctx* ctx, const float* qn, const float* qnorm, int Q, int32_t* idx1, float* d1, float* d2,
               const int32_t* q_count = nullptr, int q_expected = 0);
-// Delivery of a batch's heads into a caller's host block (api_steps.hip): delivery_begin -> where the delivering kernel
+// Delivery of a batch's heads into a caller's host block (api_frame.hip): delivery_begin -> where the delivering kernel
 // writes (the block itself when the device can address it, else the context's staging buffer); delivery_end -> the copy
 // out of the staging buffer if one is needed, and the event behind it all.
 int delivery_begin(mh_ctx* ctx, void* host_block, size_t bytes, unsigned char** dst_dev);

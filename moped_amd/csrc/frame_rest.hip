@@ -1,0 +1,553 @@
+// The device-resident frame: its buffers (FrameState) and frame_rest, CLUSTER .. FILTER2 behind MATCH.
+#include <cstring>
+#include <type_traits>
+
+#include "frame.h"
+
+namespace mh {
+namespace {
+
+template <typename T>
+int dev_alloc(mh_ctx* ctx, T*& p, size_t n) {
+  MH_HIP(ctx, hipMalloc(&p, (n > 0 ? n : 1) * sizeof(T)));
+  return MH_OK;
+}
+
+}  // namespace
+
+void free_fs(FrameState* fs) {
+  if (!fs) return;
+  void* ptrs[] = {fs->arena, fs->result, fs->snap, fs->fuse_dev};
+  for (void* p : ptrs)
+    if (p) hipFree(p);
+  if (fs->fb) hipHostFree(fs->fb);
+  if (fs->fetch_pin) hipHostFree(fs->fetch_pin);
+  if (fs->host_block) hipHostFree(fs->host_block);
+  delete fs;
+}
+
+int ensure_fs(mh_ctx* ctx, int max_m, int max_clusters, int max_objects, int n_models, int n_arenas) {
+  FrameState* fs = ctx->fs;
+  if (fs && fs->max_m >= max_m && fs->max_clusters >= max_clusters &&
+      fs->max_objects >= max_objects && fs->n_models_cap >= n_models && fs->n_arenas >= n_arenas)
+    return MH_OK;
+  int task_grid = 0, ms_grid = 0;
+  unsigned char* kept_result = nullptr;
+  int32_t* kept_snap = nullptr;
+  if (fs) {
+    n_arenas = std::max(n_arenas, fs->n_arenas);
+    task_grid = fs->task_grid;
+    ms_grid = fs->ms_grid;
+    max_m = std::max(max_m, fs->max_m);
+    max_clusters = std::max(max_clusters, fs->max_clusters);
+    max_objects = std::max(max_objects, fs->max_objects);
+    n_models = std::max(n_models, fs->n_models_cap);
+    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (max_objects == fs->max_objects) {   // the result blocks keep their size: frames not fetched yet stay fetchable
+      kept_result = fs->result;
+      kept_snap = fs->snap;
+      fs->result = nullptr;
+      fs->snap = nullptr;
+    }
+    free_fs(fs);
+    ctx->fs = nullptr;
+  }
+  fs = new FrameState;
+  ctx->fs = fs;
+  fs->max_m = max_m;
+  fs->max_clusters = max_clusters;
+  fs->max_objects = max_objects;
+  fs->n_models_cap = n_models;
+  fs->n_arenas = n_arenas;
+  if (task_grid) {   // (what the launches had learnt about the frames' task counts)
+    fs->task_grid = task_grid;
+    fs->ms_grid = ms_grid;
+  }
+  int rc = 0;
+  // two passes over the same list: sizes first (pointers are offsets into a null arena), then the real addresses
+  for (int pass = 0; pass < 2 && !rc; ++pass) {
+    size_t off = 0;
+    unsigned char* const base = fs->arena;
+    auto carve = [&](auto*& p, size_t n) {
+      typedef typename std::remove_reference<decltype(*p)>::type T;
+      p = reinterpret_cast<T*>(base + off);
+      off += ((n > 0 ? n : 1) * sizeof(T) + 255) & ~(size_t)255;
+    };
+    carve(fs->counts, 1);
+    carve(fs->n_slots, 1);
+    carve(fs->n_clusters, 1);
+    carve(fs->n_clusters2, 1);
+    carve(fs->tickets, 8);
+    carve(fs->acc_q, max_m);
+    carve(fs->acc_model, max_m);
+    carve(fs->m_q, max_m);
+    carve(fs->m_model, max_m);
+    carve(fs->m_rep, max_m);
+    carve(fs->m_corr, max_m);
+    carve(fs->m_depth, max_m);
+    carve(fs->m_img, max_m);
+    carve(fs->mi_img, max_m);
+    carve(fs->mi_corr, max_m);
+    carve(fs->off2, (size_t)n_models + 1);
+    carve(fs->model_off, (size_t)n_models + 1);
+    carve(fs->ms_members, max_m);
+    carve(fs->ms_cl_start, (size_t)max_m + n_models + 1);
+    carve(fs->ms_ncl, (size_t)n_models + 1);
+    carve(fs->cl_model, max_clusters);
+    carve(fs->cl_begin, max_clusters);
+    carve(fs->cl_count, max_clusters);
+    carve(fs->obj_model, max_objects);
+    carve(fs->obj_ninl, max_objects);
+    carve(fs->obj_cluster, max_objects);
+    carve(fs->obj_valid, max_objects);
+    carve(fs->obj_npts, max_objects);
+    carve(fs->obj_clsize, (size_t)2 * max_objects);
+    carve(fs->obj_pose, (size_t)7 * max_objects);
+    carve(fs->obj_err, max_objects);
+    carve(fs->obj_score, max_objects);
+    carve(fs->obj_score_raw, max_objects);
+    carve(fs->best, max_m);
+    carve(fs->new_members, max_m);
+    carve(fs->hyp, max_objects);
+    carve(fs->rf_pts, (size_t)9 * max_m);
+    carve(fs->rf_list, (size_t)4 * max_m);
+    if (pass == 0) {
+      fs->arena_bytes = off;
+      rc |= dev_alloc(ctx, fs->arena, off * n_arenas);
+    }
+  }
+  fs->result_bytes = 16 + sizeof(mh_object) * (size_t)max_objects;
+  if (kept_result) {
+    fs->result = kept_result;
+    fs->snap = kept_snap;
+  } else {
+    rc |= dev_alloc(ctx, fs->result, fs->result_bytes * MH_MAX_BATCH);
+    if (!rc) MH_HIP(ctx, hipMemsetAsync(fs->result, 0, fs->result_bytes * MH_MAX_BATCH, ctx->stream));   // "0 objects" before the first frame
+    rc |= dev_alloc(ctx, fs->snap, 4 * MH_MAX_BATCH);
+    if (!rc) MH_HIP(ctx, hipMemsetAsync(fs->snap, 0, sizeof(int32_t) * 4 * MH_MAX_BATCH, ctx->stream));   // (a slot fetched before it was written reads zeros)
+  }
+  rc |= dev_alloc(ctx, fs->fuse_dev, 2);
+  if (!rc) {
+    if (hipHostMalloc(&fs->fb, 3 * MH_MAX_BATCH * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) rc = MH_ERR_HIP;
+    else std::memset(fs->fb, 0xFF, 3 * MH_MAX_BATCH * sizeof(int32_t));   // -1 = nothing known yet
+    if (hipHostMalloc(&fs->fetch_pin, sizeof(*fs->fetch_pin), hipHostMallocDefault) != hipSuccess) rc = MH_ERR_HIP;
+    if (hipHostMalloc(&fs->host_block, sizeof(*fs->host_block), hipHostMallocDefault) != hipSuccess) rc = MH_ERR_HIP;
+    else std::memset(fs->host_block, 0, sizeof(*fs->host_block));
+  }
+  if (rc) {   // a half-built state must not look valid to the next call
+    free_fs(fs);
+    ctx->fs = nullptr;
+    return MH_ERR_HIP;
+  }
+  // every frame's tickets, claim table (best), obj_valid / obj_score / obj_npts start at zero
+  MH_HIP(ctx, hipMemsetAsync(fs->arena, 0, fs->arena_bytes * n_arenas, ctx->stream));
+  fs->host_seq_expect = 0;   // (tickets[7], the device's count of host-block writes, is zero again)
+  fs->host_armed = false;
+  return MH_OK;
+}
+
+FilterBuffers make_fb(const FrameState* fs, int n_models) {
+  FilterBuffers fb;
+  fb.corr = fs->m_corr;
+  fb.m_rep = fs->m_rep;
+  fb.m_img = nullptr;
+  fb.cams = nullptr;
+  fb.n_images = 1;
+  fb.model_off = fs->model_off;
+  fb.n_models = n_models;
+  fb.max_m = fs->max_m;
+  fb.obj_model = fs->obj_model;
+  fb.obj_pose = fs->obj_pose;
+  fb.obj_score = fs->obj_score;
+  fb.obj_score_raw = fs->obj_score_raw;
+  fb.obj_valid = fs->obj_valid;
+  fb.obj_npts = fs->obj_npts;
+  fb.max_objects = fs->max_objects;
+  fb.best = fs->best;
+  fb.obj_clsize = fs->obj_clsize;
+  fb.new_members = fs->new_members;
+  fb.cl_model = fs->cl_model;
+  fb.cl_begin = fs->cl_begin;
+  fb.cl_count = fs->cl_count;
+  fb.max_clusters = fs->max_clusters;
+  return fb;
+}
+
+namespace {
+
+// Result block of a frame that stops after POSE (run_stage2 = 0): the valid objects in
+// list order.  Frames with the FILTER stages get it from the last FILTER launch.
+__global__ void pack_result_kernel(unsigned char* result, const int32_t* n_slots,
+                                   const int32_t* obj_valid, const int32_t* obj_model,
+                                   const float* obj_pose, const float* obj_score,
+                                   const int32_t* obj_npts, int max_objects, const FrameCounts* counts) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  mh_object* out = reinterpret_cast<mh_object*>(result + 16);
+  int k = 0;
+  const int n = *n_slots;
+  for (int o = 0; o < n && k < max_objects; ++o) {
+    if (!obj_valid[o]) continue;
+    mh_object ob;
+    ob.model = obj_model[o];
+    for (int j = 0; j < 7; ++j) ob.pose[j] = obj_pose[7 * o + j];
+    ob.score = obj_score[o];
+    ob.n_points = obj_npts[o];
+    out[k++] = ob;
+  }
+  reinterpret_cast<int32_t*>(result)[0] = k;
+  reinterpret_cast<int32_t*>(result)[1] = counts->error;   // capacity flags, as the last FILTER launch reports them
+}
+
+}  // namespace
+
+int ensure_linkage_scratch(mh_ctx* ctx, size_t floats) {
+  if (floats <= ctx->lk_scratch_floats) return MH_OK;
+  // 3 n^2 floats per (model, frame) problem: 37 MB per frame at 3 000 matches, 0.6 GB for a batch of 16 -- and it grows
+  // with the square of what a caller reserves.  Bounded per context (mh_set_linkage_scratch_limit, default 4 GiB)
+  // with an error the caller can act on instead of an allocation that takes the device's memory from the other slots.
+  if (floats * sizeof(float) > ctx->lk_scratch_limit) {
+    ctx->err = "linkage clusterer: " + std::to_string(floats * sizeof(float) >> 20) + " MiB of similarity-matrix scratch asked for, the "
+               "context's limit is " + std::to_string(ctx->lk_scratch_limit >> 20) + " MiB (fewer frames per batch, fewer queries "
+               "reserved, or mh_set_linkage_scratch_limit)";
+    return MH_ERR_CAPACITY;
+  }
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (ctx->lk_scratch) MH_HIP(ctx, hipFree(ctx->lk_scratch));
+  ctx->lk_scratch = nullptr;
+  ctx->lk_scratch_floats = 0;
+  MH_HIP(ctx, hipMalloc(&ctx->lk_scratch, floats * sizeof(float)));
+  ctx->lk_scratch_floats = floats;
+  return MH_OK;
+}
+
+// Device buffers of the depth rules: patch map, per-(model, patch) counts (kept zero), keep flags.
+// (frames > 1: a merged batch -- every frame's patch map, counters and keep flags, frame after frame)
+static int ensure_rule_buffers(mh_ctx* ctx, int patches, int Q, int frames) {
+  mh_ctx::DepthRuleState& rs = ctx->rules;
+  if (patches > 4096) {
+    ctx->err = "depth rules: more than 4096 patches (raise PatchSize)";
+    return MH_ERR_CAPACITY;
+  }
+  Q *= frames;
+  if (patches * frames > rs.patches_cap) {
+    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (rs.inv_size) MH_HIP(ctx, hipFree(rs.inv_size));
+    rs.inv_size = nullptr;
+    MH_HIP(ctx, hipMalloc(&rs.inv_size, sizeof(double) * patches * frames));
+    rs.patches_cap = patches * frames;
+  }
+  const size_t need = (size_t)std::max(ctx->n_models, 1) * patches * frames;
+  if (need > rs.cnt_cap) {
+    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (rs.cnt) MH_HIP(ctx, hipFree(rs.cnt));
+    rs.cnt = nullptr;
+    MH_HIP(ctx, hipMalloc(&rs.cnt, sizeof(int32_t) * need));
+    MH_HIP(ctx, hipMemsetAsync(rs.cnt, 0, sizeof(int32_t) * need, ctx->stream));
+    rs.cnt_cap = need;
+  }
+  if (Q > rs.keep_cap) {
+    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (rs.keep1) MH_HIP(ctx, hipFree(rs.keep1));
+    rs.keep1 = nullptr;
+    MH_HIP(ctx, hipMalloc(&rs.keep1, (size_t)Q));
+    rs.keep_cap = Q;
+  }
+  return MH_OK;
+}
+
+void stamp(mh_ctx* ctx, int i) {
+  if (ctx->timing) hipEventRecord(ctx->ev[i], ctx->stream);
+}
+
+// CLUSTER .. FILTER2 of a device-resident frame in six launches, from the call's record (FrameCall, frame.h) and the
+// context's longer-lived state alone.  c.gathered != nullptr: exchange-1 blocks ([n_shards][3][Q]) to merge first.
+// c.batch_n > 1: the frames of a batch together, one launch per stage (FrameBatch, steps.h; the caller has checked
+// merged_batch_ok) -- q_uv / the top-2 arrays name frame 0's, the slot is 0, c.seeds the frames' seeds.
+// c.stage_lo .. c.stage_hi (mh_step_*: the six slots one call each on a frame that stays on the device): only the stages
+// 0 MATCH's tail (ratio test + lists), 1 CLUSTER, 2 POSE, 3 FILTER, 4 POSE2, 5 FILTER2 in that range are launched, FILTER
+// as launches of its own; everything else of the frame's state is left as the stage before wrote it.
+int frame_rest(mh_ctx* ctx, const FrameCall& c) {
+  FrameState* fs = ctx->fs;
+  const float* const q_uv_dev = c.q_uv;
+  const int Q = c.Q, batch_n = c.batch_n, stage_lo = c.stage_lo, stage_hi = c.stage_hi;
+  const mh_frame_params* const prm = c.prm;
+  const bool stepped = stage_lo != 0 || stage_hi != 5;
+  auto runs = [&](int stage) { return stage >= stage_lo && stage <= stage_hi; };
+  if (!stepped) ctx->step.done = -1;   // (a whole frame overwrites whatever a stepped frame left in the arrays)
+  FrameBatch fb1, fb2;
+  const FrameBatch *b1 = nullptr, *b2 = nullptr;
+  if (batch_n > 1) {
+    fb1.arena = fs->arena_bytes;
+    fb1.q = Q;
+    fb1.result_bytes = (int)fs->result_bytes;
+    fb1.n = batch_n;
+    fb2 = fb1;
+    for (int f = 0; f < batch_n; ++f) {
+      fb1.seed[f] = c.seeds[f];
+      fb2.seed[f] = c.seeds[f] ^ 0x5DEECE66Dull;
+    }
+    b1 = &fb1;
+    b2 = &fb2;
+  }
+  hipStream_t s = ctx->stream;
+  const DevCam dc = make_devcam(*c.cam);
+  const int nm = ctx->n_models;
+  // group_kernel keeps one LDS histogram bin per model: every entry point (fused, sharded, batched)
+  // comes through here, so the bound is checked here and not in the callers
+  if (nm > MH_MAX_MODELS) {
+    ctx->err = "more than 8192 models per context";
+    return MH_ERR_CAPACITY;
+  }
+  unsigned char* const result = fs->result + (size_t)c.slot * fs->result_bytes;
+  int32_t* const snap = fs->snap + 4 * c.slot;
+  // (mh_frame_fetch_matches_slot: a merged batch leaves every frame's lists in its own arena, a frame on its own in arena 0)
+  fs->list_first = c.slot;
+  fs->list_n = batch_n > 1 ? batch_n : 1;
+  // Every workgroup of the POSE / FILTER launches needs a free compute unit to start even if
+  // it has no task, and MATCH kernels of other frames keep all of them busy: launch about as
+  // many workgroups as the previous frame had tasks (experiment builds: MH_TASK_GRID pins the number, MH_MS_GRID the
+  // CLUSTER launch's -- 0 = one workgroup per model, the old shape).
+  static const int grid_env = exp_int("MH_TASK_GRID", 0);
+  // POSE / POSE2: one row of workgroups for all frames of the launch, about as many as the launches before found tasks
+  // (+ 25%); nothing known yet: the per-frame guess (the last fetched frame's task count) times the frames
+  // (what the launches before found in the batch's frames, or `guess` where one of them is not known yet)
+  auto found_or = [&](const int32_t* found, long guess) {
+    long sum = 0;
+    for (int f = 0; f < batch_n; ++f) {
+      if (found[f] < 0) return guess;
+      sum += found[f];
+    }
+    return sum;
+  };
+  auto pose_grid = [&](const int32_t* found) {
+    if (grid_env > 0) return grid_env;
+    const long sum = found_or(found, (long)fs->task_grid * batch_n / 2);
+    return (int)std::min<long>(160, std::max<long>(8, sum + sum / 4 + 2));
+  };
+  const int grid = pose_grid(fs->fb), grid2 = pose_grid(fs->fb + MH_MAX_BATCH);
+  static const int ms_grid_env = exp_int("MH_MS_GRID", -1);
+  // CLUSTER: one row of workgroups for all frames of the launch, as many as the launches before found models to cluster
+  // (+ 1 per 8); nothing known yet: the per-frame guess times the frames.  Every one of them takes a whole compute unit.
+  int ms_grid = fs->ms_grid;
+  {
+    const long sum = found_or(fs->fb + 2 * MH_MAX_BATCH, (long)std::max(2, fs->ms_grid / 2) * batch_n);
+    ms_grid = (int)std::min<long>(48, std::max<long>(batch_n > 1 ? 4 : 2, sum + sum / 8 + 1));
+    if (batch_n == 1) ms_grid = std::max(ms_grid, std::min(fs->ms_grid, 8));
+  }
+  if (ms_grid_env >= 0) ms_grid = ms_grid_env;
+  const bool multi = ctx->q_img && ctx->n_images > 1 && ctx->cams_dev;
+  DepthImage dimg = ctx->depth_img;   // as the setter left it, or with the frame's own map of a batch that has one per frame
+  if (c.img) {
+    dimg.img = c.img;
+    dimg.fill = c.fill;
+  }
+  if (multi && (ctx->q_depth || dimg.img || ctx->linkage_on)) {
+    ctx->err = "frames with several images: the moped3d depth steps are single-camera";
+    return MH_ERR_ARG;
+  }
+  // a merged batch with a depth map per frame (mh_frame_set_depth_image_batch; merged_batch_ok has checked the count)
+  DepthMaps dmaps;
+  const DepthMaps* maps = nullptr;
+  if (batch_n > 1 && dimg.img) {
+    for (int f = 0; f < batch_n; ++f) {
+      dmaps.img[f] = ctx->batch_img[f];
+      dmaps.fill[f] = ctx->batch_fill[f];
+    }
+    maps = &dmaps;
+  }
+  // moped3d depth rules: patch maps of this frame's depth image, DEPTHFILTER on the features
+  DepthRules rules;
+  if (ctx->rules.on && dimg.img && runs(0)) {
+    mh_ctx::DepthRuleState& rs = ctx->rules;
+    const int pw = (dimg.w + rs.patch - 1) / rs.patch, ph = (dimg.h + rs.patch - 1) / rs.patch;
+    int rc = ensure_rule_buffers(ctx, pw * ph, Q, batch_n);
+    if (rc) return rc;
+    const bool filters = rs.feature_filter >= 0.f || rs.match_filter >= 0.f;
+    if (filters) launch_depth_patches(dimg, rs.K, rs.patch, rs.inv_size, s, maps, batch_n);
+    if (rs.feature_filter >= 0.f) {
+      launch_feature_density(q_uv_dev, Q, ctx->feat_count_dev, rs.patch, pw, ph, rs.inv_size, rs.feature_filter,
+                             rs.keep1, s, batch_n);
+      rules.keep1 = rs.keep1;
+    }
+    if (rs.match_filter >= 0.f) {
+      rules.inv_size = rs.inv_size;
+      rules.cnt = rs.cnt;
+      rules.filter2 = rs.match_filter;
+    }
+    rules.patch = rs.patch;
+    rules.pw = pw;
+    rules.ph = ph;
+    if (rs.ratio_table && rs.table_models >= nm) rules.ratio_table = reinterpret_cast<const float4*>(rs.ratio_table);
+    rules.max_depth = rs.max_depth;
+    rules.default_depth = rs.default_depth;
+    rules.cauchy_scale = rs.cauchy_scale;
+  }
+  // MATCH tail: (shard merge,) ratio test + per-model lists; resets the frame's counters
+  const int q0 = c.q0;   // frame of a batch matched in one launch: its slice of the top-2 arrays
+  if (runs(0))
+  launch_group(c.gathered, c.n_shards, ctx->nn_idx + q0, ctx->nn_d1 + q0, ctx->nn_d2 + q0, Q, prm->ratio, q_uv_dev,
+               ctx->db_model, ctx->db_xyz, ctx->N, ctx->rmap, nm, fs->max_m, fs->acc_q,
+               fs->acc_model, fs->m_q, fs->m_model, fs->m_corr, fs->m_rep, fs->model_off,
+               ctx->q_depth ? ctx->q_depth + q0 : nullptr,   // (a batch's depth attributes lie frame after frame like its queries)
+               fs->m_depth, dimg, fs->counts, fs->n_slots, fs->best, s, rules, c.shard_stride, c.plane_stride, b1,
+               c.slot == 0 ? ctx->exchange_tags : nullptr, maps);
+  stamp(ctx, 2);
+  // CLUSTER (+ flat cluster table, snap[0..1])
+  const bool have_depth = ctx->q_depth || dimg.img;
+  if (!runs(1)) {
+  } else if (ctx->linkage_on && have_depth && dimg.img) {
+    // moped3d: linkage over similarity matrices; 3 n^2 floats of scratch per model, n <= LK_CAP
+    // (a merged batch: every frame its own region)
+    const size_t need = 3 * (size_t)std::min(fs->max_m, LK_CAP) * (size_t)fs->max_m;
+    int rc = ensure_linkage_scratch(ctx, need * (size_t)std::max(1, batch_n));
+    if (rc) return rc;
+    launch_linkage_models(fs->m_corr, reinterpret_cast<const float*>(fs->m_depth), fs->model_off, nm, dimg,
+                          ctx->linkage, ctx->lk_scratch, batch_n > 1 ? need : ctx->lk_scratch_floats, fs->ms_members,
+                          fs->ms_cl_start, fs->ms_ncl, fs->max_clusters, fs->cl_model, fs->cl_begin, fs->cl_count,
+                          fs->n_clusters, snap, fs->counts, fs->tickets + 0, s, ms_grid, b1, maps,
+                          fs->fb + 2 * MH_MAX_BATCH);
+  } else if (multi) {
+    // MeanShift per (model, image) in image order (CLUSTER_MEAN_SHIFT_CPU.hpp:189-195)
+    launch_image_split(fs->m_corr, fs->m_q, fs->m_model, fs->model_off, nm, ctx->q_img + (size_t)c.frame * Q, ctx->n_images, fs->counts,
+                       fs->m_img, fs->m_rep, fs->mi_corr, fs->mi_img, fs->off2, s);
+    launch_meanshift_models(fs->mi_corr, fs->off2, nm * ctx->n_images, prm->ms_radius, prm->ms_merge,
+                            prm->ms_min_pts, prm->ms_max_iter, fs->ms_members, fs->ms_cl_start,
+                            fs->ms_ncl, fs->max_clusters, fs->cl_model, fs->cl_begin, fs->cl_count,
+                            fs->n_clusters, snap, fs->counts, fs->tickets + 0, s, ctx->n_images, ms_grid);
+  } else
+  launch_meanshift_models(fs->m_corr, fs->model_off, nm, prm->ms_radius, prm->ms_merge,
+                          prm->ms_min_pts, prm->ms_max_iter, fs->ms_members, fs->ms_cl_start,
+                          fs->ms_ncl, fs->max_clusters, fs->cl_model, fs->cl_begin, fs->cl_count,
+                          fs->n_clusters, snap, fs->counts, fs->tickets + 0, s, 1, ms_grid, b1, fs->fb + 2 * MH_MAX_BATCH);
+  stamp(ctx, 3);
+  PoseImages img1, img2;   // POSE works on the (model, image, query) copy, POSE2 on FILTER's clusters over the match lists
+  if (multi) {
+    img1.cams = img2.cams = ctx->cams_dev;
+    img1.n_images = img2.n_images = ctx->n_images;
+    img1.img_of = fs->mi_img;
+    img2.img_of = fs->m_img;
+  }
+  // POSE (+ slot count, snap[2] = objects after POSE).  With the FILTER stages on, each FILTER runs in the tail of
+  // the POSE launch before it (its last workgroup: filter_dev.h) -- four launches per frame instead of six; a
+  // dependent launch costs the pipeline ~5% of its throughput whatever is in it (MH_FUSE_FILTER=0: launches of
+  // their own, the same objects).
+  static const bool fuse_filter = exp_int("MH_FUSE_FILTER", 1) != 0;
+  const float* depth4 = (ctx->q_depth || dimg.img) ? reinterpret_cast<const float*>(fs->m_depth) : nullptr;
+  FilterBuffers fb = make_fb(fs, nm);
+  if (multi) {
+    fb.m_img = fs->m_img;
+    fb.cams = ctx->cams_dev;
+    fb.n_images = ctx->n_images;
+  }
+  const bool fused = fuse_filter && prm->run_stage2 && !ctx->timing && !stepped;   // (stage timing wants the steps apart)
+  // (one frame alone in result slot 0: FILTER2's tail also writes the host's block, mh_frame_fetch reads it without a copy)
+  fs->host_armed = batch_n == 1 && c.slot == 0 && prm->run_stage2 && fs->host_block && !stepped;
+  if (fs->host_armed) ++fs->host_seq_expect;
+  const FilterTail ft1{fs->tickets + 2, snap + 3, nullptr, grid, nullptr, nullptr, nullptr},
+      ft2{fs->tickets + 4, nullptr, result, grid, fs->host_armed ? fs->host_block : nullptr, fs->host_armed ? snap : nullptr,
+          fs->host_armed ? fs->tickets + 7 : nullptr};
+  FilterFuse ff1, ff2;
+  ff1.fb = ff2.fb = &fb;
+  ff1.tail = &ft1;
+  ff2.tail = &ft2;
+  ff1.n_clusters_dev = fs->n_clusters2;   // FILTER writes POSE2's cluster count, FILTER2 the frame's final one
+  ff2.n_clusters_dev = fs->n_clusters;
+  ff1.dev = fs->fuse_dev;
+  ff1.shadow = &fs->fuse_shadow[0];
+  ff1.shadow_valid = &fs->fuse_valid[0];
+  ff2.dev = fs->fuse_dev + 1;
+  ff2.shadow = &fs->fuse_shadow[1];
+  ff2.shadow_valid = &fs->fuse_valid[1];
+  ff1.min_points = prm->f1_min_points;
+  ff1.feature_distance = prm->f1_feature_distance;
+  ff1.min_score = prm->f1_min_score;
+  ff2.min_points = prm->f2_min_points;
+  ff2.feature_distance = prm->f2_feature_distance;
+  ff2.min_score = prm->f2_min_score;
+  PoseSplit split;
+  split.hyp = (fused && ctx->pose_split) ? fs->hyp : nullptr;   // (the refine launch closes the frames through the fused FILTER tail)
+  split.pts = fs->rf_pts;
+  split.list = fs->rf_list;
+  split.max_m = fs->max_m;
+  if (runs(2))
+  launch_pose(multi ? fs->mi_corr : fs->m_corr, depth4, ctx->depth_kind, ctx->depth_alpha, fs->ms_members, fs->cl_model,
+              fs->cl_begin, fs->cl_count, fs->n_clusters, fs->max_clusters, dc, prm->pose1, c.seed, fs->n_slots,
+              fs->max_objects, fs->obj_model, fs->obj_pose, fs->obj_ninl, fs->obj_err, fs->obj_cluster,
+              fs->obj_valid, fs->counts, PoseTail{fs->tickets + 1, fs->n_slots, snap + 2, grid, fs->fb}, s, img1,
+              fused ? &ff1 : nullptr, b1, &split);
+  stamp(ctx, 4);
+  if (prm->run_stage2) {
+    // FILTER (snap[3] = objects kept)
+    if (!fused && runs(3))
+      launch_filter(fb, dc, prm->f1_min_points, prm->f1_feature_distance, prm->f1_min_score,
+                    fs->n_slots, fs->n_clusters2, fs->counts, ft1, s);
+    stamp(ctx, 5);
+    // POSE2 on the rewritten clusters, objects appended after the kept ones
+    if (runs(4))
+    launch_pose(fs->m_corr, depth4, ctx->depth_kind, ctx->depth_alpha, fs->new_members, fs->cl_model,
+                fs->cl_begin, fs->cl_count, fs->n_clusters2, fs->max_clusters, dc, prm->pose2,
+                c.seed ^ 0x5DEECE66Dull, fs->n_slots, fs->max_objects, fs->obj_model, fs->obj_pose,
+                fs->obj_ninl, fs->obj_err, fs->obj_cluster, fs->obj_valid, fs->counts,
+                PoseTail{fs->tickets + 3, fs->n_slots, nullptr, grid2, fs->fb + MH_MAX_BATCH}, s, img2, fused ? &ff2 : nullptr, b2,
+                &split);
+    stamp(ctx, 6);
+    // FILTER2 (+ the frame's result block)
+    if (!fused && runs(5))
+      launch_filter(fb, dc, prm->f2_min_points, prm->f2_feature_distance, prm->f2_min_score,
+                    fs->n_slots, fs->n_clusters, fs->counts, ft2, s);
+    stamp(ctx, 7);
+  } else {
+    for (int i = 5; i <= 7; ++i) stamp(ctx, i);
+    hipLaunchKernelGGL(pack_result_kernel, dim3(1), dim3(1), 0, s, result, fs->n_slots,
+                       fs->obj_valid, fs->obj_model, fs->obj_pose, fs->obj_score, fs->obj_npts,
+                       fs->max_objects, fs->counts);
+  }
+  stamp(ctx, 8);
+  MH_HIP(ctx, hipGetLastError());
+  return MH_OK;
+}
+
+// The frames of a batch can share their launches when nothing of the frame is per-context state: no depth
+// attributes / map / rules (one map per context), one image, the fused FILTER tails (the stand-alone FILTER and
+// result-packing kernels are per frame), no stage timing, no graph replay.  MH_MERGE_BATCH=0: frame after frame.
+// Per-query depth ATTRIBUTES (mh_frame_set_depth: B Q entries, frame after frame like the queries) travel with a merged
+// batch where the caller says so (`attrs_ok`: mh_frame_enqueue_batch) -- group_kernel takes frame f's slice, the per-frame
+// arenas hold every frame's m_depth, pose_kernel<1 | 2> shifts its pointers like pose_kernel<0>.
+// A depth MAP per frame (mh_frame_set_depth_image_batch with as many maps as the batch has frames: `maps_for`), the depth
+// rules and the linkage clusterer travel with it too (round 4): depth_patch / feature_density / group / linkage_models
+// take frame f's map from a DepthMaps table and its rule buffers behind those of the frames before it.
+bool merged_batch_ok(const mh_ctx* ctx, const mh_frame_params* prm, bool attrs_ok, int maps_for) {
+  static const bool on = exp_int("MH_MERGE_BATCH", 1) != 0;
+  static const bool fuse_filter = exp_int("MH_FUSE_FILTER", 1) != 0;
+  static const bool merge_maps = exp_int("MH_MERGE_MAPS", 1) != 0;
+  const bool maps_ok = merge_maps && attrs_ok && maps_for > 1 && ctx->batch_imgs == maps_for && ctx->depth_img.img;
+  return on && fuse_filter && prm->run_stage2 && !ctx->timing && (attrs_ok || !ctx->q_depth) &&
+         (maps_ok || (!ctx->depth_img.img && !ctx->rules.on && !ctx->linkage_on)) && !(ctx->q_img && ctx->n_images > 1);
+}
+
+int ensure_batch_arenas(mh_ctx* ctx, int B) {
+  FrameState* fs = ctx->fs;
+  if (fs->n_arenas >= B) return MH_OK;   // (the usual case; the first batch pays one reallocation)
+  return ensure_fs(ctx, fs->max_m, fs->max_clusters, fs->max_objects, fs->n_models_cap, B);
+}
+
+// Buffers for a launch of Q queries = `frames` frames of q_frame queries each (0: one frame of Q): the MATCH side for
+// all of them, the working arrays of the rest chain per frame (a frame has at most as many matches as queries) with
+// `frames` copies, so that a merged batch never reallocates behind work that is already enqueued.
+int prepare_frame(mh_ctx* ctx, int Q, int q_frame, int frames) {
+  int rc = ensure_frame_buffers(ctx, Q);
+  if (rc) return rc;
+  if ((rc = ensure_match_scratch(ctx, Q))) return rc;
+  const int want_m = ctx->fs ? ctx->fs->max_m : 0;
+  const int mc = ctx->fs ? ctx->fs->max_clusters : 1024;
+  const int mo = ctx->fs ? ctx->fs->max_objects : 4096;
+  // (several images: CLUSTER's per-"model" tables hold one entry per (model, image) pair)
+  return ensure_fs(ctx, std::max(want_m, q_frame > 0 ? q_frame : Q), mc, mo,
+                   ctx->n_models * (ctx->n_images > 1 ? ctx->n_images : 1), frames);
+}
+}  // namespace mh
+
+extern "C" void mh_free_frame_state(mh_ctx* ctx) {
+  mh::free_fs(ctx->fs);
+  ctx->fs = nullptr;
+}
