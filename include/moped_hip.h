@@ -696,6 +696,15 @@ int mh_frame_fetch_matches_slot(mh_ctx* ctx, int slot, int32_t* query_host, int3
  * (FILTER_PROJECTION_CPU.hpp:89).  Read only; the same slots and errors as mh_frame_fetch_matches_slot, and slot -1 =
  * the last frame (the lists mh_frame_fetch_matches gives). */
 int mh_frame_fetch_match_reps_slot(mh_ctx* ctx, int slot, int32_t* rep_host, int cap, int32_t* n_matches);
+/* For tests, in the style of mh_db_debug_fetch: what the moped3d front end (mh_frame_set_depth_rules + a depth map)
+ * left behind for frame `slot` of the last frame / batch, by host-side copies after the stream has drained.
+ *   which 0: inv_size, double [pw ph] -- per patch 1.0 / sizeMap (DEPTHFILTER_CPU.hpp:168-178,193)
+ *   which 1: keep1, uint8 [Q]         -- DEPTHFILTER's verdict on every feature (feature_density >= 0)
+ *   which 2: m_depth, mh_depth [M]    -- DEPTHMAP_PROP's world point and Cauchy weight of every accepted match, in the
+ *                                        order of mh_frame_fetch_matches_slot (any frame with depth attributes)
+ * bytes must be exactly the array's size; a wrong size, a slot whose maps are gone or an array the last frame did not
+ * write -> MH_ERR_ARG, nothing is read. */
+int mh_depth_rules_debug_fetch(mh_ctx* ctx, int which, int slot, void* out_host, size_t bytes);
 /* Device address of the frame's packed result block {int32 n; mh_object[cap]}
  * for exchange 2 (gather of per-rank objects); *bytes = its size. */
 int mh_frame_result_dev(mh_ctx* ctx, void** block_dev, int64_t* bytes);

@@ -111,7 +111,7 @@ EXPORTS = [
     "mh_models_add_xml_buffer", "mh_models_count", "mh_models_rows", "mh_models_name", "mh_models_range",
     "mh_models_desc", "mh_models_xyz", "mh_models_save", "mh_models_load", "mh_db_upload_models",
     "mh_db_splice", "mh_db_reserve", "mh_db_adopt", "mh_db_generation", "mh_db_model_rows", "mh_db_splice_models",
-    "mh_db_debug_fetch", "mh_db_debug_screen", "mh_db_debug_route", "mh_db_edit_ms",
+    "mh_db_debug_fetch", "mh_depth_rules_debug_fetch", "mh_db_debug_screen", "mh_db_debug_route", "mh_db_edit_ms",
     "mh_db_upload_raw", "mh_db_share", "mh_match_stats", "mh_match_set_mode", "mh_match_launches", "mh_pose_set_split", "mh_frame_fetch_match_points", "mh_screen_margin", "mh_frame_counters", "mh_match_timing", "mh_frame_set_images", "mh_filter_images",
     "mh_pose_ransac_images",
     "mh_comm_unique_id", "mh_comm_create", "mh_comm_create_all", "mh_comm_create_host", "mh_comm_destroy", "mh_comm_info",
@@ -257,6 +257,7 @@ def load():
     L.mh_db_model_rows.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.mh_db_splice_models.argtypes = [vp, i32, i32, vp, i32]
     L.mh_db_debug_fetch.argtypes = [vp, i32, vp, C.c_size_t]
+    L.mh_depth_rules_debug_fetch.argtypes = [vp, i32, i32, vp, C.c_size_t]
     L.mh_db_debug_screen.argtypes = [vp, vp]
     L.mh_db_debug_route.argtypes = [vp, i32]
     L.mh_db_edit_ms.argtypes = [vp, C.POINTER(f32)]
@@ -1306,6 +1307,18 @@ class Context:
             r.n_models = tab.shape[0]
         k = np.ascontiguousarray(K if K is not None else [0, 0, 0, 0], np.float32)
         self._ck(self.L.mh_frame_set_depth_rules(self.h, C.byref(r), _ptr(k)), "mh_frame_set_depth_rules")
+
+    def depth_rules_debug_fetch(self, which: str, slot=0, n=None) -> np.ndarray:
+        """What the depth front end left for frame `slot` (mh_depth_rules_debug_fetch): 'inv_size' float64 [n = pw ph],
+        'keep1' uint8 [n = Q], 'm_depth' DEPTH_DTYPE [n = the frame's match count, default: asked from the lists]."""
+        k, dt = {"inv_size": (0, np.float64), "keep1": (1, np.uint8), "m_depth": (2, DEPTH_DTYPE)}[which]
+        if n is None:
+            assert which == "m_depth", "inv_size and keep1 need their length"
+            n = len(self.frame_fetch_matches_slot(slot)[0])
+        out = np.zeros(int(n), dt)
+        self._ck(self.L.mh_depth_rules_debug_fetch(self.h, k, int(slot), _ptr(out) if n else None, out.nbytes),
+                 "mh_depth_rules_debug_fetch")
+        return out
 
     def frame_fetch_matches(self, cap=1 << 16):
         q = np.zeros(cap, np.int32)

@@ -1024,6 +1024,38 @@ int mh_frame_fetch_match_points(mh_ctx* ctx, mh_corr* corr_host, int cap, int32_
   return MH_OK;
 }
 
+int mh_depth_rules_debug_fetch(mh_ctx* ctx, int which, int slot, void* out_host, size_t bytes) {
+  static const char* const who = "mh_depth_rules_debug_fetch";
+  if (!ctx || which < 0 || which > 2 || slot < 0 || slot >= MH_MAX_BATCH || (bytes > 0 && !out_host)) return MH_ERR_ARG;
+  auto refuse = [&](const char* why) {
+    ctx->err = std::string(who) + ": " + why;
+    return MH_ERR_ARG;
+  };
+  const mh_ctx::DepthRuleState& rs = ctx->rules;
+  if (which == 2) {
+    if (!ctx->fs || !rs.last.depth) return refuse("the last frame carried no depth attributes");
+    size_t a = 0;
+    int take = 0;
+    int32_t n = 0;
+    if (int rc = match_lists(ctx, who, slot, INT_MAX, &n, &a, &take)) return rc;
+    if (bytes != sizeof(mh_depth) * (size_t)n) return refuse("bytes is not the frame's match count times sizeof(mh_depth)");
+    if (n > 0)
+      MH_HIP(ctx, hipMemcpy(out_host, reinterpret_cast<const unsigned char*>(ctx->fs->m_depth) + a, bytes, hipMemcpyDeviceToHost));
+    return MH_OK;
+  }
+  const int f = slot - rs.last.first;
+  if (f < 0 || f >= rs.last.frames) return refuse("no depth rules ran on that frame (or its maps have been overwritten)");
+  if (which == 0 ? !rs.last.inv : !rs.last.keep) return refuse("the last frame's rules did not write that array");
+  const size_t extent = which == 0 ? sizeof(double) * (size_t)rs.last.patches : (size_t)rs.last.q;
+  if (bytes != extent) return refuse("bytes is not the array's size (0: 8 pw ph, 1: Q)");
+  if (int rc_enter = mh::enter(ctx)) return rc_enter;
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const void* src = which == 0 ? static_cast<const void*>(rs.inv_size + (size_t)f * rs.last.patches)
+                               : static_cast<const void*>(rs.keep1 + (size_t)f * rs.last.q);
+  if (bytes > 0) MH_HIP(ctx, hipMemcpy(out_host, src, bytes, hipMemcpyDeviceToHost));
+  return MH_OK;
+}
+
 int mh_frame_fetch_matches(mh_ctx* ctx, int32_t* query_host, int32_t* model_host, int cap, int32_t* n_matches) {
   if (!ctx || !ctx->fs) return MH_ERR_ARG;
   return mh_frame_fetch_matches_slot(ctx, ctx->fs->list_first + ctx->fs->list_n - 1, query_host, model_host, cap, n_matches);

@@ -260,6 +260,12 @@ struct mh_ctx {
     size_t cnt_cap = 0;
     uint8_t* keep1 = nullptr;       // device [max_q]
     int keep_cap = 0;
+    // what the last frame's front end left in these buffers (mh_depth_rules_debug_fetch): patches and queries per
+    // frame, the result slots [first, first + frames) whose maps lie frame after frame, which arrays were written
+    struct Last {
+      int patches = 0, q = 0, first = 0, frames = 0;
+      bool inv = false, keep = false, depth = false;
+    } last;
   } rules;
 
   // moped3d CLUSTER_LINKAGE instead of mean shift (mh_frame_set_cluster_linkage)

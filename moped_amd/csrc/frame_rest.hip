@@ -357,12 +357,22 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
   }
   // moped3d depth rules: patch maps of this frame's depth image, DEPTHFILTER on the features
   DepthRules rules;
+  if (runs(0)) {
+    ctx->rules.last = mh_ctx::DepthRuleState::Last();
+    ctx->rules.last.depth = ctx->q_depth || dimg.img;   // group_kernel fills m_depth
+  }
   if (ctx->rules.on && dimg.img && runs(0)) {
     mh_ctx::DepthRuleState& rs = ctx->rules;
     const int pw = (dimg.w + rs.patch - 1) / rs.patch, ph = (dimg.h + rs.patch - 1) / rs.patch;
     int rc = ensure_rule_buffers(ctx, pw * ph, Q, batch_n);
     if (rc) return rc;
     const bool filters = rs.feature_filter >= 0.f || rs.match_filter >= 0.f;
+    rs.last.patches = pw * ph;
+    rs.last.q = Q;
+    rs.last.first = c.slot;
+    rs.last.frames = std::max(1, batch_n);
+    rs.last.inv = filters;
+    rs.last.keep = rs.feature_filter >= 0.f;
     if (filters) launch_depth_patches(dimg, rs.K, rs.patch, rs.inv_size, s, maps, batch_n);
     if (rs.feature_filter >= 0.f) {
       launch_feature_density(q_uv_dev, Q, ctx->feat_count_dev, rs.patch, pw, ph, rs.inv_size, rs.feature_filter,

@@ -9,9 +9,16 @@
 #   /root/reference/moped2/libmoped/libs/libs.tgz             (vendored ANN 1.1.1,
 #        levmar 2.4, libsiftfast 1.1 -- unpacked into a temp dir outside the repo,
 #        compiled with gcc/g++ directly, temp dir removed afterwards)
-# plus our own wrapper oracle/ref_harness.cpp.  The reference's build system is
+# plus our own wrapper oracle/ref_harness.cpp, and
+# oracle/_ref/libmoped_ref_steps2.so / libmoped_ref_steps3d.so: four of the
+# reference's STEP classes (mean shift, FILTER_PROJECTION; DEPTHFILTER,
+# DEPTHMAP_PROP, moped3d's mean shift) behind oracle/ref_steps_harness.cpp, which
+# stands in for src/util.hpp and includes the step headers where they lie:
+#   /root/reference/moped2/libmoped/{include,src}     (-DREF_STEPS_MOPED2)
+#   /root/reference/moped3d/libmoped/{include,src}    (-DREF_STEPS_MOPED3D)
+# with the golden flags of libmoped_ref.so.  The reference's build system is
 # not run, nothing from the reference is copied into the repo, and the only
-# outputs are the two .so files under oracle/_ref/ (git-ignored).
+# outputs are the .so files under oracle/_ref/ (git-ignored).
 #
 # No-op (exit 0) when /root/reference is absent (GPU box): the prebuilt files
 # travel with the snapshot.
@@ -25,6 +32,26 @@ if [ ! -f "$LIBMOPED/libs/libs.tgz" ]; then
   exit 0
 fi
 mkdir -p "$OUT"
+
+# the STEP classes: one translation unit per tree (both define the same names in MopedNS)
+build_steps() {  # $1 = output name, $2 = tree, $3 = -D
+  local tree="$REF/$2/libmoped"
+  if [ ! -d "$tree/src" ]; then
+    echo "build_ref: $tree not present; keeping prebuilt $1 as is"
+    return 0
+  fi
+  if [ "$OUT/$1" -nt "$HERE/ref_steps_harness.cpp" ] && [ "$OUT/$1" -nt "$HERE/build_ref.sh" ]; then
+    echo "build_ref: $1 up to date"
+    return 0
+  fi
+  g++ -O2 -w -fPIC -std=gnu++98 -fno-delete-null-pointer-checks -fopenmp "$3" \
+      -I"$tree/include" -I"$tree/src" -shared "$HERE/ref_steps_harness.cpp" -o "$OUT/$1.tmp" -lm
+  mv "$OUT/$1.tmp" "$OUT/$1"
+  echo "build_ref: wrote $OUT/$1"
+}
+build_steps libmoped_ref_steps2.so moped2 -DREF_STEPS_MOPED2
+build_steps libmoped_ref_steps3d.so moped3d -DREF_STEPS_MOPED3D
+
 if [ "$OUT/libmoped_ref.so" -nt "$HERE/ref_harness.cpp" ] && \
    [ "$OUT/libmoped_ref_fast.so" -nt "$HERE/ref_harness.cpp" ] && \
    [ "$OUT/libmoped_ref.so" -nt "$HERE/build_ref.sh" ]; then

@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE ONLY -- CPU restatement of moped3d's DEPTHFILL step, the checker of mh_depth_fill.
 // Follows moped3d/libmoped/src/depthfill/DEPTH_FILL_EXACT_CPU.hpp (config.hpp:39:
 // `new DEPTH_FILL_EXACT_CPU(8, false)`); Float = float (include/moped.hpp:73-77).  Parity unpinned: the step's header
-// needs OpenCV through util.hpp and the reference holds no fixture for it; written from the source text,
+// itself works on IplImage (OpenCV) and the reference holds no fixture for it; written from the source text,
 // quirks kept:
 //   - the nearest-neighbour upsampling advances its source row one output row late (:80-82: `ly` is bumped at the
 //     END of the row whose index is a multiple of the factor), the bilinear one does not (:106-110);

@@ -18,8 +18,9 @@
 // float overloads.  Coordinates outside the depth / distance maps are clamped to them (the
 // reference clamps for the depth map only, :222-229).
 //
-// PARITY UNPINNED: moped3d's step headers need OpenCV -> no reference build; restated from the
-// source text, hand-worked cases in tests/test_linkage_cpu.py.
+// PARITY UNPINNED: CLUSTER_LINKAGE_CPU.hpp itself uses IplImage (unlike the step headers that
+// oracle/ref_steps_harness.cpp builds) -> no reference build; restated from the source text,
+// hand-worked cases in tests/test_linkage_cpu.py.
 #include <cfloat>
 #include <cmath>
 #include <cstdint>

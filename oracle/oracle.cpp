@@ -557,7 +557,8 @@ void orc_match_merge(const int32_t* idx1_s, const float* d1_s, const float* d2_s
 }
 
 // ---------------------------------------------------------------------------
-// mean shift (CLUSTER_MEAN_SHIFT_CPU.hpp:80-158) -- PARITY UNPINNED
+// mean shift (CLUSTER_MEAN_SHIFT_CPU.hpp:80-158) -- pinned against the class's own process()
+// (oracle/ref_steps_harness.cpp, tests/test_ref_steps_cpu.py)
 // ---------------------------------------------------------------------------
 int orc_meanshift(const float* pts, int n, int dim, float radius, float merge, int min_pts,
                   int max_iter, int32_t* members, int32_t* cluster_off, int* n_iter) {

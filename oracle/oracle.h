@@ -12,12 +12,13 @@
  *              (oracle/_ref, tests/golden/match_*.npz)
  *   project /  pinned against the reference's project()/TransformMatrix and
  *   LM refine  levmar slevmar_dif (oracle/_ref, tests/golden/pose_*.npz)
- *   mean shift PARITY UNPINNED: the algorithm lives wholly inside
- *              CLUSTER_MEAN_SHIFT_CPU.hpp, which cannot be compiled here
- *              (needs util.hpp -> OpenCV headers) and the reference holds no
- *              fixture for it; restated from the source text only.
- *   RANSAC skeleton / FILTER: restated from the source text; the numerical
- *              kernels they call are the pinned ones above.
+ *   mean shift / FILTER: restated from the source text and pinned against
+ *              the reference's own CLUSTER_MEAN_SHIFT_CPU / FILTER_PROJECTION_CPU
+ *              (their headers compile against stand-ins for util.hpp:
+ *              oracle/ref_steps_harness.cpp, tests/test_ref_steps_cpu.py)
+ *   RANSAC skeleton: PARITY UNPINNED -- it lives inside the POSE classes around
+ *              levmar; restated from the source text, the numerical kernels it
+ *              calls are the pinned ones above.
  */
 #pragma once
 #include <stdint.h>

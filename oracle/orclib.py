@@ -217,17 +217,25 @@ def cauchy_weight(fill_distance, scale=0.1):
     return (1.0 / (np.float32(1) + f * f).astype(np.float64)).astype(np.float32)
 
 
-def depthmap_prop(depth_img, fill_img, uv, scale=0.1):
+def depthmap_lookup(depth_img, fill_img, uv):
     """DEPTHMAP_PROP_CPU::process (moped3d/libmoped/src/depthprop/DEPTHMAP_PROP_CPU.hpp:101-134):
-    per keypoint the pixel (int)u, (int)v of the 4-float depth map -> world3D = its x,y,z;
-    fillDistance from the distance map or -1; -> (world [n,3], cauchy weight [n]).  Pixels
+    per keypoint the pixel (int)u, (int)v of the 4-float depth map -> depthData.coord3D = its x,y,z;
+    fillDistance from the distance map or -1; -> (world [n,3], fillDistance [n]).  Pixels
     outside the map are clamped (the reference indexes out of bounds there)."""
     h, w = depth_img.shape[:2]
     ix = np.clip(uv[:, 0].astype(np.int32), 0, w - 1)
     iy = np.clip(uv[:, 1].astype(np.int32), 0, h - 1)
     world = depth_img[iy, ix, :3].astype(np.float32)
     fd = fill_img[iy, ix].astype(np.float32) if fill_img is not None else np.full(len(uv), -1, np.float32)
-    return world, cauchy_weight(fd, scale)
+    return world, fd
+
+
+def depthmap_prop(depth_img, fill_img, uv, scale=0.1):
+    """depthmap_lookup with the fill distance turned into the Cauchy weight POSE gives it (a restatement of
+    getCauchyWeight, which lives in the POSE header): -> (world [n,3], cauchy weight [n])."""
+    world, fd = depthmap_lookup(depth_img, fill_img, uv)
+    with np.errstate(all="ignore"):
+        return world, cauchy_weight(fd, scale)
 
 
 def residuals_depth(mode, pose7, uv, xyz, world, wgt, K, cam, alpha):
@@ -772,7 +780,8 @@ def ref_sift(gray, cap=16384):
 
 # ---- moped3d depth rules: DEPTHFILTER_CPU and MATCH_ADAPTIVE_FLANN_CPU's ratio ----
 # Restated from the source text in numpy with the reference's float / double mix (Float = float,
-# unsuffixed literals = double).  moped3d's step classes need OpenCV headers -> no reference build.
+# unsuffixed literals = double).  DEPTHFILTER_CPU is pinned to the class itself (ref_depthfilter_keep below,
+# tests/test_ref_steps_cpu.py); MATCH_ADAPTIVE_FLANN_CPU needs cv::flann -> no reference build of the ratio rules.
 
 _f = np.float32
 
@@ -826,15 +835,15 @@ def _density_replay(n, inv):
     return c
 
 
-def depthfilter_keep(depth_img, K, patch, density, uv, group_off=None):
-    """DEPTHFILTER_CPU::process (:181-249): keep[i] for points uv, filtered per group (ToFilter = 1:
-    one group = all features; ToFilter = 2: one group per model's matches)."""
-    inv, pw, ph = depth_patch_inv_size(depth_img, K, patch)
-    filt = _f(_f(_f(density) * _f(100)) * _f(100))            # Float filter = Density*100*100 (:132)
+def depthfilter_density(depth_img, K, patch, uv, group_off=None, patch_map=None):
+    """DEPTHFILTER_CPU::process (:181-249) up to its comparison: the dilated density (Float) of every point's patch,
+    counted per group (ToFilter = 1: one group = all features; ToFilter = 2: one group per model's matches).
+    patch_map: depth_patch_inv_size's result, where the caller has it already."""
+    inv, pw, ph = patch_map if patch_map is not None else depth_patch_inv_size(depth_img, K, patch)
     n = len(uv)
     if group_off is None:
         group_off = [0, n]
-    keep = np.zeros(n, bool)
+    dens = np.zeros(n, _f)
     with np.errstate(all="ignore"):
         for g in range(len(group_off) - 1):
             a, b = int(group_off[g]), int(group_off[g + 1])
@@ -851,8 +860,20 @@ def depthfilter_keep(depth_img, K, patch, density, uv, group_off=None):
                     src = val[ys, xs]
                     upd = src > dil[yd, xd]
                     dil[yd, xd] = np.where(upd, src, dil[yd, xd])
-            keep[a:b] = dil.ravel()[p] > filt
-    return keep
+            dens[a:b] = dil.ravel()[p]
+    return dens
+
+
+def density_filter(density):
+    """`Float filter = Density*100*100` (DEPTHFILTER_CPU.hpp:130)."""
+    return _f(_f(_f(density) * _f(100)) * _f(100))
+
+
+def depthfilter_keep(depth_img, K, patch, density, uv, group_off=None, patch_map=None):
+    """DEPTHFILTER_CPU::process (:181-249): keep[i] for points uv, filtered per group (ToFilter = 1:
+    one group = all features; ToFilter = 2: one group per model's matches)."""
+    with np.errstate(all="ignore"):
+        return depthfilter_density(depth_img, K, patch, uv, group_off, patch_map) > density_filter(density)
 
 
 def _ratio_at(depth, cp, max_depth):
@@ -988,3 +1009,117 @@ def depth_fill(depth_img, K, scale=8, bilinear=False):
     if used < 0:
         raise ValueError("orc_depth_fill: bad arguments")
     return out, dist, used
+
+
+# ---- the reference's own STEP classes (oracle/ref_steps_harness.cpp; only where oracle/_ref was built) ----
+# libmoped_ref_steps2.so: moped2's CLUSTER_MEAN_SHIFT_CPU and FILTER_PROJECTION_CPU; libmoped_ref_steps3d.so: moped3d's
+# DEPTHFILTER_CPU, DEPTHMAP_PROP_CPU and CLUSTER_MEAN_SHIFT_CPU.  Every wrapper drives the class's own process().
+
+_ref_steps = {}
+
+
+def _ref_steps_path(tree):
+    return os.path.join(HERE, "_ref", "libmoped_ref_steps2.so" if tree == 2 else "libmoped_ref_steps3d.so")
+
+
+def ref_steps_available():
+    return os.path.exists(_ref_steps_path(2)) and os.path.exists(_ref_steps_path(3))
+
+
+def ref_steps(tree):
+    """tree = 2 (moped2) or 3 (moped3d)."""
+    if tree not in _ref_steps:
+        R = C.CDLL(_ref_steps_path(tree))
+        R.ref_steps_tree.restype = C.c_int
+        assert R.ref_steps_tree() == tree
+        R.ref_meanshift_step.restype = C.c_int
+        R.ref_meanshift_step.argtypes = [_f32p, C.c_int, _i32p, _i32p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
+                                         C.c_int, _i32p, _i32p, _i32p]
+        if tree == 2:
+            R.ref_filter_step.restype = C.c_int
+            R.ref_filter_step.argtypes = [_f32p, _i32p, _f32p, _i32p, C.c_int, _i32p, _f32p, C.c_int, _f32p, _f32p,
+                                          C.c_int, C.c_int, C.c_float, C.c_float, _f32p, _u8p, _i32p, _i32p, _i32p]
+        else:
+            R.ref_depthfilter.restype = C.c_int
+            R.ref_depthfilter.argtypes = [_f32p, C.c_int, C.c_int, _f32p, C.c_int, C.c_float, C.c_int, _f32p, _i32p,
+                                          C.c_int, C.c_int, _u8p]
+            R.ref_depthmap_prop.restype = C.c_int
+            R.ref_depthmap_prop.argtypes = [_f32p, C.c_void_p, C.c_int, C.c_int, _f32p, C.c_int, _f32p, _f32p, _f32p,
+                                            _u8p]
+        _ref_steps[tree] = R
+    return _ref_steps[tree]
+
+
+def ref_depthfilter_keep(depth_img, K, patch, density, uv, group_off=None):
+    """DEPTHFILTER_CPU::process itself: keep[i] as depthfilter_keep gives it (group_off None: ToFilter = 1, the points
+    are the frame's features; else ToFilter = 2, one group per model).  Coordinates must lie inside the map."""
+    img = _c(depth_img, np.float32)
+    h, w = img.shape[:2]
+    uv = _c(uv, np.float32).reshape(-1, 2)
+    n = len(uv)
+    assert n == 0 or (uv.min() >= 0 and uv[:, 0].max() < w and uv[:, 1].max() < h), "the class reads out of bounds there"
+    keep = np.zeros(max(n, 1), np.uint8)
+    off = _c(group_off if group_off is not None else [0, n], np.int32)
+    rc = ref_steps(3).ref_depthfilter(img.reshape(-1), w, h, _c(K, np.float32), int(patch), float(density),
+                                      1 if group_off is None else 2, uv.reshape(-1), off, len(off) - 1, n, keep)
+    assert rc == 0
+    return keep[:n].astype(bool)
+
+
+def ref_depthmap_prop(depth_img, fill_img, uv):
+    """DEPTHMAP_PROP_CPU::process itself -> (coord3D [n,3], depth [n], fillDistance [n], depthValid [n]) of every match's
+    depthData.  fill_img None: no distance map among the images.  Coordinates must lie inside the map."""
+    img = _c(depth_img, np.float32)
+    h, w = img.shape[:2]
+    uv = _c(uv, np.float32).reshape(-1, 2)
+    n = len(uv)
+    assert n == 0 or (uv.min() >= 0 and uv[:, 0].max() < w and uv[:, 1].max() < h), "the class reads out of bounds there"
+    xyz = np.zeros((max(n, 1), 3), np.float32)
+    depth = np.zeros(max(n, 1), np.float32)
+    fd = np.zeros(max(n, 1), np.float32)
+    valid = np.zeros(max(n, 1), np.uint8)
+    fill = _c(fill_img, np.float32) if fill_img is not None else None
+    assert fill is None or fill.shape == (h, w)
+    rc = ref_steps(3).ref_depthmap_prop(img.reshape(-1), fill.ctypes.data if fill is not None else None, w, h,
+                                        uv.reshape(-1), n, xyz.reshape(-1), depth, fd, valid)
+    assert rc == 0
+    return xyz[:n], depth[:n], fd[:n], valid[:n].astype(bool)
+
+
+def ref_meanshift_step(pts, image_of=None, model_off=None, n_images=1, radius=200.0, merge=20.0, min_pts=7,
+                       max_iter=100, tree=2):
+    """CLUSTER_MEAN_SHIFT_CPU::process itself (tree 2: moped2's; 3: moped3d's, where pts of dim 3 run its use3D
+    branch).  Matches of model m = rows [model_off[m], model_off[m+1]) (default: one model), image_of their images
+    (default: image 0).  -> (clusters in the class's order as arrays of indices into the model's matches, their models)."""
+    pts = _c(pts, np.float32)
+    n, dim = (pts.shape[0], pts.shape[1]) if pts.ndim == 2 else (0, 2)
+    off = _c(model_off if model_off is not None else [0, n], np.int32)
+    img = _c(image_of if image_of is not None else np.zeros(n), np.int32)
+    members = np.zeros(max(n, 1), np.int32)
+    cl_off = np.zeros(n + 2, np.int32)
+    cl_model = np.zeros(n + 1, np.int32)
+    k = ref_steps(tree).ref_meanshift_step(pts.reshape(-1), dim, img, off, len(off) - 1, n_images, radius, merge,
+                                           min_pts, max_iter, members, cl_off, cl_model)
+    assert k >= 0, k
+    return [members[cl_off[i]:cl_off[i + 1]].copy() for i in range(k)], cl_model[:k].copy()
+
+
+def ref_filter_step(uv, xyz, model_off, obj_model, obj_pose, Ks, cams, min_points, feature_distance, min_score,
+                    image_of=None):
+    """FILTER_PROJECTION_CPU::process itself (moped2) -> (score, keep, order, clusters) as filter_projection /
+    filter_images give them.  Ks [n_images, 4], cams [n_images, 7]; image_of None: every match in image 0."""
+    Ks, cams, n_img = _cams(Ks, cams)
+    n_obj, M = len(obj_model), len(uv)
+    score = np.zeros(max(n_obj, 1), np.float32)
+    keep = np.zeros(max(n_obj, 1), np.uint8)
+    order = np.zeros(max(n_obj, 1), np.int32)
+    members = np.zeros(max(M, 1), np.int32)
+    off = np.zeros(n_obj + 2, np.int32)
+    img = _c(image_of if image_of is not None else np.zeros(M), np.int32)
+    k = ref_steps(2).ref_filter_step(_c(uv, np.float32).reshape(-1), img, _c(xyz, np.float32).reshape(-1),
+                                     _c(model_off, np.int32), len(model_off) - 1, _c(obj_model, np.int32),
+                                     _c(obj_pose, np.float32).reshape(-1), n_obj, Ks.reshape(-1), cams.reshape(-1), n_img,
+                                     int(min_points), float(feature_distance), float(min_score), score, keep, order,
+                                     members, off)
+    assert k >= 0, k
+    return score[:n_obj], keep[:n_obj].astype(bool), order[:k].copy(), [members[off[i]:off[i + 1]].copy() for i in range(k)]

@@ -22,11 +22,11 @@
 // /root/reference (the vendored tarball is unpacked into a temp dir outside
 // the repo) and the only output is oracle/_ref/libmoped_ref.so.
 //
-// NOT built from the reference: the STEP classes themselves
-// (MATCH_ANN_CPU / CLUSTER_MEAN_SHIFT_CPU / POSE_RANSAC_* / FILTER_*). They
-// need src/util.hpp, which includes OpenCV headers this image does not have
-// (util.hpp:51-52); no stand-in headers are written, so those classes are
-// treated as unbuildable here (see DESIGN.md "Oracle").  The small amount of
+// NOT built here: the STEP classes themselves.  They need src/util.hpp, which
+// includes OpenCV headers this image does not have (util.hpp:51-52).  Four of
+// them (mean shift, FILTER_PROJECTION, DEPTHFILTER, DEPTHMAP_PROP) are built
+// against stand-ins for util.hpp in oracle/ref_steps_harness.cpp; MATCH_ANN_CPU
+// and POSE_RANSAC_* are not (see DESIGN.md "Oracle").  The small amount of
 // glue this file adds around the libraries (the residual callback, the
 // search loop) is our own restatement and says so where it appears.
 //

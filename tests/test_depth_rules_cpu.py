@@ -1,7 +1,8 @@
 """Oracle restatement of moped3d's DEPTHFILTER_CPU and MATCH_ADAPTIVE_FLANN_CPU ratio rules
 (orclib.depthfilter_keep / adaptive_ratio / adaptive_control_points): hand-worked cases.
-PARITY UNPINNED against a reference build (moped3d's steps need OpenCV headers); the GPU path is
-compared index-exactly with these functions in tests/test_gpu_depth_rules.py."""
+depthfilter_keep is pinned to DEPTHFILTER_CPU::process itself in tests/test_ref_steps_cpu.py; the adaptive ratio stays
+PARITY UNPINNED (MATCH_ADAPTIVE_FLANN_CPU needs cv::flann).  The GPU path is compared index-exactly with these functions
+in tests/test_gpu_depth_rules.py and stage by stage in tests/test_gpu_depth_stages.py."""
 import numpy as np
 
 import orclib

@@ -1,5 +1,5 @@
 """Oracle restatement of moped3d's CLUSTER_LINKAGE_CPU (oracle/linkage_oracle.cpp): hand-worked
-cases.  PARITY UNPINNED against a reference build (moped3d's steps need OpenCV headers); the GPU
+cases.  PARITY UNPINNED against a reference build (CLUSTER_LINKAGE_CPU.hpp works on IplImage); the GPU
 kernel is compared with this oracle in tests/test_gpu_linkage.py."""
 import numpy as np
 

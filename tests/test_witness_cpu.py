@@ -1,5 +1,6 @@
 """Differential fuzz: oracle/oracle.cpp against the independent restatements of tests/witness/witness.py on the rows the
-reference cannot pin here (mean shift, the RANSAC skeleton, FILTER -- their headers need OpenCV).  Two
+reference could not pin when they were written (mean shift, the RANSAC skeleton, FILTER; mean shift and
+FILTER are now also held to the reference's own classes on these generators, tests/test_ref_steps_cpu.py).  Two
 restatements of the same text, one over std::list / std::map in C++, one over numpy arrays, must agree on every case:
 >= 10 000 cases each, drawn to hit what the text makes delicate -- chain merges, merges into canopies that have already
 left the list, ties at Radius / Merge, duplicate image coordinates, tied random keys, equal scores."""

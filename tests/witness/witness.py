@@ -1,4 +1,5 @@
-"""Second witnesses for the rows of SURVEY.md 8(a) that no reference build can pin (the STEP headers need OpenCV):
+"""Second witnesses for rows of SURVEY.md 8(a) that had no reference build when this was written (mean shift and FILTER
+have one since: tests/test_ref_steps_cpu.py; the RANSAC skeleton, inside the POSE classes, still has none):
 restatements of the reference's TEXT written independently of oracle/oracle.cpp and by another route -- numpy arrays
 and index arithmetic where the oracle (like the reference) walks std::list / std::map -- so that a misreading would have
 to be made twice, in two different shapes, to go unnoticed.  tests/test_witness_cpu.py runs the oracle against these on
