@@ -22,32 +22,19 @@ int use_stream(mh_ctx* ctx) {
 }
 
 int ensure_scratch(mh_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->scratch_cap) return MH_OK;
-  if (ctx->scratch) MH_HIP(ctx, hipFree(ctx->scratch));
-  ctx->scratch = nullptr;
-  ctx->scratch_cap = 0;
-  size_t cap = bytes + bytes / 4 + 4096;
-  MH_HIP(ctx, hipMalloc(&ctx->scratch, cap));
-  ctx->scratch_cap = cap;
+  if (bytes > ctx->scratch.cap) MH_HIP(ctx, ctx->scratch.ensure(bytes + bytes / 4 + 4096, ctx->stream));
   return MH_OK;
 }
 
 int ensure_pinned(mh_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->pinned_cap) return MH_OK;
-  if (ctx->pinned) MH_HIP(ctx, hipHostFree(ctx->pinned));
-  ctx->pinned = nullptr;
-  ctx->pinned_cap = 0;
-  size_t cap = bytes + bytes / 4 + 4096;
-  MH_HIP(ctx, hipHostMalloc(&ctx->pinned, cap, hipHostMallocDefault));
-  ctx->pinned_cap = cap;
+  if (bytes > ctx->pinned.cap) MH_HIP(ctx, ctx->pinned.ensure(bytes + bytes / 4 + 4096, ctx->stream));
   return MH_OK;
 }
 
-static void free_screen_bufs(mh_ctx* ctx) {
-  ScreenBufs& b = ctx->sbuf;
-  for (void* p : {(void*)b.qh, (void*)b.qbad, (void*)b.part, (void*)b.tau, (void*)b.ovf_cnt, (void*)b.recs, (void*)b.ovf, (void*)b.stats, (void*)b.inc})
-    if (p) hipFree(p);
-  b = ScreenBufs();
+int ensure_own_depth(mh_ctx* ctx, size_t px) {
+  MH_HIP(ctx, ctx->own_depth.ensure(px * 4, ctx->stream));
+  MH_HIP(ctx, ctx->own_fill.ensure(px, ctx->stream));
+  return MH_OK;
 }
 
 // the context's view of its store
@@ -71,42 +58,38 @@ void bind_store(mh_ctx* ctx) {
 }
 
 int ensure_match_scratch(mh_ctx* ctx, int Q) {
-  const size_t need_pack = match_pack_floats(Q);
-  if (need_pack > ctx->match_pack_cap) {
-    if (ctx->match_pack) MH_HIP(ctx, hipFree(ctx->match_pack));
-    ctx->match_pack = nullptr;
-    ctx->match_pack_cap = 0;
-    MH_HIP(ctx, hipMalloc(&ctx->match_pack, need_pack * sizeof(float)));
-    ctx->match_pack_cap = need_pack;
-  }
-  size_t need = match_scratch_elems(Q, ctx->N > 0 ? ctx->N : 1);
-  if (need > ctx->match_scratch_cap) {
-    if (ctx->match_scratch) MH_HIP(ctx, hipFree(ctx->match_scratch));
-    ctx->match_scratch = nullptr;
-    ctx->match_scratch_cap = 0;
-    MH_HIP(ctx, hipMalloc(&ctx->match_scratch, need * sizeof(Top2)));
-    ctx->match_scratch_cap = need;
-  }
+  hipStream_t s = ctx->stream;
+  MH_HIP(ctx, ctx->match_pack.ensure(match_pack_floats(Q), s));
+  MH_HIP(ctx, ctx->match_scratch.ensure(match_scratch_elems(Q, ctx->N > 0 ? ctx->N : 1), s));
   // the screen's scratch (only for a DB the screen can serve)
   const int q_pad = screen_q_pad(Q);
   if (ctx->sdb.usable && q_pad > ctx->sbuf.q_pad) {
     ScreenBufs& b = ctx->sbuf;
-    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    free_screen_bufs(ctx);
-    const size_t slots = (size_t)q_pad * screen_rec_slots();
-    MH_HIP(ctx, hipMalloc(&b.qh, (size_t)q_pad * DIM * sizeof(_Float16)));
-    MH_HIP(ctx, hipMalloc(&b.qbad, (size_t)q_pad));
-    MH_HIP(ctx, hipMalloc(&b.part, screen_part_bytes(q_pad)));
-    MH_HIP(ctx, hipMalloc(&b.tau, (size_t)q_pad * sizeof(float)));
-    MH_HIP(ctx, hipMalloc(&b.recs, slots * sizeof(uint2)));
-    MH_HIP(ctx, hipMalloc(&b.ovf_cnt, (size_t)q_pad * sizeof(int32_t)));
-    MH_HIP(ctx, hipMalloc(&b.ovf, (size_t)q_pad * SCREEN_OVF_CAP * sizeof(uint2)));
-    MH_HIP(ctx, hipMalloc(&b.stats, (size_t)q_pad * 3 * sizeof(unsigned int)));
-    MH_HIP(ctx, hipMalloc(&b.inc, ((size_t)q_pad + 1) * sizeof(unsigned int)));
-    MH_HIP(ctx, hipMemsetAsync(b.inc, 0, ((size_t)q_pad + 1) * sizeof(unsigned int), ctx->stream));
-    MH_HIP(ctx, hipMemsetAsync(b.recs, 0, slots * sizeof(uint2), ctx->stream));
-    MH_HIP(ctx, hipMemsetAsync(b.ovf_cnt, 0, (size_t)q_pad * sizeof(int32_t), ctx->stream));
-    MH_HIP(ctx, hipMemsetAsync(b.stats, 0, (size_t)q_pad * 3 * sizeof(unsigned int), ctx->stream));
+    mh_ctx::ScreenOwn& o = ctx->screen_own;
+    b = ScreenBufs();
+    const size_t qp = (size_t)q_pad, slots = qp * screen_rec_slots();
+    MH_HIP(ctx, o.qh.ensure(qp * DIM, s));
+    MH_HIP(ctx, o.qbad.ensure(qp, s));
+    MH_HIP(ctx, o.part.ensure(screen_part_bytes(q_pad), s));
+    MH_HIP(ctx, o.tau.ensure(qp, s));
+    MH_HIP(ctx, o.recs.ensure(slots, s));
+    MH_HIP(ctx, o.ovf_cnt.ensure(qp, s));
+    MH_HIP(ctx, o.ovf.ensure(qp * SCREEN_OVF_CAP, s));
+    MH_HIP(ctx, o.stats.ensure(qp * 3, s));
+    MH_HIP(ctx, o.inc.ensure(qp + 1, s));
+    MH_HIP(ctx, hipMemsetAsync(o.inc, 0, (qp + 1) * sizeof(unsigned int), s));
+    MH_HIP(ctx, hipMemsetAsync(o.recs, 0, slots * sizeof(uint2), s));
+    MH_HIP(ctx, hipMemsetAsync(o.ovf_cnt, 0, qp * sizeof(int32_t), s));
+    MH_HIP(ctx, hipMemsetAsync(o.stats, 0, qp * 3 * sizeof(unsigned int), s));
+    b.qh = o.qh;
+    b.qbad = o.qbad;
+    b.part = reinterpret_cast<float2*>(o.part.p);
+    b.tau = o.tau;
+    b.recs = o.recs;
+    b.ovf_cnt = o.ovf_cnt;
+    b.ovf = o.ovf;
+    b.stats = o.stats;
+    b.inc = o.inc;
     b.ovf_cap = SCREEN_OVF_CAP;
     b.q_pad = q_pad;   // only now: a failed allocation above leaves q_pad = 0 and the next call starts over
   }
@@ -142,26 +125,19 @@ int ctx_match(mh_ctx* ctx, const float* qn, const float* qnorm, int Q, int32_t* 
   return MH_OK;
 }
 
-template <typename T>
-static int realloc_dev(mh_ctx* ctx, T*& p, size_t n) {
-  if (p) MH_HIP(ctx, hipFree(p));
-  p = nullptr;
-  MH_HIP(ctx, hipMalloc(&p, (n > 0 ? n : 1) * sizeof(T)));
-  return MH_OK;
-}
-
 int ensure_frame_buffers(mh_ctx* ctx, int Q) {
   if (Q <= ctx->max_q) return MH_OK;
   int cap = ctx->max_q > 0 ? ctx->max_q : 4096;
   while (cap < Q) cap *= 2;
-  int rc;
-  if ((rc = realloc_dev(ctx, ctx->q_desc, (size_t)cap * DIM))) return rc;
-  if ((rc = realloc_dev(ctx, ctx->q_norm, cap))) return rc;
-  if ((rc = realloc_dev(ctx, ctx->q_uv, (size_t)cap * 2))) return rc;
-  if ((rc = realloc_dev(ctx, ctx->nn_idx, cap))) return rc;
-  if ((rc = realloc_dev(ctx, ctx->nn_d1, cap))) return rc;
-  if ((rc = realloc_dev(ctx, ctx->nn_d2, cap))) return rc;
-  ctx->max_q = cap;
+  const size_t n = (size_t)cap;
+  hipStream_t s = ctx->stream;
+  MH_HIP(ctx, ctx->q_desc.ensure(n * DIM, s));
+  MH_HIP(ctx, ctx->q_norm.ensure(n, s));
+  MH_HIP(ctx, ctx->q_uv.ensure(n * 2, s));
+  MH_HIP(ctx, ctx->nn_idx.ensure(n, s));
+  MH_HIP(ctx, ctx->nn_d1.ensure(n, s));
+  MH_HIP(ctx, ctx->nn_d2.ensure(n, s));
+  ctx->max_q = cap;   // the group's guard, once every member has its size
   return MH_OK;
 }
 
@@ -193,6 +169,7 @@ void mh_free_frame_state(mh_ctx* ctx);  // frame_rest.hip
 void mh_free_sift_state(mh_ctx* ctx);   // api_sift.hip
 void mh_free_undistort_state(mh_ctx* ctx);   // undistort.hip
 
+// (the context's buffers free themselves with `delete ctx`, the store with its last user)
 void mh_destroy(mh_ctx* ctx) {
   if (!ctx) return;
   hipSetDevice(ctx->device);
@@ -200,23 +177,10 @@ void mh_destroy(mh_ctx* ctx) {
   mh_free_frame_state(ctx);
   mh_free_sift_state(ctx);
   mh_free_undistort_state(ctx);
-  free_screen_bufs(ctx);
-  mh::free_exchange(ctx);
   db_poll_held(ctx, true);
   for (hipEvent_t e : ctx->held_events) hipEventDestroy(e);
   for (hipEvent_t e : ctx->db_ev)
     if (e) hipEventDestroy(e);
-  if (ctx->db_stage) hipFree(ctx->db_stage);
-  ctx->store.reset();   // the DB goes with its last user
-  ctx->pool.reset();
-  void* ptrs[] = {ctx->q_desc, ctx->q_norm,
-                  ctx->q_uv,    ctx->nn_idx,  ctx->nn_d1,  ctx->nn_d2,    ctx->match_scratch,
-                  ctx->scratch, ctx->match_pack, ctx->rules.ratio_table, ctx->rules.inv_size, ctx->rules.cnt,
-                  ctx->rules.keep1, ctx->lk_scratch, ctx->own_depth, ctx->own_fill, ctx->cams_dev, ctx->df_buf, ctx->img_counts, ctx->hf_img,
-                  ctx->imf.desc, ctx->imf.xy, ctx->imf.words, ctx->imf.q_img, ctx->imf.cams};
-  for (void* p : ptrs)
-    if (p) hipFree(p);
-  if (ctx->pinned) hipHostFree(ctx->pinned);
   if (ctx->wb_ev) hipEventDestroy(ctx->wb_ev);
   if (ctx->wb_stream) hipStreamDestroy(ctx->wb_stream);
   if (ctx->ev_made)
@@ -225,7 +189,6 @@ void mh_destroy(mh_ctx* ctx) {
     for (auto& e : set)
       if (e) hipEventDestroy(e);
   if (ctx->dlv.done) hipEventDestroy(ctx->dlv.done);
-  if (ctx->dlv.stage) hipFree(ctx->dlv.stage);
   if (ctx->lane_in) hipEventDestroy(ctx->lane_in);
   if (ctx->lane_out) hipEventDestroy(ctx->lane_out);
   if (ctx->own_stream) hipStreamDestroy(ctx->own_stream);
@@ -365,13 +328,13 @@ int mh_db_upload_raw(mh_ctx* ctx, const float* desc_host, const int32_t* model_o
   st->model_begin = grouped ? std::move(model_begin) : std::vector<int32_t>();
   st->generation = 0;
   bind_store(ctx);
+  hipStream_t s = ctx->stream;
   if (Npad > st->cap) {
     st->cap = 0;   // until every array has its new size
-    int rc;
-    if ((rc = realloc_dev(ctx, st->desc, Npad * DIM))) return rc;
-    if ((rc = realloc_dev(ctx, st->norm, Npad))) return rc;
-    if ((rc = realloc_dev(ctx, st->xyz, Npad * 3))) return rc;
-    if ((rc = realloc_dev(ctx, st->model, Npad))) return rc;
+    MH_HIP(ctx, st->desc.ensure(Npad * DIM, s));
+    MH_HIP(ctx, st->norm.ensure(Npad, s));
+    MH_HIP(ctx, st->xyz.ensure(Npad * 3, s));
+    MH_HIP(ctx, st->model.ensure(Npad, s));
     st->cap = Npad;
   }
   st->n_models = n_models;
@@ -398,12 +361,11 @@ int mh_db_upload_raw(mh_ctx* ctx, const float* desc_host, const int32_t* model_o
       const size_t need_h = screen_db_half_elems(N);
       if (need_h > st->cap_h) {
         st->cap_h = 0;
-        int rc;
-        if ((rc = realloc_dev(ctx, st->desc_h, need_h))) return rc;
-        if ((rc = realloc_dev(ctx, st->neg_h, screen_dneg_elems(N)))) return rc;
+        MH_HIP(ctx, st->desc_h.ensure(need_h, s));
+        MH_HIP(ctx, st->neg_h.ensure(screen_dneg_elems(N), s));
         st->cap_h = need_h;
       }
-      if (!st->stats) MH_HIP(ctx, hipMalloc(&st->stats, 8 * sizeof(unsigned int)));
+      MH_HIP(ctx, st->stats.ensure(8, s));
       MH_HIP(ctx, hipMemsetAsync(st->stats, 0, 8 * sizeof(unsigned int), ctx->stream));
       launch_db_to_half(st->desc, st->norm, N, st->desc_h, st->neg_h, st->stats, ctx->stream);
       MH_HIP(ctx, hipGetLastError());
@@ -446,11 +408,8 @@ int mh_db_upload_blocks(mh_ctx* ctx, const float* desc_host, const int32_t* mode
   std::vector<int32_t> llo(n_blocks + 1);
   llo[0] = 0;
   for (int b = 0; b < n_blocks; ++b) llo[b + 1] = llo[b] + block_rows[b];
-  if (st->blk_glo) MH_HIP(ctx, hipFree(st->blk_glo));
-  if (st->blk_llo) MH_HIP(ctx, hipFree(st->blk_llo));
-  st->blk_glo = st->blk_llo = nullptr;
-  MH_HIP(ctx, hipMalloc(&st->blk_glo, sizeof(int32_t) * n_blocks));
-  MH_HIP(ctx, hipMalloc(&st->blk_llo, sizeof(int32_t) * (n_blocks + 1)));
+  MH_HIP(ctx, st->blk_glo.ensure(n_blocks, ctx->stream));
+  MH_HIP(ctx, st->blk_llo.ensure((size_t)n_blocks + 1, ctx->stream));
   MH_HIP(ctx, hipMemcpy(st->blk_glo, block_global_row, sizeof(int32_t) * n_blocks, hipMemcpyHostToDevice));
   MH_HIP(ctx, hipMemcpy(st->blk_llo, llo.data(), sizeof(int32_t) * (n_blocks + 1), hipMemcpyHostToDevice));
   st->n_blocks = n_blocks;
@@ -558,10 +517,10 @@ static int match_host(mh_ctx* ctx, const float* q_host, float* normalized_out, i
     launch_row_norms(ctx->q_desc, ctx->q_norm, Q, ctx->stream);
   if ((rc = ctx_match(ctx, ctx->q_desc, ctx->q_norm, Q, ctx->nn_idx, ctx->nn_d1, ctx->nn_d2))) return rc;
   // the reference's acceptance test on squared distances (MATCH_ANN_CPU.hpp:165)
-  int32_t* d_acc = (int32_t*)ctx->scratch;
+  int32_t* d_acc = (int32_t*)ctx->scratch.p;
   launch_accept(ctx->nn_idx, ctx->nn_d1, ctx->nn_d2, Q, ratio, d_acc, ctx->stream);
   MH_HIP(ctx, hipGetLastError());
-  int32_t* h_acc = (int32_t*)ctx->pinned;
+  int32_t* h_acc = (int32_t*)ctx->pinned.p;
   int32_t* h_raw = h_acc + Q;
   float* h_d1 = (float*)(h_raw + Q);
   float* h_d2 = h_d1 + Q;
@@ -673,18 +632,14 @@ int mh_screen_values(mh_ctx* ctx, const float* q_host, int Q, int n_rows, float*
   MH_HIP(ctx, hipSetDevice(ctx->device));
   if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
   const int q_pad = screen_q_pad(Q);
-  float *qd = nullptr, *qn = nullptr, *out = nullptr;
-  _Float16* qh = nullptr;
-  uint8_t* qbad = nullptr;
+  hipStream_t s = ctx->stream;
+  DevBuf<float> qd, qn, out;
+  DevBuf<_Float16> qh;
+  DevBuf<uint8_t> qbad;
   int rc = MH_OK;
-  auto done = [&]() {
-    for (void* p : {(void*)qd, (void*)qn, (void*)out, (void*)qh, (void*)qbad})
-      if (p) hipFree(p);
-  };
-  if (hipMalloc(&qd, (size_t)Q * DIM * 4) != hipSuccess || hipMalloc(&qn, (size_t)Q * 4) != hipSuccess ||
-      hipMalloc(&out, (size_t)Q * n_rows * 4) != hipSuccess || hipMalloc(&qh, (size_t)q_pad * DIM * 2) != hipSuccess ||
-      hipMalloc(&qbad, (size_t)q_pad) != hipSuccess) {
-    done();
+  if (qd.ensure((size_t)Q * DIM, s) != hipSuccess || qn.ensure(Q, s) != hipSuccess ||
+      out.ensure((size_t)Q * n_rows, s) != hipSuccess || qh.ensure((size_t)q_pad * DIM, s) != hipSuccess ||
+      qbad.ensure(q_pad, s) != hipSuccess) {
     ctx->err = "mh_screen_values: out of device memory";
     return MH_ERR_HIP;
   }
@@ -697,7 +652,6 @@ int mh_screen_values(mh_ctx* ctx, const float* q_host, int Q, int n_rows, float*
     ctx->err = "mh_screen_values: device error";
     rc = MH_ERR_HIP;
   }
-  done();
   if (dmax) *dmax = ctx->sdb.dmax;
   if (spread) *spread = ctx->sdb.spread;
   return rc;
@@ -719,16 +673,12 @@ int mh_screen_sample_values(mh_ctx* ctx, const float* q_host, int Q, const int32
   }
   MH_HIP(ctx, hipSetDevice(ctx->device));
   if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
-  float *qd = nullptr, *out = nullptr;
-  int32_t* rd = nullptr;
+  hipStream_t s = ctx->stream;
+  DevBuf<float> qd, out;
+  DevBuf<int32_t> rd;
   int rc = MH_OK;
-  auto done = [&]() {
-    for (void* p : {(void*)qd, (void*)out, (void*)rd})
-      if (p) hipFree(p);
-  };
-  if (hipMalloc(&qd, (size_t)Q * DIM * 4) != hipSuccess || hipMalloc(&out, (size_t)Q * 16 * 4) != hipSuccess ||
-      hipMalloc(&rd, (size_t)Q * 2 * 4) != hipSuccess) {
-    done();
+  if (qd.ensure((size_t)Q * DIM, s) != hipSuccess || out.ensure((size_t)Q * 16, s) != hipSuccess ||
+      rd.ensure((size_t)Q * 2, s) != hipSuccess) {
     ctx->err = "mh_screen_sample_values: out of device memory";
     return MH_ERR_HIP;
   }
@@ -740,7 +690,6 @@ int mh_screen_sample_values(mh_ctx* ctx, const float* q_host, int Q, const int32
     ctx->err = "mh_screen_sample_values: device error";
     rc = MH_ERR_HIP;
   }
-  done();
   return rc;
 }
 

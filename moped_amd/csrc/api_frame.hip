@@ -213,7 +213,8 @@ namespace mh {
 
 // the frame's cameras into the context's device table
 int upload_cams(mh_ctx* ctx, const mh_cam* cams, int n_images) {
-  if (!ctx->cams_dev) MH_HIP(ctx, hipMalloc(&ctx->cams_dev, sizeof(DevCam) * MH_MAX_IMAGES));
+  MH_HIP(ctx, ctx->cams_dev.ensure(MH_MAX_IMAGES, ctx->stream));
+  ctx->cams_view = ctx->cams_dev;
   DevCam h[MH_MAX_IMAGES];
   for (int i = 0; i < n_images; ++i) h[i] = make_devcam(cams[i]);
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));   // frames in flight still read the old table
@@ -262,14 +263,7 @@ int host_frame_begin(mh_ctx* ctx, float* q_desc_host, const float* q_uv_host, co
   MH_HIP(ctx, hipMemcpyAsync(ctx->q_desc, q_desc_host, (size_t)Q * DIM * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   MH_HIP(ctx, hipMemcpyAsync(ctx->q_uv, q_uv_host, (size_t)Q * 2 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   if (n_images > 1) {
-    if (ctx->hf_img_cap < Q) {
-      MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      if (ctx->hf_img) hipFree(ctx->hf_img);
-      ctx->hf_img = nullptr;
-      ctx->hf_img_cap = 0;
-      MH_HIP(ctx, hipMalloc(&ctx->hf_img, (size_t)ctx->max_q * sizeof(int32_t)));
-      ctx->hf_img_cap = ctx->max_q;
-    }
+    if (ctx->hf_img.cap < (size_t)Q) MH_HIP(ctx, ctx->hf_img.ensure((size_t)ctx->max_q, ctx->stream));   // (as many rows as the frame buffers)
     MH_HIP(ctx, hipMemcpyAsync(ctx->hf_img, q_image_host, (size_t)Q * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     if ((rc = mh_frame_set_images(ctx, ctx->hf_img, cams, n_images))) return rc;
   } else if (ctx->q_img) {
@@ -304,14 +298,7 @@ int delivery_begin(mh_ctx* ctx, void* host_block, size_t bytes, unsigned char** 
     return MH_OK;
   }
   (void)hipGetLastError();   // not pinned / not mapped: through the staging buffer
-  if (d.stage_cap < bytes) {
-    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (d.stage) hipFree(d.stage);
-    d.stage = nullptr;
-    d.stage_cap = 0;
-    MH_HIP(ctx, hipMalloc(&d.stage, bytes));
-    d.stage_cap = bytes;
-  }
+  MH_HIP(ctx, d.stage.ensure(bytes, ctx->stream));
   *dst_dev = d.stage;
   return MH_OK;
 }
@@ -499,16 +486,7 @@ int mh_frame_set_depth_image_host(mh_ctx* ctx, const float* depth_xyzn_host, con
   if (width <= 0 || height <= 0) return MH_ERR_ARG;
   if (int rc_enter = mh::enter(ctx)) return rc_enter;
   const size_t px = (size_t)width * height;
-  if (px > ctx->own_depth_px) {
-    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->own_depth) MH_HIP(ctx, hipFree(ctx->own_depth));
-    if (ctx->own_fill) MH_HIP(ctx, hipFree(ctx->own_fill));
-    ctx->own_depth = ctx->own_fill = nullptr;
-    ctx->own_depth_px = 0;
-    MH_HIP(ctx, hipMalloc(&ctx->own_depth, px * 4 * sizeof(float)));
-    MH_HIP(ctx, hipMalloc(&ctx->own_fill, px * sizeof(float)));
-    ctx->own_depth_px = px;
-  }
+  if (int rc = ensure_own_depth(ctx, px)) return rc;
   MH_HIP(ctx, hipMemcpyAsync(ctx->own_depth, depth_xyzn_host, px * 4 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   if (fill_distance_host)
     MH_HIP(ctx, hipMemcpyAsync(ctx->own_fill, fill_distance_host, px * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
@@ -563,21 +541,15 @@ int mh_frame_set_depth_rules(mh_ctx* ctx, const mh_depth_rules* r, const float K
   rs.default_depth = r->default_depth;
   rs.cauchy_scale = r->cauchy_scale;
   if (r->ratio_table) {
-    if (r->n_models > rs.table_models) {
-      MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      if (rs.ratio_table) MH_HIP(ctx, hipFree(rs.ratio_table));
-      rs.ratio_table = nullptr;
-      rs.table_models = 0;
-      MH_HIP(ctx, hipMalloc(&rs.ratio_table, sizeof(float) * 4 * r->n_models));
-    }
+    rs.table_models = 0;
+    MH_HIP(ctx, rs.ratio_table.ensure((size_t)4 * r->n_models, ctx->stream));
     MH_HIP(ctx, hipMemcpyAsync(rs.ratio_table, r->ratio_table, sizeof(float) * 4 * r->n_models, hipMemcpyHostToDevice,
                                ctx->stream));
     MH_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the host table may go away after the call
     rs.table_models = r->n_models;
   } else if (rs.ratio_table) {
     MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    MH_HIP(ctx, hipFree(rs.ratio_table));
-    rs.ratio_table = nullptr;
+    rs.ratio_table.reset();   // (null = no table to the kernels)
     rs.table_models = 0;
   }
   rs.on = true;
@@ -666,7 +638,7 @@ int mh_frame_enqueue_image_batch(mh_ctx* ctx, const uint8_t* const* gray_dev, in
   if (rc) return rc;
   hipStream_t s = ctx->stream;
   if (!ctx->img_counts) {
-    MH_HIP(ctx, hipMalloc(&ctx->img_counts, MH_MAX_BATCH * sizeof(int32_t)));
+    MH_HIP(ctx, ctx->img_counts.ensure(MH_MAX_BATCH, s));
     MH_HIP(ctx, hipMemsetAsync(ctx->img_counts, 0, MH_MAX_BATCH * sizeof(int32_t), s));
   }
   // UNDISTORTED_IMAGE (mh_frame_set_undistort): one remap launch for the B images into the context's staging buffer
@@ -686,30 +658,18 @@ int mh_frame_enqueue_image_batch(mh_ctx* ctx, const uint8_t* const* gray_dev, in
 // the image index of `list_rows` packed rows.
 static int ensure_images_frame(mh_ctx* ctx, int images, int cap, size_t list_rows) {
   mh_ctx::ImagesFrame& m = ctx->imf;
+  hipStream_t s = ctx->stream;
   const size_t rows = (size_t)images * cap;
-  if (rows > m.rows) {
-    if (m.rows) MH_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (a frame in flight may still read the old staging)
-    if (m.desc) hipFree(m.desc);
-    if (m.xy) hipFree(m.xy);
-    m.desc = m.xy = nullptr;
-    m.rows = 0;
-    MH_HIP(ctx, hipMalloc(&m.desc, rows * DIM * sizeof(float)));
-    MH_HIP(ctx, hipMalloc(&m.xy, rows * 2 * sizeof(float)));
-    m.rows = rows;
-  }
+  MH_HIP(ctx, m.desc.ensure(rows * DIM, s));   // (a frame in flight may still read the old staging: ensure waits for it)
+  MH_HIP(ctx, m.xy.ensure(rows * 2, s));
   if (!m.words) {
-    MH_HIP(ctx, hipMalloc(&m.words, 3 * MH_MAX_BATCH * sizeof(int32_t)));
-    MH_HIP(ctx, hipMemsetAsync(m.words, 0, 3 * MH_MAX_BATCH * sizeof(int32_t), ctx->stream));
+    MH_HIP(ctx, m.words.ensure(3 * MH_MAX_BATCH, s));
+    MH_HIP(ctx, hipMemsetAsync(m.words, 0, 3 * MH_MAX_BATCH * sizeof(int32_t), s));
   }
-  if (!m.cams) MH_HIP(ctx, hipMalloc(&m.cams, sizeof(DevCam) * MH_MAX_IMAGES));
-  if (list_rows > m.q_img_cap) {
-    if (m.q_img_cap) MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (m.q_img) hipFree(m.q_img);
-    m.q_img = nullptr;
-    m.q_img_cap = 0;
-    MH_HIP(ctx, hipMalloc(&m.q_img, list_rows * sizeof(int32_t)));
-    MH_HIP(ctx, hipMemsetAsync(m.q_img, 0, list_rows * sizeof(int32_t), ctx->stream));   // (rows past a frame's total are never written)
-    m.q_img_cap = list_rows;
+  MH_HIP(ctx, m.cams.ensure(MH_MAX_IMAGES, s));
+  if (list_rows > m.q_img.cap) {
+    MH_HIP(ctx, m.q_img.ensure(list_rows, s));
+    MH_HIP(ctx, hipMemsetAsync(m.q_img, 0, list_rows * sizeof(int32_t), s));   // (rows past a frame's total are never written)
   }
   return MH_OK;
 }
@@ -737,19 +697,19 @@ static int enqueue_images(mh_ctx* ctx, const char* who, const uint8_t* const* gr
   if (ctx->imf.und_n && ctx->imf.und_n != n)
     return refuse(MH_ERR_ARG, "mh_frame_set_undistort_images gave coefficients for another number of cameras");
   if (int rc_enter = mh::enter(ctx)) return rc_enter;
-  // the call owns the context's image indices and cameras for its own duration: whatever mh_frame_set_images left is the
-  // caller's again afterwards, and a later one-camera frame finds no image index of this one
+  // the call points the context's views of the image indices and cameras at its own for its own duration: whatever
+  // mh_frame_set_images left is the caller's again afterwards, and a later one-camera frame finds no image index of this one
   struct Restore {
     mh_ctx* ctx;
     const int32_t* q_img;
-    DevCam* cams_dev;
+    const DevCam* cams_view;
     int n_images;
     ~Restore() {
       ctx->q_img = q_img;
-      ctx->cams_dev = cams_dev;
+      ctx->cams_view = cams_view;
       ctx->n_images = n_images;
     }
-  } restore{ctx, ctx->q_img, ctx->cams_dev, ctx->n_images};
+  } restore{ctx, ctx->q_img, ctx->cams_view, ctx->n_images};
   ctx->q_img = nullptr;
   ctx->n_images = n;   // (sizes CLUSTER's per-(model, image) tables in prepare_frame)
   const int Q = n * cap;   // rows of one frame
@@ -760,7 +720,7 @@ static int enqueue_images(mh_ctx* ctx, const char* who, const uint8_t* const* gr
   mh_ctx::ImagesFrame& m = ctx->imf;
   if (n > 1) {
     ctx->q_img = m.q_img;
-    ctx->cams_dev = m.cams;
+    ctx->cams_view = m.cams;
   }
   hipStream_t s = ctx->stream;
   // UNDISTORTED_IMAGE per camera: one remap launch, every image with the map of its camera (one set of coefficients

@@ -11,30 +11,20 @@ using namespace mh;
 struct SiftState {
   int width = 0, height = 0, double_size = -1, cap = 0, images = 1;
   SiftPlan plan;
-  SiftBuffers B = {};
-  uint8_t* gray = nullptr;       // staging for host-pointer calls
-  float *desc = nullptr, *xy = nullptr, *scale_ori = nullptr;
-  int32_t* n_dev = nullptr;
+  SiftBuffers B = {};            // what the launches take: views of the next six
+  DevBuf<float> pyramid, tmp;
+  DevBuf<unsigned int> owner;
+  DevBuf<SiftCandidate> cand;
+  DevBuf<SiftKey> keys;
+  DevBuf<int32_t> counters;
+  DevBuf<uint8_t> gray;          // staging for host-pointer calls
+  DevBuf<float> desc, xy, scale_ori;
+  DevBuf<int32_t> n_dev;
   unsigned int own_epoch = 0;    // B.own_epoch points here
   int last_n = 0;                // image slots the last launch filled (mh_sift_debug_*); 0 = none yet
 };
 
 namespace {
-
-void free_sift(SiftState* st) {
-  if (!st) return;
-  void* ptrs[] = {st->B.pyramid, st->B.tmp, st->B.owner, st->B.cand, st->B.keys, st->B.counters,
-                  st->gray,      st->desc,  st->xy,      st->scale_ori, st->n_dev};
-  for (void* p : ptrs)
-    if (p) hipFree(p);
-  delete st;
-}
-
-template <typename T>
-int alloc(mh_ctx* ctx, T*& p, size_t n) {
-  MH_HIP(ctx, hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-  return MH_OK;
-}
 
 // images > 1: room for a batch's images side by side (mh_frame_enqueue_image_batch: one launch per stage for all of them)
 int ensure_sift(mh_ctx* ctx, int width, int height, int double_size, int cap, int images = 1) {
@@ -49,7 +39,7 @@ int ensure_sift(mh_ctx* ctx, int width, int height, int double_size, int cap, in
     MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     cap = std::max(cap, st->cap);
     images = std::max(images, st->images);
-    free_sift(st);
+    delete st;
     ctx->sift = nullptr;
   }
   st = new SiftState;
@@ -61,35 +51,42 @@ int ensure_sift(mh_ctx* ctx, int width, int height, int double_size, int cap, in
   st->images = images;
   if (sift_plan(width, height, double_size, &st->plan) == 0) {
     ctx->err = "mh_sift: image too small (both sides must exceed 12 pixels after scaling)";
-    free_sift(st);   // no half-built state: the next call with this geometry fails the same way
+    delete st;   // no half-built state: the next call with this geometry fails the same way
     ctx->sift = nullptr;
     return MH_ERR_ARG;
   }
   size_t owner = 0;
   for (int o = 0; o < st->plan.n_octaves; ++o) owner += (size_t)st->plan.rows[o] * st->plan.cols[o];
-  int rc = 0;
   const size_t ni = (size_t)images;
-  rc |= alloc(ctx, st->B.pyramid, st->plan.floats * ni);
-  rc |= alloc(ctx, st->B.tmp, (size_t)st->plan.rows0 * st->plan.cols0 * ni);
-  rc |= alloc(ctx, st->B.owner, owner * ni);
+  hipStream_t s = ctx->stream;
   st->B.owner_elems = owner;
   st->B.own_epoch = &st->own_epoch;
   st->B.cand_cap = 4 * cap;
   st->B.key_cap = cap;
   st->B.images = images;
-  rc |= alloc(ctx, st->B.cand, (size_t)st->B.cand_cap * ni);
-  rc |= alloc(ctx, st->B.keys, (size_t)cap * ni);
-  rc |= alloc(ctx, st->B.counters, 4 * ni);
-  rc |= alloc(ctx, st->gray, (size_t)width * height);
-  rc |= alloc(ctx, st->desc, (size_t)cap * 128);
-  rc |= alloc(ctx, st->xy, (size_t)cap * 2);
-  rc |= alloc(ctx, st->scale_ori, (size_t)cap * 2);
-  rc |= alloc(ctx, st->n_dev, 1);
-  if (rc) {
-    free_sift(st);
+  hipError_t e = st->pyramid.ensure(st->plan.floats * ni, s);
+  if (e == hipSuccess) e = st->tmp.ensure((size_t)st->plan.rows0 * st->plan.cols0 * ni, s);
+  if (e == hipSuccess) e = st->owner.ensure(owner * ni, s);
+  if (e == hipSuccess) e = st->cand.ensure((size_t)st->B.cand_cap * ni, s);
+  if (e == hipSuccess) e = st->keys.ensure((size_t)cap * ni, s);
+  if (e == hipSuccess) e = st->counters.ensure(4 * ni, s);
+  if (e == hipSuccess) e = st->gray.ensure((size_t)width * height, s);
+  if (e == hipSuccess) e = st->desc.ensure((size_t)cap * 128, s);
+  if (e == hipSuccess) e = st->xy.ensure((size_t)cap * 2, s);
+  if (e == hipSuccess) e = st->scale_ori.ensure((size_t)cap * 2, s);
+  if (e == hipSuccess) e = st->n_dev.ensure(1, s);
+  if (e != hipSuccess) {
+    delete st;
     ctx->sift = nullptr;
+    ctx->err = std::string("mh_sift: ") + hipGetErrorString(e);
     return MH_ERR_HIP;
   }
+  st->B.pyramid = st->pyramid;
+  st->B.tmp = st->tmp;
+  st->B.owner = st->owner;
+  st->B.cand = st->cand;
+  st->B.keys = st->keys;
+  st->B.counters = st->counters;
   return MH_OK;
 }
 
@@ -132,7 +129,7 @@ int sift_into_batch(mh_ctx* ctx, const uint8_t* const* gray_dev, int n, int widt
 extern "C" {
 
 void mh_free_sift_state(mh_ctx* ctx) {
-  free_sift(ctx->sift);
+  delete ctx->sift;
   ctx->sift = nullptr;
 }
 
@@ -316,8 +313,8 @@ int mh_sift_debug_blur(mh_ctx* ctx, int variant, const float* src_host, int src_
   const int rows = half ? src_rows >> 1 : src_rows, cols = half ? src_cols >> 1 : src_cols;
   const size_t spx = (size_t)src_rows * src_cols, px = (size_t)std::max(rows, 0) * std::max(cols, 0);
   // one allocation: source | dst | dog | half | scratch (8 images)
-  float* buf = nullptr;
-  MH_HIP(ctx, hipMalloc(&buf, (spx + 11 * std::max<size_t>(px, 1)) * sizeof(float)));
+  DevBuf<float> buf;
+  MH_HIP(ctx, buf.ensure(spx + 11 * std::max<size_t>(px, 1), ctx->stream));
   float *src = buf, *dst = buf + spx, *dog = dst + px, *hdst = dog + px, *scratch = hdst + px;
   int rc = MH_OK;
   hipError_t e = hipMemcpyAsync(src, src_host, spx * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
@@ -333,8 +330,7 @@ int mh_sift_debug_blur(mh_ctx* ctx, int variant, const float* src_host, int src_
       if (e == hipSuccess && half_host) e = hipMemcpyAsync(half_host, hdst, px * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
     }
   }
-  const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-  hipFree(buf);
+  const hipError_t e2 = hipStreamSynchronize(ctx->stream);   // (before buf goes)
   if (e == hipSuccess) e = e2;
   if (e != hipSuccess) {
     ctx->err = std::string("mh_sift_debug_blur: ") + hipGetErrorString(e);

@@ -52,7 +52,7 @@ int mh_meanshift(mh_ctx* ctx, const float* pts_host, int n, int dim, float radiu
   const size_t b_i = (size_t)(n + 2) * sizeof(int32_t);
   int rc = ensure_scratch(ctx, b_pts + 4 * b_i + 64);
   if (rc) return rc;
-  unsigned char* base = (unsigned char*)ctx->scratch;
+  unsigned char* base = ctx->scratch;
   float* d_pts = (float*)base;
   int32_t* d_members = (int32_t*)(base + ((b_pts + 15) & ~(size_t)15));
   int32_t* d_start = d_members + (n + 2);
@@ -113,7 +113,7 @@ int mh_meanshift_batch(mh_ctx* ctx, const float* pts_host, const int32_t* off, i
   int rc = ensure_scratch(ctx, b_pts + ints * sizeof(int32_t) + 64);
   if (rc) return rc;
   if ((rc = ensure_pinned(ctx, (2 * (size_t)total + n_start + n_problems) * sizeof(int32_t)))) return rc;
-  unsigned char* base = (unsigned char*)ctx->scratch;
+  unsigned char* base = ctx->scratch;
   float* d_pts = (float*)base;
   int32_t* d_off = (int32_t*)(base + b_pts);
   int32_t* d_members = d_off + n_off;
@@ -127,7 +127,7 @@ int mh_meanshift_batch(mh_ctx* ctx, const float* pts_host, const int32_t* off, i
                          d_ncl, d_label, s);
   MH_HIP(ctx, hipGetLastError());
   // members, label, cl_start, ncl are contiguous on the device: one copy back
-  int32_t* h = (int32_t*)ctx->pinned;
+  int32_t* h = (int32_t*)ctx->pinned.p;
   MH_HIP(ctx, hipMemcpyAsync(h, d_members, (2 * (size_t)total + n_start + n_problems) * sizeof(int32_t),
                              hipMemcpyDeviceToHost, s));
   MH_HIP(ctx, hipStreamSynchronize(s));
@@ -171,7 +171,7 @@ static int pose_ransac_impl(mh_ctx* ctx, const mh_corr* corr_host, const mh_dept
       }
     if ((rc = upload_cams(ctx, cam, n_images))) return rc;
     MH_HIP(ctx, hipMemcpyAsync(fs->m_img, image_of_host, (size_t)total * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    images.cams = ctx->cams_dev;
+    images.cams = ctx->cams_view;
     images.img_of = fs->m_img;
     images.n_images = n_images;
   }
@@ -193,7 +193,7 @@ static int pose_ransac_impl(mh_ctx* ctx, const mh_corr* corr_host, const mh_dept
   MH_HIP(ctx, hipGetLastError());
   // the five result arrays into one pinned block (pageable destinations make every one of these copies a blocking one)
   if (int rc_pin = ensure_pinned(ctx, (size_t)n_obj * 11 * 4)) return rc_pin;
-  int32_t* const valid = static_cast<int32_t*>(ctx->pinned);
+  int32_t* const valid = reinterpret_cast<int32_t*>(ctx->pinned.p);
   int32_t* const ninl = valid + n_obj;
   int32_t* const ocl = ninl + n_obj;
   float* const err = reinterpret_cast<float*>(ocl + n_obj);
@@ -288,7 +288,7 @@ int mh_cluster_linkage(mh_ctx* ctx, const mh_corr* corr_host, const mh_depth* de
   const size_t ints = n_off + 2 * (size_t)total + n_start + n_problems;
   if ((rc = ensure_scratch(ctx, b_corr + b_depth + ints * sizeof(int32_t) + 64))) return rc;
   if ((rc = ensure_pinned(ctx, (2 * (size_t)total + n_start + n_problems) * sizeof(int32_t)))) return rc;
-  unsigned char* base = (unsigned char*)ctx->scratch;
+  unsigned char* base = ctx->scratch;
   mh_corr* d_corr = (mh_corr*)base;
   float* d_depth = (float*)(base + b_corr);
   int32_t* d_off = (int32_t*)(base + b_corr + b_depth);
@@ -307,10 +307,10 @@ int mh_cluster_linkage(mh_ctx* ctx, const mh_corr* corr_host, const mh_depth* de
   lp.sigma2d = prm->sigma2d;
   lp.sigma3d = prm->sigma3d;
   lp.linkage_type = prm->linkage_type;
-  launch_linkage_batch(d_corr, d_depth, d_off, n_problems, ctx->depth_img, lp, ctx->lk_scratch, ctx->lk_scratch_floats,
+  launch_linkage_batch(d_corr, d_depth, d_off, n_problems, ctx->depth_img, lp, ctx->lk_scratch, ctx->lk_scratch.cap,
                        d_members, d_start, d_ncl, d_label, s);
   MH_HIP(ctx, hipGetLastError());
-  int32_t* hbuf = (int32_t*)ctx->pinned;
+  int32_t* hbuf = (int32_t*)ctx->pinned.p;
   MH_HIP(ctx, hipMemcpyAsync(hbuf, d_members, (2 * (size_t)total + n_start + n_problems) * sizeof(int32_t),
                              hipMemcpyDeviceToHost, s));
   MH_HIP(ctx, hipStreamSynchronize(s));
@@ -328,7 +328,7 @@ int mh_project_test(mh_ctx* ctx, const float pose[7], const mh_corr* corr_host, 
   const size_t b_c = (size_t)n * sizeof(mh_corr);
   int rc = ensure_scratch(ctx, b_c + (size_t)n * 5 + 256);
   if (rc) return rc;
-  unsigned char* base = (unsigned char*)ctx->scratch;
+  unsigned char* base = ctx->scratch;
   mh_corr* d_c = (mh_corr*)base;
   float* d_e = (float*)(base + ((b_c + 15) & ~(size_t)15));
   float* d_pose = d_e + n;
@@ -398,7 +398,7 @@ int mh_filter_images(mh_ctx* ctx, const mh_corr* corr_host, const int32_t* image
   fb.max_objects = n_obj;  // grid size; arrays are at least this large
   if (multi) {
     fb.m_img = fs->m_img;
-    fb.cams = ctx->cams_dev;
+    fb.cams = ctx->cams_view;
     fb.n_images = n_images;
   }
   launch_filter(fb, make_devcam(*cam), min_points, feature_distance, min_score, fs->n_slots,
@@ -408,7 +408,7 @@ int mh_filter_images(mh_ctx* ctx, const mh_corr* corr_host, const int32_t* image
   // blocking copies after it cost the step 0.1 ms: profiles/r02_host_step_timing.txt)
   const size_t words = 1 + 4 * (size_t)n_obj + (size_t)std::max(M, 1);
   if ((rc = ensure_pinned(ctx, words * 4))) return rc;
-  int32_t* const hp = static_cast<int32_t*>(ctx->pinned);
+  int32_t* const hp = reinterpret_cast<int32_t*>(ctx->pinned.p);
   int32_t* const h_kept = hp;
   float* const sc = reinterpret_cast<float*>(hp + 1);
   int32_t* const old_of = hp + 1 + n_obj;

@@ -126,7 +126,7 @@ int mh_step_match_fetch(mh_ctx* ctx, int32_t* model_off_host, int32_t* match_que
   FrameState* fs = ctx->fs;
   const int nm = ctx->n_models, take = std::min(st.Q, fs->max_m);   // (a frame accepts at most one match per query)
   if (int rc = ensure_pinned(ctx, 64 + (size_t)(nm + 1 + take) * 4 + (size_t)take * sizeof(mh_corr) + 64)) return rc;
-  PinCursor pc{static_cast<unsigned char*>(ctx->pinned)};
+  PinCursor pc{ctx->pinned};
   FrameCounts* fc = pc.take<FrameCounts>(1, fs->counts);
   int32_t* off = pc.take<int32_t>(nm + 1, fs->model_off);
   int32_t* mq = pc.take<int32_t>(take, fs->m_q);
@@ -173,7 +173,7 @@ int mh_step_cluster(mh_ctx* ctx, float radius, float merge, int min_pts, int max
   const int M = st.M, tab = std::min(fs->max_clusters, std::max(M, 1));
   if (int rc = ensure_pinned(ctx, 256 + (size_t)(3 * tab + std::max(M, 1)) * 4)) return rc;
   if (int rc = step_stage(ctx, &p, 0, 1)) return rc;
-  PinCursor pc{static_cast<unsigned char*>(ctx->pinned)};
+  PinCursor pc{ctx->pinned};
   FrameCounts* fc = pc.take<FrameCounts>(1, fs->counts);
   int32_t* ncl = pc.take<int32_t>(1, fs->n_clusters);
   int32_t* cm = pc.take<int32_t>(tab, fs->cl_model);
@@ -227,7 +227,7 @@ int mh_step_pose(mh_ctx* ctx, int which, const mh_pose_params* prm, uint64_t see
   // (frame_rest keys POSE2's random streams with seed ^ 0x5DEECE66D: undone here, the caller's seed is the stage's)
   if (int rc = ensure_pinned(ctx, 256 + (size_t)std::max(n_new, 1) * (4 + 4 + 28))) return rc;
   if (int rc = step_stage(ctx, &p, which == 1 ? seed : seed ^ 0x5DEECE66Dull, stage)) return rc;
-  PinCursor pc{static_cast<unsigned char*>(ctx->pinned)};
+  PinCursor pc{ctx->pinned};
   FrameCounts* fc = pc.take<FrameCounts>(1, fs->counts);
   int32_t* valid = pc.take<int32_t>(n_new, fs->obj_valid + base);
   int32_t* model = pc.take<int32_t>(n_new, fs->obj_model + base);
@@ -285,7 +285,7 @@ int mh_step_filter(mh_ctx* ctx, int which, int min_points, float feature_distanc
   const int nb = std::max(st.n_slots, 1), tab = std::min(nb, fs->max_clusters), M = std::max(st.M, 1);
   if (int rc = ensure_pinned(ctx, 512 + (size_t)(2 * nb + 2 * tab + M) * 4)) return rc;
   if (int rc = step_stage(ctx, &p, 0, stage)) return rc;
-  PinCursor pc{static_cast<unsigned char*>(ctx->pinned)};
+  PinCursor pc{ctx->pinned};
   FrameCounts* fc = pc.take<FrameCounts>(1, fs->counts);
   int32_t* kept_p = pc.take<int32_t>(1, fs->n_slots);
   float* sc = pc.take<float>(nb, fs->obj_score_raw);

@@ -131,20 +131,8 @@ int ensure_exchange(mh_ctx* ctx, int world, int BQ, int B) {
   const size_t stride = 3 * (size_t)BQ + (size_t)B * EX2_WORDS;
   if (ex.local && ex.stride == stride && ex.world == world && ex.batch == B) return MH_OK;
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));   // an earlier frame may still read the old blocks
-  if (ex.cap_local < stride) {
-    if (ex.local) hipFree(ex.local);
-    ex.local = nullptr;
-    ex.cap_local = 0;
-    MH_HIP(ctx, hipMalloc(&ex.local, stride * 4));
-    ex.cap_local = stride;
-  }
-  if (ex.cap_gather < stride * world) {
-    if (ex.gathered) hipFree(ex.gathered);
-    ex.gathered = nullptr;
-    ex.cap_gather = 0;
-    MH_HIP(ctx, hipMalloc(&ex.gathered, stride * world * 4));
-    ex.cap_gather = stride * world;
-  }
+  MH_HIP(ctx, ex.local.ensure(stride, ctx->stream));
+  MH_HIP(ctx, ex.gathered.ensure(stride * world, ctx->stream));
   MH_HIP(ctx, hipMemsetAsync(ex.local, 0, stride * 4, ctx->stream));
   MH_HIP(ctx, hipMemsetAsync(ex.gathered, 0, stride * world * 4, ctx->stream));
   ex.stride = stride;
@@ -258,15 +246,6 @@ __global__ void __launch_bounds__(128) deliver_previous_kernel(const int32_t* __
 }
 
 }  // namespace
-
-namespace mh {
-void free_exchange(mh_ctx* ctx) {
-  if (ctx->ex.local) hipFree(ctx->ex.local);
-  if (ctx->ex.gathered) hipFree(ctx->ex.gathered);
-  if (ctx->ex.flush) hipFree(ctx->ex.flush);
-  ctx->ex = mh_ctx::Exchange();
-}
-}  // namespace mh
 
 extern "C" {
 
@@ -454,14 +433,7 @@ int mh_frame_gather_objects(mh_ctx* ctx, mh_comm* comm, int slot, mh_object* obj
   if (int rc = mh_frame_result_dev(ctx, &block, &bytes)) return rc;
   auto& ex = ctx->ex;
   const size_t need = (size_t)bytes * comm->world;
-  if (ex.flush_bytes < need) {
-    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ex.flush) hipFree(ex.flush);
-    ex.flush = nullptr;
-    ex.flush_bytes = 0;
-    MH_HIP(ctx, hipMalloc(&ex.flush, need));
-    ex.flush_bytes = need;
-  }
+  MH_HIP(ctx, ex.flush.ensure(need, ctx->stream));
   const unsigned char* mine = static_cast<const unsigned char*>(block) + (size_t)slot * bytes;
   if (int rc = comm_allgather(ctx, comm, mine, ex.flush, (size_t)bytes)) return rc;
   ex.host.resize(need / 4);

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "common.h"
+#include "devbuf.h"
 #include "screen.h"
 #include "steps.h"
 
@@ -35,17 +36,17 @@ struct DbStore {
   int N = 0, n_models = 0;
   int32_t index_base = 0;
   int n_blocks = 0;            // > 1: the rows are n_blocks runs of global rows (mh_db_upload_blocks; RowMap, common.h)
-  int32_t* blk_glo = nullptr;  // device [n_blocks]: first global row of each block
-  int32_t* blk_llo = nullptr;  // device [n_blocks + 1]: first local row of each block, N at the end
-  float* desc = nullptr;       // [rows padded to 128][128], zero padding rows
-  float* norm = nullptr;       // [padded] dot(d,d), +inf on padding rows
-  float* xyz = nullptr;        // [padded][3]
-  int32_t* model = nullptr;    // [padded]
-  size_t cap = 0;              // rows allocated
-  _Float16* desc_h = nullptr;  // f16 image for the screen (match_screen.hip)
-  float* neg_h = nullptr;      // [tiles][192] -norm/2 per row + row-block extrema (screen.h)
-  size_t cap_h = 0;            // elements allocated
-  unsigned int* stats = nullptr;
+  mh::DevBuf<int32_t> blk_glo;   // device [n_blocks]: first global row of each block
+  mh::DevBuf<int32_t> blk_llo;   // device [n_blocks + 1]: first local row of each block, N at the end
+  mh::DevBuf<float> desc;        // [rows padded to 128][128], zero padding rows
+  mh::DevBuf<float> norm;        // [padded] dot(d,d), +inf on padding rows
+  mh::DevBuf<float> xyz;         // [padded][3]
+  mh::DevBuf<int32_t> model;     // [padded]
+  size_t cap = 0;                // rows every one of the four holds (written after the last of them has its size)
+  mh::DevBuf<_Float16> desc_h;   // f16 image for the screen (match_screen.hip)
+  mh::DevBuf<float> neg_h;       // [tiles][192] -norm/2 per row + row-block extrema (screen.h)
+  size_t cap_h = 0;              // elements of desc_h, once neg_h has its size too
+  mh::DevBuf<unsigned int> stats;
   mh::ScreenDb screen;
   // what an edit needs to know (host side): the rows are grouped by model in ascending order, and then model m's rows
   // are [model_begin[m], model_begin[m + 1]) (empty models allowed)
@@ -54,13 +55,12 @@ struct DbStore {
   uint64_t generation = 0;            // edits since the upload (mh_db_generation)
   hipEvent_t ready = nullptr;         // recorded behind the edit that filled this set (mh_db_adopt waits on it)
   std::shared_ptr<DbPool> pool;       // where the set parks when its last holder lets go (none: it is freed)
-  ~DbStore() {
+  ~DbStore() {   // (the arrays free themselves afterwards: hipFree finds a block's device by itself)
+    if (!ready) return;
     int cur = 0;
     const bool have = hipGetDevice(&cur) == hipSuccess;
     hipSetDevice(device);
-    for (void* p : {(void*)desc, (void*)norm, (void*)xyz, (void*)model, (void*)desc_h, (void*)neg_h, (void*)stats, (void*)blk_glo, (void*)blk_llo})
-      if (p) hipFree(p);
-    if (ready) hipEventDestroy(ready);
+    hipEventDestroy(ready);
     if (have) hipSetDevice(cur);
   }
 };
@@ -130,7 +130,16 @@ struct mh_ctx {
   float* db_xyz = nullptr;       // [N][3]
   int32_t* db_model = nullptr;   // [N]
   mh::ScreenDb sdb;
-  mh::ScreenBufs sbuf;           // the screen's per-frame scratch
+  mh::ScreenBufs sbuf;           // the screen's per-frame scratch as the launches take it: views of `screen_own`
+  struct ScreenOwn {             // ... which ensure_match_scratch sizes together (sbuf.q_pad says for how many queries)
+    mh::DevBuf<_Float16> qh;
+    mh::DevBuf<uint8_t> qbad;
+    mh::DevBuf<unsigned char> part;
+    mh::DevBuf<float> tau;
+    mh::DevBuf<uint2> recs, ovf;
+    mh::DevBuf<int32_t> ovf_cnt;
+    mh::DevBuf<unsigned int> stats, inc;
+  } screen_own;
   int match_mode = -1;           // mh_match_set_mode
   int pose_split = 1;            // mh_pose_set_split: POSE as two launches (hypotheses, one-wavefront refines) in the frame paths
   // ---- edits of the resident DB (db_edit.hip) ----
@@ -142,8 +151,7 @@ struct mh_ctx {
   };
   std::vector<HeldStore> held;
   std::vector<hipEvent_t> held_events;   // idle events of released entries
-  float* db_stage = nullptr;         // an edit's new rows: [cap][128] descriptors, [cap] norm terms, [cap][3] coordinates
-  size_t db_stage_cap = 0;           // rows
+  mh::DevBuf<float> db_stage;        // an edit's new rows: [rows][128] descriptors, [rows] norm terms, [rows][3] coordinates
   int db_edit_route = 0;             // 0: the fused pass (db_splice_kernel); 1: device copies + the upload's preparation (mh_db_debug_route)
   hipEvent_t db_ev[2] = {nullptr, nullptr};   // around an edit's pass over the rows when timing is on (mh_db_edit_ms)
   bool db_ev_valid = false;
@@ -154,22 +162,18 @@ struct mh_ctx {
 
   // ---- per-frame buffers ----
   int max_q = 0, max_clusters = 0, max_objects = 0;
-  float* q_desc = nullptr;       // [max_q][128] staging for host-pointer entry points
-  float* q_norm = nullptr;       // [max_q]
-  float* q_uv = nullptr;         // [max_q][2]
-  int32_t* nn_idx = nullptr;     // [max_q]
-  float* nn_d1 = nullptr;        // [max_q]
-  float* nn_d2 = nullptr;        // [max_q]
-  mh::Top2* match_scratch = nullptr;
-  size_t match_scratch_cap = 0;
-  float* match_pack = nullptr;   // queries re-laid out for scalar loads (match.hip)
-  size_t match_pack_cap = 0;
+  mh::DevBuf<float> q_desc;      // [max_q][128] staging for host-pointer entry points
+  mh::DevBuf<float> q_norm;      // [max_q]
+  mh::DevBuf<float> q_uv;        // [max_q][2]
+  mh::DevBuf<int32_t> nn_idx;    // [max_q]
+  mh::DevBuf<float> nn_d1;       // [max_q]
+  mh::DevBuf<float> nn_d2;       // [max_q]
+  mh::DevBuf<mh::Top2> match_scratch;
+  mh::DevBuf<float> match_pack;  // queries re-laid out for scalar loads (match.hip)
 
   // generic byte scratch for host-pointer entry points
-  void* scratch = nullptr;
-  size_t scratch_cap = 0;
-  void* pinned = nullptr;
-  size_t pinned_cap = 0;
+  mh::DevBuf<unsigned char> scratch;
+  mh::PinBuf<unsigned char> pinned;
   // mh_frame_run_host's write-back of the normalised descriptors: a stream of its own behind an event recorded right
   // after normalize_kernel, so that the 1.5 MB copy runs beside MATCH .. FILTER2 instead of after them
   hipStream_t wb_stream = nullptr;
@@ -196,7 +200,7 @@ struct mh_ctx {
   bool und_on = false;                // mh_frame_set_undistort: the image paths remap before FEAT
   float und_dist[4] = {0, 0, 0, 0};   // ... with these k1, k2, p1, p2 and the frame camera's K
   int32_t* feat_count_dev = nullptr;  // frame enqueued from an image: device word with its keypoint count
-  int32_t* img_counts = nullptr;      // mh_frame_enqueue_image_batch: [MH_MAX_BATCH] keypoint counts of the batch's images (device)
+  mh::DevBuf<int32_t> img_counts;     // mh_frame_enqueue_image_batch: [MH_MAX_BATCH] keypoint counts of the batch's images (device)
   int feat_expected = 0;              // keypoints of the last fetched image frame (sizes the next MATCH launch)
   int feat_last = -1;
   const float4* batch_img[MH_MAX_BATCH] = {};   // depth maps of the frames of a batch (mh_frame_set_depth_image_batch)
@@ -206,32 +210,29 @@ struct mh_ctx {
 
   // N > 1 (comm.hip): the send / receive blocks of the frame exchange, the flush buffer of the last frames
   struct Exchange {
-    int32_t* local = nullptr;      // [3][B Q] top-2 words + B result heads
-    int32_t* gathered = nullptr;   // world of those
-    size_t cap_local = 0, cap_gather = 0, stride = 0;   // words
+    mh::DevBuf<int32_t> local;      // [3][B Q] top-2 words + B result heads
+    mh::DevBuf<int32_t> gathered;   // world of those
+    size_t stride = 0;              // words
     int world = 0, batch = 0, bq = 0;
-    unsigned char* flush = nullptr;
-    size_t flush_bytes = 0;
+    mh::DevBuf<unsigned char> flush;
     std::vector<int32_t> host;
   } ex;
 
   // frames with several images (mh_frame_set_images): image of every query + the cameras; n_images == 1 = off
   const int32_t* q_img = nullptr;     // device, [Q]
-  int32_t* hf_img = nullptr;          // mh_frame_run_host's copy of the per-query image indices
-  int hf_img_cap = 0;
-  mh::DevCam* cams_dev = nullptr;     // device, [MH_MAX_IMAGES]
+  mh::DevBuf<int32_t> hf_img;         // mh_frame_run_host's copy of the per-query image indices
+  mh::DevBuf<mh::DevCam> cams_dev;    // device, [MH_MAX_IMAGES]: the table mh_frame_set_images fills
+  const mh::DevCam* cams_view = nullptr;   // the table the kernels read (not owned): cams_dev, or imf.cams while mh_frame_enqueue_images runs
   int n_images = 1;
 
   // frames with several cameras from device images (mh_frame_enqueue_images[_batch]): FEAT writes every image's list at a
   // stride of `cap` rows here, images_pack_kernel hands them over to the frames' packed lists (images_pack.hip)
   struct ImagesFrame {
-    float* desc = nullptr;         // device [rows][128]
-    float* xy = nullptr;           // device [rows][2]
-    size_t rows = 0;
-    int32_t* words = nullptr;      // device [3][MH_MAX_BATCH]: FEAT's count per image | the clamped count per image | the total per frame
-    int32_t* q_img = nullptr;      // device: image index of every row of the packed lists
-    size_t q_img_cap = 0;
-    mh::DevCam* cams = nullptr;    // device [MH_MAX_IMAGES]: the rig of the call in flight (the table of mh_frame_set_images stays the caller's)
+    mh::DevBuf<float> desc;        // device [rows][128]
+    mh::DevBuf<float> xy;          // device [rows][2]
+    mh::DevBuf<int32_t> words;     // device [3][MH_MAX_BATCH]: FEAT's count per image | the clamped count per image | the total per frame
+    mh::DevBuf<int32_t> q_img;     // device: image index of every row of the packed lists
+    mh::DevBuf<mh::DevCam> cams;   // device [MH_MAX_IMAGES]: the rig of the call in flight (the table of mh_frame_set_images stays the caller's)
     int n_live = 0;                // images of the frame whose total feat_count_dev names (0: not such a frame)
     int last_n = 0;                // mh_frame_image_counts: images of the frame last fetched, their clamped counts
     int32_t last[MH_MAX_IMAGES] = {};
@@ -252,14 +253,11 @@ struct mh_ctx {
     float feature_filter = -1.f, match_filter = -1.f;   // Density * 100 * 100; < 0 = off
     float K[4] = {0, 0, 0, 0};
     float max_depth = 4.f, default_depth = 1.f, cauchy_scale = 0.1f;
-    float* ratio_table = nullptr;   // device [n_models][4] or nullptr
-    int table_models = 0;
-    double* inv_size = nullptr;     // device [patches]
-    int patches_cap = 0;
-    int32_t* cnt = nullptr;         // device [n_models][patches], zero between frames
-    size_t cnt_cap = 0;
-    uint8_t* keep1 = nullptr;       // device [max_q]
-    int keep_cap = 0;
+    mh::DevBuf<float> ratio_table;  // device [n_models][4]
+    int table_models = 0;           // models of the table in use (0: none)
+    mh::DevBuf<double> inv_size;    // device [patches]
+    mh::DevBuf<int32_t> cnt;        // device [n_models][patches], zero between frames
+    mh::DevBuf<uint8_t> keep1;      // device [max_q]
     // what the last frame's front end left in these buffers (mh_depth_rules_debug_fetch): patches and queries per
     // frame, the result slots [first, first + frames) whose maps lie frame after frame, which arrays were written
     struct Last {
@@ -271,20 +269,17 @@ struct mh_ctx {
   // moped3d CLUSTER_LINKAGE instead of mean shift (mh_frame_set_cluster_linkage)
   bool linkage_on = false;
   mh::LinkageParams linkage;
-  float* own_depth = nullptr;     // device copies of a host depth / distance map (mh_frame_set_depth_image_host)
-  float* own_fill = nullptr;
-  size_t own_depth_px = 0;
-  float* lk_scratch = nullptr;
-  unsigned char* df_buf = nullptr; // mh_depth_fill: [status words | downscaled depths | downscaled distances]
-  size_t lk_scratch_floats = 0;
+  mh::DevBuf<float> own_depth;    // device copies of a host depth / distance map (ensure_own_depth)
+  mh::DevBuf<float> own_fill;
+  mh::DevBuf<float> lk_scratch;
+  mh::DevBuf<unsigned char> df_buf;   // mh_depth_fill: [status words | downscaled depths | downscaled distances]
   size_t lk_scratch_limit = (size_t)4 << 30;   // bytes; mh_set_linkage_scratch_limit
 
   // mh_frame_fetch_batch_async / mh_frame_fetch_previous_async: delivery of a batch's objects into the caller's pinned block
   struct Delivery {
     hipEvent_t done = nullptr;          // recorded behind the delivery on the context's stream
     bool pending = false;
-    unsigned char* stage = nullptr;     // device staging for blocks the device cannot write directly
-    size_t stage_cap = 0;
+    mh::DevBuf<unsigned char> stage;    // device staging for blocks the device cannot write directly
     unsigned char* host_block = nullptr;   // the pending delivery's destination, as the caller knows it
     int B = 0, max_objects = 0;
     uint32_t tag = 0;
@@ -299,8 +294,6 @@ struct mh_ctx {
 };
 
 namespace mh {
-
-void free_exchange(mh_ctx* ctx);   // comm.hip
 
 #define MH_HIP(ctx, call)                                                         \
   do {                                                                            \
@@ -317,6 +310,7 @@ void db_poll_held(mh_ctx* ctx, bool wait);   // db_edit.hip: let go of adopted-a
 int ensure_frame_buffers(mh_ctx* ctx, int Q);
 int ensure_scratch(mh_ctx* ctx, size_t bytes);
 int ensure_pinned(mh_ctx* ctx, size_t bytes);
+int ensure_own_depth(mh_ctx* ctx, size_t px);   // own_depth [px][4] and own_fill [px]
 int ensure_match_scratch(mh_ctx* ctx, int Q);
 // MATCH of Q normalised queries against the context's DB on its stream: exact (idx1, d1, d2) per query, by the
 // two-stage screen when it pays and the DB allows it, else by the exact kernels (bit-identical results either way).

@@ -127,11 +127,6 @@ int refuse(mh_ctx* ctx, const char* who, const char* why) {
   return MH_ERR_ARG;
 }
 
-template <typename T>
-hipError_t dev_alloc(T*& p, size_t n) {
-  return hipMalloc(&p, (n > 0 ? n : 1) * sizeof(T));
-}
-
 // a buffer set for cap_rows rows (a multiple of 128), with the f16 image's arrays when a store of that many rows can have one
 int alloc_set(mh_ctx* ctx, size_t cap_rows, std::shared_ptr<DbStore>& out) {
   if (screen_dneg_elems(128) != (size_t)DB_DD) {
@@ -140,16 +135,17 @@ int alloc_set(mh_ctx* ctx, size_t cap_rows, std::shared_ptr<DbStore>& out) {
   }
   std::shared_ptr<DbStore> st = make_store(ctx->device);
   cap_rows = std::max<size_t>(cap_rows, 128);
-  MH_HIP(ctx, dev_alloc(st->desc, cap_rows * DIM));
-  MH_HIP(ctx, dev_alloc(st->norm, cap_rows));
-  MH_HIP(ctx, dev_alloc(st->xyz, cap_rows * 3));
-  MH_HIP(ctx, dev_alloc(st->model, cap_rows));
+  hipStream_t s = ctx->stream;   // (a fresh set: nothing to wait for)
+  MH_HIP(ctx, st->desc.ensure(cap_rows * DIM, s));
+  MH_HIP(ctx, st->norm.ensure(cap_rows, s));
+  MH_HIP(ctx, st->xyz.ensure(cap_rows * 3, s));
+  MH_HIP(ctx, st->model.ensure(cap_rows, s));
   st->cap = cap_rows;
   if (screen_wanted(1 << 30, (int)cap_rows)) {
-    MH_HIP(ctx, dev_alloc(st->desc_h, screen_db_half_elems((int)cap_rows)));
-    MH_HIP(ctx, dev_alloc(st->neg_h, screen_dneg_elems((int)cap_rows)));
+    MH_HIP(ctx, st->desc_h.ensure(screen_db_half_elems((int)cap_rows), s));
+    MH_HIP(ctx, st->neg_h.ensure(screen_dneg_elems((int)cap_rows), s));
     st->cap_h = screen_db_half_elems((int)cap_rows);
-    MH_HIP(ctx, dev_alloc(st->stats, 8));
+    MH_HIP(ctx, st->stats.ensure(8, s));
   }
   MH_HIP(ctx, hipEventCreateWithFlags(&st->ready, hipEventDisableTiming));
   st->pool = ctx->pool;
@@ -182,14 +178,13 @@ int take_set(mh_ctx* ctx, size_t n_pad, bool image, std::shared_ptr<DbStore>& ou
   return alloc_set(ctx, std::max(n_pad, cap_rows), out);
 }
 
+// rows the staging block holds: descriptors, norm terms and coordinates lie at that pitch one after the other
+size_t stage_rows(const mh_ctx* ctx) { return ctx->db_stage.cap / (DIM + 1 + 3); }
+
 int ensure_stage(mh_ctx* ctx, size_t rows) {
-  if (rows <= ctx->db_stage_cap) return MH_OK;
-  if (ctx->db_stage) MH_HIP(ctx, hipFree(ctx->db_stage));
-  ctx->db_stage = nullptr;
-  ctx->db_stage_cap = 0;
+  if (rows <= stage_rows(ctx)) return MH_OK;
   const size_t cap = std::max<size_t>(rows + rows / 4, 4096);
-  MH_HIP(ctx, hipMalloc(&ctx->db_stage, cap * (DIM + 1 + 3) * sizeof(float)));
-  ctx->db_stage_cap = cap;
+  MH_HIP(ctx, ctx->db_stage.ensure(cap * (DIM + 1 + 3), ctx->stream));
   return MH_OK;
 }
 
@@ -216,8 +211,8 @@ int run_splice(mh_ctx* ctx, int b, int e, int n_rows, int model_id, int model_de
   st->n_blocks = 0;
   st->index_base = 0;
   const float* stage = ctx->db_stage;
-  const float* stage_norm = stage ? stage + ctx->db_stage_cap * DIM : nullptr;
-  const float* stage_xyz = stage ? stage_norm + ctx->db_stage_cap : nullptr;
+  const float* stage_norm = stage ? stage + stage_rows(ctx) * DIM : nullptr;
+  const float* stage_xyz = stage ? stage_norm + stage_rows(ctx) : nullptr;
   const bool timed = ctx->timing;
   if (timed)
     for (hipEvent_t& ev : ctx->db_ev)
@@ -385,8 +380,8 @@ int mh_db_splice(mh_ctx* ctx, int op, int model, const float* desc, const float*
     int rc = ensure_stage(ctx, (size_t)n_rows);
     if (rc) return rc;
     float* sd = ctx->db_stage;
-    float* sn = sd + ctx->db_stage_cap * DIM;
-    float* sx = sn + ctx->db_stage_cap;
+    float* sn = sd + stage_rows(ctx) * DIM;
+    float* sx = sn + stage_rows(ctx);
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     MH_HIP(ctx, hipMemcpyAsync(sd, desc, (size_t)n_rows * DIM * sizeof(float), kind, ctx->stream));
     MH_HIP(ctx, hipMemcpyAsync(sx, xyz, (size_t)n_rows * 3 * sizeof(float), kind, ctx->stream));

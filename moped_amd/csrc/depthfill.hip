@@ -210,10 +210,10 @@ extern "C" int mh_depth_fill(mh_ctx* ctx, float* depth_xyzn_dev, int width, int 
   const int n_full = width * height;
   // [overflow word, valid count] + the downscaled maps: the context's own (the status outlives the call)
   if (!ctx->df_buf) {
-    MH_HIP(ctx, hipMalloc(&ctx->df_buf, 64 + 2 * sizeof(float) * (size_t)DF_MAX_PIX));
+    MH_HIP(ctx, ctx->df_buf.ensure(64 + 2 * sizeof(float) * (size_t)DF_MAX_PIX, s));
     MH_HIP(ctx, hipMemsetAsync(ctx->df_buf, 0, 64, s));
   }
-  int32_t* words = reinterpret_cast<int32_t*>(ctx->df_buf);
+  int32_t* words = reinterpret_cast<int32_t*>(ctx->df_buf.p);
   float* zfill = reinterpret_cast<float*>(ctx->df_buf + 64);
   float* fdist = zfill + DF_MAX_PIX;
   int scale = scale_factor;   // (the overflow word words[0] is sticky until mh_depth_fill_status reads it)
@@ -277,16 +277,7 @@ extern "C" int mh_depth_fill_host(mh_ctx* ctx, float* depth_xyzn_host, int width
   MH_HIP(ctx, hipSetDevice(ctx->device));
   if (int rc = use_stream(ctx)) return rc;
   const size_t px = (size_t)width * height;
-  if (px > ctx->own_depth_px) {
-    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->own_depth) MH_HIP(ctx, hipFree(ctx->own_depth));
-    if (ctx->own_fill) MH_HIP(ctx, hipFree(ctx->own_fill));
-    ctx->own_depth = ctx->own_fill = nullptr;
-    ctx->own_depth_px = 0;
-    MH_HIP(ctx, hipMalloc(&ctx->own_depth, px * 4 * sizeof(float)));
-    MH_HIP(ctx, hipMalloc(&ctx->own_fill, px * sizeof(float)));
-    ctx->own_depth_px = px;
-  }
+  if (int rc = ensure_own_depth(ctx, px)) return rc;
   MH_HIP(ctx, hipMemcpyAsync(ctx->own_depth, depth_xyzn_host, px * 4 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   if (int rc = mh_depth_fill(ctx, ctx->own_depth, width, height, scale_factor, bilinear, K, ctx->own_fill, scale_used)) return rc;
   MH_HIP(ctx, hipMemcpyAsync(depth_xyzn_host, ctx->own_depth, px * 4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));

@@ -13,7 +13,7 @@ struct FrameState {
   // The working arrays below (counts .. tickets) are carved out of ONE allocation of MH_MAX_BATCH equal arenas: the
   // pointers name frame 0's copy, frame f of a batch that goes through the stages in one launch (FrameBatch, steps.h)
   // has its own at + f * arena_bytes.  Results and count snapshots are slot-indexed arrays outside the arenas.
-  unsigned char* arena = nullptr;
+  mh::DevBuf<unsigned char> arena;
   size_t arena_bytes = 0;
   int n_arenas = 1;   // copies allocated: 1 until the first merged batch of B frames asks for B
   mh::FrameCounts* counts = nullptr;
@@ -46,9 +46,9 @@ struct FrameState {
   float* rf_pts = nullptr;
   int32_t* rf_list = nullptr;
   // packed result {int32 n; int32 pad[3]; mh_object[max_objects]}
-  unsigned char* result = nullptr;
+  mh::DevBuf<unsigned char> result;
   size_t result_bytes = 0;
-  int32_t* snap = nullptr;  // [4] counts snapshot: matches, clusters, objects after POSE, after FILTER
+  mh::DevBuf<int32_t> snap;  // [4] counts snapshot: matches, clusters, objects after POSE, after FILTER
   int task_grid = 32;   // workgroups for the POSE/FILTER launches: follows the task count of the last fetched frame
   int ms_grid = 8;      // ... and of the CLUSTER launch: its cluster count + head room
   // result slots whose match lists are still in the arenas: [list_first, list_first + list_n) (frame_rest, from its call's slot)
@@ -56,7 +56,7 @@ struct FrameState {
   // What the last launches found, written by the kernels' tails into host-visible (pinned, mapped) words and read -- without
   // any synchronisation: a guess is all it is -- when the next launches are sized: [0][f] (cluster, replica) tasks of POSE
   // in frame f of the batch, [1][f] of POSE2, [2][f] models that CLUSTER had to cluster.
-  int32_t* fb = nullptr;
+  mh::PinBuf<int32_t> fb;
   // mh_frame_fetch[_slot]: where the frame's head, counters and first objects land -- pinned, so that the copies are
   // enqueued together and one synchronisation ends them (into pageable memory every one of them blocks: four round
   // trips, ~40 us of one synchronous frame's 550)
@@ -67,14 +67,15 @@ struct FrameState {
     mh::FrameCounts fc;
     int32_t n_feat;
     int32_t img_n[MH_MAX_IMAGES];   // mh_frame_enqueue_images: the images' clamped counts lie right behind the frame's total (one copy)
-  }* fetch_pin = nullptr;
+  };
+  mh::PinBuf<FetchPin> fetch_pin;
   // one frame alone: the closing workgroup of FILTER2 writes the frame's head, counters and objects HERE itself
   // (page-locked, device-writable): mh_frame_fetch then synchronises and reads -- no copy at all
-  mh::FrameHostBlock* host_block = nullptr;
+  mh::PinBuf<mh::FrameHostBlock> host_block;
   bool host_armed = false;   // the frame enqueued last writes host_block (a batch, a frame without FILTER2: no)
   uint32_t host_seq_expect = 0;   // armed enqueues so far = what host_block->seq reads once the last of them is through
   // the fused FILTER / FILTER2 steps' arguments on the device + what the host last stored there (FilterFuse, steps.h)
-  mh::FilterFuseArgs* fuse_dev = nullptr;   // [2]
+  mh::DevBuf<mh::FilterFuseArgs> fuse_dev;   // [2]
   mh::FilterFuseArgs fuse_shadow[2];
   bool fuse_valid[2] = {false, false};
   unsigned int* tickets = nullptr;  // [8] last_workgroup() words: 0 CLUSTER, 1 POSE, 2 FILTER, 3 POSE2, 4 FILTER2
@@ -114,7 +115,6 @@ inline int enter(mh_ctx* ctx) {
 
 // frame_rest.hip
 int ensure_fs(mh_ctx* ctx, int max_m, int max_clusters, int max_objects, int n_models, int n_arenas = 1);
-void free_fs(FrameState* fs);
 int prepare_frame(mh_ctx* ctx, int Q, int q_frame = 0, int frames = 1);
 int frame_rest(mh_ctx* ctx, const FrameCall& c);
 bool merged_batch_ok(const mh_ctx* ctx, const mh_frame_params* prm, bool attrs_ok = false, int maps_for = 0);

@@ -5,26 +5,6 @@
 #include "frame.h"
 
 namespace mh {
-namespace {
-
-template <typename T>
-int dev_alloc(mh_ctx* ctx, T*& p, size_t n) {
-  MH_HIP(ctx, hipMalloc(&p, (n > 0 ? n : 1) * sizeof(T)));
-  return MH_OK;
-}
-
-}  // namespace
-
-void free_fs(FrameState* fs) {
-  if (!fs) return;
-  void* ptrs[] = {fs->arena, fs->result, fs->snap, fs->fuse_dev};
-  for (void* p : ptrs)
-    if (p) hipFree(p);
-  if (fs->fb) hipHostFree(fs->fb);
-  if (fs->fetch_pin) hipHostFree(fs->fetch_pin);
-  if (fs->host_block) hipHostFree(fs->host_block);
-  delete fs;
-}
 
 int ensure_fs(mh_ctx* ctx, int max_m, int max_clusters, int max_objects, int n_models, int n_arenas) {
   FrameState* fs = ctx->fs;
@@ -32,8 +12,8 @@ int ensure_fs(mh_ctx* ctx, int max_m, int max_clusters, int max_objects, int n_m
       fs->max_objects >= max_objects && fs->n_models_cap >= n_models && fs->n_arenas >= n_arenas)
     return MH_OK;
   int task_grid = 0, ms_grid = 0;
-  unsigned char* kept_result = nullptr;
-  int32_t* kept_snap = nullptr;
+  DevBuf<unsigned char> kept_result;
+  DevBuf<int32_t> kept_snap;
   if (fs) {
     n_arenas = std::max(n_arenas, fs->n_arenas);
     task_grid = fs->task_grid;
@@ -44,12 +24,10 @@ int ensure_fs(mh_ctx* ctx, int max_m, int max_clusters, int max_objects, int n_m
     n_models = std::max(n_models, fs->n_models_cap);
     MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (max_objects == fs->max_objects) {   // the result blocks keep their size: frames not fetched yet stay fetchable
-      kept_result = fs->result;
-      kept_snap = fs->snap;
-      fs->result = nullptr;
-      fs->snap = nullptr;
+      kept_result = std::move(fs->result);
+      kept_snap = std::move(fs->snap);
     }
-    free_fs(fs);
+    delete fs;
     ctx->fs = nullptr;
   }
   fs = new FrameState;
@@ -63,9 +41,13 @@ int ensure_fs(mh_ctx* ctx, int max_m, int max_clusters, int max_objects, int n_m
     fs->task_grid = task_grid;
     fs->ms_grid = ms_grid;
   }
-  int rc = 0;
+  hipStream_t s = ctx->stream;
+  hipError_t e = hipSuccess;
+  auto also = [&e](hipError_t next) {   // the first failure is the one reported
+    if (e == hipSuccess) e = next;
+  };
   // two passes over the same list: sizes first (pointers are offsets into a null arena), then the real addresses
-  for (int pass = 0; pass < 2 && !rc; ++pass) {
+  for (int pass = 0; pass < 2 && e == hipSuccess; ++pass) {
     size_t off = 0;
     unsigned char* const base = fs->arena;
     auto carve = [&](auto*& p, size_t n) {
@@ -113,32 +95,31 @@ int ensure_fs(mh_ctx* ctx, int max_m, int max_clusters, int max_objects, int n_m
     carve(fs->rf_list, (size_t)4 * max_m);
     if (pass == 0) {
       fs->arena_bytes = off;
-      rc |= dev_alloc(ctx, fs->arena, off * n_arenas);
+      also(fs->arena.ensure(off * n_arenas, s));
     }
   }
   fs->result_bytes = 16 + sizeof(mh_object) * (size_t)max_objects;
   if (kept_result) {
-    fs->result = kept_result;
-    fs->snap = kept_snap;
+    fs->result = std::move(kept_result);
+    fs->snap = std::move(kept_snap);
   } else {
-    rc |= dev_alloc(ctx, fs->result, fs->result_bytes * MH_MAX_BATCH);
-    if (!rc) MH_HIP(ctx, hipMemsetAsync(fs->result, 0, fs->result_bytes * MH_MAX_BATCH, ctx->stream));   // "0 objects" before the first frame
-    rc |= dev_alloc(ctx, fs->snap, 4 * MH_MAX_BATCH);
-    if (!rc) MH_HIP(ctx, hipMemsetAsync(fs->snap, 0, sizeof(int32_t) * 4 * MH_MAX_BATCH, ctx->stream));   // (a slot fetched before it was written reads zeros)
+    also(fs->result.ensure(fs->result_bytes * MH_MAX_BATCH, s));
+    if (e == hipSuccess) also(hipMemsetAsync(fs->result, 0, fs->result_bytes * MH_MAX_BATCH, s));   // "0 objects" before the first frame
+    also(fs->snap.ensure(4 * MH_MAX_BATCH, s));
+    if (e == hipSuccess) also(hipMemsetAsync(fs->snap, 0, sizeof(int32_t) * 4 * MH_MAX_BATCH, s));   // (a slot fetched before it was written reads zeros)
   }
-  rc |= dev_alloc(ctx, fs->fuse_dev, 2);
-  if (!rc) {
-    if (hipHostMalloc(&fs->fb, 3 * MH_MAX_BATCH * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) rc = MH_ERR_HIP;
-    else std::memset(fs->fb, 0xFF, 3 * MH_MAX_BATCH * sizeof(int32_t));   // -1 = nothing known yet
-    if (hipHostMalloc(&fs->fetch_pin, sizeof(*fs->fetch_pin), hipHostMallocDefault) != hipSuccess) rc = MH_ERR_HIP;
-    if (hipHostMalloc(&fs->host_block, sizeof(*fs->host_block), hipHostMallocDefault) != hipSuccess) rc = MH_ERR_HIP;
-    else std::memset(fs->host_block, 0, sizeof(*fs->host_block));
-  }
-  if (rc) {   // a half-built state must not look valid to the next call
-    free_fs(fs);
+  also(fs->fuse_dev.ensure(2, s));
+  also(fs->fb.ensure(3 * MH_MAX_BATCH, s));
+  also(fs->fetch_pin.ensure(1, s));
+  also(fs->host_block.ensure(1, s));
+  if (e != hipSuccess) {   // a half-built state must not look valid to the next call
+    delete fs;
     ctx->fs = nullptr;
+    ctx->err = std::string("frame buffers: ") + hipGetErrorString(e);
     return MH_ERR_HIP;
   }
+  std::memset(fs->fb, 0xFF, 3 * MH_MAX_BATCH * sizeof(int32_t));   // -1 = nothing known yet
+  std::memset(fs->host_block, 0, sizeof(FrameHostBlock));
   // every frame's tickets, claim table (best), obj_valid / obj_score / obj_npts start at zero
   MH_HIP(ctx, hipMemsetAsync(fs->arena, 0, fs->arena_bytes * n_arenas, ctx->stream));
   fs->host_seq_expect = 0;   // (tickets[7], the device's count of host-block writes, is zero again)
@@ -201,7 +182,7 @@ __global__ void pack_result_kernel(unsigned char* result, const int32_t* n_slots
 }  // namespace
 
 int ensure_linkage_scratch(mh_ctx* ctx, size_t floats) {
-  if (floats <= ctx->lk_scratch_floats) return MH_OK;
+  if (floats <= ctx->lk_scratch.cap) return MH_OK;
   // 3 n^2 floats per (model, frame) problem: 37 MB per frame at 3 000 matches, 0.6 GB for a batch of 16 -- and it grows
   // with the square of what a caller reserves.  Bounded per context (mh_set_linkage_scratch_limit, default 4 GiB)
   // with an error the caller can act on instead of an allocation that takes the device's memory from the other slots.
@@ -211,12 +192,7 @@ int ensure_linkage_scratch(mh_ctx* ctx, size_t floats) {
                "reserved, or mh_set_linkage_scratch_limit)";
     return MH_ERR_CAPACITY;
   }
-  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->lk_scratch) MH_HIP(ctx, hipFree(ctx->lk_scratch));
-  ctx->lk_scratch = nullptr;
-  ctx->lk_scratch_floats = 0;
-  MH_HIP(ctx, hipMalloc(&ctx->lk_scratch, floats * sizeof(float)));
-  ctx->lk_scratch_floats = floats;
+  MH_HIP(ctx, ctx->lk_scratch.ensure(floats, ctx->stream));
   return MH_OK;
 }
 
@@ -229,29 +205,13 @@ static int ensure_rule_buffers(mh_ctx* ctx, int patches, int Q, int frames) {
     return MH_ERR_CAPACITY;
   }
   Q *= frames;
-  if (patches * frames > rs.patches_cap) {
-    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (rs.inv_size) MH_HIP(ctx, hipFree(rs.inv_size));
-    rs.inv_size = nullptr;
-    MH_HIP(ctx, hipMalloc(&rs.inv_size, sizeof(double) * patches * frames));
-    rs.patches_cap = patches * frames;
-  }
+  MH_HIP(ctx, rs.inv_size.ensure((size_t)(patches * frames), ctx->stream));
   const size_t need = (size_t)std::max(ctx->n_models, 1) * patches * frames;
-  if (need > rs.cnt_cap) {
-    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (rs.cnt) MH_HIP(ctx, hipFree(rs.cnt));
-    rs.cnt = nullptr;
-    MH_HIP(ctx, hipMalloc(&rs.cnt, sizeof(int32_t) * need));
+  if (need > rs.cnt.cap) {
+    MH_HIP(ctx, rs.cnt.ensure(need, ctx->stream));
     MH_HIP(ctx, hipMemsetAsync(rs.cnt, 0, sizeof(int32_t) * need, ctx->stream));
-    rs.cnt_cap = need;
   }
-  if (Q > rs.keep_cap) {
-    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (rs.keep1) MH_HIP(ctx, hipFree(rs.keep1));
-    rs.keep1 = nullptr;
-    MH_HIP(ctx, hipMalloc(&rs.keep1, (size_t)Q));
-    rs.keep_cap = Q;
-  }
+  MH_HIP(ctx, rs.keep1.ensure((size_t)std::max(Q, 0), ctx->stream));
   return MH_OK;
 }
 
@@ -335,7 +295,7 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
     if (batch_n == 1) ms_grid = std::max(ms_grid, std::min(fs->ms_grid, 8));
   }
   if (ms_grid_env >= 0) ms_grid = ms_grid_env;
-  const bool multi = ctx->q_img && ctx->n_images > 1 && ctx->cams_dev;
+  const bool multi = ctx->q_img && ctx->n_images > 1 && ctx->cams_view;
   DepthImage dimg = ctx->depth_img;   // as the setter left it, or with the frame's own map of a batch that has one per frame
   if (c.img) {
     dimg.img = c.img;
@@ -387,7 +347,7 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
     rules.patch = rs.patch;
     rules.pw = pw;
     rules.ph = ph;
-    if (rs.ratio_table && rs.table_models >= nm) rules.ratio_table = reinterpret_cast<const float4*>(rs.ratio_table);
+    if (rs.ratio_table && rs.table_models >= nm) rules.ratio_table = reinterpret_cast<const float4*>(rs.ratio_table.p);
     rules.max_depth = rs.max_depth;
     rules.default_depth = rs.default_depth;
     rules.cauchy_scale = rs.cauchy_scale;
@@ -412,7 +372,7 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
     int rc = ensure_linkage_scratch(ctx, need * (size_t)std::max(1, batch_n));
     if (rc) return rc;
     launch_linkage_models(fs->m_corr, reinterpret_cast<const float*>(fs->m_depth), fs->model_off, nm, dimg,
-                          ctx->linkage, ctx->lk_scratch, batch_n > 1 ? need : ctx->lk_scratch_floats, fs->ms_members,
+                          ctx->linkage, ctx->lk_scratch, batch_n > 1 ? need : ctx->lk_scratch.cap, fs->ms_members,
                           fs->ms_cl_start, fs->ms_ncl, fs->max_clusters, fs->cl_model, fs->cl_begin, fs->cl_count,
                           fs->n_clusters, snap, fs->counts, fs->tickets + 0, s, ms_grid, b1, maps,
                           fs->fb + 2 * MH_MAX_BATCH);
@@ -432,7 +392,7 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
   stamp(ctx, 3);
   PoseImages img1, img2;   // POSE works on the (model, image, query) copy, POSE2 on FILTER's clusters over the match lists
   if (multi) {
-    img1.cams = img2.cams = ctx->cams_dev;
+    img1.cams = img2.cams = ctx->cams_view;
     img1.n_images = img2.n_images = ctx->n_images;
     img1.img_of = fs->mi_img;
     img2.img_of = fs->m_img;
@@ -446,7 +406,7 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
   FilterBuffers fb = make_fb(fs, nm);
   if (multi) {
     fb.m_img = fs->m_img;
-    fb.cams = ctx->cams_dev;
+    fb.cams = ctx->cams_view;
     fb.n_images = ctx->n_images;
   }
   const bool fused = fuse_filter && prm->run_stage2 && !ctx->timing && !stepped;   // (stage timing wants the steps apart)
@@ -558,6 +518,6 @@ int prepare_frame(mh_ctx* ctx, int Q, int q_frame, int frames) {
 }  // namespace mh
 
 extern "C" void mh_free_frame_state(mh_ctx* ctx) {
-  mh::free_fs(ctx->fs);
+  delete ctx->fs;
   ctx->fs = nullptr;
 }

@@ -27,10 +27,10 @@ struct FixPos {
 struct UndMap {
   int width = 0, height = 0;
   float K[4] = {}, dist[4] = {};
-  float* mapx = nullptr;   // [height][width]
-  float* mapy = nullptr;
-  FixPos* fix = nullptr;
-  size_t cap = 0;          // pixels allocated
+  DevBuf<float> mapx;      // [height][width]
+  DevBuf<float> mapy;
+  DevBuf<FixPos> fix;
+  size_t cap = 0;          // pixels every one of the three holds
   uint64_t used = 0;       // LRU stamp; 0 = empty
 };
 
@@ -108,20 +108,6 @@ __global__ void remap_kernel(RemapImages imgs, int w, int h) {
   imgs.dst[blockIdx.z][p] = (uint8_t)((s + (1 << 14)) >> 15);
 }
 
-template <typename T>
-int grow(mh_ctx* ctx, T*& p, size_t& cap, size_t n) {
-  if (n <= cap) return MH_OK;
-  if (p) {
-    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));   // earlier work on the stream may still read it
-    hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  MH_HIP(ctx, hipMalloc(&p, n * sizeof(T)));
-  cap = n;
-  return MH_OK;
-}
-
 bool finite4(const float* v) {
   for (int k = 0; k < 4; ++k)
     if (!std::isfinite(v[k])) return false;
@@ -148,17 +134,8 @@ int check_camera(mh_ctx* ctx, const char* what, int width, int height, const flo
 struct UndistortState {
   UndMap maps[UND_ENTRIES];
   uint64_t tick = 0;
-  uint8_t* in = nullptr;    // mh_undistort: the host image
-  size_t in_cap = 0;
-  uint8_t* out = nullptr;   // mh_undistort's result; the resident path's undistorted image(s)
-  size_t out_cap = 0;
-  ~UndistortState() {
-    for (UndMap& m : maps)
-      for (void* p : {(void*)m.mapx, (void*)m.mapy, (void*)m.fix})
-        if (p) hipFree(p);
-    if (in) hipFree(in);
-    if (out) hipFree(out);
-  }
+  DevBuf<uint8_t> in;    // mh_undistort: the host image
+  DevBuf<uint8_t> out;   // mh_undistort's result; the resident path's undistorted image(s)
 };
 
 namespace {
@@ -180,16 +157,11 @@ int get_map(mh_ctx* ctx, int width, int height, const float* K, const float* dis
   }
   const size_t n = (size_t)width * height;
   if (n > slot->cap) {
-    if (slot->cap) MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (void* p : {(void*)slot->mapx, (void*)slot->mapy, (void*)slot->fix})
-      if (p) hipFree(p);
-    slot->mapx = slot->mapy = nullptr;
-    slot->fix = nullptr;
     slot->cap = 0;
     slot->used = 0;
-    MH_HIP(ctx, hipMalloc(&slot->mapx, n * sizeof(float)));
-    MH_HIP(ctx, hipMalloc(&slot->mapy, n * sizeof(float)));
-    MH_HIP(ctx, hipMalloc(&slot->fix, n * sizeof(FixPos)));
+    MH_HIP(ctx, slot->mapx.ensure(n, ctx->stream));
+    MH_HIP(ctx, slot->mapy.ensure(n, ctx->stream));
+    MH_HIP(ctx, slot->fix.ensure(n, ctx->stream));
     slot->cap = n;
   }
   slot->width = width;
@@ -243,7 +215,7 @@ int undistort_frame(mh_ctx* ctx, const uint8_t* const* gray_dev, int n, int widt
   if (int rc = get_map(ctx, width, height, K, ctx->und_dist, &m)) return rc;
   const size_t px = (size_t)width * height;
   UndistortState* st = ctx->und;
-  if (int rc = grow(ctx, st->out, st->out_cap, px * n)) return rc;
+  MH_HIP(ctx, st->out.ensure(px * n, ctx->stream));
   uint8_t* dst[MH_MAX_BATCH];
   for (int f = 0; f < n; ++f) dst[f] = st->out + f * px;
   if (int rc = launch_remap(ctx, m, gray_dev, dst, n)) return rc;
@@ -264,7 +236,7 @@ int undistort_frame_images(mh_ctx* ctx, const uint8_t* const* gray_dev, int n, i
     if (int rc = get_map(ctx, width, height, cams[i].K, dist[i], &maps[i])) return rc;
   const size_t px = (size_t)width * height;
   UndistortState* st = ctx->und;
-  if (int rc = grow(ctx, st->out, st->out_cap, px * n)) return rc;
+  MH_HIP(ctx, st->out.ensure(px * n, ctx->stream));
   uint8_t* dst[MH_MAX_BATCH];
   for (int f = 0; f < n; ++f) dst[f] = st->out + f * px;
   if (int rc = launch_remap(ctx, maps, n_cams, gray_dev, dst, n)) return rc;
@@ -306,8 +278,8 @@ int mh_undistort(mh_ctx* ctx, const uint8_t* gray_host, uint8_t* out_host, int w
   if (int rc = get_map(ctx, width, height, K, dist, &m)) return rc;
   UndistortState* st = ctx->und;
   const size_t px = (size_t)width * height;
-  if (int rc = grow(ctx, st->in, st->in_cap, px)) return rc;
-  if (int rc = grow(ctx, st->out, st->out_cap, px)) return rc;
+  MH_HIP(ctx, st->in.ensure(px, ctx->stream));
+  MH_HIP(ctx, st->out.ensure(px, ctx->stream));
   MH_HIP(ctx, hipMemcpyAsync(st->in, gray_host, px, hipMemcpyHostToDevice, ctx->stream));
   const uint8_t* src = st->in;
   uint8_t* dst = st->out;

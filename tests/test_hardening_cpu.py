@@ -34,3 +34,13 @@ def test_model_loaders_survive_a_mutation_fuzz_under_asan_and_ubsan():
 def test_plugin_headers_compile_against_the_references_own_moped_hpp():
     out = subprocess.run(["make", "-s", "-B", "-C", HOST, "check_ref"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "compile against the reference's moped.hpp" in out.stdout, (out.stdout, out.stderr[-3000:])
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_owning_buffer_type_holds_its_growth_rule_under_asan_and_ubsan():
+    # csrc/devbuf.h against counting stand-ins for the runtime calls (moped_amd/host/devbuf_test.cpp): no call within the
+    # capacity, one synchronisation before a held block is replaced, empty after a failed allocation and after a move,
+    # every block freed once -- a double free or a leak is a sanitizer report
+    out = subprocess.run(["make", "-s", "-B", "-C", HOST, "devbuf_check"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
+    assert "devbuf_test: no finding" in out.stdout, out.stdout
