@@ -254,6 +254,12 @@ int mh_match_query_candidates(mh_ctx* ctx, int Q, uint32_t* out);
  * pointers are device memory; work is enqueued on the context's stream. */
 int mh_match_local_dev(mh_ctx* ctx, const float* qn_dev, const float* qnorm_dev, int Q,
                        int32_t* idx1_dev, float* d1_dev, float* d2_dev);
+/* mh_match_local_dev for Q rows of capacity of which the first min(Q, *q_count_dev) are queries, the count read on the
+ * device (as the image frames have it behind FEAT): the rows behind the count get idx -1, d1 = d2 = inf without being
+ * searched.  q_expected: the host's estimate of the count (sizes the launches), 0 = Q. */
+int mh_match_local_counted_dev(mh_ctx* ctx, const float* qn_dev, const float* qnorm_dev, int Q,
+                               const int32_t* q_count_dev, int q_expected, int32_t* idx1_dev, float* d1_dev,
+                               float* d2_dev);
 int mh_match_merge_dev(mh_ctx* ctx, const int32_t* idx1_s_dev, const float* d1_s_dev,
                        const float* d2_s_dev, int n_shards, int Q,
                        int32_t* idx1_dev, float* d1_dev, float* d2_dev);

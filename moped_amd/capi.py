@@ -97,7 +97,7 @@ class mh_depth_rules(C.Structure):
 
 EXPORTS = [
     "mh_create", "mh_destroy", "mh_last_error", "mh_set_stream", "mh_synchronize", "mh_reserve",
-    "mh_db_upload", "mh_db_size", "mh_normalize", "mh_match", "mh_normalize_match", "mh_match_local_dev",
+    "mh_db_upload", "mh_db_size", "mh_normalize", "mh_match", "mh_normalize_match", "mh_match_local_dev", "mh_match_local_counted_dev",
     "mh_match_merge_dev", "mh_normalize_dev", "mh_meanshift", "mh_meanshift_batch", "mh_pose_ransac", "mh_pose_ransac_depth",
     "mh_frame_set_depth", "mh_project_test",
     "mh_filter", "mh_frame_default_params", "mh_frame_enqueue", "mh_frame_set_depth_image", "mh_frame_enqueue_match_local",
@@ -176,6 +176,8 @@ def load():
     L.mh_match.argtypes = [vp, vp, i32, f32, vp, vp, vp, vp]
     L.mh_normalize_match.argtypes = [vp, vp, i32, f32, vp, vp, vp, vp]
     L.mh_match_local_dev.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+    if hasattr(L, "mh_match_local_counted_dev"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
+        L.mh_match_local_counted_dev.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp]
     L.mh_match_merge_dev.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp]
     L.mh_normalize_dev.argtypes = [vp, vp, vp, i32]
     L.mh_meanshift.argtypes = [vp, vp, i32, i32, f32, f32, i32, i32, vp, vp, C.POINTER(C.c_int32)]
@@ -1486,6 +1488,12 @@ class Context:
         self._ck(self.L.mh_match_local_dev(self.h, C.c_void_p(qn_ptr), C.c_void_p(qnorm_ptr), Q,
                                            C.c_void_p(idx_ptr), C.c_void_p(d1_ptr), C.c_void_p(d2_ptr)),
                  "mh_match_local_dev")
+
+    def match_local_counted_dev(self, qn_ptr, qnorm_ptr, Q, q_count_ptr, q_expected, idx_ptr, d1_ptr, d2_ptr):
+        """match_local_dev for Q rows of capacity, the number of queries among them read on the device."""
+        self._ck(self.L.mh_match_local_counted_dev(self.h, C.c_void_p(qn_ptr), C.c_void_p(qnorm_ptr), Q, C.c_void_p(q_count_ptr),
+                                                   int(q_expected), C.c_void_p(idx_ptr), C.c_void_p(d1_ptr), C.c_void_p(d2_ptr)),
+                 "mh_match_local_counted_dev")
 
     def match_merge_dev(self, idx_s_ptr, d1_s_ptr, d2_s_ptr, n_shards, Q, idx_ptr, d1_ptr, d2_ptr):
         self._ck(self.L.mh_match_merge_dev(self.h, C.c_void_p(idx_s_ptr), C.c_void_p(d1_s_ptr),

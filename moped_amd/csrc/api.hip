@@ -112,6 +112,7 @@ int ctx_match(mh_ctx* ctx, const float* qn, const float* qnorm, int Q, int32_t* 
       ++ctx->mev_used;
     }
     ctx->sbuf.big = ctx->lane_stream;
+    ctx->sbuf.n_cus = ctx->n_cus;
     ctx->sbuf.ev_in = ctx->lane_in;
     ctx->sbuf.ev_out = ctx->lane_out;
     launch_match_screen(qn, qnorm, Q, ctx->db_desc, ctx->db_norm, ctx->N, ctx->rmap, ctx->sdb, ctx->sbuf, idx1, d1,
@@ -158,6 +159,7 @@ int mh_create(int device, mh_ctx** out) {
   mh_ctx* ctx = new (std::nothrow) mh_ctx;
   if (!ctx) return MH_ERR_HIP;
   ctx->device = device;
+  ctx->n_cus = prop.multiProcessorCount;
   // The context's own stream is created on first use (mh_use_stream): a host that
   // installs its own stream with mh_set_stream never takes a hardware queue for it.
   ctx->stream = nullptr;
@@ -477,6 +479,19 @@ int mh_match_local_dev(mh_ctx* ctx, const float* qn_dev, const float* qnorm_dev,
   MH_HIP(ctx, hipSetDevice(ctx->device));
   if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
   int rc = ctx_match(ctx, qn_dev, qnorm_dev, Q, idx1_dev, d1_dev, d2_dev);
+  if (rc) return rc;
+  MH_HIP(ctx, hipGetLastError());
+  return MH_OK;
+}
+
+int mh_match_local_counted_dev(mh_ctx* ctx, const float* qn_dev, const float* qnorm_dev, int Q, const int32_t* q_count_dev,
+                               int q_expected, int32_t* idx1_dev, float* d1_dev, float* d2_dev) {
+  if (!ctx || Q < 0 || q_expected < 0 || !q_count_dev || (Q > 0 && (!qn_dev || !qnorm_dev || !idx1_dev || !d1_dev || !d2_dev)))
+    return MH_ERR_ARG;
+  if (Q == 0) return MH_OK;
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
+  int rc = ctx_match(ctx, qn_dev, qnorm_dev, Q, idx1_dev, d1_dev, d2_dev, q_count_dev, q_expected);
   if (rc) return rc;
   MH_HIP(ctx, hipGetLastError());
   return MH_OK;

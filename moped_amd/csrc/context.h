@@ -116,6 +116,7 @@ struct mh_lane {
 
 struct mh_ctx {
   int device = 0;
+  int n_cus = 0;   // compute units of the device (mh_create)
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   std::string err;

@@ -32,6 +32,7 @@
 // touch all 64 banks once).  Queries sit on the accumulator's lane axis, rows on its register axis:
 // a lane's 16 values of a 32x32 block are 16 rows of ONE query, so the running maxima are lane-local
 // v_max3_f32 (8 per block) and only a lane with a hit looks at individual values.
+#include <type_traits>
 #include <hip/hip_fp16.h>
 
 #include <algorithm>
@@ -1221,7 +1222,11 @@ __device__ __forceinline__ void merge(Best& a, float ob1, float ob2, int oi1) { 
 // One wavefront per query; every lane runs the canonical chain of one candidate row at a time:
 // dot = fmaf chain over k = 0..127 from 0, dist = max(0, fmaf(-2, dot, qq + dd)).  The query's coordinates are
 // wave-uniform (LDS broadcast reads), the row comes straight from HBM / the Infinity Cache, 16 bytes per load.
-constexpr int RS_WAVES = 4;          // queries per workgroup
+constexpr int RS_WAVES = 4;          // wavefronts per workgroup, one query each
+#ifdef MH_EXPERIMENTS
+constexpr int RS_WAVES_FAT = 16;     // ... of a chip-filling launch's fat workgroups, two of which hold a compute unit
+constexpr int RS_FAT_K = 2;          // ... and that many of them per compute unit are the whole grid (their wavefronts walk the queries)
+#endif
 constexpr int RS_MAXC = 1024;        // candidate rows a query may have before it is searched by brute force
 constexpr int RS_STAGE = 8;          // candidate rows staged through LDS (8 x 512 bytes = the candidate list's 4 KB)
 static_assert(RS_STAGE * DIM * 4 <= RS_MAXC * 4 && RS_STAGE % 2 == 0 && RS_STAGE <= 32, "staged rows live in the candidate list's LDS");
@@ -1280,47 +1285,122 @@ __device__ __forceinline__ v4f sample_pair_values(const float* __restrict__ q_ld
   return acc;
 }
 
-// (eight wavefronts per SIMD -- what the kernel's LDS allows -- instead of the five its 82 VGPRs would: 64 VGPRs and four
-// spilled registers; the kernel lives on queries in flight.  Config 1: 0.096 -> 0.085 ms)
-__global__ __launch_bounds__(64 * RS_WAVES) __attribute__((amdgpu_waves_per_eu(8, 8))) void rescore_kernel(
-    const float* __restrict__ qn, const float* __restrict__ qnorm, const uint8_t* __restrict__ qbad, int Q,
-    const int32_t* __restrict__ q_count, const float* __restrict__ db, const float* __restrict__ dnorm, int N,
-    RowMap rmap, uint2* __restrict__ recs, int n_slots, int32_t* __restrict__ ovf_cnt, uint2* __restrict__ ovf,
-    int ovf_cap, float dmax, const float* __restrict__ tau, float spread, int32_t* __restrict__ idx1, float* __restrict__ d1, float* __restrict__ d2,
-    unsigned int* __restrict__ stats, int32_t zero_idx, float zero_d1, float zero_d2, SampleGeom g,
-    const unsigned int* __restrict__ inc, unsigned int* __restrict__ inc_count, const _Float16* __restrict__ dbh,
-    const float* __restrict__ dneg) {
-  MH_TRACE_SCOPE(mh::TK_PASS_C);
-  __shared__ __attribute__((aligned(16))) float q_s[RS_WAVES][DIM];
-  __shared__ __attribute__((aligned(16))) int cand_s[RS_WAVES][RS_MAXC];   // the candidate list, then RS_STAGE rows of them
-  __shared__ int ncand_s[RS_WAVES];
-  __shared__ int samp_s[RS_WAVES][SC_SA_SLOTS];   // row0 of the sampled tiles' records that survive the thinning
-  __shared__ int nsamp_s[RS_WAVES];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int q = blockIdx.x * RS_WAVES + wave;
-  if (q >= Q) return;
-  // Everything the query's wavefront reads before it knows its candidates is asked for HERE, in one go: the kernel lives
-  // on round trips (a query is ~a dozen loads and ~400 fmaf), and loads issued behind the branches below each cost one.
-  // the query's slots in scan order: pass B's n_slots, then (one-sweep launches) the g.sa_slots of the sampled tiles'
-  // records, which lie behind pass B's SC_SLOTS_MAX; then the overflow list
-  constexpr int RS_ITERS = (SC_SLOT_PITCH + SCREEN_OVF_CAP + 63) / 64;
-  uint2* mine = recs + (size_t)q * SC_SLOT_PITCH;
-  const int n_own = n_slots + g.sa_slots;
-  auto slot_at = [&](int j) -> uint2& { return mine[j < n_slots ? j : SC_SLOTS_MAX + (j - n_slots)]; };
-  uint2 recv[RS_ITERS];
+// (eight wavefronts per SIMD -- what the kernel's LDS allows -- instead of the five its 82 VGPRs would; the kernel lives on
+// queries in flight.  Config 1: 0.096 -> 0.085 ms)
+//
+// Launch shape.  WAVES wavefronts per workgroup, each with an LDS region of its own (no workgroup barrier anywhere: only
+// wave_lds_sync).  Wavefront w of the grid's W = gridDim.x * WAVES takes the queries w, w + W, w + 2 W, ...  The product
+// launches a wavefront per query in workgroups of four, so the loop runs once.  The other shapes exist in experiment
+// builds (launch_match_screen's MH_PASSC_* switches): workgroups of 16 wavefronts, two per compute unit (or of 12 at six
+// wavefronts per SIMD and 80 registers), a grid of RS_FAT_K such workgroups per compute unit whose wavefronts walk, and
+// PF = what a walking wavefront asks for one query ahead, at the top of the iteration before (0 = nothing; 1 = the next
+// query's record slots; 2 = the slots, the scalars and the row; a query's slots are written by its own wavefront alone,
+// so reading them early races with nothing).  None of them paid on top of the product's shape (DESIGN.md 4,
+// profiles/passc_persistent_ab.txt).  Where wavefronts walk the striding is static, no ticket: a query that is searched by
+// brute force (an overflowed list, a query f16 cannot hold: the whole DB on one wavefront) delays the later queries of
+// its own wavefront and nobody else's; tests/test_gpu_passc_persistent.py puts such queries into the first, second and
+// third trip of the same wavefronts.
+constexpr int RS_ITERS = (SC_SLOT_PITCH + SCREEN_OVF_CAP + 63) / 64;
+struct RsScalars {   // what a query's wavefront reads besides its slots before it knows its candidates
+  int bad;
+  float nq, tau_q;
+  int n_ovf;
+  unsigned incw;
+  float2 qv;
+};
+constexpr size_t rs_lds_bytes(int waves) { return (size_t)waves * (DIM * 4 + RS_MAXC * 4 + SC_SA_SLOTS * 4 + 8); }
+
+struct RsArgs {
+  const float* qn;
+  const float* qnorm;
+  const uint8_t* qbad;
+  int Q;
+  const int32_t* q_count;
+  const float* db;
+  const float* dnorm;
+  int N;
+  RowMap rmap;
+  uint2* recs;
+  int n_slots;
+  int32_t* ovf_cnt;
+  uint2* ovf;
+  int ovf_cap;
+  float dmax;
+  const float* tau;
+  float spread;
+  int32_t* idx1;
+  float* d1;
+  float* d2;
+  unsigned int* stats;
+  int32_t zero_idx;
+  float zero_d1, zero_d2;
+  SampleGeom g;
+  const unsigned int* inc;
+  unsigned int* inc_count;
+  const _Float16* dbh;
+  const float* dneg;
+};
+// The kernel's arguments as an iteration of the loop reads them: from the kernel argument segment (the one struct is all
+// of it), through a pointer the compiler cannot see through.  Read once in front of the loop they would all live in scalar
+// registers across it -- some sixty, with the loop's own more than a wavefront has: 74 of them spilled, and 46 vector
+// registers after them -- where the kernel without a loop fetches each next to its use; so does every iteration now.
+typedef const __attribute__((address_space(4))) RsArgs* RsArgsPtr;
+__device__ __forceinline__ RsArgsPtr rs_args() {
+  RsArgsPtr p = (RsArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return p;
+}
+
+// a query's slots in scan order: pass B's n_slots, then (one-sweep launches) the sa_slots of the sampled tiles' records,
+// which lie behind pass B's SC_SLOTS_MAX; then the overflow list
+__device__ __forceinline__ void rs_load_slots(const uint2* recs, int n_slots, int sa_slots, int q, int lane, uint2 (&rv)[RS_ITERS]) {
+  const uint2* theirs = recs + (size_t)q * SC_SLOT_PITCH;
+  const int n_own = n_slots + sa_slots;
 #pragma unroll
   for (int it = 0; it < RS_ITERS; ++it) {
     const int j = it * 64 + lane;
-    recv[it] = j < n_own ? slot_at(j) : make_uint2(0u, 0u);
+    rv[it] = j < n_own ? theirs[j < n_slots ? j : SC_SLOTS_MAX + (j - n_slots)] : make_uint2(0u, 0u);
   }
-  const int Qe = q_count ? min(Q, *q_count) : Q;
-  const int bad = qbad[q];
-  const float nq = qnorm[q];
-  const float tau_q = tau[q];
-  const int n_ovf = ovf_cnt[q];
-  const unsigned incw = inc ? inc[q] : 0u;
-  const float2 qv = reinterpret_cast<const float2*>(qn + (size_t)q * DIM)[lane];
+}
+// (qbad, qnorm, tau, inc: written by the launches before this one, read-only here -- read as constant memory they come
+// through the scalar unit, all in flight at once, where a global load of a wave-uniform address inside the loop is waited
+// for on the spot.  So does the query's overflow count: its wavefront is the only one to write it, and does so after this
+// read, so whichever state of the cache line the scalar cache holds has the query's own word right.  The compiler takes
+// constant memory for never written: what keeps this read in front of the kernel's own `ovf_cnt[q] = 0` is not the address
+// space but the data -- that store is made only `if (n_ovf ...)`, on the value read here -- and no word is read again after
+// it was written.  `inc` may be absent.)
+#define RS_CONST(T, p) ((const __attribute__((address_space(4))) T*)(p))
+__device__ __forceinline__ RsScalars rs_load_scalars(const uint8_t* qbad, const float* qnorm, const float* tau, const int32_t* ovf_cnt,
+                                                     const unsigned int* inc, const float* qn, int q, int lane) {
+  RsScalars v;
+  v.qv = reinterpret_cast<const float2*>(qn + (size_t)q * DIM)[lane];
+  v.n_ovf = RS_CONST(int32_t, ovf_cnt)[q];
+  const unsigned w = RS_CONST(unsigned int, inc ? inc : reinterpret_cast<const unsigned int*>(tau))[q];
+  v.bad = (RS_CONST(unsigned int, qbad)[q >> 2] >> (8 * (q & 3))) & 0xFFu;   // (the byte's word: the scalar unit reads no bytes; [q_pad], q_pad % 256 == 0)
+  v.nq = RS_CONST(float, qnorm)[q];
+  v.tau_q = RS_CONST(float, tau)[q];
+  v.incw = inc ? w : 0u;
+  return v;
+}
+
+// One query on one wavefront: `recv` its slots and `sc` what else it reads first (asked for by the caller), the four LDS
+// regions the wavefront's own.
+__device__ __forceinline__ void rescore_query(
+    int q, int lane, float* q_sw, int* cand_sw, int* samp_sw, int* ncand_sw, int* nsamp_sw, uint2 (&recv)[RS_ITERS], const RsScalars sc, int Qe,
+    const float* __restrict__ db, const float* __restrict__ dnorm, int N,
+    RowMap rmap, uint2* __restrict__ recs, int n_slots, int32_t* __restrict__ ovf_cnt, uint2* __restrict__ ovf,
+    int ovf_cap, float dmax, float spread, int32_t* __restrict__ idx1, float* __restrict__ d1, float* __restrict__ d2,
+    unsigned int* __restrict__ stats, int32_t zero_idx, float zero_d1, float zero_d2, SampleGeom g,
+    unsigned int* __restrict__ inc_count, const _Float16* __restrict__ dbh, const float* __restrict__ dneg) {
+  uint2* mine = recs + (size_t)q * SC_SLOT_PITCH;
+  const int n_own = n_slots + g.sa_slots;
+  auto slot_at = [&](int j) -> uint2& { return mine[j < n_slots ? j : SC_SLOTS_MAX + (j - n_slots)]; };
+  const int bad = sc.bad;
+  const float nq = sc.nq;
+  const float tau_q = sc.tau_q;
+  const int n_ovf = sc.n_ovf;
+  const unsigned incw = sc.incw;
+  const float2 qv = sc.qv;
   // (the values are wanted HERE: without this the compiler moves the loads behind the tests below, one round trip each)
   asm volatile("" ::"v"(bad), "v"(nq), "v"(tau_q), "v"(n_ovf), "v"(incw), "v"(qv.x), "v"(qv.y), "s"(Qe));
   if (q >= Qe) {   // no such query in this frame: "no neighbour", like combine_splits_kernel (pass B left it no records)
@@ -1348,12 +1428,13 @@ __global__ __launch_bounds__(64 * RS_WAVES) __attribute__((amdgpu_waves_per_eu(8
     }
     return;
   }
+  wave_lds_sync();   // the iteration before has read its query row and its staged rows
   if (lane == 0) {
-    ncand_s[wave] = 0;
-    nsamp_s[wave] = 0;
+    *ncand_sw = 0;
+    *nsamp_sw = 0;
   }
-  q_s[wave][2 * lane] = qv.x;
-  q_s[wave][2 * lane + 1] = qv.y;
+  q_sw[2 * lane] = qv.x;
+  q_sw[2 * lane + 1] = qv.y;
   // ---- records -> candidate row list in LDS; the slots read are emptied for the next frame ----
   bool brute = n_ovf > ovf_cap || bad == 1;
   int n_cand = 0;
@@ -1415,41 +1496,41 @@ __global__ __launch_bounds__(64 * RS_WAVES) __attribute__((amdgpu_waves_per_eu(8
       // a sampled tile's record names no rows (its mask is all 8): which of them lie above tau is found below, for the
       // records that are still here
       if (bits && (rec.x & SC_REC_SAMPLE)) {
-        const int w = atomicAdd(&nsamp_s[wave], 1);
-        if (w < SC_SA_SLOTS) samp_s[wave][w] = row0;
+        const int w = atomicAdd(nsamp_sw, 1);
+        if (w < SC_SA_SLOTS) samp_sw[w] = row0;
         bits = 0;
       }
       // candidates in any order (the exact top-2 below breaks ties by row number): an LDS counter hands out places
       while (bits) {
         const int r = __builtin_ctz(bits);
         bits &= bits - 1;
-        const int w = atomicAdd(&ncand_s[wave], 1);
-        if (w < RS_MAXC) cand_s[wave][w] = row0 + (r & 3) + hi_stride * (r >> 2);
+        const int w = atomicAdd(ncand_sw, 1);
+        if (w < RS_MAXC) cand_sw[w] = row0 + (r & 3) + hi_stride * (r >> 2);
       }
     }
     wave_lds_sync();
     // The surviving sampled records, two per MFMA set: the rows whose screen value -- pass A's own, see sample_pair_values --
     // exceeds tau become candidates, as pass B's rule has it for every other tile; a record none of whose rows does (its
     // packed maximum lay between tau - P and tau) leaves none.
-    const int n_samp = min(nsamp_s[wave], SC_SA_SLOTS), n_pad_rows = (N + SC_TILE - 1) / SC_TILE * SC_TILE;
+    const int n_samp = min(*nsamp_sw, SC_SA_SLOTS), n_pad_rows = (N + SC_TILE - 1) / SC_TILE * SC_TILE;
     for (int p = 0; p < n_samp; p += 2) {
       const bool pair = p + 1 < n_samp;
-      const int rx = samp_s[wave][p], ry = samp_s[wave][pair ? p + 1 : p];
+      const int rx = samp_sw[p], ry = samp_sw[pair ? p + 1 : p];
       if (rx + 19 >= n_pad_rows || ry + 19 >= n_pad_rows) continue;   // (not a block of the DB: never written)
-      const v4f w = sample_pair_values(q_s[wave], dbh, dneg, rx, ry, lane);
+      const v4f w = sample_pair_values(q_sw, dbh, dneg, rx, ry, lane);
       const int grp = lane >> 4;
       if ((lane & 15) == 0 && (grp < 2 || pair)) {
         const int base = (grp < 2 ? rx : ry) + 16 * (grp & 1);
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           if (w[r] > tau_q) {
-            const int at = atomicAdd(&ncand_s[wave], 1);
-            if (at < RS_MAXC) cand_s[wave][at] = base + r;
+            const int at = atomicAdd(ncand_sw, 1);
+            if (at < RS_MAXC) cand_sw[at] = base + r;
           }
       }
     }
     if (n_samp) wave_lds_sync();
-    n_cand = ncand_s[wave];
+    n_cand = *ncand_sw;
     if (n_cand > RS_MAXC) brute = true;
   } else if (n_ovf > ovf_cap) {
     for (int j = lane; j < n_own; j += 64) slot_at(j) = make_uint2(0u, 0u);   // the lists overflowed: empty every slot
@@ -1464,11 +1545,11 @@ __global__ __launch_bounds__(64 * RS_WAVES) __attribute__((amdgpu_waves_per_eu(8
     // per row, all of them in flight at once -- into the LDS the candidate list lay in (chunk c of staged row r at
     // c ^ r: the lanes that run the chains read different banks), and lane r runs row r's chain from there: the same
     // fmaf chain in the same order as exact_dist, its 512 bytes read from LDS instead of in four dependent round trips.
-    const int my_row = lane < n_cand ? cand_s[wave][lane] : -1;
+    const int my_row = lane < n_cand ? cand_sw[lane] : -1;
     const bool my_ok = my_row >= 0 && my_row < N;
     const float my_dn = my_ok ? dnorm[my_row] : 0.f;
     wave_lds_sync();   // every lane holds its candidate: the list's memory is free
-    float4* stage = reinterpret_cast<float4*>(cand_s[wave]);
+    float4* stage = reinterpret_cast<float4*>(cand_sw);
     const int n_st = min(n_cand, RS_STAGE);
     const int half = lane >> 5, c = lane & 31;
     float4 v[RS_STAGE / 2];
@@ -1488,7 +1569,7 @@ __global__ __launch_bounds__(64 * RS_WAVES) __attribute__((amdgpu_waves_per_eu(8
     if (lane < n_st) {
       if (my_ok) {
         float sdot = 0.f;
-        const float4* qs4 = reinterpret_cast<const float4*>(q_s[wave]);
+        const float4* qs4 = reinterpret_cast<const float4*>(q_sw);
 #pragma unroll 8
         for (int k = 0; k < 32; ++k) {
           const float4 x = stage[lane * 32 + (k ^ lane)], y = qs4[k];
@@ -1497,12 +1578,12 @@ __global__ __launch_bounds__(64 * RS_WAVES) __attribute__((amdgpu_waves_per_eu(8
         take(best, fmaxf(fmaf(-2.f, sdot, nq + my_dn), 0.f), my_row);
       }
     } else if (my_ok) {
-      take(best, exact_dist(q_s[wave], db + (size_t)my_row * DIM, nq, my_dn), my_row);
+      take(best, exact_dist(q_sw, db + (size_t)my_row * DIM, nq, my_dn), my_row);
     }
   } else {
     for (int k = lane; k < n_rows; k += 64) {
-      const int row = brute ? k : cand_s[wave][k];
-      if (row >= 0 && row < N) take(best, exact_dist(q_s[wave], db + (size_t)row * DIM, nq, dnorm[row]), row);
+      const int row = brute ? k : cand_sw[k];
+      if (row >= 0 && row < N) take(best, exact_dist(q_sw, db + (size_t)row * DIM, nq, dnorm[row]), row);
     }
   }
   if (incw && !brute) {
@@ -1517,7 +1598,7 @@ __global__ __launch_bounds__(64 * RS_WAVES) __attribute__((amdgpu_waves_per_eu(8
       for (int k = sel0 * SC_TILE + lane; k < sel1 * SC_TILE; k += 64) {
         const int row = (g.tile_first + (k >> 7) * g.tile_stride) * SC_TILE + (k & 127);
         if (((incw >> (28 + ((k & 15) >> 2))) & 1u) && row < N)
-          take(best, exact_dist(q_s[wave], db + (size_t)row * DIM, nq, dnorm[row]), row);
+          take(best, exact_dist(q_sw, db + (size_t)row * DIM, nq, dnorm[row]), row);
       }
     }
     if (lane == 0 && inc_count) atomicAdd(inc_count, 1u);
@@ -1539,6 +1620,69 @@ __global__ __launch_bounds__(64 * RS_WAVES) __attribute__((amdgpu_waves_per_eu(8
     }
   }
 }
+
+// RsArgs is the kernel's ONLY parameter: rs_args() reads it from offset 0 of the kernel argument segment (the assertion
+// behind the kernel holds the signature to that).
+// The product (<4, 0>, a wavefront per query) runs the loop once and keeps its form all the same: it is the form that was
+// measured (profiles/passc_persistent_ab.txt, the row WAVES=4), its arguments fetched next to their uses inside the
+// iteration and no scratch memory; the same per-query code without the loop around it was not measured.
+template <int WAVES, int PF>
+__global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVES == 12 ? 6 : 8, WAVES == 12 ? 6 : 8))) void rescore_kernel(const RsArgs args) {
+  MH_TRACE_SCOPE(mh::TK_PASS_C);
+  // dynamic LDS (sixteen wavefronts' regions are more than the 64 KB a kernel may declare): [WAVES][DIM] query rows,
+  // [WAVES][RS_MAXC] candidate lists (then RS_STAGE rows of them), [WAVES][SC_SA_SLOTS] row0 of the sampled tiles'
+  // records that survive the thinning, the two counters
+  extern __shared__ __attribute__((aligned(16))) unsigned char rs_lds[];
+  const int lane0 = threadIdx.x & 63;
+  const int wave0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int q_first = blockIdx.x * WAVES + wave0, q_stride = (int)gridDim.x * WAVES;
+  if (q_first >= args.Q) return;
+  const int Qe = args.q_count ? min(args.Q, *RS_CONST(int32_t, args.q_count)) : args.Q;   // (the one value an iteration does not read anew)
+  uint2 recv_next[RS_ITERS];
+  RsScalars sc_next = {};
+  if (PF >= 1) rs_load_slots(args.recs, args.n_slots, args.g.sa_slots, q_first, lane0, recv_next);
+  if (PF >= 2) sc_next = rs_load_scalars(args.qbad, args.qnorm, args.tau, args.ovf_cnt, args.inc, args.qn, q_first, lane0);
+  for (int q = q_first;; q += q_stride) {
+    // (what an iteration derives from the lane and the wavefront's number -- addresses, masks -- it derives anew, as it
+    // reads the arguments anew: kept in registers across the loop these values, too, end in scratch memory)
+    int lane = lane0, wave = wave0;
+    asm volatile("" : "+v"(lane), "+s"(wave));
+    float* const q_sw = reinterpret_cast<float*>(rs_lds) + wave * DIM;
+    int* const cand_sw = reinterpret_cast<int*>(rs_lds + (size_t)WAVES * DIM * 4) + wave * RS_MAXC;
+    int* const samp_sw = reinterpret_cast<int*>(rs_lds + (size_t)WAVES * (DIM + RS_MAXC) * 4) + wave * SC_SA_SLOTS;
+    int* const ncand_sw = reinterpret_cast<int*>(rs_lds + (size_t)WAVES * (DIM + RS_MAXC + SC_SA_SLOTS) * 4) + wave;
+    int* const nsamp_sw = ncand_sw + WAVES;
+    const RsArgsPtr A = rs_args();
+    const int Q = A->Q;
+    if (q >= Q) break;
+    // Everything the query's wavefront reads before it knows its candidates is asked for HERE, in one go (or was, an
+    // iteration ago): the kernel lives on round trips (a query is ~a dozen loads and ~400 fmaf), and loads issued behind
+    // the branches of rescore_query each cost one.
+    uint2 recv[RS_ITERS];
+    if (PF >= 1) {
+#pragma unroll
+      for (int it = 0; it < RS_ITERS; ++it) recv[it] = recv_next[it];
+    } else {
+      rs_load_slots(A->recs, A->n_slots, A->g.sa_slots, q, lane, recv);
+    }
+    const RsScalars sc = PF >= 2 ? sc_next : rs_load_scalars(A->qbad, A->qnorm, A->tau, A->ovf_cnt, A->inc, A->qn, q, lane);
+    if (PF >= 1 && q + q_stride < Q) {   // the next query of this wavefront: consumed an iteration from here
+      rs_load_slots(A->recs, A->n_slots, A->g.sa_slots, q + q_stride, lane, recv_next);
+      if (PF >= 2) sc_next = rs_load_scalars(A->qbad, A->qnorm, A->tau, A->ovf_cnt, A->inc, A->qn, q + q_stride, lane);
+    }
+    RowMap rmap;
+    rmap.glo = A->rmap.glo;
+    rmap.llo = A->rmap.llo;
+    rmap.nb = A->rmap.nb;
+    rmap.base = A->rmap.base;
+    const SampleGeom g = {A->g.sa_slots, A->g.pack_bits, A->g.tile_first, A->g.tile_stride, A->g.tiles_base, A->g.tiles_rem, A->g.n_sel};
+    rescore_query(q, lane, q_sw, cand_sw, samp_sw, ncand_sw, nsamp_sw, recv, sc, Qe, A->db, A->dnorm, A->N, rmap, A->recs,
+                  A->n_slots, A->ovf_cnt, A->ovf, A->ovf_cap, A->dmax, A->spread, A->idx1, A->d1, A->d2, A->stats, A->zero_idx,
+                  A->zero_d1, A->zero_d2, g, A->inc_count, A->dbh, A->dneg);
+  }
+}
+static_assert(std::is_same<decltype(&rescore_kernel<RS_WAVES, 0>), void (*)(RsArgs)>::value,
+              "rs_args() reads RsArgs from offset 0 of the kernel argument segment: it must stay the only parameter");
 
 // The screen value of every (query, row) pair of a small problem, by the arithmetic of pass A: one wavefront per
 // (32 queries, 32 rows), operands straight from the f16 images, the accumulator seeded with the rows' -dd/2, the eight
@@ -1872,6 +2016,13 @@ void launch_passes16(ScreenArgs a, int Q, int qe, int n_tiles, int sample, int b
   *geom_out = g;
 }
 
+template <int WAVES, int PF>
+void launch_pass_c(int grid, hipStream_t s, const RsArgs& args) {
+  static DynLds attr;
+  attr.ensure(rescore_kernel<WAVES, PF>, rs_lds_bytes(WAVES));
+  hipLaunchKernelGGL((rescore_kernel<WAVES, PF>), dim3(grid), dim3(64 * WAVES), rs_lds_bytes(WAVES), s, args);
+}
+
 // which kernels a MATCH launch runs on (launch_match_screen): queries per workgroup / 256, and whether the 16x16x32 passes
 struct ShapeChoice {
   int nqb_sel;
@@ -1979,11 +2130,32 @@ void launch_match_screen(const float* qn, const float* qnorm, int Q, const float
     hipEventRecord(sb.ev_out, sbig);
     hipStreamWaitEvent(s, sb.ev_out, 0);
   }
-  // pass C
-  hipLaunchKernelGGL(rescore_kernel, dim3((Q + RS_WAVES - 1) / RS_WAVES), dim3(64 * RS_WAVES), 0, s, qn, qnorm, sb.qbad, Q,
-                     q_count, db, dnorm, N, rmap, sb.recs, n_slots, sb.ovf_cnt, sb.ovf, sb.ovf_cap, sdb.dmax, (const float*)sb.tau, sdb.spread, idx1, d1, d2,
-                     sb.stats, sdb.zero_idx, sdb.zero_d1, sdb.zero_d2, geom, geom.sa_slots > 0 ? (const unsigned int*)sb.inc : nullptr,
-                     sb.inc ? sb.inc + sb.q_pad : nullptr, sdb.dbh, sdb.dneg);
+  // pass C: a wavefront per query, four to a workgroup
+  RsArgs ca;
+  ca.qn = qn; ca.qnorm = qnorm; ca.qbad = sb.qbad; ca.Q = Q; ca.q_count = q_count; ca.db = db; ca.dnorm = dnorm; ca.N = N;
+  ca.rmap = rmap; ca.recs = sb.recs; ca.n_slots = n_slots; ca.ovf_cnt = sb.ovf_cnt; ca.ovf = sb.ovf; ca.ovf_cap = sb.ovf_cap;
+  ca.dmax = sdb.dmax; ca.tau = sb.tau; ca.spread = sdb.spread; ca.idx1 = idx1; ca.d1 = d1; ca.d2 = d2; ca.stats = sb.stats;
+  ca.zero_idx = sdb.zero_idx; ca.zero_d1 = sdb.zero_d1; ca.zero_d2 = sdb.zero_d2; ca.g = geom;
+  ca.inc = geom.sa_slots > 0 ? sb.inc : nullptr; ca.inc_count = sb.inc ? sb.inc + sb.q_pad : nullptr; ca.dbh = sdb.dbh; ca.dneg = sdb.dneg;
+#ifdef MH_EXPERIMENTS
+  // the shapes that were measured against this one (rescore_kernel's comment; scripts/ab_env.sh): MH_PASSC_WAVES = 16 / 12
+  // for the launches of more than two fat workgroups per compute unit (MH_PASSC_FAT_ALL = 1: for every launch), MH_PASSC_K
+  // such workgroups per compute unit as the whole grid (0 = a wavefront per query), MH_PASSC_PREFETCH = 0 / 1 / 2
+  static const int pc_waves = exp_int("MH_PASSC_WAVES", RS_WAVES), pc_k = exp_int("MH_PASSC_K", RS_FAT_K);
+  static const int pc_pf = exp_int("MH_PASSC_PREFETCH", 0), pc_all = exp_int("MH_PASSC_FAT_ALL", 0);
+  const int n_cus = sb.n_cus > 0 ? sb.n_cus : 256;
+  const int fat_waves = pc_waves == 12 ? 12 : RS_WAVES_FAT;
+  if (pc_waves != RS_WAVES && (pc_all || Q > RS_FAT_K * n_cus * RS_WAVES_FAT)) {
+    const int cover = (Q + fat_waves - 1) / fat_waves, grid = pc_k > 0 ? std::min(cover, pc_k * n_cus) : cover;
+    if (fat_waves == 12 && pc_pf == 0) launch_pass_c<12, 0>(grid, s, ca);
+    else if (fat_waves == 12 && pc_pf == 1) launch_pass_c<12, 1>(grid, s, ca);
+    else if (fat_waves == 12) launch_pass_c<12, 2>(grid, s, ca);
+    else if (pc_pf == 0) launch_pass_c<RS_WAVES_FAT, 0>(grid, s, ca);
+    else if (pc_pf == 1) launch_pass_c<RS_WAVES_FAT, 1>(grid, s, ca);
+    else launch_pass_c<RS_WAVES_FAT, 2>(grid, s, ca);
+  } else
+#endif
+  launch_pass_c<RS_WAVES, 0>((Q + RS_WAVES - 1) / RS_WAVES, s, ca);
   if (sb.ev) hipEventRecord(sb.ev[5], s);
 }
 

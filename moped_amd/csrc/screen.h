@@ -39,6 +39,7 @@ struct ScreenBufs {
   // [q_pad] the queries' incomplete words of the one-sweep launches (which lane slots of pass A pass C has to sweep; 0 = none),
   // then one counter: queries that took that sweep since the last mh_match_incomplete(reset)
   unsigned int* inc = nullptr;
+  int n_cus = 0;                   // compute units of the device, 0 = not known (experiment builds: the grid of pass C's walking shapes)
 };
 
 // ---- what a candidate record says about its block (pass B writes it, pass C prunes by it) -------------------------
