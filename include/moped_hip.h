@@ -537,6 +537,19 @@ int mh_frame_set_depth_image_host(mh_ctx* ctx, const float* depth_xyzn_host, con
 int mh_depth_fill(mh_ctx* ctx, float* depth_xyzn_dev, int width, int height, int scale_factor, int bilinear,
                   const float K[4], float* fill_distance_dev, int* scale_used);
 int mh_depth_fill_status(mh_ctx* ctx);
+/* DEPTHFILL of n_frames <= MH_MAX_BATCH maps of one size, each in place with its own distance map, in ONE launch per
+ * stage: what moped3d's pipeline (moped3d/libmoped/src/config.hpp:39, DEPTH_FILL_EXACT_CPU.hpp:268-349) does to every
+ * frame's map, for the frames of a batch at once -- the FIFO wavefront of a map occupies ONE workgroup for as long as its
+ * holes are deep (0.07-0.10 ms for speckle and shallow holes, about 2.4 ms for sensor-like blobs of up to 70 pixels radius
+ * over half the map), the maps of a batch occupy one workgroup each side by side.  Every frame needs a depth map and a
+ * distance map of its own: the frames are filled in place at the same time, the same buffer for two frames -> MH_ERR_ARG.  Every map's result is bit for bit what mh_depth_fill
+ * gives that map alone (the same kernel bodies behind entry points of their own; mh_depth_fill's launches are unchanged).  Asynchronous on the context's stream;
+ * the overflow word is shared and sticky (mh_depth_fill_status reports a ring overflow of any frame of any batch since
+ * the last status).  The downscaled map's 8192-pixel limit -> MH_ERR_CAPACITY before anything is launched;
+ * scale_factor = -1 would need a read-back per map -> MH_ERR_ARG (mh_depth_fill takes it, one map per call).  The
+ * first call sizes the context's scratch for MH_MAX_BATCH frames (2 MiB), so no later batch waits for one in flight. */
+int mh_depth_fill_batch(mh_ctx* ctx, float* const* depth_xyzn_dev, float* const* fill_distance_dev, int n_frames,
+                        int width, int height, int scale_factor, int bilinear, const float K[4]);
 /* The same on host maps (what the DEPTH_FILL_EXACT_HIP plugin calls): upload, fill, both maps back, status. */
 int mh_depth_fill_host(mh_ctx* ctx, float* depth_xyzn_host, int width, int height, int scale_factor, int bilinear,
                        const float K[4], float* fill_distance_host, int* scale_used);
@@ -705,7 +718,9 @@ int mh_frame_fetch_match_reps_slot(mh_ctx* ctx, int slot, int32_t* rep_host, int
 /* For tests, in the style of mh_db_debug_fetch: what the moped3d front end (mh_frame_set_depth_rules + a depth map)
  * left behind for frame `slot` of the last frame / batch, by host-side copies after the stream has drained.
  *   which 0: inv_size, double [pw ph] -- per patch 1.0 / sizeMap (DEPTHFILTER_CPU.hpp:168-178,193)
- *   which 1: keep1, uint8 [Q]         -- DEPTHFILTER's verdict on every feature (feature_density >= 0)
+ *   which 1: keep1, uint8 [Q]         -- DEPTHFILTER's verdict on every feature (feature_density >= 0); a frame from an
+ *                                        image: Q = the keypoint capacity, the flags behind the frame's keypoint count
+ *                                        are not written (nothing reads them: those rows have no neighbour)
  *   which 2: m_depth, mh_depth [M]    -- DEPTHMAP_PROP's world point and Cauchy weight of every accepted match, in the
  *                                        order of mh_frame_fetch_matches_slot (any frame with depth attributes)
  * bytes must be exactly the array's size; a wrong size, a slot whose maps are gone or an array the last frame did not
@@ -835,14 +850,28 @@ int mh_sift_debug_blur(mh_ctx* ctx, int variant, const float* src_host, int src_
  * kernels read the count (query blocks beyond it leave at once); more keypoints than that -> the
  * first max_keypoints in list order are used.  Results: mh_frame_fetch; mh_frame_keypoints = the
  * keypoint count of the frame last fetched; mh_frame_features_dev = the device buffers
- * (descriptors already L2-normalised like MATCH_ANN_CPU.hpp:157 leaves them). */
+ * (descriptors already L2-normalised like MATCH_ANN_CPU.hpp:157 leaves them).
+ * With a depth map (mh_frame_set_depth_image), the depth rules (mh_frame_set_depth_rules) and the linkage clusterer this
+ * is moped3d's pipeline (moped3d/libmoped/src/config.hpp:38-49) behind FEAT for one Kinect frame: DEPTHFILTER counts
+ * the frame's keypoints from the device word, not the capacity (tests/test_gpu_kinect_image_batch.py). */
 int mh_frame_enqueue_image(mh_ctx* ctx, const uint8_t* gray_dev, int width, int height, int double_size,
                            int max_keypoints, const mh_cam* cam, const mh_frame_params* prm, uint64_t seed);
 /* B <= MH_MAX_BATCH images at once: FEAT image by image (every image's keypoints at a stride of max_keypoints rows,
  * its count in a device word of its own), then ONE MATCH launch sequence over all of them -- an image's ~600
  * keypoints alone leave the matrix pipes a sixth as busy per query as a batch does --, then CLUSTER..FILTER2 image
  * after image into result slots 0 .. B-1 (mh_frame_fetch_slot).  Every image's objects are bit for bit those of
- * mh_frame_enqueue_image(..., seeds[f]) on it alone.  One camera; not combined with depth maps or image indices. */
+ * mh_frame_enqueue_image(..., seeds[f]) on it alone.  One camera.
+ * moped3d's front end (moped3d/libmoped/src/config.hpp:38-49: DEPTHFILTER x 2, the adaptive ratio, DEPTHMAP_PROP,
+ * CLUSTER_LINKAGE or mean shift, either depth residual of POSE) travels with the batch when the context holds exactly
+ * one depth map per image: mh_frame_set_depth_image_batch with n_images maps (n_images = 1: mh_frame_set_depth_image
+ * counts too).  Frame f reads map f and counts its own keypoints (count word f): rows behind a frame's count, whatever
+ * an earlier batch left there, reach no keep flag, patch counter, ratio or match.  The frames share one launch per
+ * stage; with mh_enable_timing on they run one after the other, each with its own map and count.  Depth maps are not
+ * undistorted (mh_frame_set_undistort remaps the gray images only).
+ * Refused with MH_ERR_ARG, the context unchanged, the message naming the call to use instead: per-query depth attributes
+ * (mh_frame_set_depth: nobody has attributes for keypoints the device makes), a per-query image index with more than
+ * one image (mh_frame_set_images), a number of depth maps other than n_images, the depth rules without any depth map
+ * (as before: they would be ignored). */
 int mh_frame_enqueue_image_batch(mh_ctx* ctx, const uint8_t* const* gray_dev, int n_images, int width, int height,
                                  int double_size, int max_keypoints, const mh_cam* cam, const mh_frame_params* prm,
                                  const uint64_t* seeds);

@@ -103,7 +103,7 @@ EXPORTS = [
     "mh_filter", "mh_frame_default_params", "mh_frame_enqueue", "mh_frame_set_depth_image", "mh_frame_enqueue_match_local",
     "mh_frame_enqueue_rest", "mh_frame_fetch", "mh_frame_result_dev", "mh_enable_timing", "mh_timing",
     "mh_frame_set_cluster_linkage", "mh_cluster_linkage", "mh_frame_set_depth_image_host",
-    "mh_depth_fill", "mh_depth_fill_status", "mh_depth_fill_host",
+    "mh_depth_fill", "mh_depth_fill_status", "mh_depth_fill_host", "mh_depth_fill_batch",
     "mh_frame_enqueue_rest_batch", "mh_frame_enqueue_rest_frames", "mh_frame_fetch_slot", "mh_frame_result_copy_slots_dev",
     "mh_frame_set_depth_rules", "mh_frame_fetch_matches", "mh_frame_enqueue_rest_strided", "mh_frame_result_copy_dev",
     "mh_sift_extract", "mh_sift_extract_dev", "mh_frame_enqueue_image", "mh_frame_enqueue_image_batch", "mh_frame_features_dev", "mh_frame_keypoints",
@@ -210,6 +210,10 @@ def load():
     L.mh_frame_set_depth_image_host.argtypes = [vp, vp, vp, i32, i32, i32, f32, f32]
     L.mh_depth_fill.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.mh_depth_fill_status.argtypes = [vp]
+    # (EXPORTS lists it and build() insists on it; absent only in the parent's build that scripts/ab_lib.sh names through
+    #  MH_LIB_PATH to measure it against this one)
+    if hasattr(L, "mh_depth_fill_batch"):
+        L.mh_depth_fill_batch.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, i32, vp]
     L.mh_depth_fill_host.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.mh_frame_set_cluster_linkage.argtypes = [vp, C.POINTER(mh_linkage_params)]
     L.mh_cluster_linkage.argtypes = [vp, vp, vp, vp, i32, C.POINTER(mh_linkage_params), vp, vp, vp]
@@ -898,6 +902,18 @@ class Context:
         self._ck(self.L.mh_depth_fill(self.h, C.c_void_p(depth_ptr), width, height, int(scale), 1 if bilinear else 0,
                                       _ptr(k), C.c_void_p(fill_ptr), C.byref(used)), "mh_depth_fill")
         return used.value
+
+    def depth_fill_batch_dev(self, depth_ptrs, fill_ptrs, width, height, K, scale=8, bilinear=False):
+        """DEPTHFILL of len(depth_ptrs) device maps of one size, each in place with its own distance map: one launch per
+        stage for all of them; asynchronous (depth_fill_status reports a ring overflow of any of them)."""
+        n = len(depth_ptrs)
+        if len(fill_ptrs) != n:
+            raise ValueError("one distance map per depth map")
+        k = np.ascontiguousarray(K, np.float32)
+        d = (C.c_void_p * max(n, 1))(*depth_ptrs)
+        f = (C.c_void_p * max(n, 1))(*fill_ptrs)
+        self._ck(self.L.mh_depth_fill_batch(self.h, d, f, n, width, height, int(scale), 1 if bilinear else 0, _ptr(k)),
+                 "mh_depth_fill_batch")
 
     def depth_fill_status(self):
         self._ck(self.L.mh_depth_fill_status(self.h), "mh_depth_fill_status")

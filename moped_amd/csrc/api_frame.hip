@@ -132,7 +132,8 @@ int result_copy_bytes(mh_ctx* ctx, int max_objects, size_t* bytes) {
 // The B frames of a batch through the rest chain, from frame 0's record (the frames' keypoints, top-2 entries and
 // gathered blocks lie Q entries apart).  merge (the caller has asked merged_batch_ok and reserved B arenas' worth): ONE
 // call for all of them.  Else frame f as a call of its own: result slot f, its slice of the top-2 arrays and of the image
-// indices, and -- own_maps, a batch with a depth map per frame (mh_frame_set_depth_image_batch) -- its own map.
+// indices, and -- own_maps, a batch with a depth map per frame (mh_frame_set_depth_image_batch) -- its own map; c.q_count
+// (an image batch): the frames' keypoint counts, one word per frame.
 int rest_of_batch(mh_ctx* ctx, FrameCall c, int B, const uint64_t* seeds, bool merge, bool own_maps = false) {
   if (merge) {
     if (int rc = ensure_batch_arenas(ctx, B)) return rc;
@@ -144,6 +145,7 @@ int rest_of_batch(mh_ctx* ctx, FrameCall c, int B, const uint64_t* seeds, bool m
   }
   const float* const q_uv = c.q_uv;
   const int32_t* const gathered = c.gathered;
+  const int32_t* const q_count = c.q_count;
   own_maps = own_maps && B > 1 && ctx->batch_imgs == B && ctx->depth_img.img;
   int rc = MH_OK;
   for (int f = 0; f < B && rc == MH_OK; ++f) {
@@ -152,6 +154,7 @@ int rest_of_batch(mh_ctx* ctx, FrameCall c, int B, const uint64_t* seeds, bool m
     c.q0 = gathered ? 0 : f * c.Q;   // (gathered blocks are merged into the head of the top-2 arrays)
     c.slot = c.frame = f;
     c.seed = seeds[f];
+    c.q_count = q_count ? q_count + f : nullptr;
     if (own_maps) {
       c.img = ctx->batch_img[f];
       c.fill = ctx->batch_fill[f];
@@ -169,13 +172,16 @@ int image_frame_rest(mh_ctx* ctx, int Q, int32_t* n_dev, const mh_cam* cam, cons
   launch_normalize(ctx->q_desc, ctx->q_norm, Q, ctx->stream, n_dev);
   if (int rc = ctx_match(ctx, ctx->q_desc, ctx->q_norm, Q, ctx->nn_idx, ctx->nn_d1, ctx->nn_d2, n_dev, ctx->feat_expected)) return rc;
   stamp(ctx, 1);
-  return frame_rest(ctx, FrameCall{ctx->q_uv, Q, cam, prm, seed});
+  FrameCall c{ctx->q_uv, Q, cam, prm, seed};
+  c.q_count = n_dev;   // (DEPTHFILTER counts the frame's keypoints, not the capacity)
+  return frame_rest(ctx, c);
 }
 
 // mh_frame_enqueue_image[s]_batch behind FEAT: B frames' keypoint lists lie Q rows apart in the context's query buffers,
 // frame f's length in counts[f] (device) -- normalise, ONE MATCH launch sequence over all of them, the rest chain
+// (own_maps: with the depth map mh_frame_set_depth_image_batch handed in for every frame)
 int image_batch_rest(mh_ctx* ctx, int Q, int B, const int32_t* counts, const mh_cam* cam, const mh_frame_params* prm,
-                     const uint64_t* seeds, bool merge) {
+                     const uint64_t* seeds, bool merge, bool own_maps = false) {
   hipStream_t s = ctx->stream;
   launch_normalize_batch(ctx->q_desc, ctx->q_norm, Q, B, s, counts);   // (one launch: blockIdx.y = image)
   MH_HIP(ctx, hipGetLastError());
@@ -187,7 +193,9 @@ int image_batch_rest(mh_ctx* ctx, int Q, int B, const int32_t* counts, const mh_
   hipLaunchKernelGGL(image_batch_mask_kernel, dim3((B * Q + 255) / 256), dim3(256), 0, s, ctx->nn_idx, ctx->nn_d1, ctx->nn_d2,
                      counts, Q, B);
   stamp(ctx, 1);
-  return rest_of_batch(ctx, FrameCall{ctx->q_uv, Q, cam, prm, 0}, B, seeds, merge);
+  FrameCall c{ctx->q_uv, Q, cam, prm, 0};
+  c.q_count = counts;   // (rows past a frame's count hold what the slot's previous occupant left: DEPTHFILTER must not count them)
+  return rest_of_batch(ctx, c, B, seeds, merge, own_maps);
 }
 
 // mh_frame_enqueue_rest*: one frame's rest chain behind the shards' gathered blocks -- shard k's block is [3][Q] words at
@@ -627,13 +635,30 @@ int mh_frame_enqueue_image_batch(mh_ctx* ctx, const uint8_t* const* gray_dev, in
     return MH_ERR_ARG;
   for (int f = 0; f < B; ++f)
     if (!gray_dev[f]) return MH_ERR_ARG;
-  if (ctx->depth_img.img || ctx->rules.on || ctx->q_depth || (ctx->q_img && ctx->n_images > 1)) {
-    ctx->err = "mh_frame_enqueue_image_batch: depth maps / rules / attributes and image indices belong to ONE frame";
+  // moped3d's front end (a depth map per image, the rules, the linkage clusterer, either depth residual) travels with the
+  // batch; what belongs to host-made queries does not.  Nothing of the context has changed when a refusal returns.
+  auto refuse = [&](const char* why) {
+    ctx->err = std::string("mh_frame_enqueue_image_batch: ") + why;
     return MH_ERR_ARG;
-  }
+  };
+  if (ctx->q_depth)
+    return refuse("per-query depth attributes (mh_frame_set_depth) cannot belong to keypoints the device makes: hand in the "
+                  "depth maps (mh_frame_set_depth_image_batch), or clear them with mh_frame_set_depth(ctx, NULL, ..)");
+  if (ctx->q_img && ctx->n_images > 1)
+    return refuse("a per-query image index (mh_frame_set_images) cannot belong to keypoints the device makes: "
+                  "mh_frame_enqueue_images_batch takes frames of several cameras");
+  const bool maps = ctx->depth_img.img != nullptr;
+  const int n_maps = !maps ? 0 : (ctx->batch_imgs > 0 ? ctx->batch_imgs : 1);   // (mh_frame_set_depth_image: one map)
+  if (maps && n_maps != B)
+    return refuse("the context holds another number of depth maps than the batch has images: mh_frame_set_depth_image_batch "
+                  "with one map per image (one image: mh_frame_set_depth_image), or mh_frame_set_depth_image(ctx, NULL, ..) "
+                  "for a batch without depth");
+  if (!maps && ctx->rules.on)
+    return refuse("the depth rules (mh_frame_set_depth_rules) need a depth map per image: mh_frame_set_depth_image_batch, or "
+                  "mh_frame_set_depth_rules(ctx, NULL, NULL) for a batch without them");
   if (int rc_enter = mh::enter(ctx)) return rc_enter;
   const int Q = max_keypoints;
-  const bool merge = B > 1 && merged_batch_ok(ctx, prm);
+  const bool merge = B > 1 && merged_batch_ok(ctx, prm, true, B);
   int rc = prepare_frame(ctx, B * Q, Q, merge ? B : 1);
   if (rc) return rc;
   hipStream_t s = ctx->stream;
@@ -651,7 +676,7 @@ int mh_frame_enqueue_image_batch(mh_ctx* ctx, const uint8_t* const* gray_dev, in
   // (round 4: ONE launch per FEAT stage for all B images -- a frame's 26 dependent launches were what bounded this path)
   if ((rc = sift_into_batch(ctx, gray_dev, B, width, height, double_size, Q, ctx->q_desc, ctx->q_uv, ctx->img_counts)))
     return rc;
-  return image_batch_rest(ctx, Q, B, ctx->img_counts, cam, prm, seeds, merge);
+  return image_batch_rest(ctx, Q, B, ctx->img_counts, cam, prm, seeds, merge, true);
 }
 
 // Storage of the image hand-over: FEAT's staging for `images` images of `cap` rows, the count words, the rig's table,

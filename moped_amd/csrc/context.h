@@ -273,7 +273,7 @@ struct mh_ctx {
   mh::DevBuf<float> own_depth;    // device copies of a host depth / distance map (ensure_own_depth)
   mh::DevBuf<float> own_fill;
   mh::DevBuf<float> lk_scratch;
-  mh::DevBuf<unsigned char> df_buf;   // mh_depth_fill: [status words | downscaled depths | downscaled distances]
+  mh::DevBuf<unsigned char> df_buf;   // mh_depth_fill[_batch]: [status words | per frame: downscaled depths, downscaled distances]
   size_t lk_scratch_limit = (size_t)4 << 30;   // bytes; mh_set_linkage_scratch_limit
 
   // mh_frame_fetch_batch_async / mh_frame_fetch_previous_async: delivery of a batch's objects into the caller's pinned block

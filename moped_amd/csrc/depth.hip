@@ -84,7 +84,8 @@ namespace {
 constexpr int DF_MAX_PATCHES = 4096;
 
 // DEPTHFILTER with ToFilter = 1 (:181-211): keep[q] = 1 where the dilated density of the
-// feature's patch exceeds `filter`.  Single workgroup.
+// feature's patch exceeds `filter`.  Single workgroup per frame; q_count: the frames' keypoint counts on the device, one
+// word per frame (rows past a frame's count are whatever the buffer held before: they count for nothing).
 __global__ __launch_bounds__(1024) void feature_density_kernel(const float* __restrict__ q_uv, int Q,
                                                                const int32_t* __restrict__ q_count, int patch, int pw,
                                                                int ph, const double* __restrict__ inv_size,
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(1024) void feature_density_kernel(const float* __re
     keep += (size_t)blockIdx.y * Q;
     inv_size += (size_t)blockIdx.y * P;
   }
-  if (q_count) Q = min(Q, *q_count);
+  if (q_count) Q = min(Q, q_count[blockIdx.y]);
   for (int p = threadIdx.x; p < P; p += blockDim.x) cnt[p] = 0;
   __syncthreads();
   for (int q = threadIdx.x; q < Q; q += blockDim.x) atomicAdd(&cnt[patch_of(q_uv[2 * q], q_uv[2 * q + 1], patch, pw, ph)], 1);

@@ -37,10 +37,20 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// One workgroup.  zfill / fdist: [dh][dw] the filled downscaled depths and the fill's distance map (times `scale`).
-__global__ __launch_bounds__(DF_THREADS) void depth_fill_kernel(const float4* __restrict__ depth, int w, int h, int scale,
-                                                                int dw, int dh, float* __restrict__ zfill,
-                                                                float* __restrict__ fdist, int32_t* __restrict__ err) {
+// The maps of a batch, by value (mh_depth_fill_batch: one per frame), and where a frame's downscaled maps lie in the
+// context's scratch: zfill / fdist, [dh][dw] the filled downscaled depths and the fill's distance map (times `scale`),
+// DF_MAX_PIX floats each, frame after frame.  mh_depth_fill launches the same bodies through entry points that take
+// its one map's pointers directly: its launches are what they were before there were batches.
+struct DfMaps {
+  float4* depth[MH_MAX_BATCH] = {};
+  float* dist[MH_MAX_BATCH] = {};
+};
+constexpr size_t DF_FRAME_FLOATS = 2 * (size_t)DF_MAX_PIX;
+
+// One workgroup: one map.  zfill / fdist: [dh][dw] the filled downscaled depths and the fill's distance map.
+__device__ __forceinline__ void depth_fill_body(const float4* __restrict__ depth, int w, int h, int scale, int dw, int dh,
+                                                float* __restrict__ zfill, float* __restrict__ fdist,
+                                                int32_t* __restrict__ err) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   DfLds& L = *reinterpret_cast<DfLds*>(smem);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -119,11 +129,23 @@ __global__ __launch_bounds__(DF_THREADS) void depth_fill_kernel(const float4* __
     if (!L.valid[p] && L.src[p] != p) zfill[p] = zfill[L.src[p]];   // setDepth(xp, yp, getDepth(x0, y0)): sources are valid pixels, never rewritten
   }
 }
+__global__ __launch_bounds__(DF_THREADS) void depth_fill_kernel(const float4* __restrict__ depth, int w, int h, int scale,
+                                                                int dw, int dh, float* __restrict__ zfill,
+                                                                float* __restrict__ fdist, int32_t* __restrict__ err) {
+  depth_fill_body(depth, w, h, scale, dw, dh, zfill, fdist, err);
+}
+// ... one workgroup per frame (blockIdx.x)
+__global__ __launch_bounds__(DF_THREADS) void depth_fill_batch_kernel(DfMaps maps, int w, int h, int scale, int dw, int dh,
+                                                                      float* __restrict__ scratch, int32_t* __restrict__ err) {
+  float* zfill = scratch + blockIdx.x * DF_FRAME_FLOATS;
+  depth_fill_body(maps.depth[blockIdx.x], w, h, scale, dw, dh, zfill, zfill + DF_MAX_PIX, err);
+}
 
 // Upsampling + normalisation, one thread per pixel of the full map.
-__global__ void depth_fill_upscale_kernel(float4* __restrict__ depth, int w, int h, int scale, int dw, int dh, int bilinear,
-                                          const float* __restrict__ zfill, const float* __restrict__ fdist, float k0, float k1,
-                                          float k2, float k3, float* __restrict__ dist_out) {
+__device__ __forceinline__ void depth_fill_upscale_body(float4* __restrict__ depth, int w, int h, int scale, int dw, int dh,
+                                                        int bilinear, const float* __restrict__ zfill,
+                                                        const float* __restrict__ fdist, float k0, float k1, float k2,
+                                                        float k3, float* __restrict__ dist_out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= w * h) return;
   const int uy = i / w, ux = i - uy * w;
@@ -178,10 +200,26 @@ __global__ void depth_fill_upscale_kernel(float4* __restrict__ depth, int w, int
   depth[i] = px;
   dist_out[i] = fd;
 }
+__global__ void depth_fill_upscale_kernel(float4* __restrict__ depth, int w, int h, int scale, int dw, int dh, int bilinear,
+                                          const float* __restrict__ zfill, const float* __restrict__ fdist, float k0, float k1,
+                                          float k2, float k3, float* __restrict__ dist_out) {
+  depth_fill_upscale_body(depth, w, h, scale, dw, dh, bilinear, zfill, fdist, k0, k1, k2, k3, dist_out);
+}
+// ... blockIdx.y = frame
+__global__ void depth_fill_upscale_batch_kernel(DfMaps maps, int w, int h, int scale, int dw, int dh, int bilinear,
+                                                const float* __restrict__ scratch, float k0, float k1, float k2, float k3) {
+  const float* zfill = scratch + blockIdx.y * DF_FRAME_FLOATS;
+  depth_fill_upscale_body(maps.depth[blockIdx.y], w, h, scale, dw, dh, bilinear, zfill, zfill + DF_MAX_PIX, k0, k1, k2, k3,
+                          maps.dist[blockIdx.y]);
+}
 
 __global__ void depth_fill_scale1_kernel(const float* __restrict__ fdist, int n, float* __restrict__ dist_out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dist_out[i] = fdist[i];
+}
+__global__ void depth_fill_scale1_batch_kernel(DfMaps maps, const float* __restrict__ scratch, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) maps.dist[blockIdx.y][i] = scratch[blockIdx.y * DF_FRAME_FLOATS + DF_MAX_PIX + i];
 }
 
 __global__ void depth_count_valid_kernel(const float4* __restrict__ depth, int n, int32_t* __restrict__ count) {
@@ -189,6 +227,71 @@ __global__ void depth_count_valid_kernel(const float4* __restrict__ depth, int n
   const bool v = i < n && depth[i].z >= 0.f;
   const unsigned long long m = __ballot(v);
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(count, __popcll(m));
+}
+
+// The context's scratch for `frames` frames: [overflow word, valid count | the frames' downscaled maps].  Growing a held
+// block synchronises the stream (DevBuf::ensure) and would lose the sticky overflow word: it is carried over.
+int df_scratch(mh_ctx* ctx, int frames) {
+  hipStream_t s = ctx->stream;
+  const size_t need = 64 + sizeof(float) * DF_FRAME_FLOATS * (size_t)frames;
+  if (ctx->df_buf.cap >= need) return MH_OK;
+  int32_t word = 0;
+  if (ctx->df_buf) {
+    MH_HIP(ctx, hipMemcpyAsync(&word, ctx->df_buf, sizeof word, hipMemcpyDeviceToHost, s));
+    MH_HIP(ctx, hipStreamSynchronize(s));
+  }
+  MH_HIP(ctx, ctx->df_buf.ensure(need, s));
+  MH_HIP(ctx, hipMemsetAsync(ctx->df_buf, 0, 64, s));
+  if (word) {
+    MH_HIP(ctx, hipMemcpyAsync(ctx->df_buf, &word, sizeof word, hipMemcpyHostToDevice, s));
+    MH_HIP(ctx, hipStreamSynchronize(s));   // (`word` leaves scope)
+  }
+  return MH_OK;
+}
+
+// FILL + upsampling at a fixed scale >= 1, one launch per stage: of the one map (depth, dist), or -- batch != nullptr --
+// of the table's n_frames maps of one size.
+int df_launch(mh_ctx* ctx, const char* who, float4* depth, float* dist, const DfMaps* batch, int n_frames, int width, int height,
+              int scale, int bilinear, const float K[4]) {
+  const int dw = width / scale, dh = height / scale;
+  if (dw < 1 || dh < 1) {
+    ctx->err = std::string(who) + ": scale factor larger than the map";
+    return MH_ERR_ARG;
+  }
+  if ((long)dw * dh > DF_MAX_PIX) {
+    ctx->err = std::string(who) + ": the downscaled map has more than 8192 pixels (the fill is LDS resident)";
+    return MH_ERR_CAPACITY;
+  }
+  hipStream_t s = ctx->stream;
+  const int n_full = width * height;
+  int32_t* words = reinterpret_cast<int32_t*>(ctx->df_buf.p);
+  float* scratch = reinterpret_cast<float*>(ctx->df_buf + 64);
+  if (!batch) {
+    float* zfill = scratch;
+    float* fdist = zfill + DF_MAX_PIX;
+    static DynLds attr;
+    attr.ensure(depth_fill_kernel, sizeof(DfLds));
+    hipLaunchKernelGGL(depth_fill_kernel, dim3(1), dim3(DF_THREADS), sizeof(DfLds), s, depth, width, height, scale, dw, dh, zfill,
+                       fdist, words);
+    if (scale == 1)   // :336-338: the filled map never reaches the frame, the distance map does
+      hipLaunchKernelGGL(depth_fill_scale1_kernel, dim3((n_full + 255) / 256), dim3(256), 0, s, fdist, n_full, dist);
+    else
+      hipLaunchKernelGGL(depth_fill_upscale_kernel, dim3((n_full + 255) / 256), dim3(256), 0, s, depth, width, height, scale, dw,
+                         dh, bilinear ? 1 : 0, zfill, fdist, K[0], K[1], K[2], K[3], dist);
+  } else {
+    static DynLds attr;
+    attr.ensure(depth_fill_batch_kernel, sizeof(DfLds));
+    hipLaunchKernelGGL(depth_fill_batch_kernel, dim3(n_frames), dim3(DF_THREADS), sizeof(DfLds), s, *batch, width, height, scale,
+                       dw, dh, scratch, words);
+    const dim3 grid((n_full + 255) / 256, n_frames);
+    if (scale == 1)
+      hipLaunchKernelGGL(depth_fill_scale1_batch_kernel, grid, dim3(256), 0, s, *batch, scratch, n_full);
+    else
+      hipLaunchKernelGGL(depth_fill_upscale_batch_kernel, grid, dim3(256), 0, s, *batch, width, height, scale, dw, dh,
+                         bilinear ? 1 : 0, scratch, K[0], K[1], K[2], K[3]);
+  }
+  MH_HIP(ctx, hipGetLastError());
+  return MH_OK;
 }
 
 }  // namespace
@@ -208,14 +311,9 @@ extern "C" int mh_depth_fill(mh_ctx* ctx, float* depth_xyzn_dev, int width, int 
   if (int rc = use_stream(ctx)) return rc;
   hipStream_t s = ctx->stream;
   const int n_full = width * height;
-  // [overflow word, valid count] + the downscaled maps: the context's own (the status outlives the call)
-  if (!ctx->df_buf) {
-    MH_HIP(ctx, ctx->df_buf.ensure(64 + 2 * sizeof(float) * (size_t)DF_MAX_PIX, s));
-    MH_HIP(ctx, hipMemsetAsync(ctx->df_buf, 0, 64, s));
-  }
+  // the context's own scratch (the status outlives the call)
+  if (int rc = df_scratch(ctx, 1)) return rc;
   int32_t* words = reinterpret_cast<int32_t*>(ctx->df_buf.p);
-  float* zfill = reinterpret_cast<float*>(ctx->df_buf + 64);
-  float* fdist = zfill + DF_MAX_PIX;
   int scale = scale_factor;   // (the overflow word words[0] is sticky until mh_depth_fill_status reads it)
   if (scale == -1) {   // :283-296: the factor follows the share of holes (one small reduction + a 4-byte read)
     MH_HIP(ctx, hipMemsetAsync(words + 1, 0, sizeof(int32_t), s));
@@ -227,28 +325,44 @@ extern "C" int mh_depth_fill(mh_ctx* ctx, float* depth_xyzn_dev, int width, int 
     const float invalid_ratio = ((float)width * height - valid_count) / (width * height);
     scale = invalid_ratio < 0.1 ? 1 : invalid_ratio < 0.2 ? 2 : invalid_ratio < 0.4 ? 4 : invalid_ratio < 0.6 ? 8 : 16;
   }
-  const int dw = width / scale, dh = height / scale;
-  if (dw < 1 || dh < 1) {
-    ctx->err = "mh_depth_fill: scale factor larger than the map";
+  if (int rc = df_launch(ctx, "mh_depth_fill", reinterpret_cast<float4*>(depth_xyzn_dev), fill_distance_dev, nullptr, 1, width,
+                         height, scale, bilinear, K))
+    return rc;
+  if (scale_used) *scale_used = scale;
+  return MH_OK;
+}
+
+extern "C" int mh_depth_fill_batch(mh_ctx* ctx, float* const* depth_xyzn_dev, float* const* fill_distance_dev, int n_frames,
+                                   int width, int height, int scale_factor, int bilinear, const float K[4]) {
+  if (!ctx) return MH_ERR_ARG;
+  if (scale_factor == -1) {
+    ctx->err = "mh_depth_fill_batch: the automatic factor needs a read-back per map (mh_depth_fill takes -1, one map per call)";
     return MH_ERR_ARG;
   }
-  if ((long)dw * dh > DF_MAX_PIX) {
-    ctx->err = "mh_depth_fill: the downscaled map has more than 8192 pixels (the fill is LDS resident)";
-    return MH_ERR_CAPACITY;
+  bool ok = depth_xyzn_dev && fill_distance_dev && K && n_frames >= 1 && n_frames <= MH_MAX_BATCH && width > 0 && height > 0 &&
+            scale_factor >= 1;
+  for (int f = 0; ok && f < n_frames; ++f) ok = depth_xyzn_dev[f] && fill_distance_dev[f];
+  if (!ok) {
+    ctx->err = "mh_depth_fill_batch: bad arguments";
+    return MH_ERR_ARG;
   }
-  if (scale_used) *scale_used = scale;
-  static DynLds attr;
-  attr.ensure(depth_fill_kernel, sizeof(DfLds));
-  hipLaunchKernelGGL(depth_fill_kernel, dim3(1), dim3(DF_THREADS), sizeof(DfLds), s,
-                     reinterpret_cast<const float4*>(depth_xyzn_dev), width, height, scale, dw, dh, zfill, fdist, words);
-  if (scale == 1)   // :336-338: the filled map never reaches the frame, the distance map does
-    hipLaunchKernelGGL(depth_fill_scale1_kernel, dim3((n_full + 255) / 256), dim3(256), 0, s, fdist, n_full, fill_distance_dev);
-  else
-    hipLaunchKernelGGL(depth_fill_upscale_kernel, dim3((n_full + 255) / 256), dim3(256), 0, s,
-                       reinterpret_cast<float4*>(depth_xyzn_dev), width, height, scale, dw, dh, bilinear ? 1 : 0, zfill, fdist,
-                       K[0], K[1], K[2], K[3], fill_distance_dev);
-  MH_HIP(ctx, hipGetLastError());
-  return MH_OK;
+  // the frames are filled in place side by side: a map handed in twice would have one frame read what the other has filled
+  for (int f = 1; f < n_frames; ++f)
+    for (int g = 0; g < f; ++g)
+      if (depth_xyzn_dev[f] == depth_xyzn_dev[g] || fill_distance_dev[f] == fill_distance_dev[g]) {
+        ctx->err = "mh_depth_fill_batch: the same depth or distance map for two frames (every frame needs buffers of its own)";
+        return MH_ERR_ARG;
+      }
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = use_stream(ctx)) return rc;
+  // room for MH_MAX_BATCH frames from the first batch on: no later batch regrows the block behind one in flight
+  if (int rc = df_scratch(ctx, MH_MAX_BATCH)) return rc;
+  DfMaps maps;
+  for (int f = 0; f < n_frames; ++f) {
+    maps.depth[f] = reinterpret_cast<float4*>(depth_xyzn_dev[f]);
+    maps.dist[f] = fill_distance_dev[f];
+  }
+  return df_launch(ctx, "mh_depth_fill_batch", nullptr, nullptr, &maps, n_frames, width, height, scale_factor, bilinear, K);
 }
 
 extern "C" int mh_depth_fill_status(mh_ctx* ctx) {

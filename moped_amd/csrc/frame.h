@@ -103,6 +103,8 @@ struct FrameCall {
   // the frame's own depth map where a batch has one per frame (mh_frame_set_depth_image_batch); nullptr: the context's
   const float4* img = nullptr;
   const float* fill = nullptr;
+  // the frame's keypoint count on the device where FEAT made the keypoints (batch_n > 1: one word per frame), nullptr: Q
+  const int32_t* q_count = nullptr;
 };
 
 namespace mh {

@@ -335,7 +335,7 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
     rs.last.keep = rs.feature_filter >= 0.f;
     if (filters) launch_depth_patches(dimg, rs.K, rs.patch, rs.inv_size, s, maps, batch_n);
     if (rs.feature_filter >= 0.f) {
-      launch_feature_density(q_uv_dev, Q, ctx->feat_count_dev, rs.patch, pw, ph, rs.inv_size, rs.feature_filter,
+      launch_feature_density(q_uv_dev, Q, c.q_count, rs.patch, pw, ph, rs.inv_size, rs.feature_filter,
                              rs.keep1, s, batch_n);
       rules.keep1 = rs.keep1;
     }

@@ -94,7 +94,7 @@ __device__ __forceinline__ float density_replay(int n, double inv) {
 // (maps, n_frames > 1: the frames of a batch in one launch, frame f's patch map at inv_size + f pw ph)
 void launch_depth_patches(const DepthImage& dimg, const float K[4], int patch, double* inv_size, hipStream_t s,
                           const DepthMaps* maps = nullptr, int n_frames = 1);
-// DEPTHFILTER on the detected features: keep[q] for q < min(Q, *q_count).
+// DEPTHFILTER on the detected features: keep[q] for q < min(Q, q_count[frame]) (q_count: one device word per frame, or null).
 void launch_feature_density(const float* q_uv, int Q, const int32_t* q_count, int patch, int pw, int ph,
                             const double* inv_size, float filter, uint8_t* keep, hipStream_t s,
                             int n_frames = 1 /* > 1: q_uv / keep / inv_size frame after frame (Q, Q, pw ph apart) */);

@@ -285,6 +285,29 @@ class FramePipeline:
         self.ctxs[slot].frame_enqueue_images_batch(list(gray_ptrs), n_images, w, h, double_size, max_keypoints, Ks, cams,
                                                    self.params, seeds)
 
+    # ---- Kinect frames: a gray image and a depth map per frame, both on the device ---------------------------
+    def enqueue_kinect_batch(self, slot: int, gray_ptrs, depth_ptrs, fill_ptrs, w: int, h: int, seeds, fill_scale=8,
+                             bilinear: bool = False, max_keypoints: int = 2048, double_size: bool = True,
+                             kind: int = capi.DEPTH_BACKPROJECTION, alpha: float = 0.5, cauchy_scale: float = 0.1, keep=None):
+        """len(seeds) frames of moped3d's pipeline (config.hpp:38-49) on the slot's stream: DEPTHFILL of every depth map
+        [h, w, 4] in place + its distance map [h, w] (one launch per stage; fill_scale=None: the maps arrive filled, their
+        distance maps with them), the maps handed to the frames, FEAT .. FILTER2 of the images as one image batch; objects
+        in result slots 0.. (fetch_batch).  The context's depth rules / linkage clusterer are what their setters left.
+        `keep`: the tensors behind the pointers, held until the slot's next enqueue."""
+        if self.exchange:
+            raise ValueError("frames from device images run on one GPU's whole database")
+        B = len(seeds)
+        if not (1 <= B <= capi.MAX_BATCH) or len(gray_ptrs) != B or len(depth_ptrs) != B or len(fill_ptrs) != B:
+            raise ValueError("one image, one depth map, one distance map and one seed per frame, at most MAX_BATCH frames")
+        c = self.ctxs[slot]
+        self._inputs[slot] = keep
+        self._batch[slot] = B
+        if fill_scale is not None:
+            c.depth_fill_batch_dev(list(depth_ptrs), list(fill_ptrs), w, h, self.K, fill_scale, bilinear)
+        c.frame_set_depth_image_batch(list(depth_ptrs), list(fill_ptrs), w, h, kind, alpha, cauchy_scale)
+        c.frame_enqueue_image_batch(list(gray_ptrs), w, h, double_size, max_keypoints, self.K, self.cam, self.params, seeds,
+                                    _cam_struct=self._cam)
+
     def fetch_batch(self, slot: int, B: int):
         return [self.ctxs[slot].frame_fetch_slot(f) for f in range(B)]
 
