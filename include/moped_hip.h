@@ -25,6 +25,7 @@
  *                       moped3d/libmoped/src/pose/POSE_RANSAC_LM_DIFF_REPROJECTION_DEPTH_CPU.hpp:106-216
  *   mh_project_test     testAllPoints / project()        …REPROJECTION_CPU.hpp:166-180, include/moped.hpp:330-354
  *   mh_filter           FILTER_PROJECTION_CPU::process   src/filter/FILTER_PROJECTION_CPU.hpp:80-162
+ *   mh_filter_depth     FILTER_PROJECTION_DEPTH_CPU::process   moped3d .../filter/FILTER_PROJECTION_DEPTH_CPU.hpp:140-329
  *   mh_frame_*          the per-frame loop over those steps, MopedPimpl::processImages
  *                                                        src/moped.cpp:166-194 (device-resident form)
  *
@@ -377,6 +378,51 @@ int mh_filter(mh_ctx* ctx, const mh_corr* corr_host, const int32_t* model_off, i
               int min_points, float feature_distance, float min_score,
               float* score, uint8_t* keep, int32_t* out_order, int32_t* cl_members,
               int32_t* cl_off, int32_t* n_kept);
+
+/* ---- FILTER, depth class (moped3d) ---------------------------------------------- */
+
+/* FILTER_PROJECTION_DEPTH_CPU (moped3d/libmoped/src/filter/FILTER_PROJECTION_DEPTH_CPU.hpp:140-329):
+ * FILTER_PROJECTION_CPU plus a test of every object's pose against the frame's depth map.  A sample of the model's
+ * own 3-D points is transformed by the pose and projected into the depth camera; where the sensor MEASURED a depth (not
+ * a filled pixel) that lies behind the point, the object pays a Cauchy penalty, the "incorrect score" IS (:207-267);
+ * object->score = score - IS (:270) and MinScore is applied to that (:309).  Keypoint ownership still goes by the
+ * projection score (:277). */
+typedef struct {
+  float plausible_sq_distance;  /* PlausibleSqDistance: matches with err2 below it are the clusterSize IS is scaled to (:202-204, :266) */
+  float depth_fraction;         /* DepthFraction: cauchyScale = DepthFraction * kinectDepth (:248) */
+  float min_keypoint_fraction;  /* MinKeypointFraction: used <= (int)(fraction * n_test) -> IS = 0 (:260) */
+} mh_filter_depth_params;
+
+/* TestPoints (:94-116) of the context: a CSR of 3-D model points, model m's slice is xyz_host[off_host[m] ..
+ * off_host[m + 1]) in the order the reference would walk TestPoints[m].  The library does not sample: which points to
+ * take is the caller's choice, as the reference makes it with rand() (:78-92, :107-113).  Copied into the context.
+ * n_models == 0 clears them.  The call records the context's database (model count, mh_db_generation): after an edit or
+ * a new upload the points must be set again -- frames and mh_filter_depth fail with MH_ERR_ARG until then, and launch
+ * nothing. */
+int mh_filter_depth_set_points(mh_ctx* ctx, const float* xyz_host, const int32_t* off_host, int n_models);
+
+/* FILTER_PROJECTION_DEPTH_CPU::process (:140-329) for one image: mh_filter's arguments and results, plus the depth map's
+ * camera (:162 K = intrinsicLinearCalibration, :221 TM = its pose), the class's own parameters and, optionally, per
+ * object in list order: the IS that was subtracted (:260-267), usedKeypointCount (:237) and clusterSize (:202-204).
+ * The map is the one the context holds (mh_frame_set_depth_image[_host]; fill_distance NULL = every pixel measured);
+ * without one, without test points for n_models models or with stale ones: MH_ERR_ARG.  A projected coordinate that is
+ * NaN, infinite or outside int's range -- where the reference's (int) is undefined -- counts as off the image. */
+int mh_filter_depth(mh_ctx* ctx, const mh_corr* corr_host, const int32_t* model_off, int n_models,
+                    const int32_t* obj_model, const float* obj_pose, int n_obj, const mh_cam* cam,
+                    int min_points, float feature_distance, float min_score, const mh_cam* depth_cam,
+                    const mh_filter_depth_params* prm, float* score, uint8_t* keep, int32_t* out_order,
+                    int32_t* cl_members, int32_t* cl_off, int32_t* n_kept, float* incorrect_score, int32_t* used,
+                    int32_t* plausible);
+
+/* FILTER (f1) and / or FILTER2 (f2) of the frames enqueued from now on are FILTER_PROJECTION_DEPTH_CPU (:140-329) with
+ * the frame's depth map (mh_frame_set_depth_image[_batch | _host]) seen through depth_cam, MinPoints / FeatureDistance /
+ * MinScore from mh_frame_params as before.  NULL: that slot stays FILTER_PROJECTION_CPU; both NULL: off.  Such a frame
+ * runs its FILTER steps as launches of their own and the frames of a batch one after the other, each with its own map.
+ * Refused with MH_ERR_ARG before anything is enqueued: no depth map, several cameras, the sharded entry points
+ * (mh_frame_enqueue_sharded*, mh_frame_enqueue_rest*), test points not set or stale.  mh_step_filter stays the plain
+ * class. */
+int mh_frame_set_filter_depth(mh_ctx* ctx, const mh_filter_depth_params* f1, const mh_filter_depth_params* f2,
+                              const mh_cam* depth_cam);
 
 /* ---- whole frame, device resident --------------------------------------------- */
 

@@ -95,6 +95,19 @@ class mh_depth_rules(C.Structure):
                 ("default_depth", C.c_float), ("cauchy_scale", C.c_float)]
 
 
+class mh_filter_depth_params(C.Structure):
+    """FILTER_PROJECTION_DEPTH_CPU's own constructor arguments (PlausibleSqDistance, DepthFraction, MinKeypointFraction)."""
+    _fields_ = [("plausible_sq_distance", C.c_float), ("depth_fraction", C.c_float), ("min_keypoint_fraction", C.c_float)]
+
+
+def make_filter_depth_params(p):
+    """None, an mh_filter_depth_params or (plausible_sq_distance, depth_fraction, min_keypoint_fraction)."""
+    if p is None or isinstance(p, mh_filter_depth_params):
+        return p
+    a, b, c = p
+    return mh_filter_depth_params(float(a), float(b), float(c))
+
+
 EXPORTS = [
     "mh_create", "mh_destroy", "mh_last_error", "mh_set_stream", "mh_synchronize", "mh_reserve",
     "mh_db_upload", "mh_db_size", "mh_normalize", "mh_match", "mh_normalize_match", "mh_match_local_dev", "mh_match_local_counted_dev",
@@ -130,6 +143,7 @@ EXPORTS = [
     "mh_screen_sample_values", "mh_match_query_candidates",
     "mh_frame_enqueue_images", "mh_frame_enqueue_images_batch", "mh_frame_set_undistort_images", "mh_frame_image_counts",
     "mh_frame_features_image_dev",
+    "mh_filter_depth_set_points", "mh_filter_depth", "mh_frame_set_filter_depth",
 ]
 COMM_ID_BYTES = 128      # MH_COMM_ID_BYTES
 EX2_OBJECTS = 62         # MH_EX2_OBJECTS
@@ -350,6 +364,12 @@ def load():
         L.mh_frame_set_undistort_images.argtypes = [vp, vp, i32]
         L.mh_frame_image_counts.argtypes = [vp, vp, i32, C.POINTER(C.c_int32)]
         L.mh_frame_features_image_dev.argtypes = [vp, C.POINTER(vp)]
+    if hasattr(L, "mh_filter_depth"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
+        L.mh_filter_depth_set_points.argtypes = [vp, vp, vp, i32]
+        L.mh_filter_depth.argtypes = [vp, vp, vp, i32, vp, vp, i32, C.POINTER(mh_cam), i32, f32, f32, C.POINTER(mh_cam),
+                                      C.POINTER(mh_filter_depth_params), vp, vp, vp, vp, vp, C.POINTER(C.c_int32), vp, vp, vp]
+        L.mh_frame_set_filter_depth.argtypes = [vp, C.POINTER(mh_filter_depth_params), C.POINTER(mh_filter_depth_params),
+                                                C.POINTER(mh_cam)]
     _lib = L
     return L
 
@@ -1100,6 +1120,72 @@ class Context:
         k = kept.value
         clusters = [members[off[i]:off[i + 1]].copy() for i in range(k)]
         return score[:n_obj], keep[:n_obj].astype(bool), order[:k].copy(), clusters
+
+    # ---- FILTER, depth class (moped3d FILTER_PROJECTION_DEPTH_CPU) ----
+    def filter_depth_set_points(self, points_xyz, points_off):
+        """The models' test points: points_xyz [total, 3], points_off [n_models + 1] (model m's slice in the order the
+        reference walks TestPoints[m]).  None / an empty offset list clears them.  To be set again after a DB edit."""
+        if points_off is None or len(points_off) <= 1:
+            self._ck(self.L.mh_filter_depth_set_points(self.h, None, None, 0), "mh_filter_depth_set_points")
+            return
+        off = np.ascontiguousarray(points_off, np.int32)
+        xyz = np.ascontiguousarray(points_xyz, np.float32).reshape(-1, 3)
+        if off[-1] != len(xyz):
+            raise ValueError("points_off[-1] is not the number of points")
+        self._ck(self.L.mh_filter_depth_set_points(self.h, _ptr(xyz), _ptr(off), len(off) - 1), "mh_filter_depth_set_points")
+
+    def filter_depth(self, corr, model_off, obj_model, obj_pose, K, cam, min_points, feature_distance, min_score,
+                     depth_K, depth_cam, params):
+        """filter() of the depth class on the depth map the context holds (frame_set_depth_image[_host]) -> (score, keep,
+        order, clusters, incorrect_score, used, plausible); params: (PlausibleSqDistance, DepthFraction,
+        MinKeypointFraction)."""
+        corr = np.ascontiguousarray(corr, CORR_DTYPE)
+        model_off = np.ascontiguousarray(model_off, np.int32)
+        obj_model = np.ascontiguousarray(obj_model, np.int32)
+        obj_pose = np.ascontiguousarray(obj_pose, np.float32)
+        n_obj = obj_model.shape[0]
+        M = corr.shape[0]
+        score = np.zeros(max(n_obj, 1), np.float32)
+        keep = np.zeros(max(n_obj, 1), np.uint8)
+        order = np.zeros(max(n_obj, 1), np.int32)
+        members = np.zeros(max(M, 1), np.int32)
+        off = np.zeros(n_obj + 2, np.int32)
+        inc = np.zeros(max(n_obj, 1), np.float32)
+        used = np.zeros(max(n_obj, 1), np.int32)
+        plausible = np.zeros(max(n_obj, 1), np.int32)
+        kept = C.c_int32(0)
+        c, dc = make_cam(K, cam), make_cam(depth_K, depth_cam)
+        prm = make_filter_depth_params(params)
+        self._ck(self.L.mh_filter_depth(self.h, _ptr(corr), _ptr(model_off), len(model_off) - 1, _ptr(obj_model),
+                                        _ptr(obj_pose), n_obj, C.byref(c), min_points, feature_distance, min_score,
+                                        C.byref(dc), C.byref(prm), _ptr(score), _ptr(keep), _ptr(order), _ptr(members),
+                                        _ptr(off), C.byref(kept), _ptr(inc), _ptr(used), _ptr(plausible)), "mh_filter_depth")
+        k = kept.value
+        clusters = [members[off[i]:off[i + 1]].copy() for i in range(k)]
+        return (score[:n_obj], keep[:n_obj].astype(bool), order[:k].copy(), clusters, inc[:n_obj], used[:n_obj],
+                plausible[:n_obj])
+
+    def frame_set_depth_image_host(self, depth_img, fill_img, kind=DEPTH_BACKPROJECTION, alpha=0.5, cauchy_scale=0.1):
+        """The frame's depth map [h, w, 4] (+ fill-distance map [h, w] or None) from host arrays, copied into the
+        context; depth_img None: no map."""
+        if depth_img is None:
+            self._ck(self.L.mh_frame_set_depth_image_host(self.h, None, None, 0, 0, 0, alpha, cauchy_scale),
+                     "mh_frame_set_depth_image_host")
+            return
+        d = np.ascontiguousarray(depth_img, np.float32)
+        h, w = d.shape[:2]
+        f = None if fill_img is None else np.ascontiguousarray(fill_img, np.float32).reshape(h, w)
+        self._ck(self.L.mh_frame_set_depth_image_host(self.h, _ptr(d), _ptr(f), w, h, kind, alpha, cauchy_scale),
+                 "mh_frame_set_depth_image_host")
+
+    def frame_set_filter_depth(self, f1=None, f2=None, depth_K=None, depth_cam=None):
+        """FILTER (f1) / FILTER2 (f2) of the frames enqueued from now on as the depth class; None: that slot stays plain,
+        both None: off.  f1, f2: (PlausibleSqDistance, DepthFraction, MinKeypointFraction)."""
+        p1, p2 = make_filter_depth_params(f1), make_filter_depth_params(f2)
+        dc = make_cam(depth_K, depth_cam) if depth_K is not None else None
+        self._ck(self.L.mh_frame_set_filter_depth(self.h, C.byref(p1) if p1 is not None else None,
+                                                  C.byref(p2) if p2 is not None else None,
+                                                  C.byref(dc) if dc is not None else None), "mh_frame_set_filter_depth")
 
     # ---- frame (device pointers as ints) ----
     def frame_enqueue(self, q_desc_ptr, q_uv_ptr, Q, K, cam, params: mh_frame_params, seed=1):

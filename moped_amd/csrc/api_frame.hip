@@ -203,6 +203,7 @@ int image_batch_rest(mh_ctx* ctx, int Q, int B, const int32_t* counts, const mh_
 int enqueue_rest(mh_ctx* ctx, const float* q_uv_dev, int Q, const int32_t* gathered_dev, int n_shards, int shard_stride,
                  int plane_stride, int slot, const mh_cam* cam, const mh_frame_params* prm, uint64_t seed) {
   if (!ctx || Q <= 0 || !q_uv_dev || !gathered_dev || n_shards <= 0 || !cam || !prm) return MH_ERR_ARG;
+  if (int rc = filter_depth_frame_ok(ctx, "mh_frame_enqueue_rest", prm, 1, true)) return rc;
   if (int rc_enter = mh::enter(ctx)) return rc_enter;
   if (int rc = prepare_frame(ctx, Q)) return rc;
   stamp(ctx, 1);
@@ -232,6 +233,8 @@ int upload_cams(mh_ctx* ctx, const mh_cam* cams, int n_images) {
 
 int enqueue_features(mh_ctx* ctx, float* q_desc_dev, const float* q_uv_dev, int Q, const mh_cam* cam,
                      const mh_frame_params* prm, uint64_t seed, const FeatureOptions& opt) {
+  if (opt.stage_lo == 0 && opt.stage_hi == 5)   // (a whole frame: mh_step_* keep the plain FILTER)
+    if (int rc = filter_depth_frame_ok(ctx, "frame", prm)) return rc;
   if (int rc_enter = enter(ctx)) return rc_enter;
   if (int rc = prepare_frame(ctx, Q)) return rc;
   ctx->feat_count_dev = nullptr;
@@ -503,6 +506,23 @@ int mh_frame_set_depth_image_host(mh_ctx* ctx, const float* depth_xyzn_host, con
                                   alpha, cauchy_scale);
 }
 
+// FILTER / FILTER2 of the frames as FILTER_PROJECTION_DEPTH_CPU (moped3d .../filter/FILTER_PROJECTION_DEPTH_CPU.hpp:140-329)
+int mh_frame_set_filter_depth(mh_ctx* ctx, const mh_filter_depth_params* f1, const mh_filter_depth_params* f2,
+                              const mh_cam* depth_cam) {
+  if (!ctx) return MH_ERR_ARG;
+  if ((f1 || f2) && !depth_cam) {
+    ctx->err = "mh_frame_set_filter_depth: the depth map's camera is missing";
+    return MH_ERR_ARG;
+  }
+  mh_ctx::FilterDepthState& fd = ctx->fdepth;
+  fd.on[0] = f1 != nullptr;
+  fd.on[1] = f2 != nullptr;
+  if (f1) fd.prm[0] = *f1;
+  if (f2) fd.prm[1] = *f2;
+  if (depth_cam) fd.cam = *depth_cam;
+  return MH_OK;
+}
+
 int mh_set_linkage_scratch_limit(mh_ctx* ctx, size_t bytes) {
   if (!ctx) return MH_ERR_ARG;
   ctx->lk_scratch_limit = bytes ? bytes : (size_t)4 << 30;
@@ -617,6 +637,7 @@ int mh_frame_run_host(mh_ctx* ctx, float* q_desc_host, const float* q_uv_host, c
 int mh_frame_enqueue_image(mh_ctx* ctx, const uint8_t* gray_dev, int width, int height, int double_size,
                            int max_keypoints, const mh_cam* cam, const mh_frame_params* prm, uint64_t seed) {
   if (!ctx || !gray_dev || width <= 0 || height <= 0 || max_keypoints <= 0 || !cam || !prm) return MH_ERR_ARG;
+  if (int rc_fd = filter_depth_frame_ok(ctx, "mh_frame_enqueue_image", prm)) return rc_fd;
   if (int rc_enter = mh::enter(ctx)) return rc_enter;
   const int Q = max_keypoints;
   int rc = prepare_frame(ctx, Q);
@@ -656,6 +677,7 @@ int mh_frame_enqueue_image_batch(mh_ctx* ctx, const uint8_t* const* gray_dev, in
   if (!maps && ctx->rules.on)
     return refuse("the depth rules (mh_frame_set_depth_rules) need a depth map per image: mh_frame_set_depth_image_batch, or "
                   "mh_frame_set_depth_rules(ctx, NULL, NULL) for a batch without them");
+  if (int rc_fd = filter_depth_frame_ok(ctx, "mh_frame_enqueue_image_batch", prm)) return rc_fd;
   if (int rc_enter = mh::enter(ctx)) return rc_enter;
   const int Q = max_keypoints;
   const bool merge = B > 1 && merged_batch_ok(ctx, prm, true, B);
@@ -717,6 +739,7 @@ static int enqueue_images(mh_ctx* ctx, const char* who, const uint8_t* const* gr
   if ((long long)F * n * cap > INT_MAX) return refuse(MH_ERR_CAPACITY, "too many rows");
   for (int j = 0; j < F * n; ++j)
     if (!gray_dev[j]) return refuse(MH_ERR_ARG, "null image");
+  if (int rc_fd = filter_depth_frame_ok(ctx, who, prm, n)) return rc_fd;
   if (ctx->depth_img.img || ctx->rules.on || ctx->q_depth || (n > 1 && ctx->linkage_on))
     return refuse(MH_ERR_ARG, "depth maps / rules / attributes and the linkage clusterer are single-camera");
   if (ctx->imf.und_n && ctx->imf.und_n != n)
@@ -833,6 +856,7 @@ int mh_frame_enqueue_batch(mh_ctx* ctx, float* q_desc_dev, const float* q_uv_dev
                "frame of the batch)";
     return MH_ERR_ARG;
   }
+  if (int rc_fd = filter_depth_frame_ok(ctx, "mh_frame_enqueue_batch", prm)) return rc_fd;
   if (int rc_enter = mh::enter(ctx)) return rc_enter;
   const bool merge = B > 1 && merged_batch_ok(ctx, prm, true, B);
   int rc = prepare_frame(ctx, B * Q, Q, merge ? B : 1);   // (the arenas before any work is enqueued)
@@ -926,6 +950,7 @@ int mh_frame_enqueue_rest_frames(mh_ctx* ctx, const float* q_uv_dev, int Q, cons
   if (!ctx || Q <= 0 || !q_uv_dev || !gathered_dev || n_shards <= 0 || !cam || !prm || !seeds || B < 1 || B > MH_MAX_BATCH ||
       plane_stride_words < Q || shard_stride_words < 3 * plane_stride_words)
     return MH_ERR_ARG;
+  if (int rc_fd = filter_depth_frame_ok(ctx, "mh_frame_enqueue_rest_frames", prm, 1, true)) return rc_fd;
   if (int rc_enter = mh::enter(ctx)) return rc_enter;
   const bool merge = B > 1 && merged_batch_ok(ctx, prm);
   if (int rc = prepare_frame(ctx, merge ? B * Q : Q, Q, merge ? B : 1)) return rc;

@@ -357,10 +357,20 @@ int mh_filter(mh_ctx* ctx, const mh_corr* corr_host, const int32_t* model_off, i
                           feature_distance, min_score, score, keep, out_order, cl_members, cl_off, n_kept);
 }
 
-int mh_filter_images(mh_ctx* ctx, const mh_corr* corr_host, const int32_t* image_of_host, const int32_t* model_off,
-                     int n_models, const int32_t* obj_model, const float* obj_pose, int n_obj, const mh_cam* cam,
-                     int n_images, int min_points, float feature_distance, float min_score, float* score,
-                     uint8_t* keep, int32_t* out_order, int32_t* cl_members, int32_t* cl_off, int32_t* n_kept) {
+// mh_filter_depth's additions to a FILTER call (depth == nullptr: the plain class)
+struct FilterDepthCall {
+  const mh_cam* depth_cam;
+  const mh_filter_depth_params* prm;
+  float* incorrect_score;
+  int32_t* used;
+  int32_t* plausible;
+};
+
+static int filter_impl(mh_ctx* ctx, const mh_corr* corr_host, const int32_t* image_of_host, const int32_t* model_off,
+                       int n_models, const int32_t* obj_model, const float* obj_pose, int n_obj, const mh_cam* cam,
+                       int n_images, int min_points, float feature_distance, float min_score, float* score,
+                       uint8_t* keep, int32_t* out_order, int32_t* cl_members, int32_t* cl_off, int32_t* n_kept,
+                       const FilterDepthCall* depth) {
   if (!ctx || !model_off || n_models <= 0 || n_obj < 0 || !cam || !n_kept || n_images < 1 || n_images > MH_MAX_IMAGES ||
       (n_images > 1 && !image_of_host))
     return MH_ERR_ARG;
@@ -401,12 +411,24 @@ int mh_filter_images(mh_ctx* ctx, const mh_corr* corr_host, const int32_t* image
     fb.cams = ctx->cams_view;
     fb.n_images = n_images;
   }
-  launch_filter(fb, make_devcam(*cam), min_points, feature_distance, min_score, fs->n_slots,
-                fs->n_clusters, fs->counts, FilterTail{fs->tickets + 5, nullptr, nullptr, 0, nullptr, nullptr, nullptr}, s);
+  const FilterTail tail{fs->tickets + 5, nullptr, nullptr, 0, nullptr, nullptr, nullptr};
+  float* d_is = nullptr;   // the depth class's per-object outputs: IS | used | plausible in the context's byte scratch
+  if (depth) {
+    if ((rc = ensure_scratch(ctx, 3 * (size_t)n_obj * 4))) return rc;
+    d_is = reinterpret_cast<float*>(ctx->scratch.p);
+    FilterDepthArgs da = make_filter_depth_args(ctx, ctx->depth_img, *depth->prm, *depth->depth_cam);
+    da.out_is = d_is;
+    da.out_used = reinterpret_cast<int32_t*>(d_is) + n_obj;
+    da.out_plausible = reinterpret_cast<int32_t*>(d_is) + 2 * (size_t)n_obj;
+    launch_filter_depth(fb, make_devcam(*cam), min_points, feature_distance, min_score, da, fs->n_slots, fs->n_clusters,
+                        fs->counts, tail, s);
+  } else
+    launch_filter(fb, make_devcam(*cam), min_points, feature_distance, min_score, fs->n_slots, fs->n_clusters, fs->counts,
+                  tail, s);
   MH_HIP(ctx, hipGetLastError());
   // results: everything the host needs in ONE pinned block, copied behind the kernel, one synchronisation (five
   // blocking copies after it cost the step 0.1 ms: profiles/r02_host_step_timing.txt)
-  const size_t words = 1 + 4 * (size_t)n_obj + (size_t)std::max(M, 1);
+  const size_t words = 1 + 4 * (size_t)n_obj + (size_t)std::max(M, 1) + (depth ? 3 * (size_t)n_obj : 0);
   if ((rc = ensure_pinned(ctx, words * 4))) return rc;
   int32_t* const hp = reinterpret_cast<int32_t*>(ctx->pinned.p);
   int32_t* const h_kept = hp;
@@ -421,7 +443,14 @@ int mh_filter_images(mh_ctx* ctx, const mh_corr* corr_host, const int32_t* image
   MH_HIP(ctx, hipMemcpyAsync(begin, fs->cl_begin, (size_t)std::min(n_obj, fs->max_clusters) * 4, hipMemcpyDeviceToHost, s));
   MH_HIP(ctx, hipMemcpyAsync(count, fs->cl_count, (size_t)std::min(n_obj, fs->max_clusters) * 4, hipMemcpyDeviceToHost, s));
   if (M > 0) MH_HIP(ctx, hipMemcpyAsync(mem, fs->new_members, (size_t)M * 4, hipMemcpyDeviceToHost, s));
+  int32_t* const extra = mem + std::max(M, 1);   // (the depth class: IS | used | plausible)
+  if (depth) MH_HIP(ctx, hipMemcpyAsync(extra, d_is, 3 * (size_t)n_obj * 4, hipMemcpyDeviceToHost, s));
   MH_HIP(ctx, hipStreamSynchronize(s));
+  if (depth) {
+    if (depth->incorrect_score) std::memcpy(depth->incorrect_score, extra, (size_t)n_obj * 4);
+    if (depth->used) std::memcpy(depth->used, extra + n_obj, (size_t)n_obj * 4);
+    if (depth->plausible) std::memcpy(depth->plausible, extra + 2 * (size_t)n_obj, (size_t)n_obj * 4);
+  }
   const int32_t kept = std::min(*h_kept, n_obj);
   if (keep) std::memset(keep, 0, n_obj);
   if (score)
@@ -439,6 +468,71 @@ int mh_filter_images(mh_ctx* ctx, const mh_corr* corr_host, const int32_t* image
   if (cl_off) cl_off[kept] = w;
   *n_kept = kept;
   return MH_OK;
+}
+
+int mh_filter_images(mh_ctx* ctx, const mh_corr* corr_host, const int32_t* image_of_host, const int32_t* model_off,
+                     int n_models, const int32_t* obj_model, const float* obj_pose, int n_obj, const mh_cam* cam,
+                     int n_images, int min_points, float feature_distance, float min_score, float* score,
+                     uint8_t* keep, int32_t* out_order, int32_t* cl_members, int32_t* cl_off, int32_t* n_kept) {
+  return filter_impl(ctx, corr_host, image_of_host, model_off, n_models, obj_model, obj_pose, n_obj, cam, n_images,
+                     min_points, feature_distance, min_score, score, keep, out_order, cl_members, cl_off, n_kept, nullptr);
+}
+
+// TestPoints of FILTER_PROJECTION_DEPTH_CPU (moped3d .../filter/FILTER_PROJECTION_DEPTH_CPU.hpp:94-116)
+int mh_filter_depth_set_points(mh_ctx* ctx, const float* xyz_host, const int32_t* off_host, int n_models) {
+  if (!ctx || n_models < 0) return MH_ERR_ARG;
+  mh_ctx::FilterDepthState& fd = ctx->fdepth;
+  if (n_models == 0) {
+    fd.n_models = 0;
+    return MH_OK;
+  }
+  auto refuse = [&](const char* why) {
+    ctx->err = std::string("mh_filter_depth_set_points: ") + why;
+    return MH_ERR_ARG;
+  };
+  if (!off_host || off_host[0] != 0) return refuse("offsets must start at 0");
+  for (int m = 0; m < n_models; ++m)
+    if (off_host[m + 1] < off_host[m]) return refuse("offsets must not decrease");
+  const int total = off_host[n_models];
+  if (total > 0 && !xyz_host) return refuse("no points");
+  if (int rc_enter = mh::enter(ctx)) return rc_enter;
+  hipStream_t s = ctx->stream;
+  fd.n_models = 0;   // (a failure below leaves "no points")
+  MH_HIP(ctx, fd.pts.ensure(3 * (size_t)std::max(total, 1), s));
+  MH_HIP(ctx, fd.off.ensure((size_t)n_models + 1, s));
+  MH_HIP(ctx, hipStreamSynchronize(s));   // frames in flight still read the old points
+  if (total > 0) MH_HIP(ctx, hipMemcpy(fd.pts, xyz_host, 3 * (size_t)total * sizeof(float), hipMemcpyHostToDevice));
+  MH_HIP(ctx, hipMemcpy(fd.off, off_host, ((size_t)n_models + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+  fd.n_models = n_models;
+  fd.db_models = ctx->n_models;                                    // mh_db_size
+  fd.db_generation = ctx->store ? ctx->store->generation : 0;      // mh_db_generation
+  return MH_OK;
+}
+
+// FILTER_PROJECTION_DEPTH_CPU::process (moped3d .../filter/FILTER_PROJECTION_DEPTH_CPU.hpp:140-329)
+int mh_filter_depth(mh_ctx* ctx, const mh_corr* corr_host, const int32_t* model_off, int n_models,
+                    const int32_t* obj_model, const float* obj_pose, int n_obj, const mh_cam* cam, int min_points,
+                    float feature_distance, float min_score, const mh_cam* depth_cam, const mh_filter_depth_params* prm,
+                    float* score, uint8_t* keep, int32_t* out_order, int32_t* cl_members, int32_t* cl_off,
+                    int32_t* n_kept, float* incorrect_score, int32_t* used, int32_t* plausible) {
+  if (!ctx) return MH_ERR_ARG;
+  if (!depth_cam || !prm || !model_off || n_models <= 0 || n_obj < 0 || !cam || !n_kept || (n_obj > 0 && (!obj_model || !obj_pose))) {
+    ctx->err = "mh_filter_depth: bad argument";
+    return MH_ERR_ARG;
+  }
+  if (!ctx->depth_img.img) {
+    ctx->err = "mh_filter_depth: no depth map (mh_frame_set_depth_image / mh_frame_set_depth_image_host)";
+    return MH_ERR_ARG;
+  }
+  if (int rc = filter_depth_points_ok(ctx, "mh_filter_depth", n_models)) return rc;
+  for (int o = 0; o < n_obj; ++o)   // (the kernel reads the model's slice of the test points)
+    if (obj_model[o] < 0 || obj_model[o] >= n_models) {
+      ctx->err = "mh_filter_depth: object model outside [0, n_models)";
+      return MH_ERR_ARG;
+    }
+  const FilterDepthCall dc{depth_cam, prm, incorrect_score, used, plausible};
+  return filter_impl(ctx, corr_host, nullptr, model_off, n_models, obj_model, obj_pose, n_obj, cam, 1, min_points,
+                     feature_distance, min_score, score, keep, out_order, cl_members, cl_off, n_kept, &dc);
 }
 
 }  // extern "C"

@@ -150,6 +150,7 @@ int check_frame_args(mh_ctx* ctx, mh_comm* comm, const float* q_desc_dev, const 
     ctx->err = "mh_comm: the communicator was made for another device";
     return MH_ERR_ARG;
   }
+  if (int rc = mh::filter_depth_frame_ok(ctx, "mh_frame_enqueue_sharded", prm, 1, true)) return rc;   // (before the exchange)
   if (B > 1 && (ctx->q_depth || ctx->depth_img.img || ctx->rules.on)) {
     ctx->err = "sharded batch: depth attributes and depth maps / rules belong to ONE frame";
     return MH_ERR_ARG;

@@ -276,6 +276,18 @@ struct mh_ctx {
   mh::DevBuf<unsigned char> df_buf;   // mh_depth_fill[_batch]: [status words | per frame: downscaled depths, downscaled distances]
   size_t lk_scratch_limit = (size_t)4 << 30;   // bytes; mh_set_linkage_scratch_limit
 
+  // moped3d FILTER_PROJECTION_DEPTH instead of FILTER_PROJECTION (mh_filter_depth_set_points, mh_frame_set_filter_depth)
+  struct FilterDepthState {
+    mh::DevBuf<float> pts;        // device [total][3]: the models' test points, model after model
+    mh::DevBuf<int32_t> off;      // device [n_models + 1]
+    int n_models = 0;             // 0: no points set
+    int db_models = 0;            // the context's database when they were set: its model count (mh_db_size) ...
+    uint64_t db_generation = 0;   // ... and its generation (mh_db_generation)
+    bool on[2] = {false, false};  // the frames' FILTER / FILTER2 are the depth class
+    mh_filter_depth_params prm[2] = {};
+    mh_cam cam = {};              // the depth map's K and pose
+  } fdepth;
+
   // mh_frame_fetch_batch_async / mh_frame_fetch_previous_async: delivery of a batch's objects into the caller's pinned block
   struct Delivery {
     hipEvent_t done = nullptr;          // recorded behind the delivery on the context's stream
@@ -308,6 +320,12 @@ namespace mh {
 int use_stream(mh_ctx* ctx);  // make sure ctx->stream is valid (creates the own stream lazily)
 void bind_store(mh_ctx* ctx);   // the context's view of its store (api.hip)
 void db_poll_held(mh_ctx* ctx, bool wait);   // db_edit.hip: let go of adopted-away stores whose event has completed (wait: all of them)
+// The depth FILTER (mh_frame_set_filter_depth).  filter_depth_points_ok: the test points are set, for n_models models, and
+// the context's database is the one they were set for -- else MH_ERR_ARG with `who` in the message.
+// filter_depth_frame_ok: what an entry point asks before it enqueues anything of a frame that has the depth FILTER in
+// a slot (no such frame: MH_OK) -- a depth map, one camera, no shards' blocks (`sharded`), the points.
+int filter_depth_points_ok(mh_ctx* ctx, const char* who, int n_models);
+int filter_depth_frame_ok(mh_ctx* ctx, const char* who, const mh_frame_params* prm, int n_cameras = 1, bool sharded = false);
 int ensure_frame_buffers(mh_ctx* ctx, int Q);
 int ensure_scratch(mh_ctx* ctx, size_t bytes);
 int ensure_pinned(mh_ctx* ctx, size_t bytes);

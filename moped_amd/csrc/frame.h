@@ -123,6 +123,10 @@ bool merged_batch_ok(const mh_ctx* ctx, const mh_frame_params* prm, bool attrs_o
 int ensure_batch_arenas(mh_ctx* ctx, int B);
 int ensure_linkage_scratch(mh_ctx* ctx, size_t floats);
 FilterBuffers make_fb(const FrameState* fs, int n_models);
+// filter_depth_kernel's arguments from the context's test points, a depth map and the class's parameters (the per-object
+// outputs stay off)
+FilterDepthArgs make_filter_depth_args(const mh_ctx* ctx, const DepthImage& dimg, const mh_filter_depth_params& prm,
+                                       const mh_cam& depth_cam);
 void stamp(mh_ctx* ctx, int i);
 
 // api_frame.hip.  The frame's cameras into the context's device table.

@@ -154,6 +154,56 @@ FilterBuffers make_fb(const FrameState* fs, int n_models) {
   return fb;
 }
 
+FilterDepthArgs make_filter_depth_args(const mh_ctx* ctx, const DepthImage& dimg, const mh_filter_depth_params& prm,
+                                       const mh_cam& depth_cam) {
+  FilterDepthArgs a;
+  a.pts = ctx->fdepth.pts;
+  a.pts_off = ctx->fdepth.off;
+  a.img = dimg.img;
+  a.fill = dimg.fill;
+  a.w = dimg.w;
+  a.h = dimg.h;
+  a.dcam = make_devcam(depth_cam);
+  a.plausible_sq_distance = prm.plausible_sq_distance;
+  a.depth_fraction = prm.depth_fraction;
+  a.min_keypoint_fraction = prm.min_keypoint_fraction;
+  return a;
+}
+
+int filter_depth_points_ok(mh_ctx* ctx, const char* who, int n_models) {
+  const mh_ctx::FilterDepthState& fd = ctx->fdepth;
+  const char* why = nullptr;
+  if (fd.n_models <= 0)
+    why = "no test points: mh_filter_depth_set_points first";
+  else if (fd.db_models != ctx->n_models || fd.db_generation != (ctx->store ? ctx->store->generation : 0))
+    why = "the context's database is not the one the test points were set for: mh_filter_depth_set_points again after a DB "
+          "edit or upload";
+  else if (fd.n_models != n_models)
+    why = "the test points are for another number of models: mh_filter_depth_set_points with one slice per model";
+  if (!why) return MH_OK;
+  ctx->err = std::string(who) + ": depth FILTER: " + why;
+  return MH_ERR_ARG;
+}
+
+int filter_depth_frame_ok(mh_ctx* ctx, const char* who, const mh_frame_params* prm, int n_cameras, bool sharded) {
+  const mh_ctx::FilterDepthState& fd = ctx->fdepth;
+  if (!(fd.on[0] || fd.on[1]) || !prm || !prm->run_stage2) return MH_OK;
+  const char* why = nullptr;
+  if (sharded)
+    why = "frames of a sharded database cannot take it (model indices are shard-local, the test points are not): "
+          "mh_frame_set_filter_depth(ctx, NULL, NULL, NULL) on the shards, the check on the gathered objects";
+  else if (n_cameras > 1 || (ctx->q_img && ctx->n_images > 1))
+    why = "one camera per frame: mh_frame_set_images(ctx, NULL, NULL, 0) / one image per frame, or "
+          "mh_frame_set_filter_depth(ctx, NULL, NULL, NULL)";
+  else if (!ctx->depth_img.img)
+    why = "no depth map: mh_frame_set_depth_image[_batch | _host] first";
+  if (why) {
+    ctx->err = std::string(who) + ": depth FILTER (mh_frame_set_filter_depth): " + why;
+    return MH_ERR_ARG;
+  }
+  return filter_depth_points_ok(ctx, who, ctx->n_models);
+}
+
 namespace {
 
 // Result block of a frame that stops after POSE (run_stage2 = 0): the valid objects in
@@ -301,6 +351,10 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
     dimg.img = c.img;
     dimg.fill = c.fill;
   }
+  // moped3d's depth FILTER in a slot (mh_frame_set_filter_depth): whole frames only -- mh_step_filter stays the plain class
+  const bool fdepth = (ctx->fdepth.on[0] || ctx->fdepth.on[1]) && prm->run_stage2 && !stepped;
+  if (fdepth)
+    if (int rc = filter_depth_frame_ok(ctx, "frame", prm, 1, c.gathered != nullptr)) return rc;
   if (multi && (ctx->q_depth || dimg.img || ctx->linkage_on)) {
     ctx->err = "frames with several images: the moped3d depth steps are single-camera";
     return MH_ERR_ARG;
@@ -409,7 +463,11 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
     fb.cams = ctx->cams_view;
     fb.n_images = ctx->n_images;
   }
-  const bool fused = fuse_filter && prm->run_stage2 && !ctx->timing && !stepped;   // (stage timing wants the steps apart)
+  // (stage timing wants the steps apart; the depth FILTER is a launch of its own: not fused into the POSE tail)
+  const bool fused = fuse_filter && prm->run_stage2 && !ctx->timing && !stepped && !fdepth;
+  FilterDepthArgs fda[2];
+  for (int k = 0; fdepth && k < 2; ++k)
+    if (ctx->fdepth.on[k]) fda[k] = make_filter_depth_args(ctx, dimg, ctx->fdepth.prm[k], ctx->fdepth.cam);
   // (one frame alone in result slot 0: FILTER2's tail also writes the host's block, mh_frame_fetch reads it without a copy)
   fs->host_armed = batch_n == 1 && c.slot == 0 && prm->run_stage2 && fs->host_block && !stepped;
   if (fs->host_armed) ++fs->host_seq_expect;
@@ -448,7 +506,10 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
   stamp(ctx, 4);
   if (prm->run_stage2) {
     // FILTER (snap[3] = objects kept)
-    if (!fused && runs(3))
+    if (!fused && runs(3) && fdepth && ctx->fdepth.on[0])
+      launch_filter_depth(fb, dc, prm->f1_min_points, prm->f1_feature_distance, prm->f1_min_score, fda[0],
+                          fs->n_slots, fs->n_clusters2, fs->counts, ft1, s);
+    else if (!fused && runs(3))
       launch_filter(fb, dc, prm->f1_min_points, prm->f1_feature_distance, prm->f1_min_score,
                     fs->n_slots, fs->n_clusters2, fs->counts, ft1, s);
     stamp(ctx, 5);
@@ -462,7 +523,10 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
                 &split);
     stamp(ctx, 6);
     // FILTER2 (+ the frame's result block)
-    if (!fused && runs(5))
+    if (!fused && runs(5) && fdepth && ctx->fdepth.on[1])
+      launch_filter_depth(fb, dc, prm->f2_min_points, prm->f2_feature_distance, prm->f2_min_score, fda[1],
+                          fs->n_slots, fs->n_clusters, fs->counts, ft2, s);
+    else if (!fused && runs(5))
       launch_filter(fb, dc, prm->f2_min_points, prm->f2_feature_distance, prm->f2_min_score,
                     fs->n_slots, fs->n_clusters, fs->counts, ft2, s);
     stamp(ctx, 7);
@@ -486,11 +550,13 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
 // A depth MAP per frame (mh_frame_set_depth_image_batch with as many maps as the batch has frames: `maps_for`), the depth
 // rules and the linkage clusterer travel with it too (round 4): depth_patch / feature_density / group / linkage_models
 // take frame f's map from a DepthMaps table and its rule buffers behind those of the frames before it.
+// Not with the depth FILTER (mh_frame_set_filter_depth): filter_depth_kernel is a per-frame launch.
 bool merged_batch_ok(const mh_ctx* ctx, const mh_frame_params* prm, bool attrs_ok, int maps_for) {
   static const bool on = exp_int("MH_MERGE_BATCH", 1) != 0;
   static const bool fuse_filter = exp_int("MH_FUSE_FILTER", 1) != 0;
   static const bool merge_maps = exp_int("MH_MERGE_MAPS", 1) != 0;
   const bool maps_ok = merge_maps && attrs_ok && maps_for > 1 && ctx->batch_imgs == maps_for && ctx->depth_img.img;
+  if ((ctx->fdepth.on[0] || ctx->fdepth.on[1]) && prm->run_stage2) return false;   // the depth FILTER: frame after frame, each with its own map
   return on && fuse_filter && prm->run_stage2 && !ctx->timing && (attrs_ok || !ctx->q_depth) &&
          (maps_ok || (!ctx->depth_img.img && !ctx->rules.on && !ctx->linkage_on)) && !(ctx->q_img && ctx->n_images > 1);
 }

@@ -319,4 +319,26 @@ void launch_filter(const FilterBuffers& fb, const DevCam& cam, int min_points,
                    float feature_distance, float min_score, int32_t* n_slots_dev,
                    int32_t* n_clusters_dev, FrameCounts* counts, const FilterTail& tail, hipStream_t s);
 
+// ---- filter, depth class (moped3d FILTER_PROJECTION_DEPTH_CPU; filter_depth.hip) ---------
+// What filter_depth_kernel needs beside launch_filter's arguments: the models' test points (TestPoints[m] of
+// FILTER_PROJECTION_DEPTH_CPU.hpp:94-116 = rows [pts_off[m], pts_off[m + 1]) of pts), the frame's depth map with its
+// camera (:155-173) and the class's three own constructor arguments (:66-73).
+struct FilterDepthArgs {
+  const float* pts = nullptr;         // [total][3] model coordinates
+  const int32_t* pts_off = nullptr;   // [n_models + 1]
+  const float4* img = nullptr;        // [h][w] (x, y, z, norm): the map's z is word 2 (Image::getDepth)
+  const float* fill = nullptr;        // [h][w] fill distance, nullptr = every pixel measured
+  int w = 0, h = 0;
+  DevCam dcam;                        // the depth map's K and pose
+  float plausible_sq_distance = 0.f, depth_fraction = 0.f, min_keypoint_fraction = 0.f;
+  // optional, per object slot as it was BEFORE the erase: the IS that was subtracted, usedKeypointCount, clusterSize
+  float* out_is = nullptr;
+  int32_t* out_used = nullptr;
+  int32_t* out_plausible = nullptr;
+};
+// launch_filter with the depth term; one image (fb.m_img must be nullptr)
+void launch_filter_depth(const FilterBuffers& fb, const DevCam& cam, int min_points, float feature_distance,
+                         float min_score, const FilterDepthArgs& da, int32_t* n_slots_dev, int32_t* n_clusters_dev,
+                         FrameCounts* counts, const FilterTail& tail, hipStream_t s);
+
 }  // namespace mh

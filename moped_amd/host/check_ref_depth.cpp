@@ -11,4 +11,5 @@
 #include "MATCH_ADAPTIVE_BRUTE_HIP.hpp"
 #include "CLUSTER_LINKAGE_HIP.hpp"
 #include "POSE_RANSAC_P3P_DEPTH_HIP.hpp"
+#include "FILTER_PROJECTION_DEPTH_HIP.hpp"
 int main() { return 0; }

@@ -308,6 +308,21 @@ class FramePipeline:
         c.frame_enqueue_image_batch(list(gray_ptrs), w, h, double_size, max_keypoints, self.K, self.cam, self.params, seeds,
                                     _cam_struct=self._cam)
 
+    def set_filter_depth(self, points_xyz, points_off, f1=None, f2=None, depth_cam=None):
+        """FILTER (f1) and / or FILTER2 (f2) of the frames enqueued from now on as moped3d's FILTER_PROJECTION_DEPTH: the
+        pose of every object is tested against the frame's depth map, so enqueue_kinect_batch and the other depth-map
+        enqueues deliver depth-verified objects.  points_xyz [total, 3], points_off [n_models + 1]: the models' test
+        points (the caller's sample); f1, f2: (PlausibleSqDistance, DepthFraction, MinKeypointFraction) or None = that slot
+        stays the plain class, both None = off; depth_cam: (K, pose) of the depth map, default the pipeline's camera.
+        Every slot's context is set.  After add_model / replace_model / remove_model the points are stale: call again."""
+        if self.exchange:
+            raise ValueError("the depth FILTER needs one GPU's whole database: the test points are per global model")
+        K, cam = (self.K, self.cam) if depth_cam is None else depth_cam
+        for c in self.ctxs:
+            if f1 is not None or f2 is not None:
+                c.filter_depth_set_points(points_xyz, points_off)
+            c.frame_set_filter_depth(f1, f2, K, cam)
+
     def fetch_batch(self, slot: int, B: int):
         return [self.ctxs[slot].frame_fetch_slot(f) for f in range(B)]
 

@@ -12,6 +12,11 @@
 (b) DEPTHFILL alone: device events around sixteen mh_depth_fill calls of 640 x 480 maps against one mh_depth_fill_batch
     of the same maps.
 
+(c) --filter-depth (instead of (a) and (b)): batches of 16 with moped3d's depth-verified FILTER in both slots
+    (FramePipeline.set_filter_depth, 300 test points per model) against the same batches with it off, alternating rounds,
+    on maps that arrive filled; then the FILTER and FILTER2 stage times of one frame alone with stage timing on (device
+    events around filter_depth_kernel against filter_kernel).  > profiles/filter_depth.txt
+
 usage: python scripts/kinect_image_bench.py [--models 5] [--rounds 5] [--seconds 1.2] > profiles/kinect_image_batch.txt
 One process on an otherwise idle device; every shape is warmed before it is timed."""
 import argparse
@@ -52,6 +57,7 @@ def main():
     ap.add_argument("--models", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--seconds", type=float, default=1.2)
+    ap.add_argument("--filter-depth", action="store_true", help="(c): what the depth FILTER costs a batch of 16")
     args = ap.parse_args()
     import torch
     from moped_amd import capi, moped3d, synth
@@ -117,6 +123,78 @@ def main():
     def found(slot_fetch):
         objs, counts = slot_fetch
         return int(len(objs) > 0 and objs[np.argmax(objs["score"])]["model"] == args.models)
+
+    if args.filter_depth:
+        # (c) test points: 300 of every model's own points (the planar model: its keypoints), the map's camera = the image's
+        rng = np.random.default_rng(5)
+        pts, off = [], [0]
+        for m in range(n_models):
+            rows = np.nonzero(model_of == m)[0]
+            pts.append(all_xyz[rng.choice(rows, min(300, len(rows)), replace=False)])
+            off.append(off[-1] + len(pts[-1]))
+        pts, off = np.concatenate(pts), np.array(off, np.int32)
+        fd_prm = (64.0, 0.1, 0.1)                         # PlausibleSqDistance, DepthFraction, MinKeypointFraction
+        for s_ in range(SLOTS):                           # the maps arrive filled: DEPTHFILL once, outside the windows
+            restore(s_)
+            pipe.ctxs[s_].depth_fill_batch_dev([work[s_][j].data_ptr() for j in range(B)],
+                                               [fill[s_][j].data_ptr() for j in range(B)], W, H, K, 8, False)
+        pipe.synchronize()
+
+        def filled_batches(groups):
+            for g in range(groups):
+                s_ = g % SLOTS
+                pipe.enqueue_kinect_batch(s_, [imgs[(g * B + j) % len(imgs)].data_ptr() for j in range(B)],
+                                          [work[s_][j].data_ptr() for j in range(B)], [fill[s_][j].data_ptr() for j in range(B)],
+                                          W, H, [g * B + j + 1 for j in range(B)], fill_scale=None, max_keypoints=CAP)
+
+        def switch(on):
+            if on:
+                pipe.set_filter_depth(pts, off, f1=fd_prm, f2=fd_prm)
+            else:
+                pipe.set_filter_depth(None, None)
+
+        print("# Kinect batches of 16 (filled maps): depth FILTER in both slots, 300 test points per model, against off")
+        print(f"# {SLOTS} slots, 640x480, {n_models} models, GPU_MAX_HW_QUEUES={os.environ.get('GPU_MAX_HW_QUEUES')}")
+        win = {}
+        for on in (False, True):
+            switch(on)
+            filled_batches(2 * SLOTS)
+            dt = timed(filled_batches, 2 * SLOTS)
+            win[on] = max(SLOTS, int(np.ceil(args.seconds / dt * 2)) * SLOTS)
+            hits = sum(found(pipe.ctxs[SLOTS - 1].frame_fetch_slot(j)) for j in range(B))
+            print(f"# depth FILTER {'on ' if on else 'off'}: warm; {win[on] * B} frames per window; planted model best in {hits} of {B}")
+        rates = {False: [], True: []}
+        for r in range(args.rounds):
+            for on in (False, True):
+                switch(on)
+                dt = timed(filled_batches, win[on])
+                rates[on].append(win[on] * B / dt)
+                print(f"(c) round {r + 1} depth FILTER {'on ' if on else 'off'} {rates[on][-1]:9.1f} frames/s   window {dt:.3f} s")
+        for on in (False, True):
+            v = rates[on]
+            print(f"(c) depth FILTER {'on ' if on else 'off'} min {min(v):.1f} max {max(v):.1f} spread {max(v) - min(v):.1f} frames/s")
+        print(f"(c) on / off: {np.median(rates[True]) / np.median(rates[False]):.3f} of the merged, fused batch's rate (medians)")
+        # the FILTER launches of one frame alone, stage timing on (both forms then run FILTER as launches of their own)
+        c = pipe.ctxs[0]
+        c.enable_timing(True)
+        c.frame_set_depth_image(work[0][0].data_ptr(), fill[0][0].data_ptr(), W, H, capi.DEPTH_BACKPROJECTION, 0.5, 0.1)
+        for on in (False, True):
+            switch(on)
+            f1, f2 = [], []
+            for rep_ in range(-3, 20):
+                c.frame_enqueue_image(imgs[0].data_ptr(), W, H, True, CAP, K, CAM0, prm, rep_ + 10, _cam_struct=cam)
+                objs, _ = c.frame_fetch()
+                t = c.timing()
+                if rep_ >= 0:
+                    f1.append(t["filter1_ms"])
+                    f2.append(t["filter2_ms"])
+            print(f"(c) one frame, {'filter_depth_kernel' if on else 'filter_kernel      '}: FILTER median {np.median(f1) * 1e3:.1f} us "
+                  f"(min {min(f1) * 1e3:.1f}, max {max(f1) * 1e3:.1f}), FILTER2 median {np.median(f2) * 1e3:.1f} us "
+                  f"(min {min(f2) * 1e3:.1f}, max {max(f2) * 1e3:.1f}); {len(objs)} objects delivered (device events, 20 frames)")
+        c.enable_timing(False)
+        switch(False)
+        pipe.close()
+        return
 
     print("# Kinect frames, image + depth map -> objects: frame by frame against batches of 16")
     print(f"# {SLOTS} slots, 640x480, {args.models} synthetic models + the planar model, keypoint capacity {CAP}, "
