@@ -417,12 +417,32 @@ int mh_filter_depth(mh_ctx* ctx, const mh_corr* corr_host, const int32_t* model_
 /* FILTER (f1) and / or FILTER2 (f2) of the frames enqueued from now on are FILTER_PROJECTION_DEPTH_CPU (:140-329) with
  * the frame's depth map (mh_frame_set_depth_image[_batch | _host]) seen through depth_cam, MinPoints / FeatureDistance /
  * MinScore from mh_frame_params as before.  NULL: that slot stays FILTER_PROJECTION_CPU; both NULL: off.  Such a frame
- * runs its FILTER steps as launches of their own and the frames of a batch one after the other, each with its own map.
+ * runs its FILTER steps where a plain one does, in the tails of the POSE launches (POSE always as its two launches:
+ * hypotheses, then refines), and the frames of a batch that brings a map per frame (mh_frame_set_depth_image_batch with
+ * as many maps as frames) share one launch per stage, every object scored against its own frame's map; mh_frame_route
+ * says which way the last one went.  The FILTER steps are launches of their own -- the same objects, bit for bit -- with
+ * stage timing on (mh_enable_timing), with MH_FUSE_FILTER=0, with mh_pose_set_split(ctx, 0) / MH_POSE_SPLIT=0 and with
+ * more than four objects per cluster (the one-launch POSE kernel does not carry the depth class); then, and with
+ * MH_MERGE_BATCH=0 or a number of maps other than the number of frames, the frames of a batch run one after the other.
+ * Frames that run one after the other with different maps and fused FILTERs cost two one-wavefront launches each: the
+ * maps' addresses are stored on the device whenever they change.
  * Refused with MH_ERR_ARG before anything is enqueued: no depth map, several cameras, the sharded entry points
  * (mh_frame_enqueue_sharded*, mh_frame_enqueue_rest*), test points not set or stale.  mh_step_filter stays the plain
  * class. */
 int mh_frame_set_filter_depth(mh_ctx* ctx, const mh_filter_depth_params* f1, const mh_filter_depth_params* f2,
                               const mh_cam* depth_cam);
+
+/* How the last frame or batch enqueued on the context went through CLUSTER .. FILTER2: out[0] the frames it carried,
+ * out[1] 1 if they shared one launch per stage (a merged batch), out[2] 1 if the FILTER steps ran in the tails of the
+ * POSE launches (0: as launches of their own), out[3] bit 0 set if FILTER was the depth class, bit 1 if FILTER2 was.
+ * Host bookkeeping of the enqueue: no device work, no synchronisation.  All zero before the first frame. */
+int mh_frame_route(mh_ctx* ctx, int32_t out[4]);
+
+/* Debug entry, like mh_sift_debug_*: the device form mh_filter_depth scores F1 with.  0 (default): a workgroup walks the
+ * object slots, lane 0 adds the terms out of LDS -- the stand-alone FILTER launch of a frame.  1: one wavefront per
+ * object slot and no LDS -- the form the POSE tails of a fused frame run.  The results are the same bit for bit; frames
+ * ignore the setting. */
+int mh_filter_depth_debug_form(mh_ctx* ctx, int form);
 
 /* ---- whole frame, device resident --------------------------------------------- */
 

@@ -144,6 +144,7 @@ EXPORTS = [
     "mh_frame_enqueue_images", "mh_frame_enqueue_images_batch", "mh_frame_set_undistort_images", "mh_frame_image_counts",
     "mh_frame_features_image_dev",
     "mh_filter_depth_set_points", "mh_filter_depth", "mh_frame_set_filter_depth",
+    "mh_frame_route", "mh_filter_depth_debug_form",
 ]
 COMM_ID_BYTES = 128      # MH_COMM_ID_BYTES
 EX2_OBJECTS = 62         # MH_EX2_OBJECTS
@@ -370,6 +371,9 @@ def load():
                                       C.POINTER(mh_filter_depth_params), vp, vp, vp, vp, vp, C.POINTER(C.c_int32), vp, vp, vp]
         L.mh_frame_set_filter_depth.argtypes = [vp, C.POINTER(mh_filter_depth_params), C.POINTER(mh_filter_depth_params),
                                                 C.POINTER(mh_cam)]
+    if hasattr(L, "mh_frame_route"):   # (the same)
+        L.mh_frame_route.argtypes = [vp, vp]
+        L.mh_filter_depth_debug_form.argtypes = [vp, i32]
     _lib = L
     return L
 
@@ -1186,6 +1190,19 @@ class Context:
         self._ck(self.L.mh_frame_set_filter_depth(self.h, C.byref(p1) if p1 is not None else None,
                                                   C.byref(p2) if p2 is not None else None,
                                                   C.byref(dc) if dc is not None else None), "mh_frame_set_filter_depth")
+
+    def frame_route(self):
+        """How the last frame or batch enqueued went through CLUSTER .. FILTER2 (mh_frame_route) -> int32 [4]: frames,
+        1 = they shared their launches, 1 = the FILTER steps ran in the POSE tails, depth class bits (1 FILTER, 2 FILTER2).
+        Host bookkeeping: no synchronisation."""
+        o = np.zeros(4, np.int32)
+        self._ck(self.L.mh_frame_route(self.h, _ptr(o)), "mh_frame_route")
+        return o
+
+    def filter_depth_debug_form(self, form):
+        """Debug: the device form filter_depth() scores with -- 0 the workgroup form (default), 1 the wave form the fused
+        POSE tails run.  Frames ignore it."""
+        self._ck(self.L.mh_filter_depth_debug_form(self.h, int(form)), "mh_filter_depth_debug_form")
 
     # ---- frame (device pointers as ints) ----
     def frame_enqueue(self, q_desc_ptr, q_uv_ptr, Q, K, cam, params: mh_frame_params, seed=1):

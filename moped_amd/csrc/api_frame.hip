@@ -162,6 +162,7 @@ int rest_of_batch(mh_ctx* ctx, FrameCall c, int B, const uint64_t* seeds, bool m
     if (gathered) stamp(ctx, 1);
     rc = frame_rest(ctx, c);
   }
+  if (rc == MH_OK) ctx->frame_route[0] = B;   // (mh_frame_route: B frames, one after the other)
   return rc;
 }
 
@@ -520,6 +521,13 @@ int mh_frame_set_filter_depth(mh_ctx* ctx, const mh_filter_depth_params* f1, con
   if (f1) fd.prm[0] = *f1;
   if (f2) fd.prm[1] = *f2;
   if (depth_cam) fd.cam = *depth_cam;
+  return MH_OK;
+}
+
+// how the last frame or batch enqueued went through CLUSTER .. FILTER2 (frame_rest's record; no device work)
+int mh_frame_route(mh_ctx* ctx, int32_t out[4]) {
+  if (!ctx || !out) return MH_ERR_ARG;
+  for (int k = 0; k < 4; ++k) out[k] = ctx->frame_route[k];
   return MH_OK;
 }
 

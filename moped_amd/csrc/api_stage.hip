@@ -420,8 +420,8 @@ static int filter_impl(mh_ctx* ctx, const mh_corr* corr_host, const int32_t* ima
     da.out_is = d_is;
     da.out_used = reinterpret_cast<int32_t*>(d_is) + n_obj;
     da.out_plausible = reinterpret_cast<int32_t*>(d_is) + 2 * (size_t)n_obj;
-    launch_filter_depth(fb, make_devcam(*cam), min_points, feature_distance, min_score, da, fs->n_slots, fs->n_clusters,
-                        fs->counts, tail, s);
+    (ctx->fdepth.debug_form == 1 ? launch_filter_depth_wave : launch_filter_depth)(
+        fb, make_devcam(*cam), min_points, feature_distance, min_score, da, fs->n_slots, fs->n_clusters, fs->counts, tail, s);
   } else
     launch_filter(fb, make_devcam(*cam), min_points, feature_distance, min_score, fs->n_slots, fs->n_clusters, fs->counts,
                   tail, s);
@@ -533,6 +533,17 @@ int mh_filter_depth(mh_ctx* ctx, const mh_corr* corr_host, const int32_t* model_
   const FilterDepthCall dc{depth_cam, prm, incorrect_score, used, plausible};
   return filter_impl(ctx, corr_host, nullptr, model_off, n_models, obj_model, obj_pose, n_obj, cam, 1, min_points,
                      feature_distance, min_score, score, keep, out_order, cl_members, cl_off, n_kept, &dc);
+}
+
+// which device form of F1 mh_filter_depth scores with (a debug entry; frames ignore it)
+int mh_filter_depth_debug_form(mh_ctx* ctx, int form) {
+  if (!ctx) return MH_ERR_ARG;
+  if (form != 0 && form != 1) {
+    ctx->err = "mh_filter_depth_debug_form: 0 (the workgroup form) or 1 (filter_depth_score_wave)";
+    return MH_ERR_ARG;
+  }
+  ctx->fdepth.debug_form = form;
+  return MH_OK;
 }
 
 }  // extern "C"

@@ -286,7 +286,11 @@ struct mh_ctx {
     bool on[2] = {false, false};  // the frames' FILTER / FILTER2 are the depth class
     mh_filter_depth_params prm[2] = {};
     mh_cam cam = {};              // the depth map's K and pose
+    int debug_form = 0;           // mh_filter_depth_debug_form: 0 the workgroup form, 1 filter_depth_score_wave
   } fdepth;
+  // the last frame or batch enqueued: frames, 1 = they shared their launches, 1 = FILTER in the POSE tails, depth class
+  // bits (mh_frame_route; written by frame_rest on the host)
+  int32_t frame_route[4] = {0, 0, 0, 0};
 
   // mh_frame_fetch_batch_async / mh_frame_fetch_previous_async: delivery of a batch's objects into the caller's pinned block
   struct Delivery {

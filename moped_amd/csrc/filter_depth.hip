@@ -13,27 +13,17 @@
 //      `object->score < MinScore` (:309) sees the penalty.
 //  F2..F4  filter_finish (filter_dev.h), unchanged: it reads the claims' object ids and obj_score, never the claims'
 //      scores, so obj_score = score - IS and a claim key made of `score` need no second array.
+// The arithmetic lives in filter_depth_dev.h, in two forms of one F1: filter_depth_score (below; a workgroup walks the
+// slots, lane 0 adds out of LDS) for the launch of its own, filter_depth_score_wave (one object, one wavefront, no LDS)
+// for the POSE tails of a fused frame (pose.hip) and for filter_depth_wave_kernel.
 // The (int) of a projected coordinate that is NaN, infinite or outside int's range is undefined in the reference: here
 // such a point is off the image.  One image per frame (the reference projects the matches through their own image; the
 // callers refuse several).
-#include "filter_dev.h"
+#include "filter_depth_dev.h"
 
 namespace mh {
 
 namespace {
-
-// (int) p of :226 where the reference defines it; false: NaN, infinite or outside int -- off the image
-__device__ __forceinline__ bool pixel_of(float p, int& i) {
-  if (!(p >= -2147483648.f && p < 2147483648.f)) return false;
-  i = (int)p;   // truncation toward zero: (-1, 0) -> 0, inside the image as in the reference
-  return true;
-}
-
-// (int)(MinKeypointFraction * keypoints.size()) of :260; outside int (undefined in the reference): the nearest int, NaN: 0
-__device__ __forceinline__ int int_of(float v) {
-  if (!(v < 2147483648.f)) return v != v ? 0 : 0x7FFFFFFF;
-  return v < -2147483648.f ? (int)0x80000000 : (int)v;
-}
 
 // F1 of the depth class for the object slots first, first + stride, ... (every thread of the workgroup calls it): the
 // slot walk, the score chain and the claims are filter_score's (filter_dev.h), one image.
@@ -42,7 +32,6 @@ __device__ __forceinline__ void filter_depth_score(FilterLds& S, const FilterBuf
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   filter_load_slots(S, fb, n_slots, false);
   const int tw = 64 * wave;   // the wavefront's 64 words of term_s
-  const float* const zmap = reinterpret_cast<const float*>(da.img);
   const int n_listed = S.cnt_s, n_low = min(n_slots, FL_SLOTS);
   for (int idx = first + stride * wave; idx < n_listed + (n_slots - n_low); idx += stride * (FT / 64)) {
     const int o = idx < n_listed ? S.vlist_s[idx] : n_low + (idx - n_listed);
@@ -78,36 +67,9 @@ __device__ __forceinline__ void filter_depth_score(FilterLds& S, const FilterBuf
     int used = 0;               // usedKeypointCount (all lanes)
     for (int base = 0; base < np; base += 64) {
       const int j = base + lane;
-      bool on = false;          // the point falls on a pixel of the map
-      int px = 0;
-      float zp = 0.f;           // putativeDepth
-      if (j < np) {
-        const float* k = da.pts + 3 * (size_t)(pb + j);
-        float wx, wy, wz, cx, cy, cz;
-        tm_apply(T.r, T.t, k[0], k[1], k[2], wx, wy, wz);                       // PoseTM.transform (:220)
-        tm_apply_inv(da.dcam.Rc, da.dcam.tc, wx, wy, wz, cx, cy, cz);           // depthmap->TM.inverseTransform (:221)
-        const float pu = __fadd_rn(__fmul_rn(__fdiv_rn(cx, cz), da.dcam.K[0]), da.dcam.K[2]);   // :223
-        const float pv = __fadd_rn(__fmul_rn(__fdiv_rn(cy, cz), da.dcam.K[1]), da.dcam.K[3]);   // :224
-        int ix = 0, iy = 0;
-        on = pixel_of(pu, ix) && pixel_of(pv, iy) && ix >= 0 && ix < da.w && iy >= 0 && iy < da.h;   // :226-231
-        px = iy * da.w + ix;
-        zp = cz;
-      }
-      // both gathers of the step before either is used: their addresses are the lane's own arithmetic
-      float dist = 0.f, zk = 0.f;
-      if (on) {
-        if (da.fill) dist = da.fill[px];        // distanceMap->getProb (:233)
-        zk = zmap[4 * (size_t)px + 2];          // depthmap->getDepth (:239)
-      }
-      const bool use = on && !(dist > 0.f);     // :234-237
+      bool use;
+      const double term = filter_depth_point_term(T, da, j < np ? da.pts + 3 * (size_t)(pb + j) : nullptr, use);
       used += __popcll(__ballot(use));
-      double term = 0.;
-      if (use && !(zk < zp)) {                  // :244: the sensor saw something in front: an occlusion, nothing added
-        const float cauchy = __fmul_rn(da.depth_fraction, zk);   // :248
-        float t = __fdiv_rn(__fsub_rn(zp, zk), cauchy);          // :250
-        t = __fmul_rn(t, t);                                     // :251
-        term = 1.0 - (1.0 / (1.0 + (double)t));                  // :254
-      }
       S.term_s[tw + lane] = term;
       filter_wave_sync();
       if (lane == 0) {
@@ -117,16 +79,7 @@ __device__ __forceinline__ void filter_depth_score(FilterLds& S, const FilterBuf
       filter_wave_sync();
     }
     // ---- :260-270 ----
-    if (lane == 0) {
-      if (used <= int_of(__fmul_rn(da.min_keypoint_fraction, (float)np)))   // :260
-        IS = 0.f;
-      else
-        IS = __fmul_rn(IS, __fdiv_rn((float)plausible, (float)used));
-      fb.obj_score[o] = __fsub_rn(score, IS);
-      if (da.out_is) da.out_is[o] = IS;
-      if (da.out_used) da.out_used[o] = used;
-      if (da.out_plausible) da.out_plausible[o] = plausible;
-    }
+    if (lane == 0) filter_depth_close(fb, da, o, score, IS, used, plausible, np);
     // ---- the claims, by the projection score (:274-286) ----
     score = __shfl(score, 0);
     if (!(score > 0.f)) continue;
@@ -158,7 +111,33 @@ __global__ __launch_bounds__(FT) void filter_depth_kernel(FilterBuffers fb, DevC
   filter_finish(S, fb, min_points, min_score, n_slots, n_slots_dev, n_clusters_dev, counts, tail);
 }
 
+// The same through filter_depth_score_wave (mh_filter_depth_debug_form 1): every wavefront one object slot at a time --
+// the arithmetic the fused POSE tails run, under the stage-level entry without POSE in between
+__global__ __launch_bounds__(FT) void filter_depth_wave_kernel(FilterBuffers fb, DevCam cam, float feature_distance,
+                                                               int min_points, float min_score, FilterDepthArgs da,
+                                                               int32_t* n_slots_dev, int32_t* n_clusters_dev,
+                                                               FrameCounts* counts, FilterTail tail) {
+  __shared__ FilterLds S;
+  const int n_slots = *n_slots_dev;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int o = (int)blockIdx.x * (FT / 64) + wave; o < n_slots; o += (int)gridDim.x * (FT / 64))
+    if (fb.obj_valid[o])   // (wave-uniform)
+      filter_depth_score_wave(fb, cam, feature_distance, da, o, fb.obj_model[o], fb.obj_pose + 7 * (size_t)o,
+                              fb.obj_pose + 7 * (size_t)o + 4, lane);
+  if (!last_workgroup(tail.ticket)) return;
+  filter_finish(S, fb, min_points, min_score, n_slots, n_slots_dev, n_clusters_dev, counts, tail);
+}
+
 }  // namespace
+
+void launch_filter_depth_wave(const FilterBuffers& fb, const DevCam& cam, int min_points, float feature_distance,
+                              float min_score, const FilterDepthArgs& da, int32_t* n_slots_dev, int32_t* n_clusters_dev,
+                              FrameCounts* counts, const FilterTail& tail, hipStream_t s) {
+  const int want = (fb.max_objects + FT / 64 - 1) / (FT / 64);
+  const int grid = want < 1 ? 1 : (want < FILTER_GRID ? want : FILTER_GRID);
+  hipLaunchKernelGGL(filter_depth_wave_kernel, dim3(grid), dim3(FT), 0, s, fb, cam, feature_distance, min_points,
+                     min_score, da, n_slots_dev, n_clusters_dev, counts, tail);
+}
 
 void launch_filter_depth(const FilterBuffers& fb, const DevCam& cam, int min_points, float feature_distance,
                          float min_score, const FilterDepthArgs& da, int32_t* n_slots_dev, int32_t* n_clusters_dev,

@@ -147,6 +147,19 @@ __device__ __forceinline__ void filter_score(FilterLds& S, const FilterBuffers& 
   }
 }
 
+// The Float += double chain of 64 lanes' terms in lane order, the first cnt of them, in EVERY lane: each lane's 64-bit
+// term read lane by lane with two readlanes.  Adding the 0. of a skipped term leaves the float unchanged, so no lane
+// below cnt is left out.  filter_score_wave's chain, and filter_depth_score_wave's two (filter_depth_dev.h).
+__device__ __forceinline__ float filter_chain_wave(float acc, double term, int cnt) {
+  const unsigned lo = (unsigned)__double_as_longlong(term), hi = (unsigned)((unsigned long long)__double_as_longlong(term) >> 32);
+  for (int j = 0; j < cnt; ++j) {
+    const unsigned long long bits = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)hi, j) << 32) |
+                                    (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)lo, j);
+    acc = (float)((double)acc + __longlong_as_double((long long)bits));
+  }
+  return acc;
+}
+
 // F1 of ONE object by the wavefront that has just refined it (fused FILTER, round 4's end): the closing workgroup of the
 // launch then starts at F2 -- with ten objects in a frame their F1s were 40 us of its tail, one after the other; here they
 // run where the objects are made, on as many compute units.  Same arithmetic as filter_score: 64 matches per step, the
@@ -170,14 +183,7 @@ __device__ __forceinline__ void filter_score_wave(const FilterBuffers& fb, const
     }
     const bool in = e < feature_distance;
     if (in && step < 32) inl_bits |= 1u << step;
-    const double term = in ? 1. / ((double)e + 1.) : 0.;
-    const unsigned lo = (unsigned)__double_as_longlong(term), hi = (unsigned)((unsigned long long)__double_as_longlong(term) >> 32);
-    const int cnt = min(64, n - base);
-    for (int j = 0; j < cnt; ++j) {
-      const unsigned long long bits = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)hi, j) << 32) |
-                                      (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)lo, j);
-      score = (float)((double)score + __longlong_as_double((long long)bits));
-    }
+    score = filter_chain_wave(score, in ? 1. / ((double)e + 1.) : 0., min(64, n - base));
   }
   if (lane == 0) fb.obj_score[o] = score;
   if (!(score > 0.f)) return;

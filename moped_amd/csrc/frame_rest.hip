@@ -463,11 +463,32 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
     fb.cams = ctx->cams_view;
     fb.n_images = ctx->n_images;
   }
-  // (stage timing wants the steps apart; the depth FILTER is a launch of its own: not fused into the POSE tail)
-  const bool fused = fuse_filter && prm->run_stage2 && !ctx->timing && !stepped && !fdepth;
+  // (stage timing wants the steps apart; the depth class's fused F1 lives in the kernels of POSE's two launches only)
+  const bool fdepth_fusable = !fdepth || (ctx->pose_split && pose_launch_splits(prm->pose1) && pose_launch_splits(prm->pose2));
+  const bool fused = fuse_filter && prm->run_stage2 && !ctx->timing && !stepped && fdepth_fusable;
+  // the depth class of a slot: a launch of its own (fda), or -- fused -- FilterFuseDepth behind the slot's fused
+  // arguments, with the map of every frame of a merged batch
   FilterDepthArgs fda[2];
-  for (int k = 0; fdepth && k < 2; ++k)
-    if (ctx->fdepth.on[k]) fda[k] = make_filter_depth_args(ctx, dimg, ctx->fdepth.prm[k], ctx->fdepth.cam);
+  FilterFuseDepth ffd[2];
+  for (int k = 0; fdepth && k < 2; ++k) {
+    if (!ctx->fdepth.on[k]) continue;
+    fda[k] = make_filter_depth_args(ctx, dimg, ctx->fdepth.prm[k], ctx->fdepth.cam);
+    ffd[k].on = 1;
+    ffd[k].args = fda[k];
+    ffd[k].args.img = nullptr;   // (the frames' maps are in the table)
+    ffd[k].args.fill = nullptr;
+    if (maps)
+      ffd[k].maps = *maps;
+    else {
+      ffd[k].maps.img[0] = dimg.img;
+      ffd[k].maps.fill[0] = dimg.fill;
+    }
+  }
+  // (mh_frame_route)
+  ctx->frame_route[0] = batch_n > 1 ? batch_n : 1;
+  ctx->frame_route[1] = batch_n > 1;
+  ctx->frame_route[2] = fused;
+  ctx->frame_route[3] = fdepth ? (ctx->fdepth.on[0] ? 1 : 0) | (ctx->fdepth.on[1] ? 2 : 0) : 0;
   // (one frame alone in result slot 0: FILTER2's tail also writes the host's block, mh_frame_fetch reads it without a copy)
   fs->host_armed = batch_n == 1 && c.slot == 0 && prm->run_stage2 && fs->host_block && !stepped;
   if (fs->host_armed) ++fs->host_seq_expect;
@@ -492,6 +513,8 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
   ff2.min_points = prm->f2_min_points;
   ff2.feature_distance = prm->f2_feature_distance;
   ff2.min_score = prm->f2_min_score;
+  if (fdepth && ctx->fdepth.on[0]) ff1.depth = &ffd[0];
+  if (fdepth && ctx->fdepth.on[1]) ff2.depth = &ffd[1];
   PoseSplit split;
   split.hyp = (fused && ctx->pose_split) ? fs->hyp : nullptr;   // (the refine launch closes the frames through the fused FILTER tail)
   split.pts = fs->rf_pts;
@@ -541,8 +564,8 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
   return MH_OK;
 }
 
-// The frames of a batch can share their launches when nothing of the frame is per-context state: no depth
-// attributes / map / rules (one map per context), one image, the fused FILTER tails (the stand-alone FILTER and
+// The frames of a batch can share their launches when nothing of the frame is per-context state: one image, no depth
+// map / rules / linkage unless every frame brings its own map (below), the fused FILTER tails (the stand-alone FILTER and
 // result-packing kernels are per frame), no stage timing, no graph replay.  MH_MERGE_BATCH=0: frame after frame.
 // Per-query depth ATTRIBUTES (mh_frame_set_depth: B Q entries, frame after frame like the queries) travel with a merged
 // batch where the caller says so (`attrs_ok`: mh_frame_enqueue_batch) -- group_kernel takes frame f's slice, the per-frame
@@ -550,13 +573,17 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
 // A depth MAP per frame (mh_frame_set_depth_image_batch with as many maps as the batch has frames: `maps_for`), the depth
 // rules and the linkage clusterer travel with it too (round 4): depth_patch / feature_density / group / linkage_models
 // take frame f's map from a DepthMaps table and its rule buffers behind those of the frames before it.
-// Not with the depth FILTER (mh_frame_set_filter_depth): filter_depth_kernel is a per-frame launch.
+// The depth FILTER (mh_frame_set_filter_depth) travels with the maps: the fused POSE tails score every object against its
+// own frame's map (FilterFuseDepth, steps.h).
 bool merged_batch_ok(const mh_ctx* ctx, const mh_frame_params* prm, bool attrs_ok, int maps_for) {
   static const bool on = exp_int("MH_MERGE_BATCH", 1) != 0;
   static const bool fuse_filter = exp_int("MH_FUSE_FILTER", 1) != 0;
   static const bool merge_maps = exp_int("MH_MERGE_MAPS", 1) != 0;
   const bool maps_ok = merge_maps && attrs_ok && maps_for > 1 && ctx->batch_imgs == maps_for && ctx->depth_img.img;
-  if ((ctx->fdepth.on[0] || ctx->fdepth.on[1]) && prm->run_stage2) return false;   // the depth FILTER: frame after frame, each with its own map
+  // the depth FILTER: a map per frame, and the fused route (frame_rest: POSE's two launches)
+  if ((ctx->fdepth.on[0] || ctx->fdepth.on[1]) && prm->run_stage2 &&
+      !(maps_ok && ctx->pose_split && pose_launch_splits(prm->pose1) && pose_launch_splits(prm->pose2)))
+    return false;
   return on && fuse_filter && prm->run_stage2 && !ctx->timing && (attrs_ok || !ctx->q_depth) &&
          (maps_ok || (!ctx->depth_img.img && !ctx->rules.on && !ctx->linkage_on)) && !(ctx->q_img && ctx->n_images > 1);
 }

@@ -21,7 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "filter_dev.h"
+#include "filter_depth_dev.h"
 
 MH_TRACE_TU()
 
@@ -928,11 +928,24 @@ __device__ float lm_refine(float* R, float* t, const DevCam* cams, const float* 
 #else
 #define PR_PROF_PARAMS
 #endif
-template <int KIND>
+// The depth class in a fused FILTER slot (FilterFuseDepth, steps.h): filter_depth_score_wave's arguments for frame f,
+// read from device memory here, where an object is scored -- none of it travels through the RANSAC code as kernel
+// arguments.  Only instantiations of their own carry this code (pose_kernel<KIND, true, true>, pose_refine_kernel<KIND,
+// true>): a frame with the depth class always takes the two launches and those kernels, every other frame the kernels
+// it always ran.
+__device__ __forceinline__ void fused_depth_f1(const FilterFuseArgs* __restrict__ fuse, const FilterBuffers& fb, const DevCam& cam,
+                                               int f, int o, int m, const float* quat, const float* trans, int lane) {
+  FilterDepthArgs da = fuse->depth.args;
+  da.img = fuse->depth.maps.img[f];
+  da.fill = fuse->depth.maps.fill[f];
+  filter_depth_score_wave(fb, cam, fuse->feature_distance, da, o, m, quat, trans, lane);
+}
+
+template <int KIND, bool DEPTH = false /* the refine of a split launch: the fused FILTER slot may be the depth class, frame f's map */>
 __device__ void pose_refine(const float* pts, int* list, const int k, float* R, float* t, const int flags /* 1 near miss, 2 tight fit */,
                             const DevCam* cams, const mh_pose_params& prm, const float alpha, const int lane, const int slot,
                             float* __restrict__ obj_pose, int32_t* __restrict__ obj_ninl, float* __restrict__ obj_err,
-                            int32_t* obj_valid, const FilterFuseArgs* __restrict__ fuse, const unsigned long long fa PR_PROF_PARAMS) {
+                            int32_t* obj_valid, const FilterFuseArgs* __restrict__ fuse, const unsigned long long fa, const int f PR_PROF_PARAMS) {
   constexpr int PS = PointStride<KIND>::value;
   // The inliers of a pose, in point order, into list; `same` = the list already held exactly these points.
   auto collect = [&](bool& same, const float scale = 1.f) {
@@ -1120,7 +1133,10 @@ __device__ void pose_refine(const float* pts, int* list, const int k, float* R, 
     fb.obj_score = frame_ptr(fb.obj_score, fa);
     fb.best = frame_ptr(fb.best, fa);
     const int model = frame_ptr(fb.obj_model, fa)[slot];
-    filter_score_wave(fb, cams[0], fuse->feature_distance, slot, model, q, t, lane);
+    if (DEPTH && fuse->depth.on)   // (uniform; KIND 3 -- several cameras -- never comes with it)
+      fused_depth_f1(fuse, fb, cams[0], f, slot, model, q, t, lane);
+    else
+      filter_score_wave(fb, cams[0], fuse->feature_distance, slot, model, q, t, lane);
   }
 }
 #ifdef POSE_PROF   // (back to the task-level form for pose_task below)
@@ -1517,7 +1533,7 @@ __device__ void pose_task(
   for (int i = 0; i < 3; ++i) t[i] = L.best_pose[9 + i];
 #ifdef POSE_PROF
   pose_refine<KIND>(L.pts, L.list, k, R, t, (near_miss ? 1 : 0) | ((replica & 1) << 1), cams, prm, alpha, lane, slot, obj_pose, obj_ninl, obj_err, obj_valid,
-                    fuse, fa, pp_loc, &t_prof);
+                    fuse, fa, 0, pp_loc, &t_prof);
   if (threadIdx.x == 0 && obj_valid[slot]) {
     for (int i = 0; i < 6; ++i) atomicAdd(&g_pose_prof[i], pp_loc[i]);
     atomicAdd(&g_pose_prof[7], 1ull);
@@ -1525,7 +1541,7 @@ __device__ void pose_task(
   }
 #else
   pose_refine<KIND>(L.pts, L.list, k, R, t, (near_miss ? 1 : 0) | ((replica & 1) << 1), cams, prm, alpha, lane, slot, obj_pose, obj_ninl, obj_err, obj_valid,
-                    fuse, fa);
+                    fuse, fa, 0);
 #endif
 }
 
@@ -1561,8 +1577,9 @@ __device__ __forceinline__ FilterBuffers fused_filter_buffers(const FilterFuseAr
 // launch's workgroups at their START, four slots per workgroup (one wavefront each): slot o belongs to workgroup
 // (o / 4) mod G.  Returns how many slots this workgroup took.  (Round 5, first form: the closing workgroup did them all
 // at the end -- ten kept objects were three rounds of ~10 us behind everything else, 0.74 -> 0.77 ms for a frame alone.)
-__device__ __forceinline__ int pose_kept_f1(const FilterFuseArgs* __restrict__ fuse_args, const unsigned long long a, const int obj_base,
-                                            const int max_objects, const DevCam& cam) {
+template <bool DEPTH>
+__device__ __forceinline__ int pose_kept_f1(const FilterFuseArgs* __restrict__ fuse_args, const int f, const unsigned long long a,
+                                            const int obj_base, const int max_objects, const DevCam& cam) {
   const int n_old = obj_base < max_objects ? obj_base : max_objects;
   const int G = (int)gridDim.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   constexpr int NW = POSE_THREADS / 64;
@@ -1576,7 +1593,11 @@ __device__ __forceinline__ int pose_kept_f1(const FilterFuseArgs* __restrict__ f
     }
     mine += min(NW, n_old - o0);
     const int o = o0 + wave;
-    if (o < n_old && ffb.obj_valid[o])   // (wave-uniform)
+    if (!(o < n_old && ffb.obj_valid[o])) continue;   // (wave-uniform)
+    if (DEPTH && fuse_args->depth.on)   // the depth class scores them with frame f's map
+      fused_depth_f1(fuse_args, ffb, cam, f, o, ffb.obj_model[o], ffb.obj_pose + 7 * (size_t)o,
+                     ffb.obj_pose + 7 * (size_t)o + 4, lane);
+    else
       filter_score_wave(ffb, cam, fuse_args->feature_distance, o, ffb.obj_model[o], ffb.obj_pose + 7 * (size_t)o,
                         ffb.obj_pose + 7 * (size_t)o + 4, lane);
   }
@@ -1626,7 +1647,9 @@ __device__ void pose_close_frame(const int f, const unsigned long long a, const 
   }
 }
 
-template <int KIND, bool SPLIT>
+// DEPTH (a split launch only): an instantiation of its own for launches whose fused FILTER slot is the depth class -- the
+// kernels every other frame runs stay the code they were
+template <int KIND, bool SPLIT, bool DEPTH = false>
 __global__ __launch_bounds__(POSE_THREADS, SPLIT ? MH_POSE_SPLIT_WAVES : MH_POSE_MIN_WAVES) void pose_kernel(
     const mh_corr* __restrict__ corr0, const float4* __restrict__ depth0, float alpha,
     const int32_t* __restrict__ members0,
@@ -1670,7 +1693,7 @@ __global__ __launch_bounds__(POSE_THREADS, SPLIT ? MH_POSE_SPLIT_WAVES : MH_POSE
     // frames after this kernel has ended; one launch: they count in the frame's ticket like tasks)
     const int n_kept = (fuse_args && n_tasks > 0) ? (obj_base < max_objects ? obj_base : max_objects) : 0;
     if (n_kept > 0) {
-      const int took = pose_kept_f1(fuse_args, a, obj_base, max_objects, cam);
+      const int took = pose_kept_f1<DEPTH>(fuse_args, f, a, obj_base, max_objects, cam);
       if (ticket && took > 0 && frame_work_done(ticket, (unsigned)took, (unsigned)(n_tasks + n_kept))) last = true;
     }
     int first = ((int)blockIdx.x - rank_base) % G;
@@ -1711,7 +1734,7 @@ struct RefineLds {
 #ifndef MH_REFINE_MIN_WAVES
 #define MH_REFINE_MIN_WAVES 3
 #endif
-template <int KIND>
+template <int KIND, bool DEPTH = false /* as pose_kernel's */>
 __global__ __launch_bounds__(POSE_THREADS, MH_REFINE_MIN_WAVES) void pose_refine_kernel(
     const mh_corr* __restrict__ corr0, const float4* __restrict__ depth0, float alpha,
     const int32_t* __restrict__ members0, const int32_t* __restrict__ cl_begin0, const int32_t* __restrict__ cl_count0,
@@ -1810,11 +1833,11 @@ __global__ __launch_bounds__(POSE_THREADS, MH_REFINE_MIN_WAVES) void pose_refine
         for (int i = 0; i < 9; ++i) R[i] = hyp[slot].pose[i];
         for (int i = 0; i < 3; ++i) t[i] = hyp[slot].pose[9 + i];
 #ifdef POSE_PROF
-        pose_refine<KIND>(pts, list, k, R, t, hyp[slot].flags & 3, cams, prm, alpha, lane, slot, frame_ptr(obj_pose0, fa),
-                          frame_ptr(obj_ninl0, fa), frame_ptr(obj_err0, fa), frame_ptr(obj_valid0, fa), fuse_args, fa, nullptr, nullptr);
+        pose_refine<KIND, DEPTH>(pts, list, k, R, t, hyp[slot].flags & 3, cams, prm, alpha, lane, slot, frame_ptr(obj_pose0, fa),
+                          frame_ptr(obj_ninl0, fa), frame_ptr(obj_err0, fa), frame_ptr(obj_valid0, fa), fuse_args, fa, f, nullptr, nullptr);
 #else
-        pose_refine<KIND>(pts, list, k, R, t, hyp[slot].flags & 3, cams, prm, alpha, lane, slot, frame_ptr(obj_pose0, fa),
-                          frame_ptr(obj_ninl0, fa), frame_ptr(obj_err0, fa), frame_ptr(obj_valid0, fa), fuse_args, fa);
+        pose_refine<KIND, DEPTH>(pts, list, k, R, t, hyp[slot].flags & 3, cams, prm, alpha, lane, slot, frame_ptr(obj_pose0, fa),
+                          frame_ptr(obj_ninl0, fa), frame_ptr(obj_err0, fa), frame_ptr(obj_valid0, fa), fuse_args, fa, f);
 #endif
       }
     }
@@ -1913,6 +1936,7 @@ static void launch_pose_kind(const mh_corr* corr, const float4* depth, float alp
     now.min_score = fuse->min_score;
     now.min_points = fuse->min_points;
     now.n_clusters_dev = fuse->n_clusters_dev;
+    if (fuse->depth) now.depth = *fuse->depth;   // (else all zero, as the memset left it: the plain class)
     if (!*fuse->shadow_valid || std::memcmp(&now, fuse->shadow, sizeof now) != 0) {
       hipLaunchKernelGGL(store_fuse_args_kernel, dim3(1), dim3(64), 0, s, fuse->dev, now);
       std::memcpy(fuse->shadow, &now, sizeof now);
@@ -1930,16 +1954,27 @@ static void launch_pose_kind(const mh_corr* corr, const float4* depth, float alp
   static const bool split_on = exp_int("MH_POSE_SPLIT", 1) != 0;
   // (one frame alone with a handful of tasks: the launch the split adds costs more than the compute units it frees --
   //  0.688 against 0.675 ms per isolated frame; the objects are the same bits either way)
+  // (a fused slot of the depth class: always two -- only the split launch's kernels carry the depth F1; frame_rest fuses
+  //  such a frame only where pose_launch_splits says the two launches are to be had)
+  const bool depth_slot = fuse_dev && fuse->depth;
   const bool two = split_on && split && split->hyp && tail.ticket && p.max_objects_per_cluster <= 4 &&
-                   (n_frames > 1 || (tail.grid > 0 ? tail.grid : 96) > 48);
-#define MH_POSE_LAUNCH(SPLIT_)                                                                                             \
-  hipLaunchKernelGGL((pose_kernel<KIND, SPLIT_>), dim3((unsigned)std::max(1L, std::min((long)grid_cap, all_slots))),       \
+                   (n_frames > 1 || (tail.grid > 0 ? tail.grid : 96) > 48 || depth_slot);
+#define MH_POSE_LAUNCH(SPLIT_, DEPTH_)                                                                                            \
+  hipLaunchKernelGGL((pose_kernel<KIND, SPLIT_, DEPTH_>), dim3((unsigned)std::max(1L, std::min((long)grid_cap, all_slots))),       \
                      dim3(POSE_THREADS), sizeof(PoseLds<KIND>), s, corr, depth, alpha, members, cl_model, cl_begin,        \
                      cl_count, n_clusters_dev, cam, cam_table, img_of, n_images, p, seed, obj_base_dev, max_objects,      \
                      obj_model, obj_pose, obj_ninl, obj_err, obj_cluster, obj_valid, counts, tail, fuse_dev,              \
                      batch ? *batch : FrameBatch(), two ? split->hyp : (PoseHyp*)nullptr)
-  if (two) MH_POSE_LAUNCH(true);
-  else MH_POSE_LAUNCH(false);
+  bool depth_kernels = false;   // the instantiations that carry the depth class's F1 (one camera: never KIND 3)
+  if constexpr (KIND != 3) depth_kernels = two && depth_slot;
+  if (depth_kernels) {
+    if constexpr (KIND != 3) {
+      static DynLds attr_d;
+      attr_d.ensure(pose_kernel<KIND, true, true>, sizeof(PoseLds<KIND>));
+      MH_POSE_LAUNCH(true, true);
+    }
+  } else if (two) MH_POSE_LAUNCH(true, false);
+  else MH_POSE_LAUNCH(false, false);
 #undef MH_POSE_LAUNCH
   if (two) {
     static DynLds attr_r;
@@ -1949,11 +1984,26 @@ static void launch_pose_kind(const mh_corr* corr, const float4* depth, float alp
     static const long g2_cap = std::max(1, exp_int("MH_POSE_RGRID", 256));
     static const int g2_div = std::max(1, exp_int("MH_POSE_RDIV", 4));   // tasks per workgroup the grid is sized for
     const unsigned g2 = (unsigned)std::max(1L, std::min(std::min(g2_cap, (guess + g2_div - 1) / g2_div), (all_slots + 3) / 4));
-    hipLaunchKernelGGL(pose_refine_kernel<KIND>, dim3(g2), dim3(POSE_THREADS), sizeof(RefineLds<KIND>), s, corr, depth, alpha,
-                       members, cl_begin, cl_count, n_clusters_dev, cam, cam_table, img_of, n_images, p, obj_base_dev,
-                       max_objects, obj_pose, obj_ninl, obj_err, obj_valid, counts, tail, fuse_dev,
-                       batch ? *batch : FrameBatch(), *split);
+#define MH_REFINE_LAUNCH(DEPTH_)                                                                                          \
+  hipLaunchKernelGGL((pose_refine_kernel<KIND, DEPTH_>), dim3(g2), dim3(POSE_THREADS), sizeof(RefineLds<KIND>), s, corr, depth, \
+                     alpha, members, cl_begin, cl_count, n_clusters_dev, cam, cam_table, img_of, n_images, p, obj_base_dev,  \
+                     max_objects, obj_pose, obj_ninl, obj_err, obj_valid, counts, tail, fuse_dev,                            \
+                     batch ? *batch : FrameBatch(), *split)
+    if (depth_kernels) {
+      if constexpr (KIND != 3) {
+        static DynLds attr_rd;
+        attr_rd.ensure(pose_refine_kernel<KIND, true>, sizeof(RefineLds<KIND>));
+        MH_REFINE_LAUNCH(true);
+      }
+    } else
+      MH_REFINE_LAUNCH(false);
+#undef MH_REFINE_LAUNCH
   }
+}
+
+bool pose_launch_splits(const mh_pose_params& prm) {
+  static const bool split_on = exp_int("MH_POSE_SPLIT", 1) != 0;
+  return split_on && prm.max_objects_per_cluster <= 4;
 }
 
 void launch_pose(const mh_corr* corr, const float* depth4, int depth_kind, float alpha,

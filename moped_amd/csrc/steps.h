@@ -224,6 +224,7 @@ struct FilterFuse {
   float feature_distance = 0.f, min_score = 0.f;
   int min_points = 0;
   int32_t* n_clusters_dev = nullptr;
+  const struct FilterFuseDepth* depth = nullptr;   // this slot is the depth class (nullptr: the plain one)
   // where the step's arguments wait on the device (FilterFuseArgs, below) and the host's copy of what is there:
   // launch_pose stores them (a one-thread launch) only when they have changed -- for a context's frames, never again
   struct FilterFuseArgs* dev = nullptr;
@@ -245,6 +246,9 @@ void launch_pose(const mh_corr* corr, const float* depth4, int depth_kind, float
                  const FilterFuse* fuse = nullptr, const FrameBatch* batch = nullptr, const PoseSplit* split = nullptr);
 // pose_kernel<kind>'s registers / LDS / threads / resident workgroups per compute unit / spill bytes (mh_pose_kernel_info)
 int pose_kernel_info(int kind, int32_t out[8]);
+// launch_pose with a PoseSplit would take the two launches for these parameters whatever the task count (only their
+// kernels carry the depth class's fused F1: frame_rest fuses a depth FILTER slot only where this holds)
+bool pose_launch_splits(const mh_pose_params& prm);
 void launch_project_test(const float* pose7, const mh_corr* corr, int n, const DevCam& cam,
                          float thr, uint8_t* inlier, float* err2, int32_t* n_inliers,
                          hipStream_t s);
@@ -300,17 +304,6 @@ struct FrameHostBlock {
   // whose launches failed, or were replayed without frame_rest -- and mh_frame_fetch falls back to the copies.
   volatile uint32_t seq;
 };
-// The fused FILTER step's arguments as the POSE kernel reads them: from device memory, at the one place that needs them
-// (the closing workgroup of a frame), instead of ~70 scalar registers' worth of kernel arguments held -- and spilled --
-// through the RANSAC code.
-struct FilterFuseArgs {
-  FilterBuffers fb;
-  FilterTail tail;
-  float feature_distance, min_score;
-  int min_points;
-  int32_t* n_clusters_dev;
-};
-
 // n_slots_dev: number of object slots in use; after the call the kept objects are
 // compacted to slots [0, kept) in list order, *n_slots_dev = kept, and the cluster
 // table holds their rewritten clusters.  fb.best[0, n_matches) must be zero on entry and
@@ -331,14 +324,41 @@ struct FilterDepthArgs {
   int w = 0, h = 0;
   DevCam dcam;                        // the depth map's K and pose
   float plausible_sq_distance = 0.f, depth_fraction = 0.f, min_keypoint_fraction = 0.f;
+  int pad_ = 0;                       // (no padding bytes: FilterFuseArgs is compared bytewise)
   // optional, per object slot as it was BEFORE the erase: the IS that was subtracted, usedKeypointCount, clusterSize
   float* out_is = nullptr;
   int32_t* out_used = nullptr;
   int32_t* out_plausible = nullptr;
 };
+// What the depth class adds to a fused FILTER step, per slot -- FILTER and FILTER2 each carry their own flag and
+// parameters: FilterDepthArgs without a map (img / fill / out_* stay null) and the maps, entry f for frame f of a merged
+// batch (mh_frame_set_depth_image_batch), entry 0 for a frame alone.  The maps change from batch to batch where the
+// caller hands in other buffers; they are part of the compared block, so a change is one more store_fuse_args_kernel
+// launch on the context's stream, behind every launch that still reads the old ones.
+struct FilterFuseDepth {
+  int on = 0, pad_ = 0;
+  FilterDepthArgs args;
+  DepthMaps maps;
+};
+// The fused FILTER step's arguments as the POSE kernels read them: from device memory, at the places that need them --
+// the closing workgroup of a frame (all but `depth`), and the wavefronts that score an object, behind the refine and in
+// pose_kept_f1 (fb, feature_distance, depth) -- instead of ~70 scalar registers' worth of kernel arguments held -- and
+// spilled -- through the RANSAC code.
+struct FilterFuseArgs {
+  FilterBuffers fb;
+  FilterTail tail;
+  float feature_distance, min_score;
+  int min_points;
+  int32_t* n_clusters_dev;
+  FilterFuseDepth depth;   // all zero: this slot is the plain class
+};
 // launch_filter with the depth term; one image (fb.m_img must be nullptr)
 void launch_filter_depth(const FilterBuffers& fb, const DevCam& cam, int min_points, float feature_distance,
                          float min_score, const FilterDepthArgs& da, int32_t* n_slots_dev, int32_t* n_clusters_dev,
                          FrameCounts* counts, const FilterTail& tail, hipStream_t s);
+// ... scored by filter_depth_score_wave, one wavefront per object slot (mh_filter_depth_debug_form 1): the same results
+void launch_filter_depth_wave(const FilterBuffers& fb, const DevCam& cam, int min_points, float feature_distance,
+                              float min_score, const FilterDepthArgs& da, int32_t* n_slots_dev, int32_t* n_clusters_dev,
+                              FrameCounts* counts, const FilterTail& tail, hipStream_t s);
 
 }  // namespace mh

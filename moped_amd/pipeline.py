@@ -314,6 +314,9 @@ class FramePipeline:
         enqueues deliver depth-verified objects.  points_xyz [total, 3], points_off [n_models + 1]: the models' test
         points (the caller's sample); f1, f2: (PlausibleSqDistance, DepthFraction, MinKeypointFraction) or None = that slot
         stays the plain class, both None = off; depth_cam: (K, pose) of the depth map, default the pipeline's camera.
+        Such frames run like plain ones: the FILTER steps in the tails of the POSE launches, the frames of
+        enqueue_kinect_batch in one launch per stage with every object scored against its own frame's map
+        (Context.frame_route() says which way the last frame or batch went); the objects are those of the frames alone.
         Every slot's context is set.  After add_model / replace_model / remove_model the points are stale: call again."""
         if self.exchange:
             raise ValueError("the depth FILTER needs one GPU's whole database: the test points are per global model")

@@ -14,8 +14,9 @@
 
 (c) --filter-depth (instead of (a) and (b)): batches of 16 with moped3d's depth-verified FILTER in both slots
     (FramePipeline.set_filter_depth, 300 test points per model) against the same batches with it off, alternating rounds,
-    on maps that arrive filled; then the FILTER and FILTER2 stage times of one frame alone with stage timing on (device
-    events around filter_depth_kernel against filter_kernel).  > profiles/filter_depth.txt
+    on maps that arrive filled, with the route the last batch took (mh_frame_route); then the FILTER and FILTER2 stage
+    times of one frame alone with stage timing on (device events around filter_depth_kernel against filter_kernel).
+    MH_LIB_PATH names another build of the library for an A/B run.  > profiles/filter_depth.txt
 
 usage: python scripts/kinect_image_bench.py [--models 5] [--rounds 5] [--seconds 1.2] > profiles/kinect_image_batch.txt
 One process on an otherwise idle device; every shape is warmed before it is timed."""
@@ -163,6 +164,10 @@ def main():
             win[on] = max(SLOTS, int(np.ceil(args.seconds / dt * 2)) * SLOTS)
             hits = sum(found(pipe.ctxs[SLOTS - 1].frame_fetch_slot(j)) for j in range(B))
             print(f"# depth FILTER {'on ' if on else 'off'}: warm; {win[on] * B} frames per window; planted model best in {hits} of {B}")
+            if hasattr(capi.load(), "mh_frame_route"):        # (an older library named by MH_LIB_PATH has no such call)
+                r_ = pipe.ctxs[SLOTS - 1].frame_route().tolist()
+                print(f"# depth FILTER {'on ' if on else 'off'}: last batch: {r_[0]} frames, {'one launch per stage' if r_[1] else 'frame after frame'}, "
+                      f"FILTER {'in the POSE tails' if r_[2] else 'as launches of its own'}, depth class bits {r_[3]}")
         rates = {False: [], True: []}
         for r in range(args.rounds):
             for on in (False, True):
