@@ -649,7 +649,7 @@ int mh_frame_set_depth_rules(mh_ctx* ctx, const mh_depth_rules* rules, const flo
  * distances with sigma = average nearest-neighbour distance, depth-discontinuity kernel along the
  * image line between two matches, model/world distance-consistency kernel, fill-distance weighted
  * sum) and average-linkage agglomeration down to `cutoff`.  Needs the depth map
- * (mh_frame_set_depth_image); at most 1024 matches per model.  LinkageType 1 (average) only. */
+ * (mh_frame_set_depth_image); at most 1024 matches per model.  LinkageType 0, 1 (average, as shipped) or 2. */
 typedef struct mh_linkage_params {
   float cutoff;         /* 0.1 */
   int32_t min_pts;      /* 7: clusters need MORE than this many members (:535) */
@@ -943,6 +943,60 @@ int mh_frame_enqueue_image_batch(mh_ctx* ctx, const uint8_t* const* gray_dev, in
                                  const uint64_t* seeds);
 int mh_frame_features_dev(mh_ctx* ctx, float** desc_dev, float** uv_dev, int32_t** n_dev);
 int mh_frame_keypoints(mh_ctx* ctx, int32_t* n_keypoints);
+
+/* ---- moped3d's depth steps on a step's own lists (the STEP plugins DEPTHFILTER_HIP / DEPTHMAP_PROP_HIP) -----------
+ *
+ * Inside the resident frame these rules run in group_kernel / feature_density_kernel (mh_frame_set_depth_rules); a
+ * libmoped tree that keeps moped3d's DEPTHFILTER, DEPTHFILTER2 and DEPTHPROP slots (moped3d/libmoped/src/config.hpp:41,
+ * 43,44) as steps of their own hands every step its own lists.  Both calls are synchronous host round trips like
+ * mh_meanshift and mh_filter.  depth_xyzn_host [height][width][4] (x, y, z, norm; negative norm = invalid) is copied
+ * into the context-owned buffers mh_frame_set_depth_image_host fills; NULL = the map the context holds already
+ * (mh_frame_set_depth_image[_host], its width and height), so that a frame's map crosses PCIe once for all its steps.
+ * A host map handed in here serves this call alone; a frame map that lived in those buffers
+ * (mh_frame_set_depth_image_host, mh_frame_run_kinect_host) is overwritten by it and therefore switched off: set it again.
+ *
+ * mh_depth_filter: DEPTHFILTER_CPU::process (moped3d/libmoped/src/depthfilter/DEPTHFILTER_CPU.hpp:117-254) on n =
+ * group_off_host[n_groups] points uv_host [n][2]: group g = points [group_off_host[g], group_off_host[g + 1]) is counted
+ * by itself -- n_groups = 1 is ToFilter = 1 (:180-214, the detected features), n_groups = the models is ToFilter = 2
+ * (:215-251, matches[model] one after the other).  keep_host[i] = 1 where the density of point i's group per square
+ * metre of scene surface over patch_size x patch_size pixel patches, dilated 3x3 (:76-113), exceeds density * 100 * 100
+ * (:130).  K = the depth map's intrinsicLinearCalibration.  The reference's arithmetic as written: `y1 = min(..,
+ * width)` (:171), a NaN depth never wins the minimum (:162), coordinates outside the map are clamped to it (the
+ * reference indexes out of bounds).  Bit for bit the verdicts of the frame path (mh_depth_rules_debug_fetch which 1;
+ * the lists mh_frame_fetch_matches gives).  More than 4096 patches -> MH_ERR_CAPACITY. */
+int mh_depth_filter(mh_ctx* ctx, const float* depth_xyzn_host, int width, int height, const float K[4], int patch_size,
+                    float density, const float* uv_host, const int32_t* group_off_host, int n_groups, uint8_t* keep_host);
+/* Match::depthInformation (moped3d/libmoped/src/util.hpp:73-84) */
+typedef struct {
+  int32_t depth_valid;   /* depthValid: the pixel's norm >= 0 */
+  float coord3d[3];      /* coord3D: the pixel's x, y, z */
+  float depth;           /* depth: its z */
+  float fill_distance;   /* fillDistance: the ".distance" map's value, -1 without such a map */
+} mh_depth_info;
+/* mh_depth_prop: DEPTHMAP_PROP_CPU::process (moped3d/libmoped/src/depthprop/DEPTHMAP_PROP_CPU.hpp:52-134) for n points
+ * uv_host [n][2]: out_host[i] = the record of pixel ((int) u, (int) v) -- truncated, no interpolation (:103,119-132),
+ * clamped to the map.  With depth_xyzn_host, fill_distance_host [height][width] is that map's ".distance" map or NULL =
+ * none (fillDistance -1, :107-111); with depth_xyzn_host NULL the context's distance map, if it holds one. */
+int mh_depth_prop(mh_ctx* ctx, const float* depth_xyzn_host, const float* fill_distance_host, int width, int height,
+                  const float* uv_host, int n, mh_depth_info* out_host);
+
+/* ONE Kinect frame of moped3d's pipeline (moped3d/libmoped/src/config.hpp:38-49) in one synchronous call, host memory
+ * in, objects out -- what FRAME_RESIDENT_HIP's mh_frame_run_host is to moped2 (the STEP plugin FRAME_RESIDENT_3D_HIP):
+ * gray_host [height][width] and depth_xyzn_host [height][width][4] are copied into context-owned buffers; fill_scale > 0
+ * (or -1: the reference's automatic factor): mh_depth_fill(fill_scale, bilinear, K = cam->K) fills the map on the
+ * device, and the filled map and its distance map are copied back into depth_xyzn_host / fill_distance_host (both
+ * required: DEPTH_FILL_EXACT_CPU::process leaves them in the frame's images); fill_scale = 0: the maps arrive filled,
+ * fill_distance_host is read, or NULL = no distance map.  Then mh_frame_set_depth_image(kind, alpha, cauchy_scale),
+ * mh_frame_enqueue_image(double_size, max_keypoints, cam, prm, seed) and mh_frame_fetch -- the calls a host composes
+ * itself from device buffers, launch for launch (this call has no kernel of its own), so the objects are bit for bit
+ * theirs.  The depth rules and the clusterer are what mh_frame_set_depth_rules / mh_frame_set_cluster_linkage left.
+ * The frame's lists afterwards: mh_frame_fetch_matches / mh_frame_fetch_match_points; the context keeps the map
+ * (mh_depth_filter / mh_depth_prop with NULL read it). */
+int mh_frame_run_kinect_host(mh_ctx* ctx, const uint8_t* gray_host, float* depth_xyzn_host, float* fill_distance_host,
+                             int width, int height, int double_size, int max_keypoints, const mh_cam* cam,
+                             const mh_frame_params* prm, int fill_scale, int bilinear, int kind, float alpha,
+                             float cauchy_scale, uint64_t seed, mh_object* objects_host, int max_objects,
+                             int32_t* n_objects, int32_t* counts);
 
 /* ONE frame seen by n_images cameras, images resident on the device: FEAT of every image
  * (FEAT_SIFT_CPU.hpp:80-107: image 0's keypoints in libsiftfast's list order, then image 1's, ...,

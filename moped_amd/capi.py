@@ -64,6 +64,8 @@ OBJECT_DTYPE = np.dtype([("model", "<i4"), ("pose", "<f4", (7,)), ("score", "<f4
 STEP_OBJECT_DTYPE = np.dtype([("model", "<i4"), ("pose", "<f4", (7,))])   # mh_step_object
 DEPTH_DTYPE = np.dtype([("wx", "<f4"), ("wy", "<f4"), ("wz", "<f4"), ("w", "<f4")])
 DEPTH_BACKPROJECTION, DEPTH_REPROJECTION = 1, 2
+DEPTH_INFO_DTYPE = np.dtype([("depth_valid", "<i4"), ("coord3d", "<f4", (3,)), ("depth", "<f4"),
+                             ("fill_distance", "<f4")])   # mh_depth_info
 POSE_OUT_DTYPE = np.dtype([("pose", "<f4", (7,)), ("cluster", "<i4"), ("n_inliers", "<i4"), ("err", "<f4")])
 SIFT_CANDIDATE_DTYPE = np.dtype([("octave", "<i4"), ("index", "<i4"), ("key", "<u4"), ("r", "<i4"), ("c", "<i4"),
                                  ("x0", "<f4"), ("x1", "<f4"), ("x2", "<f4")])                      # mh_sift_candidate
@@ -145,6 +147,7 @@ EXPORTS = [
     "mh_frame_features_image_dev",
     "mh_filter_depth_set_points", "mh_filter_depth", "mh_frame_set_filter_depth",
     "mh_frame_route", "mh_filter_depth_debug_form",
+    "mh_depth_filter", "mh_depth_prop", "mh_frame_run_kinect_host",
 ]
 COMM_ID_BYTES = 128      # MH_COMM_ID_BYTES
 EX2_OBJECTS = 62         # MH_EX2_OBJECTS
@@ -279,6 +282,10 @@ def load():
     L.mh_db_splice_models.argtypes = [vp, i32, i32, vp, i32]
     L.mh_db_debug_fetch.argtypes = [vp, i32, vp, C.c_size_t]
     L.mh_depth_rules_debug_fetch.argtypes = [vp, i32, i32, vp, C.c_size_t]
+    L.mh_depth_filter.argtypes = [vp, vp, i32, i32, vp, i32, f32, vp, vp, i32, vp]
+    L.mh_depth_prop.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp]
+    L.mh_frame_run_kinect_host.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(mh_cam), C.POINTER(mh_frame_params),
+                                           i32, i32, i32, f32, f32, C.c_uint64, vp, i32, C.POINTER(C.c_int32), vp]
     L.mh_db_debug_screen.argtypes = [vp, vp]
     L.mh_db_debug_route.argtypes = [vp, i32]
     L.mh_db_edit_ms.argtypes = [vp, C.POINTER(f32)]
@@ -1181,6 +1188,62 @@ class Context:
         f = None if fill_img is None else np.ascontiguousarray(fill_img, np.float32).reshape(h, w)
         self._ck(self.L.mh_frame_set_depth_image_host(self.h, _ptr(d), _ptr(f), w, h, kind, alpha, cauchy_scale),
                  "mh_frame_set_depth_image_host")
+
+    def depth_filter(self, depth_img, K, patch_size, density, uv, group_off=None):
+        """moped3d's DEPTHFILTER on the caller's points uv [n, 2]: keep [n] bool.  group_off None: one group, ToFilter = 1
+        (the detected features); else [n_groups + 1], ToFilter = 2 (every model's matches counted by themselves).
+        depth_img [h, w, 4], or None = the map the context holds (frame_set_depth_image[_host])."""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        n = len(uv)
+        off = np.ascontiguousarray(group_off if group_off is not None else [0, n], np.int32)
+        if off[-1] != n:
+            raise ValueError("group_off must end at the number of points")
+        d, h, w = None, 0, 0
+        if depth_img is not None:
+            d = np.ascontiguousarray(depth_img, np.float32)
+            h, w = d.shape[:2]
+        k = np.ascontiguousarray(K, np.float32)
+        keep = np.zeros(max(n, 1), np.uint8)
+        self._ck(self.L.mh_depth_filter(self.h, _ptr(d), w, h, _ptr(k), int(patch_size), float(density), _ptr(uv), _ptr(off),
+                                        len(off) - 1, _ptr(keep)), "mh_depth_filter")
+        return keep[:n].astype(bool)
+
+    def depth_prop(self, depth_img, fill_img, uv) -> np.ndarray:
+        """moped3d's DEPTHMAP_PROP on the caller's points uv [n, 2]: DEPTH_INFO_DTYPE [n] (Match::depthInformation).
+        depth_img [h, w, 4] + fill_img [h, w] or None (fillDistance -1); depth_img None = the context's maps."""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        n = len(uv)
+        d, f, h, w = None, None, 0, 0
+        if depth_img is not None:
+            d = np.ascontiguousarray(depth_img, np.float32)
+            h, w = d.shape[:2]
+            f = None if fill_img is None else np.ascontiguousarray(fill_img, np.float32).reshape(h, w)
+        out = np.zeros(max(n, 1), DEPTH_INFO_DTYPE)
+        self._ck(self.L.mh_depth_prop(self.h, _ptr(d), _ptr(f), w, h, _ptr(uv), n, _ptr(out)), "mh_depth_prop")
+        return out[:n]
+
+    def frame_run_kinect_host(self, gray, depth_img, fill_img, K, cam, params: mh_frame_params, seed, fill_scale=8,
+                              bilinear=False, double_size=True, max_keypoints=2048, kind=DEPTH_BACKPROJECTION, alpha=0.5,
+                              cauchy_scale=0.1, max_objects=4096):
+        """One Kinect frame from host arrays in one call: gray [h, w] uint8, depth_img [h, w, 4]; fill_scale 0: the maps
+        arrive filled (fill_img [h, w] or None), else DEPTHFILL on the device first.
+        -> (objects, counts, the depth map and the distance map as the frame used them)."""
+        g = np.ascontiguousarray(gray, np.uint8)
+        h, w = g.shape
+        d = np.ascontiguousarray(depth_img, np.float32).reshape(h, w, 4).copy()
+        if fill_scale:
+            f = np.zeros((h, w), np.float32)
+        else:
+            f = None if fill_img is None else np.ascontiguousarray(fill_img, np.float32).reshape(h, w).copy()
+        c = make_cam(K, cam)
+        objs = np.zeros(max_objects, OBJECT_DTYPE)
+        n = C.c_int32(0)
+        counts = np.zeros(4, np.int32)
+        self._ck(self.L.mh_frame_run_kinect_host(self.h, _ptr(g), _ptr(d), _ptr(f), w, h, 1 if double_size else 0,
+                                                 int(max_keypoints), C.byref(c), C.byref(params), int(fill_scale),
+                                                 1 if bilinear else 0, kind, alpha, cauchy_scale, seed, _ptr(objs),
+                                                 max_objects, C.byref(n), _ptr(counts)), "mh_frame_run_kinect_host")
+        return objs[:min(n.value, max_objects)].copy(), counts, d, f
 
     def frame_set_filter_depth(self, f1=None, f2=None, depth_K=None, depth_cam=None):
         """FILTER (f1) / FILTER2 (f2) of the frames enqueued from now on as the depth class; None: that slot stays plain,

@@ -90,8 +90,161 @@ struct PinCursor {
   }
 };
 
+// The depth map a stand-alone depth step reads: the caller's host map through the context's own buffers, or (NULL) the
+// map the context holds.  The own buffers may be the frame's map (mh_frame_set_depth_image_host): overwritten, it is off.
+int step_depth_map(mh_ctx* ctx, const char* who, const float* depth_host, const float* fill_host, int width, int height,
+                   DepthImage* out) {
+  if (!depth_host) {
+    if (!ctx->depth_img.img) {
+      ctx->err = std::string(who) + ": no depth map (hand one in, or mh_frame_set_depth_image[_host] first)";
+      return MH_ERR_ARG;
+    }
+    *out = ctx->depth_img;
+    return MH_OK;
+  }
+  if (width <= 0 || height <= 0) {
+    ctx->err = std::string(who) + ": bad argument";
+    return MH_ERR_ARG;
+  }
+  if (ctx->depth_img.img && ctx->own_depth && reinterpret_cast<const float*>(ctx->depth_img.img) == ctx->own_depth.p)
+    mh_frame_set_depth_image(ctx, nullptr, nullptr, 0, 0, 0, ctx->depth_alpha, 0.f);
+  const size_t px = (size_t)width * height;
+  if (int rc = ensure_own_depth(ctx, px)) return rc;
+  MH_HIP(ctx, hipMemcpyAsync(ctx->own_depth, depth_host, px * 4 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  if (fill_host)
+    MH_HIP(ctx, hipMemcpyAsync(ctx->own_fill, fill_host, px * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  *out = DepthImage{};
+  out->img = reinterpret_cast<const float4*>(ctx->own_depth.p);
+  out->fill = fill_host ? ctx->own_fill.p : nullptr;
+  out->w = width;
+  out->h = height;
+  return MH_OK;
+}
+
 }  // namespace
 extern "C" {
+
+// ---- moped3d's DEPTHFILTER / DEPTHFILTER2 / DEPTHPROP slots as steps of their own (kernels: depth.hip) ------------------
+int mh_depth_filter(mh_ctx* ctx, const float* depth_xyzn_host, int width, int height, const float K[4], int patch_size,
+                    float density, const float* uv_host, const int32_t* group_off_host, int n_groups, uint8_t* keep_host) {
+  if (!ctx) return MH_ERR_ARG;
+  if (!K || patch_size <= 0 || n_groups < 0 || (n_groups > 0 && !group_off_host)) {
+    ctx->err = "mh_depth_filter: bad argument";
+    return MH_ERR_ARG;
+  }
+  if (n_groups == 0) return MH_OK;
+  for (int g = 0; g < n_groups; ++g)
+    if (group_off_host[0] != 0 || group_off_host[g + 1] < group_off_host[g]) {
+      ctx->err = "mh_depth_filter: offsets must start at 0 and not decrease";
+      return MH_ERR_ARG;
+    }
+  const int n = group_off_host[n_groups];
+  if (n == 0) return MH_OK;
+  if (!uv_host || !keep_host) {
+    ctx->err = "mh_depth_filter: bad argument";
+    return MH_ERR_ARG;
+  }
+  if (int rc_enter = mh::enter(ctx)) return rc_enter;
+  DepthImage dimg;
+  if (int rc = step_depth_map(ctx, "mh_depth_filter", depth_xyzn_host, nullptr, width, height, &dimg)) return rc;
+  const int pw = (dimg.w + patch_size - 1) / patch_size, ph = (dimg.h + patch_size - 1) / patch_size;
+  const size_t P = (size_t)pw * ph;
+  if (P > (size_t)depth_filter_max_patches()) {
+    ctx->err = "mh_depth_filter: more than 4096 patches (raise PatchSize)";
+    return MH_ERR_CAPACITY;
+  }
+  // device layout: inv_size (double) | uv | group_off | keep
+  const size_t b_inv = P * sizeof(double), b_uv = (size_t)n * 2 * sizeof(float);
+  const size_t b_off = (((size_t)n_groups + 1) * sizeof(int32_t) + 15) & ~(size_t)15;
+  if (int rc = ensure_scratch(ctx, b_inv + b_uv + b_off + (size_t)n + 64)) return rc;
+  if (int rc = ensure_pinned(ctx, (size_t)n)) return rc;
+  unsigned char* base = ctx->scratch;
+  double* d_inv = reinterpret_cast<double*>(base);
+  float* d_uv = reinterpret_cast<float*>(base + b_inv);
+  int32_t* d_off = reinterpret_cast<int32_t*>(base + b_inv + b_uv);
+  uint8_t* d_keep = base + b_inv + b_uv + b_off;
+  hipStream_t s = ctx->stream;
+  MH_HIP(ctx, hipMemcpyAsync(d_uv, uv_host, b_uv, hipMemcpyHostToDevice, s));
+  MH_HIP(ctx, hipMemcpyAsync(d_off, group_off_host, ((size_t)n_groups + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  launch_depth_patches(dimg, K, patch_size, d_inv, s);
+  // `Float filter = Density*100*100` (DEPTHFILTER_CPU.hpp:130)
+  launch_group_density(d_uv, d_off, n_groups, patch_size, pw, ph, d_inv, density * 100 * 100, d_keep, s);
+  MH_HIP(ctx, hipGetLastError());
+  MH_HIP(ctx, hipMemcpyAsync(ctx->pinned.p, d_keep, (size_t)n, hipMemcpyDeviceToHost, s));
+  MH_HIP(ctx, hipStreamSynchronize(s));
+  std::memcpy(keep_host, ctx->pinned.p, (size_t)n);
+  return MH_OK;
+}
+
+int mh_depth_prop(mh_ctx* ctx, const float* depth_xyzn_host, const float* fill_distance_host, int width, int height,
+                  const float* uv_host, int n, mh_depth_info* out_host) {
+  if (!ctx) return MH_ERR_ARG;
+  if (n < 0 || (n > 0 && (!uv_host || !out_host))) {
+    ctx->err = "mh_depth_prop: bad argument";
+    return MH_ERR_ARG;
+  }
+  if (n == 0) return MH_OK;
+  if (int rc_enter = mh::enter(ctx)) return rc_enter;
+  DepthImage dimg;
+  if (int rc = step_depth_map(ctx, "mh_depth_prop", depth_xyzn_host, fill_distance_host, width, height, &dimg)) return rc;
+  const size_t b_uv = ((size_t)n * 2 * sizeof(float) + 15) & ~(size_t)15, b_out = (size_t)n * sizeof(mh_depth_info);
+  if (int rc = ensure_scratch(ctx, b_uv + b_out + 64)) return rc;
+  if (int rc = ensure_pinned(ctx, b_out)) return rc;
+  float* d_uv = reinterpret_cast<float*>(ctx->scratch.p);
+  mh_depth_info* d_out = reinterpret_cast<mh_depth_info*>(ctx->scratch.p + b_uv);
+  hipStream_t s = ctx->stream;
+  MH_HIP(ctx, hipMemcpyAsync(d_uv, uv_host, (size_t)n * 2 * sizeof(float), hipMemcpyHostToDevice, s));
+  launch_depth_prop(dimg, d_uv, n, d_out, s);
+  MH_HIP(ctx, hipGetLastError());
+  MH_HIP(ctx, hipMemcpyAsync(ctx->pinned.p, d_out, b_out, hipMemcpyDeviceToHost, s));
+  MH_HIP(ctx, hipStreamSynchronize(s));
+  std::memcpy(out_host, ctx->pinned.p, b_out);
+  return MH_OK;
+}
+
+// ---- moped3d's Kinect frame in one call: the composition of mh_depth_fill, mh_frame_set_depth_image, --------------------
+// mh_frame_enqueue_image and mh_frame_fetch over context-owned copies of the host's image and maps (no kernel of its own)
+int mh_frame_run_kinect_host(mh_ctx* ctx, const uint8_t* gray_host, float* depth_xyzn_host, float* fill_distance_host,
+                             int width, int height, int double_size, int max_keypoints, const mh_cam* cam,
+                             const mh_frame_params* prm, int fill_scale, int bilinear, int kind, float alpha,
+                             float cauchy_scale, uint64_t seed, mh_object* objects_host, int max_objects,
+                             int32_t* n_objects, int32_t* counts) {
+  if (!ctx) return MH_ERR_ARG;
+  const bool fill = fill_scale != 0;
+  if (!gray_host || !depth_xyzn_host || (fill && !fill_distance_host) || width <= 0 || height <= 0 || max_keypoints <= 0 ||
+      !cam || !prm || !n_objects || (fill_scale < 1 && fill_scale != 0 && fill_scale != -1)) {
+    ctx->err = "mh_frame_run_kinect_host: bad argument";
+    return MH_ERR_ARG;
+  }
+  *n_objects = 0;
+  if (int rc_enter = mh::enter(ctx)) return rc_enter;
+  hipStream_t s = ctx->stream;
+  const size_t px = (size_t)width * height;
+  mh_frame_set_depth_image(ctx, nullptr, nullptr, 0, 0, 0, alpha, 0.f);   // (the own buffers may move)
+  if (int rc = ensure_own_depth(ctx, px)) return rc;
+  MH_HIP(ctx, ctx->own_gray.ensure(px, s));
+  MH_HIP(ctx, hipMemcpyAsync(ctx->own_gray, gray_host, px, hipMemcpyHostToDevice, s));
+  MH_HIP(ctx, hipMemcpyAsync(ctx->own_depth, depth_xyzn_host, px * 4 * sizeof(float), hipMemcpyHostToDevice, s));
+  const bool have_fill = fill || fill_distance_host;
+  if (fill) {
+    if (int rc = mh_depth_fill(ctx, ctx->own_depth, width, height, fill_scale, bilinear, cam->K, ctx->own_fill, nullptr)) return rc;
+  } else if (fill_distance_host) {
+    MH_HIP(ctx, hipMemcpyAsync(ctx->own_fill, fill_distance_host, px * sizeof(float), hipMemcpyHostToDevice, s));
+  }
+  if (int rc = mh_frame_set_depth_image(ctx, ctx->own_depth, have_fill ? ctx->own_fill.p : nullptr, width, height, kind,
+                                        alpha, cauchy_scale)) {
+    ctx->err = "mh_frame_run_kinect_host: kind must be MH_DEPTH_BACKPROJECTION or MH_DEPTH_REPROJECTION, cauchy_scale > 0";
+    return rc;
+  }
+  if (int rc = mh_frame_enqueue_image(ctx, ctx->own_gray, width, height, double_size, max_keypoints, cam, prm, seed)) return rc;
+  if (fill) {   // the frame's images as DEPTH_FILL_EXACT_CPU::process leaves them, behind the frame's launches
+    MH_HIP(ctx, hipMemcpyAsync(depth_xyzn_host, ctx->own_depth, px * 4 * sizeof(float), hipMemcpyDeviceToHost, s));
+    MH_HIP(ctx, hipMemcpyAsync(fill_distance_host, ctx->own_fill, px * sizeof(float), hipMemcpyDeviceToHost, s));
+  }
+  const int rc = mh_frame_fetch(ctx, objects_host, max_objects, n_objects, counts);
+  const int rc_fill = fill ? mh_depth_fill_status(ctx) : MH_OK;
+  return rc ? rc : rc_fill;
+}
 
 int mh_step_match(mh_ctx* ctx, float* q_desc_host, const float* q_uv_host, int Q, const mh_cam* cam, float ratio,
                   int write_back) {

@@ -272,6 +272,7 @@ struct mh_ctx {
   mh::LinkageParams linkage;
   mh::DevBuf<float> own_depth;    // device copies of a host depth / distance map (ensure_own_depth)
   mh::DevBuf<float> own_fill;
+  mh::DevBuf<uint8_t> own_gray;   // device copy of a host gray image (mh_frame_run_kinect_host)
   mh::DevBuf<float> lk_scratch;
   mh::DevBuf<unsigned char> df_buf;   // mh_depth_fill[_batch]: [status words | per frame: downscaled depths, downscaled distances]
   size_t lk_scratch_limit = (size_t)4 << 30;   // bytes; mh_set_linkage_scratch_limit

@@ -111,7 +111,71 @@ __global__ __launch_bounds__(1024) void feature_density_kernel(const float* __re
   }
 }
 
+// DEPTHFILTER as a step of its own (mh_depth_filter) on the step's own lists: group g = points [group_off[g],
+// group_off[g + 1]) -- ONE group is ToFilter = 1 (:180-214, the detected features), one group per model ToFilter = 2
+// (:215-251, every model's matches with a countMap of their own).  One workgroup per group.  The reference adds the
+// double `1.0 / sizeMap[p]` to the Float countMap[p] once per point, in list order; every addition into one patch adds
+// the same double, so the patch's value depends on how many points it has and not on where they stand in the list:
+// LDS holds the count, density_replay redoes the additions -- the arithmetic of feature_density_kernel and of
+// group_kernel's (a'), whose verdicts these are bit for bit.
+__global__ __launch_bounds__(1024) void group_density_kernel(const float* __restrict__ uv,
+                                                             const int32_t* __restrict__ group_off, int patch, int pw,
+                                                             int ph, const double* __restrict__ inv_size, float filter,
+                                                             uint8_t* __restrict__ keep) {
+  __shared__ int cnt[DF_MAX_PATCHES];
+  __shared__ float val[DF_MAX_PATCHES];
+  const int P = pw * ph;
+  const int a = group_off[blockIdx.x], b = group_off[blockIdx.x + 1];
+  if (b <= a) return;   // (the whole workgroup: an empty model)
+  for (int p = threadIdx.x; p < P; p += blockDim.x) cnt[p] = 0;
+  __syncthreads();
+  for (int i = a + threadIdx.x; i < b; i += blockDim.x) atomicAdd(&cnt[patch_of(uv[2 * i], uv[2 * i + 1], patch, pw, ph)], 1);
+  __syncthreads();
+  for (int p = threadIdx.x; p < P; p += blockDim.x) val[p] = density_replay(cnt[p], inv_size[p]);
+  __syncthreads();
+  for (int i = a + threadIdx.x; i < b; i += blockDim.x)
+    keep[i] = dilated(val, patch_of(uv[2 * i], uv[2 * i + 1], patch, pw, ph), pw, ph) > filter;
+}
+
+// DEPTHMAP_PROP as a step of its own (mh_depth_prop; DEPTHMAP_PROP_CPU.hpp:101-132): the pixel (int) u, (int) v of the
+// map -- truncated, no interpolation, clamped to the map where the reference reads out of bounds -- gives coord3D, depth
+// = its z and depthValid = (norm >= 0); fillDistance from the distance map, or -1 without one (:107-111).
+__global__ __launch_bounds__(256) void depth_prop_kernel(const float4* __restrict__ img, const float* __restrict__ fill,
+                                                         int w, int h, const float* __restrict__ uv, int n,
+                                                         mh_depth_info* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  int ix = (int)uv[2 * i], iy = (int)uv[2 * i + 1];
+  ix = ix < 0 ? 0 : (ix >= w ? w - 1 : ix);
+  iy = iy < 0 ? 0 : (iy >= h ? h - 1 : iy);
+  const size_t px = (size_t)iy * w + ix;
+  const float4 d = img[px];
+  mh_depth_info o;
+  o.depth_valid = d.w >= 0.f ? 1 : 0;
+  o.coord3d[0] = d.x;
+  o.coord3d[1] = d.y;
+  o.coord3d[2] = d.z;
+  o.depth = d.z;
+  o.fill_distance = fill ? fill[px] : -1.f;
+  out[i] = o;
+}
+
 }  // namespace
+
+int depth_filter_max_patches() { return DF_MAX_PATCHES; }
+
+void launch_group_density(const float* uv, const int32_t* group_off, int n_groups, int patch, int pw, int ph,
+                          const double* inv_size, float filter, uint8_t* keep, hipStream_t s) {
+  if (n_groups <= 0) return;
+  hipLaunchKernelGGL(group_density_kernel, dim3(n_groups), dim3(1024), 0, s, uv, group_off, patch, pw, ph, inv_size, filter,
+                     keep);
+}
+
+void launch_depth_prop(const DepthImage& dimg, const float* uv, int n, mh_depth_info* out, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(depth_prop_kernel, dim3((n + 255) / 256), dim3(256), 0, s, dimg.img, dimg.fill, dimg.w, dimg.h, uv, n,
+                     out);
+}
 
 void launch_depth_patches(const DepthImage& dimg, const float K[4], int patch, double* inv_size, hipStream_t s,
                           const DepthMaps* maps, int n_frames) {

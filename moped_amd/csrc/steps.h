@@ -98,6 +98,13 @@ void launch_depth_patches(const DepthImage& dimg, const float K[4], int patch, d
 void launch_feature_density(const float* q_uv, int Q, const int32_t* q_count, int patch, int pw, int ph,
                             const double* inv_size, float filter, uint8_t* keep, hipStream_t s,
                             int n_frames = 1 /* > 1: q_uv / keep / inv_size frame after frame (Q, Q, pw ph apart) */);
+// DEPTHFILTER on a step's own lists (mh_depth_filter): keep[i] for the points of n_groups groups, group g = points
+// [group_off[g], group_off[g + 1]) counted by themselves; pw ph <= depth_filter_max_patches().
+int depth_filter_max_patches();
+void launch_group_density(const float* uv, const int32_t* group_off, int n_groups, int patch, int pw, int ph,
+                          const double* inv_size, float filter, uint8_t* keep, hipStream_t s);
+// DEPTHMAP_PROP on a step's own points (mh_depth_prop): out[i] = the depth map's record under point i
+void launch_depth_prop(const DepthImage& dimg, const float* uv, int n, mh_depth_info* out, hipStream_t s);
 
 // ---- group -------------------------------------------------------------------
 // Ratio test + grouping by model in ascending query order (MATCH_ANN_CPU.hpp:165-176).

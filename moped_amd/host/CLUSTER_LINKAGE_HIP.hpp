@@ -54,8 +54,8 @@ class CLUSTER_LINKAGE_HIP : public MopedAlg {
         distanceMap = frameData.images[i].get();
         break;
       }
-    if (mh_frame_set_depth_image_host(ctx, (const float*)&depthmap->data[0], distanceMap ? (const float*)&distanceMap->data[0] : 0,
-                                      depthmap->width, depthmap->height, MH_DEPTH_BACKPROJECTION, 0.5f, 0.1f) != MH_OK) {
+    // (uploaded by this step only if no depth step of this frame has done so: HipDepthMaps, hip_session.hpp)
+    if (!HipDepthMaps::get().ensure(ctx, depthmap, distanceMap)) {
       HipSession::warn("mh_frame_set_depth_image_host");
       return;
     }

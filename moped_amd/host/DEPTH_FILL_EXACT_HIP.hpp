@@ -48,6 +48,7 @@ class DEPTH_FILL_EXACT_HIP : public MopedAlg {
       distance->data.resize((size_t)w * h * sizeof(Float));
       float K[4];
       for (int j = 0; j < 4; ++j) K[j] = image->intrinsicLinearCalibration[j];
+      HipDepthMaps::get().drop();   // (the fill goes through the context's own map buffers and rewrites the host map)
       if (mh_depth_fill_host(ctx, (float*)&image->data[0], w, h, scaleFactor, doBilinearInterpolation ? 1 : 0, K,
                              (float*)&distance->data[0], 0) != MH_OK) {
         HipSession::warn("mh_depth_fill_host");

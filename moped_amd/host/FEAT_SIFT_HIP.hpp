@@ -39,6 +39,11 @@ class FEAT_SIFT_HIP : public MopedAlg {
     for (int i = 0; i < (int)frameData.images.size(); i++) {
       Image* img = frameData.images[i].get();
       if (img->width <= 0 || img->height <= 0 || (int)img->data.size() < img->width * img->height) continue;
+#ifdef MOPED_AMD_WITH_DEPTH
+      // moped3d: a frame's depth and distance maps are Images too; only gray images have keypoints
+      // (moped3d/libmoped/src/feat/FEAT_SIFT_CPU.hpp:85-87)
+      if (img->imageType != IMAGE_TYPE_GRAY_IMAGE) continue;
+#endif
       vector<FrameData::DetectedFeature>& detectedFeatures = frameData.detectedFeatures[_stepName];
       int32_t n = 0;
       int rc;

@@ -150,6 +150,7 @@ class FILTER_PROJECTION_DEPTH_HIP : public MopedAlg {
       return;
     }
     HipHandover::get().drop();
+    HipDepthMaps::get().drop();   // (this step sets the context's map itself and clears it behind itself)
     if (!uploadTestPoints(ctx)) return;
     if (mh_frame_set_depth_image_host(ctx, (const float*)&depthmap->data[0], distanceMap ? (const float*)&distanceMap->data[0] : 0,
                                       depthmap->width, depthmap->height, MH_DEPTH_BACKPROJECTION, 0.5f, 0.1f) != MH_OK) {

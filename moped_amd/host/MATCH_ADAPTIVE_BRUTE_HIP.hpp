@@ -19,18 +19,23 @@
 
 namespace MopedNS {
 
-class MATCH_ADAPTIVE_BRUTE_HIP : public MopedAlg {
-  int DescriptorSize;
-  string DescriptorType;
+// What Update() of moped3d's MATCH step leaves behind (MATCH_ADAPTIVE_FLANN_CPU.hpp:100-177), shared by the step plugin
+// below and by FRAME_RESIDENT_3D_HIP: the models' descriptors normalised in place and resident on the device (uploaded, or
+// edited with IncrementalModels), the row -> model / model point tables, and per model the four control points of its
+// ratio curve -- the rows of mh_frame_set_depth_rules' ratio_table.
+struct HipAdaptiveModels {
   Float MinRatioMin, MinRatioMax, MaxRatioMin, MaxRatioMax;
   Float DimensionPeak, DimensionFade;
-  Float MaximumDepth, DefaultDepth, CauchyScale;
   bool skipCalculation;
-  int IncrementalModels;   // config key, default 0: Update() edits the resident database instead of uploading every model again
   vector<int> correspModel;
   vector<Pt<3>*> correspFeat;
   vector<float> packed;
   vector<float> controlPoints;   // per model: maxRatioDepth, minRatioDepth, ratioLow, ratioHigh
+
+  HipAdaptiveModels(Float MinRatioMin, Float MinRatioMax, Float MaxRatioMin, Float MaxRatioMax, Float DimensionPeak,
+                    Float DimensionFade)
+      : MinRatioMin(MinRatioMin), MinRatioMax(MinRatioMax), MaxRatioMin(MaxRatioMin), MaxRatioMax(MaxRatioMax),
+        DimensionPeak(DimensionPeak), DimensionFade(DimensionFade), skipCalculation(true) {}
 
   // sqrt of the image area the largest face of the (centred) bounding box covers at `depth` (:262-312)
   static Float projectedLength(const Pt<3> box[2], const Pt<4>& k, Float depth) {
@@ -69,21 +74,10 @@ class MATCH_ADAPTIVE_BRUTE_HIP : public MopedAlg {
     }
     return (left + right) / 2;
   }
-  Float getRatio(Float depth, int m) const {             // :193-215
-    if (depth > MaximumDepth) return 0;
-    const Float maxRatioDepth = controlPoints[4 * m], minRatioDepth = controlPoints[4 * m + 1],
-                ratioLow = controlPoints[4 * m + 2], ratioHigh = controlPoints[4 * m + 3];
-    if (depth < maxRatioDepth) return ratioLow + (depth / maxRatioDepth) * (ratioHigh - ratioLow);
-    if (depth < minRatioDepth) return ratioHigh;
-    if (depth < minRatioDepth * 2) return ((minRatioDepth * 2 - depth) / minRatioDepth) * ratioHigh;
-    return 0;
-  }
 
-  void Update(FrameData& frameData) {
+  // false: a call failed (skipCalculation stays true, the caller leaves configUpdated set and tries again next frame)
+  bool update(vector<SP_Model>* models, const string& DescriptorType, int IncrementalModels, FrameData& frameData) {
     skipCalculation = true;
-    MaximumDepth = 4.0;
-    DefaultDepth = 1.0;
-    CauchyScale = 0.1;
     mh_ctx* ctx = HipSession::get();
     size_t n = 0;
     for (size_t m = 0; m < models->size(); ++m) n += (*models)[m]->IPs[DescriptorType].size();
@@ -109,7 +103,7 @@ class MATCH_ADAPTIVE_BRUTE_HIP : public MopedAlg {
     if (edited) {
       skipCalculation = n <= 1;
     } else if (n > 1) {
-      if (mh_normalize(ctx, &packed[0], (int)n) != MH_OK) { HipSession::warn("mh_normalize"); return; }
+      if (mh_normalize(ctx, &packed[0], (int)n) != MH_OK) { HipSession::warn("mh_normalize"); return false; }
       x = 0;
       for (size_t m = 0; m < models->size(); ++m) {       // Update() normalises the model descriptors in place (:122)
         vector<Model::IP>& ips = (*models)[m]->IPs[DescriptorType];
@@ -118,7 +112,7 @@ class MATCH_ADAPTIVE_BRUTE_HIP : public MopedAlg {
       }
       if (mh_db_upload(ctx, &packed[0], &owner[0], &xyz[0], (int)n, (int)models->size(), 0) != MH_OK) {
         HipSession::warn("mh_db_upload");
-        return;
+        return false;
       }
       skipCalculation = false;
       if (IncrementalModels) HipResidentModels::get().record(*models, DescriptorType);
@@ -139,15 +133,46 @@ class MATCH_ADAPTIVE_BRUTE_HIP : public MopedAlg {
       controlPoints[4 * m + 2] = MinRatioMin + densityAdjust * (MinRatioMax - MinRatioMin);
       controlPoints[4 * m + 3] = MaxRatioMin + densityAdjust * (MaxRatioMax - MaxRatioMin);
     }
-    configUpdated = false;
+    return true;
+  }
+};
+
+class MATCH_ADAPTIVE_BRUTE_HIP : public MopedAlg {
+  int DescriptorSize;
+  string DescriptorType;
+  Float MaximumDepth, DefaultDepth, CauchyScale;
+  int IncrementalModels;   // config key, default 0: Update() edits the resident database instead of uploading every model again
+  HipAdaptiveModels am;
+  bool& skipCalculation;
+  vector<int>& correspModel;
+  vector<Pt<3>*>& correspFeat;
+  vector<float>& packed;
+  vector<float>& controlPoints;
+
+  Float getRatio(Float depth, int m) const {             // :193-215
+    if (depth > MaximumDepth) return 0;
+    const Float maxRatioDepth = controlPoints[4 * m], minRatioDepth = controlPoints[4 * m + 1],
+                ratioLow = controlPoints[4 * m + 2], ratioHigh = controlPoints[4 * m + 3];
+    if (depth < maxRatioDepth) return ratioLow + (depth / maxRatioDepth) * (ratioHigh - ratioLow);
+    if (depth < minRatioDepth) return ratioHigh;
+    if (depth < minRatioDepth * 2) return ((minRatioDepth * 2 - depth) / minRatioDepth) * ratioHigh;
+    return 0;
+  }
+
+  void Update(FrameData& frameData) {
+    MaximumDepth = 4.0;
+    DefaultDepth = 1.0;
+    CauchyScale = 0.1;
+    if (am.update(models, DescriptorType, IncrementalModels, frameData)) configUpdated = false;
   }
 
  public:
   MATCH_ADAPTIVE_BRUTE_HIP(int DescriptorSize, string DescriptorType, Float MinRatioMin, Float MinRatioMax,
                            Float MaxRatioMin, Float MaxRatioMax, Float DimensionPeak, Float DimensionFade)
-      : DescriptorSize(DescriptorSize), DescriptorType(DescriptorType), MinRatioMin(MinRatioMin),
-        MinRatioMax(MinRatioMax), MaxRatioMin(MaxRatioMin), MaxRatioMax(MaxRatioMax), DimensionPeak(DimensionPeak),
-        DimensionFade(DimensionFade), MaximumDepth(4.0), DefaultDepth(1.0), CauchyScale(0.1), skipCalculation(true), IncrementalModels(0) {
+      : DescriptorSize(DescriptorSize), DescriptorType(DescriptorType), MaximumDepth(4.0), DefaultDepth(1.0), CauchyScale(0.1),
+        IncrementalModels(0), am(MinRatioMin, MinRatioMax, MaxRatioMin, MaxRatioMax, DimensionPeak, DimensionFade),
+        skipCalculation(am.skipCalculation), correspModel(am.correspModel), correspFeat(am.correspFeat), packed(am.packed),
+        controlPoints(am.controlPoints) {
     capable = (DescriptorSize == MH_DESC_DIM) && HipSession::get() != 0;
   }
 
@@ -155,12 +180,12 @@ class MATCH_ADAPTIVE_BRUTE_HIP : public MopedAlg {
   const vector<float>& table() const { return controlPoints; }
 
   void getConfig(map<string, string>& config) const {
-    hipGetConfig(config, _stepName, _alg, "MATCH_ADAPTIVE_BRUTE_HIP", "MinRatioMin", MinRatioMin);
-    hipGetConfig(config, _stepName, _alg, "MATCH_ADAPTIVE_BRUTE_HIP", "MinRatioMax", MinRatioMax);
-    hipGetConfig(config, _stepName, _alg, "MATCH_ADAPTIVE_BRUTE_HIP", "MaxRatioMin", MaxRatioMin);
-    hipGetConfig(config, _stepName, _alg, "MATCH_ADAPTIVE_BRUTE_HIP", "MaxRatioMax", MaxRatioMax);
-    hipGetConfig(config, _stepName, _alg, "MATCH_ADAPTIVE_BRUTE_HIP", "DimensionPeak", DimensionPeak);
-    hipGetConfig(config, _stepName, _alg, "MATCH_ADAPTIVE_BRUTE_HIP", "DimensionFade", DimensionFade);
+    hipGetConfig(config, _stepName, _alg, "MATCH_ADAPTIVE_BRUTE_HIP", "MinRatioMin", am.MinRatioMin);
+    hipGetConfig(config, _stepName, _alg, "MATCH_ADAPTIVE_BRUTE_HIP", "MinRatioMax", am.MinRatioMax);
+    hipGetConfig(config, _stepName, _alg, "MATCH_ADAPTIVE_BRUTE_HIP", "MaxRatioMin", am.MaxRatioMin);
+    hipGetConfig(config, _stepName, _alg, "MATCH_ADAPTIVE_BRUTE_HIP", "MaxRatioMax", am.MaxRatioMax);
+    hipGetConfig(config, _stepName, _alg, "MATCH_ADAPTIVE_BRUTE_HIP", "DimensionPeak", am.DimensionPeak);
+    hipGetConfig(config, _stepName, _alg, "MATCH_ADAPTIVE_BRUTE_HIP", "DimensionFade", am.DimensionFade);
     hipGetConfig(config, _stepName, _alg, "MATCH_ADAPTIVE_BRUTE_HIP", "DescriptorType", DescriptorType);
     hipGetConfig(config, _stepName, _alg, "MATCH_ADAPTIVE_BRUTE_HIP", "DescriptorSize", DescriptorSize);
   }

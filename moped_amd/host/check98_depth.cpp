@@ -7,4 +7,7 @@ namespace std { using tr1::shared_ptr; }
 #include "MATCH_ADAPTIVE_BRUTE_HIP.hpp"
 #include "CLUSTER_LINKAGE_HIP.hpp"
 #include "POSE_RANSAC_P3P_DEPTH_HIP.hpp"
+#include "DEPTHFILTER_HIP.hpp"
+#include "DEPTHMAP_PROP_HIP.hpp"
+#include "FRAME_RESIDENT_3D_HIP.hpp"
 int main() { return 0; }

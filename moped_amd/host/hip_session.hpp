@@ -236,6 +236,56 @@ struct HipCameraTable {
   }
 };
 
+// The frame's depth map on the device, shared by moped3d's steps of one frame (DEPTHFILTER_HIP, DEPTHFILTER2,
+// DEPTHMAP_PROP_HIP, CLUSTER_LINKAGE_HIP): the first of them that finds another map than the context holds uploads it
+// (mh_frame_set_depth_image_host: 4.9 MB + 1.2 MB for 640x480), the others pass NULL and read that copy -- the map
+// crosses PCIe once per frame instead of once per step.  "The same map" = the same Image objects with the same buffers,
+// sizes and a sample of 4096 words of each (a sensor's next frame differs in nearly every pixel; a step that rewrites
+// the map in place -- DEPTH_FILL_EXACT_HIP -- or hands the context another one calls drop()).  One instance per process.
+struct HipDepthMaps {
+  unsigned long long tag;
+  bool valid;
+  unsigned long uploads;   // (tests, moped3d_hip_test)
+
+  static HipDepthMaps& get() {
+    static HipDepthMaps d;
+    return d;
+  }
+  void drop() { valid = false; }
+  static unsigned long long sample(unsigned long long h, const Image* im) {
+    const void* p = im;
+    const unsigned char* data = im->data.empty() ? 0 : &im->data[0];
+    const size_t words = im->data.size() / 4, step = words / 4096 + 1;
+    h = HipHandover::mix(h, &p, sizeof p);
+    h = HipHandover::mix(h, &data, sizeof data);
+    h = HipHandover::mix(h, &im->width, sizeof im->width);
+    h = HipHandover::mix(h, &im->height, sizeof im->height);
+    h = HipHandover::mix(h, &words, sizeof words);
+    for (size_t i = 0; i < words; i += step) h = HipHandover::mix(h, data + 4 * i, 4);
+    return h;
+  }
+  // true: the context holds depthmap (and distanceMap, or none) as its frame map
+  bool ensure(mh_ctx* ctx, const Image* depthmap, const Image* distanceMap) {
+    const size_t px = (size_t)(depthmap->width > 0 ? depthmap->width : 0) * (size_t)(depthmap->height > 0 ? depthmap->height : 0);
+    if (px == 0 || depthmap->data.size() < px * 4 * sizeof(float)) return false;
+    if (distanceMap && distanceMap->data.size() < px * sizeof(float)) distanceMap = 0;
+    unsigned long long t = sample(1469598103934665603ull, depthmap);
+    if (distanceMap) t = sample(t, distanceMap);
+    if (valid && t == tag) return true;
+    valid = false;
+    if (mh_frame_set_depth_image_host(ctx, (const float*)&depthmap->data[0], distanceMap ? (const float*)&distanceMap->data[0] : 0,
+                                      depthmap->width, depthmap->height, MH_DEPTH_BACKPROJECTION, 0.5f, 0.1f) != MH_OK)
+      return false;
+    tag = t;
+    valid = true;
+    ++uploads;
+    return true;
+  }
+
+ private:
+  HipDepthMaps() : tag(0), valid(false), uploads(0) {}
+};
+
 // Same key layout as GET_CONFIG: "<STEP>:<algIdx>:<HeaderBasename>/<var>" (src/util.hpp:62)
 template <typename T>
 inline void hipGetConfig(std::map<std::string, std::string>& config, const std::string& step, int alg,

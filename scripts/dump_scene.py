@@ -61,6 +61,36 @@ def dump_images(path, db, frame, images, q_image):
         f.write(np.asarray(q_image, "<i4").tobytes())
 
 
+def dump_kinect(path, db_desc, db_xyz, model_of, n_models, depth_img, K=synth.K_DEFAULT, cam=synth.CAM_IDENTITY, uv=None,
+                desc=None, gray=None, distance=None, patch_size=64, feature_density=0.05, match_density=0.01, fill_scale=0,
+                max_keypoints=2048):
+    """A Kinect frame for moped_amd/host/moped3d_hip_test (format in its header): the model DB, the frame's features
+    (uv [Q, 2], desc [Q, 128]) and / or its gray image [h, w] uint8, the depth map [h, w, 4] and -- for a map that
+    arrives filled (fill_scale 0) -- its distance map [h, w]."""
+    h, w = depth_img.shape[:2]
+    Q = 0 if uv is None else len(uv)
+    with open(path, "wb") as f:
+        f.write(struct.pack("<9i", n_models, Q, w, h, int(gray is not None), int(distance is not None), int(patch_size),
+                            int(fill_scale), int(max_keypoints)))
+        f.write(struct.pack("<2f", feature_density, match_density))
+        f.write(np.asarray(K, "<f4").tobytes())
+        f.write(np.asarray(cam, "<f4").tobytes())
+        for m in range(n_models):
+            rows = np.nonzero(np.asarray(model_of) == m)[0]
+            f.write(struct.pack("<i", len(rows)))
+            f.write(np.asarray(db_xyz)[rows].astype("<f4").tobytes())
+            f.write(np.asarray(db_desc)[rows].astype("<f4").tobytes())
+        if Q:
+            f.write(np.asarray(uv, "<f4").tobytes())
+            f.write(np.asarray(desc, "<f4").tobytes())
+        if gray is not None:
+            assert gray.shape == (h, w) and gray.dtype == np.uint8
+            f.write(np.ascontiguousarray(gray).tobytes())
+        f.write(np.ascontiguousarray(depth_img, "<f4").tobytes())
+        if distance is not None:
+            f.write(np.ascontiguousarray(distance, "<f4").reshape(h, w).tobytes())
+
+
 if __name__ == "__main__":
     out = sys.argv[1] if len(sys.argv) > 1 else "scene.bin"
     n_models = int(sys.argv[2]) if len(sys.argv) > 2 else 20
