@@ -673,6 +673,23 @@ int mh_set_linkage_scratch_limit(mh_ctx* ctx, size_t bytes);
 int mh_cluster_linkage(mh_ctx* ctx, const mh_corr* corr_host, const mh_depth* depth_host, const int32_t* off,
                        int n_problems, const mh_linkage_params* prm, int32_t* label, int32_t* order,
                        int32_t* n_clusters);
+/* For tests, in the style of mh_depth_rules_debug_fetch / mh_sift_debug_*: the clusterer's two halves on their own.
+ * mh_linkage_debug_matrix: ONE problem of n matches (1 .. 1024) as mh_cluster_linkage takes it (cutoff, min_pts and
+ *   linkage_type of *prm are not used) -> two n x n float matrices: A_host = the 3-D side after pass 2 -- K3D +
+ *   discontinuity kernel (CLUSTER_LINKAGE_CPU.hpp:133-149, 231-285, 681), normalised, + / x K3F (:151-173, 683-692),
+ *   BEFORE the division by its maximum (use3d_filter 0: the first sum, before its only normalisation) -- and K_host = the
+ *   final similarity (adaptiveWeightSum, :325-366) as hierarchicalCluster (:416) first sees it.  The same kernel, run with
+ *   a cutoff above every similarity so that its loop ends in the first scan.  A is computed for j >= i only: the call
+ *   mirrors it; K is handed out as the device holds it, both halves.
+ * mh_linkage_debug_agglomerate: hierarchicalCluster (:416-540) alone, over a symmetric n x n host matrix K_host in place of
+ *   the matrix stages (the kernel skips the sigmas and passes 1-3 and takes the matrix as uploaded; everything from there
+ *   on is the shipped code).  label [n] / order [n] (optional) / *n_clusters as mh_cluster_linkage's for one problem.
+ * n outside 1 .. 1024, a linkage_type outside 0 .. 2, no depth map (matrix) -> MH_ERR_ARG / MH_ERR_CAPACITY with a
+ * message, nothing is launched. */
+int mh_linkage_debug_matrix(mh_ctx* ctx, const mh_corr* corr_host, const mh_depth* depth_host, int n,
+                            const mh_linkage_params* prm, float* A_host, float* K_host);
+int mh_linkage_debug_agglomerate(mh_ctx* ctx, const float* K_host, int n, float cutoff, int min_pts, int linkage_type,
+                                 int32_t* label, int32_t* order, int32_t* n_clusters);
 /* The two halves around exchange 1 when the DB is sharded over ranks.
  *   mh_frame_enqueue_match_local : normalise + this shard's top-2 -> top2_dev, a
  *       caller-owned device block of [3][Q] 32-bit words {idx1 (global row, int32),
@@ -792,6 +809,15 @@ int mh_frame_fetch_match_reps_slot(mh_ctx* ctx, int slot, int32_t* rep_host, int
  * bytes must be exactly the array's size; a wrong size, a slot whose maps are gone or an array the last frame did not
  * write -> MH_ERR_ARG, nothing is read. */
 int mh_depth_rules_debug_fetch(mh_ctx* ctx, int which, int slot, void* out_host, size_t bytes);
+/* For tests, next to mh_frame_fetch_matches_slot: what CLUSTER left for frame `slot` of the last frame / batch, as
+ * mh_step_cluster reports a stepped frame's -- cl_model_host[c] = the model of cluster c (clusters in (model, emission)
+ * order, the order POSE walks them), members of cluster c = members_host[cl_off_host[c] .. cl_off_host[c + 1]), indices
+ * INSIDE that model's match list in the clusterer's member order.  Read from the per-model lists the clusterer wrote (the
+ * flat cluster table is FILTER's by the end of a frame).  The same slots and errors as mh_frame_fetch_matches_slot;
+ * cl_off_host holds cap_clusters + 1 entries; more clusters or members than the caps -> MH_ERR_CAPACITY with
+ * *n_clusters = their number. */
+int mh_frame_debug_fetch_clusters_slot(mh_ctx* ctx, int slot, int32_t* cl_model_host, int32_t* cl_off_host,
+                                       int32_t* members_host, int cap_clusters, int cap_members, int32_t* n_clusters);
 /* Device address of the frame's packed result block {int32 n; mh_object[cap]}
  * for exchange 2 (gather of per-rank objects); *bytes = its size. */
 int mh_frame_result_dev(mh_ctx* ctx, void** block_dev, int64_t* bytes);

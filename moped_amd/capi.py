@@ -148,6 +148,7 @@ EXPORTS = [
     "mh_filter_depth_set_points", "mh_filter_depth", "mh_frame_set_filter_depth",
     "mh_frame_route", "mh_filter_depth_debug_form",
     "mh_depth_filter", "mh_depth_prop", "mh_frame_run_kinect_host",
+    "mh_linkage_debug_matrix", "mh_linkage_debug_agglomerate", "mh_frame_debug_fetch_clusters_slot",
 ]
 COMM_ID_BYTES = 128      # MH_COMM_ID_BYTES
 EX2_OBJECTS = 62         # MH_EX2_OBJECTS
@@ -235,6 +236,10 @@ def load():
     L.mh_depth_fill_host.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.mh_frame_set_cluster_linkage.argtypes = [vp, C.POINTER(mh_linkage_params)]
     L.mh_cluster_linkage.argtypes = [vp, vp, vp, vp, i32, C.POINTER(mh_linkage_params), vp, vp, vp]
+    if hasattr(L, "mh_linkage_debug_matrix"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
+        L.mh_linkage_debug_matrix.argtypes = [vp, vp, vp, i32, C.POINTER(mh_linkage_params), vp, vp]
+        L.mh_linkage_debug_agglomerate.argtypes = [vp, vp, i32, f32, i32, i32, vp, vp, C.POINTER(C.c_int32)]
+        L.mh_frame_debug_fetch_clusters_slot.argtypes = [vp, i32, vp, vp, vp, i32, i32, C.POINTER(C.c_int32)]
     L.mh_frame_set_depth_rules.argtypes = [vp, C.POINTER(mh_depth_rules), vp]
     L.mh_frame_enqueue_rest_strided.argtypes = [vp, vp, i32, vp, i32, i32, C.POINTER(mh_cam),
                                                 C.POINTER(mh_frame_params), C.c_uint64]
@@ -1476,6 +1481,47 @@ class Context:
                 pos += sz
             out.append((clusters, lab.copy()))
         return out
+
+    # the clusterer's two halves on their own, for verification (mh_linkage_debug_*)
+    def linkage_debug_matrix(self, uv, model_xyz, world_xyz, params=None):
+        """One problem as cluster_linkage takes it -> (A, K) float32 [n, n]: the 3-D side after pass 2 (before the
+        division by its maximum) and the final similarity as the agglomeration first sees it."""
+        prm = params or default_linkage_params()
+        n = len(uv)
+        corr = np.ascontiguousarray(pack_corr(np.asarray(uv, np.float32), np.asarray(model_xyz, np.float32)))
+        dep = np.ascontiguousarray(pack_depth(np.asarray(world_xyz, np.float32), np.ones(n, np.float32)))
+        A, K = np.zeros((n, n), np.float32), np.zeros((n, n), np.float32)
+        self._ck(self.L.mh_linkage_debug_matrix(self.h, _ptr(corr), _ptr(dep), n, C.byref(prm), _ptr(A), _ptr(K)),
+                 "mh_linkage_debug_matrix")
+        return A, K
+
+    def linkage_debug_agglomerate(self, Km, cutoff=0.1, min_pts=7, linkage_type=1):
+        """The agglomeration alone over a symmetric similarity matrix [n, n] -> (clusters, label) as cluster_linkage's."""
+        Km = np.ascontiguousarray(Km, np.float32)
+        n = len(Km)
+        if Km.shape != (n, n):
+            raise ValueError("linkage_debug_agglomerate: a square matrix")
+        label, order = np.full(max(n, 1), -1, np.int32), np.full(max(n, 1), -1, np.int32)
+        ncl = C.c_int32(0)
+        self._ck(self.L.mh_linkage_debug_agglomerate(self.h, _ptr(Km), n, C.c_float(cutoff), int(min_pts), int(linkage_type),
+                                                     _ptr(label), _ptr(order), C.byref(ncl)), "mh_linkage_debug_agglomerate")
+        label = label[:n]
+        clusters, pos = [], 0
+        for c in range(ncl.value):
+            sz = int((label == c).sum())
+            clusters.append(order[pos:pos + sz].copy())
+            pos += sz
+        return clusters, label.copy()
+
+    def frame_debug_fetch_clusters_slot(self, slot=0, cap_clusters=4096, cap_members=1 << 16):
+        """CLUSTER's result of frame `slot` of the last frame / batch -> list of (model, member indices inside that model's
+        match list, in the clusterer's order), clusters in (model, emission) order."""
+        cm, co = np.zeros(cap_clusters, np.int32), np.zeros(cap_clusters + 1, np.int32)
+        mem = np.zeros(cap_members, np.int32)
+        n = C.c_int32(0)
+        self._ck(self.L.mh_frame_debug_fetch_clusters_slot(self.h, int(slot), _ptr(cm), _ptr(co), _ptr(mem), cap_clusters,
+                                                           cap_members, C.byref(n)), "mh_frame_debug_fetch_clusters_slot")
+        return [(int(cm[c]), mem[co[c]:co[c + 1]].copy()) for c in range(n.value)]
 
     def frame_set_depth_rules(self, K=None, patch_size=64, feature_density=-1.0, match_density=-1.0, ratio_table=None,
                               maximum_depth=4.0, default_depth=1.0, cauchy_scale=0.1, off=False):

@@ -1074,6 +1074,61 @@ int mh_depth_rules_debug_fetch(mh_ctx* ctx, int which, int slot, void* out_host,
   return MH_OK;
 }
 
+int mh_frame_debug_fetch_clusters_slot(mh_ctx* ctx, int slot, int32_t* cl_model_host, int32_t* cl_off_host,
+                                       int32_t* members_host, int cap_clusters, int cap_members, int32_t* n_clusters) {
+  static const char* const who = "mh_frame_debug_fetch_clusters_slot";
+  if (!ctx || !ctx->fs || !n_clusters || cap_clusters < 0 || cap_members < 0 || slot < 0 || slot >= MH_MAX_BATCH)
+    return MH_ERR_ARG;
+  *n_clusters = 0;
+  size_t a = 0;
+  int take = 0;
+  int32_t M = 0;
+  if (int rc = match_lists(ctx, who, slot, INT_MAX, &M, &a, &take)) return rc;
+  const FrameState* fs = ctx->fs;
+  const int nm = ctx->n_models;
+  if (M < 0 || M > fs->max_m || nm > fs->n_models_cap) {
+    ctx->err = std::string(who) + ": inconsistent match count";
+    return MH_ERR_HIP;
+  }
+  // the per-model lists as the clusterers write them (steps.h: members / cl_start / ncl of launch_meanshift_models)
+  std::vector<int32_t> off(nm + 1), ncl(nm + 1), start((size_t)M + nm + 1), mem(std::max(M, 1));
+  auto get = [&](std::vector<int32_t>& to, const int32_t* from, size_t n) {
+    return hipMemcpy(to.data(), reinterpret_cast<const unsigned char*>(from) + a, n * sizeof(int32_t), hipMemcpyDeviceToHost);
+  };
+  MH_HIP(ctx, get(off, fs->model_off, (size_t)nm + 1));
+  MH_HIP(ctx, get(ncl, fs->ms_ncl, (size_t)nm));
+  MH_HIP(ctx, get(start, fs->ms_cl_start, (size_t)M + nm + 1));
+  if (M > 0) MH_HIP(ctx, get(mem, fs->ms_members, (size_t)M));
+  int n = 0, w = 0;
+  for (int m = 0; m < nm; ++m) {
+    const int b = off[m], k = off[m + 1] - b;
+    if (b < 0 || k < 0 || b + k > M || ncl[m] < 0 || ncl[m] > k) {
+      ctx->err = std::string(who) + ": inconsistent cluster lists";
+      return MH_ERR_HIP;
+    }
+    const int32_t* st = start.data() + b + m;
+    for (int c = 0; c < ncl[m]; ++c, ++n) {
+      if (st[c] < 0 || st[c + 1] < st[c] || st[c + 1] > k) {
+        ctx->err = std::string(who) + ": inconsistent cluster lists";
+        return MH_ERR_HIP;
+      }
+      if (n < cap_clusters) {
+        if (cl_model_host) cl_model_host[n] = m;
+        if (cl_off_host) cl_off_host[n] = w;
+      }
+      for (int j = st[c]; j < st[c + 1]; ++j, ++w)
+        if (members_host && w < cap_members) members_host[w] = mem[b + j] - b;   // index inside the model's match list
+    }
+  }
+  if (cl_off_host && n <= cap_clusters) cl_off_host[n] = w;
+  *n_clusters = n;
+  if (n > cap_clusters || w > cap_members) {
+    ctx->err = std::string(who) + ": more clusters or members than the caller's buffers hold";
+    return MH_ERR_CAPACITY;
+  }
+  return MH_OK;
+}
+
 int mh_frame_fetch_matches(mh_ctx* ctx, int32_t* query_host, int32_t* model_host, int cap, int32_t* n_matches) {
   if (!ctx || !ctx->fs) return MH_ERR_ARG;
   return mh_frame_fetch_matches_slot(ctx, ctx->fs->list_first + ctx->fs->list_n - 1, query_host, model_host, cap, n_matches);

@@ -31,6 +31,52 @@ void unpack_clusters(const int32_t* h, const int32_t* off, int n_problems, int32
   }
 }
 
+// mh_cluster_linkage and the debug entries behind it, once the arguments are checked: upload, ONE launch of
+// linkage_batch_kernel, the clusters back.  `need`: floats of matrix scratch (3 n^2 per problem).  K_given (with
+// lp.given_matrix, one problem): its similarity matrix, in place of the matches.
+int linkage_problems(mh_ctx* ctx, const mh_corr* corr_host, const mh_depth* depth_host, const int32_t* off, int n_problems,
+                     size_t need, const LinkageParams& lp, const float* K_given, int32_t* label, int32_t* order,
+                     int32_t* n_clusters) {
+  const int total = off[n_problems];
+  if (int rc_enter = mh::enter(ctx)) return rc_enter;
+  int rc = ensure_linkage_scratch(ctx, need);
+  if (rc) return rc;
+  // device layout: corr | depth | off | members | label | cl_start (total + n_problems + 1) | ncl
+  const size_t b_corr = ((size_t)total * sizeof(mh_corr) + 15) & ~(size_t)15;
+  const size_t b_depth = (size_t)total * sizeof(mh_depth);
+  const size_t n_off = (size_t)n_problems + 1, n_start = (size_t)total + n_problems + 1;
+  const size_t ints = n_off + 2 * (size_t)total + n_start + n_problems;
+  if ((rc = ensure_scratch(ctx, b_corr + b_depth + ints * sizeof(int32_t) + 64))) return rc;
+  if ((rc = ensure_pinned(ctx, (2 * (size_t)total + n_start + n_problems) * sizeof(int32_t)))) return rc;
+  unsigned char* base = ctx->scratch;
+  mh_corr* d_corr = (mh_corr*)base;
+  float* d_depth = (float*)(base + b_corr);
+  int32_t* d_off = (int32_t*)(base + b_corr + b_depth);
+  int32_t* d_members = d_off + n_off;
+  int32_t* d_label = d_members + total;
+  int32_t* d_start = d_label + total;
+  int32_t* d_ncl = d_start + n_start;
+  hipStream_t s = ctx->stream;
+  if (!K_given) {
+    MH_HIP(ctx, hipMemcpyAsync(d_corr, corr_host, (size_t)total * sizeof(mh_corr), hipMemcpyHostToDevice, s));
+    MH_HIP(ctx, hipMemcpyAsync(d_depth, depth_host, b_depth, hipMemcpyHostToDevice, s));
+  }
+  MH_HIP(ctx, hipMemcpyAsync(d_off, off, n_off * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  // (the debug entries: one problem, whose matrix region starts the scratch -- A | Dm | member lists, linkage.hip)
+  if (K_given)
+    MH_HIP(ctx, hipMemcpyAsync(ctx->lk_scratch.p + (size_t)total * total, K_given, (size_t)total * total * sizeof(float),
+                               hipMemcpyHostToDevice, s));
+  launch_linkage_batch(d_corr, d_depth, d_off, n_problems, ctx->depth_img, lp, ctx->lk_scratch, ctx->lk_scratch.cap,
+                       d_members, d_start, d_ncl, d_label, s);
+  MH_HIP(ctx, hipGetLastError());
+  int32_t* hbuf = (int32_t*)ctx->pinned.p;
+  MH_HIP(ctx, hipMemcpyAsync(hbuf, d_members, (2 * (size_t)total + n_start + n_problems) * sizeof(int32_t),
+                             hipMemcpyDeviceToHost, s));
+  MH_HIP(ctx, hipStreamSynchronize(s));
+  unpack_clusters(hbuf, off, n_problems, label, order, n_clusters);
+  return MH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -278,28 +324,6 @@ int mh_cluster_linkage(mh_ctx* ctx, const mh_corr* corr_host, const mh_depth* de
     ctx->err = "mh_cluster_linkage: bad argument";
     return MH_ERR_ARG;
   }
-  if (int rc_enter = mh::enter(ctx)) return rc_enter;
-  int rc = ensure_linkage_scratch(ctx, need);
-  if (rc) return rc;
-  // device layout: corr | depth | off | members | label | cl_start (total + n_problems + 1) | ncl
-  const size_t b_corr = ((size_t)total * sizeof(mh_corr) + 15) & ~(size_t)15;
-  const size_t b_depth = (size_t)total * sizeof(mh_depth);
-  const size_t n_off = (size_t)n_problems + 1, n_start = (size_t)total + n_problems + 1;
-  const size_t ints = n_off + 2 * (size_t)total + n_start + n_problems;
-  if ((rc = ensure_scratch(ctx, b_corr + b_depth + ints * sizeof(int32_t) + 64))) return rc;
-  if ((rc = ensure_pinned(ctx, (2 * (size_t)total + n_start + n_problems) * sizeof(int32_t)))) return rc;
-  unsigned char* base = ctx->scratch;
-  mh_corr* d_corr = (mh_corr*)base;
-  float* d_depth = (float*)(base + b_corr);
-  int32_t* d_off = (int32_t*)(base + b_corr + b_depth);
-  int32_t* d_members = d_off + n_off;
-  int32_t* d_label = d_members + total;
-  int32_t* d_start = d_label + total;
-  int32_t* d_ncl = d_start + n_start;
-  hipStream_t s = ctx->stream;
-  MH_HIP(ctx, hipMemcpyAsync(d_corr, corr_host, (size_t)total * sizeof(mh_corr), hipMemcpyHostToDevice, s));
-  MH_HIP(ctx, hipMemcpyAsync(d_depth, depth_host, b_depth, hipMemcpyHostToDevice, s));
-  MH_HIP(ctx, hipMemcpyAsync(d_off, off, n_off * sizeof(int32_t), hipMemcpyHostToDevice, s));
   LinkageParams lp;
   lp.cutoff = prm->cutoff;
   lp.min_pts = prm->min_pts;
@@ -307,15 +331,66 @@ int mh_cluster_linkage(mh_ctx* ctx, const mh_corr* corr_host, const mh_depth* de
   lp.sigma2d = prm->sigma2d;
   lp.sigma3d = prm->sigma3d;
   lp.linkage_type = prm->linkage_type;
-  launch_linkage_batch(d_corr, d_depth, d_off, n_problems, ctx->depth_img, lp, ctx->lk_scratch, ctx->lk_scratch.cap,
-                       d_members, d_start, d_ncl, d_label, s);
-  MH_HIP(ctx, hipGetLastError());
-  int32_t* hbuf = (int32_t*)ctx->pinned.p;
-  MH_HIP(ctx, hipMemcpyAsync(hbuf, d_members, (2 * (size_t)total + n_start + n_problems) * sizeof(int32_t),
-                             hipMemcpyDeviceToHost, s));
-  MH_HIP(ctx, hipStreamSynchronize(s));
-  unpack_clusters(hbuf, off, n_problems, label, order, n_clusters);
+  return linkage_problems(ctx, corr_host, depth_host, off, n_problems, need, lp, nullptr, label, order, n_clusters);
+}
+
+int mh_linkage_debug_matrix(mh_ctx* ctx, const mh_corr* corr_host, const mh_depth* depth_host, int n,
+                            const mh_linkage_params* prm, float* A_host, float* K_host) {
+  if (!ctx) return MH_ERR_ARG;
+  if (!corr_host || !depth_host || !prm || !A_host || !K_host) {
+    ctx->err = "mh_linkage_debug_matrix: bad argument";
+    return MH_ERR_ARG;
+  }
+  if (n < 1 || n > LK_CAP) {
+    ctx->err = "mh_linkage_debug_matrix: one problem of 1 .. 1024 points";
+    return n > LK_CAP ? MH_ERR_CAPACITY : MH_ERR_ARG;
+  }
+  if (!ctx->depth_img.img) {
+    ctx->err = "mh_linkage_debug_matrix: no depth map (mh_frame_set_depth_image)";
+    return MH_ERR_ARG;
+  }
+  // the shipped kernel with a cutoff no similarity reaches: hierarchicalCluster's loop leaves in its first scan
+  // (CLUSTER_LINKAGE_CPU.hpp:468) with the matrices of passes 2 and 3 still in the problem's scratch region
+  LinkageParams lp;
+  lp.cutoff = __builtin_inff();
+  lp.min_pts = prm->min_pts;
+  lp.use3d_filter = prm->use3d_filter;
+  lp.sigma2d = prm->sigma2d;
+  lp.sigma3d = prm->sigma3d;
+  const int32_t off[2] = {0, n};
+  const size_t nn = (size_t)n * n;
+  std::vector<int32_t> label(n);
+  int32_t ncl = 0;
+  if (int rc = linkage_problems(ctx, corr_host, depth_host, off, 1, 3 * nn, lp, nullptr, label.data(), nullptr, &ncl)) return rc;
+  MH_HIP(ctx, hipMemcpy(A_host, ctx->lk_scratch.p, nn * sizeof(float), hipMemcpyDeviceToHost));
+  MH_HIP(ctx, hipMemcpy(K_host, ctx->lk_scratch.p + nn, nn * sizeof(float), hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; ++i)   // (the kernel fills A for j >= i only)
+    for (int j = 0; j < i; ++j) A_host[(size_t)i * n + j] = A_host[(size_t)j * n + i];
   return MH_OK;
+}
+
+int mh_linkage_debug_agglomerate(mh_ctx* ctx, const float* K_host, int n, float cutoff, int min_pts, int linkage_type,
+                                 int32_t* label, int32_t* order, int32_t* n_clusters) {
+  if (!ctx) return MH_ERR_ARG;
+  if (!K_host || !label || !n_clusters) {
+    ctx->err = "mh_linkage_debug_agglomerate: bad argument";
+    return MH_ERR_ARG;
+  }
+  if (linkage_type < 0 || linkage_type > 2) {
+    ctx->err = "mh_linkage_debug_agglomerate: linkage_type must be 0 (minimum), 1 (average) or 2 (maximum)";
+    return MH_ERR_ARG;
+  }
+  if (n < 1 || n > LK_CAP) {
+    ctx->err = "mh_linkage_debug_agglomerate: a matrix of 1 .. 1024 rows";
+    return n > LK_CAP ? MH_ERR_CAPACITY : MH_ERR_ARG;
+  }
+  LinkageParams lp;
+  lp.cutoff = cutoff;
+  lp.min_pts = min_pts;
+  lp.linkage_type = linkage_type;
+  lp.given_matrix = 1;
+  const int32_t off[2] = {0, n};
+  return linkage_problems(ctx, nullptr, nullptr, off, 1, 3 * (size_t)n * n, lp, K_host, label, order, n_clusters);
 }
 
 int mh_project_test(mh_ctx* ctx, const float pose[7], const mh_corr* corr_host, int n,

@@ -11,7 +11,8 @@
 //   mem: cluster member lists, row c = cluster c (capacity n)
 // Every matrix element is computed by one thread with the reference's expression order
 // (Float = float, unsuffixed literals = double); what differs from the CPU is the device's
-// expf / atan2f (a few ulp).  The agglomeration is the reference's, quirks included (see
+// expf / atan2f (a few ulp; tests/test_gpu_linkage_stages.py bounds the matrices against float64 and
+// holds the agglomeration exactly, from the device's own matrix).  The agglomeration is the reference's, quirks included (see
 // oracle/linkage_oracle.cpp): per merge, a parallel arg-max over the candidate pairs in the
 // reference's scan order (first maximum wins), the average-linkage row update, the reversed
 // append of the absorbed cluster.
@@ -131,29 +132,11 @@ __device__ float wg_max(LkLds& L, float v) {
   return L.maxv;
 }
 
-__device__ void linkage_body(LkLds& L, const mh_corr* __restrict__ corr, const float4* __restrict__ depth4, int n,
-                             const DepthImage& D, const LinkageParams& P, float* __restrict__ A,
-                             float* Dm, int32_t* __restrict__ mem, int32_t* __restrict__ members_out,
-                             int32_t member_base, int32_t* __restrict__ cl_start_out, int32_t* __restrict__ ncl_out,
-                             int32_t* __restrict__ label_out) {
+// The matrix stages (:97-366): sigmas, K2D -> Dm, K3D + discontinuity (x / + K3F) -> A, the fill-weighted sum -> both halves
+// of Dm.  The match data is in LDS (linkage_body).
+__device__ void linkage_matrix(LkLds& L, int N, const DepthImage& D, const LinkageParams& P, float* __restrict__ A,
+                               float* Dm) {
   const int tid = threadIdx.x;
-  const int N = n;
-  for (int i = tid; i < N; i += LK_THREADS) {
-    const mh_corr c = corr[i];
-    const float4 d = depth4[i];
-    L.uv[i][0] = c.u;
-    L.uv[i][1] = c.v;
-    L.mx[i][0] = c.x;
-    L.mx[i][1] = c.y;
-    L.mx[i][2] = c.z;
-    L.wx[i][0] = d.x;
-    L.wx[i][1] = d.y;
-    L.wx[i][2] = d.z;
-    L.clsize[i] = 1;
-    L.inlist[i] = 1;
-    mem[(size_t)i * N] = i;
-  }
-  __syncthreads();
   // ---- sigmas: getAverageNNDistances (:97-123) ----
   float k2DSigma = P.sigma2d, k3DSigma = P.sigma3d;
   if (P.sigma2d == -1.f || P.sigma3d == -1.f) {
@@ -252,6 +235,35 @@ __device__ void linkage_body(LkLds& L, const mh_corr* __restrict__ corr, const f
     Dm[(size_t)i * N + j] = val;
     Dm[(size_t)j * N + i] = val;
   }
+}
+
+__device__ void linkage_body(LkLds& L, const mh_corr* __restrict__ corr, const float4* __restrict__ depth4, int n,
+                             const DepthImage& D, const LinkageParams& P, float* __restrict__ A,
+                             float* Dm, int32_t* __restrict__ mem, int32_t* __restrict__ members_out,
+                             int32_t member_base, int32_t* __restrict__ cl_start_out, int32_t* __restrict__ ncl_out,
+                             int32_t* __restrict__ label_out) {
+  const int tid = threadIdx.x;
+  const int N = n;
+  for (int i = tid; i < N; i += LK_THREADS) {
+    if (!P.given_matrix) {
+      const mh_corr c = corr[i];
+      const float4 d = depth4[i];
+      L.uv[i][0] = c.u;
+      L.uv[i][1] = c.v;
+      L.mx[i][0] = c.x;
+      L.mx[i][1] = c.y;
+      L.mx[i][2] = c.z;
+      L.wx[i][0] = d.x;
+      L.wx[i][1] = d.y;
+      L.wx[i][2] = d.z;
+    }
+    L.clsize[i] = 1;
+    L.inlist[i] = 1;
+    mem[(size_t)i * N] = i;
+  }
+  __syncthreads();
+  // (P.given_matrix, mh_linkage_debug_agglomerate: Dm holds the similarity matrix already)
+  if (!P.given_matrix) linkage_matrix(L, N, D, P, A, Dm);
   __threadfence_block();
   __syncthreads();
   if (N <= LK_DLDS) {   // the agglomeration re-reads the matrix once per merge: keep it in LDS when it fits
@@ -350,10 +362,13 @@ __device__ void linkage_body(LkLds& L, const mh_corr* __restrict__ corr, const f
           // exact, no arithmetic.  A cluster i that is EMPTY (absorbed earlier) gets the reference's empty-loop value.
           // (`second` is empty by the time the reference's loop runs; a merge may also have absorbed a cluster that was
           // empty already -- the stale list entry of the scan, S2 = 0 -- and then changes nothing)
+          // The reference's loops compare with `<` / `>` from 1e20 / -1: a NaN similarity never becomes the minimum /
+          // maximum (fminf / fmaxf skip one NaN the same way), and over nothing but NaN the start value stays.
           const bool empty = L.clsize[i] == 0 || i == second;
-          if (empty) nv[u] = P.linkage_type == 0 ? 1e20f : -1.f;
-          else if (S2 == 0) nv[u] = da;
-          else nv[u] = P.linkage_type == 0 ? fminf(da, db) : fmaxf(da, db);
+          const float start = P.linkage_type == 0 ? 1e20f : -1.f;
+          float v = start;
+          if (!empty) v = S2 == 0 ? da : (P.linkage_type == 0 ? fminf(da, db) : fmaxf(da, db));
+          nv[u] = v != v ? start : v;
         }
       }
     }

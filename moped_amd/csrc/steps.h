@@ -167,6 +167,7 @@ struct LinkageParams {         // the constructor arguments used (config.hpp:45)
   int use3d_filter = 2;        // 0 none, 1 add, 2 multiply the model/world distance-consistency kernel
   float sigma2d = -1.f, sigma3d = -1.f;   // -1: average nearest-neighbour distance
   int linkage_type = 1;        // 0 minimum, 1 average (config.hpp:45), 2 maximum linkage (CLUSTER_LINKAGE_CPU.hpp:506-526)
+  int given_matrix = 0;        // internal (mh_linkage_debug_agglomerate): the similarity matrix is in the problem's scratch region already
 };
 // Floats of scratch the models kernel needs for match lists of the given sizes: 3 n^2 each.
 // depth4: per match (wx, wy, wz, weight) aligned with corr.  Outputs as launch_meanshift_models.

@@ -88,10 +88,11 @@ void bresenham(std::vector<std::pair<int, int> >& coords, int px, int py, int qx
 
 }  // namespace
 
-extern "C" int orc_cluster_linkage(const float* uv, const float* model_xyz, const float* world_xyz, int n,
-                                   const float* depth_img, int w, int h, const float* fill_img, float cutoff,
-                                   int min_pts, int use3d_filter, int linkage_type, float sigma2d, float sigma3d,
-                                   int32_t* members, int32_t* cluster_off, float* K_out) {
+extern "C" int orc_cluster_linkage_matrices(const float* uv, const float* model_xyz, const float* world_xyz, int n,
+                                            const float* depth_img, int w, int h, const float* fill_img, float cutoff,
+                                            int min_pts, int use3d_filter, int linkage_type, float sigma2d,
+                                            float sigma3d, int32_t* members, int32_t* cluster_off, float* K_out,
+                                            float* A_out) {
   cluster_off[0] = 0;
   if (n <= 0) return 0;
   const DepthMaps D = {depth_img, fill_img, w, h};
@@ -173,6 +174,12 @@ extern "C" int orc_cluster_linkage(const float* uv, const float* model_xyz, cons
       if (M[e] > maxValue) maxValue = M[e];
     for (size_t e = 0; e < NN; ++e) M[e] = M[e] / maxValue;
   };
+  // A_out: K3D as it stands before its LAST normalisation (what the device keeps in its A matrix after pass 2)
+  auto keep_A = [&]() {
+    if (A_out)
+      for (size_t e = 0; e < NN; ++e) A_out[e] = K3D[e];
+  };
+  if (!use3d_filter) keep_A();
   normalize(K3D);
   // ---- get3DFilterK (:151-173), getSum / getProduct (:683-692) ----
   if (use3d_filter) {
@@ -192,6 +199,7 @@ extern "C" int orc_cluster_linkage(const float* uv, const float* model_xyz, cons
           e = (use3d_filter == 1) ? e + val : e * val;
         }
       }
+    keep_A();
     normalize(K3D);
   }
   // ---- adaptiveWeightSum(matches, distanceMap, K2D, K3D, 0.5, 25) (:325-366) ----
@@ -217,7 +225,18 @@ extern "C" int orc_cluster_linkage(const float* uv, const float* model_xyz, cons
   }
   if (K_out)
     for (size_t e = 0; e < NN; ++e) K_out[e] = K[e];
-  // ---- hierarchicalCluster (:416-540) ----
+  return orc_linkage_agglomerate(K.data(), N, cutoff, min_pts, linkage_type, members, cluster_off);
+}
+
+// hierarchicalCluster (:416-540) over a given similarity matrix K [n][n] (symmetric; the loop reads it as the reference
+// fills `distances`: both halves from K[j][i], j >= i).  One body for orc_cluster_linkage and for tests that pin the
+// merge loop on its own (tests/linkage_ref.py is the second witness).
+extern "C" int orc_linkage_agglomerate(const float* K, int n, float cutoff, int min_pts, int linkage_type,
+                                       int32_t* members, int32_t* cluster_off) {
+  cluster_off[0] = 0;
+  if (n <= 0) return 0;
+  const int N = n;
+  const size_t NN = (size_t)N * N;
   std::vector<std::list<int> > clusters(N);
   std::vector<float> distances(NN);
   std::list<int> validIndices;
@@ -281,4 +300,12 @@ extern "C" int orc_cluster_linkage(const float* uv, const float* model_xyz, cons
     }
   }
   return ncl;
+}
+
+extern "C" int orc_cluster_linkage(const float* uv, const float* model_xyz, const float* world_xyz, int n,
+                                   const float* depth_img, int w, int h, const float* fill_img, float cutoff,
+                                   int min_pts, int use3d_filter, int linkage_type, float sigma2d, float sigma3d,
+                                   int32_t* members, int32_t* cluster_off, float* K_out) {
+  return orc_cluster_linkage_matrices(uv, model_xyz, world_xyz, n, depth_img, w, h, fill_img, cutoff, min_pts,
+                                      use3d_filter, linkage_type, sigma2d, sigma3d, members, cluster_off, K_out, nullptr);
 }

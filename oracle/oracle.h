@@ -77,6 +77,16 @@ int orc_cluster_linkage(const float* uv, const float* model_xyz, const float* wo
                         const float* depth_img, int w, int h, const float* fill_img, float cutoff,
                         int min_pts, int use3d_filter, int linkage_type, float sigma2d, float sigma3d,
                         int32_t* members, int32_t* cluster_off, float* K_out);
+/* The same with one more output: A_out (optional, n*n) = the 3-D side (K3D + discontinuity, x / + K3F) before its
+ * last normalisation. */
+int orc_cluster_linkage_matrices(const float* uv, const float* model_xyz, const float* world_xyz, int n,
+                                 const float* depth_img, int w, int h, const float* fill_img, float cutoff,
+                                 int min_pts, int use3d_filter, int linkage_type, float sigma2d, float sigma3d,
+                                 int32_t* members, int32_t* cluster_off, float* K_out, float* A_out);
+/* The agglomeration of orc_cluster_linkage (hierarchicalCluster, :416-540) over a given symmetric similarity
+ * matrix K [n][n]; members / cluster_off / return value as above. */
+int orc_linkage_agglomerate(const float* K, int n, float cutoff, int min_pts, int linkage_type, int32_t* members,
+                            int32_t* cluster_off);
 
 /* A12 project() (include/moped.hpp:330-354) for n points: pose/cam are
  * (qx,qy,qz,qw,tx,ty,tz), K = (fx,fy,cx,cy); z < 0.001 -> (FLT_MAX,FLT_MAX). */

@@ -1,9 +1,11 @@
 """Oracle restatement of moped3d's CLUSTER_LINKAGE_CPU (oracle/linkage_oracle.cpp): hand-worked
-cases.  PARITY UNPINNED against a reference build (CLUSTER_LINKAGE_CPU.hpp works on IplImage); the GPU
-kernel is compared with this oracle in tests/test_gpu_linkage.py."""
+cases, and its agglomeration (orc_linkage_agglomerate) against the Python witness of tests/linkage_ref.py.  PARITY UNPINNED
+against a reference build (CLUSTER_LINKAGE_CPU.hpp works on IplImage); the GPU kernel is compared with this oracle in
+tests/test_gpu_linkage.py and, stage by stage, in tests/test_gpu_linkage_stages.py."""
 import numpy as np
 
 import orclib
+from linkage_ref import agglomerate, flat_map, lattice, similarity_f64, world_of
 
 K = np.array([800, 800, 320, 240], np.float32)
 
@@ -96,45 +98,6 @@ def test_degenerate_inputs():
     assert orclib.cluster_linkage(same, _world(img, same), _world(img, same), img, None) == []
 
 
-def _agglomerate(Km, cutoff, min_pts, ltype):
-    """CLUSTER_LINKAGE_CPU's merge loop (:437-540) written down a second time, in Python, over a similarity matrix --
-    including what its list handling does: the absorbed cluster's index stays in the list of live indices until the NEXT
-    scan reaches it (:456-459: erased there, and the element behind it is skipped as a first index of that scan), so
-    earlier first indices still pair with it, through the matrix row the last update gave it.  Linkage of two clusters
-    = minimum (0) / maximum (2) of K over their pairs, recomputed from K (minimumLinkage :404-413: 1e20 over an empty
-    cluster, maximumLinkage :390-399: -1)."""
-    n = len(Km)
-    cl = [[i] for i in range(n)]
-    live = list(range(n))
-    D = Km.astype(np.float32).copy()
-    def link(A, B):
-        v = [Km[b, a] for a in A for b in B]
-        return np.float32((min(v) if ltype == 0 else max(v)) if v else (1e20 if ltype == 0 else -1.0))
-    remove = -1
-    while True:
-        best, pair = np.float32(-1), (0, 0)
-        x = 0
-        while x < len(live):
-            i = live[x]
-            if i == remove:
-                del live[x]          # erase; the loop's increment then skips the element that moved into this place
-                x += 1
-                continue
-            for j in live[x + 1:]:
-                if D[i, j] > best:
-                    best, pair = D[i, j], (i, j)
-            x += 1
-        if best < cutoff:
-            break
-        i, j = pair
-        cl[i] += cl[j][::-1]
-        cl[j] = []
-        remove = j
-        for k in range(n):
-            D[i, k] = D[k, i] = link(cl[k], cl[i])
-    return [c for c in cl if len(c) > min_pts]
-
-
 def test_minimum_and_maximum_linkage_against_an_independent_agglomeration():
     """LinkageType 0 / 2 (CLUSTER_LINKAGE_CPU.hpp:506-507, :525; the shipped configuration uses 1): the oracle's clusters,
     members in its order, equal a from-scratch agglomeration over the oracle's own similarity matrix."""
@@ -149,7 +112,7 @@ def test_minimum_and_maximum_linkage_against_an_independent_agglomeration():
     for ltype in (0, 2):
         for cutoff in (0.05, 0.2, 0.45, 0.7):
             got, Km = orclib.cluster_linkage(uv, world, world, img, fill, cutoff=cutoff, min_pts=1, linkage_type=ltype, want_k=True)
-            want = _agglomerate(Km, np.float32(cutoff), 1, ltype)
+            want, _ = agglomerate(Km, cutoff, 1, ltype)        # tests/linkage_ref.py
             assert [c.tolist() for c in got] == want, (ltype, cutoff)
             seen.add((ltype, len(want)))
     assert len({n for _, n in seen}) >= 2            # the cutoffs do produce different partitions
@@ -157,3 +120,107 @@ def test_minimum_and_maximum_linkage_against_an_independent_agglomeration():
     n0 = len(orclib.cluster_linkage(uv, world, world, img, fill, cutoff=0.45, min_pts=0, linkage_type=0))
     n2 = len(orclib.cluster_linkage(uv, world, world, img, fill, cutoff=0.45, min_pts=0, linkage_type=2))
     assert n0 >= n2
+
+
+# ---- the agglomeration on its own: orc_linkage_agglomerate against the Python witness (tests/linkage_ref.py) ----------
+
+def _lattice_matrix(n=36):
+    img = flat_map()
+    uv = lattice(n)
+    world = world_of(img, uv)
+    _, Km = orclib.cluster_linkage(uv, world, world, img, np.zeros((480, 640), np.float32), min_pts=0, want_k=True)
+    return Km
+
+
+def _same_clusters(Km, cutoff, min_pts, ltype):
+    got = orclib.linkage_agglomerate(Km, cutoff, min_pts, ltype)
+    want, stats = agglomerate(Km, cutoff, min_pts, ltype)
+    assert [c.tolist() for c in got] == want, (len(Km), cutoff, min_pts, ltype)
+    return want, stats
+
+
+def test_lattice_ties_drive_the_list_handling():
+    """6 x 6 pixel lattice on a flat map: few distinct similarities among the pairs, so every merge is decided by "first
+    maximum in scan order", and at cutoff 0.3 average and minimum linkage win about every second merge through the stale
+    row of the index absorbed just before.  The input must keep doing that; the oracle equals the witness for all three
+    types, members in order."""
+    Km = _lattice_matrix(36)
+    assert np.array_equal(Km, Km.T)
+    off = Km[np.triu_indices(36, 1)]
+    assert len(np.unique(off)) <= 40 and len(off) == 630
+    for ltype in (0, 1, 2):
+        for cutoff in (0.3, 0.45, 0.6):
+            want, stats = _same_clusters(Km, cutoff, 0, ltype)
+            if cutoff == 0.3 and ltype in (0, 1):
+                print(ltype, stats)
+                assert stats["stale"] >= 30 and stats["merges"] >= 2 * 36 - 4 and stats["skipped"] >= 20, stats
+    # one body: the whole oracle call gives what its agglomeration gives on its own matrix
+    img, uv = flat_map(), lattice(36)
+    world = world_of(img, uv)
+    whole = orclib.cluster_linkage(uv, world, world, img, None, cutoff=0.3, min_pts=2)
+    _, Km2 = orclib.cluster_linkage(uv, world, world, img, None, min_pts=0, want_k=True)
+    assert [c.tolist() for c in whole] == [c.tolist() for c in orclib.linkage_agglomerate(Km2, 0.3, 2, 1)]
+
+
+def three_valued(n, seed):
+    """Random symmetric matrix over {0.2, 0.5, 0.8}: ties everywhere, no structure."""
+    rng = np.random.default_rng([n, seed])
+    M = rng.choice(np.array([0.2, 0.5, 0.8], np.float32), (n, n))
+    M = np.triu(M) + np.triu(M, 1).T
+    return np.ascontiguousarray(M, np.float32)
+
+
+def test_agglomeration_on_random_and_degenerate_matrices():
+    for n in (2, 3, 17, 40):
+        for seed in range(3):
+            M = three_valued(n, seed)
+            for ltype in (0, 1, 2):
+                for cutoff in (0.1, 0.4, 0.7):
+                    _same_clusters(M, cutoff, 0, ltype)
+    # NaN entries (never a maximum, never a minimum) and rows entirely below the cutoff
+    rng = np.random.default_rng(7)
+    for n in (5, 17, 33):
+        M = three_valued(n, 9)
+        hole = np.triu(rng.random((n, n)) < 0.3, 1)
+        M[hole | hole.T] = np.nan
+        M[n // 2, :] = M[:, n // 2] = 0.05
+        M[0, :] = M[:, 0] = np.nan
+        for ltype in (0, 1, 2):
+            for cutoff in (0.1, 0.4):
+                want, _ = _same_clusters(M, cutoff, 0, ltype)
+                assert [n // 2] in want                         # below the cutoff: left alone
+                # all NaN: left alone too -- except under minimum linkage, where a merged cluster's minimum over nothing
+                # but NaN stays at its start value 1e20 (:404-413), the largest "similarity" of the next scan
+                assert ([0] in want) == (ltype != 0), (n, ltype, cutoff)
+    # min_pts counts strictly: a cluster of min_pts members is none, of min_pts + 1 it is one
+    M = np.full((7, 7), 0.1, np.float32)
+    M[:4, :4] = 0.9
+    M[4:, 4:] = 0.9
+    assert [len(c) for c in _same_clusters(M, 0.5, 3, 1)[0]] == [4]
+    assert [len(c) for c in _same_clusters(M, 0.5, 2, 1)[0]] == [4, 3]
+    assert _same_clusters(M, 0.5, 4, 1)[0] == []
+
+
+def test_float64_restatement_has_the_oracles_nan_mask():
+    """tests/linkage_ref.py similarity_f64 against the oracle's matrices: equal NaN masks, and values within float32
+    rounding of each other on a scene with a depth step, fill distances, identical pixels and identical model points."""
+    img = flat_map()
+    img[:, 320:, :3] *= 1.5
+    img[200:210, 100:110, 2] = np.nan
+    rng = np.random.default_rng(4)
+    uv = rng.uniform([0, 0], [639, 479], (40, 2)).astype(np.float32)
+    uv[5] = uv[4]                                               # identical pixels: K3F is 0 / 0 there
+    uv[7] = (104.5, 204.5)                                      # a NaN depth
+    fill = (rng.uniform(0, 30, (480, 640)) * (rng.random((480, 640)) < 0.5)).astype(np.float32)
+    world = world_of(img, uv)
+    mx = (world + rng.normal(0, 0.01, world.shape)).astype(np.float32)
+    mx[9] = mx[8]                                               # identical model points: K3F divides by zero
+    for use3d in (0, 1, 2):
+        for sig in ((-1.0, -1.0), (15.0, 0.05)):
+            _, Ko, Ao = orclib.cluster_linkage(uv, mx, world, img, fill, use3d_filter=use3d, sigma2d=sig[0], sigma3d=sig[1],
+                                               want_k=True, want_a=True)
+            A64, K64 = similarity_f64(uv, mx, world, img, fill, use3d, *sig)
+            assert np.array_equal(np.isnan(Ko), np.isnan(K64)) and np.array_equal(np.isnan(Ao), np.isnan(A64)), (use3d, sig)
+            assert np.isnan(Ko).any() and not np.isnan(Ko).all()
+            ok = ~np.isnan(Ko)
+            assert np.abs(Ko[ok] - K64[ok]).max() < 1e-4, (use3d, sig, np.abs(Ko[ok] - K64[ok]).max())
