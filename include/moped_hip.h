@@ -597,12 +597,36 @@ int mh_frame_set_depth_image_host(mh_ctx* ctx, const float* depth_xyzn_host, con
  * reduction and a 4-byte read back); with a factor of 1 the reference never hands the filled depths back
  * (:336-338) and neither does this: only the distance map is written.  *scale_used (optional) = the factor.
  * Bit-identical to the reference's arithmetic (tests/test_gpu_depthfill.py against the oracle's restatement).
- * Limits: the downscaled map holds at most 8192 pixels (640 x 480 from factor 8 on) -> MH_ERR_CAPACITY.
+ * Limits (the default mode; mh_depth_fill_set_mode below lifts them): the downscaled map holds at most 8192 pixels
+ * (640 x 480 from factor 8 on) -> MH_ERR_CAPACITY.
  * Asynchronous; mh_depth_fill_status synchronises the stream and reports MH_ERR_CAPACITY if the fill's queue
  * outgrew its 16384-entry ring in a call since the last status (no map of a real sensor comes near it). */
 int mh_depth_fill(mh_ctx* ctx, float* depth_xyzn_dev, int width, int height, int scale_factor, int bilinear,
                   const float K[4], float* fill_distance_dev, int* scale_used);
 int mh_depth_fill_status(mh_ctx* ctx);
+/* How the fill runs (opt-in, like mh_match_set_mode; the default is MH_DEPTH_FILL_REPLAY: everything above and below as
+ * it is written, limits included).  MH_DEPTH_FILL_LEVELS runs the same FIFO queue generation by generation: the seeds
+ * are generation 0, what a generation-k element pushes is generation k + 1, and within a generation the updates of
+ * different pixels never interact -- all 1024 threads of the map's workgroup work on the generation, one target pixel
+ * each, and lay out the next one in exactly the order the serial loop would have pushed it.  The results are byte for
+ * byte those of the replay wherever the replay accepts the map (tests/test_gpu_depthfill_levels.py), and mh_depth_fill,
+ * mh_depth_fill_batch, mh_depth_fill_host and everything that fills through them (mh_frame_run_kinect_host, the Kinect
+ * batch path) take any map whose downscaled size is 1 x 1 to 2^21 pixels (more: MH_ERR_CAPACITY before any launch);
+ * scale_factor = -1 in mh_depth_fill then works for every share of holes (in the batch call it stays MH_ERR_ARG).
+ * State and generation lists live in the context's scratch, 128 bytes per downscaled pixel and frame: a fill of a
+ * larger map or of more frames than any LEVELS fill before it on the context reallocates the scratch at the start of
+ * the call, before its launches (that synchronises the context's stream; the sticky overflow word is carried over).
+ * Capacity: a generation may hold up to 4 * dw * dh elements (no bound on a generation's size is known; sensor-like
+ * maps stay under 1.0 * dw * dh) and a fill up to dw * dh generations; beyond either the fill stops, nothing is written
+ * out of bounds, the sticky overflow word is set (mh_depth_fill_status -> MH_ERR_CAPACITY: the maps of that call are
+ * incomplete) and the context stays usable.  One workgroup per map, in either mode.
+ * mh_depth_fill_stats: of frame `frame` of the context's last fill, which must have been a LEVELS one (else
+ * MH_ERR_ARG): {non-empty generations processed (seeds included), largest generation, elements over all generations
+ * (saturating), overflowed}; synchronises the context. */
+enum { MH_DEPTH_FILL_REPLAY = 0, MH_DEPTH_FILL_LEVELS = 1 };
+int mh_depth_fill_set_mode(mh_ctx* ctx, int mode);
+int mh_depth_fill_get_mode(mh_ctx* ctx, int* mode);   /* (a user of a shared context saves the mode, sets its own, puts it back) */
+int mh_depth_fill_stats(mh_ctx* ctx, int frame, int32_t out[4]);
 /* DEPTHFILL of n_frames <= MH_MAX_BATCH maps of one size, each in place with its own distance map, in ONE launch per
  * stage: what moped3d's pipeline (moped3d/libmoped/src/config.hpp:39, DEPTH_FILL_EXACT_CPU.hpp:268-349) does to every
  * frame's map, for the frames of a batch at once -- the FIFO wavefront of a map occupies ONE workgroup for as long as its

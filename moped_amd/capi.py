@@ -64,6 +64,7 @@ OBJECT_DTYPE = np.dtype([("model", "<i4"), ("pose", "<f4", (7,)), ("score", "<f4
 STEP_OBJECT_DTYPE = np.dtype([("model", "<i4"), ("pose", "<f4", (7,))])   # mh_step_object
 DEPTH_DTYPE = np.dtype([("wx", "<f4"), ("wy", "<f4"), ("wz", "<f4"), ("w", "<f4")])
 DEPTH_BACKPROJECTION, DEPTH_REPROJECTION = 1, 2
+DEPTH_FILL_REPLAY, DEPTH_FILL_LEVELS = 0, 1   # mh_depth_fill_set_mode
 DEPTH_INFO_DTYPE = np.dtype([("depth_valid", "<i4"), ("coord3d", "<f4", (3,)), ("depth", "<f4"),
                              ("fill_distance", "<f4")])   # mh_depth_info
 POSE_OUT_DTYPE = np.dtype([("pose", "<f4", (7,)), ("cluster", "<i4"), ("n_inliers", "<i4"), ("err", "<f4")])
@@ -118,7 +119,7 @@ EXPORTS = [
     "mh_filter", "mh_frame_default_params", "mh_frame_enqueue", "mh_frame_set_depth_image", "mh_frame_enqueue_match_local",
     "mh_frame_enqueue_rest", "mh_frame_fetch", "mh_frame_result_dev", "mh_enable_timing", "mh_timing",
     "mh_frame_set_cluster_linkage", "mh_cluster_linkage", "mh_frame_set_depth_image_host",
-    "mh_depth_fill", "mh_depth_fill_status", "mh_depth_fill_host", "mh_depth_fill_batch",
+    "mh_depth_fill", "mh_depth_fill_status", "mh_depth_fill_host", "mh_depth_fill_batch", "mh_depth_fill_set_mode", "mh_depth_fill_get_mode", "mh_depth_fill_stats",
     "mh_frame_enqueue_rest_batch", "mh_frame_enqueue_rest_frames", "mh_frame_fetch_slot", "mh_frame_result_copy_slots_dev",
     "mh_frame_set_depth_rules", "mh_frame_fetch_matches", "mh_frame_enqueue_rest_strided", "mh_frame_result_copy_dev",
     "mh_sift_extract", "mh_sift_extract_dev", "mh_frame_enqueue_image", "mh_frame_enqueue_image_batch", "mh_frame_features_dev", "mh_frame_keypoints",
@@ -229,6 +230,9 @@ def load():
     L.mh_frame_set_depth_image_host.argtypes = [vp, vp, vp, i32, i32, i32, f32, f32]
     L.mh_depth_fill.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.mh_depth_fill_status.argtypes = [vp]
+    L.mh_depth_fill_set_mode.argtypes = [vp, i32]
+    L.mh_depth_fill_get_mode.argtypes = [vp, vp]
+    L.mh_depth_fill_stats.argtypes = [vp, i32, vp]
     # (EXPORTS lists it and build() insists on it; absent only in the parent's build that scripts/ab_lib.sh names through
     #  MH_LIB_PATH to measure it against this one)
     if hasattr(L, "mh_depth_fill_batch"):
@@ -950,6 +954,23 @@ class Context:
         f = (C.c_void_p * max(n, 1))(*fill_ptrs)
         self._ck(self.L.mh_depth_fill_batch(self.h, d, f, n, width, height, int(scale), 1 if bilinear else 0, _ptr(k)),
                  "mh_depth_fill_batch")
+
+    def depth_fill_set_mode(self, mode: int):
+        """DEPTH_FILL_REPLAY (0, the default: one wavefront replays the queue; downscaled maps of up to 8192 pixels) or
+        DEPTH_FILL_LEVELS (1: the queue generation by generation, the same bytes, downscaled maps of up to 2^21 pixels)."""
+        self._ck(self.L.mh_depth_fill_set_mode(self.h, int(mode)), "mh_depth_fill_set_mode")
+
+    def depth_fill_get_mode(self) -> int:
+        mode = C.c_int(0)
+        self._ck(self.L.mh_depth_fill_get_mode(self.h, C.byref(mode)), "mh_depth_fill_get_mode")
+        return mode.value
+
+    def depth_fill_stats(self, frame=0):
+        """Of frame `frame` of the last fill (a DEPTH_FILL_LEVELS one): -> (non-empty generations, largest generation,
+        elements over all generations, overflowed).  Synchronises the context."""
+        out = np.zeros(4, np.int32)
+        self._ck(self.L.mh_depth_fill_stats(self.h, int(frame), _ptr(out)), "mh_depth_fill_stats")
+        return tuple(int(v) for v in out)
 
     def depth_fill_status(self):
         self._ck(self.L.mh_depth_fill_status(self.h), "mh_depth_fill_status")

@@ -275,6 +275,8 @@ struct mh_ctx {
   mh::DevBuf<uint8_t> own_gray;   // device copy of a host gray image (mh_frame_run_kinect_host)
   mh::DevBuf<float> lk_scratch;
   mh::DevBuf<unsigned char> df_buf;   // mh_depth_fill[_batch]: [status words | per frame: downscaled depths, downscaled distances]
+  int df_mode = 0;                    // mh_depth_fill_set_mode (MH_DEPTH_FILL_REPLAY); LEVELS: [status words | stats | per frame: depthfill.hip]
+  int df_lv_frames = 0;               // frames of the last fill if it was a LEVELS one (mh_depth_fill_stats), else 0
   size_t lk_scratch_limit = (size_t)4 << 30;   // bytes; mh_set_linkage_scratch_limit
 
   // moped3d FILTER_PROJECTION_DEPTH instead of FILTER_PROJECTION (mh_filter_depth_set_points, mh_frame_set_filter_depth)

@@ -13,6 +13,12 @@
 // prefix count.  Everything the loop touches lives in LDS (best distance, source, validity, a circular queue), one
 // pop is ~3 dependent LDS round trips.  The rest -- downscale, seeds in raster order, upsampling (nearest neighbour
 // with the reference's late row advance, :80-82, or bilinear, :93-168), normalisation -- is parallel.
+//
+// That is MH_DEPTH_FILL_REPLAY, the default mode (mh_depth_fill_set_mode): downscaled maps of up to 8192 pixels.
+// MH_DEPTH_FILL_LEVELS, further down, runs the same queue generation by generation with all 1024 threads, its state in
+// the context's scratch: the same bytes, downscaled maps of up to 2^21 pixels.
+#include <climits>
+
 #include "context.h"
 
 namespace mh {
@@ -229,11 +235,327 @@ __global__ void depth_count_valid_kernel(const float4* __restrict__ depth, int n
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(count, __popcll(m));
 }
 
-// The context's scratch for `frames` frames: [overflow word, valid count | the frames' downscaled maps].  Growing a held
-// block synchronises the stream (DevBuf::ensure) and would lose the sticky overflow word: it is carried over.
-int df_scratch(mh_ctx* ctx, int frames) {
+// ---- MH_DEPTH_FILL_LEVELS: the same queue, generation by generation ---------------------------------------------------
+// The queue is FIFO: seeds are generation 0, what a generation-k element pushes is generation k + 1, and every element of
+// generation k is popped before any of k + 1.  Within a generation best[t] / src[t] are touched only by the elements
+// that target t, so ONE thread per target pixel t goes through t's candidates -- the elements on the (up to) nine pixels
+// of its neighbourhood -- in the order of their queue positions i and finds the records (strictly below best[t] and below
+// every earlier candidate): those are t's pushes.  The pushes of element i through neighbour slot j land at
+// exscan_i(popcount(mask[i])) + popcount(mask[i] & ((1 << j) - 1)), the order of the serial loop, so the next generation
+// is the same queue as the replay's and the results are its results bit for bit.
+//
+// Per frame, in the context's scratch (n = dw * dh, cap = DF_LV_CAP * n elements per generation):
+//   zfill, best [n]              downscaled depths; the distance map (fdist of the upsampling)
+//   src, tstamp [n]              the source of a filled hole; the last generation the pixel was listed as a target for
+//   sstamp, sstart, scnt [2][n]  per parity of the generation: the pixel carries elements of generation sstamp, they are
+//                                entries [sstart, sstart + scnt) of that parity's gpos / gsrc, ascending in position
+//   act [2][n]                   the target pixels of the generation (any order)
+//   gpos, gsrc [2][cap]          the elements, grouped by pixel: queue position within the generation, source
+//   mb [cap]                     by queue position: the 9-bit mask of record slots, after the scan | (exclusive sum << 9)
+// A generation of more than cap elements, or more than n generations, sets the sticky overflow word and ends the fill;
+// nothing is written past cap.
+constexpr int DF_LV_CAP = 4;                    // elements per generation, in downscaled pixels
+constexpr long DF_LV_MAX_PIX = 1l << 21;        // (cap = 2^23 positions: position << 9 | mask is one word)
+constexpr size_t DF_LV_HEAD = 64 + 16 * (size_t)MH_MAX_BATCH;   // [overflow word, valid count | int32[4] of stats per frame]
+constexpr size_t df_lv_frame_words(size_t n) { return (12 + 5 * (size_t)DF_LV_CAP) * n; }
+
+struct LvFrame {
+  float *zfill, *best;
+  int *src, *tstamp, *sstamp, *sstart, *scnt, *act, *gpos, *gsrc;
+  unsigned* mb;
+  int n, cap;
+};
+__device__ __forceinline__ LvFrame lv_frame(float* base, int n) {
+  LvFrame F;
+  F.n = n;
+  F.cap = DF_LV_CAP * n;
+  F.zfill = base;
+  F.best = base + n;
+  int* w = reinterpret_cast<int*>(base) + 2 * (size_t)n;
+  F.src = w;
+  F.tstamp = w + (size_t)n;
+  F.sstamp = w + 2 * (size_t)n;
+  F.sstart = w + 4 * (size_t)n;
+  F.scnt = w + 6 * (size_t)n;
+  F.act = w + 8 * (size_t)n;
+  F.gpos = w + 10 * (size_t)n;
+  F.gsrc = F.gpos + 2 * (size_t)F.cap;
+  F.mb = reinterpret_cast<unsigned*>(F.gsrc + 2 * (size_t)F.cap);
+  return F;
+}
+
+struct LvLds {
+  int wsum[DF_THREADS / 64];
+  int na_next, gtail;
+};
+
+// Exclusive sum of v over the workgroup's threads, `total` = the sum (two barriers).
+__device__ __forceinline__ int lv_block_exscan(int v, LvLds& L, int& total) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int inc = v;
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(inc, o);
+    if (lane >= o) inc += t;
+  }
+  __syncthreads();   // (the last call's readers are done with wsum)
+  if (lane == 63) L.wsum[wv] = inc;
+  __syncthreads();
+  int off = 0, tot = 0;
+  for (int k = 0; k < DF_THREADS / 64; ++k) {
+    const int s = L.wsum[k];
+    if (k < wv) off += s;
+    tot += s;
+  }
+  total = tot;
+  return off + inc - v;
+}
+
+// mb[0, m): mask -> mask | (exclusive sum of popcount(mask) << 9); -> the sum.  Every thread a contiguous chunk.
+__device__ __forceinline__ int lv_scan_masks(unsigned* mb, int m, LvLds& L) {
+  const int per = (m + DF_THREADS - 1) / DF_THREADS;
+  const int lo = min((int)threadIdx.x * per, m), hi = min(lo + per, m);
+  int sum = 0;
+  for (int i = lo; i < hi; ++i) sum += __popc(mb[i] & 0x1ffu);
+  int total;
+  unsigned run = (unsigned)lv_block_exscan(sum, L, total);
+  for (int i = lo; i < hi; ++i) {
+    const unsigned m9 = mb[i] & 0x1ffu;
+    mb[i] = (run << 9) | m9;
+    run += __popc(m9);
+  }
+  return total;
+}
+
+// Pixel u becomes a target of generation g (once: the first to raise its stamp lists it).  At most n distinct pixels.
+__device__ __forceinline__ void lv_mark_targets(const LvFrame& F, int par, int g, int t, int dw, int dh, LvLds& L) {
+  const int ty = t / dw, tx = t - ty * dw;
+  for (int dy = -1; dy <= 1; ++dy)
+    for (int dx = -1; dx <= 1; ++dx) {
+      const int ux = tx + dx, uy = ty + dy;
+      if (ux < 0 || ux >= dw || uy < 0 || uy >= dh) continue;
+      const int u = uy * dw + ux;
+      if (F.zfill[u] >= 0.f) continue;   // valid pixels are never targets (:220)
+      if (atomicMax(&F.tstamp[u], g) < g) {
+        const int a = atomicAdd(&L.na_next, 1);
+        if (a < F.n) F.act[(size_t)par * F.n + a] = u;
+      }
+    }
+}
+
+// The candidates of target t in generation k (parity par), in the order of their positions: a nine-way merge of the
+// neighbourhood's element lists.  WRITE = false: marks the records in mb, -> their number.  WRITE = true (after the scan):
+// writes them as t's elements of generation k + 1 from entry `out` on, and t's new best / src.
+template <bool WRITE>
+__device__ __forceinline__ int lv_walk(const LvFrame& F, int par, int k, int t, int dw, int dh, float dil, int out) {
+  const int ty = t / dw, tx = t - ty * dw;
+  const int* gpos = F.gpos + (size_t)par * F.cap;
+  const int* gsrc = F.gsrc + (size_t)par * F.cap;
+  int beg[9], end[9], hp[9];
+  int todo = 0;
+#pragma unroll
+  for (int j = 0; j < 9; ++j) {
+    const int qx = tx - (j % 3 - 1), qy = ty - (j / 3 - 1);   // q + (dx, dy) = t through slot j = 3 (dy + 1) + (dx + 1)
+    beg[j] = end[j] = 0;
+    hp[j] = INT_MAX;
+    if (qx >= 0 && qx < dw && qy >= 0 && qy < dh) {
+      const size_t q = (size_t)par * F.n + (qy * dw + qx);
+      if (F.sstamp[q] == k) {
+        beg[j] = F.sstart[q];
+        end[j] = min(beg[j] + F.scnt[q], F.cap);
+        if (beg[j] < end[j]) hp[j] = gpos[beg[j]];
+        todo += max(end[j] - beg[j], 0);
+      }
+    }
+  }
+  float cb = F.best[t];
+  int cs = -1, rc = 0;
+  for (int it = 0; it < todo; ++it) {
+    int jm = 0, pm = hp[0], bm = beg[0];
+#pragma unroll
+    for (int j = 1; j < 9; ++j)
+      if (hp[j] < pm) {
+        pm = hp[j];
+        jm = j;
+        bm = beg[j];
+      }
+    if (pm == INT_MAX) break;
+    const int s = gsrc[bm];
+    const int sy = s / dw, sx = s - sy * dw;
+    const long long ddx = tx - sx, ddy = ty - sy;
+    const float d = __fmul_rn(sqrtf((float)(ddx * ddx + ddy * ddy)), dil);   // :224
+    if (d < cb) {
+      cb = d;
+      cs = s;
+      if (!WRITE) {
+        if ((unsigned)pm < (unsigned)F.cap) atomicOr(&F.mb[pm], 1u << jm);
+      } else {
+        const unsigned w = (unsigned)pm < (unsigned)F.cap ? F.mb[pm] : 0u;
+        const int e = out + rc;
+        if ((unsigned)e < (unsigned)F.cap) {
+          F.gpos[(size_t)(par ^ 1) * F.cap + e] = (int)(w >> 9) + __popc(w & ((1u << jm) - 1u));
+          F.gsrc[(size_t)(par ^ 1) * F.cap + e] = s;
+        }
+      }
+      ++rc;
+    }
+#pragma unroll
+    for (int j = 0; j < 9; ++j)
+      if (j == jm) {
+        ++beg[j];
+        hp[j] = beg[j] < end[j] ? gpos[beg[j]] : INT_MAX;
+      }
+  }
+  if (WRITE && cs >= 0) {
+    F.best[t] = cb;
+    F.src[t] = cs;
+  }
+  return rc;
+}
+
+// One workgroup: the map of frame blockIdx.x.  stats[frame]: {non-empty generations, largest, elements, overflowed}.
+__global__ __launch_bounds__(DF_THREADS) void depth_fill_levels_kernel(DfMaps maps, int w, int h, int scale, int dw, int dh,
+                                                                       float* scratch, size_t frame_words, int32_t* err,
+                                                                       int32_t* stats) {
+  __shared__ LvLds L;
+  const int tid = threadIdx.x;
+  const int n = dw * dh;
+  const float4* depth = maps.depth[blockIdx.x];
+  const LvFrame F = lv_frame(scratch + blockIdx.x * frame_words, n);
+  for (int p = tid; p < n; p += DF_THREADS) {
+    const int y = p / dw, x = p - y * dw;
+    const float z = depth[(size_t)(y * scale) * w + x * scale].z;
+    F.zfill[p] = z;
+    F.best[p] = z >= 0.f ? 0.f : 1e30f;
+    F.src[p] = p;
+    F.tstamp[p] = -1;
+    F.sstamp[p] = -1;
+    F.sstamp[n + p] = -1;
+  }
+  if (tid == 0) {
+    L.na_next = 0;
+    L.gtail = 0;
+  }
+  __syncthreads();
+  // generation 0: the seeds in raster order (:194-198), valid pixels with a hole among their in-image neighbours
+  for (int p = tid; p < n; p += DF_THREADS) {
+    bool seed = false;
+    if (F.zfill[p] >= 0.f) {
+      const int y = p / dw, x = p - y * dw;
+      for (int dy = -1; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx) {
+          const int xx = x + dx, yy = y + dy;
+          if (xx >= 0 && xx < dw && yy >= 0 && yy < dh && !(F.zfill[yy * dw + xx] >= 0.f)) seed = true;
+        }
+    }
+    F.mb[p] = seed ? 1u : 0u;
+  }
+  __syncthreads();
+  int n_k = lv_scan_masks(F.mb, n, L);
+  __syncthreads();
+  for (int p = tid; p < n; p += DF_THREADS) {
+    const unsigned m = F.mb[p];
+    if (m & 1u) {
+      const int pos = (int)(m >> 9);
+      F.gpos[pos] = pos;
+      F.gsrc[pos] = p;
+      F.sstart[p] = pos;
+      F.scnt[p] = 1;
+      F.sstamp[p] = 0;
+      lv_mark_targets(F, 0, 0, p, dw, dh, L);
+    }
+  }
+  __syncthreads();
+  for (int p = tid; p < n; p += DF_THREADS) F.mb[p] = 0u;
+  int na = min(L.na_next, n);
+  __syncthreads();
+  if (tid == 0) L.na_next = 0;
+  __syncthreads();
+
+  const float dil = (float)scale;
+  int gens = 0, largest = 0, overflow = 0;
+  long long elements = 0;
+  for (int k = 0; n_k > 0; ++k) {
+    if (k >= n) {   // (no map should come here: every generation improves a pixel)
+      overflow = 1;
+      break;
+    }
+    ++gens;
+    largest = max(largest, n_k);
+    elements += n_k;
+    const int par = k & 1;
+    const int* act = F.act + (size_t)par * n;
+    // A: records of every target, marked by queue position and slot; room for them as the target's next elements
+    for (int a = tid; a < na; a += DF_THREADS) {
+      const int t = act[a];
+      const int rc = lv_walk<false>(F, par, k, t, dw, dh, dil, 0);
+      if (rc) {
+        const size_t o = (size_t)(par ^ 1) * n + t;
+        F.sstart[o] = atomicAdd(&L.gtail, rc);
+        F.scnt[o] = rc;
+        F.sstamp[o] = k + 1;
+      }
+    }
+    __syncthreads();
+    // B: positions in generation k + 1
+    const int n_next = lv_scan_masks(F.mb, n_k, L);
+    if (n_next > F.cap) {
+      overflow = 1;
+      break;
+    }
+    __syncthreads();
+    // C: the records again, now with their positions; the targets of generation k + 1 are their neighbours
+    for (int a = tid; a < na; a += DF_THREADS) {
+      const int t = act[a];
+      const size_t o = (size_t)(par ^ 1) * n + t;
+      if (F.sstamp[o] != k + 1) continue;
+      lv_walk<true>(F, par, k, t, dw, dh, dil, F.sstart[o]);
+      lv_mark_targets(F, par ^ 1, k + 1, t, dw, dh, L);
+    }
+    __syncthreads();
+    for (int i = tid; i < max(n_k, n_next); i += DF_THREADS) F.mb[i] = 0u;
+    na = min(L.na_next, n);
+    n_k = n_next;
+    __syncthreads();
+    if (tid == 0) {
+      L.na_next = 0;
+      L.gtail = 0;
+    }
+    __syncthreads();
+  }
+  __syncthreads();
+  if (tid == 0) {
+    if (overflow) atomicOr(err, 1);
+    int32_t* st = stats + 4 * blockIdx.x;
+    st[0] = gens;
+    st[1] = largest;
+    st[2] = (int32_t)min(elements, (long long)INT_MAX);
+    st[3] = overflow;
+  }
+  for (int p = tid; p < n; p += DF_THREADS)
+    if (!(F.zfill[p] >= 0.f) && F.src[p] != p) F.zfill[p] = F.zfill[F.src[p]];   // (sources are valid pixels, never rewritten)
+}
+
+// Upsampling / the scale-1 copy from the LEVELS layout (blockIdx.y = frame; zfill, fdist = the frame's first 2 n words)
+__global__ void depth_fill_upscale_levels_kernel(DfMaps maps, int w, int h, int scale, int dw, int dh, int bilinear,
+                                                 const float* __restrict__ scratch, size_t frame_words, float k0, float k1,
+                                                 float k2, float k3) {
+  const float* zfill = scratch + blockIdx.y * frame_words;
+  depth_fill_upscale_body(maps.depth[blockIdx.y], w, h, scale, dw, dh, bilinear, zfill, zfill + (size_t)dw * dh, k0, k1, k2, k3,
+                          maps.dist[blockIdx.y]);
+}
+__global__ void depth_fill_scale1_levels_kernel(DfMaps maps, const float* __restrict__ scratch, size_t frame_words, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) maps.dist[blockIdx.y][i] = scratch[blockIdx.y * frame_words + n + i];
+}
+
+// The context's scratch, `bytes` behind its 64 bytes of status words.  Growing a held block synchronises the stream
+// (DevBuf::ensure) and would lose the sticky overflow word: it is carried over.
+int df_scratch_bytes(mh_ctx* ctx, size_t bytes);
+// ... for `frames` frames of the replay: [overflow word, valid count | the frames' downscaled maps]
+int df_scratch(mh_ctx* ctx, int frames) { return df_scratch_bytes(ctx, sizeof(float) * DF_FRAME_FLOATS * (size_t)frames); }
+int df_scratch_bytes(mh_ctx* ctx, size_t bytes) {
   hipStream_t s = ctx->stream;
-  const size_t need = 64 + sizeof(float) * DF_FRAME_FLOATS * (size_t)frames;
+  const size_t need = 64 + bytes;
   if (ctx->df_buf.cap >= need) return MH_OK;
   int32_t word = 0;
   if (ctx->df_buf) {
@@ -258,10 +580,44 @@ int df_launch(mh_ctx* ctx, const char* who, float4* depth, float* dist, const Df
     ctx->err = std::string(who) + ": scale factor larger than the map";
     return MH_ERR_ARG;
   }
+  if (ctx->df_mode == MH_DEPTH_FILL_LEVELS) {
+    ctx->df_lv_frames = 0;   // (until the launches below are out: a refused or failed call leaves no stats to read)
+    const long n = (long)dw * dh;
+    if (n > DF_LV_MAX_PIX) {
+      ctx->err = std::string(who) + ": the downscaled map has more than 2^21 pixels";
+      return MH_ERR_CAPACITY;
+    }
+    // the scratch follows the map size and the frame count: it may grow here, before the launches (that synchronises)
+    const size_t frame_words = df_lv_frame_words((size_t)n);
+    if (int rc = df_scratch_bytes(ctx, DF_LV_HEAD - 64 + sizeof(float) * frame_words * (size_t)n_frames)) return rc;
+    hipStream_t s = ctx->stream;
+    const int n_full = width * height;
+    int32_t* words = reinterpret_cast<int32_t*>(ctx->df_buf.p);
+    int32_t* stats = reinterpret_cast<int32_t*>(ctx->df_buf + 64);
+    float* scratch = reinterpret_cast<float*>(ctx->df_buf + DF_LV_HEAD);
+    DfMaps one;
+    if (!batch) {
+      one.depth[0] = depth;
+      one.dist[0] = dist;
+      batch = &one;
+    }
+    hipLaunchKernelGGL(depth_fill_levels_kernel, dim3(n_frames), dim3(DF_THREADS), 0, s, *batch, width, height, scale, dw, dh,
+                       scratch, frame_words, words, stats);
+    const dim3 grid((n_full + 255) / 256, n_frames);
+    if (scale == 1)
+      hipLaunchKernelGGL(depth_fill_scale1_levels_kernel, grid, dim3(256), 0, s, *batch, scratch, frame_words, n_full);
+    else
+      hipLaunchKernelGGL(depth_fill_upscale_levels_kernel, grid, dim3(256), 0, s, *batch, width, height, scale, dw, dh,
+                         bilinear ? 1 : 0, scratch, frame_words, K[0], K[1], K[2], K[3]);
+    MH_HIP(ctx, hipGetLastError());
+    ctx->df_lv_frames = n_frames;
+    return MH_OK;
+  }
   if ((long)dw * dh > DF_MAX_PIX) {
     ctx->err = std::string(who) + ": the downscaled map has more than 8192 pixels (the fill is LDS resident)";
     return MH_ERR_CAPACITY;
   }
+  ctx->df_lv_frames = 0;   // (the replay's maps lie where the stats were)
   hipStream_t s = ctx->stream;
   const int n_full = width * height;
   int32_t* words = reinterpret_cast<int32_t*>(ctx->df_buf.p);
@@ -355,14 +711,41 @@ extern "C" int mh_depth_fill_batch(mh_ctx* ctx, float* const* depth_xyzn_dev, fl
       }
   MH_HIP(ctx, hipSetDevice(ctx->device));
   if (int rc = use_stream(ctx)) return rc;
-  // room for MH_MAX_BATCH frames from the first batch on: no later batch regrows the block behind one in flight
-  if (int rc = df_scratch(ctx, MH_MAX_BATCH)) return rc;
+  // the replay: room for MH_MAX_BATCH frames from the first batch on, so no later batch regrows the block behind one in
+  // flight.  MH_DEPTH_FILL_LEVELS sizes the block in df_launch from the map and n_frames: a larger batch regrows it there.
+  if (ctx->df_mode != MH_DEPTH_FILL_LEVELS)
+    if (int rc = df_scratch(ctx, MH_MAX_BATCH)) return rc;
   DfMaps maps;
   for (int f = 0; f < n_frames; ++f) {
     maps.depth[f] = reinterpret_cast<float4*>(depth_xyzn_dev[f]);
     maps.dist[f] = fill_distance_dev[f];
   }
   return df_launch(ctx, "mh_depth_fill_batch", nullptr, nullptr, &maps, n_frames, width, height, scale_factor, bilinear, K);
+}
+
+extern "C" int mh_depth_fill_set_mode(mh_ctx* ctx, int mode) {
+  if (!ctx || (mode != MH_DEPTH_FILL_REPLAY && mode != MH_DEPTH_FILL_LEVELS)) return MH_ERR_ARG;
+  ctx->df_mode = mode;
+  return MH_OK;
+}
+
+extern "C" int mh_depth_fill_get_mode(mh_ctx* ctx, int* mode) {
+  if (!ctx || !mode) return MH_ERR_ARG;
+  *mode = ctx->df_mode;
+  return MH_OK;
+}
+
+extern "C" int mh_depth_fill_stats(mh_ctx* ctx, int frame, int32_t out[4]) {
+  if (!ctx || !out) return MH_ERR_ARG;
+  if (!ctx->df_buf || frame < 0 || frame >= ctx->df_lv_frames) {
+    ctx->err = "mh_depth_fill_stats: no MH_DEPTH_FILL_LEVELS fill of that frame since the last fill of the other mode";
+    return MH_ERR_ARG;
+  }
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = use_stream(ctx)) return rc;
+  MH_HIP(ctx, hipMemcpyAsync(out, ctx->df_buf + 64 + 16 * (size_t)frame, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MH_OK;
 }
 
 extern "C" int mh_depth_fill_status(mh_ctx* ctx) {
@@ -375,7 +758,11 @@ extern "C" int mh_depth_fill_status(mh_ctx* ctx) {
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (word) {
     MH_HIP(ctx, hipMemsetAsync(ctx->df_buf, 0, sizeof(int32_t), ctx->stream));
-    ctx->err = "mh_depth_fill: the fill's queue outgrew its ring (the maps of that call are incomplete)";
+    // (df_lv_frames: the last fill was a MH_DEPTH_FILL_LEVELS one; the default mode keeps the text it always had)
+    ctx->err = ctx->df_lv_frames
+                   ? "mh_depth_fill: a generation of the fill outgrew 4 * dw * dh elements, or the fill dw * dh generations "
+                     "(MH_DEPTH_FILL_LEVELS; the maps of that call are incomplete)"
+                   : "mh_depth_fill: the fill's queue outgrew its ring (the maps of that call are incomplete)";
     return MH_ERR_CAPACITY;
   }
   return MH_OK;

@@ -41,6 +41,7 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
   int Kind;
   int MaxKeypoints, DoubleImSize;   // config keys: keypoint capacity of the frame (2048), libsiftfast's DoubleImSize (1)
   int IncrementalModels;
+  int LevelFill;   // config key: the frame's DEPTHFILL in MH_DEPTH_FILL_LEVELS mode (FillScale 4, 2, 1; 1280 x 960 frames)
   unsigned long frameCounter;
   int32_t lastCounts[4];
 
@@ -62,7 +63,7 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
       : FillScale(FillScale), Bilinear(Bilinear), DescriptorSize(DescriptorSize), DescriptorType(DescriptorType),
         PatchSize(PatchSize), Density1(Density1), Density2(Density2),
         am(MinRatioMin, MinRatioMax, MaxRatioMin, MaxRatioMax, DimensionPeak, DimensionFade), Alpha(Alpha),
-        Kind(MH_DEPTH_BACKPROJECTION), MaxKeypoints(2048), DoubleImSize(1), IncrementalModels(0), frameCounter(0) {
+        Kind(MH_DEPTH_BACKPROJECTION), MaxKeypoints(2048), DoubleImSize(1), IncrementalModels(0), LevelFill(0), frameCounter(0) {
     lk.cutoff = (float)Cutoff;
     lk.min_pts = MinPts;
     lk.use3d_filter = Use3DFilter;
@@ -109,6 +110,7 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
     hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "NHypotheses2", prm.pose2.n_hypotheses);
     hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "MaxKeypoints", MaxKeypoints);
     hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "DoubleImSize", DoubleImSize);
+    hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "LevelFill", LevelFill);
   }
   void setConfig(map<string, string>& config) {
     hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "Density", Density1);
@@ -116,6 +118,7 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
     hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "MaxKeypoints", MaxKeypoints);
     hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "DoubleImSize", DoubleImSize);
     hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "IncrementalModels", IncrementalModels);
+    hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "LevelFill", LevelFill);
   }
 
   void process(FrameData& frameData) {
@@ -176,6 +179,9 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
     int32_t n = 0;
     int32_t* const counts = lastCounts;
     for (int j = 0; j < 4; ++j) counts[j] = 0;
+    int fillModeBefore = MH_DEPTH_FILL_REPLAY;   // the session's context is shared: its mode is put back afterwards
+    mh_depth_fill_get_mode(ctx, &fillModeBefore);
+    if (LevelFill) mh_depth_fill_set_mode(ctx, MH_DEPTH_FILL_LEVELS);
     int rc = mh_frame_run_kinect_host(ctx, &gray->data[0], (float*)&depthmap->data[0],
                                       distanceMap ? (float*)&distanceMap->data[0] : 0, w, h, DoubleImSize, MaxKeypoints, &cam,
                                       &prm, FillScale, Bilinear ? 1 : 0, Kind, (float)Alpha,
@@ -188,12 +194,14 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
     // the context goes back to a plain one: another mh_frame_* user of the session must not inherit this pipeline's front end
     struct Restore {
       mh_ctx* ctx;
+      int fillMode;
       ~Restore() {
         mh_frame_set_depth_rules(ctx, 0, 0);
         mh_frame_set_cluster_linkage(ctx, 0);
         mh_frame_set_depth_image(ctx, 0, 0, 0, 0, 0, 0.5f, 0.1f);
+        mh_depth_fill_set_mode(ctx, fillMode);
       }
-    } restore = {ctx};
+    } restore = {ctx, fillModeBefore};
     if (rc != MH_OK) { HipSession::warn("mh_frame_run_kinect_host"); return; }
     if (fill) frameData.images.push_back(distanceMap);
     // frameData.matches as the steps up to DEPTHPROP leave it, from the device's lists

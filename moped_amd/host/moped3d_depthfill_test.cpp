@@ -1,6 +1,6 @@
 // moped3d_depthfill_test -- the DEPTHFILL step plugin driven the way moped3d's pipeline drives it
 // (moped3d/libmoped/src/config.hpp:39, src/moped.cpp: the active algorithm of every step runs on the frame):
-//   moped3d_depthfill_test in.bin out.bin [scaleFactor=8] [bilinear=0]
+//   moped3d_depthfill_test in.bin out.bin [scaleFactor=8] [bilinear=0] [levelFill=0]
 // in.bin : int32 w, h; float32 K[4]; float32 depth[h][w][4] (x, y, z, norm; z < 0 = hole)
 // out.bin: the frame's depth map after the step, then its "<name>.distance" map [h][w]
 #define MOPED_AMD_WITH_DEPTH
@@ -15,7 +15,7 @@ using namespace MopedNS;
 
 int main(int argc, char** argv) {
   if (argc < 3) {
-    std::fprintf(stderr, "usage: %s in.bin out.bin [scaleFactor] [bilinear]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s in.bin out.bin [scaleFactor] [bilinear] [levelFill]\n", argv[0]);
     return 2;
   }
   FILE* f = std::fopen(argv[1], "rb");
@@ -42,7 +42,8 @@ int main(int argc, char** argv) {
   frameData.images.push_back(depth);
 
   MopedPipeline pipeline;
-  pipeline.addAlg("DEPTHFILL", new DEPTH_FILL_EXACT_HIP(argc > 3 ? std::atoi(argv[3]) : 8, argc > 4 && std::atoi(argv[4]) != 0));
+  pipeline.addAlg("DEPTHFILL", new DEPTH_FILL_EXACT_HIP(argc > 3 ? std::atoi(argv[3]) : 8, argc > 4 && std::atoi(argv[4]) != 0,
+                                                            argc > 5 && std::atoi(argv[5]) != 0));
   list<MopedAlg*> algs = pipeline.getAlgs(true);
   if (algs.empty()) {
     std::fprintf(stderr, "DEPTHFILL: no gfx950 device / HIP library -- not capable\n");

@@ -308,6 +308,13 @@ class FramePipeline:
         c.frame_enqueue_image_batch(list(gray_ptrs), w, h, double_size, max_keypoints, self.K, self.cam, self.params, seeds,
                                     _cam_struct=self._cam)
 
+    def set_depth_fill_mode(self, mode: int):
+        """How enqueue_kinect_batch fills the maps, on every slot's context: capi.DEPTH_FILL_REPLAY (the default; maps of
+        up to 8192 downscaled pixels, 640 x 480 from fill_scale 8 on) or capi.DEPTH_FILL_LEVELS (the same bytes, maps of
+        up to 2^21 downscaled pixels: fill_scale 4, 2 or 1, 1280 x 960 frames)."""
+        for c in self.ctxs:
+            c.depth_fill_set_mode(mode)
+
     def set_filter_depth(self, points_xyz, points_off, f1=None, f2=None, depth_cam=None):
         """FILTER (f1) and / or FILTER2 (f2) of the frames enqueued from now on as moped3d's FILTER_PROJECTION_DEPTH: the
         pose of every object is tested against the frame's depth map, so enqueue_kinect_batch and the other depth-map
