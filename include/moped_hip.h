@@ -11,6 +11,9 @@
  * What each entry point replaces (paths relative to moped2/libmoped/):
  *   mh_db_upload        MATCH_ANN_CPU::Update            src/match/MATCH_ANN_CPU.hpp:72-109
  *   mh_db_splice        Moped::addModel / removeModel    src/moped.cpp:139-159 (+ the Update() they trigger)
+ *   mh_db_splice_image[s]  Moped::createPlanarModelsFromImages  src/moped.cpp:196-236 (image -> model of the store)
+ *   mh_planar_rows_dev  ... its loop over detectedFeatures  src/moped.cpp:220-232
+ *   mh_models_write_xml the file samples/createModels/createModels.cpp:121-126 writes (sXML::print, include/sXML.hpp:146-170)
  *   mh_normalize        MATCH_ANN_CPU::norm              src/match/MATCH_ANN_CPU.hpp:54-57
  *   mh_match            MATCH_ANN_CPU::process search    src/match/MATCH_ANN_CPU.hpp:155-165
  *                       (= MATCH_FLANN_CPU::process      src/match/MATCH_FLANN_CPU.hpp:133-191)
@@ -1145,6 +1148,82 @@ int mh_db_splice_models(mh_ctx* ctx, int op, int model, const mh_model_set* s, i
 /* mh_db_upload with the normalisation done on the device (normalize != 0). */
 int mh_db_upload_raw(mh_ctx* ctx, const float* desc_host, const int32_t* model_of_host,
                      const float* xyz_host, int N, int n_models, int32_t index_base, int normalize);
+/* A model from rows (e.g. the ones mh_db_splice_image hands back): `name` replaces a model of that name, else appends
+ * (moped.cpp:141-146, as mh_models_add_xml).  desc [n_rows][128], xyz [n_rows][3] are kept as given, NOT normalised;
+ * the bounding box is min / max of xyz (moped.cpp:107-125).  MH_ERR_ARG: n_rows < 0, a null name, null arrays with
+ * n_rows > 0, a set that is a mapped .mopeddb. */
+int mh_models_add_rows(mh_model_set* s, const char* name, const float* desc, const float* xyz, int64_t n_rows);
+/* Model i of the set as the `.moped.xml` file samples/createModels/createModels.cpp:121-126 writes: the tree
+ * Moped::createPlanarModelsFromImages builds (src/moped.cpp:211-233: <Model name=..> with one <Points> child, one <Point>
+ * per row with p3d, desc_type, desc), printed as sXML::print prints it (include/sXML.hpp:146-170: one tab per level,
+ * properties in std::map order = desc, desc_type, p3d), numbers as toString prints them (include/moped.hpp:359-360:
+ * ostream << float = %g, 6 significant digits; a z of 0 prints as "0", the literal of moped.cpp:225).
+ * WHICH DESCRIPTORS: the file holds the set's rows -- for a model taught by mh_db_splice_image FEAT's unit-length
+ * descriptors.  The reference's file holds what MATCH left in detectedFeatures: the same rows renormalised once more in
+ * place (src/match/MATCH_ANN_CPU.hpp:157), and only when its database had more than one point (:140, skipCalculation);
+ * the rows mh_frame_features_dev hands out after a frame are exactly those.  The 6-digit text hides the difference on
+ * almost every value; it is not pinned. */
+int mh_models_write_xml(const mh_model_set* s, int i, const char* path);
+
+/* ---- planar models from images: Moped::createPlanarModelsFromImages (src/moped.cpp:196-236) -----------------------
+ * The reference runs the pipeline's front on each image and turns every detected feature into a model point at
+ * (u scale, v scale, 0), in detectedFeatures order (:220-232); samples/createModels/createModels.cpp is its user.  Here:
+ * image on the device in, a new model in the resident store out, while frames keep flowing.
+ *
+ * form 0 (the reference's, :225): x = u scale, y = v scale, z = 0.
+ * form 1 (a plane at depth z in front of a camera K = fx, fy, cx, cy):  x = (u - cx) / fx * z, y = (v - cy) / fy * z, z.
+ * One float32 rounding per operation in that order, no fused multiply-add, correctly rounded division.
+ * roi = u0, v0, u1, v1: keypoint (u, v) is kept if u0 <= u < u1 && v0 <= v < v1 (a NaN coordinate is dropped); all zeros
+ * = every keypoint.  max_rows > 0: only the first max_rows kept keypoints (list order).  Kept rows come out densely
+ * packed in FEAT's list order; descriptors are copied unchanged. */
+typedef struct {
+  int32_t form;
+  float scale;
+  float K[4];
+  float z;
+  float roi[4];
+  int32_t max_rows;
+} mh_planar_spec;
+/* The selection alone, on given device arrays (the rows of mh_sift_extract_dev or mh_frame_features_dev): desc_dev
+ * [cap][128], xy_dev [cap][2], *n_dev keypoints (clamped to [0, cap]).  Writes the
+ * kept rows to desc_out_dev [out_cap][128] / xyz_out_dev [out_cap][3] -- the first out_cap if more are kept -- their
+ * count to *n_out_dev and Model::boundingBox (moped.cpp:107-125: min xyz, max xyz; +-10E10 when nothing is kept) to
+ * bbox_dev[6].  Rows at and beyond *n_out_dev are not written.  Stream-ordered, no host wait.  MH_ERR_ARG: a spec
+ * mh_db_splice_image refuses, descriptor arrays not 16-byte aligned. */
+int mh_planar_rows_dev(mh_ctx* ctx, const float* desc_dev, const float* xy_dev, const int32_t* n_dev, int cap,
+                       const mh_planar_spec* spec, float* desc_out_dev, float* xyz_out_dev, int out_cap,
+                       int32_t* n_out_dev, float* bbox_dev);
+/* n_images <= MH_MAX_BATCH lists in ONE launch (the layout of mh_sift_extract_batch_dev: image i at desc_dev + i cap 128,
+ * xy_dev + i cap 2, n_dev[i]); image i's rows go to desc_out_dev + i out_cap 128 / xyz_out_dev + i out_cap 3, n_out_dev[i],
+ * bbox_dev + 6 i, bit for bit what mh_planar_rows_dev writes for it alone. */
+int mh_planar_rows_batch_dev(mh_ctx* ctx, const float* desc_dev, const float* xy_dev, const int32_t* n_dev, int n_images,
+                             int cap, const mh_planar_spec* spec, float* desc_out_dev, float* xyz_out_dev, int out_cap,
+                             int32_t* n_out_dev, float* bbox_dev);
+/* createPlanarModelsFromImages for one image, into the resident store: [UNDISTORTED_IMAGE with spec->K if
+ * mh_frame_set_undistort is on] -> FEAT (max_keypoints = the list's capacity) -> selection -> mh_db_splice(op, model)
+ * of the kept rows with normalize = 1, as Update() normalises model descriptors (src/match/MATCH_ANN_CPU.hpp:94).
+ * op = MH_DB_INSERT or MH_DB_REPLACE.  The selection writes straight into the edit's staging block; the rows never
+ * leave the device.  Every guarantee of mh_db_splice holds: MH_ERR_ARG (a store that is not editable, a model index out
+ * of range, MH_DB_REMOVE, a null image, a spec with form outside 0 / 1, a non-finite scale, z or K, fx or fy = 0 in
+ * form 1 or with undistortion on, a NaN in roi, max_rows < 0) comes before anything is launched; the edit is ordered on
+ * the context's stream like mh_db_splice; flip, mh_db_adopt and mh_db_generation work as there.  ONE host wait is added:
+ * the read-back of the kept count that sizes the splice.  *n_rows, bbox[6] (either may be NULL): rows of the new model
+ * and its bounding box.  rows_desc_host [rows_cap][128], rows_xyz_host [rows_cap][3] (both or neither): the first
+ * min(*n_rows, rows_cap) selected rows, descriptors as FEAT made them (what mh_models_add_rows takes).  No kept row: the
+ * edit mh_db_splice makes of n_rows = 0 (an empty model).  More keypoints in the image than max_keypoints: the edit
+ * is made from the first max_keypoints of the list and the call returns MH_ERR_CAPACITY, as mh_sift_extract does. */
+int mh_db_splice_image(mh_ctx* ctx, int op, int model, const uint8_t* gray_dev, int width, int height, int double_size,
+                       int max_keypoints, const mh_planar_spec* spec, int32_t* n_rows, float bbox[6],
+                       float* rows_desc_host, float* rows_xyz_host, int rows_cap);
+/* n_images <= MH_MAX_BATCH device images of one size -> models model_first .. model_first + n_images - 1 (INSERT, one
+ * after the other, so image i becomes model model_first + i): FEAT as ONE batch, ONE selection launch, one read-back of
+ * all counts, then the single-model splice n_images times.  Every model, and the store afterwards, are byte for byte
+ * those of mh_db_splice_image called per image.  n_rows [n_images], bbox [n_images][6] (may be NULL); image i's host
+ * rows at rows_desc_host + i rows_cap 128 / rows_xyz_host + i rows_cap 3.  Nothing is launched on MH_ERR_ARG; an error of
+ * a later splice leaves the earlier models in. */
+int mh_db_splice_images(mh_ctx* ctx, int model_first, const uint8_t* const* gray_dev, int n_images, int width, int height,
+                        int double_size, int max_keypoints, const mh_planar_spec* spec, int32_t* n_rows, float (*bbox)[6],
+                        float* rows_desc_host, float* rows_xyz_host, int rows_cap);
 
 /* ---- timing --------------------------------------------------------------------- */
 

@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MH_LIB_PATH") or os.path.join(_HERE, "libmoped_hip.so")  # override: A/B kernel builds
 
 MH_OK = 0
+MH_ERR_CAPACITY = -3
 
 
 class MhError(RuntimeError):
@@ -103,6 +104,26 @@ class mh_filter_depth_params(C.Structure):
     _fields_ = [("plausible_sq_distance", C.c_float), ("depth_fraction", C.c_float), ("min_keypoint_fraction", C.c_float)]
 
 
+class mh_planar_spec(C.Structure):
+    _fields_ = [("form", C.c_int32), ("scale", C.c_float), ("K", C.c_float * 4), ("z", C.c_float), ("roi", C.c_float * 4),
+                ("max_rows", C.c_int32)]
+
+
+def make_planar_spec(scale=None, z=None, K=None, roi=None, max_rows=0) -> mh_planar_spec:
+    """Exactly one of `scale` (form 0: x = u scale, y = v scale, z = 0 -- moped.cpp:225) and `z` (form 1: the plane at
+    depth z in front of the camera K = fx, fy, cx, cy).  roi = (u0, v0, u1, v1), half-open; None = every keypoint."""
+    if (scale is None) == (z is None):
+        raise ValueError("exactly one of scale and z")
+    sp = mh_planar_spec()
+    sp.form = 0 if z is None else 1
+    sp.scale = 1.0 if scale is None else float(scale)
+    sp.z = 0.0 if z is None else float(z)
+    sp.K[:] = [float(v) for v in (K if K is not None else (1.0, 1.0, 0.0, 0.0))]
+    sp.roi[:] = [float(v) for v in (roi if roi is not None else (0.0, 0.0, 0.0, 0.0))]
+    sp.max_rows = int(max_rows)
+    return sp
+
+
 def make_filter_depth_params(p):
     """None, an mh_filter_depth_params or (plausible_sq_distance, depth_fraction, min_keypoint_fraction)."""
     if p is None or isinstance(p, mh_filter_depth_params):
@@ -150,6 +171,8 @@ EXPORTS = [
     "mh_frame_route", "mh_filter_depth_debug_form",
     "mh_depth_filter", "mh_depth_prop", "mh_frame_run_kinect_host",
     "mh_linkage_debug_matrix", "mh_linkage_debug_agglomerate", "mh_frame_debug_fetch_clusters_slot",
+    "mh_planar_rows_dev", "mh_planar_rows_batch_dev", "mh_db_splice_image", "mh_db_splice_images",
+    "mh_models_add_rows", "mh_models_write_xml",
 ]
 COMM_ID_BYTES = 128      # MH_COMM_ID_BYTES
 EX2_OBJECTS = 62         # MH_EX2_OBJECTS
@@ -390,6 +413,14 @@ def load():
     if hasattr(L, "mh_frame_route"):   # (the same)
         L.mh_frame_route.argtypes = [vp, vp]
         L.mh_filter_depth_debug_form.argtypes = [vp, i32]
+    if hasattr(L, "mh_planar_rows_dev"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
+        L.mh_planar_rows_dev.argtypes = [vp, vp, vp, vp, i32, C.POINTER(mh_planar_spec), vp, vp, i32, vp, vp]
+        L.mh_planar_rows_batch_dev.argtypes = [vp, vp, vp, vp, i32, i32, C.POINTER(mh_planar_spec), vp, vp, i32, vp, vp]
+        L.mh_db_splice_image.argtypes = [vp, i32, i32, vp, i32, i32, i32, i32, C.POINTER(mh_planar_spec),
+                                         C.POINTER(C.c_int32), vp, vp, vp, i32]
+        L.mh_db_splice_images.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, C.POINTER(mh_planar_spec), vp, vp, vp, vp, i32]
+        L.mh_models_add_rows.argtypes = [vp, C.c_char_p, vp, vp, C.c_int64]
+        L.mh_models_write_xml.argtypes = [vp, i32, C.c_char_p]
     _lib = L
     return L
 
@@ -671,6 +702,57 @@ class Context:
         """mh_db_splice_models: the rows of model `set_index` of a parsed set, normalised on the device."""
         self._ck(self.L.mh_db_splice_models(self.h, op, int(model), models.h if models is not None else None, int(set_index)),
                  "mh_db_splice_models")
+
+    # ---- planar models from images: createPlanarModelsFromImages (moped.cpp:196-236) ----
+    def planar_rows_dev(self, desc_ptr, xy_ptr, n_ptr, cap, spec: mh_planar_spec, desc_out_ptr, xyz_out_ptr, out_cap,
+                        n_out_ptr, bbox_ptr, n_images=1):
+        """mh_planar_rows_dev (n_images > 1: mh_planar_rows_batch_dev) on device arrays; asynchronous."""
+        a = [C.c_void_p(desc_ptr), C.c_void_p(xy_ptr), C.c_void_p(n_ptr)]
+        b = [int(cap), C.byref(spec) if spec is not None else None, C.c_void_p(desc_out_ptr), C.c_void_p(xyz_out_ptr),
+             int(out_cap), C.c_void_p(n_out_ptr), C.c_void_p(bbox_ptr)]
+        if n_images == 1:
+            self._ck(self.L.mh_planar_rows_dev(self.h, *a, *b), "mh_planar_rows_dev")
+        else:
+            self._ck(self.L.mh_planar_rows_batch_dev(self.h, *a, int(n_images), *b), "mh_planar_rows_batch_dev")
+
+    def db_splice_image(self, op, model, gray_ptr, w, h, spec: mh_planar_spec, double_size=True, max_keypoints=4096,
+                        want_rows=False):
+        """mh_db_splice_image: the device image becomes model `model` (DB_INSERT / DB_REPLACE).  -> (n_rows, bbox[6]) or,
+        with want_rows, (n_rows, bbox, desc [n,128], xyz [n,3]) -- the selected rows, descriptors as FEAT made them."""
+        n = C.c_int32(0)
+        bbox = np.zeros(6, np.float32)
+        d = np.zeros((max_keypoints, DIM), np.float32) if want_rows else None
+        x = np.zeros((max_keypoints, 3), np.float32) if want_rows else None
+        rc = self.L.mh_db_splice_image(self.h, int(op), int(model), C.c_void_p(gray_ptr), w, h, int(double_size),
+                                       int(max_keypoints), C.byref(spec) if spec is not None else None, C.byref(n),
+                                       _ptr(bbox), _ptr(d) if want_rows else None, _ptr(x) if want_rows else None,
+                                       max_keypoints if want_rows else 0)
+        # MH_ERR_CAPACITY: the edit is made, from the first max_keypoints keypoints of the list
+        self.planar_truncated = rc == MH_ERR_CAPACITY
+        self._ck(MH_OK if self.planar_truncated else rc, "mh_db_splice_image")
+        if want_rows:
+            return int(n.value), bbox, d[:n.value].copy(), x[:n.value].copy()
+        return int(n.value), bbox
+
+    def db_splice_images(self, model_first, gray_ptrs, w, h, spec: mh_planar_spec, double_size=True, max_keypoints=4096,
+                         want_rows=False):
+        """mh_db_splice_images: len(gray_ptrs) device images of one size become models model_first .. (INSERT), FEAT as
+        one batch, one selection launch.  -> (n_rows [n], bbox [n,6]) and, with want_rows, lists of desc and xyz."""
+        k = len(gray_ptrs)
+        g = (C.c_void_p * k)(*gray_ptrs)
+        n = np.zeros(k, np.int32)
+        bbox = np.zeros((k, 6), np.float32)
+        d = np.zeros((k, max_keypoints, DIM), np.float32) if want_rows else None
+        x = np.zeros((k, max_keypoints, 3), np.float32) if want_rows else None
+        rc = self.L.mh_db_splice_images(self.h, int(model_first), g, k, w, h, int(double_size), int(max_keypoints),
+                                        C.byref(spec) if spec is not None else None, _ptr(n), _ptr(bbox),
+                                        _ptr(d) if want_rows else None, _ptr(x) if want_rows else None,
+                                        max_keypoints if want_rows else 0)
+        self.planar_truncated = rc == MH_ERR_CAPACITY
+        self._ck(MH_OK if self.planar_truncated else rc, "mh_db_splice_images")
+        if want_rows:
+            return n, bbox, [d[i, :n[i]].copy() for i in range(k)], [x[i, :n[i]].copy() for i in range(k)]
+        return n, bbox
 
     def db_reserve(self, max_rows, max_models):
         self._ck(self.L.mh_db_reserve(self.h, int(max_rows), int(max_models)), "mh_db_reserve")
@@ -1786,6 +1868,20 @@ class ModelSet:
 
     def save(self, path: str):
         self._ck(self.L.mh_models_save(self.h, path.encode()), "mh_models_save")
+
+    def add_rows(self, name: str, desc, xyz):
+        """A model from rows (desc [n,128] kept as given, xyz [n,3]); a known name replaces that model."""
+        desc = np.ascontiguousarray(desc, np.float32).reshape(-1, DIM)
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        if desc.shape[0] != xyz.shape[0]:
+            raise ValueError("one xyz per descriptor")
+        self._ck(self.L.mh_models_add_rows(self.h, name.encode("latin-1"), _ptr(desc), _ptr(xyz), desc.shape[0]),
+                 "mh_models_add_rows")
+
+    def write_xml(self, i: int, path: str):
+        """Model i as the `.moped.xml` file createModels writes (mh_models_write_xml)."""
+        if self.L.mh_models_write_xml(self.h, int(i), path.encode()) != 0:
+            raise MhError(f"mh_models_write_xml: no model {i}, or cannot write {path}")
 
     @property
     def n_models(self) -> int:

@@ -124,6 +124,8 @@ int sift_into_batch(mh_ctx* ctx, const uint8_t* const* gray_dev, int n, int widt
   return MH_OK;
 }
 
+const int32_t* sift_counters_dev(mh_ctx* ctx, int slot) { return ctx->sift ? ctx->sift->B.counters + 4 * slot : nullptr; }
+
 }  // namespace mh
 
 extern "C" {

@@ -153,6 +153,12 @@ struct mh_ctx {
   std::vector<HeldStore> held;
   std::vector<hipEvent_t> held_events;   // idle events of released entries
   mh::DevBuf<float> db_stage;        // an edit's new rows: [rows][128] descriptors, [rows] norm terms, [rows][3] coordinates
+  struct Planar {                    // mh_db_splice_image[s]: FEAT's lists of the images being taught, the selection's results
+    mh::DevBuf<float> desc, xy;      // device [images][cap][128], [images][cap][2]
+    mh::DevBuf<float> rows_desc, rows_xyz;   // device [images][cap] selected rows (batch; the host copy of a single edit)
+    mh::DevBuf<int32_t> words;       // device [6][MH_MAX_BATCH]: FEAT's counts | kept counts | FEAT's 4 counter words per image
+    mh::DevBuf<float> box;           // device [MH_MAX_BATCH][6]
+  } planar;
   int db_edit_route = 0;             // 0: the fused pass (db_splice_kernel); 1: device copies + the upload's preparation (mh_db_debug_route)
   hipEvent_t db_ev[2] = {nullptr, nullptr};   // around an edit's pass over the rows when timing is on (mh_db_edit_ms)
   bool db_ev_valid = false;
@@ -377,5 +383,31 @@ struct ImagesPackArgs {
   DevCam cams[MH_MAX_IMAGES];
 };
 void launch_images_pack(const ImagesPackArgs& a, int n_frames, hipStream_t s);
+
+// planar.hip: FEAT's lists -> model rows (createPlanarModelsFromImages, moped.cpp:196-236), one launch, workgroup i =
+// image i.  Image i reads desc + i cap 128, xy + i cap 2 and n[i]; it writes its kept rows at desc_out / xyz_out + i
+// out_pitch rows (desc_copy: a second copy of the descriptors, or null), at most out_cap of them, their count to
+// n_out[i] and their bounding box to bbox + 6 i.
+struct PlanarArgs {
+  const float* desc;
+  const float* xy;
+  const int32_t* n;
+  int cap;
+  mh_planar_spec spec;
+  int all;   // the region of interest is "every keypoint"
+  float* desc_out;
+  float* desc_copy;
+  float* xyz_out;
+  size_t out_pitch;
+  int out_cap;
+  int32_t* n_out;
+  float* bbox;
+};
+void launch_planar_rows(const PlanarArgs& a, int n_images, hipStream_t s);
+// MH_ERR_ARG (and ctx->err) for a spec mh_db_splice_image refuses; *all = its roi means every keypoint
+int planar_spec_check(mh_ctx* ctx, const char* who, const mh_planar_spec* spec, int* all);
+// api_sift.hip: the four counter words of image `slot` of the context's last extraction (device): [1] keys found, [2] != 0:
+// a list overflowed
+const int32_t* sift_counters_dev(mh_ctx* ctx, int slot);
 
 }  // namespace mh

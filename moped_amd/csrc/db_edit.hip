@@ -347,32 +347,46 @@ int mh_db_generation(const mh_ctx* ctx, uint64_t* generation) {
   return MH_OK;
 }
 
-int mh_db_splice(mh_ctx* ctx, int op, int model, const float* desc, const float* xyz, int n_rows, int normalize,
-                 int on_device) {
-  if (!ctx) return MH_ERR_ARG;
-  if (op < MH_DB_INSERT || op > MH_DB_REMOVE) return refuse(ctx, "mh_db_splice", "unknown operation");
-  if (op == MH_DB_REMOVE) n_rows = 0;
-  if (n_rows < 0 || (n_rows > 0 && (!desc || !xyz))) return refuse(ctx, "mh_db_splice", "bad argument");
+// what every edit checks before anything is launched: the operation, an editable store, the model index, room for one more
+static int check_edit(mh_ctx* ctx, const char* who, int op, int model, int n_new = 1) {
+  if (op < MH_DB_INSERT || op > MH_DB_REMOVE) return refuse(ctx, who, "unknown operation");
   const DbStore* old = ctx->store.get();
-  if (const char* why = why_not_editable(old)) return refuse(ctx, "mh_db_splice", why);
+  if (const char* why = why_not_editable(old)) return refuse(ctx, who, why);
   const int nm = old ? old->n_models : 0;
   if (op == MH_DB_INSERT ? (model < 0 || model > nm) : (model < 0 || model >= nm))
-    return refuse(ctx, "mh_db_splice", nm == 0 && op != MH_DB_INSERT ? "model index out of range (the store is empty)"
-                                                                       : "model index out of range");
-  if (op == MH_DB_INSERT && nm + 1 > MH_MAX_MODELS) {
-    ctx->err = "mh_db_splice: more than MH_MAX_MODELS models";
+    return refuse(ctx, who, nm == 0 && op != MH_DB_INSERT ? "model index out of range (the store is empty)"
+                                                           : "model index out of range");
+  if (op == MH_DB_INSERT && nm + n_new > MH_MAX_MODELS) {
+    ctx->err = std::string(who) + ": more than MH_MAX_MODELS models";
     return MH_ERR_CAPACITY;
   }
+  return MH_OK;
+}
+
+// the edit of a checked (op, model) whose n_rows new rows lie in the staging block with their norm terms
+static int splice_staged(mh_ctx* ctx, int op, int model, int n_rows) {
+  const DbStore* old = ctx->store.get();
+  const int nm = old ? old->n_models : 0;
   // the rows that leave, [b, e), and the new per-model table
   static const std::vector<int32_t> none(1, 0);
   const std::vector<int32_t>& begin = old ? old->model_begin : none;   // [nm + 1]
-  const int b = begin[op == MH_DB_INSERT ? model : model];
+  const int b = begin[model];
   const int e = op == MH_DB_INSERT ? b : begin[model + 1];
   const int shift = n_rows - (e - b);
   const int delta = op == MH_DB_INSERT ? 1 : op == MH_DB_REMOVE ? -1 : 0;
   std::vector<int32_t> table(begin.begin(), begin.begin() + model + 1);   // models up to `model` begin where they began
   if (op == MH_DB_INSERT) table.push_back(b + n_rows);                     // the model that was `model`, behind the new rows
   for (int m = model + (op == MH_DB_REMOVE ? 2 : 1); m <= nm; ++m) table.push_back(begin[m] + shift);
+  return run_splice(ctx, b, e, n_rows, model, delta, std::move(table));
+}
+
+int mh_db_splice(mh_ctx* ctx, int op, int model, const float* desc, const float* xyz, int n_rows, int normalize,
+                 int on_device) {
+  if (!ctx) return MH_ERR_ARG;
+  if (op < MH_DB_INSERT || op > MH_DB_REMOVE) return refuse(ctx, "mh_db_splice", "unknown operation");
+  if (op == MH_DB_REMOVE) n_rows = 0;
+  if (n_rows < 0 || (n_rows > 0 && (!desc || !xyz))) return refuse(ctx, "mh_db_splice", "bad argument");
+  if (int rc = check_edit(ctx, "mh_db_splice", op, model)) return rc;
   MH_HIP(ctx, hipSetDevice(ctx->device));
   if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
   // stage the new rows: their norm terms by the upload's own launches, so that their bits are the upload's by construction
@@ -389,7 +403,198 @@ int mh_db_splice(mh_ctx* ctx, int op, int model, const float* desc, const float*
     else launch_row_norms(sd, sn, n_rows, ctx->stream);
     MH_HIP(ctx, hipGetLastError());
   }
-  return run_splice(ctx, b, e, n_rows, model, delta, std::move(table));
+  return splice_staged(ctx, op, model, n_rows);
+}
+
+// ---- planar models from images: createPlanarModelsFromImages (moped.cpp:196-236) into the resident store ------------
+namespace {
+
+// the arguments mh_db_splice_image[s] share, checked before anything is launched
+int check_planar_call(mh_ctx* ctx, const char* who, const uint8_t* const* gray_dev, int n_images, int width, int height,
+                      int max_keypoints, const mh_planar_spec* spec, const float* rows_desc_host, const float* rows_xyz_host,
+                      int rows_cap, int* all) {
+  if (!gray_dev || n_images <= 0 || n_images > MH_MAX_BATCH || width <= 0 || height <= 0 || max_keypoints <= 0 ||
+      (rows_desc_host == nullptr) != (rows_xyz_host == nullptr) || (rows_desc_host && rows_cap <= 0))
+    return refuse(ctx, who, "bad argument");
+  for (int i = 0; i < n_images; ++i)
+    if (!gray_dev[i]) return refuse(ctx, who, "bad argument (a null image)");
+  if (int rc = planar_spec_check(ctx, who, spec, all)) return rc;
+  if (ctx->und_on && (spec->K[0] == 0.f || spec->K[1] == 0.f)) return refuse(ctx, who, "undistortion is on and fx or fy is 0");
+  return MH_OK;
+}
+
+int ensure_planar(mh_ctx* ctx, int n_images, int cap, bool rows) {
+  mh_ctx::Planar& p = ctx->planar;
+  const size_t n = (size_t)n_images * cap;
+  hipStream_t s = ctx->stream;
+  MH_HIP(ctx, p.desc.ensure(n * DIM, s));
+  MH_HIP(ctx, p.xy.ensure(n * 2, s));
+  MH_HIP(ctx, p.words.ensure(6 * MH_MAX_BATCH, s));
+  MH_HIP(ctx, p.box.ensure(6 * MH_MAX_BATCH, s));
+  if (rows) {
+    MH_HIP(ctx, p.rows_desc.ensure(n * DIM, s));
+    MH_HIP(ctx, p.rows_xyz.ensure(n * 3, s));
+  }
+  return MH_OK;
+}
+
+// [UNDISTORTED_IMAGE] -> FEAT of n images into ctx->planar (counts in words[0 .. n)), FEAT's counter words behind the
+// kept counts (words[2 B + 4 i ..])
+int planar_feat(mh_ctx* ctx, const uint8_t* const* gray_dev, int n, int width, int height, int double_size, int cap,
+                const mh_planar_spec* spec) {
+  mh_ctx::Planar& p = ctx->planar;
+  const uint8_t* staged[MH_MAX_BATCH];
+  int rc;
+  if (ctx->und_on) {
+    if ((rc = undistort_frame(ctx, gray_dev, n, width, height, spec->K, staged))) return rc;
+    gray_dev = staged;
+  }
+  if (n == 1) {
+    if ((rc = sift_into(ctx, gray_dev[0], width, height, double_size, cap, p.desc, p.xy, nullptr, p.words))) return rc;
+  } else if ((rc = sift_into_batch(ctx, gray_dev, n, width, height, double_size, cap, p.desc, p.xy, p.words))) {
+    return rc;
+  }
+  MH_HIP(ctx, hipMemcpyAsync(p.words + 2 * MH_MAX_BATCH, sift_counters_dev(ctx, 0), (size_t)n * 4 * sizeof(int32_t),
+                             hipMemcpyDeviceToDevice, ctx->stream));
+  return MH_OK;
+}
+
+}  // namespace
+
+int mh_db_splice_image(mh_ctx* ctx, int op, int model, const uint8_t* gray_dev, int width, int height, int double_size,
+                       int max_keypoints, const mh_planar_spec* spec, int32_t* n_rows, float bbox[6],
+                       float* rows_desc_host, float* rows_xyz_host, int rows_cap) {
+  if (!ctx) return MH_ERR_ARG;
+  const char* who = "mh_db_splice_image";
+  if (n_rows) *n_rows = 0;
+  if (op != MH_DB_INSERT && op != MH_DB_REPLACE) return refuse(ctx, who, "the operation is MH_DB_INSERT or MH_DB_REPLACE");
+  int all = 0, rc;
+  if ((rc = check_planar_call(ctx, who, &gray_dev, 1, width, height, max_keypoints, spec, rows_desc_host, rows_xyz_host,
+                              rows_cap, &all)))
+    return rc;
+  if ((rc = check_edit(ctx, who, op, model))) return rc;
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
+  const int cap = max_keypoints;
+  const int limit = spec->max_rows > 0 ? std::min(cap, spec->max_rows) : cap;
+  if ((rc = ensure_planar(ctx, 1, cap, rows_desc_host != nullptr))) return rc;
+  if ((rc = ensure_stage(ctx, (size_t)limit))) return rc;
+  if ((rc = planar_feat(ctx, &gray_dev, 1, width, height, double_size, cap, spec))) return rc;
+  mh_ctx::Planar& p = ctx->planar;
+  // the selection writes the edit's staging block itself; the norm terms by the upload's own launch, over the count on
+  // the device, so that it is in flight while the count travels
+  float* sd = ctx->db_stage;
+  float* sn = sd + stage_rows(ctx) * DIM;
+  float* sx = sn + stage_rows(ctx);
+  PlanarArgs a = {};
+  a.desc = p.desc;
+  a.xy = p.xy;
+  a.n = p.words;
+  a.cap = cap;
+  a.spec = *spec;
+  a.all = all;
+  a.desc_out = sd;
+  a.desc_copy = rows_desc_host ? (float*)p.rows_desc : nullptr;   // (normalisation is in place: the host gets FEAT's bits)
+  a.xyz_out = sx;
+  a.out_pitch = 0;
+  a.out_cap = limit;
+  a.n_out = p.words + MH_MAX_BATCH;
+  a.bbox = p.box;
+  launch_planar_rows(a, 1, ctx->stream);
+  launch_normalize(sd, sn, limit, ctx->stream, a.n_out);
+  MH_HIP(ctx, hipGetLastError());
+  // the added host wait: the kept count sizes the splice (the set it fills, the per-model table)
+  int32_t kept = 0, head[4] = {0, 0, 0, 0};
+  float box[6];
+  MH_HIP(ctx, hipMemcpyAsync(&kept, a.n_out, sizeof kept, hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(ctx, hipMemcpyAsync(head, p.words + 2 * MH_MAX_BATCH, sizeof head, hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(ctx, hipMemcpyAsync(box, p.box, sizeof box, hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (kept < 0 || kept > limit) {
+    ctx->err = "mh_db_splice_image: the selection reported a count outside its capacity";
+    return MH_ERR_HIP;
+  }
+  if (rows_desc_host && kept > 0) {
+    const size_t take = (size_t)std::min(kept, rows_cap);
+    MH_HIP(ctx, hipMemcpyAsync(rows_desc_host, p.rows_desc, take * DIM * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    MH_HIP(ctx, hipMemcpyAsync(rows_xyz_host, sx, take * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if ((rc = splice_staged(ctx, op, model, kept))) return rc;   // (ends with a wait for the stream: the host rows are there)
+  if (n_rows) *n_rows = kept;
+  if (bbox) std::memcpy(bbox, box, sizeof box);
+  if (head[2] || head[1] > cap) {
+    ctx->err = "mh_db_splice_image: more keypoints than max_keypoints (" + std::to_string(head[1]) + " found); the model has the first of the list";
+    return MH_ERR_CAPACITY;
+  }
+  return MH_OK;
+}
+
+int mh_db_splice_images(mh_ctx* ctx, int model_first, const uint8_t* const* gray_dev, int n_images, int width, int height,
+                        int double_size, int max_keypoints, const mh_planar_spec* spec, int32_t* n_rows, float (*bbox)[6],
+                        float* rows_desc_host, float* rows_xyz_host, int rows_cap) {
+  if (!ctx) return MH_ERR_ARG;
+  const char* who = "mh_db_splice_images";
+  int all = 0, rc;
+  if ((rc = check_planar_call(ctx, who, gray_dev, n_images, width, height, max_keypoints, spec, rows_desc_host,
+                              rows_xyz_host, rows_cap, &all)))
+    return rc;
+  if ((rc = check_edit(ctx, who, MH_DB_INSERT, model_first, n_images))) return rc;
+  for (int i = 0; n_rows && i < n_images; ++i) n_rows[i] = 0;
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
+  const int cap = max_keypoints;
+  const int limit = spec->max_rows > 0 ? std::min(cap, spec->max_rows) : cap;
+  if ((rc = ensure_planar(ctx, n_images, cap, true))) return rc;
+  if ((rc = ensure_stage(ctx, (size_t)limit))) return rc;
+  if ((rc = planar_feat(ctx, gray_dev, n_images, width, height, double_size, cap, spec))) return rc;
+  mh_ctx::Planar& p = ctx->planar;
+  PlanarArgs a = {};
+  a.desc = p.desc;
+  a.xy = p.xy;
+  a.n = p.words;
+  a.cap = cap;
+  a.spec = *spec;
+  a.all = all;
+  a.desc_out = p.rows_desc;
+  a.desc_copy = nullptr;
+  a.xyz_out = p.rows_xyz;
+  a.out_pitch = (size_t)cap;
+  a.out_cap = limit;
+  a.n_out = p.words + MH_MAX_BATCH;
+  a.bbox = p.box;
+  launch_planar_rows(a, n_images, ctx->stream);
+  MH_HIP(ctx, hipGetLastError());
+  // one read-back for the whole batch
+  int32_t kept[MH_MAX_BATCH], head[MH_MAX_BATCH][4];
+  float box[MH_MAX_BATCH][6];
+  MH_HIP(ctx, hipMemcpyAsync(kept, a.n_out, (size_t)n_images * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(ctx, hipMemcpyAsync(head, p.words + 2 * MH_MAX_BATCH, (size_t)n_images * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(ctx, hipMemcpyAsync(box, p.box, (size_t)n_images * 6 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  bool over = false;
+  for (int i = 0; i < n_images; ++i) {
+    if (kept[i] < 0 || kept[i] > limit) {
+      ctx->err = "mh_db_splice_images: the selection reported a count outside its capacity";
+      return MH_ERR_HIP;
+    }
+    const float* rd = p.rows_desc + (size_t)i * cap * DIM;
+    const float* rx = p.rows_xyz + (size_t)i * cap * 3;
+    if (rows_desc_host && kept[i] > 0) {
+      const size_t take = (size_t)std::min(kept[i], rows_cap);
+      MH_HIP(ctx, hipMemcpyAsync(rows_desc_host + (size_t)i * rows_cap * DIM, rd, take * DIM * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+      MH_HIP(ctx, hipMemcpyAsync(rows_xyz_host + (size_t)i * rows_cap * 3, rx, take * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    // the existing single-model pass, once per image (a multi-model pass is a later change)
+    if ((rc = mh_db_splice(ctx, MH_DB_INSERT, model_first + i, rd, rx, kept[i], 1, 1))) return rc;
+    if (n_rows) n_rows[i] = kept[i];
+    if (bbox) std::memcpy(bbox[i], box[i], sizeof box[i]);
+    over = over || head[i][2] || head[i][1] > cap;
+  }
+  if (over) {
+    ctx->err = "mh_db_splice_images: an image has more keypoints than max_keypoints; its model has the first of the list";
+    return MH_ERR_CAPACITY;
+  }
+  return MH_OK;
 }
 
 int mh_db_reserve(mh_ctx* ctx, int64_t max_rows, int max_models) {

@@ -388,6 +388,57 @@ struct DbModelRecord {
 constexpr size_t PAGE = 4096;
 inline size_t page_up(size_t x) { return (x + PAGE - 1) / PAGE * PAGE; }
 
+// a model with the name of an existing one replaces it (moped.cpp:141-146); others append
+void put_model(mh_model_set* s, const std::string& name, const float bbox[6], const float* new_desc, const float* new_xyz,
+               uint64_t n) {
+  ModelEntry e;
+  e.name = name;
+  memcpy(e.bbox, bbox, sizeof e.bbox);
+  int at = -1;
+  for (size_t i = 0; i < s->models.size(); ++i)
+    if (s->models[i].name == name) at = (int)i;
+  if (at >= 0) {
+    // rebuild the flat arrays without the old rows, new rows in the old position
+    const ModelEntry old = s->models[at];
+    std::vector<float> desc, xyz;
+    desc.reserve(s->desc.size() - old.n_rows * DIM + n * DIM);
+    xyz.reserve(s->xyz.size() - old.n_rows * 3 + n * 3);
+    desc.insert(desc.end(), s->desc.begin(), s->desc.begin() + old.row_begin * DIM);
+    desc.insert(desc.end(), new_desc, new_desc + n * DIM);
+    desc.insert(desc.end(), s->desc.begin() + (old.row_begin + old.n_rows) * DIM, s->desc.end());
+    xyz.insert(xyz.end(), s->xyz.begin(), s->xyz.begin() + old.row_begin * 3);
+    xyz.insert(xyz.end(), new_xyz, new_xyz + n * 3);
+    xyz.insert(xyz.end(), s->xyz.begin() + (old.row_begin + old.n_rows) * 3, s->xyz.end());
+    s->desc.swap(desc);
+    s->xyz.swap(xyz);
+    e.row_begin = old.row_begin;
+    e.n_rows = n;
+    s->models[at] = e;
+    uint64_t run = 0;
+    for (ModelEntry& m : s->models) {
+      m.row_begin = run;
+      run += m.n_rows;
+    }
+  } else {
+    e.row_begin = s->xyz.size() / 3;
+    e.n_rows = n;
+    s->desc.insert(s->desc.end(), new_desc, new_desc + n * DIM);
+    s->xyz.insert(s->xyz.end(), new_xyz, new_xyz + n * 3);
+    s->models.push_back(e);
+  }
+  s->n_rows = s->xyz.size() / 3;
+  s->model_of.resize(s->n_rows);
+  for (size_t i = 0; i < s->models.size(); ++i)
+    for (uint64_t r = 0; r < s->models[i].n_rows; ++r) s->model_of[s->models[i].row_begin + r] = (int32_t)i;
+}
+
+// toString (moped.hpp:359-360): ostream << float, i.e. %g with 6 significant digits
+void put_number(std::string& out, float v) {
+  char buf[40];
+  const int n = snprintf(buf, sizeof buf, "%g", (double)v);
+  out.append(buf, (size_t)n);
+}
+
 }  // namespace
 
 extern "C" {
@@ -416,48 +467,72 @@ int mh_models_add_xml_buffer(mh_model_set* s, const char* data, int64_t bytes) {
              std::to_string(DIM) + " values";
     return MH_ERR_ARG;
   }
-  // a model with the name of an existing one replaces it (moped.cpp:141-146); others append
-  ModelEntry e;
-  e.name = pm.name;
-  memcpy(e.bbox, pm.bbox, sizeof e.bbox);
-  const uint64_t n = pm.xyz.size() / 3;
-  int at = -1;
-  for (size_t i = 0; i < s->models.size(); ++i)
-    if (s->models[i].name == pm.name) at = (int)i;
-  if (at >= 0) {
-    // rebuild the flat arrays without the old rows, new rows in the old position
-    const ModelEntry old = s->models[at];
-    std::vector<float> desc, xyz;
-    desc.reserve(s->desc.size() - old.n_rows * DIM + pm.desc.size());
-    xyz.reserve(s->xyz.size() - old.n_rows * 3 + pm.xyz.size());
-    desc.insert(desc.end(), s->desc.begin(), s->desc.begin() + old.row_begin * DIM);
-    desc.insert(desc.end(), pm.desc.begin(), pm.desc.end());
-    desc.insert(desc.end(), s->desc.begin() + (old.row_begin + old.n_rows) * DIM, s->desc.end());
-    xyz.insert(xyz.end(), s->xyz.begin(), s->xyz.begin() + old.row_begin * 3);
-    xyz.insert(xyz.end(), pm.xyz.begin(), pm.xyz.end());
-    xyz.insert(xyz.end(), s->xyz.begin() + (old.row_begin + old.n_rows) * 3, s->xyz.end());
-    s->desc.swap(desc);
-    s->xyz.swap(xyz);
-    e.row_begin = old.row_begin;
-    e.n_rows = n;
-    s->models[at] = e;
-    uint64_t run = 0;
-    for (ModelEntry& m : s->models) {
-      m.row_begin = run;
-      run += m.n_rows;
-    }
-  } else {
-    e.row_begin = s->xyz.size() / 3;
-    e.n_rows = n;
-    s->desc.insert(s->desc.end(), pm.desc.begin(), pm.desc.end());
-    s->xyz.insert(s->xyz.end(), pm.xyz.begin(), pm.xyz.end());
-    s->models.push_back(e);
-  }
-  s->n_rows = s->xyz.size() / 3;
-  s->model_of.resize(s->n_rows);
-  for (size_t i = 0; i < s->models.size(); ++i)
-    for (uint64_t r = 0; r < s->models[i].n_rows; ++r) s->model_of[s->models[i].row_begin + r] = (int32_t)i;
+  put_model(s, pm.name, pm.bbox, pm.desc.data(), pm.xyz.data(), pm.xyz.size() / 3);
   return MH_OK;
+}
+
+int mh_models_add_rows(mh_model_set* s, const char* name, const float* desc, const float* xyz, int64_t n_rows) {
+  if (!s) return MH_ERR_ARG;
+  if (!name || n_rows < 0 || n_rows >= (1ll << 31) || (n_rows > 0 && (!desc || !xyz))) {
+    s->err = "mh_models_add_rows: bad argument";
+    return MH_ERR_ARG;
+  }
+  if (s->map) {
+    s->err = "model set is a read-only view of a .mopeddb file";
+    return MH_ERR_ARG;
+  }
+  const ModelEntry fresh;
+  float bbox[6];
+  memcpy(bbox, fresh.bbox, sizeof bbox);
+  for (int64_t r = 0; r < n_rows; ++r)
+    for (int k = 0; k < 3; ++k) {   // Pt::min / Pt::max (moped.cpp:124-125)
+      const float v = xyz[r * 3 + k];
+      if (v < bbox[k]) bbox[k] = v;
+      if (v > bbox[3 + k]) bbox[3 + k] = v;
+    }
+  // (the rows may be views of this set's own arrays: copy first)
+  const std::vector<float> d(desc, desc + n_rows * DIM), x(xyz, xyz + n_rows * 3);
+  put_model(s, name, bbox, d.data(), x.data(), (uint64_t)n_rows);
+  return MH_OK;
+}
+
+int mh_models_write_xml(const mh_model_set* s, int i, const char* path) {
+  if (!s || !path || i < 0 || i >= (int)s->models.size()) return MH_ERR_ARG;
+  const ModelEntry& m = s->models[i];
+  const float* D = s->D() + m.row_begin * DIM;
+  const float* X = s->X() + m.row_begin * 3;
+  FILE* f = fopen(path, "wb");
+  if (!f) return MH_ERR_ARG;
+  // sXML::print (sXML.hpp:146-170): a tab per level, properties in std::map order (desc, desc_type, p3d), "/>" without children
+  std::string out = "<Model name=\"" + m.name + "\">\n";
+  bool ok = true;
+  if (m.n_rows == 0) {
+    out += "\t<Points/>\n";
+  } else {
+    out += "\t<Points>\n";
+    for (uint64_t r = 0; r < m.n_rows; ++r) {
+      out += "\t\t<Point desc=\"";
+      for (int x = 0; x < DIM; ++x) {
+        if (x) out += ' ';
+        put_number(out, D[r * DIM + x]);
+      }
+      out += "\" desc_type=\"" + s->desc_type + "\" p3d=\"";
+      for (int k = 0; k < 3; ++k) {
+        if (k) out += ' ';
+        put_number(out, X[r * 3 + k]);
+      }
+      out += "\"/>\n";
+      if (out.size() >= (1u << 20)) {
+        ok &= fwrite(out.data(), 1, out.size(), f) == out.size();
+        out.clear();
+      }
+    }
+    out += "\t</Points>\n";
+  }
+  out += "</Model>\n";
+  ok &= fwrite(out.data(), 1, out.size(), f) == out.size();
+  ok &= fclose(f) == 0;
+  return ok ? MH_OK : MH_ERR_ARG;
 }
 
 int mh_models_add_xml(mh_model_set* s, const char* path) {

@@ -9,4 +9,5 @@ namespace std { using tr1::shared_ptr; }
 #include "POSE_RANSAC_P3P_HIP.hpp"
 #include "FILTER_PROJECTION_HIP.hpp"
 #include "FRAME_RESIDENT_HIP.hpp"
+#include "planar_models_hip.hpp"
 int main() { return 0; }

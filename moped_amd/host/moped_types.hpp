@@ -13,9 +13,34 @@
 #include <list>
 #include <map>
 #include <memory>
+#include <ostream>
 #include <sstream>
 #include <string>
 #include <vector>
+
+// include/sXML.hpp as its users see it (name, children, properties, operator[], print; :120-170), written for this
+// harness: what Moped::createPlanarModelsFromImages returns (moped.hpp:385) and createModels.cpp prints.  No parser --
+// the C ABI reads model files (mh_models_add_xml).
+class sXML {
+ public:
+  std::string name;
+  std::vector<sXML> children;
+  std::map<std::string, std::string> properties;
+  std::string& operator[](const std::string& key) { return properties[key]; }
+  void print(std::ostream& out, int level = 0) const {
+    const std::string tabs(level, '\t');
+    out << tabs << "<" << name;
+    for (std::map<std::string, std::string>::const_iterator it = properties.begin(); it != properties.end(); ++it)
+      out << " " << it->first << "=\"" << it->second << "\"";
+    if (children.empty()) {
+      out << "/>" << std::endl;
+      return;
+    }
+    out << ">" << std::endl;
+    for (size_t i = 0; i < children.size(); ++i) children[i].print(out, level + 1);
+    out << tabs << "</" << name << ">" << std::endl;
+  }
+};
 
 namespace MopedNS {
 

@@ -222,6 +222,73 @@ class FramePipeline:
         self._edit(capi.DB_REMOVE, i)
         del self.model_names[i]
 
+    # ---- a model taught from a device image: Moped::createPlanarModelsFromImages (moped.cpp:196-236) ----------
+    def _adopt_planar(self, op, i, desc, xyz):
+        for c in self.ctxs[1:]:
+            c.db_adopt(self.ctxs[0])
+        self.db.splice(op, i, desc, xyz)
+
+    def _warn_if_truncated(self, max_keypoints):
+        if self.ctxs[0].planar_truncated:   # MH_ERR_CAPACITY: the edit is made, from the first keypoints of the list
+            import warnings
+            warnings.warn(f"an image has more keypoints than max_keypoints={max_keypoints}: its model holds the first "
+                          f"{max_keypoints} of FEAT's list", RuntimeWarning, stacklevel=3)
+
+    def add_planar_model(self, image_dev: torch.Tensor, name=None, scale=None, z=None, roi=None, max_rows=0,
+                         max_keypoints: int = 4096, double_size: bool = True):
+        """image_dev [h, w] uint8 on this GPU -> a model of the resident store whose points are the image's keypoints:
+        at (u scale, v scale, 0) with `scale` (the reference's form), or on the plane at depth `z` in front of the
+        pipeline's camera K with `z`; exactly one of the two.  roi = (u0, v0, u1, v1) keeps the keypoints inside it,
+        max_rows the first so many.  FEAT, the selection and the splice run on slot 0's stream, the other slots adopt;
+        the rows do not leave the device for the edit (a host copy keeps `self.db` in step).  A known name replaces that
+        model.  An image with more keypoints than max_keypoints is taught from the first max_keypoints of FEAT's list and
+        a RuntimeWarning says so.  Returns (index, n_rows, bbox[6])."""
+        if self.world > 1 or self.exchange:
+            raise ValueError("a sharded model database cannot be edited in place: rebuild the pipeline")
+        spec = capi.make_planar_spec(scale=scale, z=z, K=self.K, roi=roi, max_rows=max_rows)
+        h, w = image_dev.shape
+        known = name is not None and name in self.model_names
+        i = self.model_names.index(name) if known else self.db.n_models
+        op = capi.DB_REPLACE if known else capi.DB_INSERT
+        n, bbox, desc, xyz = self.ctxs[0].db_splice_image(op, i, image_dev.data_ptr(), w, h, spec, double_size,
+                                                          max_keypoints, want_rows=True)
+        self._adopt_planar(op, i, desc, xyz)
+        self._warn_if_truncated(max_keypoints)
+        if not known:
+            self.model_names.append(name)
+        return i, n, bbox
+
+    def add_planar_models(self, images_dev, names, scale=None, z=None, roi=None, max_rows=0, max_keypoints: int = 4096,
+                          double_size: bool = True):
+        """The same for several images of one size: new names through ONE FEAT batch and one selection launch
+        (mh_db_splice_images), known names one by one.  Returns a list of (index, n_rows, bbox)."""
+        if self.world > 1 or self.exchange:
+            raise ValueError("a sharded model database cannot be edited in place: rebuild the pipeline")
+        if len(images_dev) != len(names):
+            raise ValueError("one name per image")
+        out = [None] * len(names)
+        fresh = [k for k, nm in enumerate(names) if nm is None or (nm not in self.model_names and nm not in names[:k])]
+        for b in range(0, len(fresh), capi.MAX_BATCH):
+            part = fresh[b:b + capi.MAX_BATCH]
+            spec = capi.make_planar_spec(scale=scale, z=z, K=self.K, roi=roi, max_rows=max_rows)
+            h, w = images_dev[part[0]].shape
+            if any(tuple(images_dev[k].shape) != (h, w) for k in part):
+                raise ValueError("the images of one call have one size")
+            first = self.db.n_models
+            n, bbox, desc, xyz = self.ctxs[0].db_splice_images(first, [images_dev[k].data_ptr() for k in part], w, h, spec,
+                                                               double_size, max_keypoints, want_rows=True)
+            for c in self.ctxs[1:]:
+                c.db_adopt(self.ctxs[0])
+            self._warn_if_truncated(max_keypoints)
+            for j, k in enumerate(part):
+                self.db.splice(capi.DB_INSERT, first + j, desc[j], xyz[j])
+                self.model_names.append(names[k])
+                out[k] = (first + j, int(n[j]), bbox[j])
+        for k, nm in enumerate(names):   # known names (or a name given twice) replace, as addModel does
+            if k not in fresh:
+                out[k] = self.add_planar_model(images_dev[k], nm, scale, z, roi, max_rows, max_keypoints, double_size)
+        return out
+
     # ---- single frame in slot i ------------------------------------------------------
     def enqueue(self, slot: int, q_desc: torch.Tensor, q_uv: torch.Tensor, seed: int = 1,
                 after: "torch.cuda.Stream | None" = None):
