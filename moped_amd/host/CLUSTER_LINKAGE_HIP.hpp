@@ -9,7 +9,7 @@
 // map (:577-593); writes clusters[model] in the reference's cluster and member order; sets
 // oldClusters when the step is named "CLUSTER" (:703).
 #pragma once
-#include "hip_session.hpp"
+#include "hip_frame3d.hpp"
 
 namespace MopedNS {
 
@@ -44,16 +44,8 @@ class CLUSTER_LINKAGE_HIP : public MopedAlg {
   void process(FrameData& frameData) {
     frameData.clusters.resize(models->size());
     mh_ctx* ctx = HipSession::get();
-    Image* depthmap = 0;
-    Image* distanceMap = 0;
-    for (size_t i = 0; i < frameData.images.size(); ++i)
-      if (frameData.images[i]->imageType == IMAGE_TYPE_DEPTH_MAP) { depthmap = frameData.images[i].get(); break; }
-    if (!depthmap) return;
-    for (size_t i = 0; i < frameData.images.size(); ++i)
-      if (frameData.images[i]->imageType == IMAGE_TYPE_PROB_MAP && frameData.images[i]->name == depthmap->name + ".distance") {
-        distanceMap = frameData.images[i].get();
-        break;
-      }
+    Image *depthmap, *distanceMap;   // the FIRST depth map of the frame: the reference's loop breaks (:577-593)
+    if (!hipFindDepthMaps(frameData, true, depthmap, distanceMap)) return;
     // (uploaded by this step only if no depth step of this frame has done so: HipDepthMaps, hip_session.hpp)
     if (!HipDepthMaps::get().ensure(ctx, depthmap, distanceMap)) {
       HipSession::warn("mh_frame_set_depth_image_host");

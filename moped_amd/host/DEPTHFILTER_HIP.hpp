@@ -11,7 +11,7 @@
 // uploaded once for the frame's depth steps (HipDepthMaps).  Coordinates outside the map count for the nearest patch (the
 // reference indexes out of bounds there).
 #pragma once
-#include "hip_session.hpp"
+#include "hip_frame3d.hpp"
 
 namespace MopedNS {
 
@@ -35,16 +35,10 @@ class DEPTHFILTER_HIP : public MopedAlg {
   void process(FrameData& frameData) {
     if (frameData.images.size() < 2) return;   // :117-119
     if (ToFilter != 1 && ToFilter != 2) return;
-    Image* depthmap = 0;                        // the LAST depth map of the frame (:122-127 has no break)
-    Image* distanceMap = 0;
-    for (size_t i = 0; i < frameData.images.size(); ++i)
-      if (frameData.images[i]->imageType == IMAGE_TYPE_DEPTH_MAP) depthmap = frameData.images[i].get();
-    if (!depthmap) return;
-    for (size_t i = 0; i < frameData.images.size(); ++i)
-      if (frameData.images[i]->imageType == IMAGE_TYPE_PROB_MAP && frameData.images[i]->name == depthmap->name + ".distance") {
-        distanceMap = frameData.images[i].get();   // (not read here: it rides along for the frame's later depth steps)
-        break;
-      }
+    // the LAST depth map of the frame (:122-127 has no break); its distance map is not read here, it rides along for
+    // the frame's later depth steps
+    Image *depthmap, *distanceMap;
+    if (!hipFindDepthMaps(frameData, false, depthmap, distanceMap)) return;
     // the step's lists: one group (the features) or one per model (its matches)
     vector<float> uv;
     vector<int32_t> off(1, 0);

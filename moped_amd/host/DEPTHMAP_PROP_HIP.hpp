@@ -6,7 +6,7 @@
 // coord3D, depth, depthValid, and fillDistance from the map's ".distance" map or -1 (:98-113, 119-132).  The lookups run
 // on the device copy of the map the frame's depth steps share (mh_depth_prop; HipDepthMaps), one call for all models.
 #pragma once
-#include "hip_session.hpp"
+#include "hip_frame3d.hpp"
 
 namespace MopedNS {
 
@@ -20,19 +20,11 @@ class DEPTHMAP_PROP_HIP : public MopedAlg {
   void process(FrameData& frameData) {
     if (frameData.images.size() < 2) return;   // :54-58
     Image* gray = 0;
-    Image* depthmap = 0;
-    Image* distanceMap = 0;
-    for (size_t i = 0; i < frameData.images.size(); ++i) {   // the last of each kind (:62-72)
+    Image *depthmap, *distanceMap;
+    for (size_t i = 0; i < frameData.images.size(); ++i)   // the last of each kind (:62-72)
       if (frameData.images[i]->imageType == IMAGE_TYPE_GRAY_IMAGE) gray = frameData.images[i].get();
-      else if (frameData.images[i]->imageType == IMAGE_TYPE_DEPTH_MAP) depthmap = frameData.images[i].get();
-    }
-    if (!gray || !depthmap) return;                                                   // :75-77
+    if (!hipFindDepthMaps(frameData, false, depthmap, distanceMap) || !gray) return;   // :75-77
     if (gray->width != depthmap->width || gray->height != depthmap->height) return;   // :80-83
-    for (size_t i = 0; i < frameData.images.size(); ++i)
-      if (frameData.images[i]->imageType == IMAGE_TYPE_PROB_MAP && frameData.images[i]->name == depthmap->name + ".distance") {
-        distanceMap = frameData.images[i].get();
-        break;
-      }
     vector<float> uv;
     for (size_t m = 0; m < frameData.matches.size(); ++m)
       for (size_t k = 0; k < frameData.matches[m].size(); ++k) {

@@ -21,7 +21,7 @@
 #include <algorithm>
 #include <utility>
 
-#include "hip_session.hpp"
+#include "hip_frame3d.hpp"
 
 namespace MopedNS {
 
@@ -124,21 +124,13 @@ class FILTER_PROJECTION_DEPTH_HIP : public MopedAlg {
     if (matches.size() < models->size()) return;      // the reference's sanity check (:150-152)
 
     // the depth map and its fill-distance image (:155-173)
-    Image* depthmap = 0;
-    Image* distanceMap = 0;
-    for (size_t i = 0; i < frameData.images.size(); ++i)
-      if (frameData.images[i]->imageType == IMAGE_TYPE_DEPTH_MAP) depthmap = frameData.images[i].get();
-    if (!depthmap || depthmap->width <= 0 || depthmap->height <= 0 ||
+    Image *depthmap, *distanceMap;
+    if (!hipFindDepthMaps(frameData, false, depthmap, distanceMap) || depthmap->width <= 0 || depthmap->height <= 0 ||
         depthmap->data.size() < (size_t)depthmap->width * depthmap->height * 4 * sizeof(Float)) {
       std::clog << "[moped_hip] FILTER_PROJECTION_DEPTH_HIP: the frame has no depth map: the step is not capable" << std::endl;
       capable = false;
       return;
     }
-    for (size_t i = 0; i < frameData.images.size(); ++i)
-      if (frameData.images[i]->imageType == IMAGE_TYPE_PROB_MAP && frameData.images[i]->name == depthmap->name + ".distance") {
-        distanceMap = frameData.images[i].get();
-        break;
-      }
     if (distanceMap && distanceMap->data.size() < (size_t)depthmap->width * depthmap->height * sizeof(Float)) distanceMap = 0;
 
     const int nm = (int)models->size();
@@ -157,10 +149,7 @@ class FILTER_PROJECTION_DEPTH_HIP : public MopedAlg {
       HipSession::warn("mh_frame_set_depth_image_host");
       return;
     }
-    mh_cam depthCam;
-    for (int j = 0; j < 4; ++j) depthCam.K[j] = depthmap->intrinsicLinearCalibration[j];
-    for (int j = 0; j < 4; ++j) depthCam.cam[j] = depthmap->cameraPose.rotation[j];
-    for (int j = 0; j < 3; ++j) depthCam.cam[4 + j] = depthmap->cameraPose.translation[j];
+    const mh_cam depthCam = hipCamOf(*depthmap);
 
     vector<mh_corr> corr;
     vector<int32_t> off(nm + 1, 0);

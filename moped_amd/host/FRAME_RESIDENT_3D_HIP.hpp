@@ -71,22 +71,8 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
     lk.sigma3d = (float)Sigma3D;
     lk.linkage_type = LinkageType;
     mh_frame_default_params(&prm);
-    prm.pose1.n_hypotheses = NHyp1;
-    prm.pose1.max_objects_per_cluster = MaxObj1;
-    prm.pose1.n_pts_align = NPtsAlign1;
-    prm.pose1.min_n_pts_object = MinNPts1;
-    prm.pose1.error_threshold = (float)ErrorThreshold1;
-    prm.f1_min_points = MinPoints1;
-    prm.f1_feature_distance = (float)FeatureDistance1;
-    prm.f1_min_score = (float)MinScore1;
-    prm.pose2.n_hypotheses = NHyp2;
-    prm.pose2.max_objects_per_cluster = MaxObj2;
-    prm.pose2.n_pts_align = NPtsAlign2;
-    prm.pose2.min_n_pts_object = MinNPts2;
-    prm.pose2.error_threshold = (float)ErrorThreshold2;
-    prm.f2_min_points = MinPoints2;
-    prm.f2_feature_distance = (float)FeatureDistance2;
-    prm.f2_min_score = (float)MinScore2;
+    hipStageParams(prm, 1, NHyp1, MaxObj1, NPtsAlign1, MinNPts1, ErrorThreshold1, MinPoints1, FeatureDistance1, MinScore1);
+    hipStageParams(prm, 2, NHyp2, MaxObj2, NPtsAlign2, MinNPts2, ErrorThreshold2, MinPoints2, FeatureDistance2, MinScore2);
     prm.run_stage2 = 1;
     for (int j = 0; j < 4; ++j) lastCounts[j] = 0;
     capable = (DescriptorSize == MH_DESC_DIM) && PatchSize > 0 && LinkageType >= 0 && LinkageType <= 2 && FillScale >= -1 &&
@@ -125,13 +111,12 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
     if (configUpdated) Update(frameData);
     ++frameCounter;
     if (am.skipCalculation) return;
-    SP_Image gray, depthmap, distanceMap;
+    Image* gray = 0;   // the FIRST gray image of the frame
+    Image *depthmap, *distanceMap;
     int grayIdx = -1;
-    for (size_t i = 0; i < frameData.images.size(); ++i) {
-      if (frameData.images[i]->imageType == IMAGE_TYPE_GRAY_IMAGE && !gray) { gray = frameData.images[i]; grayIdx = (int)i; }
-      if (frameData.images[i]->imageType == IMAGE_TYPE_DEPTH_MAP) depthmap = frameData.images[i];
-    }
-    if (!gray || !depthmap) return;
+    for (size_t i = 0; i < frameData.images.size() && !gray; ++i)
+      if (frameData.images[i]->imageType == IMAGE_TYPE_GRAY_IMAGE) { gray = frameData.images[i].get(); grayIdx = (int)i; }
+    if (!hipFindDepthMaps(frameData, false, depthmap, distanceMap) || !gray) return;
     const int w = gray->width, h = gray->height;
     const size_t px = (size_t)(w > 0 ? w : 0) * (size_t)(h > 0 ? h : 0);
     if (px == 0 || depthmap->width != w || depthmap->height != h || gray->data.size() < px ||
@@ -139,20 +124,17 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
       std::clog << "[moped_hip] FRAME_RESIDENT_3D_HIP: the gray image and the depth map must have one size: frame skipped" << std::endl;
       return;
     }
-    for (size_t i = 0; i < frameData.images.size(); ++i)
-      if (frameData.images[i]->imageType == IMAGE_TYPE_PROB_MAP && frameData.images[i]->name == depthmap->name + ".distance" &&
-          frameData.images[i]->data.size() >= px * sizeof(Float)) {
-        distanceMap = frameData.images[i];
-        break;
-      }
+    if (distanceMap && distanceMap->data.size() < px * sizeof(Float)) distanceMap = 0;
     const bool fill = FillScale != 0;
+    SP_Image filled;
     if (fill) {   // DEPTH_FILL_EXACT_CPU::process appends the map's distance map to the frame
-      distanceMap = SP_Image(new Image);
-      distanceMap->imageType = IMAGE_TYPE_PROB_MAP;
-      distanceMap->width = w;
-      distanceMap->height = h;
-      distanceMap->name = depthmap->name + ".distance";
-      distanceMap->data.resize(px * sizeof(Float));
+      filled = SP_Image(new Image);
+      filled->imageType = IMAGE_TYPE_PROB_MAP;
+      filled->width = w;
+      filled->height = h;
+      filled->name = depthmap->name + ".distance";
+      filled->data.resize(px * sizeof(Float));
+      distanceMap = filled.get();
     }
     mh_ctx* ctx = HipSession::get();
     HipHandover::get().drop();
@@ -171,10 +153,7 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
     rules.cauchy_scale = 0.1f;
     if (mh_frame_set_depth_rules(ctx, &rules, K) != MH_OK) { HipSession::warn("mh_frame_set_depth_rules"); return; }
     if (mh_frame_set_cluster_linkage(ctx, &lk) != MH_OK) { HipSession::warn("mh_frame_set_cluster_linkage"); return; }
-    mh_cam cam;
-    for (int j = 0; j < 4; ++j) cam.K[j] = gray->intrinsicLinearCalibration[j];
-    for (int j = 0; j < 4; ++j) cam.cam[j] = gray->cameraPose.rotation[j];
-    for (int j = 0; j < 3; ++j) cam.cam[4 + j] = gray->cameraPose.translation[j];
+    const mh_cam cam = hipCamOf(*gray);
     vector<mh_object> out(256);
     int32_t n = 0;
     int32_t* const counts = lastCounts;
@@ -203,7 +182,7 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
       }
     } restore = {ctx, fillModeBefore};
     if (rc != MH_OK) { HipSession::warn("mh_frame_run_kinect_host"); return; }
-    if (fill) frameData.images.push_back(distanceMap);
+    if (fill) frameData.images.push_back(filled);
     // frameData.matches as the steps up to DEPTHPROP leave it, from the device's lists
     frameData.matches.clear();
     frameData.matches.resize(models->size());
@@ -237,15 +216,9 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
         }
       }
     }
-    for (int o = 0; o < n && o < (int)out.size(); ++o) {
-      if (out[o].model < 0 || out[o].model >= (int)models->size()) continue;
-      SP_Object obj(new Object);
-      frameData.objects->push_back(obj);
-      obj->pose.rotation.init(out[o].pose[0], out[o].pose[1], out[o].pose[2], out[o].pose[3]);
-      obj->pose.translation.init(out[o].pose[4], out[o].pose[5], out[o].pose[6]);
-      obj->model = (*models)[out[o].model];
-      obj->score = out[o].score;
-    }
+    for (int o = 0; o < n && o < (int)out.size(); ++o)
+      if (out[o].model >= 0 && out[o].model < (int)models->size())
+        hipAppendObject(frameData, (*models)[out[o].model], out[o].pose, out[o].score);
   }
 };
 

@@ -27,74 +27,29 @@ class FRAME_RESIDENT_HIP : public MopedAlg {
   int DescriptorSize;
   string DescriptorType;
   mh_frame_params prm;
-  bool skipCalculation;
   int IncrementalModels;   // config key, default 0: Update() edits the resident database instead of uploading every model again
+  HipModelTable db;        // what Update() leaves: the resident models and skipCalculation
   unsigned long frameCounter;
   int FillMatches;
   // the frame's descriptors / keypoints / image indices as the C ABI takes them: ONE page-locked block (mh_host_alloc),
   // grown when a frame has more features -- packing into pageable vectors cost the frame two staged 1.5 MB copies
-  void* pinBlock;
-  size_t pinBytes;
+  HipPinnedBlock pin;
   float *packed, *uv;
   int32_t* imageOf;
   vector<int32_t> matchQuery, matchModel;
 
   bool pinFor(mh_ctx* ctx, int Q) {
-    const size_t need = (size_t)Q * (MH_DESC_DIM + 2) * sizeof(float) + (size_t)Q * sizeof(int32_t);
-    if (need > pinBytes) {
-      if (pinBlock) mh_host_free(ctx, pinBlock);
-      pinBlock = NULL;
-      pinBytes = 0;
-      const size_t want = need + need / 4;
-      if (mh_host_alloc(ctx, want, &pinBlock) != MH_OK) return false;
-      pinBytes = want;
-    }
-    const size_t cap = pinBytes / ((MH_DESC_DIM + 2) * sizeof(float) + sizeof(int32_t));
-    packed = (float*)pinBlock;
+    const size_t row = (MH_DESC_DIM + 2) * sizeof(float) + sizeof(int32_t);
+    if (!pin.ensure(ctx, (size_t)Q * row)) return false;
+    const size_t cap = pin.bytes() / row;
+    packed = (float*)pin.data();
     uv = packed + cap * MH_DESC_DIM;
     imageOf = (int32_t*)(uv + cap * 2);
     return true;
   }
 
   void Update() {
-    skipCalculation = true;
-    mh_ctx* ctx = HipSession::get();
-    size_t n = 0;
-    for (size_t m = 0; m < models->size(); ++m) n += (*models)[m]->IPs[DescriptorType].size();
-    // IncrementalModels: the resident database is edited instead (HipResidentModels, hip_session.hpp)
-    if (IncrementalModels && HipResidentModels::get().update(ctx, *models, DescriptorType)) {
-      skipCalculation = n <= 1;
-      configUpdated = false;
-      return;
-    }
-    vector<float> desc(n * MH_DESC_DIM), xyz(n * 3);
-    vector<int32_t> owner(n);
-    size_t x = 0;
-    for (size_t m = 0; m < models->size(); ++m) {
-      vector<Model::IP>& ips = (*models)[m]->IPs[DescriptorType];
-      for (size_t f = 0; f < ips.size(); ++f, ++x) {
-        owner[x] = (int32_t)m;
-        for (int i = 0; i < MH_DESC_DIM; ++i) desc[x * MH_DESC_DIM + i] = ips[f].descriptor[i];
-        for (int i = 0; i < 3; ++i) xyz[x * 3 + i] = ips[f].coord3D[i];
-      }
-    }
-    if (n > 1) {
-      // Update() normalises the model descriptors in place (MATCH_ANN_CPU.hpp:94)
-      if (mh_normalize(ctx, &desc[0], (int)n) != MH_OK) { HipSession::warn("mh_normalize"); return; }
-      x = 0;
-      for (size_t m = 0; m < models->size(); ++m) {
-        vector<Model::IP>& ips = (*models)[m]->IPs[DescriptorType];
-        for (size_t f = 0; f < ips.size(); ++f, ++x)
-          for (int i = 0; i < MH_DESC_DIM; ++i) ips[f].descriptor[i] = desc[x * MH_DESC_DIM + i];
-      }
-      if (mh_db_upload(ctx, &desc[0], &owner[0], &xyz[0], (int)n, (int)models->size(), 0) != MH_OK) {
-        HipSession::warn("mh_db_upload");
-        return;
-      }
-      skipCalculation = false;
-      if (IncrementalModels) HipResidentModels::get().record(*models, DescriptorType);
-    }
-    configUpdated = false;
+    if (db.update(HipSession::get(), *models, DescriptorType, IncrementalModels)) configUpdated = false;
   }
 
  public:
@@ -104,30 +59,16 @@ class FRAME_RESIDENT_HIP : public MopedAlg {
                      int MinPoints1, Float FeatureDistance1, Float MinScore1,                                // FILTER
                      int NHyp2, int MaxObj2, int NPtsAlign2, int MinNPts2, Float ErrorThreshold2,            // POSE2
                      int MinPoints2, Float FeatureDistance2, Float MinScore2)                                // FILTER2
-      : DescriptorSize(DescriptorSize), DescriptorType(DescriptorType), skipCalculation(true), IncrementalModels(0), frameCounter(0), FillMatches(0),
-        pinBlock(NULL), pinBytes(0), packed(NULL), uv(NULL), imageOf(NULL) {
+      : DescriptorSize(DescriptorSize), DescriptorType(DescriptorType), IncrementalModels(0), frameCounter(0), FillMatches(0),
+        packed(NULL), uv(NULL), imageOf(NULL) {
     mh_frame_default_params(&prm);
     prm.ratio = (float)Ratio;
     prm.ms_radius = (float)Radius;
     prm.ms_merge = (float)Merge;
     prm.ms_min_pts = MinPts;
     prm.ms_max_iter = MaxIterations;
-    prm.pose1.n_hypotheses = NHyp1;
-    prm.pose1.max_objects_per_cluster = MaxObj1;
-    prm.pose1.n_pts_align = NPtsAlign1;
-    prm.pose1.min_n_pts_object = MinNPts1;
-    prm.pose1.error_threshold = (float)ErrorThreshold1;
-    prm.f1_min_points = MinPoints1;
-    prm.f1_feature_distance = (float)FeatureDistance1;
-    prm.f1_min_score = (float)MinScore1;
-    prm.pose2.n_hypotheses = NHyp2;
-    prm.pose2.max_objects_per_cluster = MaxObj2;
-    prm.pose2.n_pts_align = NPtsAlign2;
-    prm.pose2.min_n_pts_object = MinNPts2;
-    prm.pose2.error_threshold = (float)ErrorThreshold2;
-    prm.f2_min_points = MinPoints2;
-    prm.f2_feature_distance = (float)FeatureDistance2;
-    prm.f2_min_score = (float)MinScore2;
+    hipStageParams(prm, 1, NHyp1, MaxObj1, NPtsAlign1, MinNPts1, ErrorThreshold1, MinPoints1, FeatureDistance1, MinScore1);
+    hipStageParams(prm, 2, NHyp2, MaxObj2, NPtsAlign2, MinNPts2, ErrorThreshold2, MinPoints2, FeatureDistance2, MinScore2);
     prm.run_stage2 = 1;
     capable = (DescriptorSize == MH_DESC_DIM) && HipSession::get() != 0;
   }
@@ -168,37 +109,23 @@ class FRAME_RESIDENT_HIP : public MopedAlg {
   void process(FrameData& frameData) {
     if (configUpdated) Update();
     ++frameCounter;
-    if (skipCalculation) return;
+    if (db.skipCalculation) return;
     vector<FrameData::DetectedFeature>& feats = frameData.detectedFeatures[DescriptorType];
     if (feats.empty()) return;
     frameData.matches.resize(models->size());
     const int Q = (int)feats.size();
-    // the cameras the features refer to, renumbered in image order (as HipCameraTable does for matches)
-    vector<int> local(frameData.images.size(), -1);
-    for (int i = 0; i < Q; ++i) {
-      const int im = feats[i].imageIdx;
-      if (im < 0 || im >= (int)local.size()) {
+    // the cameras the features refer to, renumbered in image order
+    const HipCameraTable table(frameData, feats);
+    if (!table.ok) {
+      if (table.cams.empty())
         std::clog << "[moped_hip] FRAME_RESIDENT_HIP: a feature refers to an image outside FrameData::images: frame skipped" << std::endl;
-        return;
-      }
-      local[im] = 0;
-    }
-    vector<mh_cam> cams;
-    for (size_t i = 0; i < local.size(); ++i) {
-      if (local[i] < 0) continue;
-      local[i] = (int)cams.size();
-      const Image& im = *frameData.images[i];
-      mh_cam c;
-      for (int j = 0; j < 4; ++j) c.K[j] = im.intrinsicLinearCalibration[j];
-      for (int j = 0; j < 4; ++j) c.cam[j] = im.cameraPose.rotation[j];
-      for (int j = 0; j < 3; ++j) c.cam[4 + j] = im.cameraPose.translation[j];
-      cams.push_back(c);
-    }
-    if (cams.empty() || (int)cams.size() > MH_MAX_IMAGES) {
-      std::clog << "[moped_hip] FRAME_RESIDENT_HIP: the frame's features refer to " << cams.size() << " images (1.."
-                << MH_MAX_IMAGES << " supported): frame skipped" << std::endl;
+      else
+        std::clog << "[moped_hip] FRAME_RESIDENT_HIP: the frame's features refer to " << table.cams.size() << " images (1.."
+                  << MH_MAX_IMAGES << " supported): frame skipped" << std::endl;
       return;
     }
+    const vector<mh_cam>& cams = table.cams;
+    const vector<int>& local = table.local;
     mh_ctx* ctx = HipSession::get();
     if (!pinFor(ctx, Q)) { HipSession::warn("mh_host_alloc"); return; }
     // (3 000 features = 3 000 separately allocated descriptors: ~0.1 ms on one thread -- the reference's steps use OpenMP
@@ -247,15 +174,9 @@ class FRAME_RESIDENT_HIP : public MopedAlg {
         }
       }
     }
-    for (int o = 0; o < n && o < (int)out.size(); ++o) {
-      if (out[o].model < 0 || out[o].model >= (int)models->size()) continue;
-      SP_Object obj(new Object);
-      frameData.objects->push_back(obj);
-      obj->pose.rotation.init(out[o].pose[0], out[o].pose[1], out[o].pose[2], out[o].pose[3]);
-      obj->pose.translation.init(out[o].pose[4], out[o].pose[5], out[o].pose[6]);
-      obj->model = (*models)[out[o].model];
-      obj->score = out[o].score;
-    }
+    for (int o = 0; o < n && o < (int)out.size(); ++o)
+      if (out[o].model >= 0 && out[o].model < (int)models->size())
+        hipAppendObject(frameData, (*models)[out[o].model], out[o].pose, out[o].score);
   }
 };
 

@@ -15,27 +15,22 @@
 #pragma once
 #include <cmath>
 
-#include "hip_session.hpp"
+#include "hip_frame3d.hpp"
 
 namespace MopedNS {
 
 // What Update() of moped3d's MATCH step leaves behind (MATCH_ADAPTIVE_FLANN_CPU.hpp:100-177), shared by the step plugin
-// below and by FRAME_RESIDENT_3D_HIP: the models' descriptors normalised in place and resident on the device (uploaded, or
-// edited with IncrementalModels), the row -> model / model point tables, and per model the four control points of its
-// ratio curve -- the rows of mh_frame_set_depth_rules' ratio_table.
-struct HipAdaptiveModels {
+// below and by FRAME_RESIDENT_3D_HIP: the resident models with their tables (HipModelTable, hip_session.hpp) and per
+// model the four control points of its ratio curve -- the rows of mh_frame_set_depth_rules' ratio_table.
+struct HipAdaptiveModels : HipModelTable {
   Float MinRatioMin, MinRatioMax, MaxRatioMin, MaxRatioMax;
   Float DimensionPeak, DimensionFade;
-  bool skipCalculation;
-  vector<int> correspModel;
-  vector<Pt<3>*> correspFeat;
-  vector<float> packed;
   vector<float> controlPoints;   // per model: maxRatioDepth, minRatioDepth, ratioLow, ratioHigh
 
   HipAdaptiveModels(Float MinRatioMin, Float MinRatioMax, Float MaxRatioMin, Float MaxRatioMax, Float DimensionPeak,
                     Float DimensionFade)
       : MinRatioMin(MinRatioMin), MinRatioMax(MinRatioMax), MaxRatioMin(MaxRatioMin), MaxRatioMax(MaxRatioMax),
-        DimensionPeak(DimensionPeak), DimensionFade(DimensionFade), skipCalculation(true) {}
+        DimensionPeak(DimensionPeak), DimensionFade(DimensionFade) {}
 
   // sqrt of the image area the largest face of the (centred) bounding box covers at `depth` (:262-312)
   static Float projectedLength(const Pt<3> box[2], const Pt<4>& k, Float depth) {
@@ -77,46 +72,7 @@ struct HipAdaptiveModels {
 
   // false: a call failed (skipCalculation stays true, the caller leaves configUpdated set and tries again next frame)
   bool update(vector<SP_Model>* models, const string& DescriptorType, int IncrementalModels, FrameData& frameData) {
-    skipCalculation = true;
-    mh_ctx* ctx = HipSession::get();
-    size_t n = 0;
-    for (size_t m = 0; m < models->size(); ++m) n += (*models)[m]->IPs[DescriptorType].size();
-    correspModel.resize(n);
-    correspFeat.resize(n);
-    // IncrementalModels: the resident database is edited (HipResidentModels, hip_session.hpp), only the tables are rebuilt
-    const bool edited = IncrementalModels && HipResidentModels::get().update(ctx, *models, DescriptorType);
-    if (!edited) packed.resize(n * MH_DESC_DIM);
-    vector<float> xyz(edited ? 0 : n * 3);
-    vector<int32_t> owner(edited ? 0 : n);
-    size_t x = 0;
-    for (size_t m = 0; m < models->size(); ++m) {
-      vector<Model::IP>& ips = (*models)[m]->IPs[DescriptorType];
-      for (size_t f = 0; f < ips.size(); ++f, ++x) {
-        correspModel[x] = (int)m;
-        correspFeat[x] = &ips[f].coord3D;
-        if (edited) continue;
-        owner[x] = (int32_t)m;
-        for (int i = 0; i < MH_DESC_DIM; ++i) packed[x * MH_DESC_DIM + i] = ips[f].descriptor[i];
-        for (int i = 0; i < 3; ++i) xyz[x * 3 + i] = ips[f].coord3D[i];
-      }
-    }
-    if (edited) {
-      skipCalculation = n <= 1;
-    } else if (n > 1) {
-      if (mh_normalize(ctx, &packed[0], (int)n) != MH_OK) { HipSession::warn("mh_normalize"); return false; }
-      x = 0;
-      for (size_t m = 0; m < models->size(); ++m) {       // Update() normalises the model descriptors in place (:122)
-        vector<Model::IP>& ips = (*models)[m]->IPs[DescriptorType];
-        for (size_t f = 0; f < ips.size(); ++f, ++x)
-          for (int i = 0; i < MH_DESC_DIM; ++i) ips[f].descriptor[i] = packed[x * MH_DESC_DIM + i];
-      }
-      if (mh_db_upload(ctx, &packed[0], &owner[0], &xyz[0], (int)n, (int)models->size(), 0) != MH_OK) {
-        HipSession::warn("mh_db_upload");
-        return false;
-      }
-      skipCalculation = false;
-      if (IncrementalModels) HipResidentModels::get().record(*models, DescriptorType);
-    }
+    if (!HipModelTable::update(HipSession::get(), *models, DescriptorType, IncrementalModels)) return false;
     // intrinsics of the gray image (:146-153)
     Pt<4> k;
     k.init(0.f, 0.f, 0.f, 0.f);
@@ -143,16 +99,12 @@ class MATCH_ADAPTIVE_BRUTE_HIP : public MopedAlg {
   Float MaximumDepth, DefaultDepth, CauchyScale;
   int IncrementalModels;   // config key, default 0: Update() edits the resident database instead of uploading every model again
   HipAdaptiveModels am;
-  bool& skipCalculation;
-  vector<int>& correspModel;
-  vector<Pt<3>*>& correspFeat;
-  vector<float>& packed;
-  vector<float>& controlPoints;
+  vector<float> packed;    // the frame's descriptors as mh_normalize_match takes them
 
   Float getRatio(Float depth, int m) const {             // :193-215
     if (depth > MaximumDepth) return 0;
-    const Float maxRatioDepth = controlPoints[4 * m], minRatioDepth = controlPoints[4 * m + 1],
-                ratioLow = controlPoints[4 * m + 2], ratioHigh = controlPoints[4 * m + 3];
+    const Float maxRatioDepth = am.controlPoints[4 * m], minRatioDepth = am.controlPoints[4 * m + 1],
+                ratioLow = am.controlPoints[4 * m + 2], ratioHigh = am.controlPoints[4 * m + 3];
     if (depth < maxRatioDepth) return ratioLow + (depth / maxRatioDepth) * (ratioHigh - ratioLow);
     if (depth < minRatioDepth) return ratioHigh;
     if (depth < minRatioDepth * 2) return ((minRatioDepth * 2 - depth) / minRatioDepth) * ratioHigh;
@@ -170,14 +122,12 @@ class MATCH_ADAPTIVE_BRUTE_HIP : public MopedAlg {
   MATCH_ADAPTIVE_BRUTE_HIP(int DescriptorSize, string DescriptorType, Float MinRatioMin, Float MinRatioMax,
                            Float MaxRatioMin, Float MaxRatioMax, Float DimensionPeak, Float DimensionFade)
       : DescriptorSize(DescriptorSize), DescriptorType(DescriptorType), MaximumDepth(4.0), DefaultDepth(1.0), CauchyScale(0.1),
-        IncrementalModels(0), am(MinRatioMin, MinRatioMax, MaxRatioMin, MaxRatioMax, DimensionPeak, DimensionFade),
-        skipCalculation(am.skipCalculation), correspModel(am.correspModel), correspFeat(am.correspFeat), packed(am.packed),
-        controlPoints(am.controlPoints) {
+        IncrementalModels(0), am(MinRatioMin, MinRatioMax, MaxRatioMin, MaxRatioMax, DimensionPeak, DimensionFade) {
     capable = (DescriptorSize == MH_DESC_DIM) && HipSession::get() != 0;
   }
 
   // what mh_frame_set_depth_rules takes as ratio_table (valid after the first frame)
-  const vector<float>& table() const { return controlPoints; }
+  const vector<float>& table() const { return am.controlPoints; }
 
   void getConfig(map<string, string>& config) const {
     hipGetConfig(config, _stepName, _alg, "MATCH_ADAPTIVE_BRUTE_HIP", "MinRatioMin", am.MinRatioMin);
@@ -195,20 +145,12 @@ class MATCH_ADAPTIVE_BRUTE_HIP : public MopedAlg {
 
   void process(FrameData& frameData) {
     if (configUpdated) Update(frameData);
-    if (skipCalculation) return;
+    if (am.skipCalculation) return;
     vector<FrameData::DetectedFeature>& corresp = frameData.detectedFeatures[DescriptorType];
     if (corresp.empty()) return;
     // the depth map and its ".distance" map (:425-441)
-    Image* depthmap = 0;
-    Image* distanceMap = 0;
-    for (size_t i = 0; i < frameData.images.size(); ++i)
-      if (frameData.images[i]->imageType == IMAGE_TYPE_DEPTH_MAP) depthmap = frameData.images[i].get();
-    if (!depthmap) return;
-    for (size_t i = 0; i < frameData.images.size(); ++i)
-      if (frameData.images[i]->imageType == IMAGE_TYPE_PROB_MAP && frameData.images[i]->name == depthmap->name + ".distance") {
-        distanceMap = frameData.images[i].get();
-        break;
-      }
+    Image *depthmap, *distanceMap;
+    if (!hipFindDepthMaps(frameData, false, depthmap, distanceMap)) return;
     vector<vector<FrameData::Match> >& matches = frameData.matches;
     matches.resize(models->size());
     const int Q = (int)corresp.size();
@@ -229,7 +171,7 @@ class MATCH_ADAPTIVE_BRUTE_HIP : public MopedAlg {
       y = y < 0 ? 0 : (y >= depthmap->height ? depthmap->height - 1 : y);
       const Float depth = depthmap->getDepth(x, y);
       if (depth > MaximumDepth) continue;                                   // :457-460
-      const int m = correspModel[nn[i]];
+      const int m = am.correspModel[nn[i]];
       const Float weightTerm = (distanceMap ? distanceMap->getProb(x, y) : (Float)0) / CauchyScale;   // :362-364
       const Float weight = 1.0 / (1.0 + weightTerm * weightTerm);
       const Float Ratio = weight * getRatio(depth, m) + (1.0 - weight) * getRatio(DefaultDepth, m);
@@ -239,7 +181,7 @@ class MATCH_ADAPTIVE_BRUTE_HIP : public MopedAlg {
         FrameData::Match& match = matches[m].back();
         match.imageIdx = corresp[i].imageIdx;
         match.coord2D = corresp[i].coord2D;
-        match.coord3D = *correspFeat[nn[i]];
+        match.coord3D = *am.correspFeat[nn[i]];
       }
     }
   }

@@ -26,29 +26,18 @@ class MATCH_BRUTE_HIP : public MopedAlg {
   int DescriptorSize;
   string DescriptorType;
   Float Ratio;
-  bool skipCalculation;
   int IncrementalModels;   // config key, default 0: Update() edits the resident database instead of uploading every model again
-  vector<int> correspModel;
-  vector<Pt<3>*> correspFeat;
-  vector<float> packed;
+  HipModelTable db;        // what Update() leaves: the resident models, skipCalculation, row -> model / model point
+  vector<float> packed;    // process()'s pageable buffer when no page-locked block is to be had
   // the frame's descriptors and keypoints as the C ABI takes them: one page-locked block, grown on demand
-  void* pinBlock;
-  size_t pinBytes;
+  HipPinnedBlock pin;
   float *pinDesc, *pinUv;
 
   bool pinFor(mh_ctx* ctx, int Q) {
-    const size_t need = (size_t)Q * (MH_DESC_DIM + 2) * sizeof(float);
-    if (need > pinBytes) {
-      if (pinBlock) mh_host_free(ctx, pinBlock);
-      pinBlock = NULL;
-      pinBytes = 0;
-      const size_t want = need + need / 4;
-      if (mh_host_alloc(ctx, want, &pinBlock) != MH_OK) return false;
-      pinBytes = want;
-    }
-    const size_t cap = pinBytes / ((MH_DESC_DIM + 2) * sizeof(float));
-    pinDesc = (float*)pinBlock;
-    pinUv = pinDesc + cap * MH_DESC_DIM;
+    const size_t row = (MH_DESC_DIM + 2) * sizeof(float);
+    if (!pin.ensure(ctx, (size_t)Q * row)) return false;
+    pinDesc = (float*)pin.data();
+    pinUv = pinDesc + pin.bytes() / row * MH_DESC_DIM;
     return true;
   }
 
@@ -70,11 +59,7 @@ class MATCH_BRUTE_HIP : public MopedAlg {
       pinUv[2 * i] = corresp[i].coord2D[0];
       pinUv[2 * i + 1] = corresp[i].coord2D[1];
     }
-    const Image& im = *frameData.images[img];
-    mh_cam cam;
-    for (int j = 0; j < 4; ++j) cam.K[j] = im.intrinsicLinearCalibration[j];
-    for (int j = 0; j < 4; ++j) cam.cam[j] = im.cameraPose.rotation[j];
-    for (int j = 0; j < 3; ++j) cam.cam[4 + j] = im.cameraPose.translation[j];
+    const mh_cam cam = hipCamOf(*frameData.images[img]);
     if (mh_step_match(ctx, pinDesc, pinUv, Q, &cam, Ratio, 1) != MH_OK || mh_frame_wait_descriptors(ctx) != MH_OK) {
       HipSession::warn("mh_step_match");
       return false;
@@ -109,73 +94,14 @@ class MATCH_BRUTE_HIP : public MopedAlg {
     return true;
   }
 
-  // IncrementalModels: the resident database is edited (HipResidentModels, hip_session.hpp); only the row -> model and
-  // row -> coord3D tables of the upload path are rebuilt here
-  bool UpdateIncremental(mh_ctx* ctx) {
-    if (!HipResidentModels::get().update(ctx, *models, DescriptorType)) return false;
-    size_t n = 0;
-    for (size_t m = 0; m < models->size(); ++m) n += (*models)[m]->IPs[DescriptorType].size();
-    correspModel.resize(n);
-    correspFeat.resize(n);
-    size_t x = 0;
-    for (size_t m = 0; m < models->size(); ++m) {
-      vector<Model::IP>& ips = (*models)[m]->IPs[DescriptorType];
-      for (size_t f = 0; f < ips.size(); ++f, ++x) {
-        correspModel[x] = (int)m;
-        correspFeat[x] = &ips[f].coord3D;
-      }
-    }
-    skipCalculation = n <= 1;   // (the reference's rule, :102)
-    configUpdated = false;
-    return true;
-  }
-
   void Update() {
-    skipCalculation = true;
-    mh_ctx* ctx = HipSession::get();
-    if (IncrementalModels && UpdateIncremental(ctx)) return;
-    size_t n = 0;
-    for (size_t m = 0; m < models->size(); ++m) n += (*models)[m]->IPs[DescriptorType].size();
-    correspModel.resize(n);
-    correspFeat.resize(n);
-    packed.resize(n * MH_DESC_DIM);
-    vector<float> xyz(n * 3);
-    vector<int32_t> owner(n);
-    size_t x = 0;
-    for (size_t m = 0; m < models->size(); ++m) {
-      vector<Model::IP>& ips = (*models)[m]->IPs[DescriptorType];
-      for (size_t f = 0; f < ips.size(); ++f, ++x) {
-        correspModel[x] = (int)m;
-        correspFeat[x] = &ips[f].coord3D;
-        owner[x] = (int32_t)m;
-        for (int i = 0; i < MH_DESC_DIM; ++i) packed[x * MH_DESC_DIM + i] = ips[f].descriptor[i];
-        for (int i = 0; i < 3; ++i) xyz[x * 3 + i] = ips[f].coord3D[i];
-      }
-    }
-    if (n > 1) {
-      // normalise on the device (bit-identical to norm(), :54-57) and write back,
-      // as Update() mutates the model descriptors (:94)
-      if (mh_normalize(ctx, &packed[0], (int)n) != MH_OK) { HipSession::warn("mh_normalize"); return; }
-      x = 0;
-      for (size_t m = 0; m < models->size(); ++m) {
-        vector<Model::IP>& ips = (*models)[m]->IPs[DescriptorType];
-        for (size_t f = 0; f < ips.size(); ++f, ++x)
-          for (int i = 0; i < MH_DESC_DIM; ++i) ips[f].descriptor[i] = packed[x * MH_DESC_DIM + i];
-      }
-      if (mh_db_upload(ctx, &packed[0], &owner[0], &xyz[0], (int)n, (int)models->size(), 0) != MH_OK) {
-        HipSession::warn("mh_db_upload");
-        return;
-      }
-      skipCalculation = false;
-      if (IncrementalModels) HipResidentModels::get().record(*models, DescriptorType);
-    }
-    configUpdated = false;
+    if (db.update(HipSession::get(), *models, DescriptorType, IncrementalModels)) configUpdated = false;
   }
 
  public:
   MATCH_BRUTE_HIP(int DescriptorSize, string DescriptorType, Float Ratio)
-      : DescriptorSize(DescriptorSize), DescriptorType(DescriptorType), Ratio(Ratio), skipCalculation(true),
-        IncrementalModels(0), pinBlock(NULL), pinBytes(0), pinDesc(NULL), pinUv(NULL) {
+      : DescriptorSize(DescriptorSize), DescriptorType(DescriptorType), Ratio(Ratio), IncrementalModels(0),
+        pinDesc(NULL), pinUv(NULL) {
     capable = (DescriptorSize == MH_DESC_DIM) && HipSession::get() != 0;
   }
 
@@ -192,7 +118,7 @@ class MATCH_BRUTE_HIP : public MopedAlg {
   void process(FrameData& frameData) {
     HipHandover::get().drop();   // MATCH begins a frame: whatever is resident belongs to an earlier one
     if (configUpdated) Update();
-    if (skipCalculation) return;
+    if (db.skipCalculation) return;
     vector<FrameData::DetectedFeature>& corresp = frameData.detectedFeatures[DescriptorType];
     if (corresp.empty()) return;
     vector<vector<FrameData::Match> >& matches = frameData.matches;
@@ -214,7 +140,7 @@ class MATCH_BRUTE_HIP : public MopedAlg {
     // count per model, size each list once, then fill.
     vector<size_t> fill(models->size(), 0);
     for (int i = 0; i < Q; ++i)
-      if (nn[i] >= 0) ++fill[correspModel[nn[i]]];
+      if (nn[i] >= 0) ++fill[db.correspModel[nn[i]]];
     for (size_t m = 0; m < fill.size(); ++m) {
       const size_t had = matches[m].size();
       matches[m].resize(had + fill[m]);
@@ -222,10 +148,10 @@ class MATCH_BRUTE_HIP : public MopedAlg {
     }
     for (int i = 0; i < Q; ++i) {
       if (nn[i] < 0) continue;
-      FrameData::Match& out = matches[correspModel[nn[i]]][fill[correspModel[nn[i]]]++];
+      FrameData::Match& out = matches[db.correspModel[nn[i]]][fill[db.correspModel[nn[i]]]++];
       out.imageIdx = corresp[i].imageIdx;
       out.coord2D = corresp[i].coord2D;
-      out.coord3D = *correspFeat[nn[i]];
+      out.coord3D = *db.correspFeat[nn[i]];
     }
   }
 };

@@ -78,11 +78,7 @@ class POSE_RANSAC_P3P_DEPTH_HIP : public MopedAlg {
         }
       const int ncl = (int)clModel.size();
       if (ncl == 0) continue;
-      const Image& im = *frameData.images[img];
-      mh_cam cam;
-      for (int i = 0; i < 4; ++i) cam.K[i] = im.intrinsicLinearCalibration[i];
-      for (int i = 0; i < 4; ++i) cam.cam[i] = im.cameraPose.rotation[i];
-      for (int i = 0; i < 3; ++i) cam.cam[4 + i] = im.cameraPose.translation[i];
+      const mh_cam cam = hipCamOf(*frameData.images[img]);
       vector<mh_pose_out> out((size_t)ncl * MaxObjectsPerCluster);
       int32_t nout = 0;
       if (mh_pose_ransac_depth(ctx, &corr[0], &depth[0], &off[0], ncl, &cam, &prm, Kind, Alpha,
@@ -90,14 +86,7 @@ class POSE_RANSAC_P3P_DEPTH_HIP : public MopedAlg {
         HipSession::warn("mh_pose_ransac_depth");
         continue;
       }
-      for (int o = 0; o < nout; ++o) {
-        SP_Object obj(new Object);
-        frameData.objects->push_back(obj);
-        obj->pose.rotation.init(out[o].pose[0], out[o].pose[1], out[o].pose[2], out[o].pose[3]);
-        obj->pose.translation.init(out[o].pose[4], out[o].pose[5], out[o].pose[6]);
-        obj->model = (*models)[clModel[out[o].cluster]];
-        obj->score = 0;
-      }
+      for (int o = 0; o < nout; ++o) hipAppendObject(frameData, (*models)[clModel[out[o].cluster]], out[o].pose, 0);
     }
     if (_stepName == "POSE") frameData.oldObjects = *frameData.objects;
   }

@@ -56,15 +56,8 @@ class POSE_RANSAC_P3P_HIP : public MopedAlg {
       HipSession::warn("mh_step_pose");
       return false;
     }
-    for (int o = 0; o < nout; ++o) {
-      if (out[o].model < 0 || out[o].model >= (int)models->size()) continue;
-      SP_Object obj(new Object);
-      frameData.objects->push_back(obj);
-      obj->pose.rotation.init(out[o].pose[0], out[o].pose[1], out[o].pose[2], out[o].pose[3]);
-      obj->pose.translation.init(out[o].pose[4], out[o].pose[5], out[o].pose[6]);
-      obj->model = (*models)[out[o].model];
-      obj->score = 0;
-    }
+    for (int o = 0; o < nout; ++o)
+      if (out[o].model >= 0 && out[o].model < (int)models->size()) hipAppendObject(frameData, (*models)[out[o].model], out[o].pose, 0);
     ho.stage = which == 1 ? 2 : 4;
     ++ho.taken;
     ho.objectsTag = HipHandover::tagObjects(frameData);
@@ -120,14 +113,7 @@ class POSE_RANSAC_P3P_HIP : public MopedAlg {
           HipSession::warn("mh_pose_ransac_images");
           nout = 0;
         }
-        for (int o = 0; o < nout; ++o) {
-          SP_Object obj(new Object);
-          frameData.objects->push_back(obj);
-          obj->pose.rotation.init(out[o].pose[0], out[o].pose[1], out[o].pose[2], out[o].pose[3]);
-          obj->pose.translation.init(out[o].pose[4], out[o].pose[5], out[o].pose[6]);
-          obj->model = (*models)[clModel[out[o].cluster]];
-          obj->score = 0;
-        }
+        for (int o = 0; o < nout; ++o) hipAppendObject(frameData, (*models)[clModel[out[o].cluster]], out[o].pose, 0);
       }
     }
     if (_stepName == "POSE") frameData.oldObjects = *frameData.objects;

@@ -2,6 +2,16 @@
 // after another on the caller's thread, src/moped.cpp:184-191).  C++98-clean and
 // free of HIP headers so it compiles inside libmoped with its own flags
 // (-std=gnu++98, libmoped/Makefile:44-47); the GPU lives behind the C ABI.
+// Beside the session, the glue between FrameData and the C ABI that more than one step needs lives here, once:
+//   HipHandover, HipDepthMaps   what consecutive steps of a frame leave on the device for each other
+//   HipResidentModels           edits of the resident database (IncrementalModels)
+//   HipModelTable               Update() of every MATCH-like step: pack, normalise, write back, upload
+//   hipCamOf, HipCameraTable    an Image as mh_cam; the cameras a frame's matches or features refer to
+//   hipAppendObject             a result record as an Object of the frame
+//   HipPinnedBlock              the page-locked block a step packs a frame's features into
+//   hipStageParams              one POSE + FILTER stage of mh_frame_params
+//   hipGetConfig, hipSetConfig  the reference's config keys
+// (moped3d's depth-map lookup needs Image::imageType and is in hip_frame3d.hpp.)
 #pragma once
 #include <moped_hip.h>
 
@@ -202,6 +212,76 @@ struct HipResidentModels {
   HipResidentModels() : valid(false), fullUploads(0), splices(0) {}
 };
 
+// What Update() of a MATCH step leaves behind (MATCH_ANN_CPU.hpp:72-109), for MATCH_BRUTE_HIP, FRAME_RESIDENT_HIP and
+// moped3d's HipAdaptiveModels alike: every model's descriptors normalised IN PLACE (:94) and resident on the device --
+// uploaded, or edited when IncrementalModels is set and the difference is one HipResidentModels serves -- and the
+// row -> model / row -> model point tables of the upload path.
+struct HipModelTable {
+  bool skipCalculation;   // true: one row or none (the reference's rule, :102), or the last update() failed
+  std::vector<int> correspModel;
+  std::vector<Pt<3>*> correspFeat;
+
+  HipModelTable() : skipCalculation(true) {}
+
+  // false: a call failed and was reported; skipCalculation stays true, the caller leaves configUpdated set and the next
+  // frame tries again
+  bool update(mh_ctx* ctx, std::vector<SP_Model>& models, const std::string& DescriptorType, int IncrementalModels) {
+    skipCalculation = true;
+    size_t n = 0;
+    for (size_t m = 0; m < models.size(); ++m) n += models[m]->IPs[DescriptorType].size();
+    correspModel.resize(n);
+    correspFeat.resize(n);
+    size_t x = 0;
+    for (size_t m = 0; m < models.size(); ++m) {
+      std::vector<Model::IP>& ips = models[m]->IPs[DescriptorType];
+      for (size_t f = 0; f < ips.size(); ++f, ++x) {
+        correspModel[x] = (int)m;
+        correspFeat[x] = &ips[f].coord3D;
+      }
+    }
+    if (IncrementalModels && HipResidentModels::get().update(ctx, models, DescriptorType)) {
+      skipCalculation = n <= 1;
+      return true;
+    }
+    if (n <= 1) return true;
+    std::vector<float> desc(n * MH_DESC_DIM), xyz(n * 3);
+    std::vector<int32_t> owner(n);
+    x = 0;
+    for (size_t m = 0; m < models.size(); ++m) {
+      std::vector<Model::IP>& ips = models[m]->IPs[DescriptorType];
+      for (size_t f = 0; f < ips.size(); ++f, ++x) {
+        owner[x] = (int32_t)m;
+        for (int i = 0; i < MH_DESC_DIM; ++i) desc[x * MH_DESC_DIM + i] = ips[f].descriptor[i];
+        for (int i = 0; i < 3; ++i) xyz[x * 3 + i] = ips[f].coord3D[i];
+      }
+    }
+    // normalised on the device (bit-identical to norm(), :54-57) and written back, as Update() does to the models (:94)
+    if (mh_normalize(ctx, &desc[0], (int)n) != MH_OK) { HipSession::warn("mh_normalize"); return false; }
+    x = 0;
+    for (size_t m = 0; m < models.size(); ++m) {
+      std::vector<Model::IP>& ips = models[m]->IPs[DescriptorType];
+      for (size_t f = 0; f < ips.size(); ++f, ++x)
+        for (int i = 0; i < MH_DESC_DIM; ++i) ips[f].descriptor[i] = desc[x * MH_DESC_DIM + i];
+    }
+    if (mh_db_upload(ctx, &desc[0], &owner[0], &xyz[0], (int)n, (int)models.size(), 0) != MH_OK) {
+      HipSession::warn("mh_db_upload");
+      return false;
+    }
+    skipCalculation = false;
+    if (IncrementalModels) HipResidentModels::get().record(models, DescriptorType);
+    return true;
+  }
+};
+
+// An Image's camera as the C ABI takes it
+inline mh_cam hipCamOf(const Image& im) {
+  mh_cam c;
+  for (int j = 0; j < 4; ++j) c.K[j] = im.intrinsicLinearCalibration[j];
+  for (int j = 0; j < 4; ++j) c.cam[j] = im.cameraPose.rotation[j];
+  for (int j = 0; j < 3; ++j) c.cam[4 + j] = im.cameraPose.translation[j];
+  return c;
+}
+
 // The cameras of a frame for the *_images entry points.  The reference projects every match through
 // *frameData.images[match.imageIdx] whatever else the image list holds (FILTER_PROJECTION_CPU.hpp:100-104,
 // POSE_RANSAC_LM_DIFF_REPROJECTION_CPU.hpp:228-237) -- a moped3d frame carries its depth and distance maps as
@@ -209,32 +289,98 @@ struct HipResidentModels {
 // image order (which keeps CLUSTER's and FILTER's per-image ordering), and `local` maps imageIdx to that number.
 struct HipCameraTable {
   std::vector<mh_cam> cams;
-  std::vector<int> local;  // imageIdx -> index into cams, -1 = no match refers to it
-  bool ok;
+  std::vector<int> local;  // imageIdx -> index into cams, -1 = nothing refers to it
+  bool ok;                 // false: cams is empty (an imageIdx outside FrameData::images) or longer than MH_MAX_IMAGES
 
+  // from the frame's matches; says itself why a step is skipped
   explicit HipCameraTable(const FrameData& frameData) : local(frameData.images.size(), -1), ok(true) {
-    for (size_t m = 0; m < frameData.matches.size() && ok; ++m)
-      for (size_t k = 0; k < frameData.matches[m].size(); ++k) {
-        const int i = frameData.matches[m][k].imageIdx;
-        if (i < 0 || i >= (int)local.size()) { ok = false; break; }
-        local[i] = 0;
-      }
-    for (size_t i = 0; i < local.size() && ok; ++i) {
-      if (local[i] < 0) continue;
-      local[i] = (int)cams.size();
-      const Image& im = *frameData.images[i];
-      mh_cam c;
-      for (int j = 0; j < 4; ++j) c.K[j] = im.intrinsicLinearCalibration[j];
-      for (int j = 0; j < 4; ++j) c.cam[j] = im.cameraPose.rotation[j];
-      for (int j = 0; j < 3; ++j) c.cam[4 + j] = im.cameraPose.translation[j];
-      cams.push_back(c);
-    }
-    if (ok && (int)cams.size() > MH_MAX_IMAGES) ok = false;
+    for (size_t m = 0; m < frameData.matches.size(); ++m) mark(frameData.matches[m]);
+    finish(frameData);
     if (!ok)
       std::clog << "[moped_hip] frame refers to an image outside FrameData::images or to more than " << MH_MAX_IMAGES
                 << " images: step skipped" << std::endl;
   }
+  // from any list whose elements have .imageIdx (FRAME_RESIDENT_HIP: the features); silent, the step words its own message
+  template <typename List>
+  HipCameraTable(const FrameData& frameData, const List& refs) : local(frameData.images.size(), -1), ok(true) {
+    mark(refs);
+    finish(frameData);
+  }
+
+ private:
+  template <typename List>
+  void mark(const List& refs) {
+    for (size_t k = 0; k < refs.size() && ok; ++k) {
+      const int i = refs[k].imageIdx;
+      if (i < 0 || i >= (int)local.size()) ok = false;
+      else local[i] = 0;
+    }
+  }
+  void finish(const FrameData& frameData) {
+    for (size_t i = 0; i < local.size() && ok; ++i) {
+      if (local[i] < 0) continue;
+      local[i] = (int)cams.size();
+      cams.push_back(hipCamOf(*frameData.images[i]));
+    }
+    if ((int)cams.size() > MH_MAX_IMAGES) ok = false;
+  }
 };
+
+// One result record {model, pose (qx, qy, qz, qw, tx, ty, tz), score} as an Object at the end of *frameData.objects
+inline void hipAppendObject(FrameData& frameData, const SP_Model& model, const float pose[7], Float score) {
+  SP_Object obj(new Object);
+  frameData.objects->push_back(obj);
+  obj->pose.rotation.init(pose[0], pose[1], pose[2], pose[3]);
+  obj->pose.translation.init(pose[4], pose[5], pose[6]);
+  obj->model = model;
+  obj->score = score;
+}
+
+// The page-locked block (mh_host_alloc) a step packs a frame's descriptors / keypoints / image indices into, grown when a
+// frame needs more.  Freed with the context it came from: the session's, which outlives every step (a step's constructor
+// is what first calls HipSession::get()).
+class HipPinnedBlock {
+ public:
+  HipPinnedBlock() : ctx_(0), block_(0), bytes_(0) {}
+  ~HipPinnedBlock() {
+    if (block_) mh_host_free(ctx_, block_);
+  }
+  // false: no block (the allocation failed); else data() holds at least `need` bytes
+  bool ensure(mh_ctx* ctx, size_t need) {
+    if (need <= bytes_) return true;
+    if (block_) mh_host_free(ctx_, block_);
+    block_ = 0;
+    bytes_ = 0;
+    const size_t want = need + need / 4;
+    if (mh_host_alloc(ctx, want, &block_) != MH_OK) { block_ = 0; return false; }
+    ctx_ = ctx;
+    bytes_ = want;
+    return true;
+  }
+  void* data() const { return block_; }
+  size_t bytes() const { return bytes_; }
+
+ private:
+  HipPinnedBlock(const HipPinnedBlock&);
+  HipPinnedBlock& operator=(const HipPinnedBlock&);
+  mh_ctx* ctx_;
+  void* block_;
+  size_t bytes_;
+};
+
+// POSE + FILTER (stage 1) or POSE2 + FILTER2 (stage 2) of a frame, from the reference constructors' arguments
+inline void hipStageParams(mh_frame_params& prm, int stage, int NHypotheses, int MaxObjectsPerCluster, int NPtsAlign,
+                           int MinNPtsObject, Float ErrorThreshold, int MinPoints, Float FeatureDistance, Float MinScore) {
+  mh_pose_params& pose = stage == 1 ? prm.pose1 : prm.pose2;
+  pose.n_hypotheses = NHypotheses;
+  pose.max_objects_per_cluster = MaxObjectsPerCluster;
+  pose.n_pts_align = NPtsAlign;
+  pose.min_n_pts_object = MinNPtsObject;
+  pose.error_threshold = (float)ErrorThreshold;
+  (stage == 1 ? prm.f1_min_points : prm.f2_min_points) = MinPoints;
+  (stage == 1 ? prm.f1_feature_distance : prm.f2_feature_distance) = (float)FeatureDistance;
+  (stage == 1 ? prm.f1_min_score : prm.f2_min_score) = (float)MinScore;
+}
 
 // The frame's depth map on the device, shared by moped3d's steps of one frame (DEPTHFILTER_HIP, DEPTHFILTER2,
 // DEPTHMAP_PROP_HIP, CLUSTER_LINKAGE_HIP): the first of them that finds another map than the context holds uploads it

@@ -348,10 +348,7 @@ int main(int argc, char** argv) {
     if (multi) return 2;
     flat.uv = uv;
     flat.qd = qd;
-    const Image& im = *images[0];
-    for (int j = 0; j < 4; ++j) flat.cam.K[j] = im.intrinsicLinearCalibration[j];
-    for (int j = 0; j < 4; ++j) flat.cam.cam[j] = im.cameraPose.rotation[j];
-    for (int j = 0; j < 3; ++j) flat.cam.cam[4 + j] = im.cameraPose.translation[j];
+    flat.cam = hipCamOf(*images[0]);
     return run_sharded(flat, world, repeats);
   }
 

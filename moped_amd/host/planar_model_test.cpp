@@ -75,10 +75,7 @@ int main(int argc, char** argv) {
   void* gray = 0;
   if (mh_host_alloc(ctx, image->data.size(), &gray) != MH_OK) return 8;
   std::memcpy(gray, &image->data[0], image->data.size());
-  mh_cam cam;
-  for (int k = 0; k < 4; ++k) cam.K[k] = image->intrinsicLinearCalibration[k];
-  for (int k = 0; k < 4; ++k) cam.cam[k] = image->cameraPose.rotation[k];
-  for (int k = 0; k < 3; ++k) cam.cam[4 + k] = image->cameraPose.translation[k];
+  const mh_cam cam = hipCamOf(*image);
   mh_frame_params prm;
   mh_frame_default_params(&prm);
   vector<mh_object> objects(64);

@@ -44,3 +44,14 @@ def test_owning_buffer_type_holds_its_growth_rule_under_asan_and_ubsan():
     out = subprocess.run(["make", "-s", "-B", "-C", HOST, "devbuf_check"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
     assert "devbuf_test: no finding" in out.stdout, out.stdout
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_shared_model_table_and_pinned_block_under_asan_and_ubsan():
+    # hip_session.hpp's HipModelTable (Update() of MATCH_BRUTE_HIP, FRAME_RESIDENT_HIP and moped3d's HipAdaptiveModels) and
+    # HipPinnedBlock against recording stand-ins for the C-ABI calls (moped_amd/host/model_table_test.cpp): the full path's
+    # calls and arguments, too few rows, a failing normalise / upload, every edit IncrementalModels serves and the two it
+    # hands to the full path; the block's growth rule, every block freed once with its own context
+    out = subprocess.run(["make", "-s", "-B", "-C", HOST, "model_table_check"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
+    assert "model_table_test: no finding" in out.stdout, out.stdout
