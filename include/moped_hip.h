@@ -646,6 +646,43 @@ int mh_depth_fill_batch(mh_ctx* ctx, float* const* depth_xyzn_dev, float* const*
 /* The same on host maps (what the DEPTH_FILL_EXACT_HIP plugin calls): upload, fill, both maps back, status. */
 int mh_depth_fill_host(mh_ctx* ctx, float* depth_xyzn_host, int width, int height, int scale_factor, int bilinear,
                        const float K[4], float* fill_distance_host, int* scale_used);
+
+/* The depth map itself from what a Kinect delivers: the block of moped3d's ROS node in front of the pipeline
+ * (moped3d/moped3d.cpp:279-333), one thread per pixel of the map.  A raw value is read at
+ * raw + offset + y * row_stride + x * elem_stride (bytes):
+ *   MH_RAW_DEPTH_F32_M    a float in metres, NaN = no reading -> -1e30f (:288-292)
+ *   MH_RAW_DEPTH_U16_MM   OpenNI's uint16 millimetres, 0 = no reading -> -1e30f, else (float) mm * 0.001f
+ * A plain image has elem_stride 4 or 2; an organised PointCloud2 buffer is read in place with elem_stride = point_step,
+ * offset = the z field's offset, row_stride = row_step (:287: no host repacking).
+ * (width, height) == the raw size: the pixel's depth is the raw value (:298-300).  Any other size: it comes from the raw
+ * map resized to exactly (2 raw width, 2 raw height) (:303, cv::resize's bilinear path for float, restated from memory of
+ * OpenCV 2.x and therefore unpinned: csrc/depthmap.hip has the arithmetic); pixels beyond the resized map are invalid
+ * (:313-316), a smaller target crops it.  A missing reading at (x, y) invalidates [2x - 1, 2x + 2] x [2y - 1, 2y + 2].
+ * Depth < 0: the pixel's four floats are -1 (:318-319; 0.0 and -0.0 are valid); else x = depth (u - K[2]) / K[0],
+ * y = depth (v - K[3]) / K[1], z = depth, norm = sqrt(x x + y y + z z) (:325-330), every operation rounded on its own:
+ * bit for bit tests/depthmap_ref.py (tests/test_gpu_depthmap.py).  K = the DEPTH camera's fx, fy, cx, cy (:306).
+ * MH_ERR_ARG before any launch: a null pointer, a size <= 0, an unknown format, a stride or an offset that is not a
+ * multiple of the element size (or negative), a stride smaller than the element, a raw pointer not aligned to the
+ * element or a map not aligned to 16 bytes, n_frames outside 1 .. MH_MAX_BATCH, two frames writing the same map. */
+enum { MH_RAW_DEPTH_F32_M = 0, MH_RAW_DEPTH_U16_MM = 1 };
+typedef struct mh_raw_depth {
+  int32_t format, width, height;             /* the sensor's size */
+  int32_t elem_stride, row_stride, offset;   /* bytes */
+} mh_raw_depth;
+/* raw_dev -> depth_xyzn_dev [height][width][4], both on the device; asynchronous on the context's stream. */
+int mh_depth_map_from_raw_dev(mh_ctx* ctx, const void* raw_dev, const mh_raw_depth* raw, const float K[4],
+                              float* depth_xyzn_dev, int width, int height);
+/* n_frames <= MH_MAX_BATCH raw buffers of one description -> a map each, ONE launch (the frame index is in the grid);
+ * every map bit for bit what the single call gives it.  Pointer arrays on the host; asynchronous. */
+int mh_depth_map_from_raw_batch_dev(mh_ctx* ctx, const void* const* raw_dev, const mh_raw_depth* raw, const float K[4],
+                                    float* const* depth_xyzn_dev, int n_frames, int width, int height);
+/* The same for a host that holds the sensor's buffer: its offset + (raw height - 1) row_stride + (raw width - 1)
+ * elem_stride + element size bytes are copied into a context-owned buffer (1.2 MB of float z, 0.6 MB of 16-bit for
+ * 640 x 480, against the 4.9 MB of the finished map), the map is built into the buffers mh_frame_set_depth_image_host
+ * fills and copied to depth_xyzn_host; with NULL it only stays there (what mh_frame_run_kinect_raw_host goes on from).
+ * A frame's map that lived in those buffers is switched off: set it again.  Synchronous. */
+int mh_depth_map_from_raw_host(mh_ctx* ctx, const void* raw_host, const mh_raw_depth* raw, const float K[4],
+                               float* depth_xyzn_host, int width, int height);
 /* moped3d's rules on which features and matches reach CLUSTER, applied on the device inside the
  * frame (they need the depth map: mh_frame_set_depth_image):
  *  - DEPTHFILTER_CPU (moped3d/libmoped/src/depthfilter/DEPTHFILTER_CPU.hpp:117-254), ToFilter = 1
@@ -1050,6 +1087,18 @@ int mh_frame_run_kinect_host(mh_ctx* ctx, const uint8_t* gray_host, float* depth
                              const mh_frame_params* prm, int fill_scale, int bilinear, int kind, float alpha,
                              float cauchy_scale, uint64_t seed, mh_object* objects_host, int max_objects,
                              int32_t* n_objects, int32_t* counts);
+/* The same from what the sensor delivers (moped3d/moped3d.cpp:270-338: the node builds the map, then processImages):
+ * raw_host / raw as mh_depth_map_from_raw_host takes them, the map of width x height (the gray image's size, :277-278)
+ * is built on the device with K = cam->K (the cameras coincide, as for the fill of mh_frame_run_kinect_host), and from
+ * there on the call is mh_frame_run_kinect_host launch for launch: the objects and counts are bit for bit those of that
+ * call fed the same map.  depth_xyzn_host and fill_distance_host are optional OUTPUTS (NULL: nothing is copied back):
+ * the map as the frame used it (filled when fill_scale != 0) and its distance map (fill_scale != 0 only; with
+ * fill_scale = 0 there is no distance map and fill_distance_host is left alone). */
+int mh_frame_run_kinect_raw_host(mh_ctx* ctx, const uint8_t* gray_host, const void* raw_host, const mh_raw_depth* raw,
+                                 float* depth_xyzn_host, float* fill_distance_host, int width, int height,
+                                 int double_size, int max_keypoints, const mh_cam* cam, const mh_frame_params* prm,
+                                 int fill_scale, int bilinear, int kind, float alpha, float cauchy_scale, uint64_t seed,
+                                 mh_object* objects_host, int max_objects, int32_t* n_objects, int32_t* counts);
 
 /* ONE frame seen by n_images cameras, images resident on the device: FEAT of every image
  * (FEAT_SIFT_CPU.hpp:80-107: image 0's keypoints in libsiftfast's list order, then image 1's, ...,

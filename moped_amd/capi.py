@@ -124,6 +124,24 @@ def make_planar_spec(scale=None, z=None, K=None, roi=None, max_rows=0) -> mh_pla
     return sp
 
 
+RAW_DEPTH_F32_M, RAW_DEPTH_U16_MM = 0, 1   # MH_RAW_DEPTH_*
+
+
+class mh_raw_depth(C.Structure):
+    _fields_ = [("format", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("elem_stride", C.c_int32),
+                ("row_stride", C.c_int32), ("offset", C.c_int32)]
+
+
+def make_raw_depth(fmt, width, height, elem_stride=None, row_stride=None, offset=0) -> mh_raw_depth:
+    """What a sensor's depth buffer looks like: RAW_DEPTH_F32_M (float metres, NaN = no reading) or RAW_DEPTH_U16_MM
+    (uint16 millimetres, 0 = no reading), width x height readings at offset + y row_stride + x elem_stride bytes.
+    Defaults: a plain image.  A PointCloud2: elem_stride = point_step, row_stride = row_step, offset = z's offset."""
+    es = 4 if fmt == RAW_DEPTH_F32_M else 2
+    elem_stride = es if elem_stride is None else elem_stride
+    row_stride = width * elem_stride if row_stride is None else row_stride
+    return mh_raw_depth(int(fmt), int(width), int(height), int(elem_stride), int(row_stride), int(offset))
+
+
 def make_filter_depth_params(p):
     """None, an mh_filter_depth_params or (plausible_sq_distance, depth_fraction, min_keypoint_fraction)."""
     if p is None or isinstance(p, mh_filter_depth_params):
@@ -173,6 +191,8 @@ EXPORTS = [
     "mh_linkage_debug_matrix", "mh_linkage_debug_agglomerate", "mh_frame_debug_fetch_clusters_slot",
     "mh_planar_rows_dev", "mh_planar_rows_batch_dev", "mh_db_splice_image", "mh_db_splice_images",
     "mh_models_add_rows", "mh_models_write_xml",
+    "mh_depth_map_from_raw_dev", "mh_depth_map_from_raw_batch_dev", "mh_depth_map_from_raw_host",
+    "mh_frame_run_kinect_raw_host",
 ]
 COMM_ID_BYTES = 128      # MH_COMM_ID_BYTES
 EX2_OBJECTS = 62         # MH_EX2_OBJECTS
@@ -318,6 +338,14 @@ def load():
     L.mh_depth_prop.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp]
     L.mh_frame_run_kinect_host.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(mh_cam), C.POINTER(mh_frame_params),
                                            i32, i32, i32, f32, f32, C.c_uint64, vp, i32, C.POINTER(C.c_int32), vp]
+    if hasattr(L, "mh_depth_map_from_raw_dev"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
+        rd = C.POINTER(mh_raw_depth)
+        L.mh_depth_map_from_raw_dev.argtypes = [vp, vp, rd, vp, vp, i32, i32]
+        L.mh_depth_map_from_raw_batch_dev.argtypes = [vp, C.POINTER(vp), rd, vp, C.POINTER(vp), i32, i32, i32]
+        L.mh_depth_map_from_raw_host.argtypes = [vp, vp, rd, vp, vp, i32, i32]
+        L.mh_frame_run_kinect_raw_host.argtypes = [vp, vp, vp, rd, vp, vp, i32, i32, i32, i32, C.POINTER(mh_cam),
+                                                   C.POINTER(mh_frame_params), i32, i32, i32, f32, f32, C.c_uint64, vp, i32,
+                                                   C.POINTER(C.c_int32), vp]
     L.mh_db_debug_screen.argtypes = [vp, vp]
     L.mh_db_debug_route.argtypes = [vp, i32]
     L.mh_db_edit_ms.argtypes = [vp, C.POINTER(f32)]
@@ -1068,6 +1096,34 @@ class Context:
                                            C.byref(used)), "mh_depth_fill_host")
         return d, dist, used.value
 
+    # ---- the depth map from raw sensor depth (moped3d/moped3d.cpp:279-333) ----
+    def depth_map_from_raw_dev(self, raw_ptr, raw: mh_raw_depth, K, depth_ptr, width, height):
+        """A device buffer of raw sensor depth (make_raw_depth) -> the device map [height, width, 4]; asynchronous."""
+        k = np.ascontiguousarray(K, np.float32)
+        self._ck(self.L.mh_depth_map_from_raw_dev(self.h, C.c_void_p(raw_ptr) if raw_ptr else None, C.byref(raw), _ptr(k),
+                                                  C.c_void_p(depth_ptr) if depth_ptr else None, width, height),
+                 "mh_depth_map_from_raw_dev")
+
+    def depth_map_from_raw_batch_dev(self, raw_ptrs, raw: mh_raw_depth, K, depth_ptrs, width, height):
+        """len(raw_ptrs) raw buffers of one description -> a map each, one launch; asynchronous."""
+        n = len(raw_ptrs)
+        if len(depth_ptrs) != n:
+            raise ValueError("one map per raw buffer")
+        k = np.ascontiguousarray(K, np.float32)
+        r = (C.c_void_p * max(n, 1))(*raw_ptrs)
+        d = (C.c_void_p * max(n, 1))(*depth_ptrs)
+        self._ck(self.L.mh_depth_map_from_raw_batch_dev(self.h, r, C.byref(raw), _ptr(k), d, n, width, height),
+                 "mh_depth_map_from_raw_batch_dev")
+
+    def depth_map_from_raw(self, raw_buf, raw: mh_raw_depth, K, width, height):
+        """The same on a host buffer (any contiguous array holding the bytes `raw` describes) -> the map [height, width, 4]."""
+        b = np.ascontiguousarray(raw_buf)
+        k = np.ascontiguousarray(K, np.float32)
+        out = np.zeros((height, width, 4), np.float32)
+        self._ck(self.L.mh_depth_map_from_raw_host(self.h, _ptr(b), C.byref(raw), _ptr(k), _ptr(out), width, height),
+                 "mh_depth_map_from_raw_host")
+        return out
+
     def frame_set_depth_image_batch(self, depth_ptrs, fill_ptrs, width, height, kind, alpha=0.5, cauchy_scale=0.1):
         """One depth map (+ distance map, or None for all) per frame of the following batches."""
         n = len(depth_ptrs)
@@ -1351,6 +1407,29 @@ class Context:
                                                  int(max_keypoints), C.byref(c), C.byref(params), int(fill_scale),
                                                  1 if bilinear else 0, kind, alpha, cauchy_scale, seed, _ptr(objs),
                                                  max_objects, C.byref(n), _ptr(counts)), "mh_frame_run_kinect_host")
+        return objs[:min(n.value, max_objects)].copy(), counts, d, f
+
+    def frame_run_kinect_raw_host(self, gray, raw_buf, raw: mh_raw_depth, K, cam, params: mh_frame_params, seed,
+                                  fill_scale=8, bilinear=False, double_size=True, max_keypoints=2048,
+                                  kind=DEPTH_BACKPROJECTION, alpha=0.5, cauchy_scale=0.1, max_objects=4096, maps_back=True):
+        """One Kinect frame from what the sensor delivers: gray [h, w] uint8 and the raw depth buffer `raw` describes; the
+        map [h, w, 4] is built on the device (K), then the frame runs as frame_run_kinect_host's does.
+        -> (objects, counts, the depth map and the distance map as the frame used them; None, None without maps_back,
+        and no distance map with fill_scale 0)."""
+        g = np.ascontiguousarray(gray, np.uint8)
+        h, w = g.shape
+        b = np.ascontiguousarray(raw_buf)
+        d = np.zeros((h, w, 4), np.float32) if maps_back else None
+        f = np.zeros((h, w), np.float32) if maps_back and fill_scale else None
+        c = make_cam(K, cam)
+        objs = np.zeros(max_objects, OBJECT_DTYPE)
+        n = C.c_int32(0)
+        counts = np.zeros(4, np.int32)
+        self._ck(self.L.mh_frame_run_kinect_raw_host(self.h, _ptr(g), _ptr(b), C.byref(raw), _ptr(d), _ptr(f), w, h,
+                                                     1 if double_size else 0, int(max_keypoints), C.byref(c),
+                                                     C.byref(params), int(fill_scale), 1 if bilinear else 0, kind, alpha,
+                                                     cauchy_scale, seed, _ptr(objs), max_objects, C.byref(n), _ptr(counts)),
+                 "mh_frame_run_kinect_raw_host")
         return objs[:min(n.value, max_objects)].copy(), counts, d, f
 
     def frame_set_filter_depth(self, f1=None, f2=None, depth_K=None, depth_cam=None):

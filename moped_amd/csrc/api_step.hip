@@ -121,6 +121,39 @@ int step_depth_map(mh_ctx* ctx, const char* who, const float* depth_host, const 
   return MH_OK;
 }
 
+// What a Kinect frame does once its gray image is in own_gray and its map in own_depth (mh_frame_run_kinect_host,
+// mh_frame_run_kinect_raw_host): DEPTHFILL (fill_scale != 0) or the host's distance map (fill_in_host, or none), the maps
+// set, the image enqueued, the maps as the frame used them copied back where asked (depth_out_host; fill_out_host, which
+// a caller passes only with a fill), the objects fetched.
+int kinect_frame_tail(mh_ctx* ctx, const char* who, const float* fill_in_host, float* depth_out_host, float* fill_out_host,
+                      int width, int height, int double_size, int max_keypoints, const mh_cam* cam,
+                      const mh_frame_params* prm, int fill_scale, int bilinear, int kind, float alpha, float cauchy_scale,
+                      uint64_t seed, mh_object* objects_host, int max_objects, int32_t* n_objects, int32_t* counts) {
+  hipStream_t s = ctx->stream;
+  const size_t px = (size_t)width * height;
+  const bool fill = fill_scale != 0;
+  const bool have_fill = fill || fill_in_host;
+  if (fill) {
+    if (int rc = mh_depth_fill(ctx, ctx->own_depth, width, height, fill_scale, bilinear, cam->K, ctx->own_fill, nullptr)) return rc;
+  } else if (fill_in_host) {
+    MH_HIP(ctx, hipMemcpyAsync(ctx->own_fill, fill_in_host, px * sizeof(float), hipMemcpyHostToDevice, s));
+  }
+  if (int rc = mh_frame_set_depth_image(ctx, ctx->own_depth, have_fill ? ctx->own_fill.p : nullptr, width, height, kind,
+                                        alpha, cauchy_scale)) {
+    ctx->err = std::string(who) + ": kind must be MH_DEPTH_BACKPROJECTION or MH_DEPTH_REPROJECTION, cauchy_scale > 0";
+    return rc;
+  }
+  if (int rc = mh_frame_enqueue_image(ctx, ctx->own_gray, width, height, double_size, max_keypoints, cam, prm, seed)) return rc;
+  // the frame's images as DEPTH_FILL_EXACT_CPU::process leaves them, behind the frame's launches
+  if (depth_out_host)
+    MH_HIP(ctx, hipMemcpyAsync(depth_out_host, ctx->own_depth, px * 4 * sizeof(float), hipMemcpyDeviceToHost, s));
+  if (fill_out_host)
+    MH_HIP(ctx, hipMemcpyAsync(fill_out_host, ctx->own_fill, px * sizeof(float), hipMemcpyDeviceToHost, s));
+  const int rc = mh_frame_fetch(ctx, objects_host, max_objects, n_objects, counts);
+  const int rc_fill = fill ? mh_depth_fill_status(ctx) : MH_OK;
+  return rc ? rc : rc_fill;
+}
+
 }  // namespace
 extern "C" {
 
@@ -225,25 +258,35 @@ int mh_frame_run_kinect_host(mh_ctx* ctx, const uint8_t* gray_host, float* depth
   MH_HIP(ctx, ctx->own_gray.ensure(px, s));
   MH_HIP(ctx, hipMemcpyAsync(ctx->own_gray, gray_host, px, hipMemcpyHostToDevice, s));
   MH_HIP(ctx, hipMemcpyAsync(ctx->own_depth, depth_xyzn_host, px * 4 * sizeof(float), hipMemcpyHostToDevice, s));
-  const bool have_fill = fill || fill_distance_host;
-  if (fill) {
-    if (int rc = mh_depth_fill(ctx, ctx->own_depth, width, height, fill_scale, bilinear, cam->K, ctx->own_fill, nullptr)) return rc;
-  } else if (fill_distance_host) {
-    MH_HIP(ctx, hipMemcpyAsync(ctx->own_fill, fill_distance_host, px * sizeof(float), hipMemcpyHostToDevice, s));
+  return kinect_frame_tail(ctx, "mh_frame_run_kinect_host", fill ? nullptr : fill_distance_host, fill ? depth_xyzn_host : nullptr,
+                           fill ? fill_distance_host : nullptr, width, height, double_size, max_keypoints, cam, prm,
+                           fill_scale, bilinear, kind, alpha, cauchy_scale, seed, objects_host, max_objects, n_objects, counts);
+}
+
+// ... and from what the sensor delivers: the raw depth goes up instead of the map, depthmap.hip builds the map into
+// own_depth (moped3d/moped3d.cpp:279-333), the tail is the same
+int mh_frame_run_kinect_raw_host(mh_ctx* ctx, const uint8_t* gray_host, const void* raw_host, const mh_raw_depth* raw,
+                                 float* depth_xyzn_host, float* fill_distance_host, int width, int height,
+                                 int double_size, int max_keypoints, const mh_cam* cam, const mh_frame_params* prm,
+                                 int fill_scale, int bilinear, int kind, float alpha, float cauchy_scale, uint64_t seed,
+                                 mh_object* objects_host, int max_objects, int32_t* n_objects, int32_t* counts) {
+  if (!ctx) return MH_ERR_ARG;
+  const bool fill = fill_scale != 0;
+  if (!gray_host || !raw_host || !raw || width <= 0 || height <= 0 || max_keypoints <= 0 || !cam || !prm || !n_objects ||
+      (fill_scale < 1 && fill_scale != 0 && fill_scale != -1)) {
+    ctx->err = "mh_frame_run_kinect_raw_host: bad argument";
+    return MH_ERR_ARG;
   }
-  if (int rc = mh_frame_set_depth_image(ctx, ctx->own_depth, have_fill ? ctx->own_fill.p : nullptr, width, height, kind,
-                                        alpha, cauchy_scale)) {
-    ctx->err = "mh_frame_run_kinect_host: kind must be MH_DEPTH_BACKPROJECTION or MH_DEPTH_REPROJECTION, cauchy_scale > 0";
-    return rc;
-  }
-  if (int rc = mh_frame_enqueue_image(ctx, ctx->own_gray, width, height, double_size, max_keypoints, cam, prm, seed)) return rc;
-  if (fill) {   // the frame's images as DEPTH_FILL_EXACT_CPU::process leaves them, behind the frame's launches
-    MH_HIP(ctx, hipMemcpyAsync(depth_xyzn_host, ctx->own_depth, px * 4 * sizeof(float), hipMemcpyDeviceToHost, s));
-    MH_HIP(ctx, hipMemcpyAsync(fill_distance_host, ctx->own_fill, px * sizeof(float), hipMemcpyDeviceToHost, s));
-  }
-  const int rc = mh_frame_fetch(ctx, objects_host, max_objects, n_objects, counts);
-  const int rc_fill = fill ? mh_depth_fill_status(ctx) : MH_OK;
-  return rc ? rc : rc_fill;
+  *n_objects = 0;
+  mh_frame_set_depth_image(ctx, nullptr, nullptr, 0, 0, 0, alpha, 0.f);   // (the own buffers may move)
+  if (int rc = depth_map_from_raw_own(ctx, "mh_frame_run_kinect_raw_host", raw_host, raw, cam->K, width, height)) return rc;
+  hipStream_t s = ctx->stream;
+  const size_t px = (size_t)width * height;
+  MH_HIP(ctx, ctx->own_gray.ensure(px, s));
+  MH_HIP(ctx, hipMemcpyAsync(ctx->own_gray, gray_host, px, hipMemcpyHostToDevice, s));
+  return kinect_frame_tail(ctx, "mh_frame_run_kinect_raw_host", nullptr, depth_xyzn_host, fill ? fill_distance_host : nullptr,
+                           width, height, double_size, max_keypoints, cam, prm, fill_scale, bilinear, kind, alpha,
+                           cauchy_scale, seed, objects_host, max_objects, n_objects, counts);
 }
 
 int mh_step_match(mh_ctx* ctx, float* q_desc_host, const float* q_uv_host, int Q, const mh_cam* cam, float ratio,

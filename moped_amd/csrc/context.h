@@ -279,6 +279,7 @@ struct mh_ctx {
   mh::DevBuf<float> own_depth;    // device copies of a host depth / distance map (ensure_own_depth)
   mh::DevBuf<float> own_fill;
   mh::DevBuf<uint8_t> own_gray;   // device copy of a host gray image (mh_frame_run_kinect_host)
+  mh::DevBuf<unsigned char> own_raw;   // device copy of a host's raw sensor depth (mh_depth_map_from_raw_host)
   mh::DevBuf<float> lk_scratch;
   mh::DevBuf<unsigned char> df_buf;   // mh_depth_fill[_batch]: [status words | per frame: downscaled depths, downscaled distances]
   int df_mode = 0;                    // mh_depth_fill_set_mode (MH_DEPTH_FILL_REPLAY); LEVELS: [status words | stats | per frame: depthfill.hip]
@@ -344,6 +345,10 @@ int ensure_scratch(mh_ctx* ctx, size_t bytes);
 int ensure_pinned(mh_ctx* ctx, size_t bytes);
 int ensure_own_depth(mh_ctx* ctx, size_t px);   // own_depth [px][4] and own_fill [px]
 int ensure_match_scratch(mh_ctx* ctx, int Q);
+// depthmap.hip: a host's raw sensor depth uploaded into own_raw and its xyzn map built into own_depth, on the context's
+// stream, after every check of mh_depth_map_from_raw_host (`who` in the message); no wait
+int depth_map_from_raw_own(mh_ctx* ctx, const char* who, const void* raw_host, const mh_raw_depth* raw, const float K[4],
+                           int width, int height);
 // MATCH of Q normalised queries against the context's DB on its stream: exact (idx1, d1, d2) per query, by the
 // two-stage screen when it pays and the DB allows it, else by the exact kernels (bit-identical results either way).
 int ctx_match(mh_ctx* ctx, const float* qn, const float* qnorm, int Q, int32_t* idx1, float* d1, float* d2,

@@ -10,4 +10,5 @@ namespace std { using tr1::shared_ptr; }
 #include "DEPTHFILTER_HIP.hpp"
 #include "DEPTHMAP_PROP_HIP.hpp"
 #include "FRAME_RESIDENT_3D_HIP.hpp"
+#include "KINECT_DEPTHMAP_HIP.hpp"
 int main() { return 0; }

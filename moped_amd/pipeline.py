@@ -155,6 +155,7 @@ class FramePipeline:
             self.comms = self._make_comms(max(1, min(n_comms, depth)))
         self._batch = [1] * depth
         self._inputs = [None] * depth   # the slot's current input tensors: its stream may still be reading them
+        self._raw_maps = [None] * depth   # enqueue_kinect_raw_batch: the slot's (depth maps, distance maps), flat, grown on demand
         self._cam = capi.make_cam(self.K, self.cam)
 
     def _make_comms(self, n):
@@ -374,6 +375,40 @@ class FramePipeline:
         c.frame_set_depth_image_batch(list(depth_ptrs), list(fill_ptrs), w, h, kind, alpha, cauchy_scale)
         c.frame_enqueue_image_batch(list(gray_ptrs), w, h, double_size, max_keypoints, self.K, self.cam, self.params, seeds,
                                     _cam_struct=self._cam)
+
+    def enqueue_kinect_raw_batch(self, slot: int, gray_ptrs, raw_ptrs, raw_fmt: "capi.mh_raw_depth", w: int, h: int, seeds,
+                                 fill_scale=8, bilinear: bool = False, max_keypoints: int = 2048, double_size: bool = True,
+                                 kind: int = capi.DEPTH_BACKPROJECTION, alpha: float = 0.5, cauchy_scale: float = 0.1,
+                                 keep=None):
+        """The same from what the sensor delivers (moped3d/moped3d.cpp:279-333): raw_ptrs = one device buffer of raw depth
+        per frame, all as raw_fmt (capi.make_raw_depth) describes them.  The [h, w, 4] maps of the batch are built in ONE
+        launch into tensors the slot keeps (grown on demand, never shrunk), then everything is enqueue_kinect_batch:
+        DEPTHFILL of those maps (fill_scale=None: no DEPTHFILL and no distance maps), the hand-over, the image batch.
+        -> (maps [B, h, w, 4], distance maps [B, h, w] or None): views of the slot's tensors, valid until its next call."""
+        if self.exchange:
+            raise ValueError("frames from device images run on one GPU's whole database")
+        B = len(seeds)
+        if not (1 <= B <= capi.MAX_BATCH) or len(gray_ptrs) != B or len(raw_ptrs) != B:
+            raise ValueError("one image, one raw depth buffer and one seed per frame, at most MAX_BATCH frames")
+        c = self.ctxs[slot]
+        need = B * h * w
+        if self._raw_maps[slot] is None or self._raw_maps[slot][0].numel() < need * 4:
+            self.streams[slot].synchronize()   # (the slot's stream may still read the tensors this replaces)
+            self._raw_maps[slot] = (torch.empty(need * 4, dtype=torch.float32, device=self.dev),
+                                    torch.empty(need, dtype=torch.float32, device=self.dev))
+        maps = self._raw_maps[slot][0][:need * 4].view(B, h, w, 4)
+        dist = self._raw_maps[slot][1][:need].view(B, h, w)
+        depth_ptrs = [maps[f].data_ptr() for f in range(B)]
+        c.depth_map_from_raw_batch_dev(list(raw_ptrs), raw_fmt, self.K, depth_ptrs, w, h)
+        self._inputs[slot] = keep
+        self._batch[slot] = B
+        fill_ptrs = [dist[f].data_ptr() for f in range(B)] if fill_scale is not None else None
+        if fill_scale is not None:
+            c.depth_fill_batch_dev(depth_ptrs, fill_ptrs, w, h, self.K, fill_scale, bilinear)
+        c.frame_set_depth_image_batch(depth_ptrs, fill_ptrs, w, h, kind, alpha, cauchy_scale)
+        c.frame_enqueue_image_batch(list(gray_ptrs), w, h, double_size, max_keypoints, self.K, self.cam, self.params, seeds,
+                                    _cam_struct=self._cam)
+        return maps, (dist if fill_scale is not None else None)
 
     def set_depth_fill_mode(self, mode: int):
         """How enqueue_kinect_batch fills the maps, on every slot's context: capi.DEPTH_FILL_REPLAY (the default; maps of
