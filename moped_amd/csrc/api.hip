@@ -78,6 +78,7 @@ int ensure_match_scratch(mh_ctx* ctx, int Q) {
     MH_HIP(ctx, o.stats.ensure(qp * 3, s));
     MH_HIP(ctx, o.inc.ensure(qp + 1, s));
     MH_HIP(ctx, hipMemsetAsync(o.inc, 0, (qp + 1) * sizeof(unsigned int), s));
+    // (every slot empty, every count zero: the state both record layouts start from and pass C restores, screen.h)
     MH_HIP(ctx, hipMemsetAsync(o.recs, 0, slots * sizeof(uint2), s));
     MH_HIP(ctx, hipMemsetAsync(o.ovf_cnt, 0, qp * sizeof(int32_t), s));
     MH_HIP(ctx, hipMemsetAsync(o.stats, 0, qp * 3 * sizeof(unsigned int), s));

@@ -138,7 +138,7 @@ struct mh_ctx {
     mh::DevBuf<unsigned char> part;
     mh::DevBuf<float> tau;
     mh::DevBuf<uint2> recs, ovf;
-    mh::DevBuf<int32_t> ovf_cnt;
+    mh::DevBuf<int32_t> ovf_cnt;   // per query: overflow records, or (16x16x32 launches) the records of its counted list
     mh::DevBuf<unsigned int> stats, inc;
   } screen_own;
   int match_mode = -1;           // mh_match_set_mode

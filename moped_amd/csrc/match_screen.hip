@@ -244,6 +244,14 @@ constexpr int SC_SLOTS_MAX = 256;   // pass B's record slots per query: 2 halves
 // ... and behind them the slots of the records pass A's sampled tiles leave (screen_handover_kernel; the one-sweep launches)
 constexpr int SC_SA_SLOTS = 32;
 constexpr int SC_SLOT_PITCH = SC_SLOTS_MAX + SC_SA_SLOTS;
+// The 16x16x32 launches (launch_passes16) use the same memory as ONE counted list per query instead: the records lie in
+// recs[q * SC_SLOT_PITCH + 0 .. count), count = the query's word of `ovf_cnt` (those launches have no overflow list).
+// screen_handover_kernel writes its records as the list's head and stores the count; pass B appends behind them with one
+// atomic add per record, when a wavefront writes its parked hits out (screen16_kernel's flush_parked: outside the hit
+// path).  A record that finds the list full is dropped and still counted: count > SC_SLOT_PITCH sends the query to pass
+// C's brute-force search.  Pass C reads the count with its other scalars and 64 slots (one 512-byte line) in the same round
+// trip, instead of every slot a sub-list might have used.  Between launches every slot is empty and every count zero, as
+// the 32x32x16 launches -- which share a context's buffers with these -- need it: pass C re-empties what it consumed.
 
 #ifdef SC_PROF   // experiment build (make EXTRA=-DSC_PROF ...): switch parts of passes A/B off (results are wrong then)
 // and stamp a workgroup's time; scripts/screen_prof.py
@@ -255,6 +263,11 @@ static int g_sc_ablate = 0;
 #else
 #define SC_ABL(bit) 0
 #define SC_EV(e) do { } while (0)
+#endif
+#ifdef MH_EXPERIMENTS
+// hits of screen16_kernel's pass B that found their wavefront's park buffer full and were appended from the hit path
+// (mh_debug_screen_direct_appends)
+__device__ unsigned long long g_sc_direct_appends;
 #endif
 
 struct ScreenArgs {
@@ -268,9 +281,9 @@ struct ScreenArgs {
   float* part5;          // ... of screen16_kernel: [n_splits_a x 4 quarters][SC_TOPK + 1][q_pad], the same memory
   const float* tau;      // pass B's input, [q_pad] (screen_tau_kernel)
   uint2* recs;           // [q_pad][SC_SLOTS_MAX], empty (bits 0) on entry of pass B (pass C re-empties)
-  int32_t* ovf_cnt;      // [q_pad], zero on entry
-  uint2* ovf;            // [q_pad][ovf_cap]
-  int Q, q_pad, ovf_cap, sub_cap;
+  int32_t* ovf_cnt;      // [q_pad], zero on entry (screen16_kernel: the records in the query's list, set by the hand-over)
+  uint2* ovf;            // [q_pad][ovf_cap] (screen_kernel only)
+  int Q, q_pad, ovf_cap, sub_cap;   // (ovf_cap, sub_cap: screen_kernel only)
   int n_sel, tile_first, tile_stride;   // the pass covers tiles tile_first + j * tile_stride, j < n_sel
   int tiles_base, tiles_rem, n_splits;  // split s takes tiles_base selected tiles, the first tiles_rem one more
   int n_splits_a;
@@ -364,7 +377,7 @@ template <int HS>
 __global__ __launch_bounds__(64 * HO_PARTS_MAX) void screen_handover_kernel(
     const float* __restrict__ part5, int n_lane_slots, int q_pad, int Q, const int32_t* __restrict__ q_count,
     const float* __restrict__ qnorm, const uint8_t* __restrict__ qbad, float dmax, SampleGeom g, float* __restrict__ tau,
-    uint2* __restrict__ recs, unsigned int* __restrict__ inc) {
+    uint2* __restrict__ recs, int32_t* __restrict__ rec_cnt, unsigned int* __restrict__ inc) {
   MH_TRACE_SCOPE(mh::TK_TAU);
   __shared__ float s_b[HO_PARTS_MAX][64], s_s[HO_PARTS_MAX][64];
   __shared__ int s_cnt[HO_PARTS_MAX][64];
@@ -450,7 +463,7 @@ __global__ __launch_bounds__(64 * HO_PARTS_MAX) void screen_handover_kernel(
   // more records than slots (never seen): none is written, every lane slot's rows go to pass C's sweep instead
   const bool full = total > g.sa_slots;
   if (cnt && !full) {
-    uint2* mine = recs + (size_t)q * SC_SLOT_PITCH + SC_SLOTS_MAX + before;
+    uint2* mine = recs + (size_t)q * SC_SLOT_PITCH + before;   // the head of the query's list; pass B appends behind `total`
     const unsigned id_mask = (1u << g.pack_bits) - 1u;
     int n = 0;
 #pragma unroll
@@ -473,6 +486,7 @@ __global__ __launch_bounds__(64 * HO_PARTS_MAX) void screen_handover_kernel(
       qm = 0xFu;
     }
     tau[q] = t;
+    rec_cnt[q] = full ? 0 : total;
     if (inc) inc[q] = sm ? sm | (qm << 28) : 0u;
   }
 }
@@ -860,7 +874,7 @@ __global__ __launch_bounds__(64 * NW, 2) void screen_kernel(const ScreenArgs A) 
 //   - a record covers the 8 rows a lane holds of one query in a block: row0 = block + 4 quarter, bit 4 ti + r = row
 //     row0 + r + 16 ti; bit 31 of the record's row word marks the layout for pass C (the 32x32x16 records: bit r = row
 //     row0 + (r & 3) + 8 (r >> 2), 16 rows, all 16 mask bits in use);
-//   - a query's record slots are shared out over 4 x splits lane-private sub-lists (quarters) instead of 2 x splits;
+//   - a query's records go to ONE counted list (SC_SLOT_PITCH's comment), appended when the parked hits are written out;
 //   - pass A folds the lane's 8 rows of a block into ONE maximum per query (two blocks are still different rows).
 // Staging, swizzle (chunk ^ (row & 15): a 16-lane group reads 16 rows at one chunk index -- all 64 banks once), the
 // XCD-aware unit map, the parked records and the exactness argument are those of screen_kernel.
@@ -935,10 +949,9 @@ __global__ __launch_bounds__(512, 2) void screen16_kernel(const ScreenArgs A) {
     }
   // per-query state of the lane's 2 NQB queries.  Pass B is at the register limit (128 for the queries' operands, 32 + 16
   // + 16 for a row block's fragments, the accumulators and the pending block): the thresholds wait in LDS (two ds_read_b32
-  // per block, in the MFMAs' shadow) and the sub-lists' record counts are bytes of NQB / 2 registers.
+  // per block, in the MFMAs' shadow), and nobody counts records here: the queries' counts live in memory (flush_parked).
   // pass A: the lane's SC_TOPK largest packed block maxima per query, sorted, and the next largest value
   float pk[NQB][2][SC_PART5];
-  unsigned n_rec[(NQB + 1) / 2] = {};   // [nb >> 1]: byte 2 (nb & 1) + tj
   float* const tau_lds = reinterpret_cast<float*>(lds + SC_LDS16_TAU) + wave * 128;
 #pragma unroll
   for (int nb = 0; nb < NQB; ++nb)
@@ -962,23 +975,29 @@ __global__ __launch_bounds__(512, 2) void screen16_kernel(const ScreenArgs A) {
     for (int r = 3; r >= 0; --r) bits = __builtin_amdgcn_alignbit(bits, __float_as_uint(thr - d0[r]), 31);
     return (bits & 0xFFu) | ((unsigned)screen_record_value(top, thr) << 16);
   };
-  auto emit = [&](const v4f& d0, const v4f& d1, unsigned& nrec_word, int shift, int q, int row0, float top, float thr, int pos) {
-    const int nrec = (int)((nrec_word >> shift) & 0xFFu);
-    if (nrec < A.sub_cap) {   // (sub_cap <= SC_SLOTS_MAX / 4 = 64 < 256, static_assert at SB16_MAX: the byte cannot wrap)
-      const unsigned dst = (unsigned)q * SC_SLOT_PITCH + (4 * split + quarter) * A.sub_cap + nrec;
-      nrec_word += 1u << shift;
-      if (pos < SC_RECBUF16) {
-        uint4* e = recbuf + 3 * pos;
-        e[0] = make_uint4(dst, (unsigned)row0, __float_as_uint(thr), __float_as_uint(top));
-        e[1] = make_uint4(__float_as_uint(d0[0]), __float_as_uint(d0[1]), __float_as_uint(d0[2]), __float_as_uint(d0[3]));
-        e[2] = make_uint4(__float_as_uint(d1[0]), __float_as_uint(d1[1]), __float_as_uint(d1[2]), __float_as_uint(d1[3]));
-      } else {
-        A.recs[dst] = make_uint2((unsigned)row0 | SC_REC_LAYOUT16, record_bits8(d0, d1, top, thr));   // buffer full
-      }
+  // one more record into query q's list (the top of the file, "ONE counted list per query"): the place comes from the
+  // query's count; a record past the list's end is dropped, the count says so to pass C
+  auto append = [&](int q, int at, unsigned row0, unsigned bits) {
+    if (at < SC_SLOT_PITCH) A.recs[(size_t)q * SC_SLOT_PITCH + at] = make_uint2(row0 | SC_REC_LAYOUT16, bits);
+  };
+  // a hit waits in the wavefront's LDS buffer {q, row0, thr, top, 8 dots} for flush_parked; nothing here touches memory
+  // unless that buffer is full (an average sweep parks ~128 hits per wavefront against SC_RECBUF16 places)
+  auto emit = [&](const v4f& d0, const v4f& d1, int q, int row0, float top, float thr, int pos) {
+    if (pos < SC_RECBUF16) {
+      uint4* e = recbuf + 3 * pos;
+      e[0] = make_uint4((unsigned)q, (unsigned)row0, __float_as_uint(thr), __float_as_uint(top));
+      e[1] = make_uint4(__float_as_uint(d0[0]), __float_as_uint(d0[1]), __float_as_uint(d0[2]), __float_as_uint(d0[3]));
+      e[2] = make_uint4(__float_as_uint(d1[0]), __float_as_uint(d1[1]), __float_as_uint(d1[2]), __float_as_uint(d1[3]));
     } else {
-      const int opos = atomicAdd(&A.ovf_cnt[q], 1);
-      if (opos < A.ovf_cap) A.ovf[(size_t)q * A.ovf_cap + opos] = make_uint2((unsigned)row0 | SC_REC_LAYOUT16, record_bits8(d0, d1, top, thr));
-      if (pos < SC_RECBUF16) recbuf[3 * pos] = make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
+#ifdef MH_EXPERIMENTS
+      atomicAdd(&g_sc_direct_appends, 1ull);
+#endif
+      // buffer full.  (The list's address is worked out HERE: the lane's eight queries never change, and the compiler
+      // would keep eight 64-bit addresses across the sweep for this branch alone -- 16 registers this kernel does not have.)
+      const int at = atomicAdd(&A.ovf_cnt[q], 1);
+      int qa = q;
+      asm volatile("" : "+v"(qa));
+      append(qa, at, (unsigned)row0, record_bits8(d0, d1, top, thr));
     }
   };
   // the pending block: acc[ti][tj]; query tj of the lane = tiles (0, tj) and (1, tj)
@@ -986,27 +1005,44 @@ __global__ __launch_bounds__(512, 2) void screen16_kernel(const ScreenArgs A) {
     const unsigned long long h0 = __ballot(hit0), h1 = __ballot(hit1);
     if ((h0 | h1) == 0ull) return;
     if (hit0)
-      emit(p[0][0], p[1][0], n_rec[nb >> 1], 16 * (nb & 1), q0 + nb * 32 + l16, row0, m0, thr0,
+      emit(p[0][0], p[1][0], q0 + nb * 32 + l16, row0, m0, thr0,
            n_parked + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(h0 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)h0, 0u)));
     n_parked += __popcll(h0);
     if (hit1)
-      emit(p[0][1], p[1][1], n_rec[nb >> 1], 16 * (nb & 1) + 8, q0 + nb * 32 + 16 + l16, row0, m1, thr1,
+      emit(p[0][1], p[1][1], q0 + nb * 32 + 16 + l16, row0, m1, thr1,
            n_parked + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(h1 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)h1, 0u)));
     n_parked += __popcll(h1);
   };
+  // The wavefront's parked hits go to their queries' lists: lane j takes the parked records j, j + 64, j + 128.  Every
+  // atomic add of the flush is issued before the first returned place is looked at -- one round trip, at the end of the
+  // workgroup's sweep, outside the hit path.
   auto flush_parked = [&]() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    constexpr int TRIPS = (SC_RECBUF16 + 63) / 64;
     const int n = min(n_parked, SC_RECBUF16);
-    for (int j = lane; j < n; j += 64) {
-      const uint4 e = recbuf[3 * j];
-      if (e.x == 0xFFFFFFFFu) continue;
-      const uint4 x0 = recbuf[3 * j + 1], x1 = recbuf[3 * j + 2];
-      const v4f d0 = {__uint_as_float(x0.x), __uint_as_float(x0.y), __uint_as_float(x0.z), __uint_as_float(x0.w)};
-      const v4f d1 = {__uint_as_float(x1.x), __uint_as_float(x1.y), __uint_as_float(x1.z), __uint_as_float(x1.w)};
-      A.recs[e.x] = make_uint2(e.y | SC_REC_LAYOUT16, record_bits8(d0, d1, __uint_as_float(e.w), __uint_as_float(e.z)));
+    uint4 e[TRIPS];
+    int at[TRIPS];
+#pragma unroll
+    for (int i = 0; i < TRIPS; ++i) {
+      e[i] = make_uint4(0u, 0u, 0u, 0u);
+      if (lane + 64 * i < n) e[i] = recbuf[3 * (lane + 64 * i)];
     }
+#pragma unroll
+    for (int i = 0; i < TRIPS; ++i) {
+      at[i] = SC_SLOT_PITCH;
+      if (lane + 64 * i < n) at[i] = atomicAdd(&A.ovf_cnt[e[i].x], 1);
+    }
+#pragma unroll
+    for (int i = 0; i < TRIPS; ++i)
+      if (at[i] < SC_SLOT_PITCH) {
+        const int j = lane + 64 * i;
+        const uint4 x0 = recbuf[3 * j + 1], x1 = recbuf[3 * j + 2];
+        const v4f d0 = {__uint_as_float(x0.x), __uint_as_float(x0.y), __uint_as_float(x0.z), __uint_as_float(x0.w)};
+        const v4f d1 = {__uint_as_float(x1.x), __uint_as_float(x1.y), __uint_as_float(x1.z), __uint_as_float(x1.w)};
+        append((int)e[i].x, at[i], e[i].y, record_bits8(d0, d1, __uint_as_float(e[i].w), __uint_as_float(e[i].z)));
+      }
     __builtin_amdgcn_wave_barrier();
     n_parked = 0;
   };
@@ -1352,9 +1388,19 @@ __device__ __forceinline__ RsArgsPtr rs_args() {
 }
 
 // a query's slots in scan order: pass B's n_slots, then (one-sweep launches) the sa_slots of the sampled tiles' records,
-// which lie behind pass B's SC_SLOTS_MAX; then the overflow list
+// which lie behind pass B's SC_SLOTS_MAX; then the overflow list.  COMPACT (the counted list of the 16x16x32 launches):
+// the list's first 64 slots, whatever the count -- the slots behind a list's end are empty -- so that they travel with
+// the count and the other scalars; a longer list's remaining slots are fetched when the count is known (rescore_query)
+constexpr int RS_ITERS_C = (SC_SLOT_PITCH + 63) / 64;   // registers of slots a counted list can fill
+template <int COMPACT>
 __device__ __forceinline__ void rs_load_slots(const uint2* recs, int n_slots, int sa_slots, int q, int lane, uint2 (&rv)[RS_ITERS]) {
   const uint2* theirs = recs + (size_t)q * SC_SLOT_PITCH;
+  if (COMPACT) {
+    rv[0] = theirs[lane];
+#pragma unroll
+    for (int it = 1; it < RS_ITERS; ++it) rv[it] = make_uint2(0u, 0u);
+    return;
+  }
   const int n_own = n_slots + sa_slots;
 #pragma unroll
   for (int it = 0; it < RS_ITERS; ++it) {
@@ -1385,6 +1431,13 @@ __device__ __forceinline__ RsScalars rs_load_scalars(const uint8_t* qbad, const 
 
 // One query on one wavefront: `recv` its slots and `sc` what else it reads first (asked for by the caller), the four LDS
 // regions the wavefront's own.
+// COMPACT: the query's records are one counted list (SC_SLOT_PITCH's comment), `sc.n_ovf` its count, `recv[0]` its first
+// 64 slots.  Nothing below depends on the ORDER of a query's records, which the appends of concurrent wavefronts leave
+// open: the thinning bound is the second largest of the records' lower bounds (max / min folds), the keep / drop test
+// looks at one record at a time, candidates and surviving sampled records get their LDS places from counters (the
+// sampled pairs are evaluated row by row whatever their pairing), and the exact top-2 breaks ties by row number.
+static_assert(RS_ITERS_C <= RS_ITERS, "a counted list's slots fit the registers the scan has");
+template <int COMPACT>
 __device__ __forceinline__ void rescore_query(
     int q, int lane, float* q_sw, int* cand_sw, int* samp_sw, int* ncand_sw, int* nsamp_sw, uint2 (&recv)[RS_ITERS], const RsScalars sc, int Qe,
     const float* __restrict__ db, const float* __restrict__ dnorm, int N,
@@ -1393,8 +1446,9 @@ __device__ __forceinline__ void rescore_query(
     unsigned int* __restrict__ stats, int32_t zero_idx, float zero_d1, float zero_d2, SampleGeom g,
     unsigned int* __restrict__ inc_count, const _Float16* __restrict__ dbh, const float* __restrict__ dneg) {
   uint2* mine = recs + (size_t)q * SC_SLOT_PITCH;
-  const int n_own = n_slots + g.sa_slots;
-  auto slot_at = [&](int j) -> uint2& { return mine[j < n_slots ? j : SC_SLOTS_MAX + (j - n_slots)]; };
+  // (COMPACT: the records the list holds; a count above the capacity = records were dropped = brute force)
+  const int n_own = COMPACT ? min(sc.n_ovf, SC_SLOT_PITCH) : n_slots + g.sa_slots;
+  auto slot_at = [&](int j) -> uint2& { return mine[COMPACT || j < n_slots ? j : SC_SLOTS_MAX + (j - n_slots)]; };
   const int bad = sc.bad;
   const float nq = sc.nq;
   const float tau_q = sc.tau_q;
@@ -1436,7 +1490,7 @@ __device__ __forceinline__ void rescore_query(
   q_sw[2 * lane] = qv.x;
   q_sw[2 * lane + 1] = qv.y;
   // ---- records -> candidate row list in LDS; the slots read are emptied for the next frame ----
-  bool brute = n_ovf > ovf_cap || bad == 1;
+  bool brute = n_ovf > (COMPACT ? SC_SLOT_PITCH : ovf_cap) || bad == 1;
   int n_cand = 0;
   if (!brute) {
     // Every record carries the largest screen value of its rows (f16, nearest).  Two different records hold different
@@ -1456,11 +1510,23 @@ __device__ __forceinline__ void rescore_query(
       if (rec.x & SC_REC_SAMPLE) screen_sample_bounds((unsigned short)(rec.y >> 16), tau_q, pert, dmax, lo, hi);
       else screen_record_bounds((unsigned short)(rec.y >> 16), rec.x & 0x3FFFFFFFu, tau_q, spread, N, dmax, lo, hi);
     };
+    // (COMPACT: a list of more than 64 records -- rare, and the same for the whole wavefront -- has the rest of its slots
+    // fetched in a second trip, and both loops then run over those registers as well)
+    const bool more = COMPACT && n_own > 64;
+    if (more) {
 #pragma unroll
-    for (int it = 0; it < RS_ITERS; ++it) {
+      for (int it = 1; it < RS_ITERS_C; ++it) {
+        const int j = it * 64 + lane;
+        recv[it] = j < n_own ? mine[j] : make_uint2(0u, 0u);
+      }
+    }
+    auto scan = [&](int it) {
       const int j = it * 64 + lane;
       uint2 rec = recv[it];
-      if (j < n_own) {
+      if (COMPACT) {
+        if (j < n_own) mine[j] = make_uint2(0u, 0u);
+        else rec = make_uint2(0u, 0u);
+      } else if (j < n_own) {
         if (rec.y) slot_at(j) = make_uint2(0u, 0u);
       } else if (j < n_own + n_ovf) {
         rec = ovf[(size_t)q * ovf_cap + (j - n_own)];
@@ -1472,6 +1538,16 @@ __device__ __forceinline__ void rescore_query(
         l2 = fmaxf(l2, fminf(l1, lo));
         l1 = fmaxf(l1, lo);
       }
+    };
+    if (COMPACT) {
+      scan(0);
+      if (more) {
+#pragma unroll
+        for (int it = 1; it < RS_ITERS_C; ++it) scan(it);
+      }
+    } else {
+#pragma unroll
+      for (int it = 0; it < RS_ITERS; ++it) scan(it);
     }
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -1480,8 +1556,7 @@ __device__ __forceinline__ void rescore_query(
       l1 = fmaxf(l1, o1);
     }
     const float keep_from = l2 - screen_margin(nq, dmax);   // -inf with fewer than two records: everything stays
-#pragma unroll
-    for (int it = 0; it < RS_ITERS; ++it) {
+    auto keep = [&](int it) {
       const uint2 rec = recv[it];
       unsigned bits = rec.y & 0xFFFFu;
       if (bits) {
@@ -1507,6 +1582,16 @@ __device__ __forceinline__ void rescore_query(
         const int w = atomicAdd(ncand_sw, 1);
         if (w < RS_MAXC) cand_sw[w] = row0 + (r & 3) + hi_stride * (r >> 2);
       }
+    };
+    if (COMPACT) {
+      keep(0);
+      if (more) {
+#pragma unroll
+        for (int it = 1; it < RS_ITERS_C; ++it) keep(it);
+      }
+    } else {
+#pragma unroll
+      for (int it = 0; it < RS_ITERS; ++it) keep(it);
     }
     wave_lds_sync();
     // The surviving sampled records, two per MFMA set: the rows whose screen value -- pass A's own, see sample_pair_values --
@@ -1532,7 +1617,7 @@ __device__ __forceinline__ void rescore_query(
     if (n_samp) wave_lds_sync();
     n_cand = *ncand_sw;
     if (n_cand > RS_MAXC) brute = true;
-  } else if (n_ovf > ovf_cap) {
+  } else if (COMPACT ? n_ovf > 0 : n_ovf > ovf_cap) {
     for (int j = lane; j < n_own; j += 64) slot_at(j) = make_uint2(0u, 0u);   // the lists overflowed: empty every slot
   }
   if (n_ovf && lane == 0) ovf_cnt[q] = 0;
@@ -1626,7 +1711,7 @@ __device__ __forceinline__ void rescore_query(
 // The product (<4, 0>, a wavefront per query) runs the loop once and keeps its form all the same: it is the form that was
 // measured (profiles/passc_persistent_ab.txt, the row WAVES=4), its arguments fetched next to their uses inside the
 // iteration and no scratch memory; the same per-query code without the loop around it was not measured.
-template <int WAVES, int PF>
+template <int WAVES, int PF, int COMPACT>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVES == 12 ? 6 : 8, WAVES == 12 ? 6 : 8))) void rescore_kernel(const RsArgs args) {
   MH_TRACE_SCOPE(mh::TK_PASS_C);
   // dynamic LDS (sixteen wavefronts' regions are more than the 64 KB a kernel may declare): [WAVES][DIM] query rows,
@@ -1640,7 +1725,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVE
   const int Qe = args.q_count ? min(args.Q, *RS_CONST(int32_t, args.q_count)) : args.Q;   // (the one value an iteration does not read anew)
   uint2 recv_next[RS_ITERS];
   RsScalars sc_next = {};
-  if (PF >= 1) rs_load_slots(args.recs, args.n_slots, args.g.sa_slots, q_first, lane0, recv_next);
+  if (PF >= 1) rs_load_slots<COMPACT>(args.recs, args.n_slots, args.g.sa_slots, q_first, lane0, recv_next);
   if (PF >= 2) sc_next = rs_load_scalars(args.qbad, args.qnorm, args.tau, args.ovf_cnt, args.inc, args.qn, q_first, lane0);
   for (int q = q_first;; q += q_stride) {
     // (what an iteration derives from the lane and the wavefront's number -- addresses, masks -- it derives anew, as it
@@ -1663,11 +1748,11 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVE
 #pragma unroll
       for (int it = 0; it < RS_ITERS; ++it) recv[it] = recv_next[it];
     } else {
-      rs_load_slots(A->recs, A->n_slots, A->g.sa_slots, q, lane, recv);
+      rs_load_slots<COMPACT>(A->recs, A->n_slots, A->g.sa_slots, q, lane, recv);
     }
     const RsScalars sc = PF >= 2 ? sc_next : rs_load_scalars(A->qbad, A->qnorm, A->tau, A->ovf_cnt, A->inc, A->qn, q, lane);
     if (PF >= 1 && q + q_stride < Q) {   // the next query of this wavefront: consumed an iteration from here
-      rs_load_slots(A->recs, A->n_slots, A->g.sa_slots, q + q_stride, lane, recv_next);
+      rs_load_slots<COMPACT>(A->recs, A->n_slots, A->g.sa_slots, q + q_stride, lane, recv_next);
       if (PF >= 2) sc_next = rs_load_scalars(A->qbad, A->qnorm, A->tau, A->ovf_cnt, A->inc, A->qn, q + q_stride, lane);
     }
     RowMap rmap;
@@ -1676,12 +1761,12 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVE
     rmap.nb = A->rmap.nb;
     rmap.base = A->rmap.base;
     const SampleGeom g = {A->g.sa_slots, A->g.pack_bits, A->g.tile_first, A->g.tile_stride, A->g.tiles_base, A->g.tiles_rem, A->g.n_sel};
-    rescore_query(q, lane, q_sw, cand_sw, samp_sw, ncand_sw, nsamp_sw, recv, sc, Qe, A->db, A->dnorm, A->N, rmap, A->recs,
+    rescore_query<COMPACT>(q, lane, q_sw, cand_sw, samp_sw, ncand_sw, nsamp_sw, recv, sc, Qe, A->db, A->dnorm, A->N, rmap, A->recs,
                   A->n_slots, A->ovf_cnt, A->ovf, A->ovf_cap, A->dmax, A->spread, A->idx1, A->d1, A->d2, A->stats, A->zero_idx,
                   A->zero_d1, A->zero_d2, g, A->inc_count, A->dbh, A->dneg);
   }
 }
-static_assert(std::is_same<decltype(&rescore_kernel<RS_WAVES, 0>), void (*)(RsArgs)>::value,
+static_assert(std::is_same<decltype(&rescore_kernel<RS_WAVES, 0, 0>), void (*)(RsArgs)>::value,
               "rs_args() reads RsArgs from offset 0 of the kernel argument segment: it must stay the only parameter");
 
 // The screen value of every (query, row) pair of a small problem, by the arithmetic of pass A: one wavefront per
@@ -1766,6 +1851,15 @@ extern "C" int mh_debug_screen_prof(unsigned long long out[8], int reset, int ab
   }
   g_sc_ablate = ablate;
   return 0;
+}
+#endif
+#ifdef MH_EXPERIMENTS
+// the counter since the last reset, or -1 (synchronises the device)
+extern "C" long long mh_debug_screen_direct_appends(int reset) {
+  unsigned long long v = 0, z = 0;
+  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_sc_direct_appends), sizeof v) != hipSuccess) return -1;
+  if (reset && hipMemcpyToSymbol(HIP_SYMBOL(g_sc_direct_appends), &z, sizeof z) != hipSuccess) return -1;
+  return (long long)v;
 }
 #endif
 
@@ -1893,12 +1987,12 @@ void launch_passes(ScreenArgs a, int Q, int qe, int n_tiles, int sample, int blo
   *n_slots_out = 2 * Sb * a.sub_cap;
 }
 
-// The launch policy of the 16x16x32 kernels (eight wavefronts; a query's slots shared out over 4 x splits sub-lists), as
+// The launch policy of the 16x16x32 kernels (eight wavefronts; a query's records in one counted list), as
 // host arithmetic: launch_passes16 launches what this says, screen_launch_plan shows it to the tests.
 struct Plan16 {
   bool onesweep;                                  // pass A hands its tiles' records over, pass B skips them
   int stride, tile_first, n_sel_a, Sa, pack_bits; // pass A
-  int n_sel_b, Sb, sub_cap;                       // pass B
+  int n_sel_b, Sb;                                // pass B
 };
 template <int NQB>
 Plan16 plan_passes16(int qe, int n_tiles, int sample, int blocks_a, int blocks_b) {
@@ -1931,15 +2025,13 @@ Plan16 plan_passes16(int qe, int n_tiles, int sample, int blocks_a, int blocks_b
   while ((1 << bits) < blocks_slot) ++bits;
   p.onesweep = onesweep_on && p.stride > 1 && bits <= SC_PACK_BITS_MAX;
   p.pack_bits = p.onesweep ? bits : 0;
-  // Pass B's splits.  A query's 256 record slots are shared out over 4 x Sb lane-private sub-lists here (the 32x32x16
-  // passes: 2 x Sb), and a sub-list needs room for three records or queries spill into the overflow list and from there
-  // into pass C's brute-force search (12 000 queries x 250 000 rows ran 42 splits with ONE slot per sub-list for a while:
-  // 42 brute-force queries per launch, pass C 10 ms instead of 0.03): Sb <= 21.  One workgroup per compute unit, so the
+  // Pass B's splits.  Sb <= 21 dates from the lane-private layout (a query's 256 slots shared out over 4 x Sb sub-lists,
+  // each with room for three records: 12 000 queries x 250 000 rows ran 42 splits with ONE slot per sub-list for a while,
+  // 42 brute-force queries per launch, pass C 10 ms instead of 0.03); the counted lists do not need it, and it stays
+  // because the launch geometry was not to change with them.  One workgroup per compute unit, so the
   // launch takes ceil(workgroups / 256) rounds of tiles / Sb tiles each: the Sb with the least rounds x tiles, the
   // larger of equals.  (blocks_b > 0: an experiment's request, capped the same way.)
   constexpr int SB16_MAX = SC_SLOTS_MAX / 12;
-  // screen16_kernel counts a query's records per sub-list in one byte of n_rec[]; sub_cap <= SC_SLOTS_MAX / (4 * Sb)
-  static_assert(SC_SLOTS_MAX / 4 < 256, "a sub-list's record count must fit the byte screen16_kernel keeps it in");
   p.n_sel_b = p.onesweep ? n_tiles - p.n_sel_a : n_tiles;
   p.Sb = 1;
   if (blocks_b > 0) {
@@ -1954,13 +2046,9 @@ Plan16 plan_passes16(int qe, int n_tiles, int sample, int blocks_a, int blocks_b
       }
     }
   }
-  // slots per sub-list: room for three records, and on a small DB ~96 slots per query in all (a query gets ~20 records)
-  // rather than everything the 256 slots allow -- pass C reads (and re-empties) every slot of every query, and on a
-  // shard of a few models, where few splits fill the chip, 8 slots per sub-list made that scan 2 KB per query where 768
-  // bytes do.  Large DBs keep all 256: their queries' record counts have a long tail (1 M rows, 32 000 queries, 8
-  // splits: 96 slots sent 117 queries per launch into pass C's brute-force search, 69 ms instead of 3).
-  const int slots_target = n_tiles >= 2048 ? SC_SLOTS_MAX : (n_tiles >= 512 ? 160 : 96);
-  p.sub_cap = std::max(1, std::min(std::max(3, (slots_target + 4 * p.Sb - 1) / (4 * p.Sb)), SC_SLOTS_MAX / (4 * p.Sb)));
+  // (No slots per sub-list and no slot target per query any more -- `sub_cap`, `slots_target` of the lane-private layout:
+  // a query's records go to one counted list of SC_SLOT_PITCH places whatever Sb is, and pass C reads by the count.  Sb's
+  // cap above is kept as it was: this plan's eight outputs are what the launches were measured with.)
   return p;
 }
 
@@ -1991,10 +2079,10 @@ void launch_passes16(ScreenArgs a, int Q, int qe, int n_tiles, int sample, int b
   static_assert(SC_SA_SPLITS_MAX <= 2 * HO_PARTS_MAX, "a thread of screen_handover_kernel holds at most 8 lane slots");
   if (p.Sa <= HO_PARTS_MAX)
     hipLaunchKernelGGL(screen_handover_kernel<4>, dim3((a.q_pad + 63) / 64), dim3(64, p.Sa), 0, s, (const float*)a.part5, 4 * p.Sa,
-                       a.q_pad, a.Q, a.q_count, a.qnorm, a.qbad, a.dmax, g, const_cast<float*>(a.tau), a.recs, inc);
+                       a.q_pad, a.Q, a.q_count, a.qnorm, a.qbad, a.dmax, g, const_cast<float*>(a.tau), a.recs, a.ovf_cnt, inc);
   else
     hipLaunchKernelGGL(screen_handover_kernel<8>, dim3((a.q_pad + 63) / 64), dim3(64, (p.Sa + 1) / 2), 0, s, (const float*)a.part5,
-                       4 * p.Sa, a.q_pad, a.Q, a.q_count, a.qnorm, a.qbad, a.dmax, g, const_cast<float*>(a.tau), a.recs, inc);
+                       4 * p.Sa, a.q_pad, a.Q, a.q_count, a.qnorm, a.qbad, a.dmax, g, const_cast<float*>(a.tau), a.recs, a.ovf_cnt, inc);
 #ifdef MH_EXPERIMENTS
   // what the records cost pass B: thresholds no value reaches (WRONG results: timing only)
   if (exp_int("MH_SCREEN_NO_HITS", 0)) hipMemsetAsync(const_cast<float*>(a.tau), 0x7f, (size_t)a.q_pad * sizeof(float), s);
@@ -2009,18 +2097,24 @@ void launch_passes16(ScreenArgs a, int Q, int qe, int n_tiles, int sample, int b
   a.n_splits = p.Sb;
   a.tiles_base = p.n_sel_b / p.Sb;
   a.tiles_rem = p.n_sel_b % p.Sb;
-  a.sub_cap = p.sub_cap;
+  // (no sub_cap: a query's records go to its one counted list, and pass C finds them by the count)
   hipLaunchKernelGGL((screen16_kernel<1, NQB>), dim3(nqb * p.Sb), dim3(512), SC_LDS16_BYTES, s, a);
   if (ev) hipEventRecord(ev[4], s);
-  *n_slots_out = 4 * p.Sb * a.sub_cap;
+  *n_slots_out = 0;
   *geom_out = g;
 }
 
-template <int WAVES, int PF>
-void launch_pass_c(int grid, hipStream_t s, const RsArgs& args) {
+template <int WAVES, int PF, int COMPACT>
+void launch_pass_c_layout(int grid, hipStream_t s, const RsArgs& args) {
   static DynLds attr;
-  attr.ensure(rescore_kernel<WAVES, PF>, rs_lds_bytes(WAVES));
-  hipLaunchKernelGGL((rescore_kernel<WAVES, PF>), dim3(grid), dim3(64 * WAVES), rs_lds_bytes(WAVES), s, args);
+  attr.ensure(rescore_kernel<WAVES, PF, COMPACT>, rs_lds_bytes(WAVES));
+  hipLaunchKernelGGL((rescore_kernel<WAVES, PF, COMPACT>), dim3(grid), dim3(64 * WAVES), rs_lds_bytes(WAVES), s, args);
+}
+// compact: the launch's records are counted lists (the 16x16x32 launches), else the lane-private slots + overflow list
+template <int WAVES, int PF>
+void launch_pass_c(int grid, hipStream_t s, const RsArgs& args, bool compact) {
+  if (compact) launch_pass_c_layout<WAVES, PF, 1>(grid, s, args);
+  else launch_pass_c_layout<WAVES, PF, 0>(grid, s, args);
 }
 
 // which kernels a MATCH launch runs on (launch_match_screen): queries per workgroup / 256, and whether the 16x16x32 passes
@@ -2147,15 +2241,15 @@ void launch_match_screen(const float* qn, const float* qnorm, int Q, const float
   const int fat_waves = pc_waves == 12 ? 12 : RS_WAVES_FAT;
   if (pc_waves != RS_WAVES && (pc_all || Q > RS_FAT_K * n_cus * RS_WAVES_FAT)) {
     const int cover = (Q + fat_waves - 1) / fat_waves, grid = pc_k > 0 ? std::min(cover, pc_k * n_cus) : cover;
-    if (fat_waves == 12 && pc_pf == 0) launch_pass_c<12, 0>(grid, s, ca);
-    else if (fat_waves == 12 && pc_pf == 1) launch_pass_c<12, 1>(grid, s, ca);
-    else if (fat_waves == 12) launch_pass_c<12, 2>(grid, s, ca);
-    else if (pc_pf == 0) launch_pass_c<RS_WAVES_FAT, 0>(grid, s, ca);
-    else if (pc_pf == 1) launch_pass_c<RS_WAVES_FAT, 1>(grid, s, ca);
-    else launch_pass_c<RS_WAVES_FAT, 2>(grid, s, ca);
+    if (fat_waves == 12 && pc_pf == 0) launch_pass_c<12, 0>(grid, s, ca, shape.passes16);
+    else if (fat_waves == 12 && pc_pf == 1) launch_pass_c<12, 1>(grid, s, ca, shape.passes16);
+    else if (fat_waves == 12) launch_pass_c<12, 2>(grid, s, ca, shape.passes16);
+    else if (pc_pf == 0) launch_pass_c<RS_WAVES_FAT, 0>(grid, s, ca, shape.passes16);
+    else if (pc_pf == 1) launch_pass_c<RS_WAVES_FAT, 1>(grid, s, ca, shape.passes16);
+    else launch_pass_c<RS_WAVES_FAT, 2>(grid, s, ca, shape.passes16);
   } else
 #endif
-  launch_pass_c<RS_WAVES, 0>((Q + RS_WAVES - 1) / RS_WAVES, s, ca);
+  launch_pass_c<RS_WAVES, 0>((Q + RS_WAVES - 1) / RS_WAVES, s, ca, shape.passes16);
   if (sb.ev) hipEventRecord(sb.ev[5], s);
 }
 

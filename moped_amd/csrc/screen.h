@@ -25,9 +25,14 @@ struct ScreenBufs {
   uint8_t* qbad = nullptr;         // [q_pad] queries the screen does not vouch for (brute force in pass C)
   float2* part = nullptr;          // [screen_part_bytes(q_pad)] pass A's output: per-split top-2 values, or the lane slots' lists of the one-sweep launches
   float* tau = nullptr;            // [q_pad] the queries' thresholds for pass B
-  uint2* recs = nullptr;           // [q_pad][screen_rec_slots()] candidate records, all empty between frames
-  int32_t* ovf_cnt = nullptr;      // [q_pad] records in the query's overflow list; zero between frames
-  uint2* ovf = nullptr;            // [q_pad][ovf_cap]
+  // [q_pad][screen_rec_slots()] candidate records, all empty between frames.  Two layouts share the memory and that
+  // invariant: lane-private sub-lists (+ the overflow list) in the 32x32x16 launches, ONE counted list per query from
+  // slot 0 in the 16x16x32 launches (match_screen.hip, SC_SLOT_PITCH)
+  uint2* recs = nullptr;
+  // [q_pad] zero between frames.  32x32x16 launches: records in the query's overflow list; 16x16x32 launches: records
+  // in the query's list (more than screen_rec_slots() = some were dropped, brute force in pass C)
+  int32_t* ovf_cnt = nullptr;
+  uint2* ovf = nullptr;            // [q_pad][ovf_cap] (32x32x16 launches)
   int ovf_cap = 0, q_pad = 0;
   hipEvent_t* ev = nullptr;        // optional [6]: recorded around prepare / pass A / thresholds / pass B / pass C (mh_match_timing)
   // optional lane (mh_lane_create): passes A and B -- the kernels whose workgroups need whole compute units -- run on
