@@ -877,11 +877,26 @@ int mh_depth_rules_debug_fetch(mh_ctx* ctx, int which, int slot, void* out_host,
  * mh_step_cluster reports a stepped frame's -- cl_model_host[c] = the model of cluster c (clusters in (model, emission)
  * order, the order POSE walks them), members of cluster c = members_host[cl_off_host[c] .. cl_off_host[c + 1]), indices
  * INSIDE that model's match list in the clusterer's member order.  Read from the per-model lists the clusterer wrote (the
- * flat cluster table is FILTER's by the end of a frame).  The same slots and errors as mh_frame_fetch_matches_slot;
+ * flat cluster table is FILTER's by the end of a frame).  A frame with several images (mh_frame_set_images) was
+ * clustered per (model, image) pair: the lists read are the pairs' (off2 over the (model, image, query) copy of the
+ * matches), clusters come in (model, image, emission) order, cl_model_host names the real model and the members are
+ * indices inside the PAIR's list.  The same slots and errors as mh_frame_fetch_matches_slot;
  * cl_off_host holds cap_clusters + 1 entries; more clusters or members than the caps -> MH_ERR_CAPACITY with
  * *n_clusters = their number. */
 int mh_frame_debug_fetch_clusters_slot(mh_ctx* ctx, int slot, int32_t* cl_model_host, int32_t* cl_off_host,
                                        int32_t* members_host, int cap_clusters, int cap_members, int32_t* n_clusters);
+/* For tests: the FLAT cluster table of frame `slot` as the device holds it -- the arrays POSE walks.  Reads, at the
+ * slot's arena offset, cl_model / cl_begin / cl_count (row k: cluster k's model, its first entry in ms_members as an
+ * absolute position in the frame's match list -- the (model, image, query) copy for a frame with several images --
+ * and its member count), FrameCounts::n_clusters into *n_clusters (the rows CLUSTER published, which no later stage
+ * writes: that many rows are copied) and the device word fs->n_clusters into *n_clusters_now (optional; the row count
+ * the NEXT stage would read: CLUSTER's until FILTER / FILTER2 rewrite table and word, so 0 after a whole frame whose
+ * FILTER2 kept nothing).  The rows are CLUSTER's only while no FILTER has kept an object (it rewrites the first
+ * `kept` rows).  The same slots and errors as mh_frame_fetch_matches_slot; more rows than cap_clusters ->
+ * MH_ERR_CAPACITY with *n_clusters = their number and the first cap_clusters rows copied. */
+int mh_frame_debug_fetch_cluster_table_slot(mh_ctx* ctx, int slot, int32_t* cl_model_host, int32_t* cl_begin_host,
+                                            int32_t* cl_count_host, int cap_clusters, int32_t* n_clusters,
+                                            int32_t* n_clusters_now);
 /* Device address of the frame's packed result block {int32 n; mh_object[cap]}
  * for exchange 2 (gather of per-rank objects); *bytes = its size. */
 int mh_frame_result_dev(mh_ctx* ctx, void** block_dev, int64_t* bytes);

@@ -193,6 +193,7 @@ EXPORTS = [
     "mh_models_add_rows", "mh_models_write_xml",
     "mh_depth_map_from_raw_dev", "mh_depth_map_from_raw_batch_dev", "mh_depth_map_from_raw_host",
     "mh_frame_run_kinect_raw_host",
+    "mh_frame_debug_fetch_cluster_table_slot",
 ]
 COMM_ID_BYTES = 128      # MH_COMM_ID_BYTES
 EX2_OBJECTS = 62         # MH_EX2_OBJECTS
@@ -287,6 +288,8 @@ def load():
         L.mh_linkage_debug_matrix.argtypes = [vp, vp, vp, i32, C.POINTER(mh_linkage_params), vp, vp]
         L.mh_linkage_debug_agglomerate.argtypes = [vp, vp, i32, f32, i32, i32, vp, vp, C.POINTER(C.c_int32)]
         L.mh_frame_debug_fetch_clusters_slot.argtypes = [vp, i32, vp, vp, vp, i32, i32, C.POINTER(C.c_int32)]
+        L.mh_frame_debug_fetch_cluster_table_slot.argtypes = [vp, i32, vp, vp, vp, i32, C.POINTER(C.c_int32),
+                                                              C.POINTER(C.c_int32)]
     L.mh_frame_set_depth_rules.argtypes = [vp, C.POINTER(mh_depth_rules), vp]
     L.mh_frame_enqueue_rest_strided.argtypes = [vp, vp, i32, vp, i32, i32, C.POINTER(mh_cam),
                                                 C.POINTER(mh_frame_params), C.c_uint64]
@@ -1704,6 +1707,17 @@ class Context:
         self._ck(self.L.mh_frame_debug_fetch_clusters_slot(self.h, int(slot), _ptr(cm), _ptr(co), _ptr(mem), cap_clusters,
                                                            cap_members, C.byref(n)), "mh_frame_debug_fetch_clusters_slot")
         return [(int(cm[c]), mem[co[c]:co[c + 1]].copy()) for c in range(n.value)]
+
+    def frame_debug_fetch_cluster_table_slot(self, slot=0, cap_clusters=4096):
+        """The flat cluster table of frame `slot` as the device holds it (the arrays POSE walks) -> (cl_model, cl_begin,
+        cl_count, n_now): the rows CLUSTER published (FrameCounts::n_clusters of them; cl_begin = absolute position in the
+        frame's match list) and the device's current row count (fs->n_clusters: 0 once a FILTER2 has kept nothing)."""
+        cm, cb, cc = (np.zeros(cap_clusters, np.int32) for _ in range(3))
+        n, now = C.c_int32(0), C.c_int32(0)
+        self._ck(self.L.mh_frame_debug_fetch_cluster_table_slot(self.h, int(slot), _ptr(cm), _ptr(cb), _ptr(cc), cap_clusters,
+                                                                C.byref(n), C.byref(now)),
+                 "mh_frame_debug_fetch_cluster_table_slot")
+        return cm[:n.value].copy(), cb[:n.value].copy(), cc[:n.value].copy(), now.value
 
     def frame_set_depth_rules(self, K=None, patch_size=64, feature_density=-1.0, match_density=-1.0, ratio_table=None,
                               maximum_depth=4.0, default_depth=1.0, cauchy_scale=0.1, off=False):

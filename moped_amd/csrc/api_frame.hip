@@ -1085,7 +1085,9 @@ int mh_frame_debug_fetch_clusters_slot(mh_ctx* ctx, int slot, int32_t* cl_model_
   int32_t M = 0;
   if (int rc = match_lists(ctx, who, slot, INT_MAX, &M, &a, &take)) return rc;
   const FrameState* fs = ctx->fs;
-  const int nm = ctx->n_models;
+  // a frame with several images: the clusterer's "models" were the (model, image) pairs, their lists off2 over mi_corr
+  const int pairs = fs->list_pairs > 1 ? fs->list_pairs : 1;
+  const int nm = ctx->n_models * pairs;
   if (M < 0 || M > fs->max_m || nm > fs->n_models_cap) {
     ctx->err = std::string(who) + ": inconsistent match count";
     return MH_ERR_HIP;
@@ -1095,7 +1097,7 @@ int mh_frame_debug_fetch_clusters_slot(mh_ctx* ctx, int slot, int32_t* cl_model_
   auto get = [&](std::vector<int32_t>& to, const int32_t* from, size_t n) {
     return hipMemcpy(to.data(), reinterpret_cast<const unsigned char*>(from) + a, n * sizeof(int32_t), hipMemcpyDeviceToHost);
   };
-  MH_HIP(ctx, get(off, fs->model_off, (size_t)nm + 1));
+  MH_HIP(ctx, get(off, pairs > 1 ? fs->off2 : fs->model_off, (size_t)nm + 1));
   MH_HIP(ctx, get(ncl, fs->ms_ncl, (size_t)nm));
   MH_HIP(ctx, get(start, fs->ms_cl_start, (size_t)M + nm + 1));
   if (M > 0) MH_HIP(ctx, get(mem, fs->ms_members, (size_t)M));
@@ -1113,7 +1115,7 @@ int mh_frame_debug_fetch_clusters_slot(mh_ctx* ctx, int slot, int32_t* cl_model_
         return MH_ERR_HIP;
       }
       if (n < cap_clusters) {
-        if (cl_model_host) cl_model_host[n] = m;
+        if (cl_model_host) cl_model_host[n] = m / pairs;
         if (cl_off_host) cl_off_host[n] = w;
       }
       for (int j = st[c]; j < st[c + 1]; ++j, ++w)
@@ -1124,6 +1126,41 @@ int mh_frame_debug_fetch_clusters_slot(mh_ctx* ctx, int slot, int32_t* cl_model_
   *n_clusters = n;
   if (n > cap_clusters || w > cap_members) {
     ctx->err = std::string(who) + ": more clusters or members than the caller's buffers hold";
+    return MH_ERR_CAPACITY;
+  }
+  return MH_OK;
+}
+
+int mh_frame_debug_fetch_cluster_table_slot(mh_ctx* ctx, int slot, int32_t* cl_model_host, int32_t* cl_begin_host,
+                                            int32_t* cl_count_host, int cap_clusters, int32_t* n_clusters,
+                                            int32_t* n_clusters_now) {
+  static const char* const who = "mh_frame_debug_fetch_cluster_table_slot";
+  if (!ctx || !ctx->fs || !n_clusters || cap_clusters < 0 || slot < 0 || slot >= MH_MAX_BATCH) return MH_ERR_ARG;
+  *n_clusters = 0;
+  if (n_clusters_now) *n_clusters_now = 0;
+  size_t a = 0;
+  int take = 0;
+  int32_t M = 0;
+  if (int rc = match_lists(ctx, who, slot, INT_MAX, &M, &a, &take)) return rc;   // (the stream is through with the frame)
+  const FrameState* fs = ctx->fs;
+  auto at = [a](const void* p) { return reinterpret_cast<const unsigned char*>(p) + a; };
+  FrameCounts fc;
+  int32_t now = 0;
+  MH_HIP(ctx, hipMemcpy(&fc, at(fs->counts), sizeof fc, hipMemcpyDeviceToHost));
+  MH_HIP(ctx, hipMemcpy(&now, at(fs->n_clusters), sizeof now, hipMemcpyDeviceToHost));
+  const int n = fc.n_clusters;
+  if (n < 0 || n > fs->max_clusters) {
+    ctx->err = std::string(who) + ": inconsistent cluster count";
+    return MH_ERR_HIP;
+  }
+  *n_clusters = n;
+  if (n_clusters_now) *n_clusters_now = now;
+  const size_t bytes = sizeof(int32_t) * (size_t)std::min(n, cap_clusters);
+  if (bytes > 0 && cl_model_host) MH_HIP(ctx, hipMemcpy(cl_model_host, at(fs->cl_model), bytes, hipMemcpyDeviceToHost));
+  if (bytes > 0 && cl_begin_host) MH_HIP(ctx, hipMemcpy(cl_begin_host, at(fs->cl_begin), bytes, hipMemcpyDeviceToHost));
+  if (bytes > 0 && cl_count_host) MH_HIP(ctx, hipMemcpy(cl_count_host, at(fs->cl_count), bytes, hipMemcpyDeviceToHost));
+  if (n > cap_clusters) {
+    ctx->err = std::string(who) + ": more clusters than the caller's buffers hold";
     return MH_ERR_CAPACITY;
   }
   return MH_OK;

@@ -53,6 +53,9 @@ struct FrameState {
   int ms_grid = 8;      // ... and of the CLUSTER launch: its cluster count + head room
   // result slots whose match lists are still in the arenas: [list_first, list_first + list_n) (frame_rest, from its call's slot)
   int list_first = 0, list_n = 1;
+  // ... and what CLUSTER's per-"model" lists of those frames are lists of: 1 = models (model_off), n_images > 1 = (model,
+  // image) pairs in (model, image) order (off2 over mi_corr) -- the debug reads of api_frame.hip follow it
+  int list_pairs = 1;
   // What the last launches found, written by the kernels' tails into host-visible (pinned, mapped) words and read -- without
   // any synchronisation: a guess is all it is -- when the next launches are sized: [0][f] (cluster, replica) tasks of POSE
   // in frame f of the batch, [1][f] of POSE2, [2][f] models that CLUSTER had to cluster.

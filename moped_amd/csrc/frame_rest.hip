@@ -418,6 +418,7 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
   stamp(ctx, 2);
   // CLUSTER (+ flat cluster table, snap[0..1])
   const bool have_depth = ctx->q_depth || dimg.img;
+  if (runs(1)) fs->list_pairs = multi ? ctx->n_images : 1;   // (several images: MeanShift only, see above)
   if (!runs(1)) {
   } else if (ctx->linkage_on && have_depth && dimg.img) {
     // moped3d: linkage over similarity matrices; 3 n^2 floats of scratch per model, n <= LK_CAP

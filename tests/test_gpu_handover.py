@@ -85,6 +85,15 @@ def test_six_step_calls_equal_the_frame_as_one_call(world, seed, n_vis):
         assert len(mine) == len(clusters)
         for members, ref in zip(mine, clusters):
             assert np.array_equal(members, ref)
+    # ... and the oracle's, for EVERY model -- not only those that made it into the table: a model with at least MinPts
+    # matches has exactly the oracle's clusters in the oracle's member order, a model the oracle gives none has none
+    assert np.count_nonzero(np.diff(r["off"]) >= prm.ms_min_pts) >= len(np.unique(r["cm"]))
+    for m in range(db.n_models):
+        q = r["mq"][r["off"][m]:r["off"][m + 1]]
+        oracle = orclib.meanshift(fr.uv[q], prm.ms_radius, prm.ms_merge, prm.ms_min_pts, prm.ms_max_iter)[0] \
+            if len(q) >= prm.ms_min_pts else []
+        mine = [r["mem"][r["co"][k]:r["co"][k + 1]].tolist() for k in np.nonzero(r["cm"] == m)[0]]
+        assert mine == [w.tolist() for w in oracle], m
     # the final objects: FILTER2's kept list, scores, bit for bit the one-call frame's
     score2, keep2, order2, co2, mem2 = r["f2"]
     final = r["lst"][order2]
