@@ -726,7 +726,8 @@ typedef struct mh_linkage_params {
 int mh_frame_set_cluster_linkage(mh_ctx* ctx, const mh_linkage_params* prm);
 /* The clusterer's scratch is three n x n similarity matrices per (model, frame) problem (CLUSTER_LINKAGE_CPU.hpp:573-704
  * keeps the same three as vector<vector<Float>>): sized for the worst case of what the context has reserved -- 3 x 1024 x
- * max matches floats per frame of a batch, 37 MB at 3 000 -- and bounded: a frame or batch that would need more than
+ * max matches floats per frame of a batch, 37 MB at 3 000 (MH_LINKAGE_ROWMAX, below: 3 x min(4096, max matches) x max
+ * matches, 108 MB at 3 000, and 48 bytes per model + 12 per match of plan and per-point arrays) -- and bounded: a frame or batch that would need more than
  * `bytes` (0 = the default, 4 GiB) fails with MH_ERR_CAPACITY before anything is allocated or launched. */
 int mh_set_linkage_scratch_limit(mh_ctx* ctx, size_t bytes);
 /* The step on its own, n_problems point sets (one per model) in one call: corr_host / depth_host
@@ -738,7 +739,7 @@ int mh_cluster_linkage(mh_ctx* ctx, const mh_corr* corr_host, const mh_depth* de
                        int n_problems, const mh_linkage_params* prm, int32_t* label, int32_t* order,
                        int32_t* n_clusters);
 /* For tests, in the style of mh_depth_rules_debug_fetch / mh_sift_debug_*: the clusterer's two halves on their own.
- * mh_linkage_debug_matrix: ONE problem of n matches (1 .. 1024) as mh_cluster_linkage takes it (cutoff, min_pts and
+ * mh_linkage_debug_matrix: ONE problem of n matches (1 .. 1024; MH_LINKAGE_ROWMAX: 1 .. 4096, also below) as mh_cluster_linkage takes it (cutoff, min_pts and
  *   linkage_type of *prm are not used) -> two n x n float matrices: A_host = the 3-D side after pass 2 -- K3D +
  *   discontinuity kernel (CLUSTER_LINKAGE_CPU.hpp:133-149, 231-285, 681), normalised, + / x K3F (:151-173, 683-692),
  *   BEFORE the division by its maximum (use3d_filter 0: the first sum, before its only normalisation) -- and K_host = the
@@ -754,6 +755,29 @@ int mh_linkage_debug_matrix(mh_ctx* ctx, const mh_corr* corr_host, const mh_dept
                             const mh_linkage_params* prm, float* A_host, float* K_host);
 int mh_linkage_debug_agglomerate(mh_ctx* ctx, const float* K_host, int n, float cutoff, int min_pts, int linkage_type,
                                  int32_t* label, int32_t* order, int32_t* n_clusters);
+/* How the linkage clusterer runs (opt-in, per context, like mh_depth_fill_set_mode; the default is MH_LINKAGE_SCAN:
+ * everything above as it is written, the 1024-point limit and its error codes included).  MH_LINKAGE_ROWMAX computes the
+ * same matrices and the same clusters with another schedule and takes 1 .. MH_LINKAGE_MAX_POINTS points per problem:
+ *   - the matrix stage runs on the whole grid, a launch per pass (plan, nearest neighbours, sigmas and fill weights,
+ *     passes 1-3 over 32 x 32 tiles of the upper triangle); every element by the same expressions as the default mode,
+ *     the two maxima by integer atomic maxima over the floats' bit patterns (values >= 0, NaN left out, order-independent),
+ *     so A and K are the default mode's bit for bit wherever both run;
+ *   - the agglomeration (one 1024-thread workgroup per problem) keeps every listed row's first maximum over its listed
+ *     later columns and rescans only the rows a merge invalidates -- about two per merge -- where the default mode
+ *     rescans every live pair per merge; clusters, member order and labels are the reference's, quirks included.
+ * In this mode mh_cluster_linkage, mh_linkage_debug_matrix, mh_linkage_debug_agglomerate and the frames of
+ * mh_frame_set_cluster_linkage (single frames and merged batches with their own maps) accept up to 4096 points per
+ * problem; 4097 -> MH_ERR_CAPACITY, nothing launched (in a frame: the first 4096 matches and the frame's capacity flag,
+ * as the default mode does at 1024).  Scratch: 3 n^2 floats per problem as before, within mh_set_linkage_scratch_limit.
+ * mh_linkage_set_mode: any other value -> MH_ERR_ARG, the mode stays.
+ * mh_linkage_stats: counted on the device by the row-maxima kernels since the last reset -- out[0] problems clustered,
+ * out[1] merges, out[2] rows rescanned (the first fill of the row maxima not counted), out[3] the largest n; reset != 0
+ * zeroes them.  Synchronises the context.  All zero in the default mode. */
+enum { MH_LINKAGE_SCAN = 0, MH_LINKAGE_ROWMAX = 1 };
+#define MH_LINKAGE_MAX_POINTS 4096
+int mh_linkage_set_mode(mh_ctx* ctx, int mode);
+int mh_linkage_get_mode(mh_ctx* ctx, int* mode);   /* (a user of a shared context saves the mode, sets its own, puts it back) */
+int mh_linkage_stats(mh_ctx* ctx, int64_t out[4], int reset);
 /* The two halves around exchange 1 when the DB is sharded over ranks.
  *   mh_frame_enqueue_match_local : normalise + this shard's top-2 -> top2_dev, a
  *       caller-owned device block of [3][Q] 32-bit words {idx1 (global row, int32),

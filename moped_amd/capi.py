@@ -66,6 +66,8 @@ STEP_OBJECT_DTYPE = np.dtype([("model", "<i4"), ("pose", "<f4", (7,))])   # mh_s
 DEPTH_DTYPE = np.dtype([("wx", "<f4"), ("wy", "<f4"), ("wz", "<f4"), ("w", "<f4")])
 DEPTH_BACKPROJECTION, DEPTH_REPROJECTION = 1, 2
 DEPTH_FILL_REPLAY, DEPTH_FILL_LEVELS = 0, 1   # mh_depth_fill_set_mode
+LINKAGE_SCAN, LINKAGE_ROWMAX = 0, 1   # mh_linkage_set_mode
+LINKAGE_MAX_POINTS = 4096   # points per problem in LINKAGE_ROWMAX (LINKAGE_SCAN: 1024)
 DEPTH_INFO_DTYPE = np.dtype([("depth_valid", "<i4"), ("coord3d", "<f4", (3,)), ("depth", "<f4"),
                              ("fill_distance", "<f4")])   # mh_depth_info
 POSE_OUT_DTYPE = np.dtype([("pose", "<f4", (7,)), ("cluster", "<i4"), ("n_inliers", "<i4"), ("err", "<f4")])
@@ -188,7 +190,7 @@ EXPORTS = [
     "mh_filter_depth_set_points", "mh_filter_depth", "mh_frame_set_filter_depth",
     "mh_frame_route", "mh_filter_depth_debug_form",
     "mh_depth_filter", "mh_depth_prop", "mh_frame_run_kinect_host",
-    "mh_linkage_debug_matrix", "mh_linkage_debug_agglomerate", "mh_frame_debug_fetch_clusters_slot",
+    "mh_linkage_debug_matrix", "mh_linkage_debug_agglomerate", "mh_linkage_set_mode", "mh_linkage_get_mode", "mh_linkage_stats", "mh_frame_debug_fetch_clusters_slot",
     "mh_planar_rows_dev", "mh_planar_rows_batch_dev", "mh_db_splice_image", "mh_db_splice_images",
     "mh_models_add_rows", "mh_models_write_xml",
     "mh_depth_map_from_raw_dev", "mh_depth_map_from_raw_batch_dev", "mh_depth_map_from_raw_host",
@@ -283,6 +285,10 @@ def load():
         L.mh_depth_fill_batch.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, i32, vp]
     L.mh_depth_fill_host.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.mh_frame_set_cluster_linkage.argtypes = [vp, C.POINTER(mh_linkage_params)]
+    if hasattr(L, "mh_linkage_set_mode"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
+        L.mh_linkage_set_mode.argtypes = [vp, i32]
+        L.mh_linkage_get_mode.argtypes = [vp, vp]
+        L.mh_linkage_stats.argtypes = [vp, vp, i32]
     L.mh_cluster_linkage.argtypes = [vp, vp, vp, vp, i32, C.POINTER(mh_linkage_params), vp, vp, vp]
     if hasattr(L, "mh_linkage_debug_matrix"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
         L.mh_linkage_debug_matrix.argtypes = [vp, vp, vp, i32, C.POINTER(mh_linkage_params), vp, vp]
@@ -1666,6 +1672,24 @@ class Context:
                 pos += sz
             out.append((clusters, lab.copy()))
         return out
+
+    def linkage_set_mode(self, mode: int):
+        """LINKAGE_SCAN (0, the default: one workgroup per problem rescans every live pair per merge; up to 1024 points)
+        or LINKAGE_ROWMAX (1: the matrix stage on the whole grid, the merge loop over cached row maxima -- the same
+        matrices and clusters, up to LINKAGE_MAX_POINTS points).  For cluster_linkage, the debug entries and the frames."""
+        self._ck(self.L.mh_linkage_set_mode(self.h, int(mode)), "mh_linkage_set_mode")
+
+    def linkage_get_mode(self) -> int:
+        mode = C.c_int(0)
+        self._ck(self.L.mh_linkage_get_mode(self.h, C.byref(mode)), "mh_linkage_get_mode")
+        return mode.value
+
+    def linkage_stats(self, reset=False):
+        """What the LINKAGE_ROWMAX kernels counted on the device since the last reset -> (problems clustered, merges,
+        rows rescanned, largest n).  Synchronises the context."""
+        out = np.zeros(4, np.int64)
+        self._ck(self.L.mh_linkage_stats(self.h, _ptr(out), 1 if reset else 0), "mh_linkage_stats")
+        return tuple(int(v) for v in out)
 
     # the clusterer's two halves on their own, for verification (mh_linkage_debug_*)
     def linkage_debug_matrix(self, uv, model_xyz, world_xyz, params=None):

@@ -31,6 +31,9 @@ void unpack_clusters(const int32_t* h, const int32_t* off, int n_problems, int32
   }
 }
 
+// points per problem in the context's mode (mh_linkage_set_mode)
+int linkage_cap(const mh_ctx* ctx) { return ctx->lk_mode == MH_LINKAGE_ROWMAX ? LK_MAX : LK_CAP; }
+
 // mh_cluster_linkage and the debug entries behind it, once the arguments are checked: upload, ONE launch of
 // linkage_batch_kernel, the clusters back.  `need`: floats of matrix scratch (3 n^2 per problem).  K_given (with
 // lp.given_matrix, one problem): its similarity matrix, in place of the matches.
@@ -46,7 +49,15 @@ int linkage_problems(mh_ctx* ctx, const mh_corr* corr_host, const mh_depth* dept
   const size_t b_depth = (size_t)total * sizeof(mh_depth);
   const size_t n_off = (size_t)n_problems + 1, n_start = (size_t)total + n_problems + 1;
   const size_t ints = n_off + 2 * (size_t)total + n_start + n_problems;
-  if ((rc = ensure_scratch(ctx, b_corr + b_depth + ints * sizeof(int32_t) + 64))) return rc;
+  // (MH_LINKAGE_ROWMAX: the plan, the headers and the per-point arrays of the matrix stage behind them)
+  const bool rowmax = ctx->lk_mode == MH_LINKAGE_ROWMAX;
+  const size_t b_ints = (ints * sizeof(int32_t) + 63) & ~(size_t)63;
+  const size_t b_aux = rowmax ? linkage_rowmax_aux_bytes(n_problems, total) : 0;
+  if (rowmax && !ctx->lk_stats) {
+    MH_HIP(ctx, ctx->lk_stats.ensure(4, ctx->stream));
+    MH_HIP(ctx, hipMemsetAsync(ctx->lk_stats, 0, 4 * sizeof(unsigned long long), ctx->stream));
+  }
+  if ((rc = ensure_scratch(ctx, b_corr + b_depth + b_ints + b_aux + 64))) return rc;
   if ((rc = ensure_pinned(ctx, (2 * (size_t)total + n_start + n_problems) * sizeof(int32_t)))) return rc;
   unsigned char* base = ctx->scratch;
   mh_corr* d_corr = (mh_corr*)base;
@@ -66,8 +77,16 @@ int linkage_problems(mh_ctx* ctx, const mh_corr* corr_host, const mh_depth* dept
   if (K_given)
     MH_HIP(ctx, hipMemcpyAsync(ctx->lk_scratch.p + (size_t)total * total, K_given, (size_t)total * total * sizeof(float),
                                hipMemcpyHostToDevice, s));
-  launch_linkage_batch(d_corr, d_depth, d_off, n_problems, ctx->depth_img, lp, ctx->lk_scratch, ctx->lk_scratch.cap,
-                       d_members, d_start, d_ncl, d_label, s);
+  if (rowmax) {
+    int n_tiles = 0, n_rowblocks = 0;
+    for (int p = 0; p < n_problems; ++p) linkage_rowmax_units(off[p + 1] - off[p], n_tiles, n_rowblocks);
+    launch_linkage_rowmax_batch(d_corr, d_depth, d_off, n_problems, total, n_tiles, n_rowblocks, ctx->depth_img, lp,
+                                ctx->lk_scratch, ctx->lk_scratch.cap, d_members, d_start, d_ncl, d_label,
+                                base + b_corr + b_depth + b_ints, ctx->lk_stats, s);
+  } else {
+    launch_linkage_batch(d_corr, d_depth, d_off, n_problems, ctx->depth_img, lp, ctx->lk_scratch, ctx->lk_scratch.cap,
+                         d_members, d_start, d_ncl, d_label, s);
+  }
   MH_HIP(ctx, hipGetLastError());
   int32_t* hbuf = (int32_t*)ctx->pinned.p;
   MH_HIP(ctx, hipMemcpyAsync(hbuf, d_members, (2 * (size_t)total + n_start + n_problems) * sizeof(int32_t),
@@ -313,8 +332,9 @@ int mh_cluster_linkage(mh_ctx* ctx, const mh_corr* corr_host, const mh_depth* de
       ctx->err = "mh_cluster_linkage: offsets must start at 0 and not decrease";
       return MH_ERR_ARG;
     }
-    if (n > LK_CAP) {
-      ctx->err = "mh_cluster_linkage: more than 1024 points in one problem";
+    if (n > linkage_cap(ctx)) {
+      ctx->err = ctx->lk_mode == MH_LINKAGE_ROWMAX ? "mh_cluster_linkage: more than 4096 points in one problem"
+                                                   : "mh_cluster_linkage: more than 1024 points in one problem";
       return MH_ERR_CAPACITY;
     }
     need += 3 * (size_t)n * n;
@@ -334,6 +354,34 @@ int mh_cluster_linkage(mh_ctx* ctx, const mh_corr* corr_host, const mh_depth* de
   return linkage_problems(ctx, corr_host, depth_host, off, n_problems, need, lp, nullptr, label, order, n_clusters);
 }
 
+int mh_linkage_set_mode(mh_ctx* ctx, int mode) {
+  if (!ctx) return MH_ERR_ARG;
+  if (mode != MH_LINKAGE_SCAN && mode != MH_LINKAGE_ROWMAX) {
+    ctx->err = "mh_linkage_set_mode: MH_LINKAGE_SCAN or MH_LINKAGE_ROWMAX";
+    return MH_ERR_ARG;
+  }
+  ctx->lk_mode = mode;
+  return MH_OK;
+}
+
+int mh_linkage_get_mode(mh_ctx* ctx, int* mode) {
+  if (!ctx || !mode) return MH_ERR_ARG;
+  *mode = ctx->lk_mode;
+  return MH_OK;
+}
+
+int mh_linkage_stats(mh_ctx* ctx, int64_t out[4], int reset) {
+  if (!ctx || !out) return MH_ERR_ARG;
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (!ctx->lk_stats) return MH_OK;   // (no MH_LINKAGE_ROWMAX call on this context yet)
+  if (int rc_enter = mh::enter(ctx)) return rc_enter;
+  static_assert(sizeof(int64_t) == sizeof(unsigned long long), "the counters are 64-bit words");
+  MH_HIP(ctx, hipMemcpyAsync(out, ctx->lk_stats, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (reset) MH_HIP(ctx, hipMemsetAsync(ctx->lk_stats, 0, 4 * sizeof(int64_t), ctx->stream));
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MH_OK;
+}
+
 int mh_linkage_debug_matrix(mh_ctx* ctx, const mh_corr* corr_host, const mh_depth* depth_host, int n,
                             const mh_linkage_params* prm, float* A_host, float* K_host) {
   if (!ctx) return MH_ERR_ARG;
@@ -341,9 +389,10 @@ int mh_linkage_debug_matrix(mh_ctx* ctx, const mh_corr* corr_host, const mh_dept
     ctx->err = "mh_linkage_debug_matrix: bad argument";
     return MH_ERR_ARG;
   }
-  if (n < 1 || n > LK_CAP) {
-    ctx->err = "mh_linkage_debug_matrix: one problem of 1 .. 1024 points";
-    return n > LK_CAP ? MH_ERR_CAPACITY : MH_ERR_ARG;
+  if (n < 1 || n > linkage_cap(ctx)) {
+    ctx->err = ctx->lk_mode == MH_LINKAGE_ROWMAX ? "mh_linkage_debug_matrix: one problem of 1 .. 4096 points"
+                                                 : "mh_linkage_debug_matrix: one problem of 1 .. 1024 points";
+    return n >= 1 ? MH_ERR_CAPACITY : MH_ERR_ARG;
   }
   if (!ctx->depth_img.img) {
     ctx->err = "mh_linkage_debug_matrix: no depth map (mh_frame_set_depth_image)";
@@ -380,9 +429,10 @@ int mh_linkage_debug_agglomerate(mh_ctx* ctx, const float* K_host, int n, float 
     ctx->err = "mh_linkage_debug_agglomerate: linkage_type must be 0 (minimum), 1 (average) or 2 (maximum)";
     return MH_ERR_ARG;
   }
-  if (n < 1 || n > LK_CAP) {
-    ctx->err = "mh_linkage_debug_agglomerate: a matrix of 1 .. 1024 rows";
-    return n > LK_CAP ? MH_ERR_CAPACITY : MH_ERR_ARG;
+  if (n < 1 || n > linkage_cap(ctx)) {
+    ctx->err = ctx->lk_mode == MH_LINKAGE_ROWMAX ? "mh_linkage_debug_agglomerate: a matrix of 1 .. 4096 rows"
+                                                 : "mh_linkage_debug_agglomerate: a matrix of 1 .. 1024 rows";
+    return n >= 1 ? MH_ERR_CAPACITY : MH_ERR_ARG;
   }
   LinkageParams lp;
   lp.cutoff = cutoff;

@@ -285,6 +285,8 @@ struct mh_ctx {
   int df_mode = 0;                    // mh_depth_fill_set_mode (MH_DEPTH_FILL_REPLAY); LEVELS: [status words | stats | per frame: depthfill.hip]
   int df_lv_frames = 0;               // frames of the last fill if it was a LEVELS one (mh_depth_fill_stats), else 0
   size_t lk_scratch_limit = (size_t)4 << 30;   // bytes; mh_set_linkage_scratch_limit
+  int lk_mode = 0;                                // mh_linkage_set_mode (MH_LINKAGE_SCAN)
+  mh::DevBuf<unsigned long long> lk_stats;        // MH_LINKAGE_ROWMAX: problems, merges, rows rescanned, largest n (mh_linkage_stats)
 
   // moped3d FILTER_PROJECTION_DEPTH instead of FILTER_PROJECTION (mh_filter_depth_set_points, mh_frame_set_filter_depth)
   struct FilterDepthState {

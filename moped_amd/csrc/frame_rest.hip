@@ -421,11 +421,29 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
   if (runs(1)) fs->list_pairs = multi ? ctx->n_images : 1;   // (several images: MeanShift only, see above)
   if (!runs(1)) {
   } else if (ctx->linkage_on && have_depth && dimg.img) {
-    // moped3d: linkage over similarity matrices; 3 n^2 floats of scratch per model, n <= LK_CAP
+    // moped3d: linkage over similarity matrices; 3 n^2 floats of scratch per model, n <= LK_CAP (MH_LINKAGE_ROWMAX: LK_MAX)
     // (a merged batch: every frame its own region)
-    const size_t need = 3 * (size_t)std::min(fs->max_m, LK_CAP) * (size_t)fs->max_m;
-    int rc = ensure_linkage_scratch(ctx, need * (size_t)std::max(1, batch_n));
+    const bool rowmax = ctx->lk_mode == MH_LINKAGE_ROWMAX;
+    const size_t need = 3 * (size_t)std::min(fs->max_m, rowmax ? LK_MAX : LK_CAP) * (size_t)fs->max_m;
+    const size_t frames = (size_t)std::max(1, batch_n);
+    // (ROWMAX: the plan, the headers and the per-point arrays of the matrix stage behind the frames' regions)
+    const size_t aux_floats = rowmax ? (linkage_rowmax_aux_bytes((size_t)nm * frames, (size_t)fs->max_m * frames) + 3) / 4 + 16 : 0;
+    int rc = ensure_linkage_scratch(ctx, need * frames + aux_floats);
     if (rc) return rc;
+    if (rowmax) {
+      if (!ctx->lk_stats) {
+        MH_HIP(ctx, ctx->lk_stats.ensure(4, s));
+        MH_HIP(ctx, hipMemsetAsync(ctx->lk_stats, 0, 4 * sizeof(unsigned long long), s));
+      }
+      // (the frames' regions first, `need` floats each; a frame alone has all that is left before the aux block)
+      const size_t region = batch_n > 1 ? need : ctx->lk_scratch.cap - aux_floats;
+      unsigned char* aux = reinterpret_cast<unsigned char*>(ctx->lk_scratch.p + ((ctx->lk_scratch.cap - aux_floats + 15) & ~(size_t)15));
+      launch_linkage_rowmax_models(fs->m_corr, reinterpret_cast<const float*>(fs->m_depth), fs->model_off, nm, fs->max_m, dimg,
+                                   ctx->linkage, ctx->lk_scratch, region, fs->ms_members, fs->ms_cl_start, fs->ms_ncl,
+                                   fs->max_clusters, fs->cl_model, fs->cl_begin, fs->cl_count, fs->n_clusters, snap,
+                                   fs->counts, fs->tickets + 0, s, ms_grid, b1, maps, fs->fb + 2 * MH_MAX_BATCH, aux,
+                                   ctx->lk_stats);
+    } else
     launch_linkage_models(fs->m_corr, reinterpret_cast<const float*>(fs->m_depth), fs->model_off, nm, dimg,
                           ctx->linkage, ctx->lk_scratch, batch_n > 1 ? need : ctx->lk_scratch.cap, fs->ms_members,
                           fs->ms_cl_start, fs->ms_ncl, fs->max_clusters, fs->cl_model, fs->cl_begin, fs->cl_count,

@@ -15,10 +15,11 @@
 // holds the agglomeration exactly, from the device's own matrix).  The agglomeration is the reference's, quirks included (see
 // oracle/linkage_oracle.cpp): per merge, a parallel arg-max over the candidate pairs in the
 // reference's scan order (first maximum wins), the average-linkage row update, the reversed
-// append of the absorbed cluster.
+// append of the absorbed cluster.  The per-pair expressions are linkage_pair.h's, shared with linkage_rowmax.hip
+// (MH_LINKAGE_ROWMAX, mh_linkage_set_mode: another schedule for lists of up to 4096, the same bytes).
 #include <algorithm>
 
-#include "steps.h"
+#include "linkage_pair.h"
 
 namespace mh {
 
@@ -43,74 +44,6 @@ struct LkLds {
   int best_a, best_b;
   float dmat[LK_DLDS * LK_DLDS];
 };
-
-__device__ __forceinline__ float sq_dist(const float* a, const float* b, int n) {   // Pt::sqEuclDist: d = pt - this
-  float r = 0.f;
-  for (int x = 0; x < n; ++x) {
-    const float d = __fsub_rn(b[x], a[x]);
-    r = __fadd_rn(r, __fmul_rn(d, d));
-  }
-  return r;
-}
-
-__device__ __forceinline__ void saturate(int& x, int& y, int w, int h) {
-  x = x < 0 ? 0 : (x >= w ? w - 1 : x);
-  y = y < 0 ? 0 : (y >= h ? h - 1 : y);
-}
-
-// getDiscontinuityMatrix's element (:244-283): the largest difference between the slope of the
-// straight depth line from p to q and the slopes between consecutive Bresenham samples (:176-220).
-__device__ float discontinuity(const DepthImage& D, int px, int py, int qx, int qy) {
-  const float depthStart = D.img[(size_t)py * D.w + px].z, depthEnd = D.img[(size_t)qy * D.w + qx].z;
-  const int xDiff = px - qx, yDiff = py - qy;
-  const float imagePlaneDist = sqrtf((float)(xDiff * xDiff + yDiff * yDiff));
-  const float directAngle = atan2f(__fsub_rn(depthEnd, depthStart), imagePlaneDist);
-  int x0 = px, y0 = py, x1 = qx, y1 = qy, t;
-  const bool steep = abs(y1 - y0) > abs(x1 - x0);
-  if (steep) {
-    t = x0; x0 = y0; y0 = t;
-    t = x1; x1 = y1; y1 = t;
-  }
-  if (x0 > x1) {
-    t = x0; x0 = x1; x1 = t;
-    t = y0; y0 = y1; y1 = t;
-  }
-  const float deltaX = __fsub_rn((float)x1, (float)x0), deltaY = fabsf(__fsub_rn((float)y1, (float)y0));
-  const int yStep = (y0 < y1) ? 1 : -1;
-  int perStep = (x1 - x0) / 20;
-  if (perStep < 1) perStep = 1;
-  float error = 0.f;
-  const float deltaError = __fdiv_rn(deltaY, deltaX);
-  int y = y0;
-  float maxAngleDiff = -1.f;
-  int pax = 0, pay = 0;
-  bool have = false;
-  for (int x = x0; x <= x1;) {
-    const int cx = steep ? y : x, cy = steep ? x : y;
-    if (have) {
-      int ax = pax, ay = pay, bx = cx, by = cy;
-      saturate(ax, ay, D.w, D.h);
-      saturate(bx, by, D.w, D.h);
-      const float depth1 = D.img[(size_t)ay * D.w + ax].z, depth2 = D.img[(size_t)by * D.w + bx].z;
-      const float dx = (float)(pax - cx), dy = (float)(pay - cy);
-      const float pixDistance = sqrtf(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
-      const float pixAngle = atan2f(__fsub_rn(depth2, depth1), pixDistance);
-      const float angleDiff = fabsf(__fsub_rn(directAngle, pixAngle));
-      if (angleDiff > maxAngleDiff) maxAngleDiff = angleDiff;
-    }
-    pax = cx;
-    pay = cy;
-    have = true;
-    x += perStep;
-    if (x > x1) break;   // the values below are not used any more (and are NaN when p == q)
-    error = __fadd_rn(error, __fmul_rn(__fmul_rn(deltaError, (float)perStep), (float)yStep));
-    float intPart;
-    error = modff(error, &intPart);
-    y = (int)__fadd_rn((float)y, intPart);
-  }
-  const float discontinuityDiv = (float)(-2 * (M_PI / 128) * (M_PI / 128));
-  return expf(__fdiv_rn(__fmul_rn(maxAngleDiff, maxAngleDiff), discontinuityDiv));
-}
 
 // workgroup-wide maximum of `v` under the reference's `if (value > maxValue)` (NaN never wins), from -1
 __device__ float wg_max(LkLds& L, float v) {
@@ -144,7 +77,8 @@ __device__ void linkage_matrix(LkLds& L, int N, const DepthImage& D, const Linka
       float nn2 = __builtin_inff(), nn3 = __builtin_inff();   // Float = DBL_MAX
       for (int j = 0; j < N; ++j) {
         if (i == j) continue;
-        const float d2 = sqrtf(sq_dist(L.uv[i], L.uv[j], 2)), d3 = sqrtf(sq_dist(L.mx[i], L.mx[j], 3));
+        float d2, d3;
+        lk_nn_pair(L.uv[i], L.uv[j], L.mx[i], L.mx[j], d2, d3);
         if (nn2 > d2) nn2 = d2;
         if (nn3 > d3) nn3 = d3;
       }
@@ -168,14 +102,11 @@ __device__ void linkage_matrix(LkLds& L, int N, const DepthImage& D, const Linka
   }
   // ---- fill weights of adaptiveWeightSum (:331-337): 1.0 / (1 + (d*d/gammaSq)), gamma = 25 ----
   for (int i = tid; i < N; i += LK_THREADS) {
-    int x = (int)L.uv[i][0], y = (int)L.uv[i][1];
-    saturate(x, y, D.w, D.h);
-    const float d = D.fill ? D.fill[(size_t)y * D.w + x] : 0.f;
-    L.nn2[i] = (float)(1.0 / (double)__fadd_rn(1.f, __fdiv_rn(__fmul_rn(d, d), 625.f)));
+    L.nn2[i] = lk_fill_weight(D, L.uv[i]);
   }
   // ---- pass 1: K2D -> Dm, K3D + BK -> A, maximum (:133-149, 231-285, 681-682) ----
   const long long pairs = (long long)N * (N + 1) / 2;
-  const float two2 = __fmul_rn(__fmul_rn(2.f, k2DSigma), k2DSigma), two3 = __fmul_rn(__fmul_rn(2.f, k3DSigma), k3DSigma);
+  const float two2 = lk_two_sigma_sq(k2DSigma), two3 = lk_two_sigma_sq(k3DSigma);
   float mx = -1.f;
   // pair index p -> (i, j), i <= j, row-major over the upper triangle: a thread walks its pairs incrementally
   auto row_start = [&](long long i) { return i * N - i * (i - 1) / 2; };
@@ -190,12 +121,8 @@ __device__ void linkage_matrix(LkLds& L, int N, const DepthImage& D, const Linka
   for (long long p = tid; p < pairs; p += LK_THREADS) {
     int i, j;
     first_pair(p, i, j);
-    const float v2 = expf(__fdiv_rn(__fmul_rn(-1.f, sq_dist(L.uv[i], L.uv[j], 2)), two2));
-    const float v3 = expf(__fdiv_rn(__fmul_rn(-1.f, sq_dist(L.wx[i], L.wx[j], 3)), two3));
-    int ax = (int)L.uv[i][0], ay = (int)L.uv[i][1], bx = (int)L.uv[j][0], by = (int)L.uv[j][1];
-    saturate(ax, ay, D.w, D.h);
-    saturate(bx, by, D.w, D.h);
-    const float s = __fadd_rn(v3, discontinuity(D, ax, ay, bx, by));
+    float v2;
+    const float s = lk_pass1(D, L.uv[i], L.uv[j], L.wx[i], L.wx[j], two2, two3, v2);
     Dm[(size_t)i * N + j] = v2;
     A[(size_t)i * N + j] = s;
     if (s > mx) mx = s;
@@ -204,19 +131,10 @@ __device__ void linkage_matrix(LkLds& L, int N, const DepthImage& D, const Linka
   // ---- pass 2: normalise, x / + K3F, maximum (:151-173, 683-692) ----
   mx = -1.f;
   if (P.use3d_filter) {
-    const float sigma = 0.1f;
-    const float twoSigmaSq = __fmul_rn(__fmul_rn(2.f, sigma), sigma);
     for (long long p = tid; p < pairs; p += LK_THREADS) {
       int i, j;
       first_pair(p, i, j);
-      float val = 1.f;
-      if (i != j) {
-        const float dm = sqrtf(sq_dist(L.mx[i], L.mx[j], 3)), dr = sqrtf(sq_dist(L.wx[i], L.wx[j], 3));
-        const float de = __fdiv_rn(fabsf(__fsub_rn(dm, dr)), dm);
-        val = expf(__fdiv_rn(__fmul_rn(__fmul_rn(-1.f, de), de), twoSigmaSq));
-      }
-      const float e = __fdiv_rn(A[(size_t)i * N + j], max1);
-      const float s = P.use3d_filter == 1 ? __fadd_rn(e, val) : __fmul_rn(e, val);
+      const float s = lk_pass2(P.use3d_filter, i == j, L.mx[i], L.mx[j], L.wx[i], L.wx[j], A[(size_t)i * N + j], max1);
       A[(size_t)i * N + j] = s;
       if (s > mx) mx = s;
     }
@@ -226,12 +144,7 @@ __device__ void linkage_matrix(LkLds& L, int N, const DepthImage& D, const Linka
   for (long long p = tid; p < pairs; p += LK_THREADS) {
     int i, j;
     first_pair(p, i, j);
-    const float K2De = Dm[(size_t)i * N + j];
-    const float K3De = __fdiv_rn(A[(size_t)i * N + j], max2);
-    const float jointWeight = __fmul_rn(L.nn2[i], L.nn2[j]);
-    const float w2D = (float)(0.5 + 0.5 * (1.0 - (double)jointWeight));   // alpha + alphaBar*(1.0 - jointWeight)
-    const float w3D = __fmul_rn(0.5f, jointWeight);
-    const float val = __fadd_rn(__fmul_rn(w2D, K2De), __fmul_rn(w3D, K3De));
+    const float val = lk_pass3(Dm[(size_t)i * N + j], A[(size_t)i * N + j], max2, L.nn2[i], L.nn2[j]);
     Dm[(size_t)i * N + j] = val;
     Dm[(size_t)j * N + i] = val;
   }
@@ -352,24 +265,8 @@ __device__ void linkage_body(LkLds& L, const mh_corr* __restrict__ corr, const f
       nv[u] = 0.f;
       if (i < N) {
         const float da = Dm[(size_t)first * N + i], db = Dm[(size_t)second * N + i];
-        if (P.linkage_type == 1) {
-          const float a = __fmul_rn((float)S1, da), b = __fmul_rn((float)S2, db);
-          nv[u] = (float)((1.0 / (double)(S1 + S2)) * (double)__fadd_rn(a, b));
-        } else {
-          // minimum / maximum linkage (:506-507, :525): the reference recomputes min / max of K over the merged
-          // cluster's pairs (minimumLinkage :404-413, maximumLinkage :390-399); min over a union is the min of the two
-          // clusters' minima -- the row entries hold exactly those (singletons start as K itself) -- so the update is
-          // exact, no arithmetic.  A cluster i that is EMPTY (absorbed earlier) gets the reference's empty-loop value.
-          // (`second` is empty by the time the reference's loop runs; a merge may also have absorbed a cluster that was
-          // empty already -- the stale list entry of the scan, S2 = 0 -- and then changes nothing)
-          // The reference's loops compare with `<` / `>` from 1e20 / -1: a NaN similarity never becomes the minimum /
-          // maximum (fminf / fmaxf skip one NaN the same way), and over nothing but NaN the start value stays.
-          const bool empty = L.clsize[i] == 0 || i == second;
-          const float start = P.linkage_type == 0 ? 1e20f : -1.f;
-          float v = start;
-          if (!empty) v = S2 == 0 ? da : (P.linkage_type == 0 ? fminf(da, db) : fmaxf(da, db));
-          nv[u] = v != v ? start : v;
-        }
+        // average / minimum / maximum linkage (:506-526; lk_merged_value, linkage_pair.h)
+        nv[u] = lk_merged_value(P.linkage_type, da, db, S1, S2, L.clsize[i] == 0 || i == second);
       }
     }
     __threadfence_block();

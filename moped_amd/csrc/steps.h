@@ -181,6 +181,30 @@ void launch_linkage_models(const mh_corr* corr, const float* depth4, const int32
 void launch_linkage_batch(const mh_corr* corr, const float* depth4, const int32_t* off, int n_problems,
                           const DepthImage& dimg, const LinkageParams& prm, float* scratch, size_t scratch_floats,
                           int32_t* members, int32_t* cl_start, int32_t* ncl, int32_t* label, hipStream_t s);
+// MH_LINKAGE_ROWMAX (mh_linkage_set_mode; linkage_rowmax.hip): launch_linkage_batch's problems of up to LK_MAX points,
+// the matrix stage on the whole grid and the agglomeration over row maxima -- the same clusters.  n_tiles / n_rowblocks:
+// what the problems' sizes give (linkage_rowmax_units); aux: linkage_rowmax_aux_bytes of device memory; stats: the
+// context's four counters (mh_linkage_stats).
+constexpr int LK_MAX = 4096;   // == MH_LINKAGE_MAX_POINTS
+constexpr int LK_RM_TILE = 32;    // passes 1..3: a 256-thread workgroup per LK_RM_TILE x LK_RM_TILE tile of the upper triangle
+constexpr int LK_RM_ROWS = 256;   // nearest neighbours: rows per workgroup
+size_t linkage_rowmax_aux_bytes(size_t n_problems, size_t points);
+inline void linkage_rowmax_units(int n, int& n_tiles, int& n_rowblocks) {
+  const int nt = (n + LK_RM_TILE - 1) / LK_RM_TILE;
+  n_tiles += nt * (nt + 1) / 2;
+  n_rowblocks += (n + LK_RM_ROWS - 1) / LK_RM_ROWS;
+}
+void launch_linkage_rowmax_batch(const mh_corr* corr, const float* depth4, const int32_t* off, int n_problems, int total,
+                                 int n_tiles, int n_rowblocks, const DepthImage& dimg, const LinkageParams& prm,
+                                 float* scratch, size_t scratch_floats, int32_t* members, int32_t* cl_start, int32_t* ncl,
+                                 int32_t* label, unsigned char* aux, unsigned long long* stats, hipStream_t s);
+// ... and launch_linkage_models' frames (max_m: matches a frame's arrays hold; aux for n_models and max_m points per frame)
+void launch_linkage_rowmax_models(const mh_corr* corr, const float* depth4, const int32_t* model_off, int n_models, int max_m,
+                                  const DepthImage& dimg, const LinkageParams& prm, float* scratch, size_t scratch_floats,
+                                  int32_t* members, int32_t* cl_start, int32_t* ncl, int max_clusters, int32_t* cl_model,
+                                  int32_t* cl_begin, int32_t* cl_count, int32_t* n_clusters_out, int32_t* snap,
+                                  FrameCounts* counts, unsigned int* ticket, hipStream_t s, int grid, const FrameBatch* batch,
+                                  const DepthMaps* maps, int32_t* feedback, unsigned char* aux, unsigned long long* stats);
 
 // ---- pose ----------------------------------------------------------------------
 struct DevCam {

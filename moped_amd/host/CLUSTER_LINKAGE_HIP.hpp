@@ -5,6 +5,8 @@
 // Same constructor arguments (WeightGamma and Alpha are unused by the reference as well: its
 // adaptiveWeightSum call passes 0.5 and 25, :697).  LinkageType 0 (minimum), 1 (average: the shipped
 // configuration) and 2 (maximum) as the reference's update loop has them (:506-526).
+// One key of its own: RowMaxima (default 0; 1 = MH_LINKAGE_ROWMAX for this step's call -- the same clusters, match
+// lists of up to 4096 per model where the default refuses more than 1024; the session's mode is put back afterwards).
 // Reads matches[model] (coord2D, coord3D, depthData.coord3D), the depth map and its ".distance"
 // map (:577-593); writes clusters[model] in the reference's cluster and member order; sets
 // oldClusters when the step is named "CLUSTER" (:703).
@@ -22,12 +24,13 @@ class CLUSTER_LINKAGE_HIP : public MopedAlg {
   int LinkageType;
   Float Sigma2D;
   Float Sigma3D;
+  int RowMaxima;   // 0 / 1 (a config value)
 
  public:
   CLUSTER_LINKAGE_HIP(Float Cutoff, int MinPts, int Use3DFilter, Float WeightGamma, Float Alpha, int LinkageType,
                       Float Sigma2D, Float Sigma3D)
       : Cutoff(Cutoff), MinPts(MinPts), Use3DFilter(Use3DFilter), WeightGamma(WeightGamma), Alpha(Alpha),
-        LinkageType(LinkageType), Sigma2D(Sigma2D), Sigma3D(Sigma3D) {
+        LinkageType(LinkageType), Sigma2D(Sigma2D), Sigma3D(Sigma3D), RowMaxima(0) {
     capable = LinkageType >= 0 && LinkageType <= 2 && HipSession::get() != 0;
   }
 
@@ -38,8 +41,11 @@ class CLUSTER_LINKAGE_HIP : public MopedAlg {
     hipGetConfig(config, _stepName, _alg, "CLUSTER_LINKAGE_HIP", "WeightGamma", WeightGamma);
     hipGetConfig(config, _stepName, _alg, "CLUSTER_LINKAGE_HIP", "Alpha", Alpha);
     hipGetConfig(config, _stepName, _alg, "CLUSTER_LINKAGE_HIP", "LinkageType", LinkageType);
+    hipGetConfig(config, _stepName, _alg, "CLUSTER_LINKAGE_HIP", "RowMaxima", RowMaxima);
   }
-  void setConfig(map<string, string>&) {}
+  void setConfig(map<string, string>& config) {
+    hipSetConfig(config, _stepName, _alg, "CLUSTER_LINKAGE_HIP", "RowMaxima", RowMaxima);
+  }
 
   void process(FrameData& frameData) {
     frameData.clusters.resize(models->size());
@@ -79,6 +85,16 @@ class CLUSTER_LINKAGE_HIP : public MopedAlg {
       prm.sigma3d = Sigma3D;
       prm.linkage_type = LinkageType;
       vector<int32_t> label(total), order(total), ncl(n_problems);
+      // the session's context is shared: the mode is this step's for its own call only
+      struct Mode {
+        mh_ctx* ctx;
+        bool on;
+        int before;   // what another user of the session left: put back afterwards
+        Mode(mh_ctx* c, bool o) : ctx(c), on(o), before(MH_LINKAGE_SCAN) {
+          if (on && mh_linkage_get_mode(ctx, &before) == MH_OK) mh_linkage_set_mode(ctx, MH_LINKAGE_ROWMAX);
+        }
+        ~Mode() { if (on) mh_linkage_set_mode(ctx, before); }
+      } mode(ctx, RowMaxima != 0);
       if (mh_cluster_linkage(ctx, &corr[0], &depth[0], &off[0], n_problems, &prm, &label[0], &order[0], &ncl[0]) != MH_OK) {
         HipSession::warn("mh_cluster_linkage");
       } else {

@@ -42,6 +42,7 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
   int MaxKeypoints, DoubleImSize;   // config keys: keypoint capacity of the frame (2048), libsiftfast's DoubleImSize (1)
   int IncrementalModels;
   int LevelFill;   // config key: the frame's DEPTHFILL in MH_DEPTH_FILL_LEVELS mode (FillScale 4, 2, 1; 1280 x 960 frames)
+  int LinkageRowMaxima;   // config key: the frame's CLUSTER in MH_LINKAGE_ROWMAX mode (match lists of up to 4096 per model)
   unsigned long frameCounter;
   int32_t lastCounts[4];
 
@@ -63,7 +64,7 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
       : FillScale(FillScale), Bilinear(Bilinear), DescriptorSize(DescriptorSize), DescriptorType(DescriptorType),
         PatchSize(PatchSize), Density1(Density1), Density2(Density2),
         am(MinRatioMin, MinRatioMax, MaxRatioMin, MaxRatioMax, DimensionPeak, DimensionFade), Alpha(Alpha),
-        Kind(MH_DEPTH_BACKPROJECTION), MaxKeypoints(2048), DoubleImSize(1), IncrementalModels(0), LevelFill(0), frameCounter(0) {
+        Kind(MH_DEPTH_BACKPROJECTION), MaxKeypoints(2048), DoubleImSize(1), IncrementalModels(0), LevelFill(0), LinkageRowMaxima(0), frameCounter(0) {
     lk.cutoff = (float)Cutoff;
     lk.min_pts = MinPts;
     lk.use3d_filter = Use3DFilter;
@@ -97,6 +98,7 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
     hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "MaxKeypoints", MaxKeypoints);
     hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "DoubleImSize", DoubleImSize);
     hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "LevelFill", LevelFill);
+    hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "LinkageRowMaxima", LinkageRowMaxima);
   }
   void setConfig(map<string, string>& config) {
     hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "Density", Density1);
@@ -105,6 +107,7 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
     hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "DoubleImSize", DoubleImSize);
     hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "IncrementalModels", IncrementalModels);
     hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "LevelFill", LevelFill);
+    hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "LinkageRowMaxima", LinkageRowMaxima);
   }
 
   void process(FrameData& frameData) {
@@ -161,6 +164,9 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
     int fillModeBefore = MH_DEPTH_FILL_REPLAY;   // the session's context is shared: its mode is put back afterwards
     mh_depth_fill_get_mode(ctx, &fillModeBefore);
     if (LevelFill) mh_depth_fill_set_mode(ctx, MH_DEPTH_FILL_LEVELS);
+    int linkageModeBefore = MH_LINKAGE_SCAN;
+    mh_linkage_get_mode(ctx, &linkageModeBefore);
+    if (LinkageRowMaxima) mh_linkage_set_mode(ctx, MH_LINKAGE_ROWMAX);
     int rc = mh_frame_run_kinect_host(ctx, &gray->data[0], (float*)&depthmap->data[0],
                                       distanceMap ? (float*)&distanceMap->data[0] : 0, w, h, DoubleImSize, MaxKeypoints, &cam,
                                       &prm, FillScale, Bilinear ? 1 : 0, Kind, (float)Alpha,
@@ -173,14 +179,15 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
     // the context goes back to a plain one: another mh_frame_* user of the session must not inherit this pipeline's front end
     struct Restore {
       mh_ctx* ctx;
-      int fillMode;
+      int fillMode, linkageMode;
       ~Restore() {
         mh_frame_set_depth_rules(ctx, 0, 0);
         mh_frame_set_cluster_linkage(ctx, 0);
         mh_frame_set_depth_image(ctx, 0, 0, 0, 0, 0, 0.5f, 0.1f);
         mh_depth_fill_set_mode(ctx, fillMode);
+        mh_linkage_set_mode(ctx, linkageMode);
       }
-    } restore = {ctx, fillModeBefore};
+    } restore = {ctx, fillModeBefore, linkageModeBefore};
     if (rc != MH_OK) { HipSession::warn("mh_frame_run_kinect_host"); return; }
     if (fill) frameData.images.push_back(filled);
     // frameData.matches as the steps up to DEPTHPROP leave it, from the device's lists

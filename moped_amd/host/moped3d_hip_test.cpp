@@ -3,9 +3,10 @@
 // scene file (models + one frame: features or a gray image, the depth map, optionally its distance map), the frame's
 // lists printed after every step so that a test can hold each step against the oracle.
 //
-//   moped3d_hip_test [--resident] [--loop N] [--maps-out file] [--level-fill] scene.bin
+//   moped3d_hip_test [--resident] [--loop N] [--maps-out file] [--level-fill] [--linkage-rowmax] scene.bin
 //       --resident       the same scene through FRAME_RESIDENT_3D_HIP (one step, mh_frame_run_kinect_host)
 //       --level-fill     DEPTHFILL in MH_DEPTH_FILL_LEVELS mode (DEPTH_FILL_EXACT_HIP's levelFill, the one-step plugin's LevelFill key)
+//       --linkage-rowmax CLUSTER in MH_LINKAGE_ROWMAX mode (CLUSTER_LINKAGE_HIP's RowMaxima key, the one-step plugin's LinkageRowMaxima)
 //       --loop N         the frame N times; prints FPS (process() time only), the lists of the last frame
 //       --maps-out file  the frame's depth map [h][w][4] and distance map [h][w] (floats) as the steps left them
 //
@@ -110,18 +111,20 @@ static SP_Image make_image(const Scene& s, Image_Type type, const char* name, co
 }
 
 // moped3d/libmoped/src/config.hpp:38-49 with the HIP classes (UNDISTORTED_IMAGE: the scenes are undistorted)
-static void createPipeline(MopedPipeline& pipeline, const Scene& s, bool level_fill) {
+static CLUSTER_LINKAGE_HIP* createPipeline(MopedPipeline& pipeline, const Scene& s, bool level_fill) {
+  CLUSTER_LINKAGE_HIP* cluster = new CLUSTER_LINKAGE_HIP(0.1, 7, 2, 1, 0.0, 1, -1, -1);
   if (s.fill_scale != 0) pipeline.addAlg("DEPTHFILL", new DEPTH_FILL_EXACT_HIP(s.fill_scale, false, level_fill));
   if (s.Q == 0 && s.has_image) pipeline.addAlg("SIFT", new FEAT_SIFT_HIP("-1"));
   pipeline.addAlg("DEPTHFILTER", new DEPTHFILTER_HIP(s.patch, s.density1, 1));
   pipeline.addAlg("MATCH_SIFT", new MATCH_ADAPTIVE_BRUTE_HIP(128, "SIFT", 0.6, 0.75, 0.65, 0.8, 150, 50));
   pipeline.addAlg("DEPTHFILTER2", new DEPTHFILTER_HIP(s.patch, s.density2, 2));
   pipeline.addAlg("DEPTHPROP", new DEPTHMAP_PROP_HIP());
-  pipeline.addAlg("CLUSTER", new CLUSTER_LINKAGE_HIP(0.1, 7, 2, 1, 0.0, 1, -1, -1));
+  pipeline.addAlg("CLUSTER", cluster);
   pipeline.addAlg("POSE", new POSE_RANSAC_P3P_DEPTH_HIP(1024, 4, 5, 6, 8, 0.5));
   pipeline.addAlg("FILTER", new FILTER_PROJECTION_HIP(6, 4096., 2));
   pipeline.addAlg("POSE2", new POSE_RANSAC_P3P_DEPTH_HIP(1024, 4, 6, 8, 5, 0.5));
   pipeline.addAlg("FILTER2", new FILTER_PROJECTION_HIP(8, 8192., 1e-4));
+  return cluster;
 }
 
 static FRAME_RESIDENT_3D_HIP* createResidentPipeline(MopedPipeline& pipeline, const Scene& s) {
@@ -168,19 +171,20 @@ static void print_frame(const char* step, const FrameData& fd, const Scene& s, c
 }
 
 int main(int argc, char** argv) {
-  bool resident = false, level_fill = false;
+  bool resident = false, level_fill = false, linkage_rowmax = false;
   int loop = 1;
   const char* maps_out = 0;
   int a = 1;
   for (; a < argc && argv[a][0] == '-'; ++a) {
     if (std::string(argv[a]) == "--resident") resident = true;
     else if (std::string(argv[a]) == "--level-fill") level_fill = true;
+    else if (std::string(argv[a]) == "--linkage-rowmax") linkage_rowmax = true;
     else if (std::string(argv[a]) == "--loop" && a + 1 < argc) loop = std::atoi(argv[++a]);
     else if (std::string(argv[a]) == "--maps-out" && a + 1 < argc) maps_out = argv[++a];
     else { a = argc; break; }   // an option nobody knows, or one without its value
   }
   if (a + 1 != argc || loop < 1) {
-    std::fprintf(stderr, "usage: %s [--resident] [--loop N] [--maps-out file] [--level-fill] scene.bin\n", argv[0]);
+    std::fprintf(stderr, "usage: %s [--resident] [--loop N] [--maps-out file] [--level-fill] [--linkage-rowmax] scene.bin\n", argv[0]);
     return 2;
   }
   Scene s;
@@ -194,8 +198,9 @@ int main(int argc, char** argv) {
   }
   MopedPipeline pipeline;
   FRAME_RESIDENT_3D_HIP* res = 0;
+  CLUSTER_LINKAGE_HIP* cluster = 0;
   if (resident) res = createResidentPipeline(pipeline, s);
-  else createPipeline(pipeline, s, level_fill);
+  else cluster = createPipeline(pipeline, s, level_fill);
   list<MopedAlg*> all = pipeline.getAlgs();
   map<string, string> config;
   for (list<MopedAlg*>::iterator it = all.begin(); it != all.end(); ++it) {
@@ -209,7 +214,12 @@ int main(int argc, char** argv) {
   if (res) {
     config["DEPTHFILL:0:FRAME_RESIDENT_3D_HIP/MaxKeypoints"] = toString(s.max_keypoints);
     if (level_fill) config["DEPTHFILL:0:FRAME_RESIDENT_3D_HIP/LevelFill"] = "1";
+    if (linkage_rowmax) config["DEPTHFILL:0:FRAME_RESIDENT_3D_HIP/LinkageRowMaxima"] = "1";
     res->setConfig(config);
+  }
+  if (cluster && linkage_rowmax) {
+    config["CLUSTER:0:CLUSTER_LINKAGE_HIP/RowMaxima"] = "1";
+    cluster->setConfig(config);
   }
   std::printf("CONFIG_KEYS %zu\n", config.size());
 

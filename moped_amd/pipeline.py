@@ -417,6 +417,12 @@ class FramePipeline:
         for c in self.ctxs:
             c.depth_fill_set_mode(mode)
 
+    def set_linkage_mode(self, mode: int):
+        """How the linkage clusterer of the frames runs, on every slot's context: capi.LINKAGE_SCAN (the default; match
+        lists of up to 1024 per model) or capi.LINKAGE_ROWMAX (the same clusters, lists of up to 4096)."""
+        for c in self.ctxs:
+            c.linkage_set_mode(mode)
+
     def set_filter_depth(self, points_xyz, points_off, f1=None, f2=None, depth_cam=None):
         """FILTER (f1) and / or FILTER2 (f2) of the frames enqueued from now on as moped3d's FILTER_PROJECTION_DEPTH: the
         pose of every object is tested against the frame's depth map, so enqueue_kinect_batch and the other depth-map

@@ -5,7 +5,9 @@ frame at a time.  Three figures: the step wiring (config.hpp:38-49 with the HIP 
 step FRAME_RESIDENT_3D_HIP (--resident), and the same frame composed through capi from device buffers (mh_depth_fill ->
 mh_frame_set_depth_image -> mh_frame_enqueue_image -> mh_frame_fetch; the raw map restored by a device copy per frame).
 
-    python scripts/moped3d_plugins_bench.py [N] [out.txt]"""
+    python scripts/moped3d_plugins_bench.py [N] [out.txt] [--linkage-rowmax]
+
+--linkage-rowmax: CLUSTER in MH_LINKAGE_ROWMAX mode in all three (the harness's flag of that name, linkage_set_mode)."""
 import os
 import re
 import subprocess
@@ -29,8 +31,10 @@ K, CAM0, H, W, CAP = synth.K_DEFAULT, synth.CAM_IDENTITY, 480, 640, 1024
 
 def main():
     import torch
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 200
-    out = sys.argv[2] if len(sys.argv) > 2 else None
+    rowmax = "--linkage-rowmax" in sys.argv
+    argv = [a for a in sys.argv if a != "--linkage-rowmax"]
+    n = int(argv[1]) if len(argv) > 1 else 200
+    out = argv[2] if len(argv) > 2 else None
     gray = np.ascontiguousarray(np.load(os.path.join(ROOT, "tests", "golden", "sift_ref_frames.npz"))["gray0"])
     c = capi.Context(0)
     xy, _, desc = c.sift(gray)
@@ -49,13 +53,13 @@ def main():
     raw[..., 1] = (v - K[3]) / K[1] * zmap
     raw[..., 3] = np.sqrt((raw[..., :3] ** 2).sum(-1))
     lines = ["scene: bundled frame 0 (%d keypoints) + 500 clutter rows, 640x480 'blobs' map unfilled, fill_scale 8; "
-             "%d synchronous frames each, the first not timed" % (len(xy), n)]
+             "%d synchronous frames each, the first not timed%s" % (len(xy), n, "; CLUSTER in MH_LINKAGE_ROWMAX mode" if rowmax else "")]
     with tempfile.TemporaryDirectory() as tmp:
         path = os.path.join(tmp, "scene_b.bin")
         dump_scene.dump_kinect(path, db_desc, db_xyz, model_of, 2, raw, K, CAM0, gray=gray, patch_size=64, feature_density=0.8,
                                match_density=0.01, fill_scale=8, max_keypoints=CAP)
         for name, args in (("step wiring (11 steps)", []), ("FRAME_RESIDENT_3D_HIP (--resident)", ["--resident"])):
-            r = subprocess.run([BIN] + args + ["--loop", str(n), path], capture_output=True, text=True, timeout=300)
+            r = subprocess.run([BIN] + args + (["--linkage-rowmax"] if rowmax else []) + ["--loop", str(n), path], capture_output=True, text=True, timeout=300)
             if r.returncode != 0:
                 raise SystemExit("%s: status %d\n%s" % (name, r.returncode, r.stderr[-2000:]))
             fps = re.search(r"^FPS (\S+)", r.stdout, re.M).group(1)
@@ -65,6 +69,8 @@ def main():
     c.reserve(CAP)
     c.frame_set_depth_rules(K, 64, 0.8, 0.01, moped3d.ratio_table(db_xyz, model_of, 2, K))
     c.frame_set_cluster_linkage(capi.default_linkage_params())
+    if rowmax:
+        c.linkage_set_mode(capi.LINKAGE_ROWMAX)
     dev = torch.device("cuda:0")
     t_gray, t_raw = torch.from_numpy(gray).to(dev), torch.from_numpy(raw).to(dev)
     t_map, t_fill = torch.empty_like(t_raw), torch.zeros((H, W), dtype=torch.float32, device=dev)
