@@ -447,6 +447,67 @@ int mh_frame_route(mh_ctx* ctx, int32_t out[4]);
  * ignore the setting. */
 int mh_filter_depth_debug_form(mh_ctx* ctx, int form);
 
+/* ---- object hulls ------------------------------------------------------------ */
+
+#define MH_HULL_LDS_POINTS 8192   /* points of one object the hull kernel sorts in LDS; more go through global scratch */
+
+/* Object::getObjectHull (include/moped.hpp:266-287; moped3d/libmoped/include/moped.hpp:402-422) with its getConvexHull
+ * (:293-327 / :346-380) for n_obj objects of the resident database, one workgroup per object, and beside it the
+ * footprint GLOBAL_DISPLAY draws (src/GLOBAL_DISPLAY.hpp:197-207): the eight projected corners of Model::boundingBox
+ * (min / max of the model's points, src/moped.cpp:107-125).  A synchronous round trip like mh_filter.
+ *   obj_model[n_obj], obj_pose[n_obj][7]: the objects; cam: the image (project(), include/moped.hpp:330-354).
+ *   hull_xy_host[n_obj][max_vertices][2]: the first min(n_vertices[o], max_vertices) vertices of object o in the
+ *   reference's order (the backward half of the chain, newest point first, then the forward half); rows beyond them are
+ *   not written.  n_vertices[n_obj]: the true count.  Collinear and duplicate points are dropped as the reference drops
+ *   them (det <= 0); one projected point gives an empty hull, two give both, none (the reference: undefined) an empty one.
+ *   n_behind[n_obj] (optional): model points with camera-frame z < 0.001.  They are LEFT OUT of the hull -- the
+ *   reference gives them (FLT_MAX, FLT_MAX) and feeds those to the chain, whose determinants then are inf - inf.
+ *   bbox_uv_host[n_obj][8][2] (optional): the corners in the order [x][y][z] of GLOBAL_DISPLAY.hpp:198-203, index 0 =
+ *   min, 1 = max; a corner with z < 0.001 is (FLT_MAX, FLT_MAX) as project() returns it.
+ * The hull is over the rows the store holds for the model: one descriptor type (the reference walks every type's points).
+ * The vertices are bit for bit the reference's for the same projected points.
+ * MH_ERR_ARG before any launch: a null pointer, max_vertices < 1, a model index outside the database, a non-finite pose
+ * or camera element (the reference's sort order of NaN is undefined), no database, a store whose rows are not grouped by
+ * model in ascending order or that was uploaded in blocks (mh_db_upload_blocks).  n_obj = 0: MH_OK, nothing is done. */
+int mh_object_hulls(mh_ctx* ctx, const int32_t* obj_model, const float* obj_pose, int n_obj, const mh_cam* cam,
+                    int max_vertices, float* hull_xy_host, int32_t* n_vertices, int32_t* n_behind, float* bbox_uv_host);
+
+/* Debug entry, like mh_filter_depth_debug_form: the device form mh_object_hulls runs.  0 (default): points strictly
+ * inside the octagon of the cloud's eight extreme points are discarded before the sort.  1: every point is sorted and
+ * chained.  The results are the same on every input the tests hold (DESIGN.md section 6 on why that is observed and
+ * not proved). */
+int mh_hull_debug_form(mh_ctx* ctx, int form);
+
+/* Hulls of every object of a frame, computed behind the frame on the device: what MopedBench's outputObjectCH writes for
+ * every object of every frame (moped3d/libmoped/src/MopedBench.cpp:153-174) and the display steps draw.
+ * mh_frame_set_hulls: max_vertices > 0 switches them on for the frames and batches enqueued afterwards, 0 (the default)
+ * off; image: the camera of a several-camera frame whose hulls are wanted (0 otherwise).  Such a frame runs ONE more
+ * launch behind FILTER2 (run_stage2 = 0: behind POSE) over the objects of its result slots -- a merged batch one launch for
+ * all its slots -- stream-ordered, without a host wait, the object counts read on the device; the prefilter form always
+ * (mh_hull_debug_form is not consulted).  Objects, counts and everything else of the frame are what they are without
+ * hulls.  The device block: MH_MAX_BATCH slots of the reserved max_objects (mh_reserve*) records.
+ * While hulls are on, refused with MH_ERR_ARG before anything is enqueued: the sharded entry points
+ * (mh_frame_enqueue_sharded*, mh_frame_enqueue_rest*: model indices are shard-local, exchange 2 carries no hulls), an
+ * `image` that is not among the frame's cameras, a store mh_object_hulls refuses. */
+int mh_frame_set_hulls(mh_ctx* ctx, int max_vertices, int image);
+/* The hulls of the frame in result slot `slot` (mh_frame_fetch_hulls: slot 0, as mh_frame_fetch), in the order of the
+ * objects mh_frame_fetch[_slot] returns: *n_objects = their number, and for the first min(*n_objects, max_objects) of
+ * them n_vertices / n_behind / bbox_uv_host / hull_xy_host[max_objects][max_vertices][2] as mh_object_hulls gives them
+ * (vertices beyond the frame's max_vertices or the array's were not kept).  Synchronises the context's stream.
+ * MH_ERR_ARG: the frame enqueued last into that slot ran with hulls off. */
+int mh_frame_fetch_hulls_slot(mh_ctx* ctx, int slot, int max_objects, int max_vertices, float* hull_xy_host,
+                              int32_t* n_vertices, int32_t* n_behind, float* bbox_uv_host, int32_t* n_objects);
+int mh_frame_fetch_hulls(mh_ctx* ctx, int max_objects, int max_vertices, float* hull_xy_host, int32_t* n_vertices,
+                         int32_t* n_behind, float* bbox_uv_host, int32_t* n_objects);
+/* A whole batch's hulls into the caller's (page-locked) block in one stream-ordered copy, beside
+ * mh_frame_fetch_batch_async's objects: frame f's records lie at f * mh_frame_hull_block_stride(max_objects,
+ * max_vertices) -- max_vertices the value given to mh_frame_set_hulls -- record o = object o of the frame:
+ * {int32 n_vertices; int32 n_behind; float bbox_uv[8][2]; float hull_xy[max_vertices][2]}.  Records at and beyond the
+ * frame's object count (mh_frame_head::n_objects of the objects' block) are not meaningful.  mh_frame_fetch_wait waits
+ * for it too; one delivery in flight.  mh_frame_block_stride and mh_frame_head are unchanged. */
+size_t mh_frame_hull_block_stride(int max_objects, int max_vertices);
+int mh_frame_fetch_batch_hulls_async(mh_ctx* ctx, int B, int max_objects, void* host_block);
+
 /* ---- whole frame, device resident --------------------------------------------- */
 
 typedef struct {

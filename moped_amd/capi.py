@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MH_LIB_PATH") or os.path.join(_HERE, "libmoped_hip.so")  # override: A/B kernel builds
 
 MH_OK = 0
+MH_ERR_ARG = -1
 MH_ERR_CAPACITY = -3
 
 
@@ -196,12 +197,16 @@ EXPORTS = [
     "mh_depth_map_from_raw_dev", "mh_depth_map_from_raw_batch_dev", "mh_depth_map_from_raw_host",
     "mh_frame_run_kinect_raw_host",
     "mh_frame_debug_fetch_cluster_table_slot",
+    "mh_object_hulls", "mh_hull_debug_form",
+    "mh_frame_set_hulls", "mh_frame_fetch_hulls_slot", "mh_frame_fetch_hulls", "mh_frame_hull_block_stride",
+    "mh_frame_fetch_batch_hulls_async",
 ]
 COMM_ID_BYTES = 128      # MH_COMM_ID_BYTES
 EX2_OBJECTS = 62         # MH_EX2_OBJECTS
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)   # mh_allgather_fn
 
 DIM = 128   # MH_DESC_DIM
+HULL_LDS_POINTS = 8192   # MH_HULL_LDS_POINTS
 DB_INSERT, DB_REPLACE, DB_REMOVE = 0, 1, 2   # MH_DB_*
 _lib = None
 
@@ -458,6 +463,15 @@ def load():
         L.mh_db_splice_images.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, C.POINTER(mh_planar_spec), vp, vp, vp, vp, i32]
         L.mh_models_add_rows.argtypes = [vp, C.c_char_p, vp, vp, C.c_int64]
         L.mh_models_write_xml.argtypes = [vp, i32, C.c_char_p]
+    if hasattr(L, "mh_object_hulls"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
+        L.mh_object_hulls.argtypes = [vp, vp, vp, i32, C.POINTER(mh_cam), i32, vp, vp, vp, vp]
+        L.mh_hull_debug_form.argtypes = [vp, i32]
+        L.mh_frame_set_hulls.argtypes = [vp, i32, i32]
+        L.mh_frame_fetch_hulls_slot.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, C.POINTER(C.c_int32)]
+        L.mh_frame_fetch_hulls.argtypes = [vp, i32, i32, vp, vp, vp, vp, C.POINTER(C.c_int32)]
+        L.mh_frame_hull_block_stride.argtypes = [i32, i32]
+        L.mh_frame_hull_block_stride.restype = C.c_size_t
+        L.mh_frame_fetch_batch_hulls_async.argtypes = [vp, i32, i32, vp]
     _lib = L
     return L
 
@@ -551,6 +565,14 @@ FRAME_HEAD_DTYPE = np.dtype([("n_objects", "<i4"), ("flags", "<i4"), ("counts", 
 def frame_block_dtype(max_objects: int) -> np.dtype:
     """One record of a delivery block (mh_frame_fetch_batch_async): mh_frame_head + mh_object[max_objects]."""
     return np.dtype([("head", FRAME_HEAD_DTYPE), ("objects", OBJECT_DTYPE, (max_objects,))])
+
+
+def hull_block_dtype(max_objects: int, max_vertices: int) -> np.dtype:
+    """One frame of a hull delivery block (mh_frame_fetch_batch_hulls_async): max_objects records, object o's at [o]."""
+    rec = np.dtype([("n_vertices", np.int32), ("n_behind", np.int32), ("bbox_uv", np.float32, (8, 2)),
+                    ("hull_xy", np.float32, (max_vertices, 2))])
+    assert rec.itemsize * max_objects == load().mh_frame_hull_block_stride(max_objects, max_vertices)
+    return np.dtype([("objects", rec, (max_objects,))])
 
 
 def frame_block_bytes(B: int, max_objects: int) -> int:
@@ -1462,6 +1484,56 @@ class Context:
         """Debug: the device form filter_depth() scores with -- 0 the workgroup form (default), 1 the wave form the fused
         POSE tails run.  Frames ignore it."""
         self._ck(self.L.mh_filter_depth_debug_form(self.h, int(form)), "mh_filter_depth_debug_form")
+
+    # ---- object hulls ----
+    def object_hulls(self, obj_model, obj_pose, K, cam, max_vertices=64):
+        """mh_object_hulls: Object::getObjectHull of every object in the image (K, cam) + the projected corners of the
+        models' bounding boxes.  -> (hulls, n_vertices [n], n_behind [n], bbox_uv [n, 8, 2]); hulls[o] is [k, 2] with
+        k = min(n_vertices[o], max_vertices), in the reference's vertex order."""
+        obj_model = np.ascontiguousarray(obj_model, np.int32).reshape(-1)
+        obj_pose = np.ascontiguousarray(obj_pose, np.float32).reshape(-1, 7)
+        n = obj_model.shape[0]
+        assert obj_pose.shape[0] == n
+        xy = np.zeros((max(n, 1), max(int(max_vertices), 1), 2), np.float32)
+        nv = np.zeros(max(n, 1), np.int32)
+        nb = np.zeros(max(n, 1), np.int32)
+        bb = np.zeros((max(n, 1), 8, 2), np.float32)
+        c = make_cam(K, cam)
+        self._ck(self.L.mh_object_hulls(self.h, _ptr(obj_model), _ptr(obj_pose), n, C.byref(c), int(max_vertices), _ptr(xy),
+                                        _ptr(nv), _ptr(nb), _ptr(bb)), "mh_object_hulls")
+        hulls = [xy[o, :min(int(nv[o]), int(max_vertices))].copy() for o in range(n)]
+        return hulls, nv[:n], nb[:n], bb[:n]
+
+    def frame_set_hulls(self, max_vertices, image=0):
+        """mh_frame_set_hulls: frames and batches enqueued afterwards compute their objects' hulls (0 = off)."""
+        self._ck(self.L.mh_frame_set_hulls(self.h, int(max_vertices), int(image)), "mh_frame_set_hulls")
+
+    def frame_fetch_hulls(self, slot=None, max_objects=4096, max_vertices=64):
+        """mh_frame_fetch_hulls[_slot]: the hulls of the frame in result slot `slot` (None: mh_frame_fetch's frame), in the
+        order of its objects.  -> (hulls, n_vertices [n], n_behind [n], bbox_uv [n, 8, 2]) as object_hulls gives them."""
+        xy = np.zeros((max(max_objects, 1), max(int(max_vertices), 1), 2), np.float32)
+        nv = np.zeros(max(max_objects, 1), np.int32)
+        nb = np.zeros(max(max_objects, 1), np.int32)
+        bb = np.zeros((max(max_objects, 1), 8, 2), np.float32)
+        n = C.c_int32(0)
+        if slot is None:
+            self._ck(self.L.mh_frame_fetch_hulls(self.h, max_objects, int(max_vertices), _ptr(xy), _ptr(nv), _ptr(nb), _ptr(bb),
+                                                 C.byref(n)), "mh_frame_fetch_hulls")
+        else:
+            self._ck(self.L.mh_frame_fetch_hulls_slot(self.h, int(slot), max_objects, int(max_vertices), _ptr(xy), _ptr(nv), _ptr(nb),
+                                                      _ptr(bb), C.byref(n)), "mh_frame_fetch_hulls_slot")
+        k = min(n.value, max_objects)
+        return [xy[o, :min(int(nv[o]), int(max_vertices))].copy() for o in range(k)], nv[:k].copy(), nb[:k].copy(), bb[:k].copy()
+
+    def frame_fetch_batch_hulls_async(self, B, max_objects, host_ptr):
+        """mh_frame_fetch_batch_hulls_async: B frames' hull records into the caller's pinned block (hull_block_dtype);
+        frame_fetch_wait() waits for it."""
+        self._ck(self.L.mh_frame_fetch_batch_hulls_async(self.h, B, max_objects, C.c_void_p(host_ptr)),
+                 "mh_frame_fetch_batch_hulls_async")
+
+    def hull_debug_form(self, form):
+        """Debug: the device form object_hulls() runs -- 0 the octagon prefilter (default), 1 sort and chain every point."""
+        self._ck(self.L.mh_hull_debug_form(self.h, int(form)), "mh_hull_debug_form")
 
     # ---- frame (device pointers as ints) ----
     def frame_enqueue(self, q_desc_ptr, q_uv_ptr, Q, K, cam, params: mh_frame_params, seed=1):

@@ -192,6 +192,7 @@ void mh_destroy(mh_ctx* ctx) {
     for (auto& e : set)
       if (e) hipEventDestroy(e);
   if (ctx->dlv.done) hipEventDestroy(ctx->dlv.done);
+  if (ctx->hulls.done) hipEventDestroy(ctx->hulls.done);
   if (ctx->lane_in) hipEventDestroy(ctx->lane_in);
   if (ctx->lane_out) hipEventDestroy(ctx->lane_out);
   if (ctx->own_stream) hipStreamDestroy(ctx->own_stream);
@@ -377,6 +378,11 @@ int mh_db_upload_raw(mh_ctx* ctx, const float* desc_host, const int32_t* model_o
       MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
       screen_from_stats(st, h);
     }
+  }
+  if (st->grouped) {   // the per-model row ranges for the kernels that walk a model's rows (hull.hip)
+    MH_HIP(ctx, st->model_begin_dev.ensure(st->model_begin.size(), s));
+    MH_HIP(ctx, hipMemcpyAsync(st->model_begin_dev, st->model_begin.data(), st->model_begin.size() * sizeof(int32_t),
+                               hipMemcpyHostToDevice, s));
   }
   MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
   st->N = N;

@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "frame.h"
+#include "hull.h"
 
 using namespace mh;
 
@@ -350,8 +351,107 @@ int mh_frame_fetch_batch_async(mh_ctx* ctx, int B, int max_objects, void* host_b
   return delivery_end(ctx, host_block, bytes, dst, B, max_objects, tag);
 }
 
+/* ---- object hulls behind the frames (hull.hip) ---- */
+
+int mh_frame_set_hulls(mh_ctx* ctx, int max_vertices, int image) {
+  if (!ctx) return MH_ERR_ARG;
+  if (max_vertices < 0 || max_vertices > (1 << 20) || image < 0 || image >= MH_MAX_IMAGES) {
+    ctx->err = "mh_frame_set_hulls: max_vertices 0 (off) .. 2^20, image 0 .. MH_MAX_IMAGES - 1";
+    return MH_ERR_ARG;
+  }
+  ctx->hulls.max_vertices = max_vertices;
+  ctx->hulls.image = image;
+  return MH_OK;
+}
+
+size_t mh_frame_hull_block_stride(int max_objects, int max_vertices) {
+  if (max_objects < 0 || max_vertices < 0) return 0;
+  return (size_t)max_objects * hull_record_words(max_vertices) * 4;
+}
+
+// the slot holds hulls (of the frame enqueued last into it), else MH_ERR_ARG with `who`
+static int hull_slot_ok(mh_ctx* ctx, const char* who, int slot) {
+  if (!ctx->fs || slot < 0 || slot >= MH_MAX_BATCH || ctx->hulls.slot_vertices[slot] <= 0 || !ctx->hulls.block) {
+    ctx->err = std::string(who) + ": the frame in that result slot ran without hulls (mh_frame_set_hulls before it is enqueued)";
+    return MH_ERR_ARG;
+  }
+  return MH_OK;
+}
+
+int mh_frame_fetch_hulls_slot(mh_ctx* ctx, int slot, int max_objects, int max_vertices, float* hull_xy_host,
+                              int32_t* n_vertices, int32_t* n_behind, float* bbox_uv_host, int32_t* n_objects) {
+  if (!ctx) return MH_ERR_ARG;
+  if (!n_objects || max_objects < 0 || max_vertices < 1 || (max_objects > 0 && (!hull_xy_host || !n_vertices))) {
+    ctx->err = "mh_frame_fetch_hulls: bad argument";
+    return MH_ERR_ARG;
+  }
+  if (int rc = hull_slot_ok(ctx, "mh_frame_fetch_hulls", slot)) return rc;
+  if (int rc_enter = mh::enter(ctx)) return rc_enter;
+  FrameState* fs = ctx->fs;
+  mh_ctx::HullState& hs = ctx->hulls;
+  hipStream_t s = ctx->stream;
+  int32_t head[4] = {0, 0, 0, 0};
+  MH_HIP(ctx, hipMemcpyAsync(head, fs->result + (size_t)slot * fs->result_bytes, sizeof head, hipMemcpyDeviceToHost, s));
+  MH_HIP(ctx, hipStreamSynchronize(s));
+  const int n = std::min(std::max(head[0], 0), fs->max_objects);   // the objects mh_frame_fetch_slot reports, in its order
+  *n_objects = n;
+  const int take = std::min(n, max_objects);
+  if (take == 0) return MH_OK;
+  const size_t rec = hull_record_words(hs.block_vertices);
+  if (int rc = ensure_pinned(ctx, (size_t)take * rec * 4)) return rc;
+  MH_HIP(ctx, hipMemcpyAsync(ctx->pinned.p, hs.block + (size_t)slot * hs.slot_bytes, (size_t)take * rec * 4, hipMemcpyDeviceToHost, s));
+  MH_HIP(ctx, hipStreamSynchronize(s));
+  const int32_t* const w = reinterpret_cast<const int32_t*>(ctx->pinned.p);
+  for (int o = 0; o < take; ++o) {
+    const int32_t* const r = w + (size_t)o * rec;
+    n_vertices[o] = r[0];
+    if (n_behind) n_behind[o] = r[1];
+    if (bbox_uv_host) std::memcpy(bbox_uv_host + 16 * (size_t)o, r + 2, 64);
+    const int kept = std::min(std::min(r[0], hs.block_vertices), max_vertices);
+    if (kept > 0) std::memcpy(hull_xy_host + 2 * (size_t)o * max_vertices, r + 18, (size_t)kept * 8);
+  }
+  return MH_OK;
+}
+
+int mh_frame_fetch_hulls(mh_ctx* ctx, int max_objects, int max_vertices, float* hull_xy_host, int32_t* n_vertices,
+                         int32_t* n_behind, float* bbox_uv_host, int32_t* n_objects) {
+  return mh_frame_fetch_hulls_slot(ctx, 0, max_objects, max_vertices, hull_xy_host, n_vertices, n_behind, bbox_uv_host, n_objects);
+}
+
+int mh_frame_fetch_batch_hulls_async(mh_ctx* ctx, int B, int max_objects, void* host_block) {
+  if (!ctx) return MH_ERR_ARG;
+  if (!host_block || B < 1 || B > MH_MAX_BATCH || max_objects < 1) {
+    ctx->err = "mh_frame_fetch_batch_hulls_async: bad argument";
+    return MH_ERR_ARG;
+  }
+  for (int f = 0; f < B; ++f)
+    if (int rc = hull_slot_ok(ctx, "mh_frame_fetch_batch_hulls_async", f)) return rc;
+  mh_ctx::HullState& hs = ctx->hulls;
+  if (hs.pending) {
+    ctx->err = "mh_frame_fetch_batch_hulls_async: the previous delivery has not been waited for (mh_frame_fetch_wait)";
+    return MH_ERR_ARG;
+  }
+  if (int rc_enter = mh::enter(ctx)) return rc_enter;
+  if (!hs.done) MH_HIP(ctx, hipEventCreateWithFlags(&hs.done, hipEventDisableTiming));
+  const size_t stride = mh_frame_hull_block_stride(std::min(max_objects, ctx->fs->max_objects), hs.block_vertices);
+  const size_t pitch = mh_frame_hull_block_stride(max_objects, hs.block_vertices);
+  MH_HIP(ctx, hipMemcpy2DAsync(host_block, pitch, hs.block, hs.slot_bytes, stride, (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(ctx, hipEventRecord(hs.done, ctx->stream));
+  hs.pending = true;
+  return MH_OK;
+}
+
 int mh_frame_fetch_query(mh_ctx* ctx) {
   if (!ctx) return MH_ERR_ARG;
+  if (ctx->hulls.pending) {   // (mh_frame_fetch_batch_hulls_async: enqueued behind the objects' delivery, so it ends last)
+    MH_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t eh = hipEventQuery(ctx->hulls.done);
+    if (eh == hipErrorNotReady) {
+      (void)hipGetLastError();
+      return 1;
+    }
+    MH_HIP(ctx, eh);
+  }
   if (!ctx->dlv.pending) return MH_OK;
   MH_HIP(ctx, hipSetDevice(ctx->device));
   const hipError_t e = hipEventQuery(ctx->dlv.done);
@@ -366,6 +466,11 @@ int mh_frame_fetch_query(mh_ctx* ctx) {
 int mh_frame_fetch_wait(mh_ctx* ctx, int32_t* flags_or) {
   if (!ctx) return MH_ERR_ARG;
   if (flags_or) *flags_or = 0;
+  if (ctx->hulls.pending) {   // (mh_frame_fetch_batch_hulls_async)
+    MH_HIP(ctx, hipSetDevice(ctx->device));
+    MH_HIP(ctx, hipEventSynchronize(ctx->hulls.done));
+    ctx->hulls.pending = false;
+  }
   auto& d = ctx->dlv;
   if (!d.pending) return MH_OK;
   MH_HIP(ctx, hipSetDevice(ctx->device));

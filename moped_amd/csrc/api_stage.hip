@@ -1,8 +1,10 @@
 // C ABI: the stand-alone stage calls on host pointers (CLUSTER / POSE / FILTER one step at a time: upload, launch, read
 // back).  They borrow the frame's working arrays (FrameState, frame.h), so each of them ends a stepped frame.
+#include <cmath>
 #include <cstring>
 
 #include "frame.h"
+#include "hull.h"
 
 using namespace mh;
 
@@ -668,6 +670,105 @@ int mh_filter_depth_debug_form(mh_ctx* ctx, int form) {
     return MH_ERR_ARG;
   }
   ctx->fdepth.debug_form = form;
+  return MH_OK;
+}
+
+// Object::getObjectHull (moped2/libmoped/include/moped.hpp:266-327) for n_obj objects + the projected corners of their
+// models' bounding boxes (src/GLOBAL_DISPLAY.hpp:197-207): hull.hip
+int mh_object_hulls(mh_ctx* ctx, const int32_t* obj_model, const float* obj_pose, int n_obj, const mh_cam* cam,
+                    int max_vertices, float* hull_xy_host, int32_t* n_vertices, int32_t* n_behind, float* bbox_uv_host) {
+  if (!ctx) return MH_ERR_ARG;
+  auto refuse = [&](const char* why) {
+    ctx->err = std::string("mh_object_hulls: ") + why;
+    return MH_ERR_ARG;
+  };
+  if (n_obj < 0 || !cam || max_vertices < 1) return refuse("bad argument");
+  if (n_obj == 0) return MH_OK;
+  if (!obj_model || !obj_pose || !hull_xy_host || !n_vertices) return refuse("null pointer");
+  const DbStore* st = ctx->store.get();
+  if (!st) return refuse("no model database");
+  if (!st->grouped) return refuse("the rows of the store are not grouped by model in ascending order");
+  if (st->n_blocks > 1) return refuse("the store was uploaded in blocks (a sharded store has no whole models)");
+  if ((size_t)n_obj * (size_t)max_vertices > ((size_t)1 << 28)) return refuse("n_obj * max_vertices above 2^28");
+  size_t stride = 0;   // global scratch per object: what the largest model among them may need
+  for (int o = 0; o < n_obj; ++o) {
+    const int m = obj_model[o];
+    if (m < 0 || m >= st->n_models) return refuse("object model outside [0, n_models)");
+    for (int k = 0; k < 7; ++k)
+      if (!std::isfinite(obj_pose[7 * (size_t)o + k])) return refuse("non-finite pose element");
+    stride = std::max(stride, hull_scratch_points(st->model_begin[m + 1] - st->model_begin[m]));
+  }
+  for (int k = 0; k < 4; ++k)
+    if (!std::isfinite(cam->K[k])) return refuse("non-finite camera");
+  for (int k = 0; k < 7; ++k)
+    if (!std::isfinite(cam->cam[k])) return refuse("non-finite camera");
+  if (int rc_enter = mh::enter(ctx)) return rc_enter;
+  // one device block: models | poses | n_vertices | n_behind | corners | vertices | sort scratch
+  const size_t n = (size_t)n_obj;
+  const size_t w_out = 2 * n + 16 * n + 2 * n * (size_t)max_vertices;   // words the host reads back
+  const size_t w_in = n + 7 * n;
+  const size_t bytes = (w_in + w_out) * 4 + 16 + n * stride * sizeof(float2);
+  int rc = ensure_scratch(ctx, bytes);
+  if (rc) return rc;
+  if ((rc = ensure_pinned(ctx, w_out * 4))) return rc;
+  hipStream_t s = ctx->stream;
+  int32_t* const d_model = reinterpret_cast<int32_t*>(ctx->scratch.p);
+  float* const d_pose = reinterpret_cast<float*>(d_model + n);
+  int32_t* const d_nv = reinterpret_cast<int32_t*>(d_pose + 7 * n);
+  int32_t* const d_nb = d_nv + n;
+  float* const d_bb = reinterpret_cast<float*>(d_nb + n);
+  float* const d_xy = d_bb + 16 * n;
+  const size_t scratch_at = ((w_in + w_out) * 4 + 15) & ~(size_t)15;
+  MH_HIP(ctx, hipMemcpyAsync(d_model, obj_model, n * 4, hipMemcpyHostToDevice, s));
+  MH_HIP(ctx, hipMemcpyAsync(d_pose, obj_pose, n * 28, hipMemcpyHostToDevice, s));
+  HullArgs a;
+  a.core.xyz = ctx->db_xyz;
+  a.core.model_begin = st->model_begin_dev;
+  a.core.n_models = st->n_models;
+  a.core.cam = make_devcam(*cam);
+  a.core.max_vertices = max_vertices;
+  a.core.form = ctx->hull_debug_form;
+  a.core.scratch = stride ? reinterpret_cast<float2*>(ctx->scratch.p + scratch_at) : nullptr;
+  a.core.scratch_stride = stride;
+  a.obj_model = d_model;
+  a.obj_pose = d_pose;
+  a.n_obj_dev = nullptr;
+  a.n_obj = n_obj;
+  a.hull_xy = d_xy;
+  a.n_vertices = d_nv;
+  a.n_behind = d_nb;
+  a.bbox_uv = d_bb;
+  launch_object_hulls(a, s);
+  MH_HIP(ctx, hipGetLastError());
+  // the counts and corners in one copy, then only the vertices that exist (a host array's rows beyond them stay untouched)
+  int32_t* const hp = reinterpret_cast<int32_t*>(ctx->pinned.p);
+  MH_HIP(ctx, hipMemcpyAsync(hp, d_nv, w_out * 4, hipMemcpyDeviceToHost, s));
+  MH_HIP(ctx, hipStreamSynchronize(s));
+  const float* const h_bb = reinterpret_cast<const float*>(hp + 2 * n);
+  const float* const h_xy = h_bb + 16 * n;
+  for (int o = 0; o < n_obj; ++o)
+    if (hp[o] < 0) {
+      ctx->err = "mh_object_hulls: the sort scratch was too small for an object";
+      return MH_ERR_HIP;
+    }
+  for (int o = 0; o < n_obj; ++o) {
+    n_vertices[o] = hp[o];
+    if (n_behind) n_behind[o] = hp[n + o];
+    const size_t kept = (size_t)std::min(hp[o], max_vertices);
+    std::memcpy(hull_xy_host + 2 * (size_t)o * max_vertices, h_xy + 2 * (size_t)o * max_vertices, kept * 8);
+  }
+  if (bbox_uv_host) std::memcpy(bbox_uv_host, h_bb, 16 * n * 4);
+  return MH_OK;
+}
+
+// which device form mh_object_hulls runs (a debug entry; frames ignore it)
+int mh_hull_debug_form(mh_ctx* ctx, int form) {
+  if (!ctx) return MH_ERR_ARG;
+  if (form != 0 && form != 1) {
+    ctx->err = "mh_hull_debug_form: 0 (the octagon prefilter) or 1 (sort and chain every point)";
+    return MH_ERR_ARG;
+  }
+  ctx->hull_debug_form = form;
   return MH_OK;
 }
 

@@ -52,6 +52,7 @@ struct DbStore {
   // are [model_begin[m], model_begin[m + 1]) (empty models allowed)
   bool grouped = false;
   std::vector<int32_t> model_begin;   // [n_models + 1] when grouped
+  mh::DevBuf<int32_t> model_begin_dev;   // ... and its device copy (hull.hip), written with it by the upload and by every edit
   uint64_t generation = 0;            // edits since the upload (mh_db_generation)
   hipEvent_t ready = nullptr;         // recorded behind the edit that filled this set (mh_db_adopt waits on it)
   std::shared_ptr<DbPool> pool;       // where the set parks when its last holder lets go (none: it is freed)
@@ -300,6 +301,22 @@ struct mh_ctx {
     mh_cam cam = {};              // the depth map's K and pose
     int debug_form = 0;           // mh_filter_depth_debug_form: 0 the workgroup form, 1 filter_depth_score_wave
   } fdepth;
+  int hull_debug_form = 0;          // mh_hull_debug_form: 0 the octagon prefilter, 1 sort and chain every point (hull.hip)
+  // object hulls behind the frames (mh_frame_set_hulls): one launch of hull_frame_kernel behind FILTER2 (or POSE)
+  struct HullState {
+    int max_vertices = 0;             // 0 = off
+    int image = 0;                    // the camera of a several-camera frame whose hulls are wanted
+    mh::DevBuf<unsigned char> block;  // device [MH_MAX_BATCH] slots of max_objects records (hull_record_words, hull.h)
+    size_t slot_bytes = 0;            // ... bytes of a slot: the frame state's max_objects records
+    int block_vertices = 0;           // ... whose records hold that many vertices
+    mh::DevBuf<float2> scratch;       // sort scratch of the launch's workgroups (models of more than MH_HULL_LDS_POINTS rows)
+    const DbStore* scratch_store = nullptr;   // ... sized for the largest model of this store
+    uint64_t scratch_generation = 0;          // ... at this generation
+    // per result slot: the max_vertices the frame enqueued last into it ran with (0: hulls were off, or no frame yet)
+    int slot_vertices[MH_MAX_BATCH] = {};
+    hipEvent_t done = nullptr;        // mh_frame_fetch_batch_hulls_async: recorded behind the copy (mh_frame_fetch_wait)
+    bool pending = false;
+  } hulls;
   // the last frame or batch enqueued: frames, 1 = they shared their launches, 1 = FILTER in the POSE tails, depth class
   // bits (mh_frame_route; written by frame_rest on the host)
   int32_t frame_route[4] = {0, 0, 0, 0};
@@ -342,6 +359,9 @@ void db_poll_held(mh_ctx* ctx, bool wait);   // db_edit.hip: let go of adopted-a
 // a slot (no such frame: MH_OK) -- a depth map, one camera, no shards' blocks (`sharded`), the points.
 int filter_depth_points_ok(mh_ctx* ctx, const char* who, int n_models);
 int filter_depth_frame_ok(mh_ctx* ctx, const char* who, const mh_frame_params* prm, int n_cameras = 1, bool sharded = false);
+// ... and, asked by the same entry points at the same place, while hulls are on (mh_frame_set_hulls; off: MH_OK): no shards'
+// blocks, the wanted camera among the frame's, a store with whole models in ascending order
+int hulls_frame_ok(mh_ctx* ctx, const char* who, int n_cameras, bool sharded);
 int ensure_frame_buffers(mh_ctx* ctx, int Q);
 int ensure_scratch(mh_ctx* ctx, size_t bytes);
 int ensure_pinned(mh_ctx* ctx, size_t bytes);

@@ -278,6 +278,9 @@ int run_splice(mh_ctx* ctx, int b, int e, int n_rows, int model_id, int model_de
     if (image && ctx->db_edit_route == 0) launch_db_aggregates(st->norm, N, st->neg_h, st->stats, ctx->stream);
     MH_HIP(ctx, hipGetLastError());
   }
+  // the new per-model row ranges on the device (hull.hip), sized for the reserved model count so that a spare set keeps its block
+  MH_HIP(ctx, st->model_begin_dev.ensure(std::max(table.size(), (size_t)ctx->pool->max_models + 1), ctx->stream));
+  MH_HIP(ctx, hipMemcpyAsync(st->model_begin_dev, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
   MH_HIP(ctx, hipEventRecord(st->ready, ctx->stream));
   // the only host wait: the statistics words (the upload path waits for the same read-back).  It also means that this
   // context's frames on the old set have finished, so the old set may become the spare when its other holders let go.

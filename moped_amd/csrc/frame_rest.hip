@@ -3,6 +3,7 @@
 #include <type_traits>
 
 #include "frame.h"
+#include "hull.h"
 
 namespace mh {
 
@@ -185,7 +186,28 @@ int filter_depth_points_ok(mh_ctx* ctx, const char* who, int n_models) {
   return MH_ERR_ARG;
 }
 
+int hulls_frame_ok(mh_ctx* ctx, const char* who, int n_cameras, bool sharded) {
+  const mh_ctx::HullState& hs = ctx->hulls;
+  if (hs.max_vertices <= 0) return MH_OK;
+  const int cams = std::max(n_cameras, ctx->q_img ? ctx->n_images : 1);
+  const DbStore* st = ctx->store.get();
+  const char* why = nullptr;
+  if (sharded)
+    why = "frames of a sharded database carry no hulls (model indices are shard-local): mh_frame_set_hulls(ctx, 0, 0) on the "
+          "shards, mh_object_hulls on the gathered objects";
+  else if (hs.image >= cams)
+    why = "the camera whose hulls are wanted is not among the frame's";
+  else if (!st || !st->grouped || st->n_blocks > 1)
+    why = "the store's rows are not whole models in ascending order (mh_object_hulls has the same condition)";
+  if (why) {
+    ctx->err = std::string(who) + ": object hulls (mh_frame_set_hulls): " + why;
+    return MH_ERR_ARG;
+  }
+  return MH_OK;
+}
+
 int filter_depth_frame_ok(mh_ctx* ctx, const char* who, const mh_frame_params* prm, int n_cameras, bool sharded) {
+  if (int rc = hulls_frame_ok(ctx, who, n_cameras, sharded)) return rc;   // (every frame entry point asks here before it enqueues)
   const mh_ctx::FilterDepthState& fd = ctx->fdepth;
   if (!(fd.on[0] || fd.on[1]) || !prm || !prm->run_stage2) return MH_OK;
   const char* why = nullptr;
@@ -267,6 +289,31 @@ static int ensure_rule_buffers(mh_ctx* ctx, int patches, int Q, int frames) {
 
 void stamp(mh_ctx* ctx, int i) {
   if (ctx->timing) hipEventRecord(ctx->ev[i], ctx->stream);
+}
+
+// The hull block and the sort scratch of a frame's hull launch (mh_frame_set_hulls): MH_MAX_BATCH slots of the frame
+// state's max_objects records each, scratch for every workgroup of a full batch if a model needs any.  Grows only (the
+// stream is waited for then), so frames in a steady state never stop here.
+static int ensure_hull_block(mh_ctx* ctx) {
+  mh_ctx::HullState& hs = ctx->hulls;
+  const FrameState* fs = ctx->fs;
+  const size_t slot_bytes = (size_t)fs->max_objects * hull_record_words(hs.max_vertices) * 4;
+  if (slot_bytes != hs.slot_bytes || hs.block_vertices != hs.max_vertices) {
+    MH_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (hulls of earlier frames may still be on their way out of the old layout)
+    MH_HIP(ctx, hs.block.ensure(slot_bytes * MH_MAX_BATCH, ctx->stream));
+    hs.slot_bytes = slot_bytes;
+    hs.block_vertices = hs.max_vertices;
+    for (int& v : hs.slot_vertices) v = 0;   // (records of another layout)
+  }
+  if (hs.scratch_store != ctx->store.get() || hs.scratch_generation != ctx->store->generation) {   // (a new or edited database)
+    size_t stride = 0;
+    const std::vector<int32_t>& mb = ctx->store->model_begin;
+    for (size_t m = 0; m + 1 < mb.size(); ++m) stride = std::max(stride, hull_scratch_points(mb[m + 1] - mb[m]));
+    if (stride) MH_HIP(ctx, hs.scratch.ensure(stride * HULL_FRAME_GRID * MH_MAX_BATCH, ctx->stream));
+    hs.scratch_store = ctx->store.get();
+    hs.scratch_generation = ctx->store->generation;
+  }
+  return MH_OK;
 }
 
 // CLUSTER .. FILTER2 of a device-resident frame in six launches, from the call's record (FrameCall, frame.h) and the
@@ -355,6 +402,12 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
   const bool fdepth = (ctx->fdepth.on[0] || ctx->fdepth.on[1]) && prm->run_stage2 && !stepped;
   if (fdepth)
     if (int rc = filter_depth_frame_ok(ctx, "frame", prm, 1, c.gathered != nullptr)) return rc;
+  // object hulls behind the frame's last stage (mh_frame_set_hulls): whole frames only
+  const bool hulls = ctx->hulls.max_vertices > 0 && !stepped;
+  if (hulls) {
+    if (int rc = hulls_frame_ok(ctx, "frame", multi ? ctx->n_images : 1, c.gathered != nullptr)) return rc;
+    if (int rc = ensure_hull_block(ctx)) return rc;
+  }
   if (multi && (ctx->q_depth || dimg.img || ctx->linkage_on)) {
     ctx->err = "frames with several images: the moped3d depth steps are single-camera";
     return MH_ERR_ARG;
@@ -579,6 +632,31 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
                        fs->max_objects, fs->counts);
   }
   stamp(ctx, 8);
+  // the hulls of the objects the result slots now hold: one launch for all frames of the call, the counts read on the device
+  if (!stepped || runs(2))
+    for (int f = 0; f < (batch_n > 1 ? batch_n : 1) && c.slot + f < MH_MAX_BATCH; ++f) ctx->hulls.slot_vertices[c.slot + f] = 0;
+  if (hulls) {
+    mh_ctx::HullState& hs = ctx->hulls;
+    HullFrameArgs ha;
+    ha.core.xyz = ctx->db_xyz;
+    ha.core.model_begin = ctx->store->model_begin_dev;
+    ha.core.n_models = ctx->store->n_models;
+    ha.core.cam = dc;
+    ha.core.max_vertices = hs.max_vertices;
+    ha.core.form = 0;   // (frames ignore mh_hull_debug_form)
+    ha.core.scratch = hs.scratch;
+    ha.core.scratch_stride = hs.scratch ? hs.scratch.cap / ((size_t)HULL_FRAME_GRID * MH_MAX_BATCH) : 0;
+    ha.cams = multi ? ctx->cams_view : nullptr;
+    ha.image = hs.image;
+    ha.result = fs->result;
+    ha.result_bytes = fs->result_bytes;
+    ha.max_objects = fs->max_objects;
+    ha.first_slot = c.slot;
+    ha.block = hs.block;
+    ha.slot_bytes = hs.slot_bytes;
+    launch_frame_hulls(ha, batch_n > 1 ? batch_n : 1, s);
+    for (int f = 0; f < (batch_n > 1 ? batch_n : 1) && c.slot + f < MH_MAX_BATCH; ++f) hs.slot_vertices[c.slot + f] = hs.max_vertices;
+  }
   MH_HIP(ctx, hipGetLastError());
   return MH_OK;
 }

@@ -441,8 +441,30 @@ class FramePipeline:
                 c.filter_depth_set_points(points_xyz, points_off)
             c.frame_set_filter_depth(f1, f2, K, cam)
 
+    # ---- object hulls: Object::getObjectHull of every object of a frame, computed behind the frame --------------
+    def set_hulls(self, max_vertices: int, image: int = 0):
+        """Frames and batches enqueued afterwards compute the hulls of their objects (mh_frame_set_hulls; 0 = off, the
+        default).  fetch() / fetch_batch() then return (objects, counts, hulls) with hulls = (vertex lists, n_vertices,
+        n_behind, bbox_uv) in the order of the objects; deliver() adds the hull block (take_hull_delivery).  Not for a
+        sharded database (model indices are shard-local): object_hulls() on the gathered objects instead."""
+        if max_vertices and self.exchange:
+            raise capi.MhError("hulls behind the frames: single-GPU pipelines only (object_hulls() serves gathered objects)")
+        self._hull_vertices = int(max_vertices)
+        for c in self.ctxs:
+            c.frame_set_hulls(max_vertices, image)
+
+    def object_hulls(self, objects, K, cam, max_vertices: int = 64, slot: int = 0):
+        """The hulls of fetched objects (an OBJECT_DTYPE array) in the image (K, cam): mh_object_hulls, a round trip."""
+        return self.ctxs[slot].object_hulls(objects["model"], objects["pose"], K, cam, max_vertices)
+
+    def _with_hulls(self, slot, f, res):
+        if not getattr(self, "_hull_vertices", 0):
+            return res
+        objs, counts = res
+        return objs, counts, self.ctxs[slot].frame_fetch_hulls(f, max(len(objs), 1), self._hull_vertices)
+
     def fetch_batch(self, slot: int, B: int):
-        return [self.ctxs[slot].frame_fetch_slot(f) for f in range(B)]
+        return [self._with_hulls(slot, f, self.ctxs[slot].frame_fetch_slot(f)) for f in range(B)]
 
     # ---- delivery: every batch's objects into pinned host memory, no stream synchronisation ---------------
     def attach_delivery(self, max_objects: int = 16, B: int = capi.MAX_BATCH):
@@ -454,8 +476,9 @@ class FramePipeline:
                           for _ in range(self.depth)]
         self._dlv_view = [t.numpy().view(self._dlv_dtype) for t in self._dlv_host]
         self._dlv_pending = [0] * self.depth   # frames of the slot's delivery in flight
+        self._dlv_hull_host = None             # (made by the first deliver() with hulls on)
 
-    def deliver(self, slot: int, tag: int = 0):
+    def deliver(self, slot: int, tag: int = 0, hulls: bool = True):
         """Behind the batch just enqueued in `slot`: its objects (single GPU) or, with a sharded DB, all ranks' objects of
         the slot's PREVIOUS batch (they arrived with this batch's exchange) into the slot's host block."""
         c, B = self.ctxs[slot], self._batch[slot]
@@ -463,6 +486,13 @@ class FramePipeline:
             c.frame_fetch_previous_async(self._dlv_cap, self._dlv_host[slot].data_ptr(), tag)
         else:
             c.frame_fetch_batch_async(B, self._dlv_cap, self._dlv_host[slot].data_ptr(), tag)
+            hv = getattr(self, "_hull_vertices", 0) if hulls else 0
+            if hv:   # the batch's hull records beside its objects, one more stream-ordered copy
+                if self._dlv_hull_host is None or self._dlv_hull_dtype != capi.hull_block_dtype(self._dlv_cap, hv):
+                    self._dlv_hull_dtype = capi.hull_block_dtype(self._dlv_cap, hv)
+                    self._dlv_hull_host = [torch.zeros(capi.MAX_BATCH * self._dlv_hull_dtype.itemsize, dtype=torch.uint8).pin_memory()
+                                           for _ in range(self.depth)]
+                c.frame_fetch_batch_hulls_async(B, self._dlv_cap, self._dlv_hull_host[slot].data_ptr())
         self._dlv_pending[slot] = B
 
     def take_delivery(self, slot: int):
@@ -474,6 +504,10 @@ class FramePipeline:
         self.ctxs[slot].frame_fetch_wait()
         self._dlv_pending[slot] = 0
         return self._dlv_view[slot][:B]
+
+    def take_hull_delivery(self, slot: int, B: int):
+        """After take_delivery(slot): the B frames' hull records (capi.hull_block_dtype; a view of the pinned block)."""
+        return self._dlv_hull_host[slot].numpy().view(self._dlv_hull_dtype)[:B]
 
     def previous_objects_batch(self, slot: int):
         """Objects of the B frames of the batch enqueued in `slot` BEFORE the current one, from all ranks."""
@@ -489,8 +523,8 @@ class FramePipeline:
         return self.ctxs[slot].frame_previous_objects(0)
 
     def fetch(self, slot: int):
-        """Objects of the frame in `slot` (model ids global), counts[4]."""
-        return self.ctxs[slot].frame_fetch()
+        """Objects of the frame in `slot` (model ids global), counts[4]; with set_hulls on, their hulls behind them."""
+        return self._with_hulls(slot, None, self.ctxs[slot].frame_fetch())
 
     def gather_objects(self, slot: int):
         """Exchange 2 on its own: every rank's result block -> all ranks; the merged object array
