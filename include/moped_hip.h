@@ -13,6 +13,7 @@
  *   mh_db_splice        Moped::addModel / removeModel    src/moped.cpp:139-159 (+ the Update() they trigger)
  *   mh_db_splice_image[s]  Moped::createPlanarModelsFromImages  src/moped.cpp:196-236 (image -> model of the store)
  *   mh_planar_rows_dev  ... its loop over detectedFeatures  src/moped.cpp:220-232
+ *   mh_db_splice_view / mh_db_append_view / mh_db_append   (no counterpart: a model from Kinect views, grown view by view)
  *   mh_models_write_xml the file samples/createModels/createModels.cpp:121-126 writes (sXML::print, include/sXML.hpp:146-170)
  *   mh_normalize        MATCH_ANN_CPU::norm              src/match/MATCH_ANN_CPU.hpp:54-57
  *   mh_match            MATCH_ANN_CPU::process search    src/match/MATCH_ANN_CPU.hpp:155-165
@@ -1373,6 +1374,107 @@ int mh_db_splice_image(mh_ctx* ctx, int op, int model, const uint8_t* gray_dev, 
 int mh_db_splice_images(mh_ctx* ctx, int model_first, const uint8_t* const* gray_dev, int n_images, int width, int height,
                         int double_size, int max_keypoints, const mh_planar_spec* spec, int32_t* n_rows, float (*bbox)[6],
                         float* rows_desc_host, float* rows_xyz_host, int rows_cap);
+
+/* ---- 3-D models from Kinect views ------------------------------------------------------------------------------------
+ * A Kinect host has the measured 3-D point of every pixel on the device: the [h][w][4] map (x, y, z, valid) every depth
+ * entry point takes (DEPTHMAP_PROP_CPU.hpp:103-131), the depth camera at the origin as moped3d's node sets it
+ * (moped3d.cpp:259-260,275-276).  A view = image + map + the object's pose in that view, pose = (qx,qy,qz,qw,tx,ty,tz)
+ * as MOPED reports poses, X_cam = R X_model + t, q normalised.  Every keypoint whose pixel holds a measured point
+ * becomes a model row at X_model = inverseTransform(pose, point) (moped.hpp:189-194).  The first view makes the model
+ * (mh_db_splice_view), further views grow it (mh_db_append_view) and leave out the keypoints the model already holds:
+ * MOPED's models carry one descriptor per 3-D point, and a point held twice fails the 2-NN ratio test against itself
+ * (MATCH_ANN_CPU.hpp:165).
+ *
+ * Per keypoint (u, v) of the list, in list order; the FIRST failing test decides its counter:
+ *  1 pixel     u, v finite and -1 < u < w, -1 < v < h in float32; ix = (int)u, iy = (int)v (truncation,
+ *              DEPTHMAP_PROP_CPU.hpp:103: u = -0.5 reads pixel 0).  No clamping, unlike mh_depth_prop: a model point
+ *              must be measured.
+ *  2 depth     the pixel's 4th word >= 0 (:131; NaN fails)
+ *  3 fill      with a distance map and max_fill_distance >= 0: dropped if dist > max_fill_distance or NaN
+ *              (DEPTH_VERIFY_CPU.hpp:167-170)
+ *  4 roi       u0 <= u < u1 && v0 <= v < v1, all zeros = none: mh_planar_spec's rule
+ *  5 X_model   = R^T (point - t): one float32 rounding per operation in the reference's order, no fused multiply-add
+ *  6 box       min xyz, max xyz in the model frame, kept if min <= X_model <= max componentwise; all zeros = none; a
+ *              NaN coordinate is dropped when a box is set
+ *  7 duplicate only with mh_view_dup, merge_ratio > 0 and merge_dist >= 0: dropped if MATCH accepts the keypoint at
+ *              merge_ratio (d1 / d2 < merge_ratio, the test of mh_normalize_match), its nearest row belongs to `model`,
+ *              and dx dx + dy dy + dz dz <= merge_dist merge_dist against that row's xyz (float32, left to right)
+ *  8 limit     only the first max_rows kept keypoints (0 = no limit), never more than the output holds
+ * Kept rows come out densely packed in list order, descriptors unchanged, xyz = X_model.
+ * stats[8]: [0] keypoints seen, [1..7] dropped by tests 1, 2, 3, 4, 6, 7, 8; kept + sum stats[1..7] == stats[0]. */
+typedef struct {
+  float roi[4];
+  float box[6];
+  float max_fill_distance;   /* < 0: no fill test */
+  int32_t max_rows;
+  float merge_ratio;         /* duplicate test (mh_db_append_view, mh_view_dup): on if merge_ratio > 0 && merge_dist >= 0 */
+  float merge_dist;
+} mh_view_spec;
+typedef struct {
+  const void* depth_xyzn_dev;       /* device [h][w][4] floats, 16-byte aligned */
+  const float* fill_distance_dev;   /* device [h][w], or NULL */
+  float pose[7];
+  float K[4];   /* fx, fy, cx, cy of the gray image: read only while mh_frame_set_undistort is on (fx, fy != 0 then) */
+} mh_view;
+/* The duplicate test's inputs and the old rows of an append (all device): MATCH's result for the list against a store
+ * (view i of a batch at + i cap), that store's model_of [n_db_rows] and xyz [n_db_rows][3] (local rows, index_base 0),
+ * the model being grown and its rows [row_begin, row_end), whose xyz are folded into the bounding box so that it is
+ * the box of the whole model after the edit.  Duplicates are judged against these rows, never against the call's own. */
+typedef struct {
+  const int32_t* idx_dev;
+  const float* d1_dev;
+  const float* d2_dev;
+  const int32_t* model_of_dev;
+  const float* xyz_dev;
+  int32_t n_db_rows;
+  int32_t model;
+  int32_t row_begin, row_end;
+} mh_view_dup;
+/* The selection alone on given device arrays, like mh_planar_rows_dev: desc_dev [cap][128], xy_dev [cap][2], *n_dev
+ * keypoints (clamped to [0, cap]); the view's map is w x h.  dup may be NULL (no duplicate test, no old rows).  Writes
+ * desc_out_dev [out_cap][128], xyz_out_dev [out_cap][3], *n_out_dev, bbox_dev[6] (Model::boundingBox with the planar
+ * kernel's `<` / `>` rule) and stats_dev[8].  Rows at and beyond *n_out_dev are not written.  Stream-ordered, no host
+ * wait.  MH_ERR_ARG before anything is launched: a non-finite pose or box, NaN in roi, max_fill_distance, merge_ratio or
+ * merge_dist, max_rows < 0, a null map or one not 16-byte aligned, w or h <= 0, descriptor arrays not 16-byte aligned, a
+ * dup with a null array or rows outside [0, n_db_rows]. */
+int mh_view_rows_dev(mh_ctx* ctx, const float* desc_dev, const float* xy_dev, const int32_t* n_dev, int cap,
+                     const mh_view* view, int width, int height, const mh_view_spec* spec, const mh_view_dup* dup,
+                     float* desc_out_dev, float* xyz_out_dev, int out_cap, int32_t* n_out_dev, float* bbox_dev,
+                     int32_t* stats_dev);
+/* n_views <= MH_MAX_BATCH lists in ONE launch, one map and pose each (lists and outputs laid out as in
+ * mh_planar_rows_batch_dev; stats_dev + 8 i); every view's outputs are bit for bit those of the single call. */
+int mh_view_rows_batch_dev(mh_ctx* ctx, const float* desc_dev, const float* xy_dev, const int32_t* n_dev, int n_views,
+                           int cap, const mh_view* views, int width, int height, const mh_view_spec* spec,
+                           const mh_view_dup* dup, float* desc_out_dev, float* xyz_out_dev, int out_cap,
+                           int32_t* n_out_dev, float* bbox_dev, int32_t* stats_dev);
+/* Rows added behind the last row of an existing model: the splice old[0, e) ++ rows ++ old[e, N) with e = the model's
+ * end.  The model keeps its index, later models move up.  Arguments and every guarantee as mh_db_splice (which keeps
+ * refusing an operation beyond MH_DB_REMOVE): afterwards the store equals, byte for byte, a fresh mh_db_upload_raw of
+ * the same rows. */
+int mh_db_append(mh_ctx* ctx, int model, const float* desc, const float* xyz, int n_rows, int normalize, int on_device);
+/* A view becomes model `model` (op = MH_DB_INSERT or MH_DB_REPLACE): [UNDISTORTED_IMAGE of the gray image with view->K if
+ * mh_frame_set_undistort is on; the map is read as it lies, as the Kinect frames do] -> FEAT -> selection into the
+ * edit's staging block -> splice.  In every other respect the contract of mh_db_splice_image: one added host wait,
+ * MH_ERR_CAPACITY with the edit made from the first max_keypoints, host rows with FEAT's bits.  stats[8] (may be NULL)
+ * as above.  merge_ratio / merge_dist are not used (there is no model to compare with). */
+int mh_db_splice_view(mh_ctx* ctx, int op, int model, const uint8_t* gray_dev, const mh_view* view, int width, int height,
+                      int double_size, int max_keypoints, const mh_view_spec* spec, int32_t* n_rows, float bbox[6],
+                      int32_t stats[8], float* rows_desc_host, float* rows_xyz_host, int rows_cap);
+/* A further view of model `model`: its kept rows are appended (mh_db_append).  With the duplicate test on (merge_ratio > 0
+ * && merge_dist >= 0, and a store that has rows) FEAT's descriptors are normalised into a scratch copy and matched
+ * against the context's store with the count on the device, as a frame's are; the selection then drops the keypoints
+ * the model already holds.  Still one host wait before the splice.  With the test off no MATCH is launched.  *n_rows:
+ * rows added; bbox: the whole model's box after the edit. */
+int mh_db_append_view(mh_ctx* ctx, int model, const uint8_t* gray_dev, const mh_view* view, int width, int height,
+                      int double_size, int max_keypoints, const mh_view_spec* spec, int32_t* n_rows, float bbox[6],
+                      int32_t stats[8], float* rows_desc_host, float* rows_xyz_host, int rows_cap);
+/* n_views <= MH_MAX_BATCH views of one size -> models model_first .. model_first + n_views - 1 (INSERT): FEAT as ONE batch,
+ * ONE selection launch, one read-back, then the single-model splice n_views times; byte for byte what mh_db_splice_view
+ * gives per view.  n_rows [n_views], bbox [n_views][6], stats [n_views][8] (may be NULL); host rows as
+ * mh_db_splice_images.  Duplicates among the views of one call are not looked for. */
+int mh_db_splice_views(mh_ctx* ctx, int model_first, const uint8_t* const* gray_dev, const mh_view* views, int n_views,
+                       int width, int height, int double_size, int max_keypoints, const mh_view_spec* spec, int32_t* n_rows,
+                       float (*bbox)[6], int32_t (*stats)[8], float* rows_desc_host, float* rows_xyz_host, int rows_cap);
 
 /* ---- timing --------------------------------------------------------------------- */
 

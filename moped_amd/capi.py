@@ -127,6 +127,50 @@ def make_planar_spec(scale=None, z=None, K=None, roi=None, max_rows=0) -> mh_pla
     return sp
 
 
+class mh_view_spec(C.Structure):
+    _fields_ = [("roi", C.c_float * 4), ("box", C.c_float * 6), ("max_fill_distance", C.c_float), ("max_rows", C.c_int32),
+                ("merge_ratio", C.c_float), ("merge_dist", C.c_float)]
+
+
+class mh_view(C.Structure):
+    _fields_ = [("depth_xyzn_dev", C.c_void_p), ("fill_distance_dev", C.c_void_p), ("pose", C.c_float * 7), ("K", C.c_float * 4)]
+
+
+class mh_view_dup(C.Structure):
+    _fields_ = [("idx_dev", C.c_void_p), ("d1_dev", C.c_void_p), ("d2_dev", C.c_void_p), ("model_of_dev", C.c_void_p),
+                ("xyz_dev", C.c_void_p), ("n_db_rows", C.c_int32), ("model", C.c_int32), ("row_begin", C.c_int32),
+                ("row_end", C.c_int32)]
+
+
+POSE_IDENTITY = (0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0)
+
+
+def make_view_spec(roi=None, box=None, max_fill_distance=-1.0, max_rows=0, merge_ratio=0.0, merge_dist=-1.0) -> mh_view_spec:
+    """The rules of a Kinect view's selection (mh_view_spec): roi = (u0, v0, u1, v1), half-open, None = every keypoint;
+    box = (min xyz, max xyz) in the model frame, None = none; max_fill_distance < 0 = no fill test; the duplicate test of
+    an appended view is on when merge_ratio > 0 and merge_dist >= 0."""
+    sp = mh_view_spec()
+    sp.roi[:] = [float(v) for v in (roi if roi is not None else (0.0,) * 4)]
+    sp.box[:] = [float(v) for v in (box if box is not None else (0.0,) * 6)]
+    sp.max_fill_distance = float(max_fill_distance)
+    sp.max_rows = int(max_rows)
+    sp.merge_ratio = float(merge_ratio)
+    sp.merge_dist = float(merge_dist)
+    return sp
+
+
+def make_view(depth_ptr, fill_ptr=None, pose=None, K=None) -> mh_view:
+    """A view: the device depth map [h][w][4], optionally its distance map [h][w], the object's pose in the view
+    (qx, qy, qz, qw, tx, ty, tz: X_cam = R X_model + t; None = identity), K of the gray image (read only while
+    undistortion is on)."""
+    v = mh_view()
+    v.depth_xyzn_dev = depth_ptr
+    v.fill_distance_dev = fill_ptr
+    v.pose[:] = [float(x) for x in (pose if pose is not None else POSE_IDENTITY)]
+    v.K[:] = [float(x) for x in (K if K is not None else (1.0, 1.0, 0.0, 0.0))]
+    return v
+
+
 RAW_DEPTH_F32_M, RAW_DEPTH_U16_MM = 0, 1   # MH_RAW_DEPTH_*
 
 
@@ -194,6 +238,7 @@ EXPORTS = [
     "mh_linkage_debug_matrix", "mh_linkage_debug_agglomerate", "mh_linkage_set_mode", "mh_linkage_get_mode", "mh_linkage_stats", "mh_frame_debug_fetch_clusters_slot",
     "mh_planar_rows_dev", "mh_planar_rows_batch_dev", "mh_db_splice_image", "mh_db_splice_images",
     "mh_models_add_rows", "mh_models_write_xml",
+    "mh_view_rows_dev", "mh_view_rows_batch_dev", "mh_db_append", "mh_db_splice_view", "mh_db_append_view", "mh_db_splice_views",
     "mh_depth_map_from_raw_dev", "mh_depth_map_from_raw_batch_dev", "mh_depth_map_from_raw_host",
     "mh_frame_run_kinect_raw_host",
     "mh_frame_debug_fetch_cluster_table_slot",
@@ -463,6 +508,14 @@ def load():
         L.mh_db_splice_images.argtypes = [vp, i32, vp, i32, i32, i32, i32, i32, C.POINTER(mh_planar_spec), vp, vp, vp, vp, i32]
         L.mh_models_add_rows.argtypes = [vp, C.c_char_p, vp, vp, C.c_int64]
         L.mh_models_write_xml.argtypes = [vp, i32, C.c_char_p]
+    if hasattr(L, "mh_view_rows_dev"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
+        pv, ps, pd = C.POINTER(mh_view), C.POINTER(mh_view_spec), C.POINTER(mh_view_dup)
+        L.mh_view_rows_dev.argtypes = [vp, vp, vp, vp, i32, pv, i32, i32, ps, pd, vp, vp, i32, vp, vp, vp]
+        L.mh_view_rows_batch_dev.argtypes = [vp, vp, vp, vp, i32, i32, pv, i32, i32, ps, pd, vp, vp, i32, vp, vp, vp]
+        L.mh_db_append.argtypes = [vp, i32, vp, vp, i32, i32, i32]
+        L.mh_db_splice_view.argtypes = [vp, i32, i32, vp, pv, i32, i32, i32, i32, ps, C.POINTER(C.c_int32), vp, vp, vp, vp, i32]
+        L.mh_db_append_view.argtypes = [vp, i32, vp, pv, i32, i32, i32, i32, ps, C.POINTER(C.c_int32), vp, vp, vp, vp, i32]
+        L.mh_db_splice_views.argtypes = [vp, i32, vp, pv, i32, i32, i32, i32, i32, ps, vp, vp, vp, vp, vp, i32]
     if hasattr(L, "mh_object_hulls"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
         L.mh_object_hulls.argtypes = [vp, vp, vp, i32, C.POINTER(mh_cam), i32, vp, vp, vp, vp]
         L.mh_hull_debug_form.argtypes = [vp, i32]
@@ -812,6 +865,92 @@ class Context:
         if want_rows:
             return n, bbox, [d[i, :n[i]].copy() for i in range(k)], [x[i, :n[i]].copy() for i in range(k)]
         return n, bbox
+
+    # ---- 3-D models from Kinect views (mh_view_rows_dev and friends) ----
+    def view_rows_dev(self, desc_ptr, xy_ptr, n_ptr, cap, view: mh_view, w, h, spec: mh_view_spec, desc_out_ptr, xyz_out_ptr,
+                      out_cap, n_out_ptr, bbox_ptr, stats_ptr, dup: "mh_view_dup | None" = None):
+        """mh_view_rows_dev on device arrays; asynchronous."""
+        self._ck(self.L.mh_view_rows_dev(
+            self.h, C.c_void_p(desc_ptr), C.c_void_p(xy_ptr), C.c_void_p(n_ptr), int(cap),
+            C.byref(view) if view is not None else None, int(w), int(h), C.byref(spec) if spec is not None else None,
+            C.byref(dup) if dup is not None else None, C.c_void_p(desc_out_ptr), C.c_void_p(xyz_out_ptr), int(out_cap),
+            C.c_void_p(n_out_ptr), C.c_void_p(bbox_ptr), C.c_void_p(stats_ptr)), "mh_view_rows_dev")
+
+    def view_rows_batch_dev(self, desc_ptr, xy_ptr, n_ptr, cap, views, w, h, spec: mh_view_spec, desc_out_ptr, xyz_out_ptr,
+                            out_cap, n_out_ptr, bbox_ptr, stats_ptr, dup: "mh_view_dup | None" = None):
+        """mh_view_rows_batch_dev: len(views) lists, one mh_view each, in one launch; asynchronous."""
+        vs = (mh_view * len(views))(*views)
+        self._ck(self.L.mh_view_rows_batch_dev(
+            self.h, C.c_void_p(desc_ptr), C.c_void_p(xy_ptr), C.c_void_p(n_ptr), len(views), int(cap), vs, int(w), int(h),
+            C.byref(spec) if spec is not None else None, C.byref(dup) if dup is not None else None, C.c_void_p(desc_out_ptr),
+            C.c_void_p(xyz_out_ptr), int(out_cap), C.c_void_p(n_out_ptr), C.c_void_p(bbox_ptr), C.c_void_p(stats_ptr)),
+            "mh_view_rows_batch_dev")
+
+    def db_append(self, model, desc, xyz, normalize=False, on_device=False, n_rows=None):
+        """mh_db_append: rows behind the last row of model `model`.  desc [n][128], xyz [n][3]: host arrays, or device
+        pointers (ints) with on_device and n_rows."""
+        if on_device:
+            self._ck(self.L.mh_db_append(self.h, int(model), C.c_void_p(desc), C.c_void_p(xyz), int(n_rows), int(normalize), 1),
+                     "mh_db_append")
+            return
+        desc = np.ascontiguousarray(desc, np.float32).reshape(-1, DIM)
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        assert desc.shape[0] == xyz.shape[0]
+        self._ck(self.L.mh_db_append(self.h, int(model), _ptr(desc), _ptr(xyz), desc.shape[0], int(normalize), 0), "mh_db_append")
+
+    def _view_edit(self, name, head, gray_ptr, view, w, h, spec, double_size, max_keypoints, want_rows):
+        n = C.c_int32(0)
+        bbox = np.zeros(6, np.float32)
+        stats = np.zeros(8, np.int32)
+        d = np.zeros((max_keypoints, DIM), np.float32) if want_rows else None
+        x = np.zeros((max_keypoints, 3), np.float32) if want_rows else None
+        rc = getattr(self.L, name)(self.h, *head, C.c_void_p(gray_ptr), C.byref(view) if view is not None else None, w, h,
+                                   int(double_size), int(max_keypoints), C.byref(spec) if spec is not None else None,
+                                   C.byref(n), _ptr(bbox), _ptr(stats), _ptr(d) if want_rows else None,
+                                   _ptr(x) if want_rows else None, max_keypoints if want_rows else 0)
+        # MH_ERR_CAPACITY: the edit is made, from the first max_keypoints keypoints of the list
+        self.planar_truncated = rc == MH_ERR_CAPACITY
+        self._ck(MH_OK if self.planar_truncated else rc, name)
+        if want_rows:
+            return int(n.value), bbox, stats, d[:n.value].copy(), x[:n.value].copy()
+        return int(n.value), bbox, stats
+
+    def db_splice_view(self, op, model, gray_ptr, view: mh_view, w, h, spec: mh_view_spec, double_size=True,
+                       max_keypoints=4096, want_rows=False):
+        """mh_db_splice_view: the device image + depth map + pose become model `model` (DB_INSERT / DB_REPLACE).
+        -> (n_rows, bbox[6], stats[8]) or, with want_rows, (n_rows, bbox, stats, desc [n,128], xyz [n,3])."""
+        return self._view_edit("mh_db_splice_view", (int(op), int(model)), gray_ptr, view, w, h, spec, double_size,
+                               max_keypoints, want_rows)
+
+    def db_append_view(self, model, gray_ptr, view: mh_view, w, h, spec: mh_view_spec, double_size=True, max_keypoints=4096,
+                       want_rows=False):
+        """mh_db_append_view: a further view of model `model`; the keypoints it already holds are left out when the
+        spec's duplicate test is on.  Returns as db_splice_view: n_rows = rows added, bbox = the whole model's."""
+        return self._view_edit("mh_db_append_view", (int(model),), gray_ptr, view, w, h, spec, double_size, max_keypoints,
+                               want_rows)
+
+    def db_splice_views(self, model_first, gray_ptrs, views, w, h, spec: mh_view_spec, double_size=True, max_keypoints=4096,
+                        want_rows=False):
+        """mh_db_splice_views: len(views) views of one size become models model_first .. (INSERT), FEAT as one batch, one
+        selection launch.  -> (n_rows [n], bbox [n,6], stats [n,8]) and, with want_rows, lists of desc and xyz."""
+        k = len(gray_ptrs)
+        assert len(views) == k
+        g = (C.c_void_p * k)(*gray_ptrs)
+        vs = (mh_view * k)(*views)
+        n = np.zeros(k, np.int32)
+        bbox = np.zeros((k, 6), np.float32)
+        stats = np.zeros((k, 8), np.int32)
+        d = np.zeros((k, max_keypoints, DIM), np.float32) if want_rows else None
+        x = np.zeros((k, max_keypoints, 3), np.float32) if want_rows else None
+        rc = self.L.mh_db_splice_views(self.h, int(model_first), g, vs, k, w, h, int(double_size), int(max_keypoints),
+                                       C.byref(spec) if spec is not None else None, _ptr(n), _ptr(bbox), _ptr(stats),
+                                       _ptr(d) if want_rows else None, _ptr(x) if want_rows else None,
+                                       max_keypoints if want_rows else 0)
+        self.planar_truncated = rc == MH_ERR_CAPACITY
+        self._ck(MH_OK if self.planar_truncated else rc, "mh_db_splice_views")
+        if want_rows:
+            return n, bbox, stats, [d[i, :n[i]].copy() for i in range(k)], [x[i, :n[i]].copy() for i in range(k)]
+        return n, bbox, stats
 
     def db_reserve(self, max_rows, max_models):
         self._ck(self.L.mh_db_reserve(self.h, int(max_rows), int(max_models)), "mh_db_reserve")

@@ -159,6 +159,11 @@ struct mh_ctx {
     mh::DevBuf<float> rows_desc, rows_xyz;   // device [images][cap] selected rows (batch; the host copy of a single edit)
     mh::DevBuf<int32_t> words;       // device [6][MH_MAX_BATCH]: FEAT's counts | kept counts | FEAT's 4 counter words per image
     mh::DevBuf<float> box;           // device [MH_MAX_BATCH][6]
+    // mh_db_*_view[s]: the selection's statistics; mh_db_append_view's duplicate test: FEAT's descriptors normalised,
+    // their norm terms, MATCH's answer
+    mh::DevBuf<int32_t> stats;       // device [MH_MAX_BATCH][8]
+    mh::DevBuf<float> qn, qnorm, m_d1, m_d2;   // device [cap][128], [cap], [cap], [cap]
+    mh::DevBuf<int32_t> m_idx;       // device [cap]
   } planar;
   int db_edit_route = 0;             // 0: the fused pass (db_splice_kernel); 1: device copies + the upload's preparation (mh_db_debug_route)
   hipEvent_t db_ev[2] = {nullptr, nullptr};   // around an edit's pass over the rows when timing is on (mh_db_edit_ms)
@@ -433,6 +438,36 @@ struct PlanarArgs {
 void launch_planar_rows(const PlanarArgs& a, int n_images, hipStream_t s);
 // MH_ERR_ARG (and ctx->err) for a spec mh_db_splice_image refuses; *all = its roi means every keypoint
 int planar_spec_check(mh_ctx* ctx, const char* who, const mh_planar_spec* spec, int* all);
+// view_rows.hip: FEAT's lists + a Kinect view each (depth map, pose) -> model rows at the measured 3-D points, one
+// launch, workgroup i = view i; lists and outputs laid out as PlanarArgs', stats + 8 i.  dup_on: the duplicate test
+// against dup's MATCH result (view i's at + i cap); dup.row_begin .. row_end: old rows folded into the box.
+struct ViewArgs {
+  const float* desc;
+  const float* xy;
+  const int32_t* n;
+  int cap;
+  int w, h;
+  mh_view_spec spec;
+  int roi_all, box_all, dup_on;
+  mh_view_dup dup;
+  float* desc_out;
+  float* desc_copy;
+  float* xyz_out;
+  size_t out_pitch;
+  int out_cap;
+  int32_t* n_out;
+  float* bbox;
+  int32_t* stats;
+  struct View {
+    const float4* map;
+    const float* fill;
+    float pose[7];
+  } v[MH_MAX_BATCH];
+};
+void launch_view_rows(const ViewArgs& a, int n_views, hipStream_t s);
+// MH_ERR_ARG (and ctx->err) for a spec, views or map size mh_db_splice_view refuses; fills a's spec, flags and views
+int view_args_check(mh_ctx* ctx, const char* who, const mh_view* views, int n_views, int width, int height,
+                    const mh_view_spec* spec, ViewArgs* a);
 // api_sift.hip: the four counter words of image `slot` of the context's last extraction (device): [1] keys found, [2] != 0:
 // a list overflowed
 const int32_t* sift_counters_dev(mh_ctx* ctx, int slot);

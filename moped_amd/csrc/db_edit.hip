@@ -15,6 +15,7 @@
 
 #include "context.h"
 #include "steps.h"
+#include "view_check.h"
 
 using namespace mh;
 
@@ -383,6 +384,32 @@ static int splice_staged(mh_ctx* ctx, int op, int model, int n_rows) {
   return run_splice(ctx, b, e, n_rows, model, delta, std::move(table));
 }
 
+// the edit of a checked model whose n_rows new rows (staged) go behind its last row: old[0, e) ++ rows ++ old[e, N)
+static int append_staged(mh_ctx* ctx, int model, int n_rows) {
+  const DbStore* old = ctx->store.get();   // (checked: the model exists, so there is a store)
+  const int e = old->model_begin[model + 1];
+  std::vector<int32_t> table = append_table(old->model_begin, model, n_rows);
+  return run_splice(ctx, e, e, n_rows, model, 0, std::move(table));
+}
+
+// the new rows of mh_db_splice / mh_db_append into the staging block: their norm terms by the upload's own launches, so
+// that their bits are the upload's by construction
+static int stage_given_rows(mh_ctx* ctx, const float* desc, const float* xyz, int n_rows, int normalize, int on_device) {
+  if (n_rows <= 0) return MH_OK;
+  int rc = ensure_stage(ctx, (size_t)n_rows);
+  if (rc) return rc;
+  float* sd = ctx->db_stage;
+  float* sn = sd + stage_rows(ctx) * DIM;
+  float* sx = sn + stage_rows(ctx);
+  const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  MH_HIP(ctx, hipMemcpyAsync(sd, desc, (size_t)n_rows * DIM * sizeof(float), kind, ctx->stream));
+  MH_HIP(ctx, hipMemcpyAsync(sx, xyz, (size_t)n_rows * 3 * sizeof(float), kind, ctx->stream));
+  if (normalize) launch_normalize(sd, sn, n_rows, ctx->stream);
+  else launch_row_norms(sd, sn, n_rows, ctx->stream);
+  MH_HIP(ctx, hipGetLastError());
+  return MH_OK;
+}
+
 int mh_db_splice(mh_ctx* ctx, int op, int model, const float* desc, const float* xyz, int n_rows, int normalize,
                  int on_device) {
   if (!ctx) return MH_ERR_ARG;
@@ -392,35 +419,40 @@ int mh_db_splice(mh_ctx* ctx, int op, int model, const float* desc, const float*
   if (int rc = check_edit(ctx, "mh_db_splice", op, model)) return rc;
   MH_HIP(ctx, hipSetDevice(ctx->device));
   if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
-  // stage the new rows: their norm terms by the upload's own launches, so that their bits are the upload's by construction
-  if (n_rows > 0) {
-    int rc = ensure_stage(ctx, (size_t)n_rows);
-    if (rc) return rc;
-    float* sd = ctx->db_stage;
-    float* sn = sd + stage_rows(ctx) * DIM;
-    float* sx = sn + stage_rows(ctx);
-    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    MH_HIP(ctx, hipMemcpyAsync(sd, desc, (size_t)n_rows * DIM * sizeof(float), kind, ctx->stream));
-    MH_HIP(ctx, hipMemcpyAsync(sx, xyz, (size_t)n_rows * 3 * sizeof(float), kind, ctx->stream));
-    if (normalize) launch_normalize(sd, sn, n_rows, ctx->stream);
-    else launch_row_norms(sd, sn, n_rows, ctx->stream);
-    MH_HIP(ctx, hipGetLastError());
-  }
+  if (int rc = stage_given_rows(ctx, desc, xyz, n_rows, normalize, on_device)) return rc;
   return splice_staged(ctx, op, model, n_rows);
+}
+
+int mh_db_append(mh_ctx* ctx, int model, const float* desc, const float* xyz, int n_rows, int normalize, int on_device) {
+  if (!ctx) return MH_ERR_ARG;
+  if (n_rows < 0 || (n_rows > 0 && (!desc || !xyz))) return refuse(ctx, "mh_db_append", "bad argument");
+  if (int rc = check_edit(ctx, "mh_db_append", MH_DB_REPLACE, model)) return rc;   // (REPLACE's check: an existing model)
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
+  if (int rc = stage_given_rows(ctx, desc, xyz, n_rows, normalize, on_device)) return rc;
+  return append_staged(ctx, model, n_rows);
 }
 
 // ---- planar models from images: createPlanarModelsFromImages (moped.cpp:196-236) into the resident store ------------
 namespace {
 
-// the arguments mh_db_splice_image[s] share, checked before anything is launched
-int check_planar_call(mh_ctx* ctx, const char* who, const uint8_t* const* gray_dev, int n_images, int width, int height,
-                      int max_keypoints, const mh_planar_spec* spec, const float* rows_desc_host, const float* rows_xyz_host,
-                      int rows_cap, int* all) {
+// the images, sizes and host row arrays of every call that teaches from images, checked before anything is launched
+int check_images_call(mh_ctx* ctx, const char* who, const uint8_t* const* gray_dev, int n_images, int width, int height,
+                      int max_keypoints, const float* rows_desc_host, const float* rows_xyz_host, int rows_cap) {
   if (!gray_dev || n_images <= 0 || n_images > MH_MAX_BATCH || width <= 0 || height <= 0 || max_keypoints <= 0 ||
       (rows_desc_host == nullptr) != (rows_xyz_host == nullptr) || (rows_desc_host && rows_cap <= 0))
     return refuse(ctx, who, "bad argument");
   for (int i = 0; i < n_images; ++i)
     if (!gray_dev[i]) return refuse(ctx, who, "bad argument (a null image)");
+  return MH_OK;
+}
+
+// the arguments mh_db_splice_image[s] share
+int check_planar_call(mh_ctx* ctx, const char* who, const uint8_t* const* gray_dev, int n_images, int width, int height,
+                      int max_keypoints, const mh_planar_spec* spec, const float* rows_desc_host, const float* rows_xyz_host,
+                      int rows_cap, int* all) {
+  if (int rc = check_images_call(ctx, who, gray_dev, n_images, width, height, max_keypoints, rows_desc_host, rows_xyz_host, rows_cap))
+    return rc;
   if (int rc = planar_spec_check(ctx, who, spec, all)) return rc;
   if (ctx->und_on && (spec->K[0] == 0.f || spec->K[1] == 0.f)) return refuse(ctx, who, "undistortion is on and fx or fy is 0");
   return MH_OK;
@@ -444,12 +476,12 @@ int ensure_planar(mh_ctx* ctx, int n_images, int cap, bool rows) {
 // [UNDISTORTED_IMAGE] -> FEAT of n images into ctx->planar (counts in words[0 .. n)), FEAT's counter words behind the
 // kept counts (words[2 B + 4 i ..])
 int planar_feat(mh_ctx* ctx, const uint8_t* const* gray_dev, int n, int width, int height, int double_size, int cap,
-                const mh_planar_spec* spec) {
+                const float K[4]) {
   mh_ctx::Planar& p = ctx->planar;
   const uint8_t* staged[MH_MAX_BATCH];
   int rc;
   if (ctx->und_on) {
-    if ((rc = undistort_frame(ctx, gray_dev, n, width, height, spec->K, staged))) return rc;
+    if ((rc = undistort_frame(ctx, gray_dev, n, width, height, K, staged))) return rc;
     gray_dev = staged;
   }
   if (n == 1) {
@@ -459,6 +491,49 @@ int planar_feat(mh_ctx* ctx, const uint8_t* const* gray_dev, int n, int width, i
   }
   MH_HIP(ctx, hipMemcpyAsync(p.words + 2 * MH_MAX_BATCH, sift_counters_dev(ctx, 0), (size_t)n * 4 * sizeof(int32_t),
                              hipMemcpyDeviceToDevice, ctx->stream));
+  return MH_OK;
+}
+
+// Behind the selection of a one-image edit, whose rows lie in the staging block and whose count, box and (with_stats)
+// statistics in ctx->planar: the norm terms by the upload's own launch, over the count on the device, so that it is in
+// flight while the count travels; the added host wait -- the kept count sizes the splice (the set it fills, the
+// per-model table); the optional host rows; the edit (op of `model`, or append = rows behind its last);
+// MH_ERR_CAPACITY when FEAT's list overflowed.
+int staged_image_edit(mh_ctx* ctx, const char* who, bool append, int op, int model, int cap, int limit, bool with_stats,
+                      int32_t* n_rows, float bbox[6], int32_t stats[8], float* rows_desc_host, float* rows_xyz_host,
+                      int rows_cap) {
+  mh_ctx::Planar& p = ctx->planar;
+  float* sd = ctx->db_stage;
+  float* sn = sd + stage_rows(ctx) * DIM;
+  float* sx = sn + stage_rows(ctx);
+  const int32_t* n_out = p.words + MH_MAX_BATCH;
+  launch_normalize(sd, sn, limit, ctx->stream, n_out);
+  MH_HIP(ctx, hipGetLastError());
+  int32_t kept = 0, head[4] = {0, 0, 0, 0}, st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  float box[6];
+  MH_HIP(ctx, hipMemcpyAsync(&kept, n_out, sizeof kept, hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(ctx, hipMemcpyAsync(head, p.words + 2 * MH_MAX_BATCH, sizeof head, hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(ctx, hipMemcpyAsync(box, p.box, sizeof box, hipMemcpyDeviceToHost, ctx->stream));
+  if (with_stats) MH_HIP(ctx, hipMemcpyAsync(st, p.stats, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (kept < 0 || kept > limit) {
+    ctx->err = std::string(who) + ": the selection reported a count outside its capacity";
+    return MH_ERR_HIP;
+  }
+  if (rows_desc_host && kept > 0) {
+    const size_t take = (size_t)std::min(kept, rows_cap);
+    MH_HIP(ctx, hipMemcpyAsync(rows_desc_host, p.rows_desc, take * DIM * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    MH_HIP(ctx, hipMemcpyAsync(rows_xyz_host, sx, take * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  // (either ends with a wait for the stream: the host rows are there)
+  if (int rc = append ? append_staged(ctx, model, kept) : splice_staged(ctx, op, model, kept)) return rc;
+  if (n_rows) *n_rows = kept;
+  if (bbox) std::memcpy(bbox, box, sizeof box);
+  if (stats) std::memcpy(stats, st, sizeof st);
+  if (head[2] || head[1] > cap) {
+    ctx->err = std::string(who) + ": more keypoints than max_keypoints (" + std::to_string(head[1]) + " found); the model has the first of the list";
+    return MH_ERR_CAPACITY;
+  }
   return MH_OK;
 }
 
@@ -482,13 +557,11 @@ int mh_db_splice_image(mh_ctx* ctx, int op, int model, const uint8_t* gray_dev, 
   const int limit = spec->max_rows > 0 ? std::min(cap, spec->max_rows) : cap;
   if ((rc = ensure_planar(ctx, 1, cap, rows_desc_host != nullptr))) return rc;
   if ((rc = ensure_stage(ctx, (size_t)limit))) return rc;
-  if ((rc = planar_feat(ctx, &gray_dev, 1, width, height, double_size, cap, spec))) return rc;
+  if ((rc = planar_feat(ctx, &gray_dev, 1, width, height, double_size, cap, spec->K))) return rc;
   mh_ctx::Planar& p = ctx->planar;
-  // the selection writes the edit's staging block itself; the norm terms by the upload's own launch, over the count on
-  // the device, so that it is in flight while the count travels
+  // the selection writes the edit's staging block itself
   float* sd = ctx->db_stage;
-  float* sn = sd + stage_rows(ctx) * DIM;
-  float* sx = sn + stage_rows(ctx);
+  float* sx = sd + stage_rows(ctx) * (DIM + 1);
   PlanarArgs a = {};
   a.desc = p.desc;
   a.xy = p.xy;
@@ -504,32 +577,7 @@ int mh_db_splice_image(mh_ctx* ctx, int op, int model, const uint8_t* gray_dev, 
   a.n_out = p.words + MH_MAX_BATCH;
   a.bbox = p.box;
   launch_planar_rows(a, 1, ctx->stream);
-  launch_normalize(sd, sn, limit, ctx->stream, a.n_out);
-  MH_HIP(ctx, hipGetLastError());
-  // the added host wait: the kept count sizes the splice (the set it fills, the per-model table)
-  int32_t kept = 0, head[4] = {0, 0, 0, 0};
-  float box[6];
-  MH_HIP(ctx, hipMemcpyAsync(&kept, a.n_out, sizeof kept, hipMemcpyDeviceToHost, ctx->stream));
-  MH_HIP(ctx, hipMemcpyAsync(head, p.words + 2 * MH_MAX_BATCH, sizeof head, hipMemcpyDeviceToHost, ctx->stream));
-  MH_HIP(ctx, hipMemcpyAsync(box, p.box, sizeof box, hipMemcpyDeviceToHost, ctx->stream));
-  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (kept < 0 || kept > limit) {
-    ctx->err = "mh_db_splice_image: the selection reported a count outside its capacity";
-    return MH_ERR_HIP;
-  }
-  if (rows_desc_host && kept > 0) {
-    const size_t take = (size_t)std::min(kept, rows_cap);
-    MH_HIP(ctx, hipMemcpyAsync(rows_desc_host, p.rows_desc, take * DIM * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    MH_HIP(ctx, hipMemcpyAsync(rows_xyz_host, sx, take * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-  }
-  if ((rc = splice_staged(ctx, op, model, kept))) return rc;   // (ends with a wait for the stream: the host rows are there)
-  if (n_rows) *n_rows = kept;
-  if (bbox) std::memcpy(bbox, box, sizeof box);
-  if (head[2] || head[1] > cap) {
-    ctx->err = "mh_db_splice_image: more keypoints than max_keypoints (" + std::to_string(head[1]) + " found); the model has the first of the list";
-    return MH_ERR_CAPACITY;
-  }
-  return MH_OK;
+  return staged_image_edit(ctx, who, false, op, model, cap, limit, false, n_rows, bbox, nullptr, rows_desc_host, rows_xyz_host, rows_cap);
 }
 
 int mh_db_splice_images(mh_ctx* ctx, int model_first, const uint8_t* const* gray_dev, int n_images, int width, int height,
@@ -549,7 +597,7 @@ int mh_db_splice_images(mh_ctx* ctx, int model_first, const uint8_t* const* gray
   const int limit = spec->max_rows > 0 ? std::min(cap, spec->max_rows) : cap;
   if ((rc = ensure_planar(ctx, n_images, cap, true))) return rc;
   if ((rc = ensure_stage(ctx, (size_t)limit))) return rc;
-  if ((rc = planar_feat(ctx, gray_dev, n_images, width, height, double_size, cap, spec))) return rc;
+  if ((rc = planar_feat(ctx, gray_dev, n_images, width, height, double_size, cap, spec->K))) return rc;
   mh_ctx::Planar& p = ctx->planar;
   PlanarArgs a = {};
   a.desc = p.desc;
@@ -595,6 +643,180 @@ int mh_db_splice_images(mh_ctx* ctx, int model_first, const uint8_t* const* gray
   }
   if (over) {
     ctx->err = "mh_db_splice_images: an image has more keypoints than max_keypoints; its model has the first of the list";
+    return MH_ERR_CAPACITY;
+  }
+  return MH_OK;
+}
+
+// ---- 3-D models from Kinect views (view_rows.hip) into the resident store --------------------------------------------
+namespace {
+
+// the arguments mh_db_splice_view[s] / mh_db_append_view share, checked before anything is launched; fills a's view part
+int check_view_call(mh_ctx* ctx, const char* who, const uint8_t* const* gray_dev, const mh_view* views, int n, int width,
+                    int height, int max_keypoints, const mh_view_spec* spec, const float* rows_desc_host,
+                    const float* rows_xyz_host, int rows_cap, ViewArgs* a) {
+  if (int rc = check_images_call(ctx, who, gray_dev, n, width, height, max_keypoints, rows_desc_host, rows_xyz_host, rows_cap)) return rc;
+  if (int rc = view_args_check(ctx, who, views, n, width, height, spec, a)) return rc;
+  if (ctx->und_on)
+    if (const char* why = view_undistort_why(views, n)) return refuse(ctx, who, why);
+  return MH_OK;
+}
+
+int ensure_view(mh_ctx* ctx, int cap, bool match) {
+  mh_ctx::Planar& p = ctx->planar;
+  hipStream_t s = ctx->stream;
+  MH_HIP(ctx, p.stats.ensure(8 * MH_MAX_BATCH, s));
+  if (match) {
+    MH_HIP(ctx, p.qn.ensure((size_t)cap * DIM, s));
+    MH_HIP(ctx, p.qnorm.ensure(cap, s));
+    MH_HIP(ctx, p.m_idx.ensure(cap, s));
+    MH_HIP(ctx, p.m_d1.ensure(cap, s));
+    MH_HIP(ctx, p.m_d2.ensure(cap, s));
+  }
+  return MH_OK;
+}
+
+// mh_db_splice_view (append = false: op, model) and mh_db_append_view (append = true: model)
+int view_edit(mh_ctx* ctx, const char* who, bool append, int op, int model, const uint8_t* gray_dev, const mh_view* view,
+              int width, int height, int double_size, int max_keypoints, const mh_view_spec* spec, int32_t* n_rows,
+              float bbox[6], int32_t stats[8], float* rows_desc_host, float* rows_xyz_host, int rows_cap) {
+  if (n_rows) *n_rows = 0;
+  if (!append && op != MH_DB_INSERT && op != MH_DB_REPLACE) return refuse(ctx, who, "the operation is MH_DB_INSERT or MH_DB_REPLACE");
+  ViewArgs a = {};
+  int rc;
+  if ((rc = check_view_call(ctx, who, &gray_dev, view, 1, width, height, max_keypoints, spec, rows_desc_host, rows_xyz_host,
+                            rows_cap, &a)))
+    return rc;
+  if ((rc = check_edit(ctx, who, append ? (int)MH_DB_REPLACE : op, model))) return rc;   // (append: an existing model)
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
+  const int cap = max_keypoints;
+  const int limit = spec->max_rows > 0 ? std::min(cap, spec->max_rows) : cap;
+  const bool match = append && spec->merge_ratio > 0.f && spec->merge_dist >= 0.f && ctx->N > 0;
+  if ((rc = ensure_planar(ctx, 1, cap, rows_desc_host != nullptr))) return rc;
+  if ((rc = ensure_view(ctx, cap, match))) return rc;
+  if ((rc = ensure_stage(ctx, (size_t)limit))) return rc;
+  if ((rc = planar_feat(ctx, &gray_dev, 1, width, height, double_size, cap, view->K))) return rc;
+  mh_ctx::Planar& p = ctx->planar;
+  if (append && ctx->N > 0) {   // the model's rows so far: the box covers them; the duplicate test reads them
+    a.dup.model_of_dev = ctx->db_model;
+    a.dup.xyz_dev = ctx->db_xyz;
+    a.dup.n_db_rows = ctx->N;
+    a.dup.model = model;
+    a.dup.row_begin = ctx->store->model_begin[model];
+    a.dup.row_end = ctx->store->model_begin[model + 1];
+  }
+  if (match) {
+    // MATCH as a frame's: a normalised copy (the model's rows keep FEAT's bits), the count on the device
+    MH_HIP(ctx, hipMemcpyAsync(p.qn, p.desc, (size_t)cap * DIM * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    launch_normalize(p.qn, p.qnorm, cap, ctx->stream, p.words);
+    if ((rc = ctx_match(ctx, p.qn, p.qnorm, cap, p.m_idx, p.m_d1, p.m_d2, p.words, 0))) return rc;
+    a.dup.idx_dev = p.m_idx;
+    a.dup.d1_dev = p.m_d1;
+    a.dup.d2_dev = p.m_d2;
+    a.dup_on = 1;
+  }
+  // the selection writes the edit's staging block itself, as mh_db_splice_image's does
+  float* sd = ctx->db_stage;
+  a.desc = p.desc;
+  a.xy = p.xy;
+  a.n = p.words;
+  a.cap = cap;
+  a.desc_out = sd;
+  a.desc_copy = rows_desc_host ? (float*)p.rows_desc : nullptr;   // (normalisation is in place: the host gets FEAT's bits)
+  a.xyz_out = sd + stage_rows(ctx) * (DIM + 1);
+  a.out_pitch = 0;
+  a.out_cap = limit;
+  a.n_out = p.words + MH_MAX_BATCH;
+  a.bbox = p.box;
+  a.stats = p.stats;
+  launch_view_rows(a, 1, ctx->stream);
+  return staged_image_edit(ctx, who, append, op, model, cap, limit, true, n_rows, bbox, stats, rows_desc_host, rows_xyz_host, rows_cap);
+}
+
+}  // namespace
+
+int mh_db_splice_view(mh_ctx* ctx, int op, int model, const uint8_t* gray_dev, const mh_view* view, int width, int height,
+                      int double_size, int max_keypoints, const mh_view_spec* spec, int32_t* n_rows, float bbox[6],
+                      int32_t stats[8], float* rows_desc_host, float* rows_xyz_host, int rows_cap) {
+  if (!ctx) return MH_ERR_ARG;
+  return view_edit(ctx, "mh_db_splice_view", false, op, model, gray_dev, view, width, height, double_size, max_keypoints, spec,
+                   n_rows, bbox, stats, rows_desc_host, rows_xyz_host, rows_cap);
+}
+
+int mh_db_append_view(mh_ctx* ctx, int model, const uint8_t* gray_dev, const mh_view* view, int width, int height,
+                      int double_size, int max_keypoints, const mh_view_spec* spec, int32_t* n_rows, float bbox[6],
+                      int32_t stats[8], float* rows_desc_host, float* rows_xyz_host, int rows_cap) {
+  if (!ctx) return MH_ERR_ARG;
+  return view_edit(ctx, "mh_db_append_view", true, MH_DB_REPLACE, model, gray_dev, view, width, height, double_size,
+                   max_keypoints, spec, n_rows, bbox, stats, rows_desc_host, rows_xyz_host, rows_cap);
+}
+
+int mh_db_splice_views(mh_ctx* ctx, int model_first, const uint8_t* const* gray_dev, const mh_view* views, int n_views,
+                       int width, int height, int double_size, int max_keypoints, const mh_view_spec* spec, int32_t* n_rows,
+                       float (*bbox)[6], int32_t (*stats)[8], float* rows_desc_host, float* rows_xyz_host, int rows_cap) {
+  if (!ctx) return MH_ERR_ARG;
+  const char* who = "mh_db_splice_views";
+  ViewArgs a = {};
+  int rc;
+  if ((rc = check_view_call(ctx, who, gray_dev, views, n_views, width, height, max_keypoints, spec, rows_desc_host,
+                            rows_xyz_host, rows_cap, &a)))
+    return rc;
+  if ((rc = check_edit(ctx, who, MH_DB_INSERT, model_first, n_views))) return rc;
+  for (int i = 0; n_rows && i < n_views; ++i) n_rows[i] = 0;
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
+  const int cap = max_keypoints;
+  const int limit = spec->max_rows > 0 ? std::min(cap, spec->max_rows) : cap;
+  if ((rc = ensure_planar(ctx, n_views, cap, true))) return rc;
+  if ((rc = ensure_view(ctx, cap, false))) return rc;
+  if ((rc = ensure_stage(ctx, (size_t)limit))) return rc;
+  if ((rc = planar_feat(ctx, gray_dev, n_views, width, height, double_size, cap, views[0].K))) return rc;
+  mh_ctx::Planar& p = ctx->planar;
+  a.desc = p.desc;
+  a.xy = p.xy;
+  a.n = p.words;
+  a.cap = cap;
+  a.desc_out = p.rows_desc;
+  a.desc_copy = nullptr;
+  a.xyz_out = p.rows_xyz;
+  a.out_pitch = (size_t)cap;
+  a.out_cap = limit;
+  a.n_out = p.words + MH_MAX_BATCH;
+  a.bbox = p.box;
+  a.stats = p.stats;
+  launch_view_rows(a, n_views, ctx->stream);
+  MH_HIP(ctx, hipGetLastError());
+  // one read-back for the whole batch
+  int32_t kept[MH_MAX_BATCH], head[MH_MAX_BATCH][4], st[MH_MAX_BATCH][8];
+  float box[MH_MAX_BATCH][6];
+  MH_HIP(ctx, hipMemcpyAsync(kept, a.n_out, (size_t)n_views * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(ctx, hipMemcpyAsync(head, p.words + 2 * MH_MAX_BATCH, (size_t)n_views * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(ctx, hipMemcpyAsync(box, p.box, (size_t)n_views * 6 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(ctx, hipMemcpyAsync(st, p.stats, (size_t)n_views * 8 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  bool over = false;
+  for (int i = 0; i < n_views; ++i) {
+    if (kept[i] < 0 || kept[i] > limit) {
+      ctx->err = "mh_db_splice_views: the selection reported a count outside its capacity";
+      return MH_ERR_HIP;
+    }
+    const float* rd = p.rows_desc + (size_t)i * cap * DIM;
+    const float* rx = p.rows_xyz + (size_t)i * cap * 3;
+    if (rows_desc_host && kept[i] > 0) {
+      const size_t take = (size_t)std::min(kept[i], rows_cap);
+      MH_HIP(ctx, hipMemcpyAsync(rows_desc_host + (size_t)i * rows_cap * DIM, rd, take * DIM * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+      MH_HIP(ctx, hipMemcpyAsync(rows_xyz_host + (size_t)i * rows_cap * 3, rx, take * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    // the single-model pass, once per view
+    if ((rc = mh_db_splice(ctx, MH_DB_INSERT, model_first + i, rd, rx, kept[i], 1, 1))) return rc;
+    if (n_rows) n_rows[i] = kept[i];
+    if (bbox) std::memcpy(bbox[i], box[i], sizeof box[i]);
+    if (stats) std::memcpy(stats[i], st[i], sizeof st[i]);
+    over = over || head[i][2] || head[i][1] > cap;
+  }
+  if (over) {
+    ctx->err = "mh_db_splice_views: a view has more keypoints than max_keypoints; its model has the first of the list";
     return MH_ERR_CAPACITY;
   }
   return MH_OK;

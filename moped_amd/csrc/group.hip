@@ -20,11 +20,6 @@ __device__ unsigned long long g_group_prof[8];
 #endif
 constexpr int GROUP_LDS_M = 2048;       // accepted matches whose (model, pixel) wait in LDS for the rank / representative scans
 
-__device__ __forceinline__ bool accepted(int32_t idx, float d1, float d2, float ratio) {
-  // squared distances, fp32 division, exactly `ds[0]/ds[1] < Ratio` (:165)
-  return idx >= 0 && (__fdiv_rn(d1, d2) < ratio);
-}
-
 // MATCH_ADAPTIVE_FLANN_CPU::getRatio (moped3d/libmoped/src/match/MATCH_ADAPTIVE_FLANN_CPU.hpp:193-215);
 // cp = (maxRatioDepth, minRatioDepth, ratioLow, ratioHigh) of the model.
 __device__ __forceinline__ float ratio_at(float depth, const float4 cp, float max_depth) {
@@ -53,7 +48,7 @@ __global__ void accept_kernel(const int32_t* __restrict__ idx1, const float* __r
                               const float* __restrict__ d2, int Q, float ratio,
                               int32_t* __restrict__ out_idx) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q < Q) out_idx[q] = accepted(idx1[q], d1[q], d2[q], ratio) ? idx1[q] : -1;
+  if (q < Q) out_idx[q] = match_accepted(idx1[q], d1[q], d2[q], ratio) ? idx1[q] : -1;
 }
 
 // Merge of the shards' top-2 (exchange 1 of a model-sharded DB): lower index wins a tie
@@ -176,7 +171,7 @@ __global__ __launch_bounds__(GROUP_THREADS) void group_kernel(
             const float fill = dimg.fill ? dimg.fill[(size_t)y * dimg.w + x] : 0.f;
             rq = adjusted_ratio(depth, fill, rules.ratio_table[model], rules);
           }
-          ok = reachable && accepted(gi, d1[q], d2[q], rq);
+          ok = reachable && match_accepted(gi, d1[q], d2[q], rq);
         }
       }
       okv[ps] = ok;

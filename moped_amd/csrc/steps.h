@@ -128,6 +128,14 @@ void launch_group(const int32_t* gathered, int n_shards, int32_t* idx1, float* d
 void launch_rep(const mh_corr* corr, int M, int32_t* rep, hipStream_t s, const int32_t* img = nullptr);
 void launch_accept(const int32_t* idx1, const float* d1, const float* d2, int Q, float ratio,
                    int32_t* out_idx, hipStream_t s);
+#ifdef __HIPCC__
+// MATCH's acceptance test, the one place it is written (group.hip: accept_kernel and the frames' group_kernel;
+// view_rows.hip: the duplicate test of an appended view): squared distances, fp32 division, exactly
+// `ds[0]/ds[1] < Ratio` (MATCH_ANN_CPU.hpp:165)
+__device__ __forceinline__ bool match_accepted(int32_t idx, float d1, float d2, float ratio) {
+  return idx >= 0 && (__fdiv_rn(d1, d2) < ratio);
+}
+#endif
 
 // ---- mean shift ----------------------------------------------------------------
 // CLUSTER of a frame, or of the frames of a batch (`batch`): ONE row of `grid` workgroups shares the models that have

@@ -10,4 +10,5 @@ namespace std { using tr1::shared_ptr; }
 #include "FILTER_PROJECTION_HIP.hpp"
 #include "FRAME_RESIDENT_HIP.hpp"
 #include "planar_models_hip.hpp"
+#include "kinect_models_hip.hpp"
 int main() { return 0; }

@@ -82,6 +82,25 @@ class ShardedDB:
         self.block_global_row = np.zeros(1 if n else 0, np.int32)
         self.block_rows = np.full(1 if n else 0, n, np.int32)
 
+    def append(self, model: int, desc, xyz):
+        """The append form of `splice` (Context.db_append): rows behind the last row of an existing model; the model
+        keeps its index, the model ids stay as they are."""
+        if not 0 <= model < self.n_models:
+            raise ValueError("model index out of range")
+        if self.world > 1 or len(self.block_rows) > 1 or self.row_lo != 0:
+            raise ValueError("a sharded model database cannot be edited in place")
+        e = int(np.searchsorted(self.model_of, model, "right"))
+        desc = np.ascontiguousarray(desc, np.float32).reshape(-1, 128)
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        self.desc = np.ascontiguousarray(np.concatenate([self.desc[:e], desc, self.desc[e:]]))
+        self.xyz = np.ascontiguousarray(np.concatenate([self.xyz[:e], xyz, self.xyz[e:]]))
+        self.model_of = np.concatenate([self.model_of[:e], np.full(len(desc), model, np.int32), self.model_of[e:]]).astype(np.int32)
+        n = len(self.model_of)
+        self.rows = np.arange(n, dtype=np.int32)
+        self.row_lo, self.row_hi = 0, n
+        self.block_global_row = np.zeros(1 if n else 0, np.int32)
+        self.block_rows = np.full(1 if n else 0, n, np.int32)
+
     def upload(self, ctx: "capi.Context", normalized):
         if len(self.block_rows) > 1:
             ctx.db_upload_blocks(normalized, self.model_of, self.xyz, self.n_models, self.block_global_row, self.block_rows)
@@ -289,6 +308,106 @@ class FramePipeline:
             if k not in fresh:
                 out[k] = self.add_planar_model(images_dev[k], nm, scale, z, roi, max_rows, max_keypoints, double_size)
         return out
+
+    # ---- a 3-D model taught from Kinect views: image + depth map + the object's pose in the view ------------------
+    def _view_args(self, depth_dev, fill_dev, pose, roi, box, max_fill_distance, max_rows, merge_ratio=0.0, merge_dist=-1.0):
+        if self.world > 1 or self.exchange:
+            raise ValueError("a sharded model database cannot be edited in place: rebuild the pipeline")
+        view = capi.make_view(depth_dev.data_ptr(), fill_dev.data_ptr() if fill_dev is not None else None, pose, self.K)
+        spec = capi.make_view_spec(roi=roi, box=box, max_fill_distance=max_fill_distance, max_rows=max_rows,
+                                   merge_ratio=merge_ratio, merge_dist=merge_dist)
+        return view, spec
+
+    def add_kinect_model(self, image_dev: torch.Tensor, depth_dev: torch.Tensor, fill_dev=None, name=None, pose=None,
+                         roi=None, box=None, max_fill_distance=-1.0, max_rows=0, max_keypoints: int = 4096,
+                         double_size: bool = True):
+        """image_dev [h, w] uint8, depth_dev [h, w, 4] float32 (the map every depth entry point takes), optionally
+        fill_dev [h, w], all on this GPU -> a model whose points are the measured 3-D points of the image's keypoints,
+        in the model frame: pose = (qx, qy, qz, qw, tx, ty, tz) is the object's pose in this view, X_cam = R X_model + t
+        (None = the camera frame is the model frame).  roi / box / max_fill_distance / max_rows: mh_view_spec.  A known
+        name replaces that model.  FEAT, the selection and the splice run on slot 0's stream, the other slots adopt; a
+        host copy of the rows keeps `self.db` in step.  Returns (index, n_rows, bbox[6], stats[8]); the caller
+        refreshes moped3d's control points from bbox / n_rows, as after add_model."""
+        view, spec = self._view_args(depth_dev, fill_dev, pose, roi, box, max_fill_distance, max_rows)
+        h, w = image_dev.shape
+        known = name is not None and name in self.model_names
+        i = self.model_names.index(name) if known else self.db.n_models
+        op = capi.DB_REPLACE if known else capi.DB_INSERT
+        n, bbox, stats, desc, xyz = self.ctxs[0].db_splice_view(op, i, image_dev.data_ptr(), view, w, h, spec, double_size,
+                                                               max_keypoints, want_rows=True)
+        self._adopt_planar(op, i, desc, xyz)
+        self._warn_if_truncated(max_keypoints)
+        if not known:
+            self.model_names.append(name)
+        return i, n, bbox, stats
+
+    def add_kinect_models(self, images_dev, depths_dev, names, fills_dev=None, poses=None, roi=None, box=None,
+                          max_fill_distance=-1.0, max_rows=0, max_keypoints: int = 4096, double_size: bool = True):
+        """The same for several views of one size, each a model of its own: new names through ONE FEAT batch and one
+        selection launch (mh_db_splice_views), known names one by one.  Duplicates among the views are not looked for.
+        Returns a list of (index, n_rows, bbox, stats); control points as after add_kinect_model."""
+        if not (len(images_dev) == len(depths_dev) == len(names)):
+            raise ValueError("one depth map and one name per image")
+        fills_dev = fills_dev if fills_dev is not None else [None] * len(names)
+        poses = poses if poses is not None else [None] * len(names)
+        out = [None] * len(names)
+        fresh = [k for k, nm in enumerate(names) if nm is None or (nm not in self.model_names and nm not in names[:k])]
+        for b in range(0, len(fresh), capi.MAX_BATCH):
+            part = fresh[b:b + capi.MAX_BATCH]
+            h, w = images_dev[part[0]].shape
+            if any(tuple(images_dev[k].shape) != (h, w) for k in part):
+                raise ValueError("the images of one call have one size")
+            views = []
+            for k in part:
+                view, spec = self._view_args(depths_dev[k], fills_dev[k], poses[k], roi, box, max_fill_distance, max_rows)
+                views.append(view)
+            first = self.db.n_models
+            n, bbox, stats, desc, xyz = self.ctxs[0].db_splice_views(first, [images_dev[k].data_ptr() for k in part], views, w, h,
+                                                                    spec, double_size, max_keypoints, want_rows=True)
+            for c in self.ctxs[1:]:
+                c.db_adopt(self.ctxs[0])
+            self._warn_if_truncated(max_keypoints)
+            for j, k in enumerate(part):
+                self.db.splice(capi.DB_INSERT, first + j, desc[j], xyz[j])
+                self.model_names.append(names[k])
+                out[k] = (first + j, int(n[j]), bbox[j], stats[j])
+        for k, nm in enumerate(names):   # known names (or a name given twice) replace, as addModel does
+            if k not in fresh:
+                out[k] = self.add_kinect_model(images_dev[k], depths_dev[k], fills_dev[k], nm, poses[k], roi, box,
+                                               max_fill_distance, max_rows, max_keypoints, double_size)
+        return out
+
+    def extend_kinect_model(self, i: int, image_dev: torch.Tensor, depth_dev: torch.Tensor, fill_dev=None, pose=None, roi=None,
+                            box=None, max_fill_distance=-1.0, max_rows=0, merge_ratio=0.8, merge_dist=0.002,
+                            max_keypoints: int = 4096, double_size: bool = True):
+        """A further view of model i: its keypoints are appended behind the model's rows, except those the model holds
+        already -- the ones MATCH accepts at merge_ratio whose nearest row is a row of model i within merge_dist (model
+        units) of the keypoint's point.  merge_ratio <= 0 or merge_dist < 0: no such test, and no MATCH.  Returns
+        (index, rows added, bbox of the whole model, stats[8]); the caller refreshes moped3d's control points from
+        bbox and the model's new row count, as after add_model."""
+        view, spec = self._view_args(depth_dev, fill_dev, pose, roi, box, max_fill_distance, max_rows, merge_ratio, merge_dist)
+        h, w = image_dev.shape
+        n, bbox, stats, desc, xyz = self.ctxs[0].db_append_view(i, image_dev.data_ptr(), view, w, h, spec, double_size,
+                                                               max_keypoints, want_rows=True)
+        for c in self.ctxs[1:]:
+            c.db_adopt(self.ctxs[0])
+        self.db.append(i, desc, xyz)
+        self._warn_if_truncated(max_keypoints)
+        return i, n, bbox, stats
+
+    def append_model_rows(self, i: int, desc, xyz):
+        """desc [n,128] raw descriptors, xyz [n,3] behind the last row of model i (Context.db_append), normalised on the
+        device like Update(); stream ordered as every edit.  Returns (index, rows added, bbox of the whole model, None);
+        control points as after add_model."""
+        if self.world > 1 or self.exchange:
+            raise ValueError("a sharded model database cannot be edited in place: rebuild the pipeline")
+        self.ctxs[0].db_append(i, desc, xyz, normalize=True)
+        for c in self.ctxs[1:]:
+            c.db_adopt(self.ctxs[0])
+        self.db.append(i, desc, xyz)
+        mine = self.db.xyz[self.db.model_of == i]
+        bbox = np.concatenate([mine.min(0), mine.max(0)]).astype(np.float32) if len(mine) else None
+        return i, len(np.asarray(desc).reshape(-1, 128)), bbox, None
 
     # ---- single frame in slot i ------------------------------------------------------
     def enqueue(self, slot: int, q_desc: torch.Tensor, q_uv: torch.Tensor, seed: int = 1,
