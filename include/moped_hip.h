@@ -236,6 +236,8 @@ void mh_screen_record_bounds(uint16_t value_bits, uint32_t row0, float tau, floa
  *                           launched: out = {1 if one sweep, first sampled tile, sampling stride, sampled tiles, pass A
  *                           splits, identity bits, pass B splits, pass B tiles}; all zero when the launch does not run
  *                           on the 16x16x32 passes
+ *   mh_screen_park_places   hits a wavefront of pass B of the 16x16x32 launches parks in LDS during its sweep before
+ *                           further hits append to their queries' lists from the hit path (for tests that fill it)
  *   mh_match_incomplete     queries since the last reset for which a lane slot of pass A held more blocks above the
  *                           threshold than it keeps, so that pass C swept that slot's rows (bounded; never the brute-force
  *                           search mh_match_stats counts).  Synchronises the context's stream.
@@ -247,6 +249,7 @@ float mh_screen_pack_value(float v, uint32_t id, int bits);
 float mh_screen_pack_pert(float qq, float dmax, int bits);
 void mh_screen_sample_bounds(uint16_t value_bits, float tau, float pert, float dmax, float* lo, float* hi);
 void mh_screen_launch_plan(int Q, int q_expected, int N, int32_t out[8]);
+int mh_screen_park_places(void);
 int mh_match_incomplete(mh_ctx* ctx, uint32_t* count, int reset);
 int mh_screen_sample_values(mh_ctx* ctx, const float* q_host, int Q, const int32_t* row0_host, float* out_host);
 /* mh_match_stats' candidate rows -- rows that ran the canonical chain in pass C -- per query since the last reset:

@@ -229,7 +229,7 @@ EXPORTS = [
     "mh_sift_extract_batch_dev", "mh_sift_debug_plan", "mh_sift_debug_level", "mh_sift_debug_candidates",
     "mh_sift_debug_keys", "mh_sift_debug_blur",
     "mh_screen_pack_value", "mh_screen_pack_pert", "mh_screen_sample_bounds", "mh_screen_launch_plan", "mh_match_incomplete",
-    "mh_screen_sample_values", "mh_match_query_candidates",
+    "mh_screen_sample_values", "mh_match_query_candidates", "mh_screen_park_places",
     "mh_frame_enqueue_images", "mh_frame_enqueue_images_batch", "mh_frame_set_undistort_images", "mh_frame_image_counts",
     "mh_frame_features_image_dev",
     "mh_filter_depth_set_points", "mh_filter_depth", "mh_frame_set_filter_depth",
@@ -610,6 +610,13 @@ def screen_launch_plan(Q, N, q_expected=0) -> dict:
     load().mh_screen_launch_plan(int(Q), int(q_expected), int(N), _ptr(o))
     keys = ("onesweep", "tile_first", "tile_stride", "sampled_tiles", "splits_a", "pack_bits", "splits_b", "tiles_b")
     return {k: int(v) for k, v in zip(keys, o)}
+
+
+def screen_park_places() -> int:
+    """mh_screen_park_places: hits a wavefront of pass B of the 16x16x32 launches parks before it appends from the hit path."""
+    f = load().mh_screen_park_places   # (bound here, not in load(): A/B runs load older builds of the library by MH_LIB_PATH)
+    f.argtypes, f.restype = [], C.c_int
+    return int(f())
 
 
 FRAME_HEAD_DTYPE = np.dtype([("n_objects", "<i4"), ("flags", "<i4"), ("counts", "<i4", (4,)), ("tag", "<u4"), ("frame", "<i4")])

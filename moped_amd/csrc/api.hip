@@ -627,6 +627,8 @@ void mh_screen_launch_plan(int Q, int q_expected, int N, int32_t out[8]) {
   for (int k = 0; k < 8; ++k) out[k] = v[k];
 }
 
+int mh_screen_park_places(void) { return screen_park_places(); }
+
 int mh_match_incomplete(mh_ctx* ctx, uint32_t* count, int reset) {
   if (!ctx || !count) return MH_ERR_ARG;
   MH_HIP(ctx, hipSetDevice(ctx->device));

@@ -880,12 +880,29 @@ __global__ __launch_bounds__(64 * NW, 2) void screen_kernel(const ScreenArgs A) 
 // XCD-aware unit map, the parked records and the exactness argument are those of screen_kernel.
 typedef float v4f __attribute__((ext_vector_type(4)));
 constexpr int SC_REC16_BYTES = 48;                  // {slot, row0, thr, top, 8 dots}
-constexpr int SC_RECBUF16 = 8 * 1024 / SC_REC16_BYTES;   // 170 parked hits per wavefront in 8 KB
+// Parked hits per wavefront: what the 160 KB of a compute unit leave beside the tiles and the thresholds (the 256-register
+// workgroup has the CU to itself whatever its LDS), 11.25 KB.  A hit that finds the buffer full appends from the hit path
+// with an atomic add whose value it waits for, and seven wavefronts wait for it at the tile's barrier: with 170 places (8
+// KB) 51 775 hits of a judged launch did; profiles/wave_sublists_ab.txt has what pass B costs without any.
+constexpr int SC_RECBUF16 = 240;
 constexpr int SC_LDS16_TAU = SC_LDS_TILES + 8 * SC_RECBUF16 * SC_REC16_BYTES;   // the wavefronts' thresholds: 8 x 128 floats
 constexpr int SC_LDS16_BYTES = SC_LDS16_TAU + 8 * 128 * 4;
+static_assert(SC_LDS16_BYTES <= 160 * 1024, "screen16_kernel's LDS fits a gfx950 compute unit");
 
+// Experiment builds, PLACES (MH_SCREEN_PLACES; WRONG results, timing only -- what the places' atomic adds cost pass B,
+// profiles/wave_sublists_ab.txt): 1 = flush_parked takes a record's place from lane arithmetic instead of the atomic add
+// (the stores stay), 2 = so does the buffer-full branch of `emit` as well (no atomic left in the hit path), 3 = the product's
+// kernel.  (0, this build's default, also counts the hits that find the buffer full -- g_sc_direct_appends, an atomic of
+// its own in the hit path and four spilled registers more; 1, 2 and 3 do not.)
+#ifdef MH_EXPERIMENTS
+template <int MODE, int NQB, int PLACES = 0>
+#else
 template <int MODE, int NQB>
+#endif
 __global__ __launch_bounds__(512, 2) void screen16_kernel(const ScreenArgs A) {
+#ifndef MH_EXPERIMENTS
+  constexpr int PLACES = 0;
+#endif
   MH_TRACE_SCOPE(MODE == 0 ? mh::TK_PASS_A : mh::TK_PASS_B);
   constexpr int NW = 8;
   constexpr int QW = 32 * NQB;            // queries per wavefront
@@ -990,11 +1007,11 @@ __global__ __launch_bounds__(512, 2) void screen16_kernel(const ScreenArgs A) {
       e[2] = make_uint4(__float_as_uint(d1[0]), __float_as_uint(d1[1]), __float_as_uint(d1[2]), __float_as_uint(d1[3]));
     } else {
 #ifdef MH_EXPERIMENTS
-      atomicAdd(&g_sc_direct_appends, 1ull);
+      if (PLACES == 0) atomicAdd(&g_sc_direct_appends, 1ull);
 #endif
       // buffer full.  (The list's address is worked out HERE: the lane's eight queries never change, and the compiler
       // would keep eight 64-bit addresses across the sweep for this branch alone -- 16 registers this kernel does not have.)
-      const int at = atomicAdd(&A.ovf_cnt[q], 1);
+      const int at = PLACES == 2 ? SC_SA_SLOTS + (pos & 3) * A.n_splits + split : atomicAdd(&A.ovf_cnt[q], 1);
       int qa = q;
       asm volatile("" : "+v"(qa));
       append(qa, at, (unsigned)row0, record_bits8(d0, d1, top, thr));
@@ -1013,7 +1030,7 @@ __global__ __launch_bounds__(512, 2) void screen16_kernel(const ScreenArgs A) {
            n_parked + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(h1 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)h1, 0u)));
     n_parked += __popcll(h1);
   };
-  // The wavefront's parked hits go to their queries' lists: lane j takes the parked records j, j + 64, j + 128.  Every
+  // The wavefront's parked hits go to their queries' lists: lane j takes the parked records j, j + 64, j + 128, j + 192.  Every
   // atomic add of the flush is issued before the first returned place is looked at -- one round trip, at the end of the
   // workgroup's sweep, outside the hit path.
   auto flush_parked = [&]() {
@@ -1032,7 +1049,7 @@ __global__ __launch_bounds__(512, 2) void screen16_kernel(const ScreenArgs A) {
 #pragma unroll
     for (int i = 0; i < TRIPS; ++i) {
       at[i] = SC_SLOT_PITCH;
-      if (lane + 64 * i < n) at[i] = atomicAdd(&A.ovf_cnt[e[i].x], 1);
+      if (lane + 64 * i < n) at[i] = PLACES == 1 || PLACES == 2 ? SC_SA_SLOTS + ((lane + i) & 3) * A.n_splits + split : atomicAdd(&A.ovf_cnt[e[i].x], 1);
     }
 #pragma unroll
     for (int i = 0; i < TRIPS; ++i)
@@ -1900,6 +1917,7 @@ void launch_screen_prepare(const float* qn, const float* qnorm, int Q, int q_pad
 }
 
 size_t screen_rec_slots() { return SC_SLOT_PITCH; }
+int screen_park_places() { return SC_RECBUF16; }
 
 int screen_q_pad(int Q) { return (Q + SC_QPAD - 1) / SC_QPAD * SC_QPAD; }
 int screen_max_splits_a() { return 64; }
@@ -2098,6 +2116,21 @@ void launch_passes16(ScreenArgs a, int Q, int qe, int n_tiles, int sample, int b
   a.tiles_base = p.n_sel_b / p.Sb;
   a.tiles_rem = p.n_sel_b % p.Sb;
   // (no sub_cap: a query's records go to its one counted list, and pass C finds them by the count)
+#ifdef MH_EXPERIMENTS
+  // what the places' atomic adds cost pass B (screen16_kernel's PLACES; WRONG results: timing only)
+  static const int places = exp_int("MH_SCREEN_PLACES", 0);
+  static DynLds attr_p1, attr_p2, attr_p3;
+  if (places == 3) {
+    attr_p3.ensure(screen16_kernel<1, NQB, 3>, SC_LDS16_BYTES);
+    hipLaunchKernelGGL((screen16_kernel<1, NQB, 3>), dim3(nqb * p.Sb), dim3(512), SC_LDS16_BYTES, s, a);
+  } else if (places == 1) {
+    attr_p1.ensure(screen16_kernel<1, NQB, 1>, SC_LDS16_BYTES);
+    hipLaunchKernelGGL((screen16_kernel<1, NQB, 1>), dim3(nqb * p.Sb), dim3(512), SC_LDS16_BYTES, s, a);
+  } else if (places == 2) {
+    attr_p2.ensure(screen16_kernel<1, NQB, 2>, SC_LDS16_BYTES);
+    hipLaunchKernelGGL((screen16_kernel<1, NQB, 2>), dim3(nqb * p.Sb), dim3(512), SC_LDS16_BYTES, s, a);
+  } else
+#endif
   hipLaunchKernelGGL((screen16_kernel<1, NQB>), dim3(nqb * p.Sb), dim3(512), SC_LDS16_BYTES, s, a);
   if (ev) hipEventRecord(ev[4], s);
   *n_slots_out = 0;

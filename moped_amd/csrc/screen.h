@@ -144,6 +144,7 @@ size_t screen_part_bytes(int q_pad);   // pass A's output buffer
 // tiles pass A samples): out = {one-sweep launch (0 / 1), tile_first, tile_stride, sampled tiles, pass A splits, pack bits,
 // pass B splits, pass B tiles}
 void screen_launch_plan(int Q, int q_expected, int N, int out[8]);
+int screen_park_places();   // hits a wavefront of screen16_kernel's pass B parks before it appends from the hit path (SC_RECBUF16)
 // mode: -1 = decide by size, 0 = never, 1 = whenever the DB has an f16 image (mh_match_set_mode)
 bool screen_wanted(int q_expected, int N, int mode = -1);
 // Same contract as launch_match (match.hip): exact (idx1, d1, d2) per query.
