@@ -251,6 +251,24 @@ void mh_screen_sample_bounds(uint16_t value_bits, float tau, float pert, float d
 void mh_screen_launch_plan(int Q, int q_expected, int N, int32_t out[8]);
 int mh_screen_park_places(void);
 int mh_match_incomplete(mh_ctx* ctx, uint32_t* count, int reset);
+/* MATCH for a caller that applies the ratio test.  The frames' only reader of a query's (idx1, d1, d2) is the test
+ * `d1 / d2 < ratio`; of a query that fails it nothing else is read.  Pass C of the two-stage MATCH holds, after its first
+ * round trip, bounds of the query's two best screen values, and answers a query they prove to fail with (-1, inf, inf)
+ * -- "no neighbour", which the test rejects as well -- without the search.
+ *   mh_screen_reject_proved  the proof, in host arithmetic (the inline function the kernel runs): qq = dot(q,q), dmax =
+ *                            the largest row norm, h1 = the largest upper bound and l2 = the second largest lower bound
+ *                            (over distinct records) of a record's largest screen value, tau = the query's threshold.
+ *                            1 = no exact arithmetic can give d1 / d2 < ratio; 0 for ratio <= 0, a non-finite input,
+ *                            l2 = -inf or a d2 whose upper bound is not positive.
+ *   mh_match_set_accept      ratio = 0 (the default): resident single-GPU frames hand MATCH their mh_frame_params::ratio
+ *                            unless the context has a depth-adaptive ratio table; every mh_match* entry point, the
+ *                            sharded frames, the steps and the DB edits get the exact triple of every query.
+ *                            ratio > 0: mh_match / mh_normalize_match hand MATCH this ratio as well (nn_raw, d1, d2 of a
+ *                            query it rejects may then read -1, inf, inf).  ratio < 0: nobody does, frames included.
+ *   mh_match_prerejected     queries answered that way since the last reset.  Synchronises the context's stream. */
+int mh_screen_reject_proved(float qq, float dmax, float h1, float l2, float tau, float ratio);
+int mh_match_set_accept(mh_ctx* ctx, float ratio);
+int mh_match_prerejected(mh_ctx* ctx, uint32_t* count, int reset);
 int mh_screen_sample_values(mh_ctx* ctx, const float* q_host, int Q, const int32_t* row0_host, float* out_host);
 /* mh_match_stats' candidate rows -- rows that ran the canonical chain in pass C -- per query since the last reset:
  * out[q] for the first Q queries of the context's two-stage launches.  Synchronises the context's stream. */

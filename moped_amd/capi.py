@@ -245,6 +245,7 @@ EXPORTS = [
     "mh_object_hulls", "mh_hull_debug_form",
     "mh_frame_set_hulls", "mh_frame_fetch_hulls_slot", "mh_frame_fetch_hulls", "mh_frame_hull_block_stride",
     "mh_frame_fetch_batch_hulls_async",
+    "mh_screen_reject_proved", "mh_match_set_accept", "mh_match_prerejected",
 ]
 COMM_ID_BYTES = 128      # MH_COMM_ID_BYTES
 EX2_OBJECTS = 62         # MH_EX2_OBJECTS
@@ -460,6 +461,10 @@ def load():
         L.mh_screen_launch_plan.argtypes = [i32, i32, i32, vp]
         L.mh_screen_launch_plan.restype = None
         L.mh_match_incomplete.argtypes = [vp, C.POINTER(C.c_uint32), i32]
+    if hasattr(L, "mh_screen_reject_proved"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
+        L.mh_screen_reject_proved.argtypes = [f32, f32, f32, f32, f32, f32]
+        L.mh_match_set_accept.argtypes = [vp, f32]
+        L.mh_match_prerejected.argtypes = [vp, C.POINTER(C.c_uint32), i32]
     if hasattr(L, "mh_screen_sample_values"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
         L.mh_screen_sample_values.argtypes = [vp, vp, i32, vp, vp]
         L.mh_match_query_candidates.argtypes = [vp, i32, vp]
@@ -1085,6 +1090,19 @@ class Context:
         sweep of a lane slot's rows instead (mh_match_incomplete)."""
         n = C.c_uint32(0)
         self._ck(self.L.mh_match_incomplete(self.h, C.byref(n), int(reset)), "mh_match_incomplete")
+        return int(n.value)
+
+    def match_set_accept(self, ratio: float):
+        """mh_match_set_accept: 0 = the default (resident frames hand MATCH their ratio, match() gets every exact triple);
+        r > 0 = match() hands it r as well, so that the raw triple of a query r rejects may read (-1, inf, inf);
+        -1 = nobody does (frames included)."""
+        self._ck(self.L.mh_match_set_accept(self.h, float(ratio)), "mh_match_set_accept")
+
+    def match_prerejected(self, reset=False) -> int:
+        """Queries since the last reset that pass C answered (-1, inf, inf) because their records proved that the
+        ratio test rejects them (mh_match_prerejected)."""
+        n = C.c_uint32(0)
+        self._ck(self.L.mh_match_prerejected(self.h, C.byref(n), int(reset)), "mh_match_prerejected")
         return int(n.value)
 
     def normalize(self, desc):

@@ -76,8 +76,9 @@ int ensure_match_scratch(mh_ctx* ctx, int Q) {
     MH_HIP(ctx, o.ovf_cnt.ensure(qp, s));
     MH_HIP(ctx, o.ovf.ensure(qp * SCREEN_OVF_CAP, s));
     MH_HIP(ctx, o.stats.ensure(qp * 3, s));
-    MH_HIP(ctx, o.inc.ensure(qp + 1, s));
-    MH_HIP(ctx, hipMemsetAsync(o.inc, 0, (qp + 1) * sizeof(unsigned int), s));
+    const size_t inc_words = qp + 1 + (size_t)screen_prerej_words();
+    MH_HIP(ctx, o.inc.ensure(inc_words, s));
+    MH_HIP(ctx, hipMemsetAsync(o.inc, 0, inc_words * sizeof(unsigned int), s));
     // (every slot empty, every count zero: the state both record layouts start from and pass C restores, screen.h)
     MH_HIP(ctx, hipMemsetAsync(o.recs, 0, slots * sizeof(uint2), s));
     MH_HIP(ctx, hipMemsetAsync(o.ovf_cnt, 0, qp * sizeof(int32_t), s));
@@ -98,7 +99,7 @@ int ensure_match_scratch(mh_ctx* ctx, int Q) {
 }
 
 int ctx_match(mh_ctx* ctx, const float* qn, const float* qnorm, int Q, int32_t* idx1, float* d1, float* d2,
-              const int32_t* q_count, int q_expected) {
+              const int32_t* q_count, int q_expected, float accept_ratio) {
   if (Q <= 0) return MH_OK;
   int rc = ensure_match_scratch(ctx, Q);
   if (rc) return rc;
@@ -116,6 +117,7 @@ int ctx_match(mh_ctx* ctx, const float* qn, const float* qnorm, int Q, int32_t* 
     ctx->sbuf.n_cus = ctx->n_cus;
     ctx->sbuf.ev_in = ctx->lane_in;
     ctx->sbuf.ev_out = ctx->lane_out;
+    ctx->sbuf.accept_ratio = accept_ratio > 0.f ? accept_ratio : 0.f;   // (the exact kernels below answer every query)
     launch_match_screen(qn, qnorm, Q, ctx->db_desc, ctx->db_norm, ctx->N, ctx->rmap, ctx->sdb, ctx->sbuf, idx1, d1,
                         d2, ctx->stream, q_count, q_expected);
     ++ctx->match_launches[2];
@@ -537,7 +539,10 @@ static int match_host(mh_ctx* ctx, const float* q_host, float* normalized_out, i
     launch_normalize(ctx->q_desc, ctx->q_norm, Q, ctx->stream);
   else
     launch_row_norms(ctx->q_desc, ctx->q_norm, Q, ctx->stream);
-  if ((rc = ctx_match(ctx, ctx->q_desc, ctx->q_norm, Q, ctx->nn_idx, ctx->nn_d1, ctx->nn_d2))) return rc;
+  // (mh_match_set_accept(r > 0): the raw triples are then exact only for the queries r accepts)
+  if ((rc = ctx_match(ctx, ctx->q_desc, ctx->q_norm, Q, ctx->nn_idx, ctx->nn_d1, ctx->nn_d2, nullptr, 0,
+                      ctx->match_accept > 0.f ? ctx->match_accept : 0.f)))
+    return rc;
   // the reference's acceptance test on squared distances (MATCH_ANN_CPU.hpp:165)
   int32_t* d_acc = (int32_t*)ctx->scratch.p;
   launch_accept(ctx->nn_idx, ctx->nn_d1, ctx->nn_d2, Q, ratio, d_acc, ctx->stream);
@@ -599,6 +604,10 @@ long long mh_trace_fetch(unsigned long long* out, long long cap) {
 #endif
 
 float mh_screen_margin(float qq, float dmax) { return screen_margin_host(qq, dmax); }
+
+int mh_screen_reject_proved(float qq, float dmax, float h1, float l2, float tau_q, float ratio) {
+  return screen_reject_proved_host(qq, dmax, h1, l2, tau_q, ratio) ? 1 : 0;
+}
 
 uint16_t mh_screen_record_value(float top, float thr) { return screen_record_value(top, thr); }
 
@@ -715,6 +724,28 @@ int mh_screen_sample_values(mh_ctx* ctx, const float* q_host, int Q, const int32
     rc = MH_ERR_HIP;
   }
   return rc;
+}
+
+int mh_match_set_accept(mh_ctx* ctx, float ratio) {
+  if (!ctx || !(ratio == ratio) || ratio > 1e30f) return MH_ERR_ARG;
+  ctx->match_accept = ratio;
+  return MH_OK;
+}
+
+int mh_match_prerejected(mh_ctx* ctx, uint32_t* count, int reset) {
+  if (!ctx || !count) return MH_ERR_ARG;
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *count = 0;
+  if (ctx->sbuf.inc) {
+    unsigned int* c = ctx->sbuf.inc + ctx->sbuf.q_pad + 1;
+    std::vector<unsigned int> h((size_t)screen_prerej_words());
+    MH_HIP(ctx, hipMemcpy(h.data(), c, h.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < h.size(); k += (size_t)screen_prerej_pitch()) *count += h[k];
+    if (reset) MH_HIP(ctx, hipMemset(c, 0, h.size() * sizeof(unsigned int)));
+  }
+  return MH_OK;
 }
 
 int mh_match_set_mode(mh_ctx* ctx, int mode) {

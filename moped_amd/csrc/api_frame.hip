@@ -172,7 +172,10 @@ int image_frame_rest(mh_ctx* ctx, int Q, int32_t* n_dev, const mh_cam* cam, cons
   ctx->feat_count_dev = n_dev;
   stamp(ctx, 0);
   launch_normalize(ctx->q_desc, ctx->q_norm, Q, ctx->stream, n_dev);
-  if (int rc = ctx_match(ctx, ctx->q_desc, ctx->q_norm, Q, ctx->nn_idx, ctx->nn_d1, ctx->nn_d2, n_dev, ctx->feat_expected)) return rc;
+  // (the frame's ratio goes along: group_kernel is the only reader of the top-2 arrays, frame_accept_ratio)
+  if (int rc = ctx_match(ctx, ctx->q_desc, ctx->q_norm, Q, ctx->nn_idx, ctx->nn_d1, ctx->nn_d2, n_dev, ctx->feat_expected,
+                         frame_accept_ratio(ctx, prm)))
+    return rc;
   stamp(ctx, 1);
   FrameCall c{ctx->q_uv, Q, cam, prm, seed};
   c.q_count = n_dev;   // (DEPTHFILTER counts the frame's keypoints, not the capacity)
@@ -191,7 +194,8 @@ int image_batch_rest(mh_ctx* ctx, int Q, int B, const int32_t* counts, const mh_
   stamp(ctx, 0);
   hipLaunchKernelGGL(image_batch_tail_kernel, dim3((B * Q * (DIM / 4) + 255) / 256), dim3(256), 0, s, ctx->q_desc, ctx->q_norm,
                      counts, Q, B);
-  if (int rc = ctx_match(ctx, ctx->q_desc, ctx->q_norm, B * Q, ctx->nn_idx, ctx->nn_d1, ctx->nn_d2)) return rc;
+  if (int rc = ctx_match(ctx, ctx->q_desc, ctx->q_norm, B * Q, ctx->nn_idx, ctx->nn_d1, ctx->nn_d2, nullptr, 0, frame_accept_ratio(ctx, prm)))
+    return rc;
   hipLaunchKernelGGL(image_batch_mask_kernel, dim3((B * Q + 255) / 256), dim3(256), 0, s, ctx->nn_idx, ctx->nn_d1, ctx->nn_d2,
                      counts, Q, B);
   stamp(ctx, 1);
@@ -243,7 +247,12 @@ int enqueue_features(mh_ctx* ctx, float* q_desc_dev, const float* q_uv_dev, int 
   stamp(ctx, 0);
   launch_normalize(q_desc_dev, ctx->q_norm, Q, ctx->stream);
   if (opt.write_back && ctx->wb_ev) hipEventRecord(ctx->wb_ev, ctx->stream);   // (mh_frame_run_host copies them back from here)
-  if (int rc_m = ctx_match(ctx, q_desc_dev, ctx->q_norm, Q, ctx->nn_idx, ctx->nn_d1, ctx->nn_d2)) return rc_m;
+  // (a whole frame hands MATCH its ratio; a stepped one -- mh_step_*, whose later steps may come with other parameters --
+  // keeps the exact triple of every query)
+  const bool whole = opt.stage_lo == 0 && opt.stage_hi == 5;
+  if (int rc_m = ctx_match(ctx, q_desc_dev, ctx->q_norm, Q, ctx->nn_idx, ctx->nn_d1, ctx->nn_d2, nullptr, 0,
+                           whole ? frame_accept_ratio(ctx, prm) : 0.f))
+    return rc_m;
   stamp(ctx, 1);
   ctx->step.done = -1;   // (whatever a stepped frame left on the device is overwritten from here on)
   FrameCall c{q_uv_dev, Q, cam, prm, seed};
@@ -977,7 +986,8 @@ int mh_frame_enqueue_batch(mh_ctx* ctx, float* q_desc_dev, const float* q_uv_dev
   ctx->feat_count_dev = nullptr;
   stamp(ctx, 0);
   launch_normalize(q_desc_dev, ctx->q_norm, B * Q, ctx->stream);
-  if ((rc = ctx_match(ctx, q_desc_dev, ctx->q_norm, B * Q, ctx->nn_idx, ctx->nn_d1, ctx->nn_d2))) return rc;
+  if ((rc = ctx_match(ctx, q_desc_dev, ctx->q_norm, B * Q, ctx->nn_idx, ctx->nn_d1, ctx->nn_d2, nullptr, 0, frame_accept_ratio(ctx, prm))))
+    return rc;
   stamp(ctx, 1);
   // merged: the B frames through group / CLUSTER / POSE / POSE2 in one launch each
   return rest_of_batch(ctx, FrameCall{q_uv_dev, Q, cam, prm, 0}, B, seeds, merge, true);

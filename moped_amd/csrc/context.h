@@ -143,6 +143,9 @@ struct mh_ctx {
     mh::DevBuf<unsigned int> stats, inc;
   } screen_own;
   int match_mode = -1;           // mh_match_set_mode
+  // mh_match_set_accept: 0 = resident frames hand MATCH their ratio (frame_accept_ratio), mh_match* never; > 0 = mh_match /
+  // mh_normalize_match hand it this ratio as well; < 0 = nobody does
+  float match_accept = 0.f;
   int pose_split = 1;            // mh_pose_set_split: POSE as two launches (hypotheses, one-wavefront refines) in the frame paths
   // ---- edits of the resident DB (db_edit.hip) ----
   std::shared_ptr<DbPool> pool;      // buffer sets of the store this context edits or adopted
@@ -378,8 +381,15 @@ int depth_map_from_raw_own(mh_ctx* ctx, const char* who, const void* raw_host, c
                            int width, int height);
 // MATCH of Q normalised queries against the context's DB on its stream: exact (idx1, d1, d2) per query, by the
 // two-stage screen when it pays and the DB allows it, else by the exact kernels (bit-identical results either way).
+// accept_ratio > 0: the caller applies `d1 / d2 < accept_ratio` (match_accepted) to every result and reads nothing else of
+// a query that fails it; the screen may then answer such a query with (-1, inf, inf) (ScreenBufs::accept_ratio).
 int ctx_match(mh_ctx* ctx, const float* qn, const float* qnorm, int Q, int32_t* idx1, float* d1, float* d2,
-              const int32_t* q_count = nullptr, int q_expected = 0);
+              const int32_t* q_count = nullptr, int q_expected = 0, float accept_ratio = 0.f);
+// what a resident single-GPU frame hands ctx_match: its ratio, unless the context adjusts the ratio by depth
+// (rules.ratio_table: group_kernel's ratio is then another for every match) or mh_match_set_accept(-1) switched it off
+inline float frame_accept_ratio(const mh_ctx* ctx, const mh_frame_params* prm) {
+  return ctx->match_accept >= 0.f && !ctx->rules.ratio_table && prm && prm->ratio > 0.f ? prm->ratio : 0.f;
+}
 // Delivery of a batch's heads into a caller's host block (api_frame.hip): delivery_begin -> where the delivering kernel
 // writes (the block itself when the device can address it, else the context's staging buffer); delivery_end -> the copy
 // out of the staging buffer if one is needed, and the event behind it all.

@@ -75,11 +75,46 @@ constexpr int SC_REC_BYTES = 80;                   // {slot, row0, thr, top, 16 
 __host__ __device__ constexpr int sc_lds_bytes(int nw) { return SC_LDS_TILES + nw * sc_recbuf(nw) * SC_REC_BYTES; }   // + the wavefronts' hit buffers
 static_assert(SC_TILE == 128 && DIM == 128, "tile image and chunk swizzle assume 128 x 128");
 
-// error model of the screen (see the header comment)
-__host__ __device__ inline float screen_margin(float qq, float dmax) {
+// error model of the screen (see the header comment): E(q), the bound of ONE screen value's distance from w = p - dd / 2
+__host__ __device__ inline float screen_value_err(float qq, float dmax) {
   const float nq = sqrtf(fmaxf(qq, 0.f));
-  const float E = 0.000978f * nq * dmax + 4e-7f * (nq + dmax) + 3e-5f * (nq * dmax + 0.5f * dmax * dmax);
+  return 0.000978f * nq * dmax + 4e-7f * (nq + dmax) + 3e-5f * (nq * dmax + 0.5f * dmax * dmax);
+}
+__host__ __device__ inline float screen_margin(float qq, float dmax) {
+  const float E = screen_value_err(qq, dmax);
   return 2.f * E + 2e-6f * (qq + dmax * dmax);
+}
+
+// Can the ratio test `fdiv(d1, d2) < ratio` (match_accepted, steps.h) still accept this query?  Pass C asks after its first
+// round trip, when it holds of the query's records h1 = the largest upper bound and l2 = the second largest lower bound
+// (over distinct records) of a block's largest screen value; true = no, whatever the exact arithmetic gives.
+//   * Every row whose screen value exceeds tau_q is in a record (the caller sees to that: no overflowed list, no
+//     incomplete query), so every row's screen value is <= top = max(h1, tau_q).
+//   * Two different records hold different rows: two distinct rows have screen values >= l2.
+//   * A row's canonical distance is a = max(0, fl(-2 p + fl(qq + dd))) and its screen value w~ lies within E of
+//     w = p - dd / 2 (the header), so |x - (qq - 2 w~)| <= delta = 2 E + 2e-6 (qq + Dmax^2) for x = the value under the
+//     max: 2 E from the screen, and the two roundings of x are worth <= 3 * 2^-24 (qq + Dmax^2) < 1.8e-7 (qq + Dmax^2) --
+//     per value the same allowances screen_margin makes for a pair (the margin is delta in units of w~, which are half
+//     those of a; tests/test_screen_bound_cpu.py).
+//   * Hence d1 = the smallest a >= qq - 2 top - delta =: L1, and d2 = the second smallest a (over rows: equal values count
+//     twice) <= max(0, qq - 2 l2 + delta) =: U2.
+//   * If U2 > 0 and L1 >= ratio U2, then d1 >= ratio d2 with d2 > 0 or d1 = d2 = 0: the quotient is NaN or >= ratio, and
+//     the correctly rounded division keeps it there (ratio is an f32, rounding is monotone).
+// L1 and U2 are formed in f32, three roundings each of values below `mag`; `slack` = 1e-6 mag pays for them (and for a
+// compiler that contracts the expressions differently on the host and on the device), the factor on the product for its
+// own two roundings.  false for ratio <= 0, a non-finite input, l2 = -inf (fewer than two records) and U2 <= 0.
+__host__ __device__ inline bool screen_reject_proved(float qq, float dmax, float h1, float l2, float tau_q, float ratio) {
+  const float big = 1e30f;
+  if (!(ratio > 0.f) || !(ratio < big) || !(fabsf(qq) < big) || !(fabsf(dmax) < big) || !(fabsf(tau_q) < big)) return false;
+  if (!(fabsf(l2) < big) || !(h1 < big)) return false;   // (h1 = -inf cannot be, with l2 finite; it would do no harm)
+  const float top = fmaxf(h1, tau_q);
+  const float delta = 2.f * screen_value_err(qq, dmax) + 2e-6f * (qq + dmax * dmax);
+  const float mag = fabsf(qq) + 2.f * fabsf(top) + 2.f * fabsf(l2) + delta;
+  const float slack = 1e-6f * mag;
+  const float lo_d1 = qq - 2.f * top - delta - slack;
+  const float hi_d2 = qq - 2.f * l2 + delta + slack;
+  if (!(hi_d2 > 0.f)) return false;
+  return lo_d1 >= ratio * hi_d2 * 1.000001f;
 }
 
 // ---- f16 images ------------------------------------------------------------------------------
@@ -1276,6 +1311,10 @@ __device__ __forceinline__ void merge(Best& a, float ob1, float ob2, int oi1) { 
 // dot = fmaf chain over k = 0..127 from 0, dist = max(0, fmaf(-2, dot, qq + dd)).  The query's coordinates are
 // wave-uniform (LDS broadcast reads), the row comes straight from HBM / the Infinity Cache, 16 bytes per load.
 constexpr int RS_WAVES = 4;          // wavefronts per workgroup, one query each
+// ... of the accepting kernel (rescore_query's ACCEPT): four fifths of its wavefronts leave after one round trip, and a
+// workgroup holds its LDS until its slowest query is done -- one query per workgroup beat four in every round, two did not
+// beat four by the rule (profiles/accept_reject_ab.txt)
+constexpr int RS_WAVES_ACCEPT = 1;
 #ifdef MH_EXPERIMENTS
 constexpr int RS_WAVES_FAT = 16;     // ... of a chip-filling launch's fat workgroups, two of which hold a compute unit
 constexpr int RS_FAT_K = 2;          // ... and that many of them per compute unit are the whole grid (their wavefronts walk the queries)
@@ -1361,6 +1400,9 @@ struct RsScalars {   // what a query's wavefront reads besides its slots before 
   unsigned incw;
   float2 qv;
 };
+// the counters of the pre-rejected queries: query q adds to counter q % RS_PREREJ_WORDS, each on a cache line of its own
+// (two thirds of a launch's wavefronts add one: a single word would queue them all in one L2 channel)
+constexpr int RS_PREREJ_WORDS = 16, RS_PREREJ_PITCH = 64;
 constexpr size_t rs_lds_bytes(int waves) { return (size_t)waves * (DIM * 4 + RS_MAXC * 4 + SC_SA_SLOTS * 4 + 8); }
 
 struct RsArgs {
@@ -1392,6 +1434,9 @@ struct RsArgs {
   unsigned int* inc_count;
   const _Float16* dbh;
   const float* dneg;
+  // (behind everything else: the kernels that do not ask read the same words at the same offsets as before)
+  float accept_ratio;      // > 0: the caller keeps only queries that pass `d1 / d2 < accept_ratio` (screen_reject_proved)
+  unsigned int* prerej;    // RS_PREREJ_WORDS counters, RS_PREREJ_PITCH words apart: queries that left by that proof
 };
 // The kernel's arguments as an iteration of the loop reads them: from the kernel argument segment (the one struct is all
 // of it), through a pointer the compiler cannot see through.  Read once in front of the loop they would all live in scalar
@@ -1454,14 +1499,19 @@ __device__ __forceinline__ RsScalars rs_load_scalars(const uint8_t* qbad, const 
 // looks at one record at a time, candidates and surviving sampled records get their LDS places from counters (the
 // sampled pairs are evaluated row by row whatever their pairing), and the exact top-2 breaks ties by row number.
 static_assert(RS_ITERS_C <= RS_ITERS, "a counted list's slots fit the registers the scan has");
-template <int COMPACT>
+// ACCEPT: the caller applies the ratio test `accept_ratio` to the result and reads nothing of a query that fails it: a query
+// the records' bounds already prove to fail (screen_reject_proved) is answered like an absent one, (-1, inf, inf), after the
+// first round trip -- before the sampled records' evaluation, the candidate rows' gather and the chains.  Without ACCEPT
+// the code is what it was.
+template <int COMPACT, int ACCEPT = 0>
 __device__ __forceinline__ void rescore_query(
     int q, int lane, float* q_sw, int* cand_sw, int* samp_sw, int* ncand_sw, int* nsamp_sw, uint2 (&recv)[RS_ITERS], const RsScalars sc, int Qe,
     const float* __restrict__ db, const float* __restrict__ dnorm, int N,
     RowMap rmap, uint2* __restrict__ recs, int n_slots, int32_t* __restrict__ ovf_cnt, uint2* __restrict__ ovf,
     int ovf_cap, float dmax, float spread, int32_t* __restrict__ idx1, float* __restrict__ d1, float* __restrict__ d2,
     unsigned int* __restrict__ stats, int32_t zero_idx, float zero_d1, float zero_d2, SampleGeom g,
-    unsigned int* __restrict__ inc_count, const _Float16* __restrict__ dbh, const float* __restrict__ dneg) {
+    unsigned int* __restrict__ inc_count, const _Float16* __restrict__ dbh, const float* __restrict__ dneg,
+    float accept_ratio = 0.f, unsigned int* __restrict__ prerej = nullptr) {
   uint2* mine = recs + (size_t)q * SC_SLOT_PITCH;
   // (COMPACT: the records the list holds; a count above the capacity = records were dropped = brute force)
   const int n_own = COMPACT ? min(sc.n_ovf, SC_SLOT_PITCH) : n_slots + g.sa_slots;
@@ -1517,6 +1567,7 @@ __device__ __forceinline__ void rescore_query(
     // more than screen_margin below that bound cannot hold one.  Pass A's threshold comes from an eighth of the rows
     // and lets ~25 rows per query through; ~3 survive this one and get their 512-byte row fetched.
     float l1 = -__builtin_inff(), l2 = -__builtin_inff();   // the lane's two largest lower bounds
+    float h1 = -__builtin_inff();                           // ACCEPT: and its largest upper bound
     const float pert = screen_pack_pert(nq, dmax, g.pack_bits);
     auto bounds = [tau_q, spread, N, dmax, pert](uint2 rec, float& lo, float& hi) {
       // the record's value: (largest dot of the block + the block's largest -dd/2) - tau, rounded to f16.  The block's
@@ -1554,6 +1605,7 @@ __device__ __forceinline__ void rescore_query(
         bounds(rec, lo, hi);
         l2 = fmaxf(l2, fminf(l1, lo));
         l1 = fmaxf(l1, lo);
+        if (ACCEPT) h1 = fmaxf(h1, hi);
       }
     };
     if (COMPACT) {
@@ -1571,6 +1623,20 @@ __device__ __forceinline__ void rescore_query(
       const float o1 = __shfl_xor(l1, d), o2 = __shfl_xor(l2, d);
       l2 = fmaxf(fmaxf(l2, o2), fminf(l1, o1));
       l1 = fmaxf(l1, o1);
+      if (ACCEPT) h1 = fmaxf(h1, __shfl_xor(h1, d));
+    }
+    // Every record the query has was read above (no list overflowed: !brute; no lane slot of pass A left its blocks out:
+    // incw == 0), so screen_reject_proved's premises hold.  The slots read are empty again (scan), the count goes the way it
+    // goes below; the LDS counters are reset by whichever query this wavefront takes next.
+    if (ACCEPT && incw == 0u && accept_ratio > 0.f && screen_reject_proved(nq, dmax, h1, l2, tau_q, accept_ratio)) {
+      if (lane == 0) {
+        if (n_ovf) ovf_cnt[q] = 0;
+        idx1[q] = -1;
+        d1[q] = __builtin_inff();
+        d2[q] = __builtin_inff();
+        if (prerej) atomicAdd(prerej + (q % RS_PREREJ_WORDS) * RS_PREREJ_PITCH, 1u);
+      }
+      return;
     }
     const float keep_from = l2 - screen_margin(nq, dmax);   // -inf with fewer than two records: everything stays
     auto keep = [&](int it) {
@@ -1728,7 +1794,7 @@ __device__ __forceinline__ void rescore_query(
 // The product (<4, 0>, a wavefront per query) runs the loop once and keeps its form all the same: it is the form that was
 // measured (profiles/passc_persistent_ab.txt, the row WAVES=4), its arguments fetched next to their uses inside the
 // iteration and no scratch memory; the same per-query code without the loop around it was not measured.
-template <int WAVES, int PF, int COMPACT>
+template <int WAVES, int PF, int COMPACT, int ACCEPT = 0>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVES == 12 ? 6 : 8, WAVES == 12 ? 6 : 8))) void rescore_kernel(const RsArgs args) {
   MH_TRACE_SCOPE(mh::TK_PASS_C);
   // dynamic LDS (sixteen wavefronts' regions are more than the 64 KB a kernel may declare): [WAVES][DIM] query rows,
@@ -1778,6 +1844,11 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVE
     rmap.nb = A->rmap.nb;
     rmap.base = A->rmap.base;
     const SampleGeom g = {A->g.sa_slots, A->g.pack_bits, A->g.tile_first, A->g.tile_stride, A->g.tiles_base, A->g.tiles_rem, A->g.n_sel};
+    if (ACCEPT)
+      rescore_query<COMPACT, 1>(q, lane, q_sw, cand_sw, samp_sw, ncand_sw, nsamp_sw, recv, sc, Qe, A->db, A->dnorm, A->N, rmap, A->recs,
+                    A->n_slots, A->ovf_cnt, A->ovf, A->ovf_cap, A->dmax, A->spread, A->idx1, A->d1, A->d2, A->stats, A->zero_idx,
+                    A->zero_d1, A->zero_d2, g, A->inc_count, A->dbh, A->dneg, A->accept_ratio, A->prerej);
+    else
     rescore_query<COMPACT>(q, lane, q_sw, cand_sw, samp_sw, ncand_sw, nsamp_sw, recv, sc, Qe, A->db, A->dnorm, A->N, rmap, A->recs,
                   A->n_slots, A->ovf_cnt, A->ovf, A->ovf_cap, A->dmax, A->spread, A->idx1, A->d1, A->d2, A->stats, A->zero_idx,
                   A->zero_d1, A->zero_d2, g, A->inc_count, A->dbh, A->dneg);
@@ -1882,6 +1953,11 @@ extern "C" long long mh_debug_screen_direct_appends(int reset) {
 
 // ---- host side -----------------------------------------------------------------------------------
 float screen_margin_host(float qq, float dmax) { return screen_margin(qq, dmax); }
+bool screen_reject_proved_host(float qq, float dmax, float h1, float l2, float tau_q, float ratio) {
+  return screen_reject_proved(qq, dmax, h1, l2, tau_q, ratio);
+}
+int screen_prerej_words() { return RS_PREREJ_WORDS * RS_PREREJ_PITCH; }
+int screen_prerej_pitch() { return RS_PREREJ_PITCH; }
 
 size_t screen_db_half_elems(int N) { return ((size_t)N + SC_TILE - 1) / SC_TILE * SC_TILE * DIM; }
 size_t screen_dneg_elems(int N) { return ((size_t)N + SC_TILE - 1) / SC_TILE * SC_DD; }
@@ -2137,17 +2213,24 @@ void launch_passes16(ScreenArgs a, int Q, int qe, int n_tiles, int sample, int b
   *geom_out = g;
 }
 
-template <int WAVES, int PF, int COMPACT>
+template <int WAVES, int PF, int COMPACT, int ACCEPT = 0>
 void launch_pass_c_layout(int grid, hipStream_t s, const RsArgs& args) {
   static DynLds attr;
-  attr.ensure(rescore_kernel<WAVES, PF, COMPACT>, rs_lds_bytes(WAVES));
-  hipLaunchKernelGGL((rescore_kernel<WAVES, PF, COMPACT>), dim3(grid), dim3(64 * WAVES), rs_lds_bytes(WAVES), s, args);
+  attr.ensure(rescore_kernel<WAVES, PF, COMPACT, ACCEPT>, rs_lds_bytes(WAVES));
+  hipLaunchKernelGGL((rescore_kernel<WAVES, PF, COMPACT, ACCEPT>), dim3(grid), dim3(64 * WAVES), rs_lds_bytes(WAVES), s, args);
 }
 // compact: the launch's records are counted lists (the 16x16x32 launches), else the lane-private slots + overflow list
 template <int WAVES, int PF>
 void launch_pass_c(int grid, hipStream_t s, const RsArgs& args, bool compact) {
   if (compact) launch_pass_c_layout<WAVES, PF, 1>(grid, s, args);
   else launch_pass_c_layout<WAVES, PF, 0>(grid, s, args);
+}
+// the same for a caller that named its ratio test (RsArgs::accept_ratio > 0): a wavefront per query, nothing prefetched
+template <int WAVES>
+void launch_pass_c_accept(int Q, hipStream_t s, const RsArgs& args, bool compact) {
+  const int grid = (Q + WAVES - 1) / WAVES;
+  if (compact) launch_pass_c_layout<WAVES, 0, 1, 1>(grid, s, args);
+  else launch_pass_c_layout<WAVES, 0, 0, 1>(grid, s, args);
 }
 
 // which kernels a MATCH launch runs on (launch_match_screen): queries per workgroup / 256, and whether the 16x16x32 passes
@@ -2264,6 +2347,20 @@ void launch_match_screen(const float* qn, const float* qnorm, int Q, const float
   ca.dmax = sdb.dmax; ca.tau = sb.tau; ca.spread = sdb.spread; ca.idx1 = idx1; ca.d1 = d1; ca.d2 = d2; ca.stats = sb.stats;
   ca.zero_idx = sdb.zero_idx; ca.zero_d1 = sdb.zero_d1; ca.zero_d2 = sdb.zero_d2; ca.g = geom;
   ca.inc = geom.sa_slots > 0 ? sb.inc : nullptr; ca.inc_count = sb.inc ? sb.inc + sb.q_pad : nullptr; ca.dbh = sdb.dbh; ca.dneg = sdb.dneg;
+  ca.accept_ratio = sb.accept_ratio > 0.f ? sb.accept_ratio : 0.f;
+  ca.prerej = sb.inc ? sb.inc + sb.q_pad + 1 : nullptr;   // (behind the incomplete words and their counter)
+  if (ca.accept_ratio > 0.f) {
+#ifdef MH_EXPERIMENTS
+    // queries per workgroup of the accepting kernel (scripts/ab_env.sh; profiles/accept_reject_ab.txt): MH_PASSC_WAVES = 4 / 2
+    static const int pa_waves = exp_int("MH_PASSC_WAVES", RS_WAVES_ACCEPT);
+    if (pa_waves == 4) launch_pass_c_accept<4>(Q, s, ca, shape.passes16);
+    else if (pa_waves == 2) launch_pass_c_accept<2>(Q, s, ca, shape.passes16);
+    else
+#endif
+    launch_pass_c_accept<RS_WAVES_ACCEPT>(Q, s, ca, shape.passes16);
+    if (sb.ev) hipEventRecord(sb.ev[5], s);
+    return;
+  }
 #ifdef MH_EXPERIMENTS
   // the shapes that were measured against this one (rescore_kernel's comment; scripts/ab_env.sh): MH_PASSC_WAVES = 16 / 12
   // for the launches of more than two fat workgroups per compute unit (MH_PASSC_FAT_ALL = 1: for every launch), MH_PASSC_K

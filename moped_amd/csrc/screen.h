@@ -43,7 +43,12 @@ struct ScreenBufs {
   unsigned int* stats = nullptr;   // optional [q_pad][3] per-query tallies: candidate rows, brute-force searches, searches
   // [q_pad] the queries' incomplete words of the one-sweep launches (which lane slots of pass A pass C has to sweep; 0 = none),
   // then one counter: queries that took that sweep since the last mh_match_incomplete(reset)
+  // then screen_prerej_words() words: the counters of the queries pass C answered without a search (accept_ratio)
   unsigned int* inc = nullptr;
+  // > 0: the caller applies the ratio test `d1 / d2 < accept_ratio` to every result and reads nothing else of a query that
+  // fails it -- pass C then answers a query its records prove to fail with (-1, inf, inf) (screen_reject_proved); 0 = the
+  // exact triple for every query
+  float accept_ratio = 0.f;
   int n_cus = 0;                   // compute units of the device, 0 = not known (experiment builds: the grid of pass C's walking shapes)
 };
 
@@ -116,6 +121,10 @@ constexpr int SCREEN_OVF_CAP = 64;   // records in a query's overflow list befor
 size_t screen_rec_slots();           // record slots per query
 
 float screen_margin_host(float qq, float dmax);   // tau = T - margin (the error model, for tests)
+// pass C's proof that a query fails the ratio test, from its records' bounds (match_screen.hip, screen_reject_proved)
+bool screen_reject_proved_host(float qq, float dmax, float h1, float l2, float tau_q, float ratio);
+int screen_prerej_words();    // words of ScreenBufs::inc behind the incomplete words and their counter
+int screen_prerej_pitch();    // ... of which every screen_prerej_pitch()-th is a counter
 // The screen values themselves, as the matrix pipe computes them (pass A's arithmetic: f16 operands, accumulator seeded
 // with -dd/2, the block's MFMAs in ascending k -- eight v_mfma_f32_32x32x16_f16 or four k-steps of v_mfma_f32_16x16x32_f16):
 // out[q][r] for q < Q, r < n_rows (both multiples of 32; qh =
