@@ -236,6 +236,11 @@ void mh_screen_record_bounds(uint16_t value_bits, uint32_t row0, float tau, floa
  *                           launched: out = {1 if one sweep, first sampled tile, sampling stride, sampled tiles, pass A
  *                           splits, identity bits, pass B splits, pass B tiles}; all zero when the launch does not run
  *                           on the 16x16x32 passes
+ *   mh_screen_plan          the whole plan of that call, for either kernel family: out = {family (32 = the 32x32x16
+ *                           passes with lane-private record lists, 16 = the 16x16x32 passes with counted lists), 32-query
+ *                           blocks per wavefront; pass A: first tile, stride, tiles, splits, identity bits, 1 if one
+ *                           sweep; pass B: tiles, splits, slots per sub-list (0 = counted lists), first skipped tile, skip
+ *                           stride (0 = none skipped); record slots per query pass C scans (0 = by the list's count)}
  *   mh_screen_park_places   hits a wavefront of pass B of the 16x16x32 launches parks in LDS during its sweep before
  *                           further hits append to their queries' lists from the hit path (for tests that fill it)
  *   mh_match_incomplete     queries since the last reset for which a lane slot of pass A held more blocks above the
@@ -249,6 +254,8 @@ float mh_screen_pack_value(float v, uint32_t id, int bits);
 float mh_screen_pack_pert(float qq, float dmax, int bits);
 void mh_screen_sample_bounds(uint16_t value_bits, float tau, float pert, float dmax, float* lo, float* hi);
 void mh_screen_launch_plan(int Q, int q_expected, int N, int32_t out[8]);
+#define MH_SCREEN_PLAN_WORDS 14
+void mh_screen_plan(int Q, int q_expected, int N, int32_t out[MH_SCREEN_PLAN_WORDS]);
 int mh_screen_park_places(void);
 int mh_match_incomplete(mh_ctx* ctx, uint32_t* count, int reset);
 /* MATCH for a caller that applies the ratio test.  The frames' only reader of a query's (idx1, d1, d2) is the test

@@ -228,7 +228,7 @@ EXPORTS = [
     "mh_undistort_map", "mh_undistort", "mh_undistort_dev", "mh_frame_set_undistort",
     "mh_sift_extract_batch_dev", "mh_sift_debug_plan", "mh_sift_debug_level", "mh_sift_debug_candidates",
     "mh_sift_debug_keys", "mh_sift_debug_blur",
-    "mh_screen_pack_value", "mh_screen_pack_pert", "mh_screen_sample_bounds", "mh_screen_launch_plan", "mh_match_incomplete",
+    "mh_screen_pack_value", "mh_screen_pack_pert", "mh_screen_sample_bounds", "mh_screen_launch_plan", "mh_screen_plan", "mh_match_incomplete",
     "mh_screen_sample_values", "mh_match_query_candidates", "mh_screen_park_places",
     "mh_frame_enqueue_images", "mh_frame_enqueue_images_batch", "mh_frame_set_undistort_images", "mh_frame_image_counts",
     "mh_frame_features_image_dev",
@@ -615,6 +615,20 @@ def screen_launch_plan(Q, N, q_expected=0) -> dict:
     load().mh_screen_launch_plan(int(Q), int(q_expected), int(N), _ptr(o))
     keys = ("onesweep", "tile_first", "tile_stride", "sampled_tiles", "splits_a", "pack_bits", "splits_b", "tiles_b")
     return {k: int(v) for k, v in zip(keys, o)}
+
+
+SCREEN_PLAN_KEYS = ("family", "nqb", "a_tile_first", "a_stride", "a_tiles", "a_splits", "pack_bits", "onesweep",
+                    "b_tiles", "b_splits", "sub_cap", "skip_first", "skip_stride", "n_slots")
+
+
+def screen_plan(Q, N, q_expected=0) -> dict:
+    """mh_screen_plan (host arithmetic): the whole launch plan of a two-stage MATCH of Q queries against N rows, for either
+    kernel family (family = 32: the 32x32x16 passes, 16: the 16x16x32 passes)."""
+    o = np.zeros(len(SCREEN_PLAN_KEYS), np.int32)
+    f = load().mh_screen_plan   # (bound here, like mh_screen_park_places)
+    f.argtypes, f.restype = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p], None
+    f(int(Q), int(q_expected), int(N), _ptr(o))
+    return {k: int(v) for k, v in zip(SCREEN_PLAN_KEYS, o)}
 
 
 def screen_park_places() -> int:

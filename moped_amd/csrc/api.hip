@@ -603,10 +603,10 @@ long long mh_trace_fetch(unsigned long long* out, long long cap) {
 }
 #endif
 
-float mh_screen_margin(float qq, float dmax) { return screen_margin_host(qq, dmax); }
+float mh_screen_margin(float qq, float dmax) { return screen_margin(qq, dmax); }
 
 int mh_screen_reject_proved(float qq, float dmax, float h1, float l2, float tau_q, float ratio) {
-  return screen_reject_proved_host(qq, dmax, h1, l2, tau_q, ratio) ? 1 : 0;
+  return screen_reject_proved(qq, dmax, h1, l2, tau_q, ratio) ? 1 : 0;
 }
 
 uint16_t mh_screen_record_value(float top, float thr) { return screen_record_value(top, thr); }
@@ -630,10 +630,17 @@ void mh_screen_sample_bounds(uint16_t value_bits, float tau, float pert, float d
   if (hi) *hi = h;
 }
 
+void mh_screen_plan(int Q, int q_expected, int N, int32_t out[MH_SCREEN_PLAN_WORDS]) {
+  const ScreenPlan p = screen_plan(Q, q_expected, N);
+  static_assert(sizeof p == MH_SCREEN_PLAN_WORDS * sizeof(int32_t), "ScreenPlan is the words mh_screen_plan documents, nothing else");
+  memcpy(out, &p, sizeof p);
+}
+
+// the 16x16x32 launches' part of the plan (zeros for the others)
 void mh_screen_launch_plan(int Q, int q_expected, int N, int32_t out[8]) {
-  int v[8];
-  screen_launch_plan(Q, q_expected, N, v);
-  for (int k = 0; k < 8; ++k) out[k] = v[k];
+  const ScreenPlan p = screen_plan(Q, q_expected, N);
+  const int32_t v[8] = {p.onesweep, p.a_tile_first, p.a_stride, p.a_n_sel, p.a_splits, p.pack_bits, p.b_splits, p.b_n_sel};
+  for (int k = 0; k < 8; ++k) out[k] = p.family == 16 ? v[k] : 0;
 }
 
 int mh_screen_park_places(void) { return screen_park_places(); }

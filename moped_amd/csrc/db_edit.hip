@@ -22,7 +22,7 @@ using namespace mh;
 namespace {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-constexpr int DB_DD = 192;   // floats per 128-row tile of the -dd/2 array (SC_DD of match_screen.hip; checked in alloc_set)
+constexpr int DB_DD = 192;   // floats per 128-row tile of the -dd/2 array (SC_DD of screen_int.h; checked in alloc_set)
 
 struct SpliceArgs {
   const float* old_desc;   // the live set
@@ -46,7 +46,7 @@ struct SpliceArgs {
   size_t n_chunks;         // 8-float chunks of the result's padded extent
 };
 
-// One pass over the destination, shaped like db_to_half_kernel (match_screen.hip): one 8-float chunk per thread step,
+// One pass over the destination, shaped like db_to_half_kernel (screen_db.hip): one 8-float chunk per thread step,
 // grid-strided; the f32 chunk is read once and written twice (f32, f16), chunk 0 of a row carries the row's scalars.
 __global__ __launch_bounds__(256) void db_splice_kernel(const SpliceArgs a) {
   __shared__ unsigned int red[3];

@@ -1,4 +1,4 @@
-// Two-stage MATCH (match_screen.hip): what the rest of the library needs to know about it.
+// Two-stage MATCH (match_screen.hip and the screen_*.hip files): what the rest of the library needs to know about it.
 #pragma once
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
@@ -27,7 +27,7 @@ struct ScreenBufs {
   float* tau = nullptr;            // [q_pad] the queries' thresholds for pass B
   // [q_pad][screen_rec_slots()] candidate records, all empty between frames.  Two layouts share the memory and that
   // invariant: lane-private sub-lists (+ the overflow list) in the 32x32x16 launches, ONE counted list per query from
-  // slot 0 in the 16x16x32 launches (match_screen.hip, SC_SLOT_PITCH)
+  // slot 0 in the 16x16x32 launches (screen_int.h, SC_SLOT_PITCH)
   uint2* recs = nullptr;
   // [q_pad] zero between frames.  32x32x16 launches: records in the query's overflow list; 16x16x32 launches: records
   // in the query's list (more than screen_rec_slots() = some were dropped, brute force in pass C)
@@ -51,6 +51,49 @@ struct ScreenBufs {
   float accept_ratio = 0.f;
   int n_cus = 0;                   // compute units of the device, 0 = not known (experiment builds: the grid of pass C's walking shapes)
 };
+
+// ---- the error model (the header of match_screen.hip) -----------------------------------------------------------------
+// E(q), the bound of ONE screen value's distance from w = p - dd / 2; tau = T - screen_margin
+__host__ __device__ inline float screen_value_err(float qq, float dmax) {
+  const float nq = sqrtf(fmaxf(qq, 0.f));
+  return 0.000978f * nq * dmax + 4e-7f * (nq + dmax) + 3e-5f * (nq * dmax + 0.5f * dmax * dmax);
+}
+__host__ __device__ inline float screen_margin(float qq, float dmax) {
+  const float E = screen_value_err(qq, dmax);
+  return 2.f * E + 2e-6f * (qq + dmax * dmax);
+}
+
+// Can the ratio test `fdiv(d1, d2) < ratio` (match_accepted, steps.h) still accept this query?  Pass C asks after its first
+// round trip, when it holds of the query's records h1 = the largest upper bound and l2 = the second largest lower bound
+// (over distinct records) of a block's largest screen value; true = no, whatever the exact arithmetic gives.
+//   * Every row whose screen value exceeds tau_q is in a record (the caller sees to that: no overflowed list, no
+//     incomplete query), so every row's screen value is <= top = max(h1, tau_q).
+//   * Two different records hold different rows: two distinct rows have screen values >= l2.
+//   * A row's canonical distance is a = max(0, fl(-2 p + fl(qq + dd))) and its screen value w~ lies within E of
+//     w = p - dd / 2 (the header), so |x - (qq - 2 w~)| <= delta = 2 E + 2e-6 (qq + Dmax^2) for x = the value under the
+//     max: 2 E from the screen, and the two roundings of x are worth <= 3 * 2^-24 (qq + Dmax^2) < 1.8e-7 (qq + Dmax^2) --
+//     per value the same allowances screen_margin makes for a pair (the margin is delta in units of w~, which are half
+//     those of a; tests/test_screen_bound_cpu.py).
+//   * Hence d1 = the smallest a >= qq - 2 top - delta =: L1, and d2 = the second smallest a (over rows: equal values count
+//     twice) <= max(0, qq - 2 l2 + delta) =: U2.
+//   * If U2 > 0 and L1 >= ratio U2, then d1 >= ratio d2 with d2 > 0 or d1 = d2 = 0: the quotient is NaN or >= ratio, and
+//     the correctly rounded division keeps it there (ratio is an f32, rounding is monotone).
+// L1 and U2 are formed in f32, three roundings each of values below `mag`; `slack` = 1e-6 mag pays for them (and for a
+// compiler that contracts the expressions differently on the host and on the device), the factor on the product for its
+// own two roundings.  false for ratio <= 0, a non-finite input, l2 = -inf (fewer than two records) and U2 <= 0.
+__host__ __device__ inline bool screen_reject_proved(float qq, float dmax, float h1, float l2, float tau_q, float ratio) {
+  const float big = 1e30f;
+  if (!(ratio > 0.f) || !(ratio < big) || !(fabsf(qq) < big) || !(fabsf(dmax) < big) || !(fabsf(tau_q) < big)) return false;
+  if (!(fabsf(l2) < big) || !(h1 < big)) return false;   // (h1 = -inf cannot be, with l2 finite; it would do no harm)
+  const float top = fmaxf(h1, tau_q);
+  const float delta = 2.f * screen_value_err(qq, dmax) + 2e-6f * (qq + dmax * dmax);
+  const float mag = fabsf(qq) + 2.f * fabsf(top) + 2.f * fabsf(l2) + delta;
+  const float slack = 1e-6f * mag;
+  const float lo_d1 = qq - 2.f * top - delta - slack;
+  const float hi_d2 = qq - 2.f * l2 + delta + slack;
+  if (!(hi_d2 > 0.f)) return false;
+  return lo_d1 >= ratio * hi_d2 * 1.000001f;
+}
 
 // ---- what a candidate record says about its block (pass B writes it, pass C prunes by it) -------------------------
 // Pass B works on the 16 dot products a lane holds of a 32-row block.  `top` = the largest of them, `thr` = tau(q) - the
@@ -83,7 +126,7 @@ __host__ __device__ inline void screen_record_bounds(unsigned short value_bits, 
 
 // ---- the one-sweep launches: pass A's block maxima carry their block's number ---------------------------------------
 // screen16_kernel's pass A replaces the low `bits` mantissa bits of a block's largest screen value by the block's number
-// inside its lane slot (match_screen.hip, "pass A of the one-sweep launches").
+// inside its lane slot (screen_ab16.hip, "pass A of the one-sweep launches").
 __host__ __device__ inline float screen_pack_value(float v, unsigned id, int bits) {
   const unsigned keep = ~((1u << bits) - 1u);
   unsigned u;
@@ -120,10 +163,7 @@ __host__ __device__ inline void screen_sample_bounds(unsigned short value_bits, 
 constexpr int SCREEN_OVF_CAP = 64;   // records in a query's overflow list before the query falls back to brute force
 size_t screen_rec_slots();           // record slots per query
 
-float screen_margin_host(float qq, float dmax);   // tau = T - margin (the error model, for tests)
-// pass C's proof that a query fails the ratio test, from its records' bounds (match_screen.hip, screen_reject_proved)
-bool screen_reject_proved_host(float qq, float dmax, float h1, float l2, float tau_q, float ratio);
-int screen_prerej_words();    // words of ScreenBufs::inc behind the incomplete words and their counter
+int screen_prerej_words();   // words of ScreenBufs::inc behind the incomplete words and their counter
 int screen_prerej_pitch();    // ... of which every screen_prerej_pitch()-th is a counter
 // The screen values themselves, as the matrix pipe computes them (pass A's arithmetic: f16 operands, accumulator seeded
 // with -dd/2, the block's MFMAs in ascending k -- eight v_mfma_f32_32x32x16_f16 or four k-steps of v_mfma_f32_16x16x32_f16):
@@ -135,7 +175,9 @@ void launch_screen_values(const _Float16* qh, int Q, const ScreenDb& sdb, int n_
 // the 8 + 8 rows of the blocks row0[2 q] and row0[2 q + 1] (a record's row0: tile x 128 + 32 row block + 4 quarter; bit b =
 // row row0 + (b & 3) + 16 (b >> 2)), out[q][8 block + bit], by the code rescore_kernel runs (mh_screen_sample_values).
 void launch_screen_sample_values(const float* qn, int Q, const ScreenDb& sdb, const int32_t* row0, float* out, hipStream_t s);
-void launch_screen_prepare(const float* qn, const float* qnorm, int Q, int q_pad, _Float16* qh, uint8_t* qbad, hipStream_t s);
+// the queries' f16 image and flags (q_count: optional device word, the frame's own number of queries)
+void launch_screen_prepare(const float* qn, const float* qnorm, int Q, int q_pad, _Float16* qh, uint8_t* qbad, hipStream_t s,
+                           const int32_t* q_count = nullptr);
 size_t screen_db_half_elems(int N);
 size_t screen_dneg_elems(int N);   // floats of the -dd/2 array: 192 per 128-row tile (rows, row blocks' extrema)
 // f16 image + statistics {bits of max dd, bits of max |x|, non-finite flag, bits of the largest in-block spread,
@@ -149,10 +191,22 @@ void launch_db_aggregates(const float* dnorm, int N, float* dneg, unsigned int* 
 int screen_q_pad(int Q);
 int screen_max_splits_a();
 size_t screen_part_bytes(int q_pad);   // pass A's output buffer
-// The launch plan of a MATCH call, as launch_match_screen makes it (host arithmetic, for tests that have to know which
-// tiles pass A samples): out = {one-sweep launch (0 / 1), tile_first, tile_stride, sampled tiles, pass A splits, pack bits,
-// pass B splits, pass B tiles}
-void screen_launch_plan(int Q, int q_expected, int N, int out[8]);
+// The launch plan of a MATCH call of Q queries (q_expected of them expected, 0 = Q) against N rows: host arithmetic,
+// computed once by launch_match_screen and launched as stated; mh_screen_plan hands it out word by word, in this order.
+struct ScreenPlan {
+  int32_t family;        // 32 = screen_kernel (32x32x16, lane-private record lists), 16 = screen16_kernel (16x16x32, counted lists)
+  int32_t nqb;           // 32-query blocks per wavefront: a workgroup takes 256 nqb queries
+  // pass A sweeps the tiles a_tile_first + j * a_stride, j < a_n_sel, in a_splits splits
+  int32_t a_tile_first, a_stride, a_n_sel, a_splits;
+  int32_t pack_bits;     // (16) bits of a block maximum that carry the block's number; 0 = none
+  int32_t onesweep;      // (16) pass A hands its tiles' records over, pass B skips them
+  // pass B sweeps b_n_sel tiles in b_splits splits: all of them, or (one sweep) those that are not skip_first + i * skip_stride
+  int32_t b_n_sel, b_splits;
+  int32_t sub_cap;       // (32) slots of a lane's sub-list; 0 = counted lists
+  int32_t skip_first, skip_stride;   // 0 = no tile is skipped
+  int32_t n_slots;       // pass B's record slots per query that pass C scans: 2 b_splits sub_cap; 0 = by the list's count
+};
+ScreenPlan screen_plan(int Q, int q_expected, int N);
 int screen_park_places();   // hits a wavefront of screen16_kernel's pass B parks before it appends from the hit path (SC_RECBUF16)
 // mode: -1 = decide by size, 0 = never, 1 = whenever the DB has an f16 image (mh_match_set_mode)
 bool screen_wanted(int q_expected, int N, int mode = -1);

@@ -2,6 +2,8 @@
 # A/B of experiment switches on one box: bench.py's value for each "NAME=VALUE[,NAME=VALUE..]" setting (or "-" = none), interleaved.
 # The experiment build (make -C moped_amd/csrc EXTRA=-DMH_EXPERIMENTS BUILD=build_exp OUT=../libmoped_hip_exp.so) reads the switches;
 # the product build ignores them.  usage: scripts/ab_env.sh reps "bench args" setting1 setting2 ...
+# The two-stage MATCH's switches (csrc/match_screen.hip, screen_plan): MH_SCREEN_SAMPLE, MH_SCREEN_BLOCKS_A, MH_SCREEN_BLOCKS, MH_SCREEN_SPLITS_B,
+# MH_SCREEN_NQB (1 / 2 / 4), MH_SCREEN_SHAPE (1 = 32x32x16, 2 = 16x16x32), MH_SCREEN_ONESWEEP, MH_SCREEN_NO_HITS; pass C's: MH_PASSC_* (csrc/screen_rescore.hip).
 # e.g. the one-sweep MATCH launches against "pass B sweeps every tile":  scripts/ab_env.sh 5 "" MH_SCREEN_ONESWEEP=0 MH_SCREEN_ONESWEEP=1
 reps=$1; args=$2; shift 2
 export MH_LIB_PATH=$PWD/moped_amd/libmoped_hip_exp.so

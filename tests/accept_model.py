@@ -1,4 +1,4 @@
-"""What share of a frame's queries pass C can answer without a search (csrc/match_screen.hip: screen_reject_proved), as a
+"""What share of a frame's queries pass C can answer without a search (csrc/screen.h: screen_reject_proved), as a
 host model: tests/test_screen_reject_cpu.py prints it, tests/test_gpu_accept_reject.py takes its floor from it.
 
 The model sees float32 dot products in the place of the screen's f16 ones and no records: a query's largest value stands

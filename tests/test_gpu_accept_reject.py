@@ -1,4 +1,4 @@
-"""MATCH for a caller that applies the ratio test (mh_match_set_accept; csrc/match_screen.hip: rescore_query's ACCEPT form):
+"""MATCH for a caller that applies the ratio test (mh_match_set_accept; csrc/screen_rescore.hip: rescore_query's ACCEPT form):
 pass C answers a query its records prove to fail `d1 / d2 < ratio` with (-1, inf, inf) and skips the search.
 
 mh_match with mh_match_set_accept(0.8) against the same context in full mode, the exact matrix-pipe kernel

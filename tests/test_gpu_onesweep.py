@@ -1,4 +1,4 @@
-"""The one-sweep MATCH launches on the device (csrc/match_screen.hip: pass A of the 16x16x32 passes keeps the identity
+"""The one-sweep MATCH launches on the device (csrc/screen_ab16.hip: pass A of the 16x16x32 passes keeps the identity
 of its best blocks and hands the sampled tiles' records over, pass B leaves those tiles out): (idx1, d1, d2) bit for
 bit those of match_kernel / match_mfma_kernel (mh_match_set_mode 2 / 3) and of the oracle, on DBs built so that the
 rows that matter lie where the hand-over could lose them.

@@ -1,4 +1,4 @@
-"""The park buffer of pass B of the 16x16x32 MATCH launches at its edges (csrc/match_screen.hip, screen16_kernel<1, 4>: a
+"""The park buffer of pass B of the 16x16x32 MATCH launches at its edges (csrc/screen_ab16.hip, screen16_kernel<1, 4>: a
 wavefront parks the hits of its sweep in LDS -- mh_screen_park_places of them -- and writes them to their queries' lists at
 the end; a hit that finds the buffer full appends from the hit path): one wavefront's sweep leaves exactly as many hits as
 the buffer holds, one more, and half as many again, and (idx1, d1, d2) stay bit for bit those of match_kernel /

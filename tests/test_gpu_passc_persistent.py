@@ -1,4 +1,4 @@
-"""Pass C (csrc/match_screen.hip, rescore_kernel) on launches larger than the chip holds wavefronts: (idx1, d1, d2) of the
+"""Pass C (csrc/screen_rescore.hip, rescore_kernel) on launches larger than the chip holds wavefronts: (idx1, d1, d2) of the
 two-stage path must be the BITS of the exact kernels (mode 0) and of the oracle for every query -- with a device-side
 query count, with queries that leave early (all-zero) or are searched by brute force inside pass C among ordinary ones,
 at 1 .. 17 and 8191 .. 8193 queries -- and a second launch must find every record slot emptied.

@@ -1,4 +1,4 @@
-"""The counted record lists of the 16x16x32 MATCH launches on the device (csrc/match_screen.hip: the hand-over writes a
+"""The counted record lists of the 16x16x32 MATCH launches on the device (csrc/screen_ab16.hip: the hand-over writes a
 query's records from slot 0 and stores their count, pass B's wavefronts append theirs with one atomic add per record when
 they write their parked hits out, pass C reads the count and 64 slots, the rest of a longer list in a second trip, and
 searches a query whose list overflowed by brute force): (idx1, d1, d2) bit for bit those of match_kernel /

@@ -1,4 +1,4 @@
-"""Pass C names the rows of a sampled tile's record itself (csrc/match_screen.hip, rescore_kernel / sample_pair_values):
+"""Pass C names the rows of a sampled tile's record itself (csrc/screen_rescore.hip, rescore_kernel / sample_pair_values):
 screen_handover_kernel knows a block's packed maximum only, so its records say "all 8 rows", and pass C recomputes the 8
 screen values of the records that survive its thinning -- by pass A's arithmetic -- and keeps the rows above tau.
 

@@ -77,6 +77,24 @@ def test_ragged_query_counts(env, Q):
     assert _same_bits(two, [oi, o1, o2])
 
 
+def test_four_query_blocks_on_32x32x16(env):
+    """The smallest launch the plan gives to screen_kernel<*, 4>: 8 blocks of 1024 queries x 512 tiles, the policy's own
+    threshold (fewer than the 12 blocks the 16x16x32 passes start at).  test_ragged_query_counts reaches the one- and
+    two-block kernels, tests/test_gpu_onesweep.py the 16x16x32 ones."""
+    c, torch = env
+    Q, N = 8192, 65536
+    plan = capi.screen_plan(Q, N)
+    assert (plan["family"], plan["nqb"]) == (32, 4)
+    assert (capi.screen_plan(256, 8000)["nqb"], capi.screen_plan(1000, 8000)["nqb"], capi.screen_plan(16384, 32768)["family"]) == (1, 2, 16)
+    db = synth.make_db(16, 4096, seed=5)
+    dbn = orclib.normalize(db.desc)
+    assert len(dbn) == N
+    c.db_upload(dbn, db.model_of, db.xyz, db.n_models)
+    base, _, _ = synth.load_sift_fixture()
+    qn = orclib.normalize(base[np.random.default_rng(4).integers(0, len(base), Q)])
+    assert _same_bits(_search(c, torch, qn, 1), _search(c, torch, qn, 0))
+
+
 def test_shard_with_index_base_and_ragged_rows(env):
     c, torch = env
     db = synth.make_db(7, 1111, seed=9)            # 7777 rows: the last tile is padded

@@ -106,7 +106,7 @@ def _dots_f32(q, d):
     return s
 
 
-# rows of a 32-row block that one lane holds (match_screen.hip: register r of half h = row (r & 3) + 8 (r >> 2) + 4 h)
+# rows of a 32-row block that one lane holds (screen_ab32.hip: register r of half h = row (r & 3) + 8 (r >> 2) + 4 h)
 _LANE_ROWS = [np.array([(r & 3) + 8 * (r >> 2) + 4 * h for r in range(16)]) for h in (0, 1)]
 
 

@@ -1,4 +1,4 @@
-"""Completeness of pass A's hand-over in the one-sweep MATCH launches (csrc/match_screen.hip, "pass A of the
+"""Completeness of pass A's hand-over in the one-sweep MATCH launches (csrc/screen_ab16.hip, "pass A of the
 one-sweep launches"), as a restatement in numpy against the direct definition.
 
 A lane slot (split x quarter) of pass A folds the largest screen value of every 8-row block it sees into a sorted list

@@ -1,4 +1,4 @@
-"""Pass C's proof that the ratio test rejects a query (csrc/match_screen.hip: screen_reject_proved, exported as
+"""Pass C's proof that the ratio test rejects a query (csrc/screen.h: screen_reject_proved, exported as
 mh_screen_reject_proved), checked in host arithmetic against the oracle.
 
 The function sees of a query: qq, Dmax, h1 >= every screen value w~ of the DB (or tau, whichever is larger), l2 <= the second
