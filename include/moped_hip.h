@@ -1115,6 +1115,15 @@ int mh_sift_debug_level(mh_ctx* ctx, int slot, int octave, int kind, int level, 
 int mh_sift_debug_candidates(mh_ctx* ctx, int slot, mh_sift_candidate* out_host, uint8_t* won_host, int cap, int32_t* n);
 /* The key buffer, slots in the order the kernel filled them (any).  *n = their number; `cap` are written. */
 int mh_sift_debug_keys(mh_ctx* ctx, int slot, mh_sift_key* out_host, int cap, int32_t* n);
+/* The shipped descriptor kernel alone on n keys of the caller's, over the pyramid the last extraction left in `slot`,
+ * launched on `workgroups` workgroups (0: as in production, 4 096; fewer workgroups than keys: a workgroup describes
+ * several keys, as in batches of five or more images).  Keys and outputs live in temporary buffers: the context's key
+ * buffer, counters and outputs stay untouched.  Output place i (desc_host [n][128], xy_host [n][2] = (col, row),
+ * scale_ori_host [n][2], optional) = the key with i keys of larger `order`, as in production.  Synchronises.
+ * MH_ERR_ARG: no extraction yet, no such slot, n < 1, a key whose octave is outside the plan or whose index is not 1..3,
+ * `order` values that are not distinct, fsize outside (0, 64], |frow| or |fcol| above 1e6, |ori| above 8, a NaN. */
+int mh_sift_debug_describe(mh_ctx* ctx, int slot, const mh_sift_key* keys_host, int n, int workgroups, float* desc_host,
+                           float* xy_host, float* scale_ori_host);
 /* ONE blur level of a host image through a named kernel of the blur chain, with GaussianBlur's kernel for `sigma`:
  *   0  row kernel + column kernel         any tap count below 64
  *   1  tile kernel, one level             half-width <= 16

@@ -227,7 +227,7 @@ EXPORTS = [
     "mh_set_linkage_scratch_limit",
     "mh_undistort_map", "mh_undistort", "mh_undistort_dev", "mh_frame_set_undistort",
     "mh_sift_extract_batch_dev", "mh_sift_debug_plan", "mh_sift_debug_level", "mh_sift_debug_candidates",
-    "mh_sift_debug_keys", "mh_sift_debug_blur",
+    "mh_sift_debug_keys", "mh_sift_debug_describe", "mh_sift_debug_blur",
     "mh_screen_pack_value", "mh_screen_pack_pert", "mh_screen_sample_bounds", "mh_screen_launch_plan", "mh_screen_plan", "mh_match_incomplete",
     "mh_screen_sample_values", "mh_match_query_candidates", "mh_screen_park_places",
     "mh_frame_enqueue_images", "mh_frame_enqueue_images_batch", "mh_frame_set_undistort_images", "mh_frame_image_counts",
@@ -320,6 +320,7 @@ def load():
     L.mh_sift_debug_level.argtypes = [vp, i32, i32, i32, i32, vp]
     L.mh_sift_debug_candidates.argtypes = [vp, i32, vp, vp, i32, C.POINTER(C.c_int32)]
     L.mh_sift_debug_keys.argtypes = [vp, i32, vp, i32, C.POINTER(C.c_int32)]
+    L.mh_sift_debug_describe.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
     L.mh_sift_debug_blur.argtypes = [vp, i32, vp, i32, i32, f32, i32, vp, vp, vp]
     L.mh_frame_enqueue_image.argtypes = [vp, vp, i32, i32, i32, i32, C.POINTER(mh_cam), C.POINTER(mh_frame_params),
                                          C.c_uint64]
@@ -1401,6 +1402,19 @@ class Context:
         if n.value > cap:
             raise MhError(f"mh_sift_debug_keys: {n.value} keys, room for {cap}")
         return out[:n.value].copy()
+
+    def sift_debug_describe(self, keys, workgroups=0, slot=0):
+        """The shipped descriptor kernel alone on `keys` (SIFT_KEY_DTYPE, distinct `order`) over the pyramid the last
+        extraction left in `slot`, on `workgroups` workgroups (0: production's 4 096) -> (xy [n,2], scale_ori [n,2], desc
+        [n,128]); place i = the key with i keys of larger order.  The context's own keys and outputs stay untouched."""
+        k = np.ascontiguousarray(keys, SIFT_KEY_DTYPE)
+        n = len(k)
+        xy = np.zeros((n, 2), np.float32)
+        so = np.zeros((n, 2), np.float32)
+        d = np.zeros((n, 128), np.float32)
+        self._ck(self.L.mh_sift_debug_describe(self.h, slot, _ptr(k), n, workgroups, _ptr(d), _ptr(xy), _ptr(so)),
+                 "mh_sift_debug_describe")
+        return xy, so, d
 
     def sift_debug_blur(self, variant, src, sigma, half=False, want_dog=True, want_half=False):
         """One blur level of a float32 image through kernel `variant` (mh_sift_debug_blur) -> (dst, dog or None,

@@ -304,6 +304,70 @@ int mh_sift_debug_keys(mh_ctx* ctx, int slot, mh_sift_key* out_host, int cap, in
   return MH_OK;
 }
 
+int mh_sift_debug_describe(mh_ctx* ctx, int slot, const mh_sift_key* keys_host, int n, int workgroups, float* desc_host,
+                           float* xy_host, float* scale_ori_host) {
+  const char* const who = "mh_sift_debug_describe";
+  SiftState* st = last_sift(ctx, slot, who);
+  if (!st) return MH_ERR_ARG;
+  if (!keys_host || n < 1 || workgroups < 0 || workgroups > 65536 || !desc_host || !xy_host) {
+    ctx->err = std::string(who) + ": bad argument";
+    return MH_ERR_ARG;
+  }
+  // what the kernel takes on trust from the key stage: a level that exists, a window that can be counted, orders that
+  // rank the keys
+  std::vector<unsigned long long> orders(n);
+  for (int i = 0; i < n; ++i) {
+    const mh_sift_key& k = keys_host[i];
+    const bool level = k.octave >= 0 && k.octave < st->plan.n_octaves && k.index >= 1 && k.index <= 3;
+    const bool window = k.fsize > 0.f && k.fsize <= 64.f && fabsf(k.frow) <= 1e6f && fabsf(k.fcol) <= 1e6f && fabsf(k.ori) <= 8.f;
+    if (!level || !window) {   // (a NaN fails the comparisons)
+      ctx->err = std::string(who) + ": key " + std::to_string(i) +
+                 (level ? ": fsize in (0, 64], |frow|, |fcol| <= 1e6 and |ori| <= 8 are taken"
+                        : ": octave / index outside the plan (keys come from Gaussian levels 1..3)");
+      return MH_ERR_ARG;
+    }
+    orders[i] = k.order;
+  }
+  std::sort(orders.begin(), orders.end());
+  if (std::adjacent_find(orders.begin(), orders.end()) != orders.end()) {
+    ctx->err = std::string(who) + ": the keys' order values are not distinct";
+    return MH_ERR_ARG;
+  }
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
+  hipStream_t s = ctx->stream;
+  const size_t un = (size_t)n;
+  // everything temporary: the context's key buffer, counters and outputs stay as the extraction left them
+  DevBuf<SiftKey> keys;
+  DevBuf<int32_t> count, n_out;
+  DevBuf<float> desc, xy, scale_ori;
+  hipError_t e = keys.ensure(un, s);
+  if (e == hipSuccess) e = count.ensure(1, s);
+  if (e == hipSuccess) e = n_out.ensure(1, s);
+  if (e == hipSuccess) e = desc.ensure(un * 128, s);
+  if (e == hipSuccess) e = xy.ensure(un * 2, s);
+  if (e == hipSuccess) e = scale_ori.ensure(un * 2, s);
+  const int32_t n32 = n;
+  if (e == hipSuccess) e = hipMemcpyAsync(keys, keys_host, un * sizeof(SiftKey), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(count, &n32, sizeof n32, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) {
+    launch_sift_describe(st->plan, st->B.pyramid + (size_t)slot * st->plan.floats, keys, count, n,
+                         workgroups ? workgroups : SIFT_KEY_WORKGROUPS, desc, xy, scale_ori, n_out, s);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(desc_host, desc, un * 128 * sizeof(float), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(xy_host, xy, un * 2 * sizeof(float), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && scale_ori_host)
+    e = hipMemcpyAsync(scale_ori_host, scale_ori, un * 2 * sizeof(float), hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);   // (before the buffers go)
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess) {
+    ctx->err = std::string(who) + ": " + hipGetErrorString(e);
+    return MH_ERR_HIP;
+  }
+  return MH_OK;
+}
+
 int mh_sift_debug_blur(mh_ctx* ctx, int variant, const float* src_host, int src_rows, int src_cols, float sigma, int half,
                        float* dst_host, float* dog_host, float* half_host) {
   if (!ctx || !src_host || !dst_host || src_rows <= 0 || src_cols <= 0 || src_rows > 32767 || src_cols > 32767) {

@@ -88,6 +88,18 @@ void launch_sift_batch(const uint8_t* const* gray, int n, int width, int height,
                        const SiftBuffers& B, int out_cap, int out_step, float* desc_out, float* xy_out,
                        float* scale_ori_out, int32_t* n_out, int n_out_step, hipStream_t s);
 
+// Workgroups of the per-key kernels (orient, describe) for one image; each loops over its keys (a batch of five or more
+// images launches a quarter of them per image).
+constexpr int SIFT_KEY_WORKGROUPS = 4096;
+
+// For verification (mh_sift_debug_describe): the shipped describe_kernel alone, over one image's pyramid at `pyramid`
+// (the layout launch_sift leaves: plan.floats floats), on the *n_keys <= key_cap keys at `keys`, with gridDim.x =
+// workgroups.  Output place i (desc_out [key_cap][128], xy_out / scale_ori_out [key_cap][2]) = the key with i keys of
+// larger `order`; *n_out = the number of keys.  The caller vouches for every key: octave and index inside the plan,
+// finite positive fsize, distinct orders.
+void launch_sift_describe(const SiftPlan& plan, float* pyramid, const SiftKey* keys, const int32_t* n_keys, int key_cap,
+                          int workgroups, float* desc_out, float* xy_out, float* scale_ori_out, int32_t* n_out,
+                          hipStream_t s);
 
 // The owner map's claim prefix (SiftBatch::own_prefix) of the launch that left `epoch` in *SiftBuffers::own_epoch.
 unsigned sift_own_prefix(const SiftPlan& plan, unsigned epoch);

@@ -9,7 +9,8 @@
 // samples -- so the only differences to the oracle come from the device's expf / atan2f /
 // sinf / cosf / powf (a few ulp).  The Gaussian kernels are computed on the host with libm.
 // tests/test_gpu_sift_stages.py holds that stage by stage (read back through mh_sift_debug_*): pyramid, extrema and key
-// positions equal the oracle's as uint32 on every blur kernel below, fSize within 4 ulp (powf: 2 measured), angles 1e-3 rad.
+// positions equal the oracle's as uint32 on every blur kernel below, fSize within 4 ulp (powf: 2 measured), angles 1e-3 rad,
+// every descriptor within a per-key bar of a few 1e-6 of the float64 descriptor of the same key (mh_sift_debug_describe).
 //
 // Layout: the WHOLE pyramid stays resident (14 images per octave, all octaves: ~90 MB for a
 // doubled 640x480 frame), so everything after the blur chain runs ONCE over all octaves:
@@ -1424,6 +1425,28 @@ unsigned sift_own_prefix(const SiftPlan& plan, unsigned epoch) {
 
 namespace {
 
+// The kernels' table of one image's pyramid at `pyramid` (plan.floats floats: per octave 6 Gaussian + 5 DoG images) and
+// owner map at `owner` (null: a table for kernels that do not touch the map).
+SiftPyramid pyramid_of(const SiftPlan& plan, float* pyramid, unsigned int* owner) {
+  SiftPyramid P;
+  memset(&P, 0, sizeof P);
+  P.n_octaves = plan.n_octaves;
+  float* p = pyramid;
+  unsigned int* own = owner;
+  for (int o = 0; o < plan.n_octaves; ++o) {
+    SiftOctave& O = P.oct[o];
+    O.rows = plan.rows[o];
+    O.cols = plan.cols[o];
+    O.fscale = plan.fscale[o];
+    const size_t px = (size_t)O.rows * O.cols;
+    for (int i = 0; i < kScales + 3; ++i, p += px) O.gaus[i] = p;
+    for (int i = 0; i < kScales + 2; ++i, p += px) O.dog[i] = p;
+    O.owner = own;
+    if (own) own += px;
+  }
+  return P;
+}
+
 // launch_sift / launch_sift_batch: n images (n = 1: `grays` holds the one) in one launch per stage
 void launch_sift_images(const uint8_t* const* grays, int n, int width, int height, int double_size, const SiftPlan& plan,
                         const SiftBuffers& B, int out_cap, int out_step, float* desc_out, float* xy_out,
@@ -1441,22 +1464,7 @@ void launch_sift_images(const uint8_t* const* grays, int n, int width, int heigh
   SiftImages imgs;
   for (int i = 0; i < MH_MAX_BATCH; ++i) imgs.gray[i] = grays[i < n ? i : 0];
   const unsigned un = (unsigned)n;
-  SiftPyramid P;
-  memset(&P, 0, sizeof P);
-  P.n_octaves = plan.n_octaves;
-  float* p = B.pyramid;
-  unsigned int* own = B.owner;
-  for (int o = 0; o < plan.n_octaves; ++o) {
-    SiftOctave& O = P.oct[o];
-    O.rows = plan.rows[o];
-    O.cols = plan.cols[o];
-    O.fscale = plan.fscale[o];
-    const size_t px = (size_t)O.rows * O.cols;
-    for (int i = 0; i < kScales + 3; ++i, p += px) O.gaus[i] = p;
-    for (int i = 0; i < kScales + 2; ++i, p += px) O.dog[i] = p;
-    O.owner = own;
-    own += px;
-  }
+  const SiftPyramid P = pyramid_of(plan, B.pyramid, B.owner);
   // (the counters are cleared by prepare_kernel; the owner map is not cleared at all: SiftBatch::own_prefix)
   {
     const unsigned key_bits = sift_key_bits(plan);
@@ -1637,9 +1645,9 @@ void launch_sift_images(const uint8_t* const* grays, int n, int width, int heigh
   detect(0, plan.n_octaves, s);
   // (the per-key kernels loop over the keys: a batch's images share the chip, fewer workgroups per image)
   const unsigned per = n > 4 ? 4 : 1;
-  hipLaunchKernelGGL(orient_kernel, dim3(4096 / per, un), dim3(64), 0, s, P, (const SiftCandidate*)B.cand,
+  hipLaunchKernelGGL(orient_kernel, dim3(SIFT_KEY_WORKGROUPS / per, un), dim3(64), 0, s, P, (const SiftCandidate*)B.cand,
                      (const int32_t*)(B.counters + 0), B.cand_cap, B.keys, B.counters + 1, B.key_cap, B.counters + 2, Bt);
-  hipLaunchKernelGGL(describe_kernel, dim3(4096 / per, un), dim3(64 * DESC_WAVES), 0, s, P, (const SiftKey*)B.keys,
+  hipLaunchKernelGGL(describe_kernel, dim3(SIFT_KEY_WORKGROUPS / per, un), dim3(64 * DESC_WAVES), 0, s, P, (const SiftKey*)B.keys,
                      (const int32_t*)(B.counters + 1), B.key_cap, out_cap, n_out, desc_out, xy_out, scale_ori_out, Bt);
 }
 
@@ -1678,6 +1686,16 @@ void launch_sift_batch(const uint8_t* const* gray, int n, int width, int height,
   }
   launch_sift_images(gray, n, width, height, double_size, plan, B, out_cap, out_step, desc_out, xy_out, scale_ori_out,
                      n_out, n_out_step, s);
+}
+
+// describe_kernel alone (sift.h), as launch_sift_images launches it for one image, on `workgroups` workgroups.
+void launch_sift_describe(const SiftPlan& plan, float* pyramid, const SiftKey* keys, const int32_t* n_keys, int key_cap,
+                          int workgroups, float* desc_out, float* xy_out, float* scale_ori_out, int32_t* n_out,
+                          hipStream_t s) {
+  const SiftPyramid P = pyramid_of(plan, pyramid, nullptr);   // (the owner map is the earlier stages')
+  SiftBatch Bt;   // one image: no steps
+  hipLaunchKernelGGL(describe_kernel, dim3(workgroups, 1), dim3(64 * DESC_WAVES), 0, s, P, keys, n_keys, key_cap, key_cap,
+                     n_out, desc_out, xy_out, scale_ori_out, Bt);
 }
 
 // One blur level through a named kernel (sift.h): the launches launch_sift_images makes for a level, on one image.

@@ -735,6 +735,84 @@ class SiftRun:
         so = np.stack([fscale * h["fsize"], self.peaks["ang"]], 1).astype(np.float32)
         return xy[::-1].copy(), so[::-1].copy()
 
+    KEY = np.dtype([("octave", "<i4"), ("index", "<i4"), ("fsize", "<f4"), ("frow", "<f4"), ("fcol", "<f4"), ("ori", "<f4")])
+    MODES = {"f32": 0, "f64": 1, "pert": 2, "drop": 3}
+
+    def key_records(self):
+        """The same keys as make_key receives them (octave pixels), in the reference's list order: KEY records."""
+        h = self.hits[self.peaks["hit"]]
+        k = np.zeros(len(h), self.KEY)
+        for f in ("octave", "index", "fsize", "frow", "fcol"):
+            k[f] = h[f]
+        k["ori"] = self.peaks["ang"]
+        return k[::-1].copy()
+
+    def fscale(self, octave):
+        """Octave pixel -> image pixel, as float32."""
+        return (np.float32(0.5 if self.double_size else 1.0) * np.exp2(np.asarray(octave)).astype(np.float32)).astype(np.float32)
+
+    def _key_args(self, keys):
+        cols = [_c(keys[f], t) for f, t in (("octave", np.int32), ("index", np.int32), ("fsize", np.float32),
+                                            ("frow", np.float32), ("fcol", np.float32), ("ori", np.float32))]
+        return cols, [a.ctypes.data for a in cols]
+
+    def describe(self, keys, mode="f32", ulps=0, direction=0, seed=0, drop=None, with_totals=False):
+        """Descriptors of the given keys (any records with KEY's fields, e.g. the device's mh_sift_key) on this run's
+        pyramid (orc_sift_run_describe) -> [n, 128], float32, or float64 for mode 'f64'.
+          f32   make_key's arithmetic
+          f64   the samples the float32 tests select; everything after the selection in double on the float32 pixels
+          pert  f32 with every sinf / cosf / expf / gradient atan2f result moved `ulps` floats: direction +1 up, -1 down,
+                0 by a hash of (seed, key, sample, function); the selection follows the moved sinf / cosf
+          drop  f32 without one selected sample per key: drop[n] = its index in raster order, or -2 = the largest mag
+        with_totals: also the number of selected samples per key."""
+        n = len(keys)
+        L = self._L
+        L.orc_sift_run_describe.restype = C.c_int
+        L.orc_sift_run_describe.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_int, C.c_uint32,
+                                                                                      C.c_void_p, C.c_void_p, C.c_void_p]
+        keep, ptrs = self._key_args(keys)
+        out = np.zeros((n, 128), np.float64 if mode == "f64" else np.float32)
+        totals = np.zeros(n, np.int32)
+        dr = None
+        if mode == "drop":
+            dr = _c(np.broadcast_to(np.asarray(drop, np.int64), (n,)), np.int64)
+        rc = L.orc_sift_run_describe(self._run, n, *ptrs, self.MODES[mode], int(ulps), int(direction), int(seed),
+                                     dr.ctypes.data if dr is not None else None, out.ctypes.data, totals.ctypes.data)
+        if rc != 0:
+            raise ValueError("SiftRun.describe: a key's octave / index is not a level of this run that keys come from")
+        return (out, totals) if with_totals else out
+
+    def drop_row_ends(self, keys, f64, bar):
+        """Mode drop for the first / last selected sample of every window row of every key (orc_sift_run_drop_row_ends)
+        -> (tried [n, 2], detected [n, 2]): samples left out, and those whose max |drop - f64| exceeded bar[key]."""
+        n = len(keys)
+        L = self._L
+        L.orc_sift_run_drop_row_ends.restype = C.c_int
+        L.orc_sift_run_drop_row_ends.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 10
+        keep, ptrs = self._key_args(keys)
+        ref, b = _c(f64, np.float64), _c(bar, np.float64)
+        assert ref.shape == (n, 128) and b.shape == (n,)
+        tried, det = np.zeros((n, 2), np.int32), np.zeros((n, 2), np.int32)
+        if L.orc_sift_run_drop_row_ends(self._run, n, *ptrs, ref.ctypes.data, b.ctypes.data, tried.ctypes.data,
+                                        det.ctypes.data) != 0:
+            raise ValueError("SiftRun.drop_row_ends: a key's octave / index is not a level of this run that keys come from")
+        return tried, det
+
+    def descriptor_bar(self, keys, ulps):
+        """The per-key bound of a float32 device descriptor's distance from mode f64 (tests/test_sift_stages_cpu.py says
+        why this form): bar = 2 (e_ref + e_pert) + 2^-23 with e_ref = max |f32 - f64| and e_pert = the largest max |pert -
+        f32| of four perturbation runs (all up, all down, two hashed seeds) of `ulps` floats.
+        -> dict(f32, f64, e_ref, e_pert, bar, totals)."""
+        f32, totals = self.describe(keys, "f32", with_totals=True)
+        f64 = self.describe(keys, "f64")
+        e_ref = np.abs(f32.astype(np.float64) - f64).max(axis=1) if len(keys) else np.zeros(0)
+        e_pert = np.zeros(len(keys))
+        for direction, seed in ((1, 0), (-1, 0), (0, 1), (0, 2)):
+            p = self.describe(keys, "pert", ulps=ulps, direction=direction, seed=seed)
+            if len(keys):
+                e_pert = np.maximum(e_pert, np.abs(p.astype(np.float64) - f32.astype(np.float64)).max(axis=1))
+        return dict(f32=f32, f64=f64, e_ref=e_ref, e_pert=e_pert, bar=2.0 * (e_ref + e_pert) + 2.0 ** -23, totals=totals)
+
 
 def sift_taps(sigma):
     L = lib()

@@ -19,6 +19,9 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <map>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "oracle.h"
@@ -89,6 +92,18 @@ void blur(Img& dst, const Img& src, float fblur) {
   }
 }
 
+// GradOriImages' two differences at one pixel (:959-992), in T on the float pixels (T = double: describe mode f64)
+template <class T>
+void grad_at(const Img& im, int i, int j, T& dc, T& dr) {
+  const int rows = im.rows, cols = im.cols;
+  if (j == 0) dc = T(2) * ((T)im.at(i, 1) - (T)im.at(i, 0));
+  else if (j == cols - 1) dc = T(2) * ((T)im.at(i, j) - (T)im.at(i, j - 1));
+  else dc = (T)im.at(i, j + 1) - (T)im.at(i, j - 1);
+  if (i == 0) dr = T(2) * ((T)im.at(0, j) - (T)im.at(1, j));
+  else if (i == rows - 1) dr = T(2) * ((T)im.at(i - 1, j) - (T)im.at(i, j));
+  else dr = (T)im.at(i - 1, j) - (T)im.at(i + 1, j);
+}
+
 // GradOriImages (:959-992)
 void grad_ori(const Img& im, Img& grad, Img& ori) {
   const int rows = im.rows, cols = im.cols;
@@ -97,12 +112,7 @@ void grad_ori(const Img& im, Img& grad, Img& ori) {
   for (int i = 0; i < rows; ++i)
     for (int j = 0; j < cols; ++j) {
       float dc, dr;
-      if (j == 0) dc = 2.0f * (im.at(i, 1) - im.at(i, 0));
-      else if (j == cols - 1) dc = 2.0f * (im.at(i, j) - im.at(i, j - 1));
-      else dc = im.at(i, j + 1) - im.at(i, j - 1);
-      if (i == 0) dr = 2.0f * (im.at(0, j) - im.at(1, j));
-      else if (i == rows - 1) dr = 2.0f * (im.at(i - 1, j) - im.at(i, j));
-      else dr = im.at(i - 1, j) - im.at(i + 1, j);
+      grad_at(im, i, j, dc, dr);
       grad.at(i, j) = sqrtf(dc * dc + dr * dr);
       ori.at(i, j) = atan2f(dr, dc);
     }
@@ -185,36 +195,147 @@ struct Key {
   float desc[128];
 };
 
-// PlaceInIndex (:1609-1668)
-void place(float* fdesc, float mag, float ori, float rx, float cx) {
-  const float oribin = ori * (8.0f / (2 * (float)kPi));
+// PlaceInIndex (:1609-1668); T = float is the library's arithmetic, T = double describe mode f64
+template <class T>
+void place(T* fdesc, T mag, T ori, T rx, T cx) {
+  const T oribin = ori * (T)(8.0f / (2 * (float)kPi));
   const int nr = rx < 0 ? (int)(rx - 1) : (int)rx;
-  const float rf = rx - (float)nr;
+  const T rf = rx - (T)nr;
   const int nc = cx < 0 ? (int)(cx - 1) : (int)cx;
-  const float cf = cx - (float)nc;
+  const T cf = cx - (T)nc;
   const int no = oribin < 0 ? (int)(oribin - 1) : (int)oribin;
-  const float of = oribin - (float)no;
+  const T of = oribin - (T)no;
   for (int i = 0; i < 2; ++i) {
     if ((unsigned)(i + nr) >= 4) continue;
-    const float rg = i == 0 ? mag * (1 - rf) : mag * rf;
+    const T rg = i == 0 ? mag * (1 - rf) : mag * rf;
     for (int j = 0; j < 2; ++j) {
       if ((unsigned)(j + nc) >= 4) continue;
-      const float cg = j == 0 ? rg * (1 - cf) : rg * cf;
-      float* cell = fdesc + 8 * (4 * (i + nr) + j + nc);
+      const T cg = j == 0 ? rg * (1 - cf) : rg * cf;
+      T* cell = fdesc + 8 * (4 * (i + nr) + j + nc);
       for (int k = 0; k < 2; ++k) cell[(no + k) & 7] += k == 0 ? cg * (1 - of) : cg * of;
     }
   }
 }
 
 // NormalizeVec (:1519-1527)
-void normalize_vec(float* pf, int num) {
-  float acc = 0;
+template <class T>
+void normalize_vec(T* pf, int num) {
+  T acc = 0;
   for (int i = 0; i < num; ++i) acc += pf[i] * pf[i];
-  acc = 1 / sqrtf(acc);
+  acc = 1 / std::sqrt(acc);
   for (int i = 0; i < num; ++i) pf[i] *= acc;
 }
 
-// MakeKeypoint / MakeKeypointSample / KeySample / AddSample (:1424-1607), plain-C branch
+// What orc_sift_run_describe may change about the library's arithmetic (make_key itself changes nothing):
+struct Tweak {
+  int ulps = 0;     // mode pert: every result of sinf / cosf / expf and of the gradient image's atan2f moved this many floats
+  int dir = 0;      //   up (+1), down (-1) or where a hash of (seed, key, sample, function) says (0)
+  uint32_t seed = 0, key = 0;
+  long drop = -1;   // mode drop: the selected sample (counted in raster order) that is left out; -2 = the one with the largest mag
+};
+enum { FN_SIN, FN_COS, FN_EXP, FN_ATAN2 };
+
+float moved(float v, const Tweak* tw, int sample, int fn) {
+  if (!tw || tw->ulps == 0) return v;
+  int dir = tw->dir;
+  if (dir == 0) {
+    uint32_t h = (tw->seed + 1u) * 0x9E3779B1u ^ (tw->key + 1u) * 0x85EBCA6Bu ^ ((uint32_t)sample + 2u) * 0xC2B2AE35u ^
+                 ((uint32_t)fn + 1u) * 0x27D4EB2Fu;
+    h ^= h >> 16;
+    h *= 0x7FEB352Du;
+    h ^= h >> 15;
+    h *= 0x846CA68Bu;
+    h ^= h >> 16;
+    dir = (h & 1u) ? 1 : -1;
+  }
+  for (int i = 0; i < tw->ulps; ++i) v = nextafterf(v, dir > 0 ? INFINITY : -INFINITY);
+  return v;
+}
+
+// MakeKeypointSample / KeySample / AddSample (:1497-1607), plain-C branch: the descriptor of one key, 128 values.
+//   T = float, tw = null   the library's arithmetic, operation for operation (make_key)
+//   T = double             the samples the float tests select (rx, cx, the pixel inside the image: selection is float in
+//                          every mode), and from there on everything in double on the same float pixels `im`: gradient,
+//                          atan2, sin / cos of the orientation, exp, the trilinear weights, the sums, NormalizeVec, the clamp
+//   tw                     float with the tweaks above; a moved sinf / cosf moves the selection too
+// Returns the number of selected samples; sel_rows (optional) gets every selected sample's window row, in raster order.
+template <class T>
+int describe_key(T* desc, const Img* im, const Img& grad, const Img& orim, float fSize, float frow, float fcol,
+                 float forient, const Tweak* tw = nullptr, std::vector<int>* sel_rows = nullptr) {
+  constexpr bool wide = !std::is_same<T, float>::value;
+  for (int i = 0; i < 128; ++i) desc[i] = 0;
+  const int rowstart = (int)(frow + 0.5f), colstart = (int)(fcol + 0.5f);
+  const float sinang = moved(sinf(forient), tw, -1, FN_SIN), cosang = moved(cosf(forient), tw, -1, FN_COS);
+  const float fdrow = frow - (float)rowstart, fdcol = fcol - (float)colstart;
+  const float frealsize = 3.0f * fSize, firealsize = 1.0f / (3.0f * fSize);
+  const int win = (int)(frealsize * kSqrt2 * 5.0f * 0.5f + 0.5f);
+  const float fsr = sinang * firealsize, fcr = cosang * firealsize, fdrr = -fdrow * firealsize,
+              fdcr = -fdcol * firealsize;
+  // (wide only) the same four in T from the key's floats
+  [[maybe_unused]] const T wir = (T)1 / ((T)3 * (T)fSize);
+  [[maybe_unused]] const T wsr = std::sin((T)forient) * wir, wcr = std::cos((T)forient) * wir;
+  [[maybe_unused]] const T wdrr = -((T)frow - (T)rowstart) * wir, wdcr = -((T)fcol - (T)colstart) * wir;
+  long drop = tw ? tw->drop : -1;
+  int selected = 0;
+  // pass 0 (drop == -2 only) finds the selected sample with the largest mag, pass 1 describes
+  for (int pass = drop == -2 ? 0 : 1; pass < 2; ++pass) {
+    long sel = 0, best_at = -1;
+    float best = -1;
+    for (int row = -win; row <= win; ++row) {
+      const float fr = (float)row;
+      float fc = -(float)win;
+      for (int col = -win; col <= win; ++col, fc += 1) {
+        const float rpos = fsr * fc + fcr * fr + fdrr;
+        const float cpos = fcr * fc - fsr * fr + fdcr;
+        const float rx = rpos + (2.0f - 0.5f), cx = cpos + (2.0f - 0.5f);
+        if (!(rx > -0.9999f && rx < 3.9999f && cx > -0.9999f && cx < 3.9999f)) continue;
+        const int r = rowstart + row, c = colstart + col;
+        if (r < 0 || r >= grad.rows || c < 0 || c >= grad.cols) continue;
+        const long at = sel++;
+        const int sample = (row + win) * (2 * win + 1) + (col + win);
+        const float g = grad.at(r, c) * moved(expf(-0.125f * (rpos * rpos + cpos * cpos)), tw, sample, FN_EXP);
+        if (pass == 0) {
+          if (g > best) {
+            best = g;
+            best_at = at;
+          }
+          continue;
+        }
+        if (sel_rows) sel_rows->push_back(row);
+        if (at == drop) continue;
+        if constexpr (wide) {
+          const T wfc = (T)col, wfr = (T)row;
+          const T wrpos = wsr * wfc + wcr * wfr + wdrr, wcpos = wcr * wfc - wsr * wfr + wdcr;
+          T dc, dr;
+          grad_at(*im, r, c, dc, dr);
+          const T wg = std::sqrt(dc * dc + dr * dr) * std::exp((T)-0.125 * (wrpos * wrpos + wcpos * wcpos));
+          T o = std::atan2(dr, dc) - (T)forient;
+          while (o > (T)(2 * kPi)) o -= (T)(2 * kPi);
+          while (o < 0) o += (T)(2 * kPi);
+          place<T>(desc, wg, o, wrpos + (T)1.5, wcpos + (T)1.5);
+        } else {
+          float o = moved(orim.at(r, c), tw, sample, FN_ATAN2) - forient;
+          while (o > 2 * kPi) o -= 2 * kPi;
+          while (o < 0) o += 2 * kPi;
+          place<float>(desc, g, o, rx, cx);
+        }
+      }
+    }
+    if (pass == 0) drop = best_at;
+    selected = (int)sel;
+  }
+  normalize_vec(desc, 128);
+  bool again = false;
+  for (int i = 0; i < 128; ++i)
+    if (desc[i] > (T)0.2f) {
+      desc[i] = (T)0.2f;
+      again = true;
+    }
+  if (again) normalize_vec(desc, 128);
+  return selected;
+}
+
+// MakeKeypoint (:1424-1495)
 void make_key(std::vector<Key>& out, const Img& grad, const Img& orim, float fscale, float fSize, float frow,
               float fcol, float forient) {
   Key k;
@@ -222,39 +343,7 @@ void make_key(std::vector<Key>& out, const Img& grad, const Img& orim, float fsc
   k.row = fscale * frow;
   k.col = fscale * fcol;
   k.scale = fscale * fSize;
-  memset(k.desc, 0, sizeof k.desc);
-  const int rowstart = (int)(frow + 0.5f), colstart = (int)(fcol + 0.5f);
-  const float sinang = sinf(forient), cosang = cosf(forient);
-  const float fdrow = frow - (float)rowstart, fdcol = fcol - (float)colstart;
-  const float frealsize = 3.0f * fSize, firealsize = 1.0f / (3.0f * fSize);
-  const int win = (int)(frealsize * kSqrt2 * 5.0f * 0.5f + 0.5f);
-  const float fsr = sinang * firealsize, fcr = cosang * firealsize, fdrr = -fdrow * firealsize,
-              fdcr = -fdcol * firealsize;
-  for (int row = -win; row <= win; ++row) {
-    const float fr = (float)row;
-    float fc = -(float)win;
-    for (int col = -win; col <= win; ++col, fc += 1) {
-      const float rpos = fsr * fc + fcr * fr + fdrr;
-      const float cpos = fcr * fc - fsr * fr + fdcr;
-      const float rx = rpos + (2.0f - 0.5f), cx = cpos + (2.0f - 0.5f);
-      if (!(rx > -0.9999f && rx < 3.9999f && cx > -0.9999f && cx < 3.9999f)) continue;
-      const int r = rowstart + row, c = colstart + col;
-      if (r < 0 || r >= grad.rows || c < 0 || c >= grad.cols) continue;
-      const float g = grad.at(r, c) * expf(-0.125f * (rpos * rpos + cpos * cpos));
-      float o = orim.at(r, c) - forient;
-      while (o > 2 * kPi) o -= 2 * kPi;
-      while (o < 0) o += 2 * kPi;
-      place(k.desc, g, o, rx, cx);
-    }
-  }
-  normalize_vec(k.desc, 128);
-  bool again = false;
-  for (int i = 0; i < 128; ++i)
-    if (k.desc[i] > 0.2f) {
-      k.desc[i] = 0.2f;
-      again = true;
-    }
-  if (again) normalize_vec(k.desc, 128);
+  describe_key<float>(k.desc, nullptr, grad, orim, fSize, frow, fcol, forient);
   out.push_back(k);
 }
 
@@ -514,7 +603,87 @@ struct SiftRun {
   Pyramid pyr;
   Trace trace;
   std::vector<Key> keys;
+  std::map<std::pair<int, int>, std::pair<Img, Img>> grads;   // (octave, index) -> GradOriImages of that level, made on demand
 };
+
+// the gradient images of Gaussian level `index` (1..kScales: the levels keys come from) of `octave`, or null
+static const std::pair<Img, Img>* run_grads(SiftRun* R, int octave, int index) {
+  if (octave < 0 || octave >= (int)R->pyr.gaus.size() || index < 1 || index > kScales) return nullptr;
+  auto it = R->grads.find({octave, index});
+  if (it == R->grads.end()) {
+    it = R->grads.emplace(std::make_pair(octave, index), std::pair<Img, Img>()).first;
+    grad_ori(R->pyr.gaus[octave][index], it->second.first, it->second.second);
+  }
+  return &it->second;
+}
+
+// Descriptors of caller-supplied keys on the run's own pyramid (describe_key).  mode 0 f32: make_key's arithmetic ->
+// out float [n][128]; 1 f64 -> out double [n][128]; 2 pert (ulps, dir, seed: Tweak) -> float; 3 drop (drop[n]: Tweak::drop
+// per key) -> float.  totals (optional) [n]: selected samples per key, the dropped one included.  Returns 0, or -1 --
+// nothing written -- when a key's octave / index is not a level keys come from or the mode does not exist.
+int orc_sift_run_describe(void* run, int n, const int32_t* octave, const int32_t* index, const float* fsize,
+                          const float* frow, const float* fcol, const float* ori, int mode, int ulps, int dir,
+                          uint32_t seed, const int64_t* drop, void* out, int32_t* totals) {
+  SiftRun* R = static_cast<SiftRun*>(run);
+  if (mode < 0 || mode > 3 || (mode == 3 && !drop)) return -1;
+  for (int i = 0; i < n; ++i)
+    if (!run_grads(R, octave[i], index[i])) return -1;
+  for (int i = 0; i < n; ++i) {
+    const std::pair<Img, Img>& g = *run_grads(R, octave[i], index[i]);
+    int total;
+    if (mode == 1) {
+      total = describe_key<double>(static_cast<double*>(out) + (size_t)128 * i, &R->pyr.gaus[octave[i]][index[i]], g.first,
+                                   g.second, fsize[i], frow[i], fcol[i], ori[i]);
+    } else {
+      Tweak tw;
+      if (mode == 2) {
+        tw.ulps = ulps;
+        tw.dir = dir;
+        tw.seed = seed;
+        tw.key = (uint32_t)i;
+      }
+      if (mode == 3) tw.drop = (long)drop[i];
+      total = describe_key<float>(static_cast<float*>(out) + (size_t)128 * i, nullptr, g.first, g.second, fsize[i], frow[i],
+                                  fcol[i], ori[i], mode == 0 ? nullptr : &tw);
+    }
+    if (totals) totals[i] = total;
+  }
+  return 0;
+}
+
+// Mode drop for the samples an off-by-one in a window row's interval loses: for every key and every window row with a
+// selected sample, the row's first (which 0) and -- where the row has two or more -- last (which 1) selected sample is
+// left out in turn, and the result compared with the key's f64 descriptor `ref` [n][128]: tried / detected [n][2] count
+// the samples and those with max |drop - f64| > bar[key].  Returns 0, -1 as above.
+int orc_sift_run_drop_row_ends(void* run, int n, const int32_t* octave, const int32_t* index, const float* fsize,
+                               const float* frow, const float* fcol, const float* ori, const double* ref,
+                               const double* bar, int32_t* tried, int32_t* detected) {
+  SiftRun* R = static_cast<SiftRun*>(run);
+  for (int i = 0; i < n; ++i)
+    if (!run_grads(R, octave[i], index[i])) return -1;
+  std::vector<int> rows;
+  float d[128];
+  for (int i = 0; i < n; ++i) {
+    const std::pair<Img, Img>& g = *run_grads(R, octave[i], index[i]);
+    rows.clear();
+    describe_key<float>(d, nullptr, g.first, g.second, fsize[i], frow[i], fcol[i], ori[i], nullptr, &rows);
+    tried[2 * i] = tried[2 * i + 1] = detected[2 * i] = detected[2 * i + 1] = 0;
+    const long m = (long)rows.size();
+    for (long t = 0; t < m; ++t) {
+      const bool first = t == 0 || rows[t - 1] != rows[t], last = t + 1 == m || rows[t + 1] != rows[t];
+      if (!first && !last) continue;
+      const int which = first ? 0 : 1;
+      Tweak tw;
+      tw.drop = t;
+      describe_key<float>(d, nullptr, g.first, g.second, fsize[i], frow[i], fcol[i], ori[i], &tw);
+      double worst = 0;
+      for (int e = 0; e < 128; ++e) worst = std::max(worst, std::fabs((double)d[e] - ref[(size_t)128 * i + e]));
+      ++tried[2 * i + which];
+      if (worst > bar[i]) ++detected[2 * i + which];
+    }
+  }
+  return 0;
+}
 
 void* orc_sift_run(const uint8_t* gray, int w, int h, int double_size) {
   SiftRun* R = new SiftRun;

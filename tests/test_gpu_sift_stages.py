@@ -6,7 +6,11 @@ tests/test_sift_stages_cpu.py).
 Prepare, the blur chain, DoG, the 2:1 subsample, the extremum scan, the edge test, the quadratic fit and the
 first-claim rule contain no transcendental function on the device (the Gaussian taps come from the host's libm), so
 (a), (b), (d) and (e) hold bit for bit; only orient_kernel's powf / expf / atan2f may differ from libm, and (c) says by
-how much.  tests/test_gpu_sift.py keeps the final list (order, descriptors) with its statistical bars."""
+how much.  (f) holds the last stage, describe_kernel: every descriptor -- of every key of every input, of several keys
+per workgroup, and of synthetic keys at the window's, the orientation's and the 256-sample step's edges run through
+mh_sift_debug_describe -- against the float64 descriptor of the same key, within a per-key bar derived from rounding
+alone (a few 1e-6; a descriptor that lost one sample misses it: tests/test_sift_stages_cpu.py).  tests/test_gpu_sift.py
+keeps its statistical bars on the end-to-end list (count, order, pairing with the reference's keypoints)."""
 import os
 
 import numpy as np
@@ -395,3 +399,238 @@ def test_blur_variants_equal_the_oracles_blur(ctx, src_name):
             ctx.sift_debug_blur(variant, src, 1.0, **kw)
     with pytest.raises(capi.MhError, match="variant"):
         ctx.sift_debug_blur(ROWS_COLS, src, 8.0)          # 65 taps: more than the kernels' tap array holds
+
+
+# ---- (f) descriptors ----------------------------------------------------------------------------------------------
+# describe_kernel does make_key's operations in make_key's order; only sinf, cosf, expf and atan2f may differ from libm.
+# So a device descriptor's distance from the float64 descriptor of the SAME key (orclib.SiftRun.describe, mode f64: the
+# float32 tests select the samples, everything after that in double) is the oracle's own rounding plus the effect of
+# transcendental results at most FSIZE_ULP_BOUND floats away: per key
+#     bar = 2 (e_ref + e_pert) + 2^-23        (SiftRun.descriptor_bar; derivation and measured figures -- median 1.3e-6,
+#                                              largest 3.4e-6 -- in tests/test_sift_stages_cpu.py)
+# which a descriptor that lost ONE sample misses (checked there on the CPU for every key of every input).  Every key is
+# held to it: no pairing, no percentile, none left out.
+F32 = np.float32
+
+
+def _window_side(fsize):
+    """2 win + 1 of make_key's window: win = (int)(3 fSize sqrt2 5 / 2 + 0.5) in float32, as the kernel computes it."""
+    return 2 * int(F32(F32(F32(F32(F32(3.0) * F32(fsize)) * F32(1.4142136)) * F32(5.0)) * F32(0.5)) + F32(0.5)) + 1
+
+
+def _by_order(keys):
+    """The output order: place i = the key with i keys of larger `order` (generation order reversed)."""
+    return keys[np.argsort(keys["order"], kind="stable")[::-1]]
+
+
+def _check_descriptors(run, keys, dev, label, names=None):
+    """max |device - f64| <= bar for EVERY key (keys in the device's output order); -> the number of descriptors that are
+    bit-identical to the oracle's float32 ones, and the largest error / bar."""
+    q = run.descriptor_bar(keys, FSIZE_ULP_BOUND)
+    assert dev.shape == q["f64"].shape and np.all(np.isfinite(q["f64"])) and np.all(q["totals"] > 0), label
+    err = np.abs(dev.astype(np.float64) - q["f64"])
+    worst = err.max(axis=1)
+    bad = np.flatnonzero(~(worst <= q["bar"]))                        # (a NaN fails)
+    lines = []
+    for i in bad[:8]:
+        k, e = keys[i], int(np.argmax(err[i])) if np.all(np.isfinite(err[i])) else int(np.argmax(~np.isfinite(err[i])))
+        lines.append(
+            f"{label} key {i}{' [' + names[i] + ']' if names else ''}: octave {k['octave']} index {k['index']} row {k['frow']!r} "
+            f"column {k['fcol']!r} fsize {k['fsize']!r} ori {k['ori']!r}, window side {_window_side(k['fsize'])}, "
+            f"{q['totals'][i]} samples; worst entry (cell row {e // 32}, cell column {e // 8 % 4}, bin {e % 8}): device "
+            f"{dev[i, e]!r} f32 {q['f32'][i, e]!r} f64 {q['f64'][i, e]!r}; error {worst[i]:.3g} > bar {q['bar'][i]:.3g} "
+            f"(e_ref {q['e_ref'][i]:.3g}, e_pert {q['e_pert'][i]:.3g})")
+    assert len(bad) == 0, f"{len(bad)} of {len(keys)} descriptors beyond their bar\n" + "\n".join(lines)
+    same = int(np.sum(np.all(_u32(dev) == _u32(q["f32"]), axis=1)))
+    return same, float(np.max(worst / q["bar"]))
+
+
+@pytest.mark.parametrize("name", list(INPUTS))
+def test_descriptors_of_every_key(ctx, oracle, name):
+    """(f1) The extraction's own outputs: place i is the key with i keys of larger order, its position / scale /
+    orientation are fscale (fcol, frow), fscale fsize and ori as uint32, and its descriptor lies within the key's bar of
+    the float64 descriptor of that very key (the device's fsize and ori, whatever they are)."""
+    gray, dbl, run = oracle(name)
+    xy, so, d = ctx.sift(gray, double_size=dbl)
+    keys = _by_order(ctx.sift_debug_keys())
+    assert len(keys) == len(d) >= 0.99 * MIN_KEYS[name], (name, len(keys), len(d))
+    fs = run.fscale(keys["octave"])
+    assert np.array_equal(_u32(xy), _u32(np.stack([fs * keys["fcol"], fs * keys["frow"]], 1))), name
+    assert np.array_equal(_u32(so), _u32(np.stack([fs * keys["fsize"], keys["ori"]], 1))), name
+    same, ratio = _check_descriptors(run, keys, d, name)
+    print(f"\n[sift descriptors] {name}: {len(keys)} keys, {same} descriptors bit-identical to the oracle's float32 ones, "
+          f"largest error {ratio:.3g} of its bar")
+
+
+def test_describe_hook_several_keys_per_workgroup(ctx, oracle):
+    """(f2) A workgroup that describes more than one key (the ki += gridDim.x loop: in production only batches of five
+    or more images with more than 1 024 keys in one of them): 64 keys of gray0 with the window sizes alternating largest,
+    smallest, ... on 1, 3 and 64 workgroups are equal as bytes and within the bar; the mosaic's keys on the batch grid
+    (1 024 workgroups, two or three keys each) are the extraction's own outputs as bytes."""
+    gray, dbl, run = oracle("gray0")
+    ctx.sift(gray, double_size=dbl)
+    real = ctx.sift_debug_keys()
+    by_size = real[np.argsort(real["fsize"], kind="stable")]
+    n = len(by_size)
+    alt = np.stack([by_size[::-1][:32], by_size[:32]], 1).reshape(-1)          # largest, smallest, 2nd largest, ...
+    assert len(alt) == 64 and n >= 64 and _window_side(alt["fsize"][0]) >= 2 * _window_side(alt["fsize"][1])
+    outs = {wg: ctx.sift_debug_describe(alt, workgroups=wg) for wg in (1, 3, 64)}
+    for wg in (3, 64):
+        for a, b, what in zip(outs[wg], outs[1], ("xy", "scale_ori", "descriptors")):
+            assert a.tobytes() == b.tobytes(), f"{what} on {wg} workgroups differ from one workgroup's"
+    k = _by_order(alt)
+    fs = run.fscale(k["octave"])
+    assert np.array_equal(_u32(outs[1][0]), _u32(np.stack([fs * k["fcol"], fs * k["frow"]], 1)))
+    assert np.array_equal(_u32(outs[1][1]), _u32(np.stack([fs * k["fsize"], k["ori"]], 1)))
+    _check_descriptors(run, k, outs[1][2], "gray0, 64 keys on one workgroup")
+    # the hook left the extraction's keys alone
+    assert ctx.sift_debug_keys().tobytes() == real.tobytes()
+
+    gray, dbl, run = oracle("mosaic")
+    xy, so, d = ctx.sift(gray, double_size=dbl)
+    keys = ctx.sift_debug_keys()
+    assert len(keys) == len(d) > 1536
+    got = ctx.sift_debug_describe(keys, workgroups=1024)
+    for a, b, what in zip(got, (xy, so, d), ("xy", "scale_ori", "descriptors")):
+        assert a.tobytes() == b.tobytes(), f"mosaic: {what} on 1 024 workgroups differ from the extraction's"
+    assert ctx.sift_debug_keys().tobytes() == keys.tobytes()
+
+
+def test_describe_hook_refuses_what_it_cannot_run(ctx, oracle):
+    gray, dbl, run = oracle("crop97x131_und")
+    fresh = capi.Context(0)
+    try:
+        with pytest.raises(capi.MhError):                                     # no extraction yet
+            fresh.sift_debug_describe(np.zeros(1, capi.SIFT_KEY_DTYPE))
+    finally:
+        fresh.close()
+    ctx.sift(gray, double_size=dbl)
+    keys = ctx.sift_debug_keys()
+    assert len(keys) >= 2
+    ctx.sift_debug_describe(keys[:2])
+    with pytest.raises(capi.MhError):
+        ctx.sift_debug_describe(keys[:2], slot=1)
+    with pytest.raises(capi.MhError):
+        ctx.sift_debug_describe(keys[:0])
+    with pytest.raises(capi.MhError):
+        ctx.sift_debug_describe(keys[:2], workgroups=-1)
+    for field, value in (("octave", len(run.octaves)), ("octave", -1), ("index", 0), ("index", 4), ("order", keys["order"][0]),
+                         ("fsize", 0.0), ("fsize", np.nan), ("ori", np.inf)):
+        k = keys[:2].copy()
+        k[field][1] = value
+        with pytest.raises(capi.MhError):
+            ctx.sift_debug_describe(k)
+
+
+# Keys found by search on the host with desc_row_interval (moped_amd/csrc/sift_rows.h, as tests/native/sift_rows_check.cpp
+# builds it) on a 119 x 159 level -- octave 3 of a doubled 640 x 480 frame: the number of samples describe_kernel WALKS (the
+# sum of the rows' intervals; a step takes 256 of them, a wavefront 64) and, of those, the ones KeySample's tests select.
+#   (fsize, frow, fcol, ori)                                 walked  selected  window side
+STEP_KEYS = [
+    ((2.03125, 130.671875, 163.0, -0.607421875),          #      40        21           45   one wavefront, not full
+     "walk 40"),
+    ((1.640625, 129.28125, 117.890625, -1.361328125),     #      63        41           35   one lane short of a wavefront
+     "walk 63"),
+    ((3.078125, -7.609375, 169.015625, 2.98828125),       #     255       220           67   one sample short of a step
+     "walk 255"),
+    ((1.453125, 119.984375, 130.25, 0.880859375),         #     256       201           31   exactly one step
+     "walk 256"),
+    ((1.875, -1.765625, 156.625, -2.90234375),            #     257       213           41   one sample in the second step
+     "walk 257"),
+    ((1.484375, 112.328125, 24.34375, 2.166015625),       #     511       420           33
+     "walk 511"),
+    ((3.75, 119.921875, -11.46875, 1.3046875),            #     512       455           81
+     "walk 512"),
+    ((1.5, 35.90625, 152.28125, 2.46875),                 #     513       422           33
+     "walk 513"),
+    ((4.03125, 125.953125, 1.265625, -1.603515625),       #     767       712           87
+     "walk 767"),
+    ((2.0, 79.625, 35.3125, -1.5556640625),               #   1 023       900           43
+     "walk 1023"),
+    ((3.40625, 125.5, 82.984375, -0.4560546875),          #   1 024       907           73
+     "walk 1024"),
+    ((2.1875, 24.203125, 146.203125, -0.0908203125),      #   1 025       943           47
+     "walk 1025"),
+    ((4.390625, 80.53125, 161.03125, -0.9716796875),      #   2 047     1 881           95
+     "walk 2047"),
+    ((3.5, 50.625, 115.75, 2.462890625),                  #   3 071     2 758           75
+     "walk 3071"),
+]
+KPI = F32(3.141592654)
+
+
+def _orientations():
+    """What AssignOriHist can emit -- (i + peak) 2 pi / 36 + (pi / 36 - pi) for bins i = 0..35 and peak in [-0.5, 0.5], in
+    float32 -- at the ends of that range, and 0, +-pi / 2; each with its two float neighbours."""
+    forimult = F32(F32(2) * KPI / F32(36.0))
+    foriadd = F32(F32(F32(0.5) * F32(2) * KPI / F32(36.0)) - KPI)
+    ends = [F32(F32(F32(-0.5) * forimult) + foriadd), F32(F32(F32(35.5) * forimult) + foriadd)]
+    assert abs(float(ends[0]) + np.pi) < 1e-6 and abs(float(ends[1]) - np.pi) < 1e-6
+    out = []
+    for v in ends + [F32(0.0), F32(KPI / F32(2)), F32(-KPI / F32(2))]:
+        out += [np.nextafter(v, F32(-np.inf)), v, np.nextafter(v, F32(np.inf))]
+    return out
+
+
+def _synthetic_keys(octaves, with_step_keys):
+    """(names, keys) on the first octave of at most 160 columns: SIFT_KEY_DTYPE with descending `order` (the output order
+    is the list's order)."""
+    o = next(i for i, (r, c) in enumerate(octaves) if c <= 160)
+    rows, cols = octaves[o]
+    index = 1 + o % 3
+    mr, mc = rows // 2 + 0.25, cols // 2 - 0.25
+    # fsize = 1.6 powf(2, (index + X0) / 3) with index in 1..3 and |X0| <= 1.5 (InterpKeyPoint's final test)
+    smallest, largest = F32(1.6) * F32(2.0) ** F32(-0.5 / 3), F32(1.6) * F32(2.0) ** F32(1.5)
+    assert (_window_side(smallest), _window_side(largest)) == (31, 97)    # "side <= 97" in describe_kernel's comment
+    items = []
+    for a in _orientations():                                             # bin 7 wrapping to bin 0, the while wraps
+        items.append((f"ori {a!r}", 2.0, mr, mc, a))
+    below = lambda v: float(np.nextafter(F32(v), F32(-np.inf)))
+    for label, fr, fc in (
+            ("top", 2.25, mc), ("bottom", rows - 3.25, mc), ("left", mr, 2.25), ("right", mr, cols - 3.25),
+            ("top left", 2.25, 2.25), ("top right", 2.25, cols - 3.25), ("bottom left", rows - 3.25, 2.25),
+            ("bottom right", rows - 3.25, cols - 3.25),
+            ("rowstart 0", 0.25, mc), ("colstart cols - 1", mr, cols - 1.25), ("rowstart 0, colstart cols - 1", 0.25, cols - 1.25),
+            ("frow .5", rows // 2 + 0.5, mc), ("frow just below .5", below(rows // 2 + 0.5), mc),
+            ("fcol .5", mr, cols // 2 + 0.5), ("fcol just below .5", mr, below(cols // 2 + 0.5))):
+        items.append((label, 2.0, fr, fc, 0.3))
+    # sizes: the key stage's smallest and largest; 5.9 = the widest window the interval walk takes (side 127 <= DESC_MAX_SIDE);
+    # 6.0 and 7.52 = the walk over the whole square by division -- ONLY this hook reaches it: no shipped key is that large
+    for fsize, side in ((smallest, 31), (largest, 97), (5.9, 127), (6.0, 129), (7.52, 161)):
+        assert _window_side(fsize) == side
+        items.append((f"side {side}", fsize, mr, mc, -1.1))
+        items.append((f"side {side} at the corner", fsize, rows - 3.25, 2.25, 2.0))
+    if with_step_keys:
+        assert (rows, cols) == (119, 159)
+        items += [(label, *k) for k, label in STEP_KEYS]
+    keys = np.zeros(len(items), capi.SIFT_KEY_DTYPE)
+    keys["octave"], keys["index"] = o, index
+    keys["order"] = np.arange(len(items), 0, -1)
+    for f, col in (("fsize", 1), ("frow", 2), ("fcol", 3), ("ori", 4)):
+        keys[f] = [it[col] for it in items]
+    return [it[0] for it in items], keys
+
+
+@pytest.mark.parametrize("name", ["gray0", "crop8x8", "crop97x131_und"])
+def test_describe_hook_synthetic_keys_at_the_edges(ctx, oracle, name):
+    """(f3) Keys the bundled frames need not contain, through the hook on this input's pyramid (crop8x8: 14 x 14, every
+    window larger than the image), each within its bar, on the production grid and with two workgroups for all of them:
+    orientations at the ends of AssignOriHist's range and on the axes, windows cut by every side and corner, rowstart 0,
+    colstart cols - 1, centre fractions of .5, the smallest and largest size, walk totals at the edges of a 256-sample
+    step, and the whole-square walk of windows wider than DESC_MAX_SIDE."""
+    gray, dbl, run = oracle(name)
+    ctx.sift(gray, double_size=dbl)
+    names, keys = _synthetic_keys(run.octaves, with_step_keys=name == "gray0")
+    fs = run.fscale(keys["octave"])
+    first = None
+    for wg in (0, 2):
+        xy, so, d = ctx.sift_debug_describe(keys, workgroups=wg)
+        assert np.array_equal(_u32(xy), _u32(np.stack([fs * keys["fcol"], fs * keys["frow"]], 1)))
+        assert np.array_equal(_u32(so), _u32(np.stack([fs * keys["fsize"], keys["ori"]], 1)))
+        if first is None:
+            first = d
+            same, ratio = _check_descriptors(run, keys, d, f"{name}, production grid", names)
+            print(f"\n[sift descriptors] {name}: {len(keys)} synthetic keys, {same} bit-identical to the oracle's float32 "
+                  f"ones, largest error {ratio:.3g} of its bar")
+        else:
+            assert d.tobytes() == first.tobytes(), f"{name}: two workgroups give other descriptors than {len(keys)}"
