@@ -773,6 +773,61 @@ int mh_depth_map_from_raw_batch_dev(mh_ctx* ctx, const void* const* raw_dev, con
  * A frame's map that lived in those buffers is switched off: set it again.  Synchronous. */
 int mh_depth_map_from_raw_host(mh_ctx* ctx, const void* raw_host, const mh_raw_depth* raw, const float K[4],
                                float* depth_xyzn_host, int width, int height);
+
+/* The 8-bit gray image from what a camera delivers: the first line of moped3d's image callback,
+ * cv_bridge::toCvCopy(iMsg, "mono8") (moped3d/moped3d.cpp:249), on the device.  A pixel is read at
+ * raw + offset + y * row_stride + x * bytes-per-pixel; the output is a packed [height][width] gray image.  Neither pointer
+ * needs any alignment, offsets and strides are arbitrary byte counts.  The formats carry the names of ROS's
+ * sensor_msgs/image_encodings.h.  The arithmetic restates what OpenCV 2.x cvtColor does for 8-bit data, written WITHOUT
+ * OpenCV at hand and therefore UNPINNED (like the resize of mh_depth_map_from_raw_*); the project's definition is
+ * tests/image_gray_ref.py, integers only, and the kernel gives its bytes (tests/test_gpu_image_gray.py).  With R2Y = 4899,
+ * G2Y = 9617, B2Y = 1868 (sum 2^14), unsigned 32-bit sums:
+ *   MH_IMAGE_GRAY8                 the byte itself: the call only removes strides and offsets
+ *   MH_IMAGE_BGR8 / RGB8 / BGRA8 / RGBA8
+ *                                  (R2Y R + G2Y G + B2Y B + 8192) >> 14; alpha is ignored
+ *   MH_IMAGE_BAYER_RGGB8 / BGGR8 / GBRG8 / GRBG8
+ *                                  the four letters are the top-left 2 x 2 sites row by row.  Interior pixels (1 <= x <=
+ *                                  w - 2, 1 <= y <= h - 2), p the site's byte, C() a colour's coefficient: at an R or B
+ *                                  site of own colour o and opposite colour q
+ *                                    (C(q) (4 diagonal neighbours) + G2Y (4 edge neighbours) + 4 C(o) p + 32768) >> 16,
+ *                                  at a G site with ch the colour of (x + 1, y) and cv that of (x, y + 1)
+ *                                    (C(ch) (left + right) + C(cv) (up + down) + 2 G2Y p + 16384) >> 15.
+ *                                  Columns 0 and w - 1 copy columns 1 and w - 2, then rows 0 and h - 1 copy rows 1 and
+ *                                  h - 2.  Bayer images are at least 3 x 3.
+ * (moped2's node, moped2/moped.cpp:175-204, converts to BGR8 and copies `width` bytes of every three-channel row: a defect,
+ * not reproduced.)
+ * MH_ERR_ARG before any launch, the context unchanged, mh_last_error naming the argument: a null pointer, an unknown
+ * format, a size <= 0, Bayer below 3 x 3, a negative offset, row_stride < width * bytes-per-pixel, an extent (offset +
+ * (height - 1) row_stride + width * bytes-per-pixel) or width * height beyond INT_MAX, n outside 1 .. MH_MAX_BATCH, two
+ * images of a batch writing the same (or overlapping) output, an output that overlaps its own raw extent or another
+ * image's.  Nothing outside the extent is read, nothing outside the width * height output bytes is written. */
+enum { MH_IMAGE_GRAY8 = 0, MH_IMAGE_BGR8, MH_IMAGE_RGB8, MH_IMAGE_BGRA8, MH_IMAGE_RGBA8,
+       MH_IMAGE_BAYER_RGGB8, MH_IMAGE_BAYER_BGGR8, MH_IMAGE_BAYER_GBRG8, MH_IMAGE_BAYER_GRBG8 };
+typedef struct mh_raw_image {
+  int32_t format, width, height;
+  int32_t row_stride, offset;   /* bytes */
+} mh_raw_image;
+/* raw_dev -> gray_dev [height][width], both on the device; asynchronous on the context's stream (:249). */
+int mh_image_gray_dev(mh_ctx* ctx, const void* raw_dev, const mh_raw_image* fmt, uint8_t* gray_dev);
+/* n <= MH_MAX_BATCH raw buffers of one description -> a gray image each, ONE launch (the image index is in the grid): a
+ * 640 x 480 conversion is a stream of 1.2 MB and costs its launch, so a batch pays it once (:249 per frame of a batch).
+ * Every output is byte for byte the single call's.  Pointer arrays on the host; asynchronous. */
+int mh_image_gray_batch_dev(mh_ctx* ctx, const void* const* raw_dev, const mh_raw_image* fmt, uint8_t* const* gray_dev, int n);
+/* The same for a host that holds the camera's buffer (:249 as one call): its extent goes into a context-owned buffer, the
+ * gray image comes back into gray_host [height][width].  Synchronous. */
+int mh_image_gray_host(mh_ctx* ctx, const void* raw_host, const mh_raw_image* fmt, uint8_t* gray_host);
+/* The frames' images as the camera delivers them (:249 in front of processImages): while a format is set, the image
+ * pointers of mh_frame_enqueue_image, mh_frame_enqueue_image_batch, mh_frame_enqueue_images and
+ * mh_frame_enqueue_images_batch are raw buffers of that description (their width and height must be the format's, else
+ * MH_ERR_ARG).  The images of a call are converted by ONE launch into a staging buffer of the context -- its own, not the
+ * one undistortion writes --, then comes mh_frame_set_undistort[_images] if it is on, then FEAT: bit for bit
+ * mh_image_gray_batch_dev followed by the same call with no format set.  mh_frame_run_kinect_host and
+ * mh_frame_run_kinect_raw_host then read gray_host as such a raw buffer and upload its extent instead of width * height
+ * bytes; with raw depth that is the node's whole callback (:240-338) in one call.  fmt NULL = packed 8-bit gray, the default;
+ * the description is copied.  The teaching calls (mh_db_splice_image*, mh_db_splice_view*, mh_db_append_view) and
+ * mh_sift_extract* keep taking gray whatever is set here: their callers run mh_image_gray_dev first. */
+int mh_frame_set_image_format(mh_ctx* ctx, const mh_raw_image* fmt);
+
 /* moped3d's rules on which features and matches reach CLUSTER, applied on the device inside the
  * frame (they need the depth map: mh_frame_set_depth_image):
  *  - DEPTHFILTER_CPU (moped3d/libmoped/src/depthfilter/DEPTHFILTER_CPU.hpp:117-254), ToFilter = 1

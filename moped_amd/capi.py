@@ -189,6 +189,32 @@ def make_raw_depth(fmt, width, height, elem_stride=None, row_stride=None, offset
     return mh_raw_depth(int(fmt), int(width), int(height), int(elem_stride), int(row_stride), int(offset))
 
 
+# MH_IMAGE_*: what a camera delivers, under the names of ROS's sensor_msgs/image_encodings.h
+(IMAGE_GRAY8, IMAGE_BGR8, IMAGE_RGB8, IMAGE_BGRA8, IMAGE_RGBA8, IMAGE_BAYER_RGGB8, IMAGE_BAYER_BGGR8, IMAGE_BAYER_GBRG8,
+ IMAGE_BAYER_GRBG8) = range(9)
+IMAGE_BPP = {IMAGE_GRAY8: 1, IMAGE_BGR8: 3, IMAGE_RGB8: 3, IMAGE_BGRA8: 4, IMAGE_RGBA8: 4, IMAGE_BAYER_RGGB8: 1,
+             IMAGE_BAYER_BGGR8: 1, IMAGE_BAYER_GBRG8: 1, IMAGE_BAYER_GRBG8: 1}
+
+
+class mh_raw_image(C.Structure):
+    _fields_ = [("format", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("row_stride", C.c_int32),
+                ("offset", C.c_int32)]
+
+
+def make_raw_image(format, w, h, row_stride=None, offset=0) -> mh_raw_image:
+    """What a camera's image buffer looks like: an IMAGE_* format, w x h pixels at offset + y row_stride + x
+    bytes-per-pixel.  Default: packed rows.  (An unknown format keeps whatever row_stride it is given: the library
+    refuses it.)"""
+    if row_stride is None:
+        row_stride = w * IMAGE_BPP.get(format, 1)
+    return mh_raw_image(int(format), int(w), int(h), int(row_stride), int(offset))
+
+
+def raw_image_bytes(fmt: mh_raw_image) -> int:
+    """The bytes of the buffer a description speaks of: offset + (height - 1) row_stride + width bytes-per-pixel."""
+    return fmt.offset + (fmt.height - 1) * fmt.row_stride + fmt.width * IMAGE_BPP.get(fmt.format, 1)
+
+
 def make_filter_depth_params(p):
     """None, an mh_filter_depth_params or (plausible_sq_distance, depth_fraction, min_keypoint_fraction)."""
     if p is None or isinstance(p, mh_filter_depth_params):
@@ -246,6 +272,7 @@ EXPORTS = [
     "mh_frame_set_hulls", "mh_frame_fetch_hulls_slot", "mh_frame_fetch_hulls", "mh_frame_hull_block_stride",
     "mh_frame_fetch_batch_hulls_async",
     "mh_screen_reject_proved", "mh_match_set_accept", "mh_match_prerejected",
+    "mh_image_gray_dev", "mh_image_gray_batch_dev", "mh_image_gray_host", "mh_frame_set_image_format",
 ]
 COMM_ID_BYTES = 128      # MH_COMM_ID_BYTES
 EX2_OBJECTS = 62         # MH_EX2_OBJECTS
@@ -407,6 +434,12 @@ def load():
         L.mh_frame_run_kinect_raw_host.argtypes = [vp, vp, vp, rd, vp, vp, i32, i32, i32, i32, C.POINTER(mh_cam),
                                                    C.POINTER(mh_frame_params), i32, i32, i32, f32, f32, C.c_uint64, vp, i32,
                                                    C.POINTER(C.c_int32), vp]
+    if hasattr(L, "mh_image_gray_dev"):   # (the same)
+        ri = C.POINTER(mh_raw_image)
+        L.mh_image_gray_dev.argtypes = [vp, vp, ri, vp]
+        L.mh_image_gray_batch_dev.argtypes = [vp, C.POINTER(vp), ri, C.POINTER(vp), i32]
+        L.mh_image_gray_host.argtypes = [vp, vp, ri, vp]
+        L.mh_frame_set_image_format.argtypes = [vp, ri]
     L.mh_db_debug_screen.argtypes = [vp, vp]
     L.mh_db_debug_route.argtypes = [vp, i32]
     L.mh_db_edit_ms.argtypes = [vp, C.POINTER(f32)]
@@ -1334,6 +1367,56 @@ class Context:
                  "mh_depth_map_from_raw_host")
         return out
 
+    # ---- the gray image from what a camera delivers (moped3d/moped3d.cpp:249) ----
+    def image_gray_dev(self, raw_ptr, fmt: mh_raw_image, gray_ptr):
+        """A device buffer as `fmt` (make_raw_image) describes it -> the packed device gray image [height, width];
+        asynchronous."""
+        self._ck(self.L.mh_image_gray_dev(self.h, C.c_void_p(raw_ptr) if raw_ptr else None,
+                                          C.byref(fmt) if fmt is not None else None,
+                                          C.c_void_p(gray_ptr) if gray_ptr else None), "mh_image_gray_dev")
+
+    def image_gray_batch_dev(self, raw_ptrs, fmt: mh_raw_image, gray_ptrs):
+        """len(raw_ptrs) raw buffers of one description -> a gray image each, one launch; asynchronous."""
+        n = len(raw_ptrs)
+        if len(gray_ptrs) != n:
+            raise ValueError("one gray image per raw buffer")
+        r = (C.c_void_p * max(n, 1))(*raw_ptrs)
+        g = (C.c_void_p * max(n, 1))(*gray_ptrs)
+        self._ck(self.L.mh_image_gray_batch_dev(self.h, r, C.byref(fmt) if fmt is not None else None, g, n),
+                 "mh_image_gray_batch_dev")
+
+    def image_gray(self, raw_buf, fmt: mh_raw_image):
+        """The same on a host buffer (any contiguous array holding the bytes `fmt` describes) -> gray [height, width]."""
+        b = np.ascontiguousarray(raw_buf)
+        if b.nbytes < raw_image_bytes(fmt):
+            raise ValueError("the buffer is shorter than the description's extent")
+        out = np.zeros((max(fmt.height, 0), max(fmt.width, 0)), np.uint8)
+        self._ck(self.L.mh_image_gray_host(self.h, _ptr(b), C.byref(fmt), _ptr(out)), "mh_image_gray_host")
+        return out
+
+    def frame_set_image_format(self, fmt):
+        """The image pointers of frame_enqueue_image[_batch] / frame_enqueue_images[_batch] (and the gray arrays of
+        frame_run_kinect[_raw]_host) are raw buffers as `fmt` (make_raw_image) describes them from now on: converted by
+        one launch per call in front of undistortion and FEAT.  None = packed 8-bit gray, the default."""
+        self._ck(self.L.mh_frame_set_image_format(self.h, C.byref(fmt) if fmt is not None else None),
+                 "mh_frame_set_image_format")
+        self._image_fmt = None if fmt is None else mh_raw_image(fmt.format, fmt.width, fmt.height, fmt.row_stride, fmt.offset)
+
+    def _host_image(self, gray, size):
+        """The `gray` argument of frame_run_kinect[_raw]_host -> (contiguous uint8 array, w, h).  While a format is set the
+        array is the camera's buffer: it must hold the format's extent, which is what the library copies from it."""
+        g = np.ascontiguousarray(gray, np.uint8)
+        fmt = getattr(self, "_image_fmt", None)
+        if fmt is None:
+            w, h = size if size is not None else g.shape[::-1]
+            if g.size != w * h:
+                raise ValueError("gray must hold width x height bytes")
+            return g, w, h
+        if g.nbytes < raw_image_bytes(fmt):
+            raise ValueError("the buffer is shorter than the extent of the image format that is set")
+        w, h = size if size is not None else (fmt.width, fmt.height)
+        return g, w, h
+
     def frame_set_depth_image_batch(self, depth_ptrs, fill_ptrs, width, height, kind, alpha=0.5, cauchy_scale=0.1):
         """One depth map (+ distance map, or None for all) per frame of the following batches."""
         n = len(depth_ptrs)
@@ -1611,12 +1694,12 @@ class Context:
 
     def frame_run_kinect_host(self, gray, depth_img, fill_img, K, cam, params: mh_frame_params, seed, fill_scale=8,
                               bilinear=False, double_size=True, max_keypoints=2048, kind=DEPTH_BACKPROJECTION, alpha=0.5,
-                              cauchy_scale=0.1, max_objects=4096):
+                              cauchy_scale=0.1, max_objects=4096, size=None):
         """One Kinect frame from host arrays in one call: gray [h, w] uint8, depth_img [h, w, 4]; fill_scale 0: the maps
-        arrive filled (fill_img [h, w] or None), else DEPTHFILL on the device first.
+        arrive filled (fill_img [h, w] or None), else DEPTHFILL on the device first.  With frame_set_image_format on,
+        `gray` is the camera's raw buffer (at least the format's extent) and size = (w, h), default the format's, its size.
         -> (objects, counts, the depth map and the distance map as the frame used them)."""
-        g = np.ascontiguousarray(gray, np.uint8)
-        h, w = g.shape
+        g, w, h = self._host_image(gray, size)
         d = np.ascontiguousarray(depth_img, np.float32).reshape(h, w, 4).copy()
         if fill_scale:
             f = np.zeros((h, w), np.float32)
@@ -1634,13 +1717,14 @@ class Context:
 
     def frame_run_kinect_raw_host(self, gray, raw_buf, raw: mh_raw_depth, K, cam, params: mh_frame_params, seed,
                                   fill_scale=8, bilinear=False, double_size=True, max_keypoints=2048,
-                                  kind=DEPTH_BACKPROJECTION, alpha=0.5, cauchy_scale=0.1, max_objects=4096, maps_back=True):
+                                  kind=DEPTH_BACKPROJECTION, alpha=0.5, cauchy_scale=0.1, max_objects=4096, maps_back=True,
+                                  size=None):
         """One Kinect frame from what the sensor delivers: gray [h, w] uint8 and the raw depth buffer `raw` describes; the
-        map [h, w, 4] is built on the device (K), then the frame runs as frame_run_kinect_host's does.
+        map [h, w, 4] is built on the device (K), then the frame runs as frame_run_kinect_host's does.  With
+        frame_set_image_format on, `gray` is the camera's raw buffer (at least the format's extent) and size = (w, h), default the format's, its size.
         -> (objects, counts, the depth map and the distance map as the frame used them; None, None without maps_back,
         and no distance map with fill_scale 0)."""
-        g = np.ascontiguousarray(gray, np.uint8)
-        h, w = g.shape
+        g, w, h = self._host_image(gray, size)
         b = np.ascontiguousarray(raw_buf)
         d = np.zeros((h, w, 4), np.float32) if maps_back else None
         f = np.zeros((h, w), np.float32) if maps_back and fill_scale else None

@@ -760,10 +760,13 @@ int mh_frame_enqueue_image(mh_ctx* ctx, const uint8_t* gray_dev, int width, int 
                            int max_keypoints, const mh_cam* cam, const mh_frame_params* prm, uint64_t seed) {
   if (!ctx || !gray_dev || width <= 0 || height <= 0 || max_keypoints <= 0 || !cam || !prm) return MH_ERR_ARG;
   if (int rc_fd = filter_depth_frame_ok(ctx, "mh_frame_enqueue_image", prm)) return rc_fd;
+  if (int rc_if = image_format_frame_ok(ctx, "mh_frame_enqueue_image", width, height)) return rc_if;
   if (int rc_enter = mh::enter(ctx)) return rc_enter;
   const int Q = max_keypoints;
   int rc = prepare_frame(ctx, Q);
   if (rc) return rc;
+  // the camera's image (mh_frame_set_image_format): its gray copy in a staging buffer of its own
+  if ((rc = image_format_stage(ctx, &gray_dev, 1, &gray_dev))) return rc;
   // UNDISTORTED_IMAGE (mh_frame_set_undistort): FEAT reads the remapped copy in the context's staging buffer
   if (ctx->und_on && (rc = undistort_frame(ctx, &gray_dev, 1, width, height, cam->K, &gray_dev))) return rc;
   // FEAT: keypoints straight into the frame's query buffers; their number stays on the device
@@ -800,6 +803,7 @@ int mh_frame_enqueue_image_batch(mh_ctx* ctx, const uint8_t* const* gray_dev, in
     return refuse("the depth rules (mh_frame_set_depth_rules) need a depth map per image: mh_frame_set_depth_image_batch, or "
                   "mh_frame_set_depth_rules(ctx, NULL, NULL) for a batch without them");
   if (int rc_fd = filter_depth_frame_ok(ctx, "mh_frame_enqueue_image_batch", prm)) return rc_fd;
+  if (int rc_if = image_format_frame_ok(ctx, "mh_frame_enqueue_image_batch", width, height)) return rc_if;
   if (int rc_enter = mh::enter(ctx)) return rc_enter;
   const int Q = max_keypoints;
   const bool merge = B > 1 && merged_batch_ok(ctx, prm, true, B);
@@ -809,6 +813,12 @@ int mh_frame_enqueue_image_batch(mh_ctx* ctx, const uint8_t* const* gray_dev, in
   if (!ctx->img_counts) {
     MH_HIP(ctx, ctx->img_counts.ensure(MH_MAX_BATCH, s));
     MH_HIP(ctx, hipMemsetAsync(ctx->img_counts, 0, MH_MAX_BATCH * sizeof(int32_t), s));
+  }
+  // the cameras' images (mh_frame_set_image_format): one launch for the B gray copies, a staging buffer of their own
+  const uint8_t* converted[MH_MAX_BATCH];
+  if (ctx->img_fmt_on) {
+    if ((rc = image_format_stage(ctx, gray_dev, B, converted))) return rc;
+    gray_dev = converted;
   }
   // UNDISTORTED_IMAGE (mh_frame_set_undistort): one remap launch for the B images into the context's staging buffer
   const uint8_t* staged[MH_MAX_BATCH];
@@ -866,6 +876,7 @@ static int enqueue_images(mh_ctx* ctx, const char* who, const uint8_t* const* gr
     return refuse(MH_ERR_ARG, "depth maps / rules / attributes and the linkage clusterer are single-camera");
   if (ctx->imf.und_n && ctx->imf.und_n != n)
     return refuse(MH_ERR_ARG, "mh_frame_set_undistort_images gave coefficients for another number of cameras");
+  if (int rc_if = image_format_frame_ok(ctx, who, width, height)) return rc_if;
   if (int rc_enter = mh::enter(ctx)) return rc_enter;
   // the call points the context's views of the image indices and cameras at its own for its own duration: whatever
   // mh_frame_set_images left is the caller's again afterwards, and a later one-camera frame finds no image index of this one
@@ -893,6 +904,12 @@ static int enqueue_images(mh_ctx* ctx, const char* who, const uint8_t* const* gr
     ctx->cams_view = m.cams;
   }
   hipStream_t s = ctx->stream;
+  // the cameras' images (mh_frame_set_image_format): one launch for the F n gray copies, a staging buffer of their own
+  const uint8_t* converted[MH_MAX_BATCH];
+  if (ctx->img_fmt_on) {
+    if ((rc = image_format_stage(ctx, gray_dev, F * n, converted))) return rc;
+    gray_dev = converted;
+  }
   // UNDISTORTED_IMAGE per camera: one remap launch, every image with the map of its camera (one set of coefficients
   // from mh_frame_set_undistort goes with every camera's K)
   const uint8_t* staged[MH_MAX_BATCH];

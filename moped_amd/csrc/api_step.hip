@@ -250,13 +250,15 @@ int mh_frame_run_kinect_host(mh_ctx* ctx, const uint8_t* gray_host, float* depth
     return MH_ERR_ARG;
   }
   *n_objects = 0;
+  if (int rc_if = image_format_frame_ok(ctx, "mh_frame_run_kinect_host", width, height)) return rc_if;
   if (int rc_enter = mh::enter(ctx)) return rc_enter;
   hipStream_t s = ctx->stream;
   const size_t px = (size_t)width * height;
+  const size_t image_bytes = image_format_bytes(ctx, width, height);   // (mh_frame_set_image_format: the raw extent)
   mh_frame_set_depth_image(ctx, nullptr, nullptr, 0, 0, 0, alpha, 0.f);   // (the own buffers may move)
   if (int rc = ensure_own_depth(ctx, px)) return rc;
-  MH_HIP(ctx, ctx->own_gray.ensure(px, s));
-  MH_HIP(ctx, hipMemcpyAsync(ctx->own_gray, gray_host, px, hipMemcpyHostToDevice, s));
+  MH_HIP(ctx, ctx->own_gray.ensure(image_bytes, s));
+  MH_HIP(ctx, hipMemcpyAsync(ctx->own_gray, gray_host, image_bytes, hipMemcpyHostToDevice, s));
   MH_HIP(ctx, hipMemcpyAsync(ctx->own_depth, depth_xyzn_host, px * 4 * sizeof(float), hipMemcpyHostToDevice, s));
   return kinect_frame_tail(ctx, "mh_frame_run_kinect_host", fill ? nullptr : fill_distance_host, fill ? depth_xyzn_host : nullptr,
                            fill ? fill_distance_host : nullptr, width, height, double_size, max_keypoints, cam, prm,
@@ -278,12 +280,13 @@ int mh_frame_run_kinect_raw_host(mh_ctx* ctx, const uint8_t* gray_host, const vo
     return MH_ERR_ARG;
   }
   *n_objects = 0;
+  if (int rc_if = image_format_frame_ok(ctx, "mh_frame_run_kinect_raw_host", width, height)) return rc_if;
   mh_frame_set_depth_image(ctx, nullptr, nullptr, 0, 0, 0, alpha, 0.f);   // (the own buffers may move)
   if (int rc = depth_map_from_raw_own(ctx, "mh_frame_run_kinect_raw_host", raw_host, raw, cam->K, width, height)) return rc;
   hipStream_t s = ctx->stream;
-  const size_t px = (size_t)width * height;
-  MH_HIP(ctx, ctx->own_gray.ensure(px, s));
-  MH_HIP(ctx, hipMemcpyAsync(ctx->own_gray, gray_host, px, hipMemcpyHostToDevice, s));
+  const size_t image_bytes = image_format_bytes(ctx, width, height);   // (mh_frame_set_image_format: the raw extent)
+  MH_HIP(ctx, ctx->own_gray.ensure(image_bytes, s));
+  MH_HIP(ctx, hipMemcpyAsync(ctx->own_gray, gray_host, image_bytes, hipMemcpyHostToDevice, s));
   return kinect_frame_tail(ctx, "mh_frame_run_kinect_raw_host", nullptr, depth_xyzn_host, fill ? fill_distance_host : nullptr,
                            width, height, double_size, max_keypoints, cam, prm, fill_scale, bilinear, kind, alpha,
                            cauchy_scale, seed, objects_host, max_objects, n_objects, counts);

@@ -289,6 +289,11 @@ struct mh_ctx {
   mh::DevBuf<float> own_fill;
   mh::DevBuf<uint8_t> own_gray;   // device copy of a host gray image (mh_frame_run_kinect_host)
   mh::DevBuf<unsigned char> own_raw;   // device copy of a host's raw sensor depth (mh_depth_map_from_raw_host)
+  // the frames' images as the camera delivers them (mh_frame_set_image_format; image_gray.hip)
+  bool img_fmt_on = false;
+  mh_raw_image img_fmt = {};
+  mh::DevBuf<uint8_t> img_stage;       // the converted gray images of the call in flight (not undistortion's staging)
+  mh::DevBuf<unsigned char> img_raw;   // device copy of a host's raw image (mh_image_gray_host)
   mh::DevBuf<float> lk_scratch;
   mh::DevBuf<unsigned char> df_buf;   // mh_depth_fill[_batch]: [status words | per frame: downscaled depths, downscaled distances]
   int df_mode = 0;                    // mh_depth_fill_set_mode (MH_DEPTH_FILL_REPLAY); LEVELS: [status words | stats | per frame: depthfill.hip]
@@ -403,6 +408,13 @@ int undistort_frame(mh_ctx* ctx, const uint8_t* const* gray_dev, int n, int widt
                     const uint8_t** staged);
 int sift_into_batch(mh_ctx* ctx, const uint8_t* const* gray_dev, int n, int width, int height, int double_size, int cap,
                     float* desc_dev, float* xy_dev, int32_t* count_words);
+// image_gray.hip, while mh_frame_set_image_format is on (off: both MH_OK, nothing done).  image_format_frame_ok: the
+// frame's size is the format's, else MH_ERR_ARG with `who` -- asked before anything of the context changes.
+// image_format_stage: the n raw device images of a call converted by one launch on the context's stream into its staging
+// buffer; staged[f] = image f's gray copy (staged may be raw_dev itself).  image_format_bytes: what a host image spans.
+int image_format_frame_ok(mh_ctx* ctx, const char* who, int width, int height);
+int image_format_stage(mh_ctx* ctx, const uint8_t* const* raw_dev, int n, const uint8_t** staged);
+size_t image_format_bytes(const mh_ctx* ctx, int width, int height);
 // undistort.hip: the same for a rig -- image f is camera f % n_cams' and gets the map of (cams[..].K, dist[..])
 int undistort_frame_images(mh_ctx* ctx, const uint8_t* const* gray_dev, int n, int n_cams, int width, int height,
                            const mh_cam* cams, const float (*dist)[4], const uint8_t** staged);

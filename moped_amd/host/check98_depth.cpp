@@ -11,4 +11,5 @@ namespace std { using tr1::shared_ptr; }
 #include "DEPTHMAP_PROP_HIP.hpp"
 #include "FRAME_RESIDENT_3D_HIP.hpp"
 #include "KINECT_DEPTHMAP_HIP.hpp"
+#include "SENSOR_IMAGE_HIP.hpp"
 int main() { return 0; }

@@ -452,7 +452,8 @@ class FramePipeline:
                        double_size: bool = True, keep=None):
         """ONE frame seen by len(gray_ptrs) cameras (Ks [n,4], cams [n,7]): 8-bit device images of one size in, objects
         out (fetch), the keypoint counts never leave the device.  The slot's context must have room for
-        n * max_keypoints queries.  `keep`: the images' tensors, held until the slot's next enqueue."""
+        n * max_keypoints queries.  `keep`: the images' tensors, held until the slot's next enqueue.  While
+        set_image_format is on, gray_ptrs are the cameras' raw buffers of that description and (w, h) its size."""
         if self.exchange:
             raise ValueError("frames from device images run on one GPU's whole database")
         self._inputs[slot] = keep
@@ -462,7 +463,8 @@ class FramePipeline:
     def enqueue_images_batch(self, slot: int, gray_ptrs, n_images: int, w: int, h: int, Ks, cams, seeds,
                              max_keypoints: int = 2048, double_size: bool = True, keep=None):
         """len(seeds) frames of one rig of n_images cameras (frame f's images: gray_ptrs[f n_images : (f + 1) n_images])
-        through one FEAT launch per stage and ONE MATCH launch sequence; their objects in result slots 0.. (fetch_batch)."""
+        through one FEAT launch per stage and ONE MATCH launch sequence; their objects in result slots 0.. (fetch_batch).
+        While set_image_format is on, gray_ptrs are raw buffers of that description, converted by one launch."""
         if self.exchange:
             raise ValueError("frames from device images run on one GPU's whole database")
         B = len(seeds)
@@ -480,6 +482,8 @@ class FramePipeline:
         [h, w, 4] in place + its distance map [h, w] (one launch per stage; fill_scale=None: the maps arrive filled, their
         distance maps with them), the maps handed to the frames, FEAT .. FILTER2 of the images as one image batch; objects
         in result slots 0.. (fetch_batch).  The context's depth rules / linkage clusterer are what their setters left.
+        While set_image_format is on, gray_ptrs are the camera's raw buffers of that description (bgr8, a Bayer mosaic, ..),
+        converted by one launch in front of FEAT; the depth maps are what they were.
         `keep`: the tensors behind the pointers, held until the slot's next enqueue."""
         if self.exchange:
             raise ValueError("frames from device images run on one GPU's whole database")
@@ -503,6 +507,7 @@ class FramePipeline:
         per frame, all as raw_fmt (capi.make_raw_depth) describes them.  The [h, w, 4] maps of the batch are built in ONE
         launch into tensors the slot keeps (grown on demand, never shrunk), then everything is enqueue_kinect_batch:
         DEPTHFILL of those maps (fill_scale=None: no DEPTHFILL and no distance maps), the hand-over, the image batch.
+        While set_image_format is on, gray_ptrs are the camera's raw buffers too: image and depth as the sensor delivers them.
         -> (maps [B, h, w, 4], distance maps [B, h, w] or None): views of the slot's tensors, valid until its next call."""
         if self.exchange:
             raise ValueError("frames from device images run on one GPU's whole database")
@@ -535,6 +540,16 @@ class FramePipeline:
         up to 2^21 downscaled pixels: fill_scale 4, 2 or 1, 1280 x 960 frames)."""
         for c in self.ctxs:
             c.depth_fill_set_mode(mode)
+
+    def set_image_format(self, fmt):
+        """What the image pointers of enqueue_images[_batch] and enqueue_kinect[_raw]_batch mean, on every slot's context:
+        a capi.make_raw_image description (bgr8, rgb8, bgra8, rgba8, a Bayer mosaic, gray with strides) = the camera's
+        buffers, converted to gray on the device by one launch per call (moped3d/moped3d.cpp:249); None = packed 8-bit
+        gray, the default.  Not with a sharded database, like every call that takes device images."""
+        if fmt is not None and self.exchange:
+            raise ValueError("frames from device images run on one GPU's whole database")
+        for c in self.ctxs:
+            c.frame_set_image_format(fmt)
 
     def set_linkage_mode(self, mode: int):
         """How the linkage clusterer of the frames runs, on every slot's context: capi.LINKAGE_SCAN (the default; match
