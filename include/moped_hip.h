@@ -923,6 +923,55 @@ enum { MH_LINKAGE_SCAN = 0, MH_LINKAGE_ROWMAX = 1 };
 int mh_linkage_set_mode(mh_ctx* ctx, int mode);
 int mh_linkage_get_mode(mh_ctx* ctx, int* mode);   /* (a user of a shared context saves the mode, sets its own, puts it back) */
 int mh_linkage_stats(mh_ctx* ctx, int64_t out[4], int reset);
+/* moped3d's second depth-aware clusterer: CLUSTER_WEIGHTED_MEAN_SHIFT_CPU
+ * (moped3d/libmoped/src/cluster/CLUSTER_WEIGHTED_MEAN_SHIFT_CPU.hpp:72-208), a true mean shift over the matches'
+ * camera-frame points.  Every point starts as an active canopy; an iteration moves every active canopy to the mean --
+ * weighted by a Cauchy function of the fill distance -- of the points within `radius` of its centre and then switches
+ * off, in a greedy ordered scan, every later canopy within `merge` of an active one.  The clusters are the points
+ * within `radius` of the surviving centres, kept when they have MORE than min_pts members: they MAY OVERLAP, a point
+ * can be a member of several.  O(iterations x n^2), no matrix; at most 2048 points per problem.  fp32 in the
+ * reference's operation order: clusters, member order, centres and iteration counts are its own, bit for bit. */
+typedef struct mh_wms_params {
+  float radius;               /* canopy radius, in the points' unit */
+  float merge;                /* centres closer than this merge */
+  int32_t min_pts;            /* clusters need MORE than this many members (:154) */
+  int32_t max_iter;
+  float half_weight_distance; /* the fill distance at which a point's weight is 1/2 (:184-186) */
+} mh_wms_params;
+/* The step on its own, n_problems point sets (one per (model, image)) in one call -- one upload, one launch, one
+ * download: xyz_host [total][3] = the matches' camera-frame points, fill_host [total] = their fill distances, problem p =
+ * rows [off[p], off[p+1]).  The clusters of all problems come back as one CSR in problem order, in the reference's
+ * emission order within a problem: n_clusters[p] of them belong to problem p, cluster k's members are
+ * members[cl_off[k] .. cl_off[k+1]) -- problem-local row indices, DESCENDING as the reference's push_front leaves them.
+ * cl_off holds cap_clusters + 1 entries, members cap_members.  If more clusters or members exist than the caps hold:
+ * MH_ERR_CAPACITY, needed[0..1] = the clusters / members that exist (also filled on success; may be NULL), and the
+ * longest prefix of the cluster list that fits both caps is written -- whole clusters only, n_clusters[] counts those.
+ * MH_ERR_ARG before any launch, mh_last_error naming the argument: a null pointer, an `off` that does not start at 0 or
+ * decreases, a problem of more than 2048 points, a NaN or negative radius / merge / half_weight_distance, max_iter < 0,
+ * a negative cap. */
+int mh_cluster_wms(mh_ctx* ctx, const float* xyz_host, const float* fill_host, const int32_t* off, int n_problems,
+                   const mh_wms_params* prm, int32_t* n_clusters, int32_t* cl_off, int cap_clusters, int32_t* members,
+                   int cap_members, int64_t needed[2]);
+/* For tests, in the style of mh_linkage_debug_*: the same kernel on the same arguments, its state instead of the
+ * clusters -- per point the weight [total], the final centre [total][3] (a canopy that was switched off keeps the centre
+ * it had then) and the active flag [total]; per problem the iteration count (the reference's nIter). */
+int mh_wms_debug_state(mh_ctx* ctx, const float* xyz_host, const float* fill_host, const int32_t* off, int n_problems,
+                       const mh_wms_params* prm, float* weight, float* centre, int32_t* active, int32_t* iterations);
+/* CLUSTER of the following single-camera frames: this clusterer over the matches' camera-frame points from the depth map
+ * (what DEPTHMAP_PROP leaves in depthData.coord3D), fill distances read from the frame's fill map at ((int) u, (int) v),
+ * clamped to the map as mh_depth_prop clamps; -1 without a fill map (DEPTHMAP_PROP_CPU.hpp:107-111).  prm == NULL switches
+ * it off.  It and mh_frame_set_cluster_linkage exclude each other: the one set last (with parameters) is on.
+ * The clusters may overlap, so POSE reads their members from a buffer of the context, MH_WMS_MEMBER_FACTOR x the matches
+ * the context has reserved (allocated when the mode is set, regrown when a frame reserves more).  Model m's clusters
+ * may hold up to MH_WMS_MEMBER_FACTOR x its match count: the first cluster that would pass that is dropped whole, with
+ * the model's later ones, and the frame's capacity flag is set (MH_ERR_CAPACITY from the fetch, the objects of the
+ * clusters kept delivered).  A model's first 2048 matches are clustered (more: the capacity flag, as mean shift).
+ * mh_frame_debug_fetch_clusters_slot and mh_frame_debug_fetch_cluster_table_slot follow the buffer (the last frame's).
+ * Such frames do not share launches: a batch runs frame by frame.  Refused with MH_ERR_ARG by the frame calls: no depth
+ * map, several cameras, the sharded entry points, the stepped calls (mh_step_*).  MH_ERR_ARG here, the context
+ * unchanged: a NaN or negative radius / merge / half_weight_distance, max_iter < 0. */
+#define MH_WMS_MEMBER_FACTOR 4
+int mh_frame_set_cluster_wms(mh_ctx* ctx, const mh_wms_params* prm);
 /* The two halves around exchange 1 when the DB is sharded over ranks.
  *   mh_frame_enqueue_match_local : normalise + this shard's top-2 -> top2_dev, a
  *       caller-owned device block of [3][Q] 32-bit words {idx1 (global row, int32),

@@ -96,6 +96,19 @@ def default_linkage_params():
     return mh_linkage_params(0.1, 7, 2, -1.0, -1.0, 1)
 
 
+class mh_wms_params(C.Structure):
+    """CLUSTER_WEIGHTED_MEAN_SHIFT_CPU's constructor arguments (Radius, Merge, MinPts, MaxIterations, halfWeightDistance)."""
+    _fields_ = [("radius", C.c_float), ("merge", C.c_float), ("min_pts", C.c_int32), ("max_iter", C.c_int32),
+                ("half_weight_distance", C.c_float)]
+
+    def __init__(self, radius=0.1, merge=0.02, min_pts=7, max_iter=100, half_weight_distance=10.0):
+        super().__init__(radius, merge, min_pts, max_iter, half_weight_distance)
+
+
+WMS_MAX_POINTS = 2048   # points per weighted mean-shift problem
+WMS_MEMBER_FACTOR = 4   # MH_WMS_MEMBER_FACTOR: a model's clusters in a frame hold up to this many times its matches
+
+
 class mh_depth_rules(C.Structure):
     _fields_ = [("patch_size", C.c_int32), ("feature_density", C.c_float), ("match_density", C.c_float),
                 ("ratio_table", C.c_void_p), ("n_models", C.c_int32), ("maximum_depth", C.c_float),
@@ -273,6 +286,7 @@ EXPORTS = [
     "mh_frame_fetch_batch_hulls_async",
     "mh_screen_reject_proved", "mh_match_set_accept", "mh_match_prerejected",
     "mh_image_gray_dev", "mh_image_gray_batch_dev", "mh_image_gray_host", "mh_frame_set_image_format",
+    "mh_cluster_wms", "mh_wms_debug_state", "mh_frame_set_cluster_wms",
 ]
 COMM_ID_BYTES = 128      # MH_COMM_ID_BYTES
 EX2_OBJECTS = 62         # MH_EX2_OBJECTS
@@ -375,6 +389,10 @@ def load():
         L.mh_frame_debug_fetch_clusters_slot.argtypes = [vp, i32, vp, vp, vp, i32, i32, C.POINTER(C.c_int32)]
         L.mh_frame_debug_fetch_cluster_table_slot.argtypes = [vp, i32, vp, vp, vp, i32, C.POINTER(C.c_int32),
                                                               C.POINTER(C.c_int32)]
+    if hasattr(L, "mh_cluster_wms"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
+        L.mh_cluster_wms.argtypes = [vp, vp, vp, vp, i32, C.POINTER(mh_wms_params), vp, vp, i32, vp, i32, vp]
+        L.mh_wms_debug_state.argtypes = [vp, vp, vp, vp, i32, C.POINTER(mh_wms_params), vp, vp, vp, vp]
+        L.mh_frame_set_cluster_wms.argtypes = [vp, C.POINTER(mh_wms_params)]
     L.mh_frame_set_depth_rules.argtypes = [vp, C.POINTER(mh_depth_rules), vp]
     L.mh_frame_enqueue_rest_strided.argtypes = [vp, vp, i32, vp, i32, i32, C.POINTER(mh_cam),
                                                 C.POINTER(mh_frame_params), C.c_uint64]
@@ -2020,6 +2038,70 @@ class Context:
                 pos += sz
             out.append((clusters, lab.copy()))
         return out
+
+    # moped3d's weighted mean shift (CLUSTER_WEIGHTED_MEAN_SHIFT_CPU) on its own
+    @staticmethod
+    def _wms_pack(problems):
+        sizes = [len(p[0]) for p in problems]
+        off = np.zeros(len(problems) + 1, np.int32)
+        off[1:] = np.cumsum(sizes)
+        total = int(off[-1])
+        xyz, fill = np.zeros((max(total, 1), 3), np.float32), np.zeros(max(total, 1), np.float32)
+        for p, b in zip(problems, off):
+            if len(p[0]):
+                xyz[b:b + len(p[0])] = np.asarray(p[0], np.float32).reshape(-1, 3)
+                fill[b:b + len(p[0])] = np.asarray(p[1], np.float32)
+        return off, xyz, fill
+
+    def frame_set_cluster_wms(self, params: "mh_wms_params | None"):
+        """CLUSTER of the following single-camera frames: the weighted mean shift over the depth map's points (None: off;
+        it and frame_set_cluster_linkage exclude each other, the one set last is on)."""
+        self._ck(self.L.mh_frame_set_cluster_wms(self.h, C.byref(params) if params is not None else None),
+                 "mh_frame_set_cluster_wms")
+
+    def cluster_wms_raw(self, problems, params, cap_clusters, cap_members):
+        """mh_cluster_wms as it is -> (status, n_clusters [problems], cl_off [cap_clusters + 1], members [cap_members],
+        needed (clusters, members)); the arrays are pre-filled with -1 so that a test sees what was written."""
+        off, xyz, fill = self._wms_pack(problems)
+        ncl = np.full(max(len(problems), 1), -1, np.int32)
+        cl_off = np.full(cap_clusters + 1, -1, np.int32)
+        members = np.full(max(cap_members, 1), -1, np.int32)
+        needed = np.zeros(2, np.int64)
+        rc = self.L.mh_cluster_wms(self.h, _ptr(xyz), _ptr(fill), _ptr(off), len(problems), C.byref(params), _ptr(ncl),
+                                   _ptr(cl_off), int(cap_clusters), _ptr(members), int(cap_members), _ptr(needed))
+        return rc, ncl[:len(problems)], cl_off, members[:cap_members], (int(needed[0]), int(needed[1]))
+
+    def cluster_wms(self, problems, params=None):
+        """problems: list of (xyz [n, 3] camera-frame points, fill [n] fill distances), one per (model, image), each of up
+        to WMS_MAX_POINTS points -> per problem the list of clusters in the reference's order, each an int32 array of
+        problem-local indices, descending.  Clusters may overlap."""
+        prm = params or mh_wms_params()
+        total = sum(len(p[0]) for p in problems)
+        cap_c, cap_m = max(total, 1), max(4 * total, 1)
+        for _ in range(2):
+            rc, ncl, cl_off, members, needed = self.cluster_wms_raw(problems, prm, cap_c, cap_m)
+            if rc != MH_ERR_CAPACITY:
+                break
+            cap_c, cap_m = max(needed[0], 1), max(needed[1], 1)   # (overlap beyond four memberships per point: ask again)
+        self._ck(rc, "mh_cluster_wms")
+        out, k = [], 0
+        for p in range(len(problems)):
+            out.append([members[cl_off[k + c]:cl_off[k + c + 1]].copy() for c in range(int(ncl[p]))])
+            k += int(ncl[p])
+        return out
+
+    def wms_debug_state(self, problems, params=None):
+        """The same problems through the same kernel -> per problem (weight [n], centre [n, 3], active [n] bool,
+        iterations): the weights, the final centres, which canopies survived, the reference's nIter."""
+        prm = params or mh_wms_params()
+        off, xyz, fill = self._wms_pack(problems)
+        total = int(off[-1])
+        weight, centre = np.zeros(max(total, 1), np.float32), np.zeros((max(total, 1), 3), np.float32)
+        active, iters = np.zeros(max(total, 1), np.int32), np.zeros(max(len(problems), 1), np.int32)
+        self._ck(self.L.mh_wms_debug_state(self.h, _ptr(xyz), _ptr(fill), _ptr(off), len(problems), C.byref(prm), _ptr(weight),
+                                           _ptr(centre), _ptr(active), _ptr(iters)), "mh_wms_debug_state")
+        return [(weight[b:e].copy(), centre[b:e].copy(), active[b:e].astype(bool), int(iters[p]))
+                for p, (b, e) in enumerate(zip(off[:-1], off[1:]))]
 
     def linkage_set_mode(self, mode: int):
         """LINKAGE_SCAN (0, the default: one workgroup per problem rescans every live pair per merge; up to 1024 points)

@@ -659,12 +659,41 @@ int mh_frame_set_cluster_linkage(mh_ctx* ctx, const mh_linkage_params* prm) {
   }
   ctx->linkage_on = prm != nullptr;
   if (prm) {
+    ctx->wms_on = false;   // (the two clusterers exclude each other: the one set last is on)
     ctx->linkage.cutoff = prm->cutoff;
     ctx->linkage.min_pts = prm->min_pts;
     ctx->linkage.use3d_filter = prm->use3d_filter;
     ctx->linkage.sigma2d = prm->sigma2d;
     ctx->linkage.sigma3d = prm->sigma3d;
     ctx->linkage.linkage_type = prm->linkage_type;
+  }
+  return MH_OK;
+}
+
+int mh_frame_set_cluster_wms(mh_ctx* ctx, const mh_wms_params* prm) {
+  if (!ctx) return MH_ERR_ARG;
+  if (prm) {   // (before anything of the context changes)
+    const char* bad = !(prm->radius >= 0.f) ? "radius must be a number >= 0" : !(prm->merge >= 0.f) ? "merge must be a number >= 0"
+                      : !(prm->half_weight_distance >= 0.f) ? "half_weight_distance must be a number >= 0"
+                      : prm->max_iter < 0 ? "max_iter < 0" : nullptr;
+    if (bad) {
+      ctx->err = std::string("mh_frame_set_cluster_wms: ") + bad;
+      return MH_ERR_ARG;
+    }
+  }
+  ctx->wms_on = prm != nullptr;
+  if (prm) {
+    ctx->linkage_on = false;   // (the one set last is on)
+    ctx->wms.radius = prm->radius;
+    ctx->wms.merge = prm->merge;
+    ctx->wms.min_pts = prm->min_pts;
+    ctx->wms.max_iter = prm->max_iter;
+    ctx->wms.half_weight_distance = prm->half_weight_distance;
+    // the members' buffer, for the matches the context has reserved (a frame that reserves more regrows it)
+    if (ctx->fs) {
+      if (int rc_enter = mh::enter(ctx)) return rc_enter;
+      if (int rc = ensure_wms_buffers(ctx)) return rc;
+    }
   }
   return MH_OK;
 }
@@ -872,8 +901,8 @@ static int enqueue_images(mh_ctx* ctx, const char* who, const uint8_t* const* gr
   for (int j = 0; j < F * n; ++j)
     if (!gray_dev[j]) return refuse(MH_ERR_ARG, "null image");
   if (int rc_fd = filter_depth_frame_ok(ctx, who, prm, n)) return rc_fd;
-  if (ctx->depth_img.img || ctx->rules.on || ctx->q_depth || (n > 1 && ctx->linkage_on))
-    return refuse(MH_ERR_ARG, "depth maps / rules / attributes and the linkage clusterer are single-camera");
+  if (ctx->depth_img.img || ctx->rules.on || ctx->q_depth || (n > 1 && (ctx->linkage_on || ctx->wms_on)))
+    return refuse(MH_ERR_ARG, "depth maps / rules / attributes and the linkage / weighted mean-shift clusterers are single-camera");
   if (ctx->imf.und_n && ctx->imf.und_n != n)
     return refuse(MH_ERR_ARG, "mh_frame_set_undistort_images gave coefficients for another number of cameras");
   if (int rc_if = image_format_frame_ok(ctx, who, width, height)) return rc_if;
@@ -1232,7 +1261,16 @@ int mh_frame_debug_fetch_clusters_slot(mh_ctx* ctx, int slot, int32_t* cl_model_
   MH_HIP(ctx, get(off, pairs > 1 ? fs->off2 : fs->model_off, (size_t)nm + 1));
   MH_HIP(ctx, get(ncl, fs->ms_ncl, (size_t)nm));
   MH_HIP(ctx, get(start, fs->ms_cl_start, (size_t)M + nm + 1));
-  if (M > 0) MH_HIP(ctx, get(mem, fs->ms_members, (size_t)M));
+  // (the weighted mean shift: model m's members at factor x off[m] of the context's buffer, up to factor x its matches)
+  const int fct = fs->list_wms ? WMS_MEMBER_FACTOR : 1;
+  if (fs->list_wms) {
+    if (pairs > 1 || !ctx->wms_members || ctx->wms_members.cap < (size_t)fct * M) {
+      ctx->err = std::string(who) + ": inconsistent member buffer";
+      return MH_ERR_HIP;
+    }
+    mem.resize((size_t)fct * std::max(M, 1));
+    if (M > 0) MH_HIP(ctx, hipMemcpy(mem.data(), ctx->wms_members.p, (size_t)fct * M * sizeof(int32_t), hipMemcpyDeviceToHost));
+  } else if (M > 0) MH_HIP(ctx, get(mem, fs->ms_members, (size_t)M));
   int n = 0, w = 0;
   for (int m = 0; m < nm; ++m) {
     const int b = off[m], k = off[m + 1] - b;
@@ -1242,7 +1280,7 @@ int mh_frame_debug_fetch_clusters_slot(mh_ctx* ctx, int slot, int32_t* cl_model_
     }
     const int32_t* st = start.data() + b + m;
     for (int c = 0; c < ncl[m]; ++c, ++n) {
-      if (st[c] < 0 || st[c + 1] < st[c] || st[c + 1] > k) {
+      if (st[c] < 0 || st[c + 1] < st[c] || st[c + 1] > fct * k) {
         ctx->err = std::string(who) + ": inconsistent cluster lists";
         return MH_ERR_HIP;
       }
@@ -1251,7 +1289,7 @@ int mh_frame_debug_fetch_clusters_slot(mh_ctx* ctx, int slot, int32_t* cl_model_
         if (cl_off_host) cl_off_host[n] = w;
       }
       for (int j = st[c]; j < st[c + 1]; ++j, ++w)
-        if (members_host && w < cap_members) members_host[w] = mem[b + j] - b;   // index inside the model's match list
+        if (members_host && w < cap_members) members_host[w] = mem[(size_t)fct * b + j] - b;   // index inside the model's match list
     }
   }
   if (cl_off_host && n <= cap_clusters) cl_off_host[n] = w;

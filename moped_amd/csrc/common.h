@@ -226,7 +226,8 @@ template <typename WorkFn>
 __device__ __forceinline__ int layout_cluster_table(int n_models, const int32_t* __restrict__ model_off, int32_t* ncl,
                                                     const int32_t* cl_start, int models_div, int max_clusters,
                                                     int32_t* __restrict__ cl_model, int32_t* __restrict__ cl_begin,
-                                                    int32_t* __restrict__ cl_count, int* lay_s, WorkFn work) {
+                                                    int32_t* __restrict__ cl_count, int* lay_s, WorkFn work,
+                                                    int member_factor = 1 /* model m's members start at member_factor * model_off[m] */) {
   const int n_waves = (int)(blockDim.x >> 6), wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
   int k0 = 0;
   for (int c0 = 0; c0 < n_models; c0 += (int)blockDim.x) {
@@ -259,7 +260,7 @@ __device__ __forceinline__ int layout_cluster_table(int n_models, const int32_t*
       const int k = first + c;
       if (k >= max_clusters) break;
       cl_model[k] = mm / models_div;
-      cl_begin[k] = bb + st[c];
+      cl_begin[k] = member_factor * bb + st[c];
       cl_count[k] = st[c + 1] - st[c];
     }
     k0 += total;

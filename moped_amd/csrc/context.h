@@ -284,6 +284,11 @@ struct mh_ctx {
 
   // moped3d CLUSTER_LINKAGE instead of mean shift (mh_frame_set_cluster_linkage)
   bool linkage_on = false;
+  // moped3d CLUSTER_WEIGHTED_MEAN_SHIFT instead (mh_frame_set_cluster_wms; whichever of the two was set last is on)
+  bool wms_on = false;
+  mh::WmsParams wms;
+  mh::DevBuf<int32_t> wms_members;        // MH_WMS_MEMBER_FACTOR x max_m: the frame's clusters' members (they may overlap)
+  mh::DevBuf<unsigned char> wms_state;    // the kernel's per-point / per-model state (wms_state_bytes)
   mh::LinkageParams linkage;
   mh::DevBuf<float> own_depth;    // device copies of a host depth / distance map (ensure_own_depth)
   mh::DevBuf<float> own_fill;

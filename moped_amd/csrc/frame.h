@@ -33,6 +33,7 @@ struct FrameState {
   int32_t* model_off = nullptr;
   // cluster
   int32_t *ms_members = nullptr, *ms_cl_start = nullptr, *ms_ncl = nullptr;
+  bool list_wms = false;   // the last frame's CLUSTER was the weighted mean shift: members in ctx->wms_members, MH_WMS_MEMBER_FACTOR x model_off apart
   int32_t *cl_model = nullptr, *cl_begin = nullptr, *cl_count = nullptr;
   // objects
   int32_t *obj_model = nullptr, *obj_ninl = nullptr, *obj_cluster = nullptr, *obj_valid = nullptr,
@@ -122,6 +123,7 @@ inline int enter(mh_ctx* ctx) {
 int ensure_fs(mh_ctx* ctx, int max_m, int max_clusters, int max_objects, int n_models, int n_arenas = 1);
 int prepare_frame(mh_ctx* ctx, int Q, int q_frame = 0, int frames = 1);
 int frame_rest(mh_ctx* ctx, const FrameCall& c);
+int ensure_wms_buffers(mh_ctx* ctx);   // ctx->wms_members / wms_state for what ctx->fs holds
 bool merged_batch_ok(const mh_ctx* ctx, const mh_frame_params* prm, bool attrs_ok = false, int maps_for = 0);
 int ensure_batch_arenas(mh_ctx* ctx, int B);
 int ensure_linkage_scratch(mh_ctx* ctx, size_t floats);

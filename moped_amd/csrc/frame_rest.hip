@@ -408,6 +408,16 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
     if (int rc = hulls_frame_ok(ctx, "frame", multi ? ctx->n_images : 1, c.gathered != nullptr)) return rc;
     if (int rc = ensure_hull_block(ctx)) return rc;
   }
+  // moped3d's weighted mean shift (mh_frame_set_cluster_wms): whole single-camera frames of this context over a depth map
+  if (ctx->wms_on) {
+    const char* why = !dimg.img ? "no depth map (mh_frame_set_depth_image)" : multi ? "frames with several images" :
+                      c.gathered ? "the sharded entry points" : stepped ? "stepped frames" : nullptr;
+    if (why) {
+      ctx->err = std::string("frame: the weighted mean-shift clusterer does not take ") + why;
+      return MH_ERR_ARG;
+    }
+    if (int rc = ensure_wms_buffers(ctx)) return rc;
+  }
   if (multi && (ctx->q_depth || dimg.img || ctx->linkage_on)) {
     ctx->err = "frames with several images: the moped3d depth steps are single-camera";
     return MH_ERR_ARG;
@@ -472,7 +482,13 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
   // CLUSTER (+ flat cluster table, snap[0..1])
   const bool have_depth = ctx->q_depth || dimg.img;
   if (runs(1)) fs->list_pairs = multi ? ctx->n_images : 1;   // (several images: MeanShift only, see above)
+  if (runs(1)) fs->list_wms = ctx->wms_on;
   if (!runs(1)) {
+  } else if (ctx->wms_on) {
+    // (frame after frame: merged_batch_ok is false in this mode)
+    launch_wms_models(fs->m_corr, reinterpret_cast<const float*>(fs->m_depth), fs->model_off, nm, fs->max_m, dimg, ctx->wms,
+                      ctx->wms_state.p, ctx->wms_members.p, WMS_MEMBER_FACTOR, fs->ms_cl_start, fs->ms_ncl, fs->max_clusters,
+                      fs->cl_model, fs->cl_begin, fs->cl_count, fs->n_clusters, snap, fs->counts, fs->tickets + 0, s);
   } else if (ctx->linkage_on && have_depth && dimg.img) {
     // moped3d: linkage over similarity matrices; 3 n^2 floats of scratch per model, n <= LK_CAP (MH_LINKAGE_ROWMAX: LK_MAX)
     // (a merged batch: every frame its own region)
@@ -593,7 +609,8 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
   split.list = fs->rf_list;
   split.max_m = fs->max_m;
   if (runs(2))
-  launch_pose(multi ? fs->mi_corr : fs->m_corr, depth4, ctx->depth_kind, ctx->depth_alpha, fs->ms_members, fs->cl_model,
+  launch_pose(multi ? fs->mi_corr : fs->m_corr, depth4, ctx->depth_kind, ctx->depth_alpha,
+              ctx->wms_on ? ctx->wms_members.p : fs->ms_members, fs->cl_model,
               fs->cl_begin, fs->cl_count, fs->n_clusters, fs->max_clusters, dc, prm->pose1, c.seed, fs->n_slots,
               fs->max_objects, fs->obj_model, fs->obj_pose, fs->obj_ninl, fs->obj_err, fs->obj_cluster,
               fs->obj_valid, fs->counts, PoseTail{fs->tickets + 1, fs->n_slots, snap + 2, grid, fs->fb}, s, img1,
@@ -672,7 +689,15 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
 // take frame f's map from a DepthMaps table and its rule buffers behind those of the frames before it.
 // The depth FILTER (mh_frame_set_filter_depth) travels with the maps: the fused POSE tails score every object against its
 // own frame's map (FilterFuseDepth, steps.h).
+int ensure_wms_buffers(mh_ctx* ctx) {
+  const FrameState* fs = ctx->fs;
+  MH_HIP(ctx, ctx->wms_members.ensure((size_t)WMS_MEMBER_FACTOR * std::max(fs->max_m, 1), ctx->stream));
+  MH_HIP(ctx, ctx->wms_state.ensure(wms_state_bytes((size_t)std::max(fs->n_models_cap, 1), (size_t)std::max(fs->max_m, 1)), ctx->stream));
+  return MH_OK;
+}
+
 bool merged_batch_ok(const mh_ctx* ctx, const mh_frame_params* prm, bool attrs_ok, int maps_for) {
+  if (ctx->wms_on) return false;   // the members' buffer is the context's: a batch runs frame by frame
   static const bool on = exp_int("MH_MERGE_BATCH", 1) != 0;
   static const bool fuse_filter = exp_int("MH_FUSE_FILTER", 1) != 0;
   static const bool merge_maps = exp_int("MH_MERGE_MAPS", 1) != 0;

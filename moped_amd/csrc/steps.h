@@ -214,6 +214,36 @@ void launch_linkage_rowmax_models(const mh_corr* corr, const float* depth4, cons
                                   FrameCounts* counts, unsigned int* ticket, hipStream_t s, int grid, const FrameBatch* batch,
                                   const DepthMaps* maps, int32_t* feedback, unsigned char* aux, unsigned long long* stats);
 
+// ---- weighted mean shift (moped3d CLUSTER_WEIGHTED_MEAN_SHIFT_CPU; wms.hip) ------------------
+struct WmsParams {             // the constructor arguments
+  float radius = 0.1f, merge = 0.02f;
+  int min_pts = 7;             // clusters need MORE than this many members
+  int max_iter = 100;
+  float half_weight_distance = 10.f;   // the fill distance at which a point's Cauchy weight is 1/2
+};
+// Bytes of device memory (16-byte aligned) launch_wms_batch keeps its per-point / per-problem state in.
+size_t wms_state_bytes(size_t n_problems, size_t total);
+// n_problems independent point sets in one launch: problem p = rows [off[p], off[p+1]) (<= MS_CAP) of xyz [total][3]
+// and fill [total] (fill distances).  The clusters of all problems, in (problem, canopy) order and with problem-local
+// member indices, descending, come back as one CSR: out_tot[0..1] = clusters / members that EXIST, cl_off[k] for
+// k <= min(clusters, cap_clusters), and the members of the clusters that lie inside both caps (a prefix of the list;
+// never part of a cluster).  The *_out pointers (optional) receive where in `state` the final centres + weights
+// [total], the active flags [total] and the per-problem kept clusters / members / iteration counts live.
+// *ticket: zero before the launch (last_workgroup).
+void launch_wms_batch(const float* xyz, const float* fill, const int32_t* off, int n_problems, int total, const WmsParams& prm,
+                      void* state, float4** cw_out, int32_t** active_out, int32_t** ncl_out, int32_t** nmem_out,
+                      int32_t** iters_out, long long* out_tot, int32_t* cl_off, int cap_clusters, int32_t* members,
+                      int cap_members, unsigned int* ticket, hipStream_t s);
+
+// CLUSTER of a single-camera frame with this clusterer (one workgroup per model; outputs as launch_meanshift_models,
+// except that model m's members lie at members[factor * model_off[m] ..), at most factor x its matches: clusters may
+// overlap).  members: factor * max_m words; state: wms_state_bytes(n_models, max_m).
+constexpr int WMS_MEMBER_FACTOR = 4;   // == MH_WMS_MEMBER_FACTOR
+void launch_wms_models(const mh_corr* corr, const float* depth4, const int32_t* model_off, int n_models, int max_m,
+                       const DepthImage& dimg, const WmsParams& prm, void* state, int32_t* members, int factor, int32_t* cl_start,
+                       int32_t* ncl, int max_clusters, int32_t* cl_model, int32_t* cl_begin, int32_t* cl_count,
+                       int32_t* n_clusters_out, int32_t* snap, FrameCounts* counts, unsigned int* ticket, hipStream_t s);
+
 // ---- pose ----------------------------------------------------------------------
 struct DevCam {
   float K[4];

@@ -43,6 +43,11 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
   int IncrementalModels;
   int LevelFill;   // config key: the frame's DEPTHFILL in MH_DEPTH_FILL_LEVELS mode (FillScale 4, 2, 1; 1280 x 960 frames)
   int LinkageRowMaxima;   // config key: the frame's CLUSTER in MH_LINKAGE_ROWMAX mode (match lists of up to 4096 per model)
+  // config keys: the frame's CLUSTER as CLUSTER_WEIGHTED_MEAN_SHIFT_CPU instead of the linkage class (ClusterWeighted 1) with
+  // that class's Radius, Merge, MinPts, MaxIterations, halfWeightDistance (mh_frame_set_cluster_wms); clusters[model] is
+  // then filled too (the clusters may overlap)
+  int ClusterWeighted;
+  mh_wms_params wp;
   unsigned long frameCounter;
   int32_t lastCounts[4];
 
@@ -64,7 +69,12 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
       : FillScale(FillScale), Bilinear(Bilinear), DescriptorSize(DescriptorSize), DescriptorType(DescriptorType),
         PatchSize(PatchSize), Density1(Density1), Density2(Density2),
         am(MinRatioMin, MinRatioMax, MaxRatioMin, MaxRatioMax, DimensionPeak, DimensionFade), Alpha(Alpha),
-        Kind(MH_DEPTH_BACKPROJECTION), MaxKeypoints(2048), DoubleImSize(1), IncrementalModels(0), LevelFill(0), LinkageRowMaxima(0), frameCounter(0) {
+        Kind(MH_DEPTH_BACKPROJECTION), MaxKeypoints(2048), DoubleImSize(1), IncrementalModels(0), LevelFill(0), LinkageRowMaxima(0), ClusterWeighted(0), frameCounter(0) {
+    wp.radius = 0.1f;
+    wp.merge = 0.02f;
+    wp.min_pts = 7;
+    wp.max_iter = 100;
+    wp.half_weight_distance = 10.f;
     lk.cutoff = (float)Cutoff;
     lk.min_pts = MinPts;
     lk.use3d_filter = Use3DFilter;
@@ -99,6 +109,12 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
     hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "DoubleImSize", DoubleImSize);
     hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "LevelFill", LevelFill);
     hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "LinkageRowMaxima", LinkageRowMaxima);
+    hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "ClusterWeighted", ClusterWeighted);
+    hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "ClusterWeightedRadius", wp.radius);
+    hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "ClusterWeightedMerge", wp.merge);
+    hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "ClusterWeightedMinPts", wp.min_pts);
+    hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "ClusterWeightedMaxIterations", wp.max_iter);
+    hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "ClusterWeightedHalfWeightDistance", wp.half_weight_distance);
   }
   void setConfig(map<string, string>& config) {
     hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "Density", Density1);
@@ -108,6 +124,12 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
     hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "IncrementalModels", IncrementalModels);
     hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "LevelFill", LevelFill);
     hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "LinkageRowMaxima", LinkageRowMaxima);
+    hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "ClusterWeighted", ClusterWeighted);
+    hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "ClusterWeightedRadius", wp.radius);
+    hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "ClusterWeightedMerge", wp.merge);
+    hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "ClusterWeightedMinPts", wp.min_pts);
+    hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "ClusterWeightedMaxIterations", wp.max_iter);
+    hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "ClusterWeightedHalfWeightDistance", wp.half_weight_distance);
   }
 
   void process(FrameData& frameData) {
@@ -156,6 +178,8 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
     rules.cauchy_scale = 0.1f;
     if (mh_frame_set_depth_rules(ctx, &rules, K) != MH_OK) { HipSession::warn("mh_frame_set_depth_rules"); return; }
     if (mh_frame_set_cluster_linkage(ctx, &lk) != MH_OK) { HipSession::warn("mh_frame_set_cluster_linkage"); return; }
+    // (set after the linkage class: the one set last is on)
+    if (ClusterWeighted && mh_frame_set_cluster_wms(ctx, &wp) != MH_OK) { HipSession::warn("mh_frame_set_cluster_wms"); return; }
     const mh_cam cam = hipCamOf(*gray);
     vector<mh_object> out(256);
     int32_t n = 0;
@@ -183,6 +207,7 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
       ~Restore() {
         mh_frame_set_depth_rules(ctx, 0, 0);
         mh_frame_set_cluster_linkage(ctx, 0);
+        mh_frame_set_cluster_wms(ctx, 0);
         mh_frame_set_depth_image(ctx, 0, 0, 0, 0, 0, 0.5f, 0.1f);
         mh_depth_fill_set_mode(ctx, fillMode);
         mh_linkage_set_mode(ctx, linkageMode);
@@ -220,6 +245,21 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
           mt.depthData.depth = have ? info[k].depth : 0.f;
           mt.depthData.fillDistance = have ? info[k].fill_distance : -1.f;
           frameData.matches[mm[k]].push_back(mt);
+        }
+      }
+    }
+    // the weighted mean shift's clusters: member indices inside the model's match list, as the CLUSTER step leaves them
+    if (ClusterWeighted && M > 0 && counts[1] > 0) {
+      vector<int32_t> cm(counts[1]), co((size_t)counts[1] + 1), mem((size_t)MH_WMS_MEMBER_FACTOR * M);
+      int32_t nc = 0;
+      if (mh_frame_debug_fetch_clusters_slot(ctx, 0, &cm[0], &co[0], &mem[0], counts[1], (int)mem.size(), &nc) != MH_OK) {
+        HipSession::warn("mh_frame_debug_fetch_clusters_slot");
+      } else {
+        for (int k = 0; k < nc; ++k) {
+          if (cm[k] < 0 || cm[k] >= (int)models->size()) continue;
+          frameData.clusters[cm[k]].resize(frameData.clusters[cm[k]].size() + 1);
+          FrameData::Cluster& cl = frameData.clusters[cm[k]].back();
+          for (int j = co[k]; j < co[k + 1]; ++j) cl.push_back(mem[j]);
         }
       }
     }

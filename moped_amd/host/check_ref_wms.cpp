@@ -1,0 +1,11 @@
+// CLUSTER_WEIGHTED_MEAN_SHIFT_HIP.hpp against moped3d's REAL include/moped.hpp (`make check_ref_wms`): Pt, Image and
+// FrameData's members are then the reference's own types, util.hpp's part comes from the mirror (see check_ref.cpp).
+#include <cstring>
+#include <iostream>
+#include <sstream>
+#include <string>
+#include <moped.hpp>
+#define MOPED_AMD_WITH_DEPTH 1
+#include "moped_util_mirror.hpp"
+#include "CLUSTER_WEIGHTED_MEAN_SHIFT_HIP.hpp"
+int main() { return 0; }

@@ -6,6 +6,9 @@
 //   moped3d_hip_test [--resident] [--loop N] [--maps-out file] [--level-fill] [--linkage-rowmax] scene.bin
 //       --resident       the same scene through FRAME_RESIDENT_3D_HIP (one step, mh_frame_run_kinect_host)
 //       --level-fill     DEPTHFILL in MH_DEPTH_FILL_LEVELS mode (DEPTH_FILL_EXACT_HIP's levelFill, the one-step plugin's LevelFill key)
+//       --cluster-wms R M MinPts MaxIter HWD   CLUSTER_WEIGHTED_MEAN_SHIFT_HIP with these arguments in the CLUSTER slot of the
+//                        step wiring, or -- with --resident -- as FRAME_RESIDENT_3D_HIP's ClusterWeighted... keys (moped3d's
+//                        other depth-aware clusterer)
 //       --linkage-rowmax CLUSTER in MH_LINKAGE_ROWMAX mode (CLUSTER_LINKAGE_HIP's RowMaxima key, the one-step plugin's LinkageRowMaxima)
 //       --loop N         the frame N times; prints FPS (process() time only), the lists of the last frame
 //       --maps-out file  the frame's depth map [h][w][4] and distance map [h][w] (floats) as the steps left them
@@ -37,6 +40,7 @@
 #include "MATCH_ADAPTIVE_BRUTE_HIP.hpp"
 #include "DEPTHMAP_PROP_HIP.hpp"
 #include "CLUSTER_LINKAGE_HIP.hpp"
+#include "CLUSTER_WEIGHTED_MEAN_SHIFT_HIP.hpp"
 #include "POSE_RANSAC_P3P_DEPTH_HIP.hpp"
 #include "FILTER_PROJECTION_HIP.hpp"
 #include "FRAME_RESIDENT_3D_HIP.hpp"
@@ -111,15 +115,18 @@ static SP_Image make_image(const Scene& s, Image_Type type, const char* name, co
 }
 
 // moped3d/libmoped/src/config.hpp:38-49 with the HIP classes (UNDISTORTED_IMAGE: the scenes are undistorted)
-static CLUSTER_LINKAGE_HIP* createPipeline(MopedPipeline& pipeline, const Scene& s, bool level_fill) {
-  CLUSTER_LINKAGE_HIP* cluster = new CLUSTER_LINKAGE_HIP(0.1, 7, 2, 1, 0.0, 1, -1, -1);
+// wms (--cluster-wms): Radius, Merge, MinPts, MaxIterations, halfWeightDistance of CLUSTER_WEIGHTED_MEAN_SHIFT_HIP in the
+// CLUSTER slot instead (0 is returned then: the linkage step's own key has nobody to go to)
+static CLUSTER_LINKAGE_HIP* createPipeline(MopedPipeline& pipeline, const Scene& s, bool level_fill, const double* wms) {
+  CLUSTER_LINKAGE_HIP* cluster = wms ? 0 : new CLUSTER_LINKAGE_HIP(0.1, 7, 2, 1, 0.0, 1, -1, -1);
   if (s.fill_scale != 0) pipeline.addAlg("DEPTHFILL", new DEPTH_FILL_EXACT_HIP(s.fill_scale, false, level_fill));
   if (s.Q == 0 && s.has_image) pipeline.addAlg("SIFT", new FEAT_SIFT_HIP("-1"));
   pipeline.addAlg("DEPTHFILTER", new DEPTHFILTER_HIP(s.patch, s.density1, 1));
   pipeline.addAlg("MATCH_SIFT", new MATCH_ADAPTIVE_BRUTE_HIP(128, "SIFT", 0.6, 0.75, 0.65, 0.8, 150, 50));
   pipeline.addAlg("DEPTHFILTER2", new DEPTHFILTER_HIP(s.patch, s.density2, 2));
   pipeline.addAlg("DEPTHPROP", new DEPTHMAP_PROP_HIP());
-  pipeline.addAlg("CLUSTER", cluster);
+  if (wms) pipeline.addAlg("CLUSTER", new CLUSTER_WEIGHTED_MEAN_SHIFT_HIP(wms[0], wms[1], (unsigned)wms[2], (unsigned)wms[3], wms[4]));
+  else pipeline.addAlg("CLUSTER", cluster);
   pipeline.addAlg("POSE", new POSE_RANSAC_P3P_DEPTH_HIP(1024, 4, 5, 6, 8, 0.5));
   pipeline.addAlg("FILTER", new FILTER_PROJECTION_HIP(6, 4096., 2));
   pipeline.addAlg("POSE2", new POSE_RANSAC_P3P_DEPTH_HIP(1024, 4, 6, 8, 5, 0.5));
@@ -174,6 +181,8 @@ int main(int argc, char** argv) {
   bool resident = false, level_fill = false, linkage_rowmax = false;
   int loop = 1;
   const char* maps_out = 0;
+  double wms[5];
+  bool cluster_wms = false;
   int a = 1;
   for (; a < argc && argv[a][0] == '-'; ++a) {
     if (std::string(argv[a]) == "--resident") resident = true;
@@ -181,10 +190,18 @@ int main(int argc, char** argv) {
     else if (std::string(argv[a]) == "--linkage-rowmax") linkage_rowmax = true;
     else if (std::string(argv[a]) == "--loop" && a + 1 < argc) loop = std::atoi(argv[++a]);
     else if (std::string(argv[a]) == "--maps-out" && a + 1 < argc) maps_out = argv[++a];
+    else if (std::string(argv[a]) == "--cluster-wms" && a + 5 < argc) {
+      cluster_wms = true;
+      for (int k = 0; k < 5; ++k) wms[k] = std::atof(argv[++a]);
+    }
     else { a = argc; break; }   // an option nobody knows, or one without its value
   }
   if (a + 1 != argc || loop < 1) {
-    std::fprintf(stderr, "usage: %s [--resident] [--loop N] [--maps-out file] [--level-fill] [--linkage-rowmax] scene.bin\n", argv[0]);
+    std::fprintf(stderr, "usage: %s [--resident] [--loop N] [--maps-out file] [--level-fill] [--linkage-rowmax] [--cluster-wms R M MinPts MaxIter HWD] scene.bin\n", argv[0]);
+    return 2;
+  }
+  if (cluster_wms && (linkage_rowmax || wms[2] < 0 || wms[3] < 0)) {
+    std::fprintf(stderr, "--cluster-wms: without --linkage-rowmax, MinPts and MaxIter >= 0\n");
     return 2;
   }
   Scene s;
@@ -200,7 +217,7 @@ int main(int argc, char** argv) {
   FRAME_RESIDENT_3D_HIP* res = 0;
   CLUSTER_LINKAGE_HIP* cluster = 0;
   if (resident) res = createResidentPipeline(pipeline, s);
-  else cluster = createPipeline(pipeline, s, level_fill);
+  else cluster = createPipeline(pipeline, s, level_fill, cluster_wms ? wms : 0);
   list<MopedAlg*> all = pipeline.getAlgs();
   map<string, string> config;
   for (list<MopedAlg*>::iterator it = all.begin(); it != all.end(); ++it) {
@@ -215,6 +232,12 @@ int main(int argc, char** argv) {
     config["DEPTHFILL:0:FRAME_RESIDENT_3D_HIP/MaxKeypoints"] = toString(s.max_keypoints);
     if (level_fill) config["DEPTHFILL:0:FRAME_RESIDENT_3D_HIP/LevelFill"] = "1";
     if (linkage_rowmax) config["DEPTHFILL:0:FRAME_RESIDENT_3D_HIP/LinkageRowMaxima"] = "1";
+    if (cluster_wms) {
+      static const char* const keys[5] = {"Radius", "Merge", "MinPts", "MaxIterations", "HalfWeightDistance"};
+      config["DEPTHFILL:0:FRAME_RESIDENT_3D_HIP/ClusterWeighted"] = "1";
+      for (int k = 0; k < 5; ++k)
+        config[std::string("DEPTHFILL:0:FRAME_RESIDENT_3D_HIP/ClusterWeighted") + keys[k]] = toString(k == 2 || k == 3 ? (double)(int)wms[k] : wms[k]);
+    }
     res->setConfig(config);
   }
   if (cluster && linkage_rowmax) {

@@ -575,6 +575,15 @@ class FramePipeline:
                 c.filter_depth_set_points(points_xyz, points_off)
             c.frame_set_filter_depth(f1, f2, K, cam)
 
+    def set_cluster_wms(self, params: "capi.mh_wms_params | None"):
+        """CLUSTER of the frames enqueued from now on as moped3d's CLUSTER_WEIGHTED_MEAN_SHIFT_CPU over the depth map's
+        points (Context.frame_set_cluster_wms on every slot's context; None = off).  Single-camera frames with a depth
+        map on an unsharded database; a batch runs frame by frame."""
+        if params is not None and self.exchange:
+            raise capi.MhError("the weighted mean-shift clusterer: single-GPU pipelines only")
+        for c in self.ctxs:
+            c.frame_set_cluster_wms(params)
+
     # ---- object hulls: Object::getObjectHull of every object of a frame, computed behind the frame --------------
     def set_hulls(self, max_vertices: int, image: int = 0):
         """Frames and batches enqueued afterwards compute the hulls of their objects (mh_frame_set_hulls; 0 = off, the
