@@ -391,6 +391,34 @@ int mh_project_test(mh_ctx* ctx, const float pose[7], const mh_corr* corr_host, 
                     const mh_cam* cam, float thr, uint8_t* inlier_host, float* err2_host,
                     int32_t* n_inliers);
 
+/* For verification only (tests/test_gpu_pose_rows.py), in the style of mh_sift_debug_* / mh_wms_debug_state: the device
+ * functions of POSE's LM refine on one wavefront, everything they compute written out.  Host pointers, temporary device
+ * buffers, one launch, synchronised; nothing of the context's frame state changes.
+ *
+ * mh_pose_debug_rows: kind = the points' layout, res = the residual model, one of the pairs the refine runs: (0,0)
+ * (1,1) (2,2) (3,3) (1,0) (2,0).  0 reprojection, 1 back-projection + depth, 2 reprojection + depth, 3 reprojection with
+ * every point in its own image.  phase 0: plain errors, 1: the reference's squared errors.  Pose R [9] row major, t [3]
+ * (world frame); cams [n_images] (kinds 0..2 use cams[0]).  pts [n_pts][stride] in the kernel's own layout: u, v, x, y,
+ * z, then for kind 3 the image number as an int in word 5 (stride 6), for kinds 1 and 2 wx, wy, wz, cauchyWeight (stride
+ * 9); kind 0: stride 5.  list [n]: indices into pts.
+ * Out, per list entry i: nrows [n], r [n][4], J [n][4][6] (rows >= nrows[i]: the word MH_POSE_DEBUG_FILL); of the whole
+ * list: cost (the sum of squared rows), H [21] (upper triangle of J^T J, row by row, scaled as the refine scales it) and
+ * g [6] (J^T r), each summed over the wavefront exactly as the refine sums them; devcams [n_images][16]: K [4], Rc [9],
+ * tc [3] of every camera as the kernel got them.
+ * MH_ERR_ARG, a message that begins with the call's name and nothing written: a null pointer; n_pts or n outside
+ * 1 .. MH_POSE_MAX_PTS; a list entry outside [0, n_pts); a kind-3 image word outside [0, n_images); n_images outside
+ * 1 .. MH_MAX_IMAGES; another (kind, res) pair; a phase other than 0, 1. */
+#define MH_POSE_MAX_PTS 2048
+#define MH_POSE_DEBUG_FILL 0xFFC0DE00u
+int mh_pose_debug_rows(mh_ctx* ctx, int kind, int res, int phase, float alpha, const float R[9], const float t[3],
+                       const mh_cam* cams, int n_images, const float* pts, int n_pts, const int32_t* list, int n,
+                       int32_t* nrows, float* r, float* J, float* cost, float* H, float* g, float* devcams);
+/* One LM step's linear algebra, the same work in all 64 lanes: *solved = whether (H + mu I) dx = -g had a Cholesky
+ * factor (H [21] packed as above); dx [6], Rn [9] = exp([dx[0..2]]x) R, tn [3] = t + dx[3..5] (without a solution: every
+ * word MH_POSE_DEBUG_FILL); *lanes_agree = the 64 lanes held the same words.  MH_ERR_ARG on a null pointer. */
+int mh_pose_debug_step(mh_ctx* ctx, const float H[21], const float g[6], float mu, const float R[9], const float t[3],
+                       int32_t* solved, float dx[6], float Rn[9], float tn[3], int32_t* lanes_agree);
+
 /* ---- FILTER (N1) ------------------------------------------------------------- */
 
 /* FILTER_PROJECTION_CPU::process for one image.  corr_host: all matches in

@@ -287,7 +287,11 @@ EXPORTS = [
     "mh_screen_reject_proved", "mh_match_set_accept", "mh_match_prerejected",
     "mh_image_gray_dev", "mh_image_gray_batch_dev", "mh_image_gray_host", "mh_frame_set_image_format",
     "mh_cluster_wms", "mh_wms_debug_state", "mh_frame_set_cluster_wms",
+    "mh_pose_debug_rows", "mh_pose_debug_step",
 ]
+POSE_DEBUG_FILL = 0xFFC0DE00   # MH_POSE_DEBUG_FILL
+POSE_MAX_PTS = 2048            # MH_POSE_MAX_PTS
+POSE_POINT_STRIDE = {0: 5, 1: 9, 2: 9, 3: 6}   # words of one point in mh_pose_debug_rows' pts, by kind
 COMM_ID_BYTES = 128      # MH_COMM_ID_BYTES
 EX2_OBJECTS = 62         # MH_EX2_OBJECTS
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)   # mh_allgather_fn
@@ -393,6 +397,9 @@ def load():
         L.mh_cluster_wms.argtypes = [vp, vp, vp, vp, i32, C.POINTER(mh_wms_params), vp, vp, i32, vp, i32, vp]
         L.mh_wms_debug_state.argtypes = [vp, vp, vp, vp, i32, C.POINTER(mh_wms_params), vp, vp, vp, vp]
         L.mh_frame_set_cluster_wms.argtypes = [vp, C.POINTER(mh_wms_params)]
+    if hasattr(L, "mh_pose_debug_rows"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
+        L.mh_pose_debug_rows.argtypes = [vp, i32, i32, i32, f32, vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.mh_pose_debug_step.argtypes = [vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp]
     L.mh_frame_set_depth_rules.argtypes = [vp, C.POINTER(mh_depth_rules), vp]
     L.mh_frame_enqueue_rest_strided.argtypes = [vp, vp, i32, vp, i32, i32, C.POINTER(mh_cam),
                                                 C.POINTER(mh_frame_params), C.c_uint64]
@@ -1571,6 +1578,42 @@ class Context:
         self._ck(self.L.mh_project_test(self.h, _ptr(p), _ptr(corr), n, C.byref(c), thr, _ptr(inl),
                                         _ptr(e2), C.byref(cnt)), "mh_project_test")
         return cnt.value, inl[:n].astype(bool), e2[:n]
+
+    def pose_debug_rows(self, kind, res, phase, alpha, R, t, cams, pts, lst):
+        """The LM refine's residual rows, Jacobians, cost and normal equations at pose (R [3,3], t [3]) as the shipped device
+        functions compute them (mh_pose_debug_rows).  cams: [(K, cam7), ...]; pts: the kernel's own layout, float32 words
+        [n_pts, POSE_POINT_STRIDE[kind]]; lst: point indices.  -> dict of nrows [n], r [n,4], J [n,4,6] (uint32 words:
+        rows a model does not have hold POSE_DEBUG_FILL), cost, H [21], g [6] (uint32 words) and devcams [n_images,16]
+        (K, Rc, tc as the kernels got them)."""
+        R = np.ascontiguousarray(R, np.float32).reshape(9)
+        t = np.ascontiguousarray(t, np.float32).reshape(3)
+        pts = np.ascontiguousarray(pts, np.float32)
+        lst = np.ascontiguousarray(lst, np.int32)
+        arr = (mh_cam * max(len(cams), 1))(*[make_cam(K, cam) for K, cam in cams])
+        n = len(lst)
+        nrows = np.zeros(n, np.int32)
+        r = np.zeros((n, 4), np.uint32)
+        J = np.zeros((n, 4, 6), np.uint32)
+        sums = np.zeros(28, np.uint32)
+        dc = np.zeros((len(cams), 16), np.float32)
+        self._ck(self.L.mh_pose_debug_rows(self.h, kind, res, phase, alpha, _ptr(R), _ptr(t), C.cast(arr, C.c_void_p), len(cams),
+                                           _ptr(pts), len(pts), _ptr(lst), n, _ptr(nrows), _ptr(r), _ptr(J), _ptr(sums),
+                                           _ptr(sums[1:]), _ptr(sums[22:]), _ptr(dc)), "mh_pose_debug_rows")
+        return dict(nrows=nrows, r=r, J=J, cost=sums[0], H=sums[1:22].copy(), g=sums[22:28].copy(), devcams=dc)
+
+    def pose_debug_step(self, H, g, mu, R, t):
+        """One LM step's linear algebra on the device (mh_pose_debug_step): solve6(H [21], g [6], mu), rotate_left(dx, R),
+        t + dx[3:] -> (solved, dx [6], Rn [3,3], tn [3], lanes_agree); without a solution the floats hold
+        POSE_DEBUG_FILL."""
+        H = np.ascontiguousarray(H, np.float32).reshape(21)
+        g = np.ascontiguousarray(g, np.float32).reshape(6)
+        R = np.ascontiguousarray(R, np.float32).reshape(9)
+        t = np.ascontiguousarray(t, np.float32).reshape(3)
+        dx, Rn, tn = np.zeros(6, np.float32), np.zeros(9, np.float32), np.zeros(3, np.float32)
+        ok, agree = C.c_int32(0), C.c_int32(0)
+        self._ck(self.L.mh_pose_debug_step(self.h, _ptr(H), _ptr(g), mu, _ptr(R), _ptr(t), C.byref(ok), _ptr(dx), _ptr(Rn),
+                                           _ptr(tn), C.byref(agree)), "mh_pose_debug_step")
+        return bool(ok.value), dx, Rn.reshape(3, 3), tn, bool(agree.value)
 
     # ---- FILTER ----
     def filter(self, corr, model_off, obj_model, obj_pose, K, cam, min_points, feature_distance, min_score):

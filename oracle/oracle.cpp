@@ -666,6 +666,13 @@ void orc_residuals(const float pose7[7], const float* uv, const float* xyz, int 
   residuals(pose7, uv, xyz, n, c, hx);
 }
 
+void orc_residuals_images(const float pose7[7], const float* uv, const float* xyz, const int32_t* img, int n,
+                          const float* K, const float* cam, int n_images, float* hx) {
+  std::vector<Camera> cams(n_images);
+  for (int i = 0; i < n_images; i++) camera_init(cams[i], K + 4 * i, cam + 7 * i);
+  residuals_images(pose7, uv, xyz, img, n, cams.data(), hx);
+}
+
 static int test_all_points(const float* pose7, const float* uv, const float* xyz, int n,
                            const Camera& c, float thr, uint8_t* inlier) {
   Mat34 T;

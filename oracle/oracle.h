@@ -97,6 +97,10 @@ void orc_project(const float pose7[7], const float* xyz, int n, const float K[4]
  * hx[2n] squared pixel residuals, (-z + 10) twice when z < 0. */
 void orc_residuals(const float pose7[7], const float* uv, const float* xyz, int n,
                    const float K[4], const float cam[7], float* hx);
+/* The same with every correspondence in its own image (LmData::image, :213-237): img[i] in [0, n_images) selects
+ * K[4 * img[i]..], cam[7 * img[i]..]. */
+void orc_residuals_images(const float pose7[7], const float* uv, const float* xyz, const int32_t* img, int n,
+                          const float* K, const float* cam, int n_images, float* hx);
 
 /* A12 testAllPoints (…REPROJECTION_CPU.hpp:166-180): inlier[i] = squared
  * reprojection error < thr.  Returns the inlier count. */

@@ -66,6 +66,7 @@ def lib():
         L.orc_meanshift.restype = C.c_int
         L.orc_project.argtypes = [_f32p, _f32p, C.c_int, _f32p, _f32p, _f32p]
         L.orc_residuals.argtypes = [_f32p, _f32p, _f32p, C.c_int, _f32p, _f32p, _f32p]
+        L.orc_residuals_images.argtypes = [_f32p, _f32p, _f32p, _i32p, C.c_int, _f32p, _f32p, C.c_int, _f32p]
         L.orc_test_all_points.argtypes = [_f32p, _f32p, _f32p, C.c_int, _f32p, _f32p, C.c_float, _u8p]
         L.orc_test_all_points.restype = C.c_int
         L.orc_optimize_camera.argtypes = [_f32p, _f32p, _f32p, C.c_int, _f32p, _f32p, C.c_int, _f32p]
@@ -169,6 +170,18 @@ def residuals(pose7, uv, xyz, K, cam):
     lib().orc_residuals(_c(pose7, np.float32), _c(uv, np.float32).reshape(-1),
                         _c(xyz, np.float32).reshape(-1), n, _c(K, np.float32),
                         _c(cam, np.float32), hx)
+    return hx
+
+
+def residuals_images(pose7, uv, xyz, img, Ks, cams):
+    """lmFuncQuat with every correspondence in its own image: Ks [m,4], cams [m,7], img [n] in [0, m)."""
+    n = uv.shape[0]
+    img = _c(img, np.int32)
+    Ks, cams = _c(Ks, np.float32).reshape(-1, 4), _c(cams, np.float32).reshape(-1, 7)
+    assert len(Ks) == len(cams) and (n == 0 or (img.min() >= 0 and img.max() < len(Ks)))
+    hx = np.empty(2 * n, np.float32)
+    lib().orc_residuals_images(_c(pose7, np.float32), _c(uv, np.float32).reshape(-1), _c(xyz, np.float32).reshape(-1),
+                               img, n, Ks.reshape(-1), cams.reshape(-1), len(Ks), hx)
     return hx
 
 
