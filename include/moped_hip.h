@@ -14,6 +14,8 @@
  *   mh_db_splice_image[s]  Moped::createPlanarModelsFromImages  src/moped.cpp:196-236 (image -> model of the store)
  *   mh_planar_rows_dev  ... its loop over detectedFeatures  src/moped.cpp:220-232
  *   mh_db_splice_view / mh_db_append_view / mh_db_append   (no counterpart: a model from Kinect views, grown view by view)
+ *   mh_db_merge_view / mh_db_keep_rows   moped-modeling-py src/MopedModeling.py:863-894, :915 (one descriptor per point from all
+ *                       its observations, nviews; here the plain mean, on the device, view by view)
  *   mh_models_write_xml the file samples/createModels/createModels.cpp:121-126 writes (sXML::print, include/sXML.hpp:146-170)
  *   mh_normalize        MATCH_ANN_CPU::norm              src/match/MATCH_ANN_CPU.hpp:54-57
  *   mh_match            MATCH_ANN_CPU::process search    src/match/MATCH_ANN_CPU.hpp:155-165
@@ -1637,6 +1639,57 @@ int mh_db_splice_view(mh_ctx* ctx, int op, int model, const uint8_t* gray_dev, c
 int mh_db_append_view(mh_ctx* ctx, int model, const uint8_t* gray_dev, const mh_view* view, int width, int height,
                       int double_size, int max_keypoints, const mh_view_spec* spec, int32_t* n_rows, float bbox[6],
                       int32_t stats[8], float* rows_desc_host, float* rows_xyz_host, int rows_cap);
+/* ---- re-seen points: merged, counted, pruned ----
+ * mh_db_append_view drops a keypoint the model already holds.  mh_db_merge_view folds it into the row it re-observes
+ * instead, as MOPED's model builder gives every model point one descriptor from all its observations and writes their
+ * number (moped-modeling-py MopedModeling.py:863-894, :915) -- with the plain mean where the builder runs a mean shift
+ * over dozens of observations: a model taught on the device sees a handful of views.
+ *
+ * The model's rows before the call are [row_begin, row_end) of the store.  For an old row r: d_r its descriptor as the
+ * store holds it (normalised), p_r its point, c_r >= 1 its view count (no array: 1).  The observations of r are the
+ * keypoints rule 7 drops whose nearest row is r, in list order i_1 < .. < i_k; q_i the keypoint's descriptor as MATCH saw
+ * it (the normalised scratch copy), X_i its X_model.  float32, one rounding per operation, no fused multiply-add:
+ *   a = q_i1; a = a + q_ij (j = 2 .. k); if k > 1: a = a / (float)k;   s  = d_r * (float)c_r + a
+ *   b = X_i1; b = b + X_ij (j = 2 .. k); if k > 1: b = b / (float)k;   p' = (p_r * (float)c_r + b) / (float)(c_r + 1)
+ * The new row is A1's normalisation of s by the code every upload uses, its point p', its count c_r + 1: a count of
+ * views, not of keypoints.  Rows without an observation keep their bits and their count.  Duplicates are judged against
+ * the rows present before the call; the merge does not feed back into the call's verdicts.
+ *
+ * The merge alone on given device arrays, like mh_view_rows_dev (same lists, view, spec and dup -- which is required):
+ * qn_desc_dev [cap][128] the normalised copy MATCH searched, old_desc_dev the store's [n_db_rows][128], views_in_dev
+ * [row_end - row_begin] or NULL.  Writes merged_idx_dev (relative to row_begin, ascending), merged_desc_dev = s (NOT
+ * normalised), merged_xyz_dev = p', at most merged_cap rows of each; *n_merged_dev = the full count even beyond
+ * merged_cap; views_out_dev [row_end - row_begin].  With the duplicate test off nothing merges.  Stream-ordered, no host
+ * wait.  No floating-point atomics: one wavefront sums a row's observations in list order, so the result depends neither
+ * on the grid nor on the order workgroups run in.  MH_ERR_ARG before anything is launched: whatever mh_view_rows_dev
+ * refuses, a null dup, old_desc_dev null or not 16-byte aligned, a null output, merged_cap < 0. */
+int mh_view_merge_dev(mh_ctx* ctx, const float* desc_dev, const float* qn_desc_dev, const float* xy_dev, const int32_t* n_dev,
+                      int cap, const mh_view* view, int width, int height, const mh_view_spec* spec, const mh_view_dup* dup,
+                      const float* old_desc_dev, const int32_t* views_in_dev, int32_t* merged_idx_dev, float* merged_desc_dev,
+                      float* merged_xyz_dev, int merged_cap, int32_t* n_merged_dev, int32_t* views_out_dev);
+/* A further view of model `model`, merged: mh_db_append_view's path ([UNDISTORTED_IMAGE] -> FEAT -> normalised copy ->
+ * MATCH -> selection) + the merge, into the edit's staging block, ONE host wait, one splice.  views_in_host [n_views_in]
+ * = the model's counts (n_views_in = its row count), or NULL / 0 = all ones; a count < 1 is refused.  *n_added new rows
+ * (byte for byte mh_db_append_view's, count 1), *n_merged rows merged; stats as mh_db_append_view; bbox over the model's
+ * final points.  rows_*_host: the new rows with FEAT's bits; merged_*_host (all three or none, at most merged_cap rows):
+ * the merged rows' index in the model, s and p'; views_out_host: the counts of the model's rows after the edit --
+ * views_out_cap >= rows before + min(max_keypoints, max_rows if > 0), what the view can add at most, else MH_ERR_ARG
+ * with nothing launched.
+ * Guarantee: a caller who keeps a host mirror of raw rows, overwrites mirror rows merged_idx with merged_desc /
+ * merged_xyz and appends the new rows holds a mirror whose fresh mh_db_upload_raw(normalize = 1) equals the store byte
+ * for byte.  Untouched rows are not normalised again.  With the duplicate test off (merge_ratio <= 0 or merge_dist < 0)
+ * or a store without rows the call is mh_db_append_view: n_merged = 0, the old counts followed by ones, no MATCH.
+ * MH_ERR_CAPACITY as mh_db_append_view; a sharded store is refused, like every edit. */
+int mh_db_merge_view(mh_ctx* ctx, int model, const uint8_t* gray_dev, const mh_view* view, int width, int height,
+                     int double_size, int max_keypoints, const mh_view_spec* spec, const int32_t* views_in_host, int n_views_in,
+                     int32_t* n_added, int32_t* n_merged, float bbox[6], int32_t stats[8], float* rows_desc_host,
+                     float* rows_xyz_host, int rows_cap, int32_t* merged_idx_host, float* merged_desc_host,
+                     float* merged_xyz_host, int merged_cap, int32_t* views_out_host, int views_out_cap);
+/* Model `model` keeps the rows whose flag is set (n_flags = its row count), in order: a stable compaction of the store's
+ * own rows (descriptor, norm term, point) on the device, then a REPLACE splice; nothing is normalised again, so the
+ * store equals a fresh mh_db_upload_raw(normalize = 1) of the mirror's kept rows.  No flag set: the empty model that
+ * mh_db_splice makes of n_rows = 0.  *n_rows: rows kept; bbox: their box. */
+int mh_db_keep_rows(mh_ctx* ctx, int model, const uint8_t* keep_host, int n_flags, int32_t* n_rows, float bbox[6]);
 /* n_views <= MH_MAX_BATCH views of one size -> models model_first .. model_first + n_views - 1 (INSERT): FEAT as ONE batch,
  * ONE selection launch, one read-back, then the single-model splice n_views times; byte for byte what mh_db_splice_view
  * gives per view.  n_rows [n_views], bbox [n_views][6], stats [n_views][8] (may be NULL); host rows as

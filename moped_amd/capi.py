@@ -278,6 +278,7 @@ EXPORTS = [
     "mh_planar_rows_dev", "mh_planar_rows_batch_dev", "mh_db_splice_image", "mh_db_splice_images",
     "mh_models_add_rows", "mh_models_write_xml",
     "mh_view_rows_dev", "mh_view_rows_batch_dev", "mh_db_append", "mh_db_splice_view", "mh_db_append_view", "mh_db_splice_views",
+    "mh_view_merge_dev", "mh_db_merge_view", "mh_db_keep_rows",
     "mh_depth_map_from_raw_dev", "mh_depth_map_from_raw_batch_dev", "mh_depth_map_from_raw_host",
     "mh_frame_run_kinect_raw_host",
     "mh_frame_debug_fetch_cluster_table_slot",
@@ -580,6 +581,12 @@ def load():
         L.mh_db_splice_view.argtypes = [vp, i32, i32, vp, pv, i32, i32, i32, i32, ps, C.POINTER(C.c_int32), vp, vp, vp, vp, i32]
         L.mh_db_append_view.argtypes = [vp, i32, vp, pv, i32, i32, i32, i32, ps, C.POINTER(C.c_int32), vp, vp, vp, vp, i32]
         L.mh_db_splice_views.argtypes = [vp, i32, vp, pv, i32, i32, i32, i32, i32, ps, vp, vp, vp, vp, vp, i32]
+    if hasattr(L, "mh_view_merge_dev"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
+        pv, ps, pd, pi = C.POINTER(mh_view), C.POINTER(mh_view_spec), C.POINTER(mh_view_dup), C.POINTER(C.c_int32)
+        L.mh_view_merge_dev.argtypes = [vp, vp, vp, vp, vp, i32, pv, i32, i32, ps, pd, vp, vp, vp, vp, vp, i32, vp, vp]
+        L.mh_db_merge_view.argtypes = [vp, i32, vp, pv, i32, i32, i32, i32, ps, vp, i32, pi, pi, vp, vp, vp, vp, i32,
+                                       vp, vp, vp, i32, vp, i32]
+        L.mh_db_keep_rows.argtypes = [vp, i32, vp, i32, pi, vp]
     if hasattr(L, "mh_object_hulls"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
         L.mh_object_hulls.argtypes = [vp, vp, vp, i32, C.POINTER(mh_cam), i32, vp, vp, vp, vp]
         L.mh_hull_debug_form.argtypes = [vp, i32]
@@ -1013,6 +1020,61 @@ class Context:
         spec's duplicate test is on.  Returns as db_splice_view: n_rows = rows added, bbox = the whole model's."""
         return self._view_edit("mh_db_append_view", (int(model),), gray_ptr, view, w, h, spec, double_size, max_keypoints,
                                want_rows)
+
+    def view_merge_dev(self, desc_ptr, qn_ptr, xy_ptr, n_ptr, cap, view: mh_view, w, h, spec: mh_view_spec, dup: mh_view_dup,
+                       old_desc_ptr, views_in_ptr, merged_idx_ptr, merged_desc_ptr, merged_xyz_ptr, merged_cap, n_merged_ptr,
+                       views_out_ptr):
+        """mh_view_merge_dev on device arrays: the keypoints rule 7 drops, folded into the rows they re-observe;
+        asynchronous."""
+        self._ck(self.L.mh_view_merge_dev(
+            self.h, C.c_void_p(desc_ptr), C.c_void_p(qn_ptr), C.c_void_p(xy_ptr), C.c_void_p(n_ptr), int(cap),
+            C.byref(view) if view is not None else None, int(w), int(h), C.byref(spec) if spec is not None else None,
+            C.byref(dup) if dup is not None else None, C.c_void_p(old_desc_ptr), C.c_void_p(views_in_ptr),
+            C.c_void_p(merged_idx_ptr), C.c_void_p(merged_desc_ptr), C.c_void_p(merged_xyz_ptr), int(merged_cap),
+            C.c_void_p(n_merged_ptr), C.c_void_p(views_out_ptr)), "mh_view_merge_dev")
+
+    def db_merge_view(self, model, gray_ptr, view: mh_view, w, h, spec: mh_view_spec, double_size=True, max_keypoints=4096,
+                      views_in=None, want_rows=True):
+        """mh_db_merge_view: a further view of model `model`; the keypoints the model already holds are folded into their
+        rows.  views_in: the model's view counts (None: all ones).  -> (n_added, n_merged, bbox[6], stats[8], views_out
+        [rows after], merged_idx [m], merged_desc [m,128] (s, not normalised), merged_xyz [m,3], desc [n,128], xyz [n,3]);
+        the last five are None without want_rows."""
+        _, rows = self.db_model_rows(model)
+        vin = None if views_in is None else np.ascontiguousarray(views_in, np.int32)
+        limit = min(max_keypoints, spec.max_rows) if spec is not None and spec.max_rows > 0 else max_keypoints
+        vout = np.zeros(rows + limit, np.int32)
+        na, nm = C.c_int32(0), C.c_int32(0)
+        bbox = np.zeros(6, np.float32)
+        stats = np.zeros(8, np.int32)
+        mcap = min(rows, max_keypoints) if want_rows else 0
+        d = np.zeros((max_keypoints, DIM), np.float32) if want_rows else None
+        x = np.zeros((max_keypoints, 3), np.float32) if want_rows else None
+        mi = np.zeros(max(mcap, 1), np.int32) if want_rows else None
+        md = np.zeros((max(mcap, 1), DIM), np.float32) if want_rows else None
+        mx = np.zeros((max(mcap, 1), 3), np.float32) if want_rows else None
+        opt = lambda a: _ptr(a) if a is not None else None
+        rc = self.L.mh_db_merge_view(self.h, int(model), C.c_void_p(gray_ptr), C.byref(view) if view is not None else None, w, h,
+                                     int(double_size), int(max_keypoints), C.byref(spec) if spec is not None else None,
+                                     opt(vin), 0 if vin is None else len(vin), C.byref(na), C.byref(nm), _ptr(bbox), _ptr(stats),
+                                     opt(d), opt(x), max_keypoints if want_rows else 0, opt(mi), opt(md), opt(mx), mcap,
+                                     _ptr(vout), len(vout))
+        # MH_ERR_CAPACITY: the edit is made, from the first max_keypoints keypoints of the list
+        self.planar_truncated = rc == MH_ERR_CAPACITY
+        self._ck(MH_OK if self.planar_truncated else rc, "mh_db_merge_view")
+        n, m = int(na.value), int(nm.value)
+        vout = vout[:rows + n].copy()
+        if want_rows:
+            return n, m, bbox, stats, vout, mi[:m].copy(), md[:m].copy(), mx[:m].copy(), d[:n].copy(), x[:n].copy()
+        return n, m, bbox, stats, vout, None, None, None, None, None
+
+    def db_keep_rows(self, model, keep):
+        """mh_db_keep_rows: model `model` keeps the rows whose flag is set, in order.  -> (n_rows, bbox[6])."""
+        keep = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8)
+        n = C.c_int32(0)
+        bbox = np.zeros(6, np.float32)
+        self._ck(self.L.mh_db_keep_rows(self.h, int(model), _ptr(keep) if len(keep) else None, len(keep), C.byref(n), _ptr(bbox)),
+                 "mh_db_keep_rows")
+        return int(n.value), bbox
 
     def db_splice_views(self, model_first, gray_ptrs, views, w, h, spec: mh_view_spec, double_size=True, max_keypoints=4096,
                         want_rows=False):

@@ -167,6 +167,13 @@ struct mh_ctx {
     mh::DevBuf<int32_t> stats;       // device [MH_MAX_BATCH][8]
     mh::DevBuf<float> qn, qnorm, m_d1, m_d2;   // device [cap][128], [cap], [cap], [cap]
     mh::DevBuf<int32_t> m_idx;       // device [cap]
+    // the merge of re-seen points (view_merge.hip): per keypoint the row it re-observes and its X_model, the marks of
+    // the touched rows; mh_db_merge_view's results: s as handed to the host, its normalised copy with the norm terms
+    mh::DevBuf<int32_t> mg_obs_row, mg_touched;   // device [cap], [rows]
+    mh::DevBuf<float> mg_obs_xyz;                 // device [cap][3]
+    mh::DevBuf<int32_t> mg_idx, mg_views_in, mg_views_out, mg_n;   // device [rows] x 3, [1]
+    mh::DevBuf<float> mg_desc, mg_desc_n, mg_norm, mg_xyz, mg_box;   // device [rows][128] x 2, [rows], [rows][3], [6]
+    mh::DevBuf<uint8_t> keep;                     // mh_db_keep_rows' flags, device [rows]
   } planar;
   int db_edit_route = 0;             // 0: the fused pass (db_splice_kernel); 1: device copies + the upload's preparation (mh_db_debug_route)
   hipEvent_t db_ev[2] = {nullptr, nullptr};   // around an edit's pass over the rows when timing is on (mh_db_edit_ms)
@@ -495,6 +502,33 @@ void launch_view_rows(const ViewArgs& a, int n_views, hipStream_t s);
 // MH_ERR_ARG (and ctx->err) for a spec, views or map size mh_db_splice_view refuses; fills a's spec, flags and views
 int view_args_check(mh_ctx* ctx, const char* who, const mh_view* views, int n_views, int width, int height,
                     const mh_view_spec* spec, ViewArgs* a);
+// view_merge.hip: the keypoints of view 0 of `v` that rule 7 drops (v.dup, v.dup_on; the selection's outputs in v are not
+// used), folded into the rows [v.dup.row_begin, v.dup.row_end) they re-observe -- the arithmetic above mh_view_merge_dev.
+struct MergeArgs {
+  ViewArgs v;
+  const float* qn;            // the list's descriptors as MATCH saw them, [cap][128]
+  const float* old_desc;      // the store's descriptors, [v.dup.n_db_rows][128]
+  const int32_t* views_in;    // [rows], or null: every count is 1
+  int32_t* obs_row;           // scratch [cap]
+  float* obs_xyz;             // scratch [cap][3]
+  int32_t* touched;           // scratch [rows]
+  int32_t* merged_idx;        // [merged_cap], relative to row_begin, ascending
+  float* merged_desc;         // [merged_cap][128]: s, not normalised
+  float* merged_desc_copy;    // a second copy, or null
+  float* merged_xyz;          // [merged_cap][3]
+  int merged_cap;
+  int32_t* n_merged;          // the full count
+  int32_t* views_out;         // [rows]
+};
+int launch_view_merge(mh_ctx* ctx, const MergeArgs& m);
+int ensure_view_merge(mh_ctx* ctx, int cap, int rows);   // the scratch arrays of ctx->planar
+void launch_view_merge_scatter(const int32_t* idx, const int32_t* n_merged, int cap, const float* desc, const float* norm,
+                               const float* xyz, float* stage_desc, float* stage_norm, float* stage_xyz, hipStream_t s);
+// bbox[6] = Model::boundingBox of xyz[0, n_fixed + *n_more) (n_more may be null)
+void launch_view_box(const float* xyz, int n_fixed, const int32_t* n_more, float* bbox, hipStream_t s);
+// rows [b, b + rows) of (desc, norm, xyz) whose flag is set, packed in order into the stage arrays; their box
+void launch_view_keep(const uint8_t* keep, int b, int rows, const float* desc, const float* norm, const float* xyz,
+                      float* stage_desc, float* stage_norm, float* stage_xyz, float* bbox, hipStream_t s);
 // api_sift.hip: the four counter words of image `slot` of the context's last extraction (device): [1] keys found, [2] != 0:
 // a list overflowed
 const int32_t* sift_counters_dev(mh_ctx* ctx, int slot);

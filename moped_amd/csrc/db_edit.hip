@@ -676,26 +676,16 @@ int ensure_view(mh_ctx* ctx, int cap, bool match) {
   return MH_OK;
 }
 
-// mh_db_splice_view (append = false: op, model) and mh_db_append_view (append = true: model)
-int view_edit(mh_ctx* ctx, const char* who, bool append, int op, int model, const uint8_t* gray_dev, const mh_view* view,
-              int width, int height, int double_size, int max_keypoints, const mh_view_spec* spec, int32_t* n_rows,
-              float bbox[6], int32_t stats[8], float* rows_desc_host, float* rows_xyz_host, int rows_cap) {
-  if (n_rows) *n_rows = 0;
-  if (!append && op != MH_DB_INSERT && op != MH_DB_REPLACE) return refuse(ctx, who, "the operation is MH_DB_INSERT or MH_DB_REPLACE");
-  ViewArgs a = {};
+// What mh_db_splice_view, mh_db_append_view and mh_db_merge_view share behind their checks: the buffers, [UNDISTORTED_IMAGE]
+// -> FEAT into ctx->planar, the model's rows so far (append: the box covers them, the duplicate test reads them) and, with
+// the duplicate test on, MATCH of a normalised copy as a frame's.  Fills a's lists and dup part.
+int view_front(mh_ctx* ctx, bool append, int model, const uint8_t* gray_dev, const mh_view* view, int width, int height,
+               int double_size, int cap, size_t stage, const mh_view_spec* spec, bool host_rows, ViewArgs& a) {
   int rc;
-  if ((rc = check_view_call(ctx, who, &gray_dev, view, 1, width, height, max_keypoints, spec, rows_desc_host, rows_xyz_host,
-                            rows_cap, &a)))
-    return rc;
-  if ((rc = check_edit(ctx, who, append ? (int)MH_DB_REPLACE : op, model))) return rc;   // (append: an existing model)
-  MH_HIP(ctx, hipSetDevice(ctx->device));
-  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
-  const int cap = max_keypoints;
-  const int limit = spec->max_rows > 0 ? std::min(cap, spec->max_rows) : cap;
   const bool match = append && spec->merge_ratio > 0.f && spec->merge_dist >= 0.f && ctx->N > 0;
-  if ((rc = ensure_planar(ctx, 1, cap, rows_desc_host != nullptr))) return rc;
+  if ((rc = ensure_planar(ctx, 1, cap, host_rows))) return rc;
   if ((rc = ensure_view(ctx, cap, match))) return rc;
-  if ((rc = ensure_stage(ctx, (size_t)limit))) return rc;
+  if ((rc = ensure_stage(ctx, stage))) return rc;
   if ((rc = planar_feat(ctx, &gray_dev, 1, width, height, double_size, cap, view->K))) return rc;
   mh_ctx::Planar& p = ctx->planar;
   if (append && ctx->N > 0) {   // the model's rows so far: the box covers them; the duplicate test reads them
@@ -716,22 +706,152 @@ int view_edit(mh_ctx* ctx, const char* who, bool append, int op, int model, cons
     a.dup.d2_dev = p.m_d2;
     a.dup_on = 1;
   }
-  // the selection writes the edit's staging block itself, as mh_db_splice_image's does
-  float* sd = ctx->db_stage;
   a.desc = p.desc;
   a.xy = p.xy;
   a.n = p.words;
   a.cap = cap;
-  a.desc_out = sd;
-  a.desc_copy = rows_desc_host ? (float*)p.rows_desc : nullptr;   // (normalisation is in place: the host gets FEAT's bits)
-  a.xyz_out = sd + stage_rows(ctx) * (DIM + 1);
+  a.desc_copy = host_rows ? (float*)p.rows_desc : nullptr;   // (normalisation is in place: the host gets FEAT's bits)
   a.out_pitch = 0;
-  a.out_cap = limit;
   a.n_out = p.words + MH_MAX_BATCH;
   a.bbox = p.box;
   a.stats = p.stats;
+  return MH_OK;
+}
+
+// mh_db_splice_view (append = false: op, model) and mh_db_append_view (append = true: model)
+int view_edit(mh_ctx* ctx, const char* who, bool append, int op, int model, const uint8_t* gray_dev, const mh_view* view,
+              int width, int height, int double_size, int max_keypoints, const mh_view_spec* spec, int32_t* n_rows,
+              float bbox[6], int32_t stats[8], float* rows_desc_host, float* rows_xyz_host, int rows_cap) {
+  if (n_rows) *n_rows = 0;
+  if (!append && op != MH_DB_INSERT && op != MH_DB_REPLACE) return refuse(ctx, who, "the operation is MH_DB_INSERT or MH_DB_REPLACE");
+  ViewArgs a = {};
+  int rc;
+  if ((rc = check_view_call(ctx, who, &gray_dev, view, 1, width, height, max_keypoints, spec, rows_desc_host, rows_xyz_host,
+                            rows_cap, &a)))
+    return rc;
+  if ((rc = check_edit(ctx, who, append ? (int)MH_DB_REPLACE : op, model))) return rc;   // (append: an existing model)
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
+  const int cap = max_keypoints;
+  const int limit = spec->max_rows > 0 ? std::min(cap, spec->max_rows) : cap;
+  if ((rc = view_front(ctx, append, model, gray_dev, view, width, height, double_size, cap, (size_t)limit, spec,
+                       rows_desc_host != nullptr, a)))
+    return rc;
+  // the selection writes the edit's staging block itself, as mh_db_splice_image's does
+  float* sd = ctx->db_stage;
+  a.desc_out = sd;
+  a.xyz_out = sd + stage_rows(ctx) * (DIM + 1);
+  a.out_cap = limit;
   launch_view_rows(a, 1, ctx->stream);
   return staged_image_edit(ctx, who, append, op, model, cap, limit, true, n_rows, bbox, stats, rows_desc_host, rows_xyz_host, rows_cap);
+}
+
+// mh_db_merge_view with the duplicate test on: the model's rows, the merged ones among them overwritten, and the new rows
+// behind them make up the staging block; one REPLACE splice.  Untouched rows are copied with their norm terms, so they
+// keep their bits; only merged and new rows are normalised.
+int merge_view_edit(mh_ctx* ctx, const char* who, int model, const uint8_t* gray_dev, const mh_view* view, int width, int height,
+                    int double_size, int cap, const mh_view_spec* spec, ViewArgs& a, const int32_t* views_in_host,
+                    int32_t* n_added, int32_t* n_merged, float bbox[6], int32_t stats[8], float* rows_desc_host,
+                    float* rows_xyz_host, int rows_cap, int32_t* merged_idx_host, float* merged_desc_host,
+                    float* merged_xyz_host, int merged_cap, int32_t* views_out_host) {
+  int rc;
+  const int limit = spec->max_rows > 0 ? std::min(cap, spec->max_rows) : cap;
+  const int b = ctx->store->model_begin[model], e = ctx->store->model_begin[model + 1], rows = e - b;
+  const int mcap = std::max(std::min(rows, cap), 1);   // a merged row has an observation of its own
+  if ((rc = view_front(ctx, true, model, gray_dev, view, width, height, double_size, cap, (size_t)rows + limit, spec,
+                       rows_desc_host != nullptr, a)))
+    return rc;
+  if ((rc = ensure_view_merge(ctx, cap, rows))) return rc;
+  mh_ctx::Planar& p = ctx->planar;
+  hipStream_t s = ctx->stream;
+  const size_t rows1 = (size_t)std::max(rows, 1);
+  MH_HIP(ctx, p.mg_idx.ensure((size_t)mcap, s));
+  MH_HIP(ctx, p.mg_views_in.ensure(rows1, s));
+  MH_HIP(ctx, p.mg_views_out.ensure(rows1, s));
+  MH_HIP(ctx, p.mg_n.ensure(1, s));
+  MH_HIP(ctx, p.mg_desc.ensure((size_t)mcap * DIM, s));
+  MH_HIP(ctx, p.mg_desc_n.ensure((size_t)mcap * DIM, s));
+  MH_HIP(ctx, p.mg_norm.ensure((size_t)mcap, s));
+  MH_HIP(ctx, p.mg_xyz.ensure((size_t)mcap * 3, s));
+  MH_HIP(ctx, p.mg_box.ensure(6, s));
+  float* sd = ctx->db_stage;
+  float* sn = sd + stage_rows(ctx) * DIM;
+  float* sx = sn + stage_rows(ctx);
+  const DbStore* st = ctx->store.get();
+  if (rows > 0) {
+    MH_HIP(ctx, hipMemcpyAsync(sd, st->desc + (size_t)b * DIM, (size_t)rows * DIM * sizeof(float), hipMemcpyDeviceToDevice, s));
+    MH_HIP(ctx, hipMemcpyAsync(sn, st->norm + b, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
+    MH_HIP(ctx, hipMemcpyAsync(sx, st->xyz + (size_t)b * 3, (size_t)rows * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (views_in_host)
+      MH_HIP(ctx, hipMemcpyAsync(p.mg_views_in, views_in_host, (size_t)rows * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  }
+  // the selection: the new rows behind the model's
+  a.desc_out = sd + (size_t)rows * DIM;
+  a.xyz_out = sx + (size_t)rows * 3;
+  a.out_cap = limit;
+  launch_view_rows(a, 1, s);
+  // the merge: s into mg_desc (the host's) and mg_desc_n, which the upload's own launch normalises; then over the staged rows
+  MergeArgs m = {};
+  m.v = a;
+  m.qn = p.qn;
+  m.old_desc = st->desc;
+  m.views_in = views_in_host ? (const int32_t*)p.mg_views_in : nullptr;
+  m.obs_row = p.mg_obs_row;
+  m.obs_xyz = p.mg_obs_xyz;
+  m.touched = p.mg_touched;
+  m.merged_idx = p.mg_idx;
+  m.merged_desc = p.mg_desc;
+  m.merged_desc_copy = p.mg_desc_n;
+  m.merged_xyz = p.mg_xyz;
+  m.merged_cap = rows > 0 ? mcap : 0;
+  m.n_merged = p.mg_n;
+  m.views_out = p.mg_views_out;
+  if ((rc = launch_view_merge(ctx, m))) return rc;
+  if (rows > 0) {
+    launch_normalize(p.mg_desc_n, p.mg_norm, mcap, s, p.mg_n);
+    launch_view_merge_scatter(p.mg_idx, p.mg_n, mcap, p.mg_desc_n, p.mg_norm, p.mg_xyz, sd, sn, sx, s);
+  }
+  launch_normalize(sd + (size_t)rows * DIM, sn + rows, limit, s, a.n_out);
+  launch_view_box(sx, rows, a.n_out, p.mg_box, s);
+  MH_HIP(ctx, hipGetLastError());
+  // the one host wait before the splice: the counts size it
+  int32_t kept = 0, nm = 0, head[4] = {0, 0, 0, 0}, stv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  float box[6];
+  MH_HIP(ctx, hipMemcpyAsync(&kept, a.n_out, sizeof kept, hipMemcpyDeviceToHost, s));
+  MH_HIP(ctx, hipMemcpyAsync(&nm, p.mg_n, sizeof nm, hipMemcpyDeviceToHost, s));
+  MH_HIP(ctx, hipMemcpyAsync(head, p.words + 2 * MH_MAX_BATCH, sizeof head, hipMemcpyDeviceToHost, s));
+  MH_HIP(ctx, hipMemcpyAsync(box, p.mg_box, sizeof box, hipMemcpyDeviceToHost, s));
+  MH_HIP(ctx, hipMemcpyAsync(stv, p.stats, sizeof stv, hipMemcpyDeviceToHost, s));
+  MH_HIP(ctx, hipStreamSynchronize(s));
+  if (kept < 0 || kept > limit || nm < 0 || nm > (rows > 0 ? mcap : 0)) {
+    ctx->err = std::string(who) + ": the selection or the merge reported a count outside its capacity";
+    return MH_ERR_HIP;
+  }
+  if (rows_desc_host && kept > 0) {
+    const size_t take = (size_t)std::min(kept, rows_cap);
+    MH_HIP(ctx, hipMemcpyAsync(rows_desc_host, p.rows_desc, take * DIM * sizeof(float), hipMemcpyDeviceToHost, s));
+    MH_HIP(ctx, hipMemcpyAsync(rows_xyz_host, sx + (size_t)rows * 3, take * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+  }
+  if (merged_idx_host && nm > 0) {
+    const size_t take = (size_t)std::min(nm, merged_cap);
+    MH_HIP(ctx, hipMemcpyAsync(merged_idx_host, p.mg_idx, take * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    MH_HIP(ctx, hipMemcpyAsync(merged_desc_host, p.mg_desc, take * DIM * sizeof(float), hipMemcpyDeviceToHost, s));
+    MH_HIP(ctx, hipMemcpyAsync(merged_xyz_host, p.mg_xyz, take * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+  }
+  if (views_out_host && rows > 0)
+    MH_HIP(ctx, hipMemcpyAsync(views_out_host, p.mg_views_out, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  // (ends with a wait for the stream: the host arrays are there)
+  if ((rc = splice_staged(ctx, MH_DB_REPLACE, model, rows + kept))) return rc;
+  if (views_out_host) std::fill(views_out_host + rows, views_out_host + rows + kept, 1);
+  if (n_added) *n_added = kept;
+  if (n_merged) *n_merged = nm;
+  if (bbox) std::memcpy(bbox, box, sizeof box);
+  if (stats) std::memcpy(stats, stv, sizeof stv);
+  if (head[2] || head[1] > cap) {
+    ctx->err = std::string(who) + ": more keypoints than max_keypoints (" + std::to_string(head[1]) + " found); the model has the first of the list";
+    return MH_ERR_CAPACITY;
+  }
+  return MH_OK;
 }
 
 }  // namespace
@@ -750,6 +870,82 @@ int mh_db_append_view(mh_ctx* ctx, int model, const uint8_t* gray_dev, const mh_
   if (!ctx) return MH_ERR_ARG;
   return view_edit(ctx, "mh_db_append_view", true, MH_DB_REPLACE, model, gray_dev, view, width, height, double_size,
                    max_keypoints, spec, n_rows, bbox, stats, rows_desc_host, rows_xyz_host, rows_cap);
+}
+
+int mh_db_merge_view(mh_ctx* ctx, int model, const uint8_t* gray_dev, const mh_view* view, int width, int height,
+                     int double_size, int max_keypoints, const mh_view_spec* spec, const int32_t* views_in_host, int n_views_in,
+                     int32_t* n_added, int32_t* n_merged, float bbox[6], int32_t stats[8], float* rows_desc_host,
+                     float* rows_xyz_host, int rows_cap, int32_t* merged_idx_host, float* merged_desc_host,
+                     float* merged_xyz_host, int merged_cap, int32_t* views_out_host, int views_out_cap) {
+  if (!ctx) return MH_ERR_ARG;
+  const char* who = "mh_db_merge_view";
+  if (n_added) *n_added = 0;
+  if (n_merged) *n_merged = 0;
+  ViewArgs a = {};
+  int rc;
+  if ((rc = check_view_call(ctx, who, &gray_dev, view, 1, width, height, max_keypoints, spec, rows_desc_host, rows_xyz_host,
+                            rows_cap, &a)))
+    return rc;
+  if ((rc = check_edit(ctx, who, MH_DB_REPLACE, model))) return rc;   // an existing model
+  const int rows = ctx->store->model_begin[model + 1] - ctx->store->model_begin[model];
+  if (const char* why = view_counts_why(views_in_host, n_views_in, rows)) return refuse(ctx, who, why);
+  if ((merged_idx_host == nullptr) != (merged_desc_host == nullptr) || (merged_idx_host == nullptr) != (merged_xyz_host == nullptr) ||
+      merged_cap < 0)
+    return refuse(ctx, who, "bad argument (the merged rows' host arrays come together; merged_cap >= 0)");
+  const int cap = max_keypoints;
+  const int limit = spec->max_rows > 0 ? std::min(cap, spec->max_rows) : cap;
+  // (the rows after the edit are known only behind the selection: the bound is what it can add at most)
+  if (views_out_host && (long long)views_out_cap < (long long)rows + limit)
+    return refuse(ctx, who, "views_out_cap is below the model's rows + the rows the view may add (max_rows, or max_keypoints)");
+  if (!(spec->merge_ratio > 0.f && spec->merge_dist >= 0.f && ctx->N > 0)) {
+    // the test off, or nothing to compare with: mh_db_append_view, the old counts followed by ones
+    int32_t kept = 0;
+    rc = view_edit(ctx, who, true, MH_DB_REPLACE, model, gray_dev, view, width, height, double_size, max_keypoints, spec, &kept,
+                   bbox, stats, rows_desc_host, rows_xyz_host, rows_cap);
+    if (rc != MH_OK && rc != MH_ERR_CAPACITY) return rc;
+    if (n_added) *n_added = kept;
+    if (views_out_host) {
+      if (views_in_host) std::copy(views_in_host, views_in_host + rows, views_out_host);
+      else std::fill(views_out_host, views_out_host + rows, 1);
+      std::fill(views_out_host + rows, views_out_host + rows + kept, 1);
+    }
+    return rc;
+  }
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
+  return merge_view_edit(ctx, who, model, gray_dev, view, width, height, double_size, cap, spec, a, views_in_host, n_added,
+                         n_merged, bbox, stats, rows_desc_host, rows_xyz_host, rows_cap, merged_idx_host, merged_desc_host,
+                         merged_xyz_host, merged_cap, views_out_host);
+}
+
+int mh_db_keep_rows(mh_ctx* ctx, int model, const uint8_t* keep_host, int n_flags, int32_t* n_rows, float bbox[6]) {
+  if (!ctx) return MH_ERR_ARG;
+  const char* who = "mh_db_keep_rows";
+  if (int rc = check_edit(ctx, who, MH_DB_REPLACE, model)) return rc;
+  const DbStore* st = ctx->store.get();
+  const int b = st->model_begin[model], rows = st->model_begin[model + 1] - b;
+  if (n_flags != rows || (rows > 0 && !keep_host)) return refuse(ctx, who, "n_flags is not the model's row count, or no flags");
+  MH_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc_stream = mh::use_stream(ctx)) return rc_stream;
+  mh_ctx::Planar& p = ctx->planar;
+  MH_HIP(ctx, p.keep.ensure((size_t)std::max(rows, 1), ctx->stream));
+  MH_HIP(ctx, p.mg_box.ensure(6, ctx->stream));
+  if (int rc = ensure_stage(ctx, (size_t)std::max(rows, 1))) return rc;
+  int kept = 0;
+  for (int r = 0; r < rows; ++r) kept += keep_host[r] != 0;
+  float* sd = ctx->db_stage;
+  float* sn = sd + stage_rows(ctx) * DIM;
+  float* sx = sn + stage_rows(ctx);
+  if (rows > 0) MH_HIP(ctx, hipMemcpyAsync(p.keep, keep_host, (size_t)rows, hipMemcpyHostToDevice, ctx->stream));
+  // the store's own rows, packed in order with their norm terms: nothing is normalised again
+  launch_view_keep(p.keep, b, rows, st->desc, st->norm, st->xyz, sd, sn, sx, p.mg_box, ctx->stream);
+  MH_HIP(ctx, hipGetLastError());
+  float box[6];
+  MH_HIP(ctx, hipMemcpyAsync(box, p.mg_box, sizeof box, hipMemcpyDeviceToHost, ctx->stream));
+  if (int rc = splice_staged(ctx, MH_DB_REPLACE, model, kept)) return rc;   // (ends with a wait for the stream)
+  if (n_rows) *n_rows = kept;
+  if (bbox) std::memcpy(bbox, box, sizeof box);
+  return MH_OK;
 }
 
 int mh_db_splice_views(mh_ctx* ctx, int model_first, const uint8_t* const* gray_dev, const mh_view* views, int n_views,

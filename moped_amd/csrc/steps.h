@@ -130,7 +130,7 @@ void launch_accept(const int32_t* idx1, const float* d1, const float* d2, int Q,
                    int32_t* out_idx, hipStream_t s);
 #ifdef __HIPCC__
 // MATCH's acceptance test, the one place it is written (group.hip: accept_kernel and the frames' group_kernel;
-// view_rows.hip: the duplicate test of an appended view): squared distances, fp32 division, exactly
+// view_rows_dev.h: the duplicate test of an appended or merged view): squared distances, fp32 division, exactly
 // `ds[0]/ds[1] < Ratio` (MATCH_ANN_CPU.hpp:165)
 __device__ __forceinline__ bool match_accepted(int32_t idx, float d1, float d2, float ratio) {
   return idx >= 0 && (__fdiv_rn(d1, d2) < ratio);

@@ -60,6 +60,33 @@ inline const char* view_dup_why(const mh_view_dup* dup) {
   return nullptr;
 }
 
+// why mh_view_merge_dev refuses its own arrays (the view, the spec and the map size are view_call_why's); dup is required
+inline const char* view_merge_why(const float* desc_dev, const float* qn_desc_dev, const float* xy_dev, const int32_t* n_dev, int cap,
+                                  const mh_view_dup* dup, const float* old_desc_dev, const int32_t* views_in_dev,
+                                  const int32_t* merged_idx_dev, const float* merged_desc_dev, const float* merged_xyz_dev,
+                                  int merged_cap, const int32_t* n_merged_dev, const int32_t* views_out_dev) {
+  if (!desc_dev || !qn_desc_dev || !xy_dev || !n_dev || cap <= 0) return "bad argument (a null list, or cap <= 0)";
+  if (((uintptr_t)desc_dev & 15) || ((uintptr_t)qn_desc_dev & 15) || ((uintptr_t)xy_dev & 7))
+    return "bad argument (descriptor arrays are 16-byte aligned, xy 8-byte)";
+  if (!dup) return "no mh_view_dup (the merge needs MATCH's answer and the model's rows)";
+  if (const char* why = view_dup_why(dup)) return why;
+  if (!old_desc_dev || ((uintptr_t)old_desc_dev & 15)) return "the store's descriptors are null or not 16-byte aligned";
+  if ((uintptr_t)views_in_dev & 3) return "a count array that is not 4-byte aligned";
+  if (!merged_idx_dev || !merged_desc_dev || !merged_xyz_dev || !n_merged_dev || !views_out_dev) return "a null output";
+  if ((uintptr_t)merged_desc_dev & 15) return "merged descriptors that are not 16-byte aligned";
+  if (merged_cap < 0) return "merged_cap < 0";
+  return nullptr;
+}
+
+// why a host-side array of view counts is refused for a model of n_rows rows (nullptr array: every count is 1)
+inline const char* view_counts_why(const int32_t* views, int n_views, int n_rows) {
+  if (!views) return n_views == 0 ? nullptr : "n_views_in != 0 without an array";
+  if (n_views != n_rows) return "n_views_in is not the model's row count";
+  for (int i = 0; i < n_views; ++i)
+    if (views[i] < 1 || views[i] == 0x7FFFFFFF) return "a view count < 1 (or one that cannot grow by one)";
+  return nullptr;
+}
+
 // mh_db_append: the per-model row ranges after n_rows rows went behind the last row of `model` (0 <= model < models);
 // begin = the ranges before, [models + 1]
 inline std::vector<int32_t> append_table(const std::vector<int32_t>& begin, int model, int n_rows) {

@@ -12,8 +12,8 @@
 #include <cmath>
 
 #include "context.h"
-#include "geom.h"
 #include "view_check.h"
+#include "view_rows_dev.h"
 
 using namespace mh;
 
@@ -21,20 +21,6 @@ namespace {
 
 constexpr int VR_THREADS = 1024;
 constexpr int VR_WAVES = VR_THREADS / 64;
-enum { VR_KEEP = 0, VR_PIXEL, VR_DEPTH, VR_FILL, VR_ROI, VR_BOX, VR_DUP, VR_LIMIT, VR_NONE };   // 1 .. 7 = the stats word
-
-struct Box6 {
-  float mn0, mn1, mn2, mx0, mx1, mx2;
-  // Pt::min / Pt::max (moped.hpp): a NaN coordinate leaves the box as it is
-  __device__ __forceinline__ void add(float x, float y, float z) {
-    mn0 = x < mn0 ? x : mn0;
-    mn1 = y < mn1 ? y : mn1;
-    mn2 = z < mn2 ? z : mn2;
-    mx0 = x > mx0 ? x : mx0;
-    mx1 = y > mx1 ? y : mx1;
-    mx2 = z > mx2 ? z : mx2;
-  }
-};
 
 __global__ __launch_bounds__(VR_THREADS) void view_rows_kernel(const ViewArgs a) {
   __shared__ int wcnt[VR_WAVES];
@@ -44,24 +30,14 @@ __global__ __launch_bounds__(VR_THREADS) void view_rows_kernel(const ViewArgs a)
   const int view = blockIdx.x;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const float* desc = a.desc + (size_t)view * a.cap * DIM;
-  const float2* xy = reinterpret_cast<const float2*>(a.xy) + (size_t)view * a.cap;
   float* desc_out = a.desc_out + (size_t)view * a.out_pitch * DIM;
   float* desc_copy = a.desc_copy ? a.desc_copy + (size_t)view * a.out_pitch * DIM : nullptr;
   float* xyz_out = a.xyz_out + (size_t)view * a.out_pitch * 3;
-  const float4* map = a.v[view].map;
-  const float* fill = a.spec.max_fill_distance >= 0.f ? a.v[view].fill : nullptr;
-  const int32_t* m_idx = a.dup_on ? a.dup.idx_dev + (size_t)view * a.cap : nullptr;
-  const float* m_d1 = a.dup_on ? a.dup.d1_dev + (size_t)view * a.cap : nullptr;
-  const float* m_d2 = a.dup_on ? a.dup.d2_dev + (size_t)view * a.cap : nullptr;
-  TM T;
-  tm_from_pose(T, a.v[view].pose, a.v[view].pose + 4);
+  ViewJudge J;
+  view_judge_init(J, a, view);
   const int n = min(max(a.n[view], 0), a.cap);
   const int limit = a.spec.max_rows > 0 ? min(a.out_cap, a.spec.max_rows) : a.out_cap;
-  const float r0 = a.spec.roi[0], r1 = a.spec.roi[1], r2 = a.spec.roi[2], r3 = a.spec.roi[3];
-  const float wf = (float)a.w, hf = (float)a.h;
-  const float far2 = __fmul_rn(a.spec.merge_dist, a.spec.merge_dist);
-  const float big = 10E10f;   // moped.cpp:107-108
-  Box6 bb = {big, big, big, -big, -big, -big};
+  Box6 bb = box6_empty();
   if (t < 8) drop_s[t] = 0;
   // the rows the model has already: the box is the whole model's after the edit
   if (a.dup.xyz_dev)
@@ -74,35 +50,7 @@ __global__ __launch_bounds__(VR_THREADS) void view_rows_kernel(const ViewArgs a)
     const int i = c0 + t;
     int why = VR_NONE;
     float x = 0.f, y = 0.f, z = 0.f;
-    if (i < n) {
-      const float2 p = xy[i];
-      const float u = p.x, v = p.y;
-      why = VR_KEEP;
-      // 1: NaN fails the comparisons, +-inf the bounds
-      if (!(u > -1.f && u < wf && v > -1.f && v < hf)) why = VR_PIXEL;
-      if (why == VR_KEEP) {
-        const size_t px = (size_t)(int)v * a.w + (int)u;   // (int): truncation, -0.5 -> 0 (DEPTHMAP_PROP_CPU.hpp:103)
-        const float4 m = map[px];
-        if (!(m.w >= 0.f)) why = VR_DEPTH;                                            // 2 (:131)
-        else if (fill && !(fill[px] <= a.spec.max_fill_distance)) why = VR_FILL;      // 3 (DEPTH_VERIFY_CPU.hpp:167-170)
-        else if (!a.roi_all && !(u >= r0 && u < r2 && v >= r1 && v < r3)) why = VR_ROI;   // 4
-        else {
-          tm_apply_inv(T.r, T.t, m.x, m.y, m.z, x, y, z);                             // 5
-          if (!a.box_all && !(x >= a.spec.box[0] && x <= a.spec.box[3] && y >= a.spec.box[1] && y <= a.spec.box[4] &&
-                              z >= a.spec.box[2] && z <= a.spec.box[5]))
-            why = VR_BOX;                                                             // 6
-          else if (m_idx) {                                                           // 7
-            const int32_t j = m_idx[i];
-            if (match_accepted(j, m_d1[i], m_d2[i], a.spec.merge_ratio) && j < a.dup.n_db_rows && a.dup.model_of_dev[j] == a.dup.model) {
-              const float* o = a.dup.xyz_dev + (size_t)j * 3;
-              const float dx = __fsub_rn(x, o[0]), dy = __fsub_rn(y, o[1]), dz = __fsub_rn(z, o[2]);
-              const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-              if (d2 <= far2) why = VR_DUP;
-            }
-          }
-        }
-      }
-    }
+    if (i < n) why = view_verdict(a, J, i, x, y, z);
     const bool keep = why == VR_KEEP;
     const unsigned long long bal = __ballot(keep);
     if (lane == 0) wcnt[wave] = __popcll(bal);
@@ -141,14 +89,7 @@ __global__ __launch_bounds__(VR_THREADS) void view_rows_kernel(const ViewArgs a)
     __syncthreads();   // wcnt and src_s are the next chunk's
   }
   // the box: wavefront, then workgroup (the accumulators hold no NaN)
-  for (int off = 32; off >= 1; off >>= 1) {
-    bb.mn0 = fminf(bb.mn0, __shfl_xor(bb.mn0, off));
-    bb.mn1 = fminf(bb.mn1, __shfl_xor(bb.mn1, off));
-    bb.mn2 = fminf(bb.mn2, __shfl_xor(bb.mn2, off));
-    bb.mx0 = fmaxf(bb.mx0, __shfl_xor(bb.mx0, off));
-    bb.mx1 = fmaxf(bb.mx1, __shfl_xor(bb.mx1, off));
-    bb.mx2 = fmaxf(bb.mx2, __shfl_xor(bb.mx2, off));
-  }
+  bb.wave_reduce();
   if (lane == 0) {
     red[wave][0] = bb.mn0;
     red[wave][1] = bb.mn1;

@@ -1,10 +1,14 @@
 // kinect_model_test -- a model taught from two Kinect views through createModelFromKinectViews_HIP, and put to use:
 //
-//   kinect_model_test view0.gray view0.depth view1.gray view1.depth width height name out_dir
+//   kinect_model_test [--merge] [--min-views K] view0.gray view0.depth view1.gray view1.depth width height name out_dir
 //
 // *.gray = width x height raw 8-bit pixels, *.depth = width x height x 4 raw floats (x, y, z, valid), the object's pose in
 // both views the identity.  The first view becomes model 0 of an empty store, the second is appended without the
 // keypoints the model holds already (merge ratio 0.8, 2 mm).  The model is saved through mh_models_add_rows +
+// With --merge the second view goes in through createMergedModelFromKinectViews_HIP instead: the keypoints the model holds
+// are folded into their rows, and with --min-views K the rows fewer than K views saw are dropped; a line
+//   VIEWS n1 n2 ...        (rows seen by 1, 2, ... views)
+// follows the MODEL line.  The model is saved through mh_models_add_rows +
 // mh_models_write_xml to <out_dir>/<name>.moped.xml, the store's arrays are dumped to <out_dir>/store.{desc,xyz,model}
 // (mh_db_debug_fetch), and view 0's image runs as a frame.  Prints
 //   MODEL <name> INDEX i ROWS n BBOX x0 y0 z0 x1 y1 z1 / FILE <path> / STORE ROWS N MODELS m /
@@ -38,8 +42,23 @@ static bool dump(mh_ctx* ctx, int which, size_t bytes, const std::string& path) 
 }
 
 int main(int argc, char** argv) {
-  if (argc != 9) {
-    std::fprintf(stderr, "usage: kinect_model_test view0.gray view0.depth view1.gray view1.depth width height name out_dir\n");
+  bool merge = false;
+  int min_views = 1;
+  while (argc > 1 && argv[1][0] == '-' && argv[1][1] == '-') {
+    const std::string opt = argv[1];
+    if (opt == "--merge") {
+      merge = true;
+      ++argv, --argc;
+    } else if (opt == "--min-views" && argc > 2) {
+      min_views = std::atoi(argv[2]);
+      argv += 2, argc -= 2;
+    } else {
+      break;
+    }
+  }
+  if (argc != 9 || min_views < 1 || (min_views > 1 && !merge)) {
+    std::fprintf(stderr, "usage: kinect_model_test [--merge] [--min-views K] view0.gray view0.depth view1.gray view1.depth width height name out_dir\n"
+                         "       (--min-views needs --merge)\n");
     return 2;
   }
   const int w = std::atoi(argv[5]), h = std::atoi(argv[6]);
@@ -69,12 +88,24 @@ int main(int argc, char** argv) {
 
   // teach
   int index = -1;
-  SP_Model model = createModelFromKinectViews_HIP(ctx, name, images, depthmaps, poses, &index);
+  vector<int> views;
+  SP_Model model = merge ? createMergedModelFromKinectViews_HIP(ctx, name, images, depthmaps, poses, min_views, &index, &views)
+                         : createModelFromKinectViews_HIP(ctx, name, images, depthmaps, poses, &index);
   if (!model) return 4;
   const vector<Model::IP>& ips = model->IPs["SIFT"];
   std::printf("MODEL %s INDEX %d ROWS %zu BBOX %.9g %.9g %.9g %.9g %.9g %.9g\n", model->name.c_str(), index, ips.size(),
               model->boundingBox[0][0], model->boundingBox[0][1], model->boundingBox[0][2], model->boundingBox[1][0],
               model->boundingBox[1][1], model->boundingBox[1][2]);
+  if (merge) {
+    vector<int> seen(3, 0);   // [k]: rows k views saw
+    for (size_t k = 0; k < views.size(); ++k) {
+      if ((size_t)views[k] >= seen.size()) seen.resize(views[k] + 1, 0);
+      ++seen[views[k]];
+    }
+    std::printf("VIEWS");
+    for (size_t k = 1; k < seen.size(); ++k) std::printf(" %d", seen[k]);
+    std::printf("\n");
+  }
 
   // save it: the rows as the store got them
   {

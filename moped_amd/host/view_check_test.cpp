@@ -129,6 +129,55 @@ int main() {
     CHECK(mh::view_dup_why(&b) == nullptr);
   }
 
+  // ---- mh_view_merge_dev's own arrays, mh_db_merge_view's host counts ----
+  {
+    alignas(16) static float d[8];
+    int32_t idx[1] = {0};
+    float f[3] = {0, 0, 0};
+    const mh_view_dup dup = {idx, f, f, idx, f, 10, 0, 2, 7};
+    CHECK(mh::view_merge_why(d, d, d, idx, 4, &dup, d, nullptr, idx, d, f, 0, idx, idx) == nullptr);
+    CHECK(mh::view_merge_why(d, d, d, idx, 4, &dup, d, idx, idx, d, f, 3, idx, idx) == nullptr);
+    CHECK(says(mh::view_merge_why(nullptr, d, d, idx, 4, &dup, d, nullptr, idx, d, f, 0, idx, idx), "null list"));
+    CHECK(says(mh::view_merge_why(d, nullptr, d, idx, 4, &dup, d, nullptr, idx, d, f, 0, idx, idx), "null list"));
+    CHECK(says(mh::view_merge_why(d, d, nullptr, idx, 4, &dup, d, nullptr, idx, d, f, 0, idx, idx), "null list"));
+    CHECK(says(mh::view_merge_why(d, d, d, nullptr, 4, &dup, d, nullptr, idx, d, f, 0, idx, idx), "null list"));
+    CHECK(says(mh::view_merge_why(d, d, d, idx, 0, &dup, d, nullptr, idx, d, f, 0, idx, idx), "cap <= 0"));
+    CHECK(says(mh::view_merge_why(d + 1, d, d, idx, 4, &dup, d, nullptr, idx, d, f, 0, idx, idx), "16-byte aligned"));
+    CHECK(says(mh::view_merge_why(d, d + 2, d, idx, 4, &dup, d, nullptr, idx, d, f, 0, idx, idx), "16-byte aligned"));
+    CHECK(says(mh::view_merge_why(d, d, d + 1, idx, 4, &dup, d, nullptr, idx, d, f, 0, idx, idx), "xy 8-byte"));
+    CHECK(says(mh::view_merge_why(d, d, d, idx, 4, nullptr, d, nullptr, idx, d, f, 0, idx, idx), "no mh_view_dup"));
+    mh_view_dup bad = dup;
+    bad.row_end = 11;
+    CHECK(says(mh::view_merge_why(d, d, d, idx, 4, &bad, d, nullptr, idx, d, f, 0, idx, idx), "rows outside"));
+    CHECK(says(mh::view_merge_why(d, d, d, idx, 4, &dup, nullptr, nullptr, idx, d, f, 0, idx, idx), "store's descriptors"));
+    CHECK(says(mh::view_merge_why(d, d, d, idx, 4, &dup, d + 1, nullptr, idx, d, f, 0, idx, idx), "store's descriptors"));
+    CHECK(says(mh::view_merge_why(d, d, d, idx, 4, &dup, d, nullptr, nullptr, d, f, 0, idx, idx), "null output"));
+    CHECK(says(mh::view_merge_why(d, d, d, idx, 4, &dup, d, nullptr, idx, nullptr, f, 0, idx, idx), "null output"));
+    CHECK(says(mh::view_merge_why(d, d, d, idx, 4, &dup, d, nullptr, idx, d, nullptr, 0, idx, idx), "null output"));
+    CHECK(says(mh::view_merge_why(d, d, d, idx, 4, &dup, d, nullptr, idx, d, f, 0, nullptr, idx), "null output"));
+    CHECK(says(mh::view_merge_why(d, d, d, idx, 4, &dup, d, nullptr, idx, d, f, 0, idx, nullptr), "null output"));
+    CHECK(says(mh::view_merge_why(d, d, d, idx, 4, &dup, d, nullptr, idx, d + 1, f, 0, idx, idx), "merged descriptors"));
+    CHECK(says(mh::view_merge_why(d, d, d, idx, 4, &dup, d, nullptr, idx, d, f, -1, idx, idx), "merged_cap < 0"));
+    // the counts: exactly n_rows of them are read (a read behind them is ASan's)
+    for (int n = 0; n <= 5; ++n) {
+      std::vector<int32_t> v(n, 1);
+      CHECK(mh::view_counts_why(n ? &v[0] : nullptr, n, n) == nullptr);
+      CHECK(mh::view_counts_why(nullptr, 0, n) == nullptr);
+      CHECK(n == 0 || says(mh::view_counts_why(nullptr, n, n), "without an array"));
+      if (n == 0) continue;
+      CHECK(says(mh::view_counts_why(&v[0], n, n + 1), "row count"));
+      CHECK(says(mh::view_counts_why(&v[0], n, n - 1), "row count"));
+      for (int k = 0; k < n; ++k) {
+        v[k] = k & 1 ? 0 : -3;
+        CHECK(says(mh::view_counts_why(&v[0], n, n), "count < 1"));
+        v[k] = 0x7FFFFFFF;
+        CHECK(says(mh::view_counts_why(&v[0], n, n), "cannot grow"));
+        v[k] = 0x7FFFFFFE;
+        CHECK(mh::view_counts_why(&v[0], n, n) == nullptr);
+      }
+    }
+  }
+
   // ---- mh_db_append's table: against model_of spliced by hand ----
   const int sizes[][5] = {{3, 0, 5, 0, 2}, {1, 1, 1, 1, 1}, {0, 0, 0, 0, 0}, {7, 0, 0, 0, 0}, {0, 0, 0, 0, 9}};
   for (size_t c = 0; c < sizeof sizes / sizeof sizes[0]; ++c)

@@ -56,6 +56,7 @@ class ShardedDB:
         self.model_of = np.ascontiguousarray(model_of[rows])
         self.n_models = n_models          # model ids stay global
         self.rank, self.world, self.assign = rank, world, assign
+        self.views = np.ones(len(rows), np.int32)   # per row: the views that saw it (merge_kinect_view counts; else 1)
 
     def splice(self, op: int, model: int, desc=None, xyz=None):
         """Keeps the host arrays in step with an edit of the resident store (Context.db_splice): model `model` inserted,
@@ -75,6 +76,7 @@ class ShardedDB:
         self.xyz = np.ascontiguousarray(np.concatenate([self.xyz[:b], xyz, self.xyz[e:]]))
         self.model_of = np.concatenate([self.model_of[:b], np.full(len(desc), model, np.int32),
                                         self.model_of[e:] + np.int32(delta)]).astype(np.int32)
+        self.views = np.concatenate([self.views[:b], np.ones(len(desc), np.int32), self.views[e:]]).astype(np.int32)
         self.n_models += delta
         n = len(self.model_of)
         self.rows = np.arange(n, dtype=np.int32)
@@ -95,6 +97,45 @@ class ShardedDB:
         self.desc = np.ascontiguousarray(np.concatenate([self.desc[:e], desc, self.desc[e:]]))
         self.xyz = np.ascontiguousarray(np.concatenate([self.xyz[:e], xyz, self.xyz[e:]]))
         self.model_of = np.concatenate([self.model_of[:e], np.full(len(desc), model, np.int32), self.model_of[e:]]).astype(np.int32)
+        self.views = np.concatenate([self.views[:e], np.ones(len(desc), np.int32), self.views[e:]]).astype(np.int32)
+        n = len(self.model_of)
+        self.rows = np.arange(n, dtype=np.int32)
+        self.row_lo, self.row_hi = 0, n
+        self.block_global_row = np.zeros(1 if n else 0, np.int32)
+        self.block_rows = np.full(1 if n else 0, n, np.int32)
+
+    def patch(self, model: int, idx, desc, xyz, views=None):
+        """Rows `idx` (relative to the model's first row) of an existing model overwritten (Context.db_merge_view's
+        merged rows: raw sums and points); views: the model's counts after the edit, for all its rows."""
+        if not 0 <= model < self.n_models:
+            raise ValueError("model index out of range")
+        if self.world > 1 or len(self.block_rows) > 1 or self.row_lo != 0:
+            raise ValueError("a sharded model database cannot be edited in place")
+        b, e = (int(np.searchsorted(self.model_of, model, side)) for side in ("left", "right"))
+        idx = np.asarray(idx, np.int64).reshape(-1)
+        if len(idx) and (idx.min() < 0 or idx.max() >= e - b):
+            raise ValueError("a row outside the model")
+        self.desc[b + idx] = np.asarray(desc, np.float32).reshape(-1, 128)
+        self.xyz[b + idx] = np.asarray(xyz, np.float32).reshape(-1, 3)
+        if views is not None:
+            self.views[b:e] = np.asarray(views, np.int32).reshape(e - b)
+
+    def keep(self, model: int, mask):
+        """An existing model keeps the rows whose flag is set, in order (Context.db_keep_rows)."""
+        if not 0 <= model < self.n_models:
+            raise ValueError("model index out of range")
+        if self.world > 1 or len(self.block_rows) > 1 or self.row_lo != 0:
+            raise ValueError("a sharded model database cannot be edited in place")
+        b, e = (int(np.searchsorted(self.model_of, model, side)) for side in ("left", "right"))
+        mask = np.asarray(mask).reshape(-1) != 0
+        if len(mask) != e - b:
+            raise ValueError("one flag per row of the model")
+        stay = np.ones(len(self.model_of), bool)
+        stay[b:e] = mask
+        self.desc = np.ascontiguousarray(self.desc[stay])
+        self.xyz = np.ascontiguousarray(self.xyz[stay])
+        self.model_of = np.ascontiguousarray(self.model_of[stay])
+        self.views = np.ascontiguousarray(self.views[stay])
         n = len(self.model_of)
         self.rows = np.arange(n, dtype=np.int32)
         self.row_lo, self.row_hi = 0, n
@@ -394,6 +435,43 @@ class FramePipeline:
         self.db.append(i, desc, xyz)
         self._warn_if_truncated(max_keypoints)
         return i, n, bbox, stats
+
+    def merge_kinect_view(self, i: int, image_dev: torch.Tensor, depth_dev: torch.Tensor, fill_dev=None, pose=None, roi=None,
+                          box=None, max_fill_distance=-1.0, max_rows=0, merge_ratio=0.8, merge_dist=0.002,
+                          max_keypoints: int = 4096, double_size: bool = True):
+        """A further view of model i, as extend_kinect_model, but the keypoints the model holds already are folded into the
+        rows they re-observe (Context.db_merge_view): the row's descriptor and point become the mean over its views, its
+        view count grows by one.  New rows count 1.  Returns (index, rows added, rows merged, bbox of the whole model,
+        stats[8]); model_views(i) has the counts; prune_model drops the rows few views saw."""
+        view, spec = self._view_args(depth_dev, fill_dev, pose, roi, box, max_fill_distance, max_rows, merge_ratio, merge_dist)
+        h, w = image_dev.shape
+        n, m, bbox, stats, views, midx, mdesc, mxyz, desc, xyz = self.ctxs[0].db_merge_view(
+            i, image_dev.data_ptr(), view, w, h, spec, double_size, max_keypoints, views_in=self.model_views(i), want_rows=True)
+        for c in self.ctxs[1:]:
+            c.db_adopt(self.ctxs[0])
+        self.db.patch(i, midx, mdesc, mxyz)
+        self.db.append(i, desc, xyz)
+        self.db.views[self.db.model_of == i] = views
+        self._warn_if_truncated(max_keypoints)
+        return i, n, m, bbox, stats
+
+    def model_views(self, i: int) -> np.ndarray:
+        """Per row of model i: how many views saw it (1 for rows that did not come through merge_kinect_view)."""
+        if not 0 <= i < self.db.n_models:
+            raise ValueError("model index out of range")
+        return self.db.views[self.db.model_of == i].copy()
+
+    def prune_model(self, i: int, min_views: int):
+        """Model i keeps the rows at least min_views views saw (Context.db_keep_rows: a compaction on the device, no
+        row is normalised again).  Returns (index, rows kept, bbox[6])."""
+        if self.world > 1 or self.exchange:
+            raise ValueError("a sharded model database cannot be edited in place: rebuild the pipeline")
+        mask = self.model_views(i) >= int(min_views)
+        n, bbox = self.ctxs[0].db_keep_rows(i, mask)
+        for c in self.ctxs[1:]:
+            c.db_adopt(self.ctxs[0])
+        self.db.keep(i, mask)
+        return i, n, bbox
 
     def append_model_rows(self, i: int, desc, xyz):
         """desc [n,128] raw descriptors, xyz [n,3] behind the last row of model i (Context.db_append), normalised on the
