@@ -32,6 +32,7 @@
  *   mh_project_test     testAllPoints / project()        …REPROJECTION_CPU.hpp:166-180, include/moped.hpp:330-354
  *   mh_filter           FILTER_PROJECTION_CPU::process   src/filter/FILTER_PROJECTION_CPU.hpp:80-162
  *   mh_filter_depth     FILTER_PROJECTION_DEPTH_CPU::process   moped3d .../filter/FILTER_PROJECTION_DEPTH_CPU.hpp:140-329
+ *   mh_depth_verify     DEPTH_VERIFY_CPU::process        moped3d .../depthVerify/DEPTH_VERIFY_CPU.hpp:86-208
  *   mh_frame_*          the per-frame loop over those steps, MopedPimpl::processImages
  *                                                        src/moped.cpp:166-194 (device-resident form)
  *
@@ -505,6 +506,73 @@ int mh_frame_route(mh_ctx* ctx, int32_t out[4]);
  * object slot and no LDS -- the form the POSE tails of a fused frame run.  The results are the same bit for bit; frames
  * ignore the setting. */
 int mh_filter_depth_debug_form(mh_ctx* ctx, int form);
+
+/* ---- DEPTH_VERIFY (moped3d) ---------------------------------------------------- */
+
+#define MH_DEPTH_VERIFY_CHUNK 192   /* terms of one round of the workgroup form (mh_depth_verify_debug_form 0) */
+
+/* DEPTH_VERIFY_CPU (moped3d/libmoped/src/depthVerify/DEPTH_VERIFY_CPU.hpp): the check of every object that left
+ * FILTER2 against the Kinect map.  The constructor's arguments (:64-66): */
+typedef struct {
+  float feature_distance;  /* FeatureDistance: a match with projectionError below it is plausible (:132) */
+  float max_multiplier;    /* MaxMultiplier: the cap of keypointCount / usedKeypointCount (:194-196) */
+  float max_distance;      /* MaxDistance: a keypoint on a pixel with a fill distance above it is skipped (:168) */
+  float depth_fraction;    /* DepthFraction: cauchyScale = DepthFraction * kinectDepth (:182) */
+} mh_depth_verify_params;
+
+/* What the class computes for one object, and prints (:192-202) */
+typedef struct {
+  float qs_raw, is_raw;    /* QS and IS as :192 prints them: the two ordered chains (:135, :188) */
+  float multiplier;        /* (Float)keypointCount / usedKeypointCount (:191) AFTER the cap (:194-196) */
+  float qs, is;            /* QS / plausibleMatchCount, IS * multiplier / keypointCount (:197-200) */
+  int32_t plausible;       /* plausibleMatchCount (:133) */
+  int32_t used;            /* usedKeypointCount (:171) */
+  int32_t keypoints;       /* keypointCount (:156): the rows the store holds for the model */
+  int32_t keep;            /* 0: IS > QS, the reference erases the object (:204-206) */
+} mh_verify_record;
+
+/* DEPTH_VERIFY_CPU::process (:86-208) for n_obj objects, a synchronous round trip like mh_filter_depth.
+ *   corr_host / model_off[n_models + 1]: the frame's matches, matches[m] = corr_host[model_off[m] .. model_off[m + 1])
+ *   (:128); obj_model[n_obj] (modelNum, :121-127: indices, not names), obj_pose[n_obj][7]; cam: the image the matches
+ *   were found in (project(), :129); depth_cam: the depth map's K and pose (:105, :162).
+ *   The map and its distance map are the ones the context holds (mh_frame_set_depth_image[_host]; :98-116); without a
+ *   distance map -- the reference would dereference null -- there is no distance test (:168) and every pixel is used.
+ *   The keypoints (:142-150) are the rows the resident store holds for the model, in row order: one descriptor type.
+ *   records[n_obj]: every object's numbers in list order; nothing is erased, `keep` is the verdict (:204).
+ * Both scores are the reference's ordered Float += double chains, word for word.  A keypoint that projects off the map
+ * (the reference reads outside the buffer there, :167 / :173), or to a coordinate that is NaN, infinite or outside int,
+ * is counted in keypointCount and not used.
+ * MH_ERR_ARG before any launch, records untouched: a null pointer, no depth map, no database, a store whose rows are not
+ * grouped by model in ascending order or that was uploaded in blocks (mh_object_hulls' conditions), n_models other than
+ * the store's, a model index outside the database, offsets that decrease.  n_obj = 0: MH_OK, nothing is done. */
+int mh_depth_verify(mh_ctx* ctx, const mh_corr* corr_host, const int32_t* model_off, int n_models,
+                    const int32_t* obj_model, const float* obj_pose, int n_obj, const mh_cam* cam,
+                    const mh_cam* depth_cam, const mh_depth_verify_params* prm, mh_verify_record* records);
+
+/* Debug entry, like mh_filter_depth_debug_form: the device form mh_depth_verify runs.  0 (default): a workgroup per
+ * object, three wavefronts produce MH_DEPTH_VERIFY_CHUNK terms a round into LDS and one chains them.  1: one wavefront
+ * per object and no LDS.  The records are the same bit for bit. */
+int mh_depth_verify_debug_form(mh_ctx* ctx, int form);
+
+/* DEPTH_VERIFY behind the frames: prm != NULL switches the step on for the frames and batches enqueued afterwards (NULL,
+ * the default: off), depth_cam is the depth map's K and pose (:105, :162).  Such a frame runs ONE more launch behind
+ * FILTER2 and in front of the hull launch (mh_frame_set_hulls) -- a merged batch one launch for all its slots, and it
+ * stays merged -- stream-ordered, without a host wait, the object counts read on the device.  Every object of every
+ * result slot is scored against its own frame's map (mh_frame_set_depth_image[_batch | _host]) and its own frame's match
+ * lists; a record per object is written in the order BEFORE the erase; then the objects with IS > QS (:204-206) are
+ * removed from the result slot, stably, and its object count is lowered: every fetch path, every delivery and the hulls
+ * see the reference's list.  counts[] stay as they are (counts[3] = objects after FILTER2's erase).  The frame's objects
+ * come to the host by a copy from the result slot (FILTER2's direct write into the host's block is off for such a frame).
+ * Frames that stop after POSE (run_stage2 = 0) and stepped frames (mh_step_*) ignore the setting.
+ * While it is on, refused with MH_ERR_ARG before anything is enqueued: no depth map, several cameras, the sharded entry
+ * points (mh_frame_enqueue_sharded*, mh_frame_enqueue_rest*), a store mh_depth_verify refuses. */
+int mh_frame_set_depth_verify(mh_ctx* ctx, const mh_depth_verify_params* prm, const mh_cam* depth_cam);
+/* The records of the frame in result slot `slot` (mh_frame_fetch_verify: slot 0), one per object that left FILTER2, in
+ * that order: *n_records = their number, the first min(*n_records, max_records) are written.  The objects
+ * mh_frame_fetch[_slot] returns are those with keep = 1, in the same order.  Synchronises the context's stream.
+ * MH_ERR_ARG: the frame enqueued last into that slot ran without the verification. */
+int mh_frame_fetch_verify_slot(mh_ctx* ctx, int slot, int max_records, mh_verify_record* records, int32_t* n_records);
+int mh_frame_fetch_verify(mh_ctx* ctx, int max_records, mh_verify_record* records, int32_t* n_records);
 
 /* ---- object hulls ------------------------------------------------------------ */
 

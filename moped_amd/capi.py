@@ -120,6 +120,18 @@ class mh_filter_depth_params(C.Structure):
     _fields_ = [("plausible_sq_distance", C.c_float), ("depth_fraction", C.c_float), ("min_keypoint_fraction", C.c_float)]
 
 
+class mh_depth_verify_params(C.Structure):
+    """DEPTH_VERIFY_CPU's constructor arguments (FeatureDistance, MaxMultiplier, MaxDistance, DepthFraction)."""
+    _fields_ = [("feature_distance", C.c_float), ("max_multiplier", C.c_float), ("max_distance", C.c_float),
+                ("depth_fraction", C.c_float)]
+
+
+# mh_verify_record: one object's numbers as DEPTH_VERIFY_CPU prints them, and the verdict
+VERIFY_DTYPE = np.dtype([("qs_raw", "<f4"), ("is_raw", "<f4"), ("multiplier", "<f4"), ("qs", "<f4"), ("is", "<f4"),
+                         ("plausible", "<i4"), ("used", "<i4"), ("keypoints", "<i4"), ("keep", "<i4")])
+DEPTH_VERIFY_CHUNK = 192   # MH_DEPTH_VERIFY_CHUNK
+
+
 class mh_planar_spec(C.Structure):
     _fields_ = [("form", C.c_int32), ("scale", C.c_float), ("K", C.c_float * 4), ("z", C.c_float), ("roi", C.c_float * 4),
                 ("max_rows", C.c_int32)]
@@ -236,6 +248,14 @@ def make_filter_depth_params(p):
     return mh_filter_depth_params(float(a), float(b), float(c))
 
 
+def make_depth_verify_params(p):
+    """None, an mh_depth_verify_params or (feature_distance, max_multiplier, max_distance, depth_fraction)."""
+    if p is None or isinstance(p, mh_depth_verify_params):
+        return p
+    a, b, c, d = p
+    return mh_depth_verify_params(float(a), float(b), float(c), float(d))
+
+
 EXPORTS = [
     "mh_create", "mh_destroy", "mh_last_error", "mh_set_stream", "mh_synchronize", "mh_reserve",
     "mh_db_upload", "mh_db_size", "mh_normalize", "mh_match", "mh_normalize_match", "mh_match_local_dev", "mh_match_local_counted_dev",
@@ -289,6 +309,8 @@ EXPORTS = [
     "mh_image_gray_dev", "mh_image_gray_batch_dev", "mh_image_gray_host", "mh_frame_set_image_format",
     "mh_cluster_wms", "mh_wms_debug_state", "mh_frame_set_cluster_wms",
     "mh_pose_debug_rows", "mh_pose_debug_step",
+    "mh_depth_verify", "mh_depth_verify_debug_form",
+    "mh_frame_set_depth_verify", "mh_frame_fetch_verify_slot", "mh_frame_fetch_verify",
 ]
 POSE_DEBUG_FILL = 0xFFC0DE00   # MH_POSE_DEBUG_FILL
 POSE_MAX_PTS = 2048            # MH_POSE_MAX_PTS
@@ -587,6 +609,13 @@ def load():
         L.mh_db_merge_view.argtypes = [vp, i32, vp, pv, i32, i32, i32, i32, ps, vp, i32, pi, pi, vp, vp, vp, vp, i32,
                                        vp, vp, vp, i32, vp, i32]
         L.mh_db_keep_rows.argtypes = [vp, i32, vp, i32, pi, vp]
+    if hasattr(L, "mh_depth_verify"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
+        L.mh_depth_verify.argtypes = [vp, vp, vp, i32, vp, vp, i32, C.POINTER(mh_cam), C.POINTER(mh_cam),
+                                      C.POINTER(mh_depth_verify_params), vp]
+        L.mh_depth_verify_debug_form.argtypes = [vp, i32]
+        L.mh_frame_set_depth_verify.argtypes = [vp, C.POINTER(mh_depth_verify_params), C.POINTER(mh_cam)]
+        L.mh_frame_fetch_verify_slot.argtypes = [vp, i32, i32, vp, C.POINTER(C.c_int32)]
+        L.mh_frame_fetch_verify.argtypes = [vp, i32, vp, C.POINTER(C.c_int32)]
     if hasattr(L, "mh_object_hulls"):   # (absent only in an older build named by MH_LIB_PATH for an A/B run)
         L.mh_object_hulls.argtypes = [vp, vp, vp, i32, C.POINTER(mh_cam), i32, vp, vp, vp, vp]
         L.mh_hull_debug_form.argtypes = [vp, i32]
@@ -1883,6 +1912,48 @@ class Context:
         """Debug: the device form filter_depth() scores with -- 0 the workgroup form (default), 1 the wave form the fused
         POSE tails run.  Frames ignore it."""
         self._ck(self.L.mh_filter_depth_debug_form(self.h, int(form)), "mh_filter_depth_debug_form")
+
+    # ---- DEPTH_VERIFY ----
+    def depth_verify(self, corr, model_off, obj_model, obj_pose, K, cam, depth_K, depth_cam, params):
+        """mh_depth_verify: DEPTH_VERIFY_CPU::process for every object against the depth map the context holds
+        (frame_set_depth_image[_host]) and the resident store's keypoints -> records [n_obj] (VERIFY_DTYPE), nothing
+        erased; params: (FeatureDistance, MaxMultiplier, MaxDistance, DepthFraction)."""
+        corr = np.ascontiguousarray(corr, CORR_DTYPE)
+        model_off = np.ascontiguousarray(model_off, np.int32)
+        obj_model = np.ascontiguousarray(obj_model, np.int32).reshape(-1)
+        obj_pose = np.ascontiguousarray(obj_pose, np.float32).reshape(-1, 7)
+        n = obj_model.shape[0]
+        assert obj_pose.shape[0] == n
+        rec = np.zeros(max(n, 1), VERIFY_DTYPE)
+        c, dc = make_cam(K, cam), make_cam(depth_K, depth_cam)
+        prm = make_depth_verify_params(params)
+        self._ck(self.L.mh_depth_verify(self.h, _ptr(corr), _ptr(model_off), len(model_off) - 1, _ptr(obj_model),
+                                        _ptr(obj_pose), n, C.byref(c), C.byref(dc), C.byref(prm), _ptr(rec)), "mh_depth_verify")
+        return rec[:n]
+
+    def frame_set_depth_verify(self, params, depth_K=None, depth_cam=None):
+        """mh_frame_set_depth_verify: frames and batches enqueued afterwards run DEPTH_VERIFY behind FILTER2 and deliver
+        the objects it leaves; params: (FeatureDistance, MaxMultiplier, MaxDistance, DepthFraction) or None = off;
+        depth_K, depth_cam: the depth map's camera."""
+        prm = make_depth_verify_params(params)
+        if prm is None:
+            self._ck(self.L.mh_frame_set_depth_verify(self.h, None, None), "mh_frame_set_depth_verify")
+            return
+        dc = make_cam(depth_K, depth_cam)
+        self._ck(self.L.mh_frame_set_depth_verify(self.h, C.byref(prm), C.byref(dc)), "mh_frame_set_depth_verify")
+
+    def frame_fetch_verify(self, slot=0, max_records=4096):
+        """mh_frame_fetch_verify_slot: the records (VERIFY_DTYPE) of the frame in result slot `slot`, one per object that
+        left FILTER2, in that order; the frame's fetched objects are those with keep = 1."""
+        rec = np.zeros(max(max_records, 1), VERIFY_DTYPE)
+        n = C.c_int32(0)
+        self._ck(self.L.mh_frame_fetch_verify_slot(self.h, int(slot), int(max_records), _ptr(rec), C.byref(n)),
+                 "mh_frame_fetch_verify_slot")
+        return rec[:min(n.value, max_records)].copy()
+
+    def depth_verify_debug_form(self, form):
+        """mh_depth_verify_debug_form: 0 a workgroup per object (default), 1 a wavefront per object."""
+        self._ck(self.L.mh_depth_verify_debug_form(self.h, int(form)), "mh_depth_verify_debug_form")
 
     # ---- object hulls ----
     def object_hulls(self, obj_model, obj_pose, K, cam, max_vertices=64):

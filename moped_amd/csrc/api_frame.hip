@@ -427,6 +427,54 @@ int mh_frame_fetch_hulls(mh_ctx* ctx, int max_objects, int max_vertices, float* 
   return mh_frame_fetch_hulls_slot(ctx, 0, max_objects, max_vertices, hull_xy_host, n_vertices, n_behind, bbox_uv_host, n_objects);
 }
 
+/* ---- DEPTH_VERIFY behind the frames (depth_verify.hip) ---- */
+
+int mh_frame_set_depth_verify(mh_ctx* ctx, const mh_depth_verify_params* prm, const mh_cam* depth_cam) {
+  if (!ctx) return MH_ERR_ARG;
+  if (prm && !depth_cam) {
+    ctx->err = "mh_frame_set_depth_verify: the depth map's camera is missing";
+    return MH_ERR_ARG;
+  }
+  ctx->verify.on = prm != nullptr;
+  if (prm) {
+    ctx->verify.prm = *prm;
+    ctx->verify.cam = *depth_cam;
+  }
+  return MH_OK;
+}
+
+// mh_frame_fetch_verify[_slot] (`who`: the entry point, for its messages)
+static int fetch_verify(mh_ctx* ctx, const char* who, int slot, int max_records, mh_verify_record* records, int32_t* n_records) {
+  if (!ctx) return MH_ERR_ARG;
+  if (!n_records || max_records < 0 || (max_records > 0 && !records)) {
+    ctx->err = std::string(who) + ": bad argument";
+    return MH_ERR_ARG;
+  }
+  mh_ctx::VerifyState& vs = ctx->verify;
+  if (!ctx->fs || slot < 0 || slot >= MH_MAX_BATCH || !vs.slot_on[slot] || !vs.block) {
+    ctx->err = std::string(who) + ": the frame in that result slot ran without DEPTH_VERIFY (mh_frame_set_depth_verify before "
+               "it is enqueued)";
+    return MH_ERR_ARG;
+  }
+  if (int rc_enter = mh::enter(ctx)) return rc_enter;
+  if (int rc = ensure_pinned(ctx, vs.slot_bytes)) return rc;
+  MH_HIP(ctx, hipMemcpyAsync(ctx->pinned.p, vs.block.p + (size_t)slot * vs.slot_bytes, vs.slot_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const int32_t* const head = reinterpret_cast<const int32_t*>(ctx->pinned.p);
+  *n_records = head[0];
+  const int take = std::min(std::min(head[0], max_records), ctx->fs->max_objects);
+  if (take > 0) std::memcpy(records, head + 4, (size_t)take * sizeof(mh_verify_record));
+  return MH_OK;
+}
+
+int mh_frame_fetch_verify_slot(mh_ctx* ctx, int slot, int max_records, mh_verify_record* records, int32_t* n_records) {
+  return fetch_verify(ctx, "mh_frame_fetch_verify_slot", slot, max_records, records, n_records);
+}
+
+int mh_frame_fetch_verify(mh_ctx* ctx, int max_records, mh_verify_record* records, int32_t* n_records) {
+  return fetch_verify(ctx, "mh_frame_fetch_verify", 0, max_records, records, n_records);
+}
+
 int mh_frame_fetch_batch_hulls_async(mh_ctx* ctx, int B, int max_objects, void* host_block) {
   if (!ctx) return MH_ERR_ARG;
   if (!host_block || B < 1 || B > MH_MAX_BATCH || max_objects < 1) {

@@ -3,6 +3,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "depth_verify.h"
 #include "frame.h"
 #include "hull.h"
 
@@ -769,6 +770,89 @@ int mh_hull_debug_form(mh_ctx* ctx, int form) {
     return MH_ERR_ARG;
   }
   ctx->hull_debug_form = form;
+  return MH_OK;
+}
+
+// DEPTH_VERIFY_CPU::process (moped3d/libmoped/src/depthVerify/DEPTH_VERIFY_CPU.hpp:86-208) for n_obj objects:
+// depth_verify.hip
+int mh_depth_verify(mh_ctx* ctx, const mh_corr* corr_host, const int32_t* model_off, int n_models,
+                    const int32_t* obj_model, const float* obj_pose, int n_obj, const mh_cam* cam,
+                    const mh_cam* depth_cam, const mh_depth_verify_params* prm, mh_verify_record* records) {
+  if (!ctx) return MH_ERR_ARG;
+  auto refuse = [&](const char* why) {
+    ctx->err = std::string("mh_depth_verify: ") + why;
+    return MH_ERR_ARG;
+  };
+  if (n_obj < 0 || n_models < 0) return refuse("bad argument");
+  if (!model_off || !cam || !depth_cam || !prm) return refuse("null pointer");
+  if (n_obj > 0 && (!obj_model || !obj_pose || !records)) return refuse("null pointer");
+  if (!ctx->depth_img.img) return refuse("no depth map (mh_frame_set_depth_image / mh_frame_set_depth_image_host)");
+  const DbStore* st = ctx->store.get();
+  if (!st) return refuse("no model database");
+  if (!st->grouped) return refuse("the rows of the store are not grouped by model in ascending order");
+  if (st->n_blocks > 1) return refuse("the store was uploaded in blocks (a sharded store has no whole models)");
+  if (n_models != st->n_models) return refuse("n_models is not the number of models of the database");
+  if (model_off[0] != 0) return refuse("offsets must start at 0");
+  for (int m = 0; m < n_models; ++m)
+    if (model_off[m + 1] < model_off[m]) return refuse("offsets must not decrease");
+  const int M = model_off[n_models];
+  if (M > 0 && !corr_host) return refuse("null pointer");
+  for (int o = 0; o < n_obj; ++o)
+    if (obj_model[o] < 0 || obj_model[o] >= n_models) return refuse("object model outside [0, n_models)");
+  if (n_obj == 0) return MH_OK;
+  if (int rc_enter = mh::enter(ctx)) return rc_enter;
+  // one device block: records | poses | models | offsets | matches
+  const size_t n = (size_t)n_obj;
+  const size_t w_rec = n * (sizeof(mh_verify_record) / 4);
+  const size_t words = w_rec + 7 * n + n + ((size_t)n_models + 1) + 5 * (size_t)std::max(M, 1);
+  int rc = ensure_scratch(ctx, words * 4);
+  if (rc) return rc;
+  if ((rc = ensure_pinned(ctx, w_rec * 4))) return rc;
+  hipStream_t s = ctx->stream;
+  mh_verify_record* const d_rec = reinterpret_cast<mh_verify_record*>(ctx->scratch.p);
+  float* const d_pose = reinterpret_cast<float*>(ctx->scratch.p) + w_rec;
+  int32_t* const d_model = reinterpret_cast<int32_t*>(d_pose + 7 * n);
+  int32_t* const d_off = d_model + n;
+  mh_corr* const d_corr = reinterpret_cast<mh_corr*>(d_off + n_models + 1);
+  MH_HIP(ctx, hipMemcpyAsync(d_pose, obj_pose, n * 28, hipMemcpyHostToDevice, s));
+  MH_HIP(ctx, hipMemcpyAsync(d_model, obj_model, n * 4, hipMemcpyHostToDevice, s));
+  MH_HIP(ctx, hipMemcpyAsync(d_off, model_off, ((size_t)n_models + 1) * 4, hipMemcpyHostToDevice, s));
+  if (M > 0) MH_HIP(ctx, hipMemcpyAsync(d_corr, corr_host, (size_t)M * sizeof(mh_corr), hipMemcpyHostToDevice, s));
+  DepthVerifyListArgs a;
+  a.core.xyz = ctx->db_xyz;
+  a.core.model_begin = st->model_begin_dev;
+  a.core.img = ctx->depth_img.img;
+  a.core.fill = ctx->depth_img.fill;
+  a.core.w = ctx->depth_img.w;
+  a.core.h = ctx->depth_img.h;
+  a.core.cam = make_devcam(*cam);
+  a.core.dcam = make_devcam(*depth_cam);
+  a.core.feature_distance = prm->feature_distance;
+  a.core.max_multiplier = prm->max_multiplier;
+  a.core.max_distance = prm->max_distance;
+  a.core.depth_fraction = prm->depth_fraction;
+  a.corr = d_corr;
+  a.model_off = d_off;
+  a.obj_model = d_model;
+  a.obj_pose = d_pose;
+  a.n_obj = n_obj;
+  a.rec = d_rec;
+  launch_depth_verify(a, ctx->depth_verify_debug_form, s);
+  MH_HIP(ctx, hipGetLastError());
+  MH_HIP(ctx, hipMemcpyAsync(ctx->pinned.p, d_rec, w_rec * 4, hipMemcpyDeviceToHost, s));
+  MH_HIP(ctx, hipStreamSynchronize(s));
+  std::memcpy(records, ctx->pinned.p, w_rec * 4);
+  return MH_OK;
+}
+
+// which device form mh_depth_verify runs (a debug entry)
+int mh_depth_verify_debug_form(mh_ctx* ctx, int form) {
+  if (!ctx) return MH_ERR_ARG;
+  if (form != 0 && form != 1) {
+    ctx->err = "mh_depth_verify_debug_form: 0 (a workgroup per object) or 1 (a wavefront per object)";
+    return MH_ERR_ARG;
+  }
+  ctx->depth_verify_debug_form = form;
   return MH_OK;
 }
 

@@ -326,6 +326,18 @@ struct mh_ctx {
     mh_cam cam = {};              // the depth map's K and pose
     int debug_form = 0;           // mh_filter_depth_debug_form: 0 the workgroup form, 1 filter_depth_score_wave
   } fdepth;
+  int depth_verify_debug_form = 0;  // mh_depth_verify_debug_form: 0 a workgroup per object, 1 a wavefront per object (depth_verify.hip)
+  // DEPTH_VERIFY behind the frames (mh_frame_set_depth_verify): one launch of depth_verify_frame_kernel behind FILTER2
+  struct VerifyState {
+    bool on = false;
+    mh_depth_verify_params prm = {};
+    mh_cam cam = {};                  // the depth map's K and pose
+    // device [MH_MAX_BATCH] slots of {int32 n_before; int32 pad[3]; mh_verify_record[max_objects]}, and the slots' tickets
+    mh::DevBuf<unsigned char> block;
+    mh::DevBuf<unsigned int> tickets;
+    size_t slot_bytes = 0;
+    bool slot_on[MH_MAX_BATCH] = {};  // per result slot: the frame enqueued last into it ran with the verification
+  } verify;
   int hull_debug_form = 0;          // mh_hull_debug_form: 0 the octagon prefilter, 1 sort and chain every point (hull.hip)
   // object hulls behind the frames (mh_frame_set_hulls): one launch of hull_frame_kernel behind FILTER2 (or POSE)
   struct HullState {
@@ -387,6 +399,9 @@ int filter_depth_frame_ok(mh_ctx* ctx, const char* who, const mh_frame_params* p
 // ... and, asked by the same entry points at the same place, while hulls are on (mh_frame_set_hulls; off: MH_OK): no shards'
 // blocks, the wanted camera among the frame's, a store with whole models in ascending order
 int hulls_frame_ok(mh_ctx* ctx, const char* who, int n_cameras, bool sharded);
+// ... and while DEPTH_VERIFY is on (mh_frame_set_depth_verify; off, or a frame without FILTER2: MH_OK): a depth map, one
+// camera, no shards, a store of whole models
+int depth_verify_frame_ok(mh_ctx* ctx, const char* who, const mh_frame_params* prm, int n_cameras, bool sharded);
 int ensure_frame_buffers(mh_ctx* ctx, int Q);
 int ensure_scratch(mh_ctx* ctx, size_t bytes);
 int ensure_pinned(mh_ctx* ctx, size_t bytes);

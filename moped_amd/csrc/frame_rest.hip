@@ -3,6 +3,7 @@
 #include <type_traits>
 
 #include "frame.h"
+#include "depth_verify.h"
 #include "hull.h"
 
 namespace mh {
@@ -206,8 +207,29 @@ int hulls_frame_ok(mh_ctx* ctx, const char* who, int n_cameras, bool sharded) {
   return MH_OK;
 }
 
+int depth_verify_frame_ok(mh_ctx* ctx, const char* who, const mh_frame_params* prm, int n_cameras, bool sharded) {
+  if (!ctx->verify.on || !prm || !prm->run_stage2) return MH_OK;
+  const DbStore* st = ctx->store.get();
+  const char* why = nullptr;
+  if (sharded)
+    why = "frames of a sharded database cannot take it (model indices are shard-local): mh_frame_set_depth_verify(ctx, NULL, "
+          "NULL) on the shards, mh_depth_verify on the gathered objects";
+  else if (n_cameras > 1 || (ctx->q_img && ctx->n_images > 1))
+    why = "one camera per frame";
+  else if (!ctx->depth_img.img)
+    why = "no depth map: mh_frame_set_depth_image[_batch | _host] first";
+  else if (!st || !st->grouped || st->n_blocks > 1)
+    why = "the store's rows are not whole models in ascending order (mh_depth_verify has the same condition)";
+  if (why) {
+    ctx->err = std::string(who) + ": DEPTH_VERIFY (mh_frame_set_depth_verify): " + why;
+    return MH_ERR_ARG;
+  }
+  return MH_OK;
+}
+
 int filter_depth_frame_ok(mh_ctx* ctx, const char* who, const mh_frame_params* prm, int n_cameras, bool sharded) {
   if (int rc = hulls_frame_ok(ctx, who, n_cameras, sharded)) return rc;   // (every frame entry point asks here before it enqueues)
+  if (int rc = depth_verify_frame_ok(ctx, who, prm, n_cameras, sharded)) return rc;
   const mh_ctx::FilterDepthState& fd = ctx->fdepth;
   if (!(fd.on[0] || fd.on[1]) || !prm || !prm->run_stage2) return MH_OK;
   const char* why = nullptr;
@@ -408,6 +430,23 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
     if (int rc = hulls_frame_ok(ctx, "frame", multi ? ctx->n_images : 1, c.gathered != nullptr)) return rc;
     if (int rc = ensure_hull_block(ctx)) return rc;
   }
+  // moped3d's DEPTH_VERIFY behind FILTER2 (mh_frame_set_depth_verify): whole frames only
+  const bool verify = ctx->verify.on && prm->run_stage2 && !stepped;
+  if (verify) {
+    if (int rc = depth_verify_frame_ok(ctx, "frame", prm, multi ? ctx->n_images : 1, c.gathered != nullptr)) return rc;
+    mh_ctx::VerifyState& vs = ctx->verify;
+    const size_t slot_bytes = 16 + (size_t)fs->max_objects * sizeof(mh_verify_record);
+    if (slot_bytes != vs.slot_bytes || !vs.tickets) {
+      MH_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (records of earlier frames may still be read out of the old layout)
+      MH_HIP(ctx, vs.block.ensure(slot_bytes * MH_MAX_BATCH, ctx->stream));
+      if (!vs.tickets) {
+        MH_HIP(ctx, vs.tickets.ensure(MH_MAX_BATCH, ctx->stream));
+        MH_HIP(ctx, hipMemsetAsync(vs.tickets, 0, MH_MAX_BATCH * sizeof(unsigned int), ctx->stream));
+      }
+      vs.slot_bytes = slot_bytes;
+      for (bool& v : vs.slot_on) v = false;
+    }
+  }
   // moped3d's weighted mean shift (mh_frame_set_cluster_wms): whole single-camera frames of this context over a depth map
   if (ctx->wms_on) {
     const char* why = !dimg.img ? "no depth map (mh_frame_set_depth_image)" : multi ? "frames with several images" :
@@ -578,7 +617,8 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
   ctx->frame_route[2] = fused;
   ctx->frame_route[3] = fdepth ? (ctx->fdepth.on[0] ? 1 : 0) | (ctx->fdepth.on[1] ? 2 : 0) : 0;
   // (one frame alone in result slot 0: FILTER2's tail also writes the host's block, mh_frame_fetch reads it without a copy)
-  fs->host_armed = batch_n == 1 && c.slot == 0 && prm->run_stage2 && fs->host_block && !stepped;
+  // (not with DEPTH_VERIFY behind it: the erase rewrites the result slot, and the fetch copies from there)
+  fs->host_armed = batch_n == 1 && c.slot == 0 && prm->run_stage2 && fs->host_block && !stepped && !verify;
   if (fs->host_armed) ++fs->host_seq_expect;
   const FilterTail ft1{fs->tickets + 2, snap + 3, nullptr, grid, nullptr, nullptr, nullptr},
       ft2{fs->tickets + 4, nullptr, result, grid, fs->host_armed ? fs->host_block : nullptr, fs->host_armed ? snap : nullptr,
@@ -649,6 +689,40 @@ int frame_rest(mh_ctx* ctx, const FrameCall& c) {
                        fs->max_objects, fs->counts);
   }
   stamp(ctx, 8);
+  // DEPTH_VERIFY of the objects the result slots now hold, in front of the hulls: one launch for all frames of the call,
+  // the counts read on the device; the frames' last workgroups erase
+  if (!stepped || runs(2))
+    for (int f = 0; f < (batch_n > 1 ? batch_n : 1) && c.slot + f < MH_MAX_BATCH; ++f) ctx->verify.slot_on[c.slot + f] = false;
+  if (verify) {
+    mh_ctx::VerifyState& vs = ctx->verify;
+    DepthVerifyFrameArgs va;
+    va.core.xyz = ctx->db_xyz;
+    va.core.model_begin = ctx->store->model_begin_dev;
+    va.core.img = dimg.img;
+    va.core.fill = dimg.fill;
+    va.core.w = dimg.w;
+    va.core.h = dimg.h;
+    va.core.cam = dc;
+    va.core.dcam = make_devcam(vs.cam);
+    va.core.feature_distance = vs.prm.feature_distance;
+    va.core.max_multiplier = vs.prm.max_multiplier;
+    va.core.max_distance = vs.prm.max_distance;
+    va.core.depth_fraction = vs.prm.depth_fraction;
+    va.maps_on = maps != nullptr;
+    if (maps) va.maps = *maps;
+    va.corr = fs->m_corr;
+    va.model_off = fs->model_off;
+    va.arena_bytes = fs->arena_bytes;
+    va.result = fs->result;
+    va.result_bytes = fs->result_bytes;
+    va.max_objects = fs->max_objects;
+    va.first_slot = c.slot;
+    va.block = vs.block;
+    va.slot_bytes = vs.slot_bytes;
+    va.tickets = vs.tickets;
+    launch_frame_depth_verify(va, batch_n > 1 ? batch_n : 1, s);
+    for (int f = 0; f < (batch_n > 1 ? batch_n : 1) && c.slot + f < MH_MAX_BATCH; ++f) vs.slot_on[c.slot + f] = true;
+  }
   // the hulls of the objects the result slots now hold: one launch for all frames of the call, the counts read on the device
   if (!stepped || runs(2))
     for (int f = 0; f < (batch_n > 1 ? batch_n : 1) && c.slot + f < MH_MAX_BATCH; ++f) ctx->hulls.slot_vertices[c.slot + f] = 0;

@@ -48,6 +48,10 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
   // then filled too (the clusters may overlap)
   int ClusterWeighted;
   mh_wms_params wp;
+  // config keys: DEPTH_VERIFY_CPU behind FILTER2 (DepthVerify 1) with that class's FeatureDistance, MaxMultiplier,
+  // MaxDistance, DepthFraction (mh_frame_set_depth_verify): the objects the reference's step would erase are not delivered
+  int DepthVerify;
+  mh_depth_verify_params vp;
   unsigned long frameCounter;
   int32_t lastCounts[4];
 
@@ -69,7 +73,11 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
       : FillScale(FillScale), Bilinear(Bilinear), DescriptorSize(DescriptorSize), DescriptorType(DescriptorType),
         PatchSize(PatchSize), Density1(Density1), Density2(Density2),
         am(MinRatioMin, MinRatioMax, MaxRatioMin, MaxRatioMax, DimensionPeak, DimensionFade), Alpha(Alpha),
-        Kind(MH_DEPTH_BACKPROJECTION), MaxKeypoints(2048), DoubleImSize(1), IncrementalModels(0), LevelFill(0), LinkageRowMaxima(0), ClusterWeighted(0), frameCounter(0) {
+        Kind(MH_DEPTH_BACKPROJECTION), MaxKeypoints(2048), DoubleImSize(1), IncrementalModels(0), LevelFill(0), LinkageRowMaxima(0), ClusterWeighted(0), DepthVerify(0), frameCounter(0) {
+    vp.feature_distance = 64.f;
+    vp.max_multiplier = 3.f;
+    vp.max_distance = 2.f;
+    vp.depth_fraction = 0.1f;
     wp.radius = 0.1f;
     wp.merge = 0.02f;
     wp.min_pts = 7;
@@ -115,6 +123,11 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
     hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "ClusterWeightedMinPts", wp.min_pts);
     hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "ClusterWeightedMaxIterations", wp.max_iter);
     hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "ClusterWeightedHalfWeightDistance", wp.half_weight_distance);
+    hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "DepthVerify", DepthVerify);
+    hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "VerifyFeatureDistance", vp.feature_distance);
+    hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "VerifyMaxMultiplier", vp.max_multiplier);
+    hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "VerifyMaxDistance", vp.max_distance);
+    hipGetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "VerifyDepthFraction", vp.depth_fraction);
   }
   void setConfig(map<string, string>& config) {
     hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "Density", Density1);
@@ -130,6 +143,11 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
     hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "ClusterWeightedMinPts", wp.min_pts);
     hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "ClusterWeightedMaxIterations", wp.max_iter);
     hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "ClusterWeightedHalfWeightDistance", wp.half_weight_distance);
+    hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "DepthVerify", DepthVerify);
+    hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "VerifyFeatureDistance", vp.feature_distance);
+    hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "VerifyMaxMultiplier", vp.max_multiplier);
+    hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "VerifyMaxDistance", vp.max_distance);
+    hipSetConfig(config, _stepName, _alg, "FRAME_RESIDENT_3D_HIP", "VerifyDepthFraction", vp.depth_fraction);
   }
 
   void process(FrameData& frameData) {
@@ -181,6 +199,8 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
     // (set after the linkage class: the one set last is on)
     if (ClusterWeighted && mh_frame_set_cluster_wms(ctx, &wp) != MH_OK) { HipSession::warn("mh_frame_set_cluster_wms"); return; }
     const mh_cam cam = hipCamOf(*gray);
+    const mh_cam depthCam = hipCamOf(*depthmap);
+    if (DepthVerify && mh_frame_set_depth_verify(ctx, &vp, &depthCam) != MH_OK) { HipSession::warn("mh_frame_set_depth_verify"); return; }
     vector<mh_object> out(256);
     int32_t n = 0;
     int32_t* const counts = lastCounts;
@@ -208,6 +228,7 @@ class FRAME_RESIDENT_3D_HIP : public MopedAlg {
         mh_frame_set_depth_rules(ctx, 0, 0);
         mh_frame_set_cluster_linkage(ctx, 0);
         mh_frame_set_cluster_wms(ctx, 0);
+        mh_frame_set_depth_verify(ctx, 0, 0);
         mh_frame_set_depth_image(ctx, 0, 0, 0, 0, 0, 0.5f, 0.1f);
         mh_depth_fill_set_mode(ctx, fillMode);
         mh_linkage_set_mode(ctx, linkageMode);

@@ -10,6 +10,8 @@
 //                        step wiring, or -- with --resident -- as FRAME_RESIDENT_3D_HIP's ClusterWeighted... keys (moped3d's
 //                        other depth-aware clusterer)
 //       --linkage-rowmax CLUSTER in MH_LINKAGE_ROWMAX mode (CLUSTER_LINKAGE_HIP's RowMaxima key, the one-step plugin's LinkageRowMaxima)
+//       --depth-verify FD MM MD DF   DEPTH_VERIFY_HIP( FeatureDistance, MaxMultiplier, MaxDistance, DepthFraction ) behind
+//                        FILTER2 in the step wiring, or -- with --resident -- FRAME_RESIDENT_3D_HIP's DepthVerify / Verify... keys
 //       --loop N         the frame N times; prints FPS (process() time only), the lists of the last frame
 //       --maps-out file  the frame's depth map [h][w][4] and distance map [h][w] (floats) as the steps left them
 //
@@ -43,6 +45,7 @@
 #include "CLUSTER_WEIGHTED_MEAN_SHIFT_HIP.hpp"
 #include "POSE_RANSAC_P3P_DEPTH_HIP.hpp"
 #include "FILTER_PROJECTION_HIP.hpp"
+#include "DEPTH_VERIFY_HIP.hpp"
 #include "FRAME_RESIDENT_3D_HIP.hpp"
 
 using namespace MopedNS;
@@ -117,7 +120,8 @@ static SP_Image make_image(const Scene& s, Image_Type type, const char* name, co
 // moped3d/libmoped/src/config.hpp:38-49 with the HIP classes (UNDISTORTED_IMAGE: the scenes are undistorted)
 // wms (--cluster-wms): Radius, Merge, MinPts, MaxIterations, halfWeightDistance of CLUSTER_WEIGHTED_MEAN_SHIFT_HIP in the
 // CLUSTER slot instead (0 is returned then: the linkage step's own key has nobody to go to)
-static CLUSTER_LINKAGE_HIP* createPipeline(MopedPipeline& pipeline, const Scene& s, bool level_fill, const double* wms) {
+static CLUSTER_LINKAGE_HIP* createPipeline(MopedPipeline& pipeline, const Scene& s, bool level_fill, const double* wms,
+                                           const double* verify) {
   CLUSTER_LINKAGE_HIP* cluster = wms ? 0 : new CLUSTER_LINKAGE_HIP(0.1, 7, 2, 1, 0.0, 1, -1, -1);
   if (s.fill_scale != 0) pipeline.addAlg("DEPTHFILL", new DEPTH_FILL_EXACT_HIP(s.fill_scale, false, level_fill));
   if (s.Q == 0 && s.has_image) pipeline.addAlg("SIFT", new FEAT_SIFT_HIP("-1"));
@@ -131,6 +135,7 @@ static CLUSTER_LINKAGE_HIP* createPipeline(MopedPipeline& pipeline, const Scene&
   pipeline.addAlg("FILTER", new FILTER_PROJECTION_HIP(6, 4096., 2));
   pipeline.addAlg("POSE2", new POSE_RANSAC_P3P_DEPTH_HIP(1024, 4, 6, 8, 5, 0.5));
   pipeline.addAlg("FILTER2", new FILTER_PROJECTION_HIP(8, 8192., 1e-4));
+  if (verify) pipeline.addAlg("DEPTH_VERIFY", new DEPTH_VERIFY_HIP(verify[0], verify[1], verify[2], verify[3]));
   return cluster;
 }
 
@@ -183,6 +188,8 @@ int main(int argc, char** argv) {
   const char* maps_out = 0;
   double wms[5];
   bool cluster_wms = false;
+  double verify[4];
+  bool depth_verify = false;
   int a = 1;
   for (; a < argc && argv[a][0] == '-'; ++a) {
     if (std::string(argv[a]) == "--resident") resident = true;
@@ -194,10 +201,14 @@ int main(int argc, char** argv) {
       cluster_wms = true;
       for (int k = 0; k < 5; ++k) wms[k] = std::atof(argv[++a]);
     }
+    else if (std::string(argv[a]) == "--depth-verify" && a + 4 < argc) {
+      depth_verify = true;
+      for (int k = 0; k < 4; ++k) verify[k] = std::atof(argv[++a]);
+    }
     else { a = argc; break; }   // an option nobody knows, or one without its value
   }
   if (a + 1 != argc || loop < 1) {
-    std::fprintf(stderr, "usage: %s [--resident] [--loop N] [--maps-out file] [--level-fill] [--linkage-rowmax] [--cluster-wms R M MinPts MaxIter HWD] scene.bin\n", argv[0]);
+    std::fprintf(stderr, "usage: %s [--resident] [--loop N] [--maps-out file] [--level-fill] [--linkage-rowmax] [--cluster-wms R M MinPts MaxIter HWD] [--depth-verify FD MM MD DF] scene.bin\n", argv[0]);
     return 2;
   }
   if (cluster_wms && (linkage_rowmax || wms[2] < 0 || wms[3] < 0)) {
@@ -217,7 +228,7 @@ int main(int argc, char** argv) {
   FRAME_RESIDENT_3D_HIP* res = 0;
   CLUSTER_LINKAGE_HIP* cluster = 0;
   if (resident) res = createResidentPipeline(pipeline, s);
-  else cluster = createPipeline(pipeline, s, level_fill, cluster_wms ? wms : 0);
+  else cluster = createPipeline(pipeline, s, level_fill, cluster_wms ? wms : 0, depth_verify ? verify : 0);
   list<MopedAlg*> all = pipeline.getAlgs();
   map<string, string> config;
   for (list<MopedAlg*>::iterator it = all.begin(); it != all.end(); ++it) {
@@ -237,6 +248,11 @@ int main(int argc, char** argv) {
       config["DEPTHFILL:0:FRAME_RESIDENT_3D_HIP/ClusterWeighted"] = "1";
       for (int k = 0; k < 5; ++k)
         config[std::string("DEPTHFILL:0:FRAME_RESIDENT_3D_HIP/ClusterWeighted") + keys[k]] = toString(k == 2 || k == 3 ? (double)(int)wms[k] : wms[k]);
+    }
+    if (depth_verify) {
+      static const char* const vkeys[4] = {"VerifyFeatureDistance", "VerifyMaxMultiplier", "VerifyMaxDistance", "VerifyDepthFraction"};
+      config["DEPTHFILL:0:FRAME_RESIDENT_3D_HIP/DepthVerify"] = "1";
+      for (int k = 0; k < 4; ++k) config[std::string("DEPTHFILL:0:FRAME_RESIDENT_3D_HIP/") + vkeys[k]] = toString(verify[k]);
     }
     res->setConfig(config);
   }

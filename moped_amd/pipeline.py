@@ -653,6 +653,24 @@ class FramePipeline:
                 c.filter_depth_set_points(points_xyz, points_off)
             c.frame_set_filter_depth(f1, f2, K, cam)
 
+    def set_depth_verify(self, params, depth_cam=None):
+        """Frames and batches enqueued from now on run moped3d's DEPTH_VERIFY behind FILTER2 (Context.frame_set_depth_verify
+        on every slot's context): every object is checked against its own frame's depth map and match lists, the objects
+        the reference erases are gone from what fetch() / fetch_batch() / deliver() and the hulls see.  params:
+        (FeatureDistance, MaxMultiplier, MaxDistance, DepthFraction) or None = off; depth_cam: (K, pose) of the depth map,
+        default the pipeline's camera.  Single-camera frames with a depth map on an unsharded database."""
+        if params is not None and self.exchange:
+            raise ValueError("DEPTH_VERIFY needs one GPU's whole database: the keypoints are the store's rows per global model")
+        K, cam = (self.K, self.cam) if depth_cam is None else depth_cam
+        for c in self.ctxs:
+            c.frame_set_depth_verify(params, K, cam)
+
+    def verify_records(self, slot: int = 0, frame: int = 0):
+        """The DEPTH_VERIFY records of what pipeline slot `slot` (its context) ran last, one per object that left FILTER2
+        (capi.VERIFY_DTYPE).  frame: the context's RESULT SLOT index, as fetch_batch's frame_fetch_slot(f) takes it --
+        frame f of a batch, 0 for a frame alone (mh_frame_fetch_verify_slot)."""
+        return self.ctxs[slot].frame_fetch_verify(frame)
+
     def set_cluster_wms(self, params: "capi.mh_wms_params | None"):
         """CLUSTER of the frames enqueued from now on as moped3d's CLUSTER_WEIGHTED_MEAN_SHIFT_CPU over the depth map's
         points (Context.frame_set_cluster_wms on every slot's context; None = off).  Single-camera frames with a depth
